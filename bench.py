@@ -13,8 +13,11 @@ plus the averaging half-steps of time_mix_opt = 'avgfit': 319 for tx0.1v3, not 3
 is the step wall time.  N > 1 shards the SAME global domain by blocks (strong scaling) with halo
 exchange and the solver's block-sum all-reduce on RCCL (torch.distributed backend "nccl").
 
-Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP-event timed in this process) and,
-at N = 1, `cpu_baseline` (the CPU oracle = restated reference algorithm, timed on this box's host).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints it; with --full
+the line also carries `roofline` (every phase kernel HIP-event timed in runs of its own after the timed
+steps) and, at N = 1, `kpp_deep_state` (tx0.1v3: a second state, stepped after the timed region) and
+`cpu_baseline` (the CPU oracle = restated reference algorithm, timed on the host's cores).
+--dump-outputs DIR (N = 1) writes the state the last timed step left as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -436,6 +439,126 @@ def kpp_deep_state(pkg, model, cfg, torch, nlev=12, warm=6, steps=8):
             "hblt_m_p50": round(float(np.median(H)) / 100, 1), "hblt_m_p90": round(float(np.percentile(H, 90)) / 100, 1)}
 
 
+DUMP_BYTES = 56 << 20     # --dump-outputs: all arrays together, under the 64 MB a dump may hold
+
+
+def dump_names(cfg):
+    return [("TEMP", "SALT")[n] if n < 2 else "TRACER_%d" % n for n in range(cfg.nt)] + ["UVEL", "VVEL", "PSURF", "UBTROP", "VBTROP"]
+
+
+def dump_cells(model, cfg, per_array, seed=0):
+    """The cells --dump-outputs writes, as flat offsets into this rank's local field arrays: "t3" / "u3" the 3-D ocean cells of the
+    T / U grid (k < KMT / KMU), "t2" / "u2" the ocean columns.  Global (j, i, k) order; where a grid has more than per_array of them,
+    a sample of per_array drawn with a fixed seed -- the same cells in every run with the same arguments, whatever the blocks."""
+    km, n2, nx = model.km, model.nyb * model.nxb, model.nxb
+    where = np.full((cfg.ny_global, cfg.nx_global), -1, dtype=np.int64)   # global (j, i) -> offset in a local 2-D array; -1: not held here
+    for bid in model.local_block_ids():
+        B = model.get_block(bid)
+        jj, ii = np.arange(B["jb"] - 1, B["je"]), np.arange(B["ib"] - 1, B["ie"])
+        where[np.ix_(B["j_glob"][jj] - 1, B["i_glob"][ii] - 1)] = (B["local_id"] - 1) * n2 + jj[:, None] * nx + ii[None, :]
+    where = where.ravel()
+    held = where >= 0
+    rng = np.random.default_rng(seed)
+
+    def cells(levels, nz):              # levels (nblocks, ny_block, nx_block): ocean cells per column; nz: levels of the array
+        depth = np.zeros(where.size, dtype=np.int64)
+        depth[held] = levels.ravel()[where[held]]
+        end = np.cumsum(depth)
+        total = int(end[-1])
+        r = np.arange(total) if total <= per_array else np.sort(rng.choice(total, per_array, replace=False))
+        col = np.searchsorted(end, r, side="right")
+        k = r - (end[col] - depth[col])
+        return where[col] // n2 * (nz * n2) + k * n2 + where[col] % n2
+
+    kmt, kmu = model.geti("KMT"), model.geti("KMU")
+    return {"t3": cells(kmt, km), "u3": cells(kmu, km), "t2": cells(kmt > 0, 1), "u2": cells(kmu > 0, 1)}
+
+
+def dump_outputs(model, cfg, out_dir):
+    """--dump-outputs: the prognostic state the last timed step left -- logical time level 'cur', what the next step starts from --
+    as out_dir/<name>.npy (float64) over the cells of dump_cells.  Read with pop_get_field, which changes nothing that --full measures."""
+    names = dump_names(cfg)
+    sel = dump_cells(model, cfg, DUMP_BYTES // 8 // len(names))
+    n3 = model.nblocks * model.km * model.nyb * model.nxb
+    buf = np.empty(n3)
+    fields = [("TRACER", n, "t3", n3) for n in range(cfg.nt)] + [("UVEL", 0, "u3", n3), ("VVEL", 0, "u3", n3), ("PSURF", 0, "t2", n3 // model.km),
+                                                                  ("UBTROP", 0, "u2", n3 // model.km), ("VBTROP", 0, "u2", n3 // model.km)]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (field, n, grid, count) in zip(names, fields):
+        model._chk(model.L.pop_get_field(model.h, field.encode(), 1, n, buf.ctypes.data_as(C.POINTER(C.c_double)), count))
+        np.save(os.path.join(out_dir, name + ".npy"), buf[:count][sel[grid]])
+
+
+def roofline(pkg, model, cfg, workload, world, elapsed, steps, land_frac):
+    """--full: every 3-D phase kernel timed with HIP events on its launch stream (pop_time_phase: the kernel launches only, in runs of
+    their own after the timed steps) against SURVEY.md 8(d)'s algorithmic bytes, and the barotropic solver of the timed steps"""
+    solver_ms = model.scalar("solver_ms_total")
+    solver_iters = model.scalar("solver_iterations_total")
+    solver_calls = model.scalar("solver_calls_total")
+    ms_step = 1e3 * elapsed / steps
+    vm = cfg.vmix_choice - 1
+    ncell_phys = cfg.nx_global * cfg.ny_global * cfg.km // world
+    ncell_phys = int(round(ncell_phys * (1.0 - land_frac)))
+    phases = {}
+    extra_words = {}
+    for ph, words in PHASE_WORDS.items():
+        if ph == "impvmixt" and not cfg.lpressure_avg:
+            continue
+        try:
+            ms = model.time_phase(ph, reps=10)
+        except pkg.PopError:
+            continue
+        nw = words[vm]        # SURVEY.md 8(d) words of the phase -- the only count `frac` uses
+        gb = nw * 8.0 * ncell_phys / 1e9
+        phases[ph] = {"ms": round(ms, 4), "alg_GB": round(gb, 4), "GBps": round(gb / (ms * 1e-3), 1), "alg_words": nw}
+        # del4 on large grids: the tracer / momentum launch also READS the two first-Laplacian fields and WRITES the next step's
+        # (the output of k_del4_d2t / k_del4_d2u, which are then not launched).  SURVEY 8(d) has no del4 row, so these words are
+        # reported beside the phase, never inside `frac`.
+        if ph == "tracer_rhs" and cfg.hmix_tracer == 4:
+            extra_words[ph] = 2 + (2 if model.dim("d2t_last_formed") else 0)
+        if ph == "momentum_rhs" and cfg.hmix_momentum == 4:
+            extra_words[ph] = 2 + (2 if model.dim("d2u_last_formed") else 0)
+        if ph in extra_words:
+            phases[ph]["del4_extra_words_moved"] = extra_words[ph]
+    # dominant single baroclinic stencil kernel (north_star: "fraction of HBM roofline for the baroclinic stencil")
+    dom = max((k for k in phases if k in ("tracer_rhs", "momentum_rhs")), key=lambda k: phases[k]["ms"])
+    kern = KERNEL_OF_PHASE[dom]
+    roof = {"bound": "hbm", "kernel": kern, "achieved": phases[dom]["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(phases[dom]["GBps"] / HBM_PEAK_GBS, 4),
+            "frac_definition": "SURVEY.md 8(d) words of the phase (E = 10, B = 12) x 8 B x computed cells / HIP-event launch time / 8 TB/s",
+            "traffic": pmc_traffic(workload, kern) if world == 1 else None,
+            "traffic_source": "rocprofv3 --pmc FETCH_SIZE(x2)/WRITE_SIZE passes of `bench.py --profile-run headline` (separate runs, profiles/collect_r04.sh): committed profiles/r04_pmc_traffic.json (r03 if absent), not measured in this process",
+            "alg_bytes_per_launch": phases[dom]["alg_GB"] * 1e9, "avg_launch_ms": phases[dom]["ms"], "phases": phases}
+    if dom in extra_words:
+        w = phases[dom]["alg_words"] + extra_words[dom]
+        roof["frac_all_words_moved"] = round(w * 8.0 * ncell_phys / 1e9 / (phases[dom]["ms"] * 1e-3) / HBM_PEAK_GBS, 4)
+        roof["all_words_moved"] = w
+    # both baroclinic stencil kernels together (tracer + momentum right-hand sides): 8(d) bytes / summed time
+    pair_gb = phases["tracer_rhs"]["alg_GB"] + phases["momentum_rhs"]["alg_GB"]
+    pair_ms = phases["tracer_rhs"]["ms"] + phases["momentum_rhs"]["ms"]
+    roof["baroclinic_stencils"] = {"kernels": [KERNEL_OF_PHASE["tracer_rhs"], KERNEL_OF_PHASE["momentum_rhs"]],
+                                   "achieved": round(pair_gb / (pair_ms * 1e-3), 1), "frac": round(pair_gb / (pair_ms * 1e-3) / HBM_PEAK_GBS, 4)}
+    step_words = sum(v[vm] for k, v in PHASE_WORDS.items() if k in phases)
+    roof["step_alg_GBps"] = round(step_words * 8.0 * ncell_phys * world / 1e9 / (elapsed / steps), 1)
+    # the barotropic solver (SURVEY 8d: "iterations x per-iteration time separately"; 14 words = 112 B per 2-D point per iteration)
+    if solver_calls > 0 and solver_iters > 0:
+        pts = int(round(cfg.nx_global * cfg.ny_global // world * (1.0 - land_frac)))
+        us_it = 1e3 * solver_ms / solver_iters
+        sol = {"solver": ["pcg", "ChronGear", "PCSI"][cfg.solver_choice - 1], "iterations_per_step": round(solver_iters / solver_calls, 2),
+               "ms_per_step": round(solver_ms / solver_calls, 4), "us_per_iteration": round(us_it, 2),
+               "timing": "HIP events around POP_SolversRun on the launch stream inside the timed steps (start-up, checks and the final halo included)",
+               "alg_bytes_per_iteration": 112 * pts, "active_points": pts,
+               "achieved": round(112 * pts / 1e9 / (us_it * 1e-6), 1), "unit": "GB/s",
+               "frac": round(112 * pts / 1e9 / (us_it * 1e-6) / HBM_PEAK_GBS, 4), "share_of_step": round(solver_ms / solver_calls / ms_step, 4)}
+        try:
+            sol["k_block_sums_us_isolated"] = round(1e3 * model.time_phase("block_sums", reps=50), 2)
+            sol["k_block_sums_launches_per_iteration"] = 2 if cfg.solver_choice == 1 else (1 if cfg.solver_choice == 2 else 0)
+        except pkg.PopError:
+            pass
+        roof["solver"] = sol
+    return roof
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -463,7 +586,15 @@ def main():
     ap.add_argument("--grid-input", action="store_true", help="NOT the headline: horizontal grid and bathymetry supplied by the caller (pop_create_with_grid; the synthetic "
                                                               "lat-lon arrays of tests/popcfg.synthetic_grid) instead of the internal grid; config.grid_input says so")
     ap.add_argument("--tripole", action="store_true", help="NOT the headline: tripole northern boundary (ns_boundary_type 'tripole') on the --grid-input arrays")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need, after the timed steps: the roofline (per-phase "
+                                                        "kernel times), the deep KPP boundary-layer state and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the state the last timed step left as DIR/<name>.npy (float64, ocean "
+                                                                     "cells; a fixed seeded sample of them on large grids); one GPU only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus != 1 or args.profile_run):
+        ap.error("--dump-outputs needs --gpus 1 and no --profile-run")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # no launcher around us: become one (child process; nothing here has touched the GPU yet, torch is not even imported)
@@ -607,6 +738,8 @@ def main():
         elapsed = float(t.item())
         rank_ms = [None] * world
         dist.all_gather_object(rank_ms, 1e3 * busy / args.steps)
+    if args.dump_outputs:
+        dump_outputs(model, cfg, args.dump_outputs)
     # per-rank evidence for the record: ocean columns owned, what the transport reports about itself
     kmt_phys = model.geti("KMT")[:, 2:-2, 2:-2]
     ocean_cols = [int((kmt_phys > 0).sum())]
@@ -624,86 +757,24 @@ def main():
         dist.all_gather_object(ocean_cols, int((kmt_phys > 0).sum()))
         dist.all_gather_object(cinfo, model.comm_info())
         dist.all_gather_object(paths, mine)
-    solver_ms = model.scalar("solver_ms_total")
-    solver_iters = model.scalar("solver_iterations_total")
-    solver_calls = model.scalar("solver_calls_total")
     ms_step = 1e3 * elapsed / args.steps
     # step calls per model day: with time_mix_opt = 'avgfit' a day is `full` leapfrog steps plus `half` averaging
     # half-steps (time_management.F90:820-860; tx0.1v3: 300 + 19 = 319 calls), every one a full pass of the hot path
     calls_per_day = model.dim("nsteps_per_interval")
     sypd = 86400.0 / ((elapsed / args.steps) * calls_per_day * 365.0)
 
-    # ---- roofline: every 3-D phase kernel timed with HIP events on its launch stream (pop_time_phase: the kernel launches only)
     vm = cfg.vmix_choice - 1
     ncell_local = model.nxb * model.nyb * model.km * model.nblocks
-    ncell_phys = cfg.nx_global * cfg.ny_global * cfg.km // world
     # land elimination: once it is active (after the first steps) workgroups whose 64-column row segment holds no ocean cell
     # do not run, so the algorithmic bytes are counted over the segments that do -- the units the launches process
     land_frac = model.scalar("land_tile_fraction") if model.dim("land_skip_active") else 0.0
-    ncell_phys = int(round(ncell_phys * (1.0 - land_frac)))
     # headline state: where the KPP boundary layer sits (decides how much the on-demand KPP forms save)
     hblt_levels = None
     if vm == 2:
         kbl = model.geti("KBL")[model.geti("KMT") > 0]
         if kbl.size:
             hblt_levels = [int(np.percentile(kbl, q)) for q in (50, 90, 100)]
-    phases = {}
-    extra_words = {}
-    for ph, words in PHASE_WORDS.items():
-        if ph == "impvmixt" and not cfg.lpressure_avg:
-            continue
-        try:
-            ms = model.time_phase(ph, reps=10)
-        except pkg.PopError:
-            continue
-        nw = words[vm]        # SURVEY.md 8(d) words of the phase -- the only count `frac` uses
-        gb = nw * 8.0 * ncell_phys / 1e9
-        phases[ph] = {"ms": round(ms, 4), "alg_GB": round(gb, 4), "GBps": round(gb / (ms * 1e-3), 1), "alg_words": nw}
-        # del4 on large grids: the tracer / momentum launch also READS the two first-Laplacian fields and WRITES the next step's
-        # (the output of k_del4_d2t / k_del4_d2u, which are then not launched).  SURVEY 8(d) has no del4 row, so these words are
-        # reported beside the phase, never inside `frac`.
-        if ph == "tracer_rhs" and cfg.hmix_tracer == 4:
-            extra_words[ph] = 2 + (2 if model.dim("d2t_last_formed") else 0)
-        if ph == "momentum_rhs" and cfg.hmix_momentum == 4:
-            extra_words[ph] = 2 + (2 if model.dim("d2u_last_formed") else 0)
-        if ph in extra_words:
-            phases[ph]["del4_extra_words_moved"] = extra_words[ph]
-    # dominant single baroclinic stencil kernel (north_star: "fraction of HBM roofline for the baroclinic stencil")
-    dom = max((k for k in phases if k in ("tracer_rhs", "momentum_rhs")), key=lambda k: phases[k]["ms"])
-    kern = KERNEL_OF_PHASE[dom]
-    roof = {"bound": "hbm", "kernel": kern, "achieved": phases[dom]["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(phases[dom]["GBps"] / HBM_PEAK_GBS, 4),
-            "frac_definition": "SURVEY.md 8(d) words of the phase (E = 10, B = 12) x 8 B x computed cells / HIP-event launch time / 8 TB/s",
-            "traffic": pmc_traffic(args.workload, kern) if world == 1 else None,
-            "traffic_source": "rocprofv3 --pmc FETCH_SIZE(x2)/WRITE_SIZE passes of `bench.py --profile-run headline` (separate runs, profiles/collect_r04.sh): committed profiles/r04_pmc_traffic.json (r03 if absent), not measured in this process",
-            "alg_bytes_per_launch": phases[dom]["alg_GB"] * 1e9, "avg_launch_ms": phases[dom]["ms"], "phases": phases}
-    if dom in extra_words:
-        w = phases[dom]["alg_words"] + extra_words[dom]
-        roof["frac_all_words_moved"] = round(w * 8.0 * ncell_phys / 1e9 / (phases[dom]["ms"] * 1e-3) / HBM_PEAK_GBS, 4)
-        roof["all_words_moved"] = w
-    # both baroclinic stencil kernels together (tracer + momentum right-hand sides): 8(d) bytes / summed time
-    pair_gb = phases["tracer_rhs"]["alg_GB"] + phases["momentum_rhs"]["alg_GB"]
-    pair_ms = phases["tracer_rhs"]["ms"] + phases["momentum_rhs"]["ms"]
-    roof["baroclinic_stencils"] = {"kernels": [KERNEL_OF_PHASE["tracer_rhs"], KERNEL_OF_PHASE["momentum_rhs"]],
-                                   "achieved": round(pair_gb / (pair_ms * 1e-3), 1), "frac": round(pair_gb / (pair_ms * 1e-3) / HBM_PEAK_GBS, 4)}
-    step_words = sum(v[vm] for k, v in PHASE_WORDS.items() if k in phases)
-    roof["step_alg_GBps"] = round(step_words * 8.0 * ncell_phys * world / 1e9 / (elapsed / args.steps), 1)
-    # the barotropic solver ("iterations x per-iteration time separately"; 14 words = 112 B per 2-D point per iteration)
-    if solver_calls > 0 and solver_iters > 0:
-        pts = int(round(cfg.nx_global * cfg.ny_global // world * (1.0 - land_frac)))
-        us_it = 1e3 * solver_ms / solver_iters
-        sol = {"solver": ["pcg", "ChronGear", "PCSI"][cfg.solver_choice - 1], "iterations_per_step": round(solver_iters / solver_calls, 2),
-               "ms_per_step": round(solver_ms / solver_calls, 4), "us_per_iteration": round(us_it, 2),
-               "timing": "HIP events around POP_SolversRun on the launch stream inside the timed steps (start-up, checks and the final halo included)",
-               "alg_bytes_per_iteration": 112 * pts, "active_points": pts,
-               "achieved": round(112 * pts / 1e9 / (us_it * 1e-6), 1), "unit": "GB/s",
-               "frac": round(112 * pts / 1e9 / (us_it * 1e-6) / HBM_PEAK_GBS, 4), "share_of_step": round(solver_ms / solver_calls / ms_step, 4)}
-        try:
-            sol["k_block_sums_us_isolated"] = round(1e3 * model.time_phase("block_sums", reps=50), 2)
-            sol["k_block_sums_launches_per_iteration"] = 2 if cfg.solver_choice == 1 else (1 if cfg.solver_choice == 2 else 0)
-        except pkg.PopError:
-            pass
-        roof["solver"] = sol
+    roof = roofline(pkg, model, cfg, args.workload, world, elapsed, args.steps, land_frac) if args.full else None
 
     tun = {k: v for k, v in model.tuning().items() if v is not None and k != "struct_bytes"}
     out = {
@@ -722,8 +793,9 @@ def main():
                    "kpp_surface_buoyancy": ("on-demand down to the boundary-layer depth" if vm == 2 and tun.get("kpp_lazy", 1) != 0
                                             and not cfg.lcheckekmo and cfg.kpp_ml_diagnostics != 1 else "every level"),
                    "tuning_overrides": tun},
-        "roofline": roof,
     }
+    if roof is not None:
+        out["roofline"] = roof
     out["config"]["code_paths"] = {k: v for k, v in mine.items() if k != "blocks"}
     if hblt_levels is not None:
         out["config"]["hblt_level_p50"], out["config"]["hblt_level_p90"], out["config"]["hblt_level_max"] = hblt_levels
@@ -741,12 +813,12 @@ def main():
                             "supervised": worker,
                             "rank_ms_max_over_min": round(max(rank_ms) / max(min(rank_ms), 1e-9), 3),
                             "devices_visible": torch.cuda.device_count()}
-    if world == 1 and rank == 0 and vm == 2 and not args.no_deep_state and args.workload == "tx0.1v3":
+    if args.full and world == 1 and rank == 0 and vm == 2 and not args.no_deep_state and args.workload == "tx0.1v3":
         try:
             out["kpp_deep_state"] = kpp_deep_state(pkg, model, cfg, torch)
         except Exception as e:  # noqa: BLE001  (a second measurement must never lose the headline line)
             out["kpp_deep_state"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         try:
             dt, n, scfg, scale, cores = cpu_baseline(cfg)
             build = "-O3 -march=x86-64-v3"

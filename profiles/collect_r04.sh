@@ -11,9 +11,9 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 P=$R/gpurun_out/prof_r04
 mkdir -p $P
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --steps 20 --warmup 5 > $P/tx0.1v3_bench.json 2> $P/tx0.1v3_bench.err
+python3 $R/bench.py --full --steps 20 --warmup 5 > $P/tx0.1v3_bench.json 2> $P/tx0.1v3_bench.err
 echo "tx bench done"
-python3 $R/bench.py --workload gx1v7 --steps 50 --warmup 10 > $P/gx1v7_bench.json 2> $P/gx1v7_bench.err
+python3 $R/bench.py --full --workload gx1v7 --steps 50 --warmup 10 > $P/gx1v7_bench.json 2> $P/gx1v7_bench.err
 echo "gx bench done"
 # Profiled runs (VERDICT r3 weak #9 / ADVICE: the r3 collection traced bench.py itself, so every per-kernel average mixed the headline steps with the
 # deep-boundary-layer steps and the 10 repetitions per phase of pop_time_phase): `--profile-run headline` launches nothing but warm-up + step calls of
@@ -37,6 +37,6 @@ echo "SQ done"
 unset POP_LAND_FULL_STEPS
 for n in 2 4; do
   POP_BENCH_BACKEND=gloo POP_RCCL_LIB=$R/tests/rccl_stub/librccl_stub.so POP_RCCL_STUB_BOX_MB=32 POP_RCCL_STUB_SLOT_MB=16 timeout -k 10 300 \
-    python3 -m torch.distributed.run --standalone --local-addr 127.0.0.1 --nnodes=1 --nproc-per-node $n $R/bench.py --gpus $n --steps 5 --warmup 2 --workload gx1v7 > $P/gx1v7_stub_n$n.json 2> $P/gx1v7_stub_n$n.err
+    python3 -m torch.distributed.run --standalone --local-addr 127.0.0.1 --nnodes=1 --nproc-per-node $n $R/bench.py --full --gpus $n --steps 5 --warmup 2 --workload gx1v7 > $P/gx1v7_stub_n$n.json 2> $P/gx1v7_stub_n$n.err
   echo "stub n=$n rc=$?"
 done

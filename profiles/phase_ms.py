@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print ms_per_step and selected per-phase timings from a bench.py log (last JSON line)."""
+"""Print ms_per_step and selected per-phase timings from a `bench.py --full` log (last JSON line)."""
 import json
 import sys
 

@@ -215,8 +215,8 @@ def test_bench_starts_its_own_ranks(nranks):
     env = dict(os.environ, POP_BENCH_BACKEND="gloo", POP_RCCL_LIB=STUB)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nranks), "--steps", "2", "--warmup", "1", "--workload", "gx1v7"],
-                         capture_output=True, text=True, timeout=900, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nranks), "--steps", "2", "--warmup", "1", "--workload", "gx1v7",
+                          "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
