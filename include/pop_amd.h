@@ -30,15 +30,18 @@ extern "C" {
 /* Run-time configuration: the namelist subset this path reads
  * (domain_nml, grid_nml, time_manager_nml, hmix_*_nml, vertical_mix_nml,
  *  vmix_*_nml, advect_nml, pressure_grad_nml, baroclinic_nml, &solvers). */
-#define POP_CONFIG_VERSION 5   /* layout of pop_config below; pop_create refuses any other struct_version (4: gm_transition_layer appended; 5: gm_diag_bolus and
-                                 * gm_kappa_bkg_srfbl out of reserved_i, ah_bkg_bottom and kappa_depth_* appended -- added late in round 3 without a new number) */
+#define POP_CONFIG_VERSION 6   /* layout of pop_config below (4: gm_transition_layer appended; 5: gm_diag_bolus and gm_kappa_bkg_srfbl out of reserved_i,
+                                 * ah_bkg_bottom and kappa_depth_* appended -- added late in round 3 without a new number; 6: the hmix_aniso_nml members appended).
+                                 * pop_create accepts 6 and 5; a version-5 struct is read up to kappa_depth_scale only (its size) and cannot select
+                                 * hmix_momentum = 3.  Any other struct_version is refused. */
 typedef struct pop_config {
   int struct_version;         /* = POP_CONFIG_VERSION (round 3: every option has its own named field) */
   int nx_global, ny_global, km, nt;   /* domain_size.F90 */
   int block_size_x, block_size_y;     /* domain_size.F90 */
   int ew_boundary;            /* 0 closed, 1 cyclic   (domain.F90 ew_boundary_type) */
   int ns_boundary;            /* 0 closed, 1 cyclic, 2 tripole (time stepping: with pop_create_with_grid) */
-  int hmix_momentum;          /* 2 del2, 4 del4       (horizontal_mix.F90:427-472) */
+  int hmix_momentum;          /* 2 del2, 4 del4       (horizontal_mix.F90:427-472), 3 anis (hmix_momentum_type_anis, horizontal_mix.F90:68,
+                               * 194-195, 464-472; struct_version 6: the hmix_aniso_nml members at the end) */
   int hmix_tracer;            /* 2 del2, 4 del4, 3 gm: Gent-McWilliams eddy transport + isopycnal (Redi) diffusion with ah as the isopycnal
                                * diffusivity (hmix_gm.F90:1102-2226 in the code-default hmix_gm_nml: constant kappa, kappa_freq 'never',
                                * no transition layer; see gm_slope_control, ah_bolus ... below) */
@@ -104,6 +107,29 @@ typedef struct pop_config {
   int reserved_i[1];                     /* must be 0 */
   double ah_bkg_bottom;                  /* hmix_gm_nml ah_bkg_bottom: horizontal diffusivity in the bottom half of the bottom cell (:1757-1761), 0 = none */
   double kappa_depth_1, kappa_depth_2, kappa_depth_scale;   /* gm_kappa_type = 2; scale 0 = 150000 cm */
+  /* ---- struct_version 6: hmix_aniso_nml (hmix_aniso.F90:167-224), read with hmix_momentum = 3 only.  A 0 stands for the code default
+   *      given last in each comment wherever 0 is not a meaningful value of its own. */
+  int aniso_alignment;        /* hmix_alignment_choice: 0 'grid', 1 'east' (NORM1 = cos ANGLE, NORM2 = -sin ANGLE, :777-780); 2 'flow' is refused:
+                               * :787-794 resets the whole NORM1 / NORM2 block array whenever one point is slower than eps, and land points have
+                               * U = 0, so the result depends on the block's loop order (code default 'flow') */
+  int lvariable_hmix_aniso;   /* 1: F_PARA / F_PERP of compute_ccsm_var_viscosity (:1069-1296, var_viscosity_infile 'ccsm-internal'), tapered to
+                               * AMAX_CFL without lsmag_aniso (:444-464); pop_set_field("F_PARA" | "F_PERP") replaces them as a var_viscosity_infile
+                               * would, the taper applied again (code default .false.) */
+  int lsmag_aniso;            /* 1: Smagorinsky viscosities (:807-856); refused with smag_lat_fact = 0 (:512-531 leaves F_PERP_SMAG unset then)
+                               * (code default .false.) */
+  int vconst_5;               /* points of the western-boundary buffer (:1211), 0 = 3 */
+  double visc_para, visc_perp;/* constant viscosities [cm^2/s] (code default 0) */
+  double c_para, c_perp;      /* Smagorinsky coefficients (code default 0) */
+  double u_para, u_perp;      /* accepted without effect, as in the reference: hdiffu_aniso never reads them (code default 0) */
+  double vconst_1;            /* [cm^2/s], 0 = 1e7 */
+  double vconst_2;            /* 0 = 24.5 */
+  double vconst_3;            /* 0 = 0.2 */
+  double vconst_4;            /* [1/cm], 0 = 1e-8 */
+  double vconst_6;            /* [cm^2/s], 0 = 1e7 */
+  double vconst_7;            /* [degrees], 0 = 45 */
+  double smag_lat;            /* [degrees], 0 = 20 */
+  double smag_lat_fact;       /* no default: 0 with lsmag_aniso is refused (code default 0.98) */
+  double smag_lat_gauss;      /* 0 = 98 */
 } pop_config;
 
 typedef struct pop_ctx pop_ctx;
@@ -184,6 +210,8 @@ typedef struct pop_tuning {
   int pcsi_evp_fused;      /* fused P-CSI with the EVP preconditioner: 1 = the iteration (dx, x, r = b - A x) and the sub-block solves r' = M^-1 r in ONE
                             * launch (k_pcsi_evp_step; bitwise, but measured slower: its loads are issued by the few waves of the sub-block solve);
                             * default 0 = two launches per iteration (k_pcsi_step2, k_evp_apply_wave2) */
+  int aniso_side;          /* hmix_momentum = 3: 0 = the friction k_hdiffu_aniso in line before the momentum right-hand side; default 1 = on the
+                            * side stream beside the vertical-mixing coefficients (it reads only the mix-time U, V and fixed coefficients) */
 } pop_tuning;
 void pop_tuning_init(pop_tuning *t);   /* struct_bytes = sizeof, every field POP_TUNING_UNSET */
 int pop_get_tuning(const pop_ctx *ctx, pop_tuning *resolved);   /* fields still POP_TUNING_UNSET: the size rule applied */

@@ -131,6 +131,36 @@ def make_tuning(**kw):
     return t
 
 
+ANISO_FIELDS = [("aniso_alignment", C.c_int), ("lvariable_hmix_aniso", C.c_int), ("lsmag_aniso", C.c_int), ("vconst_5", C.c_int)] + \
+    [(n, C.c_double) for n in ("visc_para", "visc_perp", "c_para", "c_perp", "u_para", "u_perp", "vconst_1", "vconst_2", "vconst_3",
+                               "vconst_4", "vconst_6", "vconst_7", "smag_lat", "smag_lat_fact", "smag_lat_gauss")]
+ANISO_ALIGNMENT = {"grid": 0, "east": 1, "flow": 2}
+_v6_types = {}
+
+
+def anisotropic_config(cfg, **hmix_aniso_nml):
+    """pop_config layout 6 (include/pop_amd.h): a copy of the caller's layout-5 struct `cfg` (any ctypes mirror, such as
+    tests/popcfg.py PopConfig) with the hmix_aniso_nml members appended and hmix_momentum = 3 ('anis').  Keywords: the
+    members by name; aniso_alignment may also be 'grid' | 'east' | 'flow'; any other pop_config field (hmix_momentum ...)."""
+    base = type(cfg)
+    if hasattr(cfg, "aniso_alignment"):
+        base = base.__mro__[1]
+    v6 = _v6_types.get(base)
+    if v6 is None:
+        v6 = _v6_types[base] = type(base.__name__ + "V6", (base,), {"_fields_": ANISO_FIELDS})
+    out = v6()
+    C.memmove(C.addressof(out), C.addressof(cfg), min(C.sizeof(cfg), C.sizeof(out)))
+    out.struct_version = 6
+    out.hmix_momentum = 3
+    for k, v in hmix_aniso_nml.items():
+        if k == "aniso_alignment" and isinstance(v, str):
+            v = ANISO_ALIGNMENT[v]
+        if not hasattr(out, k):
+            raise AttributeError("pop_config has no field %r" % k)
+        setattr(out, k, v)
+    return out
+
+
 class PopGridInput(C.Structure):
     """include/pop_amd.h pop_grid_input"""
     _fields_ = [(n, C.POINTER(C.c_double)) for n in ("ULAT", "ULON", "HTN", "HTE", "HUS", "HUW", "ANGLE")] + [("KMT", C.POINTER(C.c_int)),

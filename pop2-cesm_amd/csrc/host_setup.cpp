@@ -283,6 +283,149 @@ double host_global_sum_loc(const HostModel &h, const double *a, const double *ma
   return g;
 }
 
+// ---- anisotropic viscosity (hmix_momentum = 3): the time-independent part of init_aniso (hmix_aniso.F90:372-533) and
+// compute_ccsm_var_viscosity (:1069-1296) on every block, ghost cells included, after the grid and dtu are set
+static void aniso_setup(HostModel &h) {
+  const pop_config &c = h.c;
+  const int nxb = h.nxb, nyb = h.nyb, NB = h.nblocks_tot, km = h.km, nxg = c.nx_global, nyg = c.ny_global;
+  const size_t n2 = h.n2, A2 = n2 * NB;
+  const Shift S{nxb, nyb, n2};
+  auto idx = [&](int b, int i, int j) { return b * n2 + (size_t)j * nxb + i; };
+  auto newf = [&](const char *n) -> std::vector<double> & { auto &v = h.f2[n]; v.assign(A2, 0.0); return v; };
+  auto each = [&](auto fn) { for (int b = 0; b < NB; ++b) for (int j = 0; j < nyb; ++j) for (int i = 0; i < nxb; ++i) fn(b, i, j, idx(b, i, j)); };
+  const double pi = 4.0 * std::atan(1.0), radian = 180.0 / pi;
+  const std::vector<double> &HTN = h.f2["HTN"], &HTE = h.f2["HTE"], &DXU = h.f2["DXU"], &DYU = h.f2["DYU"];
+  const std::vector<double> &DXUR = h.f2["DXUR"], &DYUR = h.f2["DYUR"], &ULAT = h.f2["ULAT"];
+  const std::vector<int> &KMU = h.i2["KMU"];
+  // geometry :374-393, eoshift within each block array (zero fill at its edges)
+  auto &H1E = newf("H1E"), &H1W = newf("H1W"), &H2N = newf("H2N"), &H2S = newf("H2S");
+  auto &K1E = newf("K1E"), &K1W = newf("K1W"), &K2N = newf("K2N"), &K2S = newf("K2S"), &AMAX = newf("AMAX_CFL");
+  std::vector<double> WA(A2);
+  for (size_t p = 0; p < A2; ++p) { H2S[p] = HTE[p]; H1W[p] = HTN[p]; }
+  each([&](int b, int i, int j, size_t p) { H2N[p] = S(H2S, b, i, j + 1); H1E[p] = S(H1W, b, i + 1, j); });
+  for (size_t p = 0; p < A2; ++p) WA[p] = H2S[p] + H2N[p];
+  each([&](int b, int i, int j, size_t p) { const double wb = S(WA, b, i - 1, j); K1W[p] = 2.0 * (WA[p] - wb) / (WA[p] + wb) / H1W[p]; });
+  each([&](int b, int i, int j, size_t p) { K1E[p] = S(K1W, b, i + 1, j); });
+  for (size_t p = 0; p < A2; ++p) WA[p] = H1W[p] + H1E[p];
+  each([&](int b, int i, int j, size_t p) { const double wb = S(WA, b, i, j - 1); K2S[p] = 2.0 * (WA[p] - wb) / (WA[p] + wb) / H2S[p]; });
+  each([&](int b, int i, int j, size_t p) { K2N[p] = S(K2S, b, i, j + 1); });
+  for (size_t p = 0; p < A2; ++p) AMAX[p] = 0.125 / (h.dtu * (DXUR[p] * DXUR[p] + DYUR[p] * DYUR[p]));   // :392-393
+  if (c.lsmag_aniso) {
+    auto &DSMIN = newf("DSMIN"), &FPS = newf("F_PERP_SMAG");
+    const double sl = c.smag_lat != 0.0 ? c.smag_lat : 20.0, sg = c.smag_lat_gauss != 0.0 ? c.smag_lat_gauss : 98.0;
+    for (size_t p = 0; p < A2; ++p) {
+      DSMIN[p] = std::min(DXU[p], DYU[p]);                                                     // :396
+      const double w = std::fabs(ULAT[p]) * radian;                                            // :522-528
+      FPS[p] = (w >= sl) ? 1.0 - c.smag_lat_fact * std::exp(-((w - sl) * (w - sl) / sg)) : 1.0 - c.smag_lat_fact;
+    }
+  }
+  // ANGLE of horiz_grid_file, scattered as an NE-corner field (grid.F90:1524-1525; scatter_global sets no sign beyond a tripole fold);
+  // 0 on the internal lat-lon grid
+  auto &ANG = newf("ANGLE");
+  if (h.gin && h.gin->ANGLE) {
+    for (int b = 0; b < NB; ++b) {
+      const BlockInfo &B = h.all_blocks[b];
+      for (int j = 0; j < nyb; ++j) for (int i = 0; i < nxb; ++i) {
+        const int ig = B.i_glob[i], jg = B.j_glob[j];
+        if (ig == 0 || jg == 0) continue;
+        int is = ig, js = jg;
+        if (jg < 0) { js = nyg + (jg + nyg); is = nxg - ig; if (is < 1) is += nxg; if (is > nxg) is -= nxg; }
+        ANG[idx(b, i, j)] = h.gin->ANGLE[(size_t)(js - 1) * nxg + (is - 1)];
+      }
+    }
+  }
+  if (!c.lvariable_hmix_aniso) return;
+  // compute_ccsm_var_viscosity :1153-1291 ('ccsm-internal'); 0 = the code default (:211-217)
+  const double v1 = c.vconst_1 != 0.0 ? c.vconst_1 : 1.e7, v2 = c.vconst_2 != 0.0 ? c.vconst_2 : 24.5, v3 = c.vconst_3 != 0.0 ? c.vconst_3 : 0.2;
+  const double v4 = c.vconst_4 != 0.0 ? c.vconst_4 : 1.e-8, v6 = c.vconst_6 != 0.0 ? c.vconst_6 : 1.e7, v7 = c.vconst_7 != 0.0 ? c.vconst_7 : 45.0;
+  const int v5 = c.vconst_5 != 0 ? c.vconst_5 : 3;
+  const double dist_max = 1.e10;
+  // gather_global of HTN and KMU (:1159-1160): the physical cells of every block
+  std::vector<double> HTN_G((size_t)nxg * nyg, 0.0), DIST_G((size_t)nxg * nyg, 0.0);
+  std::vector<int> KMU_G((size_t)nxg * nyg, 0);
+  for (int b = 0; b < NB; ++b) {
+    const BlockInfo &B = h.all_blocks[b];
+    for (int j = B.jb - 1; j < B.je; ++j) for (int i = B.ib - 1; i < B.ie; ++i) {
+      const int ig = B.i_glob[i], jg = B.j_glob[j];
+      if (ig < 1 || jg < 1) continue;
+      HTN_G[(size_t)(jg - 1) * nxg + ig - 1] = HTN[idx(b, i, j)]; KMU_G[(size_t)(jg - 1) * nxg + ig - 1] = KMU[idx(b, i, j)];
+    }
+  }
+  for (auto &F : h.aniso_f) F.assign(h.n3 * NB, 0.0);
+  std::vector<double> DIST(A2);
+  std::vector<int> nwbp(nxg + 1), iwp;
+  for (int k = 1; k <= km; ++k) {
+    for (int jg = 1; jg <= nyg; ++jg) {   // nearest western boundary (:1173-1200), cyclic in i
+      const int *Kr = KMU_G.data() + (size_t)(jg - 1) * nxg;
+      const double *Hr = HTN_G.data() + (size_t)(jg - 1) * nxg;
+      double *Dr = DIST_G.data() + (size_t)(jg - 1) * nxg;
+      iwp.clear();
+      std::fill(nwbp.begin(), nwbp.end(), 0);
+      for (int ig = 1; ig <= nxg; ++ig) {
+        const int igp1 = (ig == nxg) ? 1 : ig + 1;
+        if (Kr[ig - 1] < k && Kr[igp1 - 1] >= k) iwp.push_back(ig);
+      }
+      if (!iwp.empty()) {
+        for (size_t n = 0; n + 1 < iwp.size(); ++n) for (int ig = iwp[n]; ig <= iwp[n + 1] - 1; ++ig) nwbp[ig] = iwp[n];
+        for (int ig = 1; ig <= nxg; ++ig) if (nwbp[ig] == 0) nwbp[ig] = iwp.back();
+      }
+      for (int ig = 1; ig <= nxg; ++ig) {   // distance to it (:1207-1240)
+        const int index = nwbp[ig], indexo = index + v5;
+        double &D = Dr[ig - 1];
+        if (index == 0) D = dist_max;
+        else if (ig >= index && ig <= indexo) D = 0.0;
+        else if (ig > indexo) D = Hr[ig - 1] + Dr[ig - 2];
+        else if (ig < index) {
+          if (indexo <= nxg) {
+            if (ig == 1) {
+              D = 0.0;
+              for (int ii = indexo + 1; ii <= nxg; ++ii) D = Hr[ii - 1] + D;
+              D = Hr[ig - 1] + D;
+            } else D = Hr[ig - 1] + Dr[ig - 2];
+          } else {
+            if (ig <= indexo - nxg) D = 0.0;
+            else D = Hr[ig - 1] + Dr[ig - 2];
+          }
+        }
+      }
+    }
+    // scatter_global(DIST, DIST_G, ..., field_loc_NEcorner, field_type_scalar) (:1243-1244)
+    for (int b = 0; b < NB; ++b) {
+      const BlockInfo &B = h.all_blocks[b];
+      for (int j = 0; j < nyb; ++j) for (int i = 0; i < nxb; ++i) {
+        const int ig = B.i_glob[i], jg = B.j_glob[j];
+        double v = 0.0;
+        if (ig != 0 && jg != 0) {
+          int is = ig, js = jg;
+          if (jg < 0) { js = nyg + (jg + nyg); is = nxg - ig; if (is < 1) is += nxg; if (is > nxg) is -= nxg; }
+          v = DIST_G[(size_t)(js - 1) * nxg + (is - 1)];
+        }
+        DIST[idx(b, i, j)] = v;
+      }
+    }
+    for (int b = 0; b < NB; ++b)   // :1251-1290
+      for (size_t p2 = 0; p2 < n2; ++p2) {
+        const size_t p = b * n2 + p2, o = (size_t)b * h.n3 + (size_t)(k - 1) * n2 + p2;
+        const double beta_f = 2.0 * OMEGA * std::cos(ULAT[p]) / RADIUS;
+        double bv = std::min(std::fabs(ULAT[p] * radian), v7) * 90.0 / v7 / radian;
+        const double bu = v1 * (1.0 + v2 * (1.0 - std::cos(2.0 * bv)));
+        bv = v3 * beta_f * (DXU[p] * DXU[p] * DXU[p]);
+        const double t = v4 * DIST[p];
+        bv = bv * std::exp(-(t * t));
+        h.aniso_f[1][o] = std::max(bu, bv);   // F_PERP
+        h.aniso_f[0][o] = std::max(bv, v6);   // F_PARA
+      }
+  }
+  if (!c.lsmag_aniso)   // taper to 1/2 the CFL limit (:444-464)
+    for (int b = 0; b < NB; ++b)
+      for (int k = 1; k <= km; ++k)
+        for (size_t p2 = 0; p2 < n2; ++p2) {
+          const size_t o = (size_t)b * h.n3 + (size_t)(k - 1) * n2 + p2;
+          const double amax = AMAX[b * n2 + p2];
+          for (auto &F : h.aniso_f) if (F[o] > amax) F[o] = amax;
+        }
+}
+
 int host_build(HostModel &h) {
   const pop_config &c = h.c;
   h.km = c.km; h.nt = c.nt;
@@ -809,6 +952,7 @@ int host_build(HostModel &h) {
       for (int i = B.ib; i <= B.ie; ++i) if (B.i_glob[i - 1] > c.nx_global / 2) DUP[idx(b, i - 1, B.je - 1)] = 1.0;
     }
   }
+  if (c.hmix_momentum == 3) aniso_setup(h);
   // ---------------- P-CSI preprocessing (POP_SolversPrep) ----------------
   if (use_evp(c) || c.solver_choice == 3) {   // POP_SolversPrep (POP_SolversMod.F90:181-320): EVP first, then Lanczos
     const std::vector<double> C0 = host_center_init(h);

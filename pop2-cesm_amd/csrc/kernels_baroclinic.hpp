@@ -488,7 +488,7 @@ k_impvmixt_back(DevGrid g, ImpvmixtBackArgs a) {
 struct MomentumRhsArgs {
   const double *UCUR, *VCUR, *UOLD, *VOLD, *UMIX, *VMIX;
   const double *RHOOLD, *RHOCUR, *RHONEW, *VVC, *DHU;
-  const double *HDU, *HDV;   // del4 only: precomputed biharmonic friction
+  const double *HDU, *HDV;   // precomputed friction (hmix_momentum = 3: hdiffu_aniso, kernels_aniso.hpp): k_momentum_rhs<true>, k_momentum_rhs_lds<., ., true>
   double *UNEW, *VNEW, *ZX, *ZY;
   // LDS kernel, del4: the first Laplacian of the CURRENT velocity (k_del4_d2u's formula, from the tile in LDS) for the next step
   double *D2N[2] = {nullptr, nullptr};

@@ -31,7 +31,9 @@ struct MomTile {
 
 // PBC: partial bottom cells (advection.F90:1245-1300, 1352, 1381-1467; hmix_del2.F90:852-886 / hmix_del4.F90:683-812;
 // vertical_mix.F90:946-995; baroclinic.F90:1037-1039) with DZU formed from KMU / DZUB (pbc_dz)
-template <int R, bool PBC = false>
+// PRE: precomputed friction (hmix_momentum = 3): the cell's own HDU, HDV are read in place of the Laplacian of UMIX, VMIX, which
+// are not staged (the um / vm slots of the tile carry HDU, HDV of the own cell only)
+template <int R, bool PBC = false, bool PRE = false>
 __global__ void __launch_bounds__(POP_COL_THREADS * R)
 k_momentum_rhs_lds(DevGrid g, StepParams sp, MomentumRhsArgs a, int tj_first, int tj_count) {
 #ifdef POP_PROBE_MOM_CONTRACT
@@ -122,13 +124,18 @@ k_momentum_rhs_lds(DevGrid g, StepParams sp, MomentumRhsArgs a, int tj_first, in
   auto load_cell = [&](int k) {
     Lev L;
     const long long o = base3 + (long long)(k - 1) * n2;
-    L.rn = RN[o]; L.rc = a.RHOCUR[o]; L.ro = RO[o]; L.um = a.UMIX[o]; L.vm = a.VMIX[o]; L.vvc = a.VVC[o];
+    L.rn = RN[o]; L.rc = a.RHOCUR[o]; L.ro = RO[o];
+    if constexpr (PRE) { L.um = a.HDU[o]; L.vm = a.HDV[o]; }
+    else { L.um = a.UMIX[o]; L.vm = a.VMIX[o]; }
+    L.vvc = a.VVC[o];
     return L;
   };
   auto load_halo = [&](int k) {
     Hal Hh;
     const long long o = hbase + (long long)(k - 1) * n2;
-    Hh.u = a.UCUR[o]; Hh.v = a.VCUR[o]; Hh.rn = RN[o]; Hh.rc = a.RHOCUR[o]; Hh.ro = RO[o]; Hh.um = a.UMIX[o]; Hh.vm = a.VMIX[o];
+    Hh.u = a.UCUR[o]; Hh.v = a.VCUR[o]; Hh.rn = RN[o]; Hh.rc = a.RHOCUR[o]; Hh.ro = RO[o];
+    if constexpr (PRE) { Hh.um = 0.0; Hh.vm = 0.0; }
+    else { Hh.um = a.UMIX[o]; Hh.vm = a.VMIX[o]; }
     return Hh;
   };
   auto rho_f = [&](double rn, double rc, double ro, double bk) { return pavg ? 0.25 * (rn + 2.0 * rc + ro) * bk : rc * bk; };
@@ -151,10 +158,11 @@ k_momentum_rhs_lds(DevGrid g, StepParams sp, MomentumRhsArgs a, int tj_first, in
       // its own cell (same addresses, same level), so it rewrites its own cell with the same values and no select is needed (r4: the
       // 14 selects `hd ? hal.x : own.x` were 28 v_cndmask of the 368 VALU instructions of a level)
       t.u[buf][lc] = own.u; t.v[buf][lc] = own.v; t.ud[buf][lc] = pu; t.vd[buf][lc] = pv;
-      t.f[buf][lc] = rho_f(cur.rn, cur.rc, cur.ro, bk); t.um[buf][lc] = cur.um; t.vm[buf][lc] = cur.vm;
+      t.f[buf][lc] = rho_f(cur.rn, cur.rc, cur.ro, bk);
+      if constexpr (!PRE) { t.um[buf][lc] = cur.um; t.vm[buf][lc] = cur.vm; }
       t.u[buf][hl] = hal.u; t.v[buf][hl] = hal.v; t.ud[buf][hl] = hu; t.vd[buf][hl] = hv;
       t.f[buf][hl] = rho_f(hal.rn, hal.rc, hal.ro, bk);
-      t.um[buf][hl] = hal.um; t.vm[buf][hl] = hal.vm;
+      if constexpr (!PRE) { t.um[buf][hl] = hal.um; t.vm[buf][hl] = hal.vm; }
     }
     const int kp1 = (k < km) ? k + 1 : km, kp2 = (k + 2 <= km) ? k + 2 : km;
     const Lev nxt = load_cell(kp1);                          // in flight while this level is computed
@@ -215,7 +223,9 @@ k_momentum_rhs_lds(DevGrid g, StepParams sp, MomentumRhsArgs a, int tj_first, in
         const double zn = t.dzu[buf][lc + T::W], zs = t.dzu[buf][lc - T::W], ze = t.dzu[buf][lc + 1], zw = t.dzu[buf][lc - 1];
         cn = dun * fmin(zn, dzu) / dzu; cs = dus * fmin(zs, dzu) / dzu; ce = due * fmin(ze, dzu) / dzu; cw = duw * fmin(zw, dzu) / dzu;
       }
-      {
+      if constexpr (PRE) {
+        FX = FX + (wet ? cur.um : 0.0); FY = FY + (wet ? cur.vm : 0.0);
+      } else {
         const double um0 = t.um[buf][lc], umn = t.um[buf][lc + T::W], ums = t.um[buf][lc - T::W], ume = t.um[buf][lc + 1], umw = t.um[buf][lc - 1];
         const double vm0 = t.vm[buf][lc], vmn = t.vm[buf][lc + T::W], vms = t.vm[buf][lc - T::W], vme = t.vm[buf][lc + 1], vmw = t.vm[buf][lc - 1];
         const double hdu = sp.am * ((cc_h * um0 + cn * umn + cs * ums + ce * ume + cw * umw) +
@@ -274,14 +284,17 @@ k_momentum_rhs_lds(DevGrid g, StepParams sp, MomentumRhsArgs a, int tj_first, in
 
 // tj_first / tj_count: window of tile rows (default: all) -- the rim / interior split around a halo exchange
 template <int R>
-inline void launch_momentum_lds(const DevGrid &g, const StepParams &sp, const MomentumRhsArgs &a, hipStream_t st, int tj_first = 0, int tj_count = -1) {
+inline void launch_momentum_lds(const DevGrid &g, const StepParams &sp, const MomentumRhsArgs &a, hipStream_t st, int tj_first = 0, int tj_count = -1,
+                                bool pre = false) {
   const int tiles_i = (g.nxb - 2 * NGHOST + POP_COL_THREADS - 1) / POP_COL_THREADS;
   const int tiles_j = (g.nyb - 2 * NGHOST + R - 1) / R;
   if (tj_count < 0) tj_count = tiles_j - tj_first;
   if (tj_count <= 0) return;
   const bool whole = tj_first == 0 && tj_count == tiles_j;
   const dim3 G(whole ? lds_launch_x<R>(g, tiles_i, tiles_j) : lds_grid_x(g.lds_order, tiles_i, tj_count), g.nblocks), B(POP_COL_THREADS, R);
-  if (g.pbc) hipLaunchKernelGGL((k_momentum_rhs_lds<R, true>), G, B, 0, st, g, sp, a, tj_first, tj_count);
+  if (pre && g.pbc) hipLaunchKernelGGL((k_momentum_rhs_lds<R, true, true>), G, B, 0, st, g, sp, a, tj_first, tj_count);
+  else if (pre) hipLaunchKernelGGL((k_momentum_rhs_lds<R, false, true>), G, B, 0, st, g, sp, a, tj_first, tj_count);
+  else if (g.pbc) hipLaunchKernelGGL((k_momentum_rhs_lds<R, true>), G, B, 0, st, g, sp, a, tj_first, tj_count);
   else hipLaunchKernelGGL((k_momentum_rhs_lds<R, false>), G, B, 0, st, g, sp, a, tj_first, tj_count);
 }
 

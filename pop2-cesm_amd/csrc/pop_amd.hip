@@ -11,6 +11,7 @@
 #include "kernels_mix.hpp"
 #include "kernels_thomas_reg.hpp"
 #include "kernels_momentum_lds.hpp"
+#include "kernels_aniso.hpp"
 #include "kernels_tracer_lds.hpp"
 #include "kernels_rf.hpp"
 #include "kernels_pcsi.hpp"
@@ -58,6 +59,8 @@ struct pop_ctx {
   // del4: the first Laplacians need only the mix-time fields, so they run on a side stream beside the vertical-mixing
   // coefficients (own output buffers d2t / d2u instead of the shared scratch; POP_DEL4_SIDE=0: in line, scratch reused)
   double *d2t[2] = {nullptr, nullptr}, *d2u[2] = {nullptr, nullptr};
+  // hmix_momentum = 3: the friction hdiffu_aniso forms (3-D, read by the momentum kernel) and the variable viscosities F_PARA, F_PERP
+  double *HDU = nullptr, *HDV = nullptr, *FPARA = nullptr, *FPERP = nullptr;
   // del4: the tracer kernel of a step also forms the first Laplacian of its CURRENT tracers -- the mix-time field of the next
   // (leapfrog) step -- from the tile it has in LDS; d2t_next receives it, d2t_next_slot is the time slot it belongs to
   double *d2t_next[2] = {nullptr, nullptr};
@@ -72,6 +75,7 @@ struct pop_ctx {
   bool uv_ghosts_ok[3] = {true, true, true};
   bool d2t_last_formed = false, d2u_last_formed = false;   // did the last tracer / momentum launch write the next step's field (bench accounting)
   hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_d2t = nullptr, ev_d2u = nullptr, ev_vmixu = nullptr;
+  bool mom_side = false;   // phase_hmix_momentum on the side stream: del4 with side_del4; anis unless pop_tuning.aniso_side = 0
   bool side_del4 = false, vmixu_pending = false, btrop_added = false, vmixu_deferred = false;   // implicit vertical mixing of U,V in flight on the side stream
   double *HBLT = nullptr, *HMXL = nullptr, *HMXL_DR = nullptr;
   MixDev mix{};
@@ -202,6 +206,14 @@ std::vector<T> local_part(const HostModel &h, const std::vector<T> &all) {
   std::vector<T> out(h.n2 * h.nblocks);
   for (int lb = 0; lb < h.nblocks; ++lb)
     std::copy(all.begin() + (size_t)(h.local_ids[lb] - 1) * h.n2, all.begin() + (size_t)h.local_ids[lb] * h.n2, out.begin() + (size_t)lb * h.n2);
+  return out;
+}
+
+// the same for an all-blocks 3-D host field (nxb, nyb, km, nblocks_tot)
+std::vector<double> local_part3(const HostModel &h, const std::vector<double> &all) {
+  std::vector<double> out(h.n3 * h.nblocks);
+  for (int lb = 0; lb < h.nblocks; ++lb)
+    std::copy(all.begin() + (size_t)(h.local_ids[lb] - 1) * h.n3, all.begin() + (size_t)h.local_ids[lb] * h.n3, out.begin() + (size_t)lb * h.n3);
   return out;
 }
 
@@ -1588,6 +1600,10 @@ int resolve(pop_ctx *c, const std::string &name, int tl, int n, double **ptr, lo
   if (name == "TLT_DIABATIC_DEPTH") return ok(c->gm.DD, a2);
   if (name == "TLT_THICKNESS") return ok(c->gm.TH, a2);
   if (name == "TLT_INTERIOR_DEPTH") return ok(c->gm.ID, a2);
+  if (name == "HDU") return ok(c->HDU, a3);                   // hmix_momentum = 3: Hdiff(U), Hdiff(V) of hdiffu_aniso at every level
+  if (name == "HDV") return ok(c->HDV, a3);
+  if (name == "F_PARA") return ok(c->FPARA, a3);              // ... with lvariable_hmix_aniso
+  if (name == "F_PERP") return ok(c->FPERP, a3);
   if (name == "SMF") return ok(c->d2[n == 0 ? "SMF1" : "SMF2"], a2);
   if (name == "SMFT") return ok(c->d2[n == 0 ? "SMFT1" : "SMFT2"], a2);
   auto it = c->d2.find(name);
@@ -1620,7 +1636,7 @@ int pop_create_with_grid(const pop_config *cfg, const pop_grid_input *grid, int 
   X(kpp_src_full, "POP_KPP_SRC_FULL") X(solver_unfused, "POP_SOLVER_UNFUSED") X(solver_nograph, "POP_SOLVER_NOGRAPH")                   \
   X(solver_presum, "POP_SOLVER_PRESUM") X(solver_distributed, "POP_SOLVER_DISTRIBUTED") X(solver_overlap_off, "POP_SOLVER_OVERLAP_OFF") \
   X(fpcg_b2, "POP_FPCG_B2") X(pcsi_step2, "POP_PCSI_STEP2") X(halo_separate, "POP_HALO_SEPARATE")                                       \
-  X(halo_overlap_off, "POP_HALO_OVERLAP_OFF") X(rccl_overlap, "POP_RCCL_OVERLAP") X(evp_wave, "POP_EVP_WAVE") X(fpcg_a_pair, "POP_FPCG_A_PAIR") X(stream_priority, "POP_STREAM_PRIORITY") X(kpp_sparse, "POP_KPP_SPARSE") X(pbc_generic_thomas, "POP_PBC_GENERIC_THOMAS") X(pbc_generic_kpp, "POP_PBC_GENERIC_KPP") X(state3d_levels, "POP_STATE3D_LEVELS") X(gm_sf_stored, "POP_GM_SF_STORED") X(pcg_persist, "POP_PCG_PERSIST") X(gm_flux_tile, "POP_GM_FLUX_TILE") X(pcsi_two_step, "POP_PCSI_TWO_STEP") X(block_sums_relay, "POP_BLOCK_SUMS_RELAY") X(pcsi_evp_fused, "POP_PCSI_EVP_FUSED")
+  X(halo_overlap_off, "POP_HALO_OVERLAP_OFF") X(rccl_overlap, "POP_RCCL_OVERLAP") X(evp_wave, "POP_EVP_WAVE") X(fpcg_a_pair, "POP_FPCG_A_PAIR") X(stream_priority, "POP_STREAM_PRIORITY") X(kpp_sparse, "POP_KPP_SPARSE") X(pbc_generic_thomas, "POP_PBC_GENERIC_THOMAS") X(pbc_generic_kpp, "POP_PBC_GENERIC_KPP") X(state3d_levels, "POP_STATE3D_LEVELS") X(gm_sf_stored, "POP_GM_SF_STORED") X(pcg_persist, "POP_PCG_PERSIST") X(gm_flux_tile, "POP_GM_FLUX_TILE") X(pcsi_two_step, "POP_PCSI_TWO_STEP") X(block_sums_relay, "POP_BLOCK_SUMS_RELAY") X(pcsi_evp_fused, "POP_PCSI_EVP_FUSED") X(aniso_side, "POP_ANISO_SIDE")
 void pop_tuning_init(pop_tuning *t) {
   if (!t) return;
   t->struct_bytes = (int)sizeof(pop_tuning);
@@ -1664,11 +1680,15 @@ int pop_read_grid_files(const char *horiz_grid_file, const char *topography_file
   return 0;
 }
 
-int pop_create_tuned(const pop_config *cfg, const pop_grid_input *grid, const pop_tuning *tuning, int rank, int nranks, int flags, pop_ctx **out) {
-  if (!cfg || !out || nranks < 1 || rank < 0 || rank >= nranks) return 1;
+int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const pop_tuning *tuning, int rank, int nranks, int flags, pop_ctx **out) {
+  if (!cfg_in || !out || nranks < 1 || rank < 0 || rank >= nranks) return 1;
   pop_ctx *c = new pop_ctx();
   *out = c;
-  c->h.c = *cfg; c->h.rank = rank; c->h.nranks = nranks;
+  // a version-5 caller's struct ends at kappa_depth_scale: read that much only (the version-6 members stay 0)
+  if (cfg_in->struct_version == POP_CONFIG_VERSION) c->h.c = *cfg_in;
+  else memcpy(&c->h.c, cfg_in, offsetof(pop_config, aniso_alignment));
+  const pop_config *cfg = &c->h.c;
+  c->h.rank = rank; c->h.nranks = nranks;
   if (cfg->hmix_tracer == 3 && cfg->gm_transition_layer == 1 && cfg->vmix_choice == 3) c->h.c.kpp_ml_diagnostics = 1;   // the diabatic depth of the transition layer is the smoothed HMXL (hmix_gm.F90:1226-1228)
   if (tuning && tuning->struct_bytes != (int)sizeof(pop_tuning)) { c->err = "pop_create_tuned: pop_tuning.struct_bytes does not match this library (use pop_tuning_init)"; return 1; }
   tuning_resolve(c->h.tun, tuning);
@@ -1678,7 +1698,7 @@ int pop_create_tuned(const pop_config *cfg, const pop_grid_input *grid, const po
   {   // every option this library does not implement is refused here, before anything is built (the reference aborts
       // in the init routine of the option's own module, e.g. vertical_mix.F90:280-296, POP_SolversMod.F90:442-472)
     auto bad = [&](const std::string &m) { c->err = "pop_create: " + m; return 1; };
-    if (cfg->struct_version != POP_CONFIG_VERSION) return bad("pop_config.struct_version is " + std::to_string(cfg->struct_version) + ", this library was built for " + std::to_string(POP_CONFIG_VERSION) + " (include/pop_amd.h)");
+    if (cfg->struct_version != POP_CONFIG_VERSION && cfg->struct_version != 5) return bad("pop_config.struct_version is " + std::to_string(cfg->struct_version) + ", this library reads 5 and " + std::to_string(POP_CONFIG_VERSION) + " (include/pop_amd.h)");
     if (cfg->reserved_i[0] != 0) return bad("pop_config.reserved_i must be 0");
     if (cfg->gm_kappa_bkg_srfbl != 0 && cfg->gm_kappa_bkg_srfbl != 1) return bad("gm_kappa_bkg_srfbl: 0 or 1");
     if (cfg->ah_bkg_bottom < 0.0) return bad("ah_bkg_bottom: >= 0");
@@ -1704,7 +1724,19 @@ int pop_create_tuned(const pop_config *cfg, const pop_grid_input *grid, const po
     if (cfg->nx_global < 1 || cfg->ny_global < 1 || cfg->km < 2 || cfg->block_size_x < 1 || cfg->block_size_y < 1) return bad("domain / block sizes must be positive (km >= 2)");
     if (cfg->ew_boundary != 0 && cfg->ew_boundary != 1) return bad("ew_boundary: 0 closed, 1 cyclic");
     if (cfg->ns_boundary < 0 || cfg->ns_boundary > 2) return bad("ns_boundary: 0 closed, 1 cyclic, 2 tripole");
-    if (cfg->hmix_momentum != 2 && cfg->hmix_momentum != 4) return bad("hmix_momentum: 2 (del2) or 4 (del4); the anisotropic viscosity is not built");
+    if (cfg->hmix_momentum == 3 && cfg->struct_version < 6) return bad("hmix_momentum = 3 (anis) needs pop_config struct_version 6: the hmix_aniso_nml members (include/pop_amd.h)");
+    if (cfg->hmix_momentum != 2 && cfg->hmix_momentum != 4 && cfg->hmix_momentum != 3) return bad("hmix_momentum: 2 (del2), 4 (del4) or 3 (anis)");
+    if (cfg->hmix_momentum == 3) {   // hmix_aniso_nml (hmix_aniso.F90:167-347)
+      if (cfg->aniso_alignment == 2)
+        return bad("aniso_alignment = 2 ('flow') is not built: hmix_aniso.F90:787-794 resets the whole NORM1 / NORM2 block array whenever one point is "
+                   "slower than eps (land points have U = 0), so the reference's result depends on the block's loop order");
+      if (cfg->aniso_alignment != 0 && cfg->aniso_alignment != 1) return bad("aniso_alignment: 0 'grid', 1 'east' (2 'flow' is not built)");
+      if (cfg->lvariable_hmix_aniso != 0 && cfg->lvariable_hmix_aniso != 1) return bad("lvariable_hmix_aniso: 0 or 1");
+      if (cfg->lsmag_aniso != 0 && cfg->lsmag_aniso != 1) return bad("lsmag_aniso: 0 or 1");
+      if (cfg->lsmag_aniso && cfg->smag_lat_fact == 0.0) return bad("lsmag_aniso with smag_lat_fact = 0: the reference leaves F_PERP_SMAG unset then (hmix_aniso.F90:512-531)");
+      if (cfg->vconst_5 < 0) return bad("vconst_5: >= 0 (0 = 3)");
+      if (cfg->vconst_7 < 0.0 || cfg->smag_lat_gauss < 0.0) return bad("vconst_7, smag_lat_gauss: > 0 (0 = 45, 98)");
+    }
     if (cfg->hmix_tracer != 2 && cfg->hmix_tracer != 4 && cfg->hmix_tracer != 3) return bad("hmix_tracer: 2 (del2), 4 (del4) or 3 (gm)");
     if (cfg->vmix_choice < 1 || cfg->vmix_choice > 3) return bad("vmix_choice: 1 const, 2 rich, 3 kpp");
     if (cfg->tadvect < 1 || cfg->tadvect > 3) return bad("tadvect: 1 centered, 2 upwind3, 3 lw_lim");
@@ -1932,6 +1964,14 @@ int pop_create_tuned(const pop_config *cfg, const pop_grid_input *grid, const po
     g.DMC = c->d2["d4DMC"]; g.DMN = c->d2["d4DMN"]; g.DMS = c->d2["d4DMS"]; g.DME = c->d2["d4DME"]; g.DMW = c->d2["d4DMW"]; g.DUM = c->d2["d4DUM"];
   }
   if (cfg->hmix_tracer == 4 || cfg->hmix_momentum == 4) { c->mix.D4AMF = c->d2["D4AMF"]; c->mix.D4AHF = c->d2["D4AHF"]; }
+  if (cfg->hmix_momentum == 3) {   // anisotropic viscosity: the friction fields and the variable viscosities (local blocks)
+    const size_t a3h = h.n3 * h.nblocks;
+    if (dev_alloc(c, &c->HDU, a3h) || dev_alloc(c, &c->HDV, a3h)) return 1;
+    if (cfg->lvariable_hmix_aniso) {
+      const std::vector<double> fpa = local_part3(h, h.aniso_f[0]), fpe = local_part3(h, h.aniso_f[1]);
+      if (dev_upload(c, &c->FPARA, fpa.data(), fpa.size()) || dev_upload(c, &c->FPERP, fpe.data(), fpe.size())) return 1;
+    }
+  }
   if (cfg->tadvect == 2) {
     const char *nx[6] = {"TALFXP", "TBETXP", "TGAMXP", "TALFXM", "TBETXM", "TDELXM"};
     const char *ny[6] = {"TALFYP", "TBETYP", "TGAMYP", "TALFYM", "TBETYM", "TDELYM"};
@@ -2038,6 +2078,7 @@ int pop_create_tuned(const pop_config *cfg, const pop_grid_input *grid, const po
         if (dev_alloc(c, &c->d2u_next[0], a3) || dev_alloc(c, &c->d2u_next[1], a3)) return 1;
     }
   }
+  c->mom_side = cfg->hmix_momentum == 3 ? (c->side != nullptr && !tun_off(h.tun.aniso_side)) : c->side_del4;
   c->nchunk = red_grid_x(g);
   if (!g.red_tiles) {   // DevGrid::red_act: the chunks (256 consecutive cells) the fused solver kernels have to visit
     const int nc = (int)((h.n2 + 255) / 256);
@@ -2448,7 +2489,7 @@ int pop_local_block_ids(const pop_ctx *c, int *ids) { std::copy(c->h.local_ids.b
 long long pop_field_count(const pop_ctx *c, const char *name) {
   const std::string n(name);
   const long long a2 = (long long)c->h.n2 * c->h.nblocks, a3 = (long long)c->h.n3 * c->h.nblocks;
-  for (const char *s : {"TRACER", "UVEL", "VVEL", "RHO", "KPP_SRC", "VVC", "UISOP", "VISOP", "WISOP", "GM_SF_SLX", "GM_SF_SLY"}) if (n == s) return a3;
+  for (const char *s : {"TRACER", "UVEL", "VVEL", "RHO", "KPP_SRC", "VVC", "UISOP", "VISOP", "WISOP", "GM_SF_SLX", "GM_SF_SLY", "HDU", "HDV", "F_PARA", "F_PERP"}) if (n == s) return a3;
   if (n == "VDC") return (long long)c->h.n2 * (c->h.km + 2) * c->h.nblocks;
   return a2;
 }
@@ -2473,7 +2514,15 @@ static int join_side(pop_ctx *c, bool keep_ahead = false) {
 }
 int pop_get_field(pop_ctx *c, const char *name, int tl, int n, double *host, long long count) {
   const std::string nm(name);
-  if (c->host_only) {   // host-only contexts expose the init-time 2-D fields of the local blocks
+  if (c->host_only) {   // host-only contexts expose the init-time 2-D fields of the local blocks (and F_PARA, F_PERP)
+    if (nm == "F_PARA" || nm == "F_PERP") {
+      const std::vector<double> &all = c->h.aniso_f[nm == "F_PARA" ? 0 : 1];
+      if (all.empty()) { c->err = nm + " exists with hmix_momentum = 3 and lvariable_hmix_aniso only"; return 1; }
+      const std::vector<double> loc = local_part3(c->h, all);
+      if ((long long)loc.size() != count) { c->err = "count mismatch for " + nm; return 1; }
+      std::copy(loc.begin(), loc.end(), host);
+      return 0;
+    }
     std::string key = nm;
     if (nm == "SMF") key = n == 0 ? "SMF1" : "SMF2";
     if (nm == "SMFT") key = n == 0 ? "SMFT1" : "SMFT2";
@@ -2500,6 +2549,19 @@ int pop_set_field(pop_ctx *c, const char *name, int tl, int n, const double *hos
   if (join_side(c)) return 1;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(p, host, cnt * sizeof(double), hipMemcpyHostToDevice));
+  if ((!strcmp(name, "F_PARA") || !strcmp(name, "F_PERP")) && !c->h.c.lsmag_aniso) {
+    // var_viscosity_infile: init_aniso tapers what it read to AMAX_CFL (hmix_aniso.F90:444-464); a min, so writing back what was read changes nothing
+    const std::vector<double> amax = local_part(c->h, c->h.f2.at("AMAX_CFL"));
+    std::vector<double> f(host, host + cnt);
+    for (int lb = 0; lb < c->h.nblocks; ++lb)
+      for (int k = 0; k < c->h.km; ++k)
+        for (size_t p2 = 0; p2 < c->h.n2; ++p2) {
+          double &v = f[(size_t)lb * c->h.n3 + (size_t)k * c->h.n2 + p2];
+          const double m = amax[(size_t)lb * c->h.n2 + p2];
+          if (v > m) v = m;
+        }
+    HIPCHK(c, hipMemcpy(p, f.data(), cnt * sizeof(double), hipMemcpyHostToDevice));
+  }
   if (!strcmp(name, "CHL") && c->h.sw.CHLI) {   // set_chl (sw_absorption.F90:500-512): the column of the transmission table per cell
     std::vector<int> idx((size_t)cnt);
     for (long long q = 0; q < cnt; ++q) idx[q] = sw_chl_index(c->h.sw, host[q]);
@@ -2939,7 +3001,22 @@ static void state_new_rows(pop_ctx *c, int j_first, int j_end) {
   hipLaunchKernelGGL(k_state3d_rows, dim3((p1 - p0 + 255) / 256, c->g.km, c->g.nblocks), dim3(256), 0, c->stream, c->g,
                      (const double *)c->TR[0][c->newt], (const double *)c->TR[1][c->newt], c->RHO[c->newt], p0, p1);
 }
-static int phase_hmix_momentum(pop_ctx *c, hipStream_t st = nullptr) {   // del4 only: first Laplacian of the velocity into d2u
+// anis: hdiffu_aniso of the mix-time velocity into HDU, HDV (every level)
+static AnisoArgs aniso_args(pop_ctx *c) {
+  const pop_config &cf = c->h.c;
+  AnisoArgs a{};
+  a.UM = c->U[c->mixt]; a.VM = c->V[c->mixt]; a.HDU = c->HDU; a.HDV = c->HDV;
+  a.H1E = c->d2["H1E"]; a.H1W = c->d2["H1W"]; a.H2N = c->d2["H2N"]; a.H2S = c->d2["H2S"];
+  a.K1E = c->d2["K1E"]; a.K1W = c->d2["K1W"]; a.K2N = c->d2["K2N"]; a.K2S = c->d2["K2S"];
+  a.AMAX = c->d2["AMAX_CFL"]; a.ANGLE = c->d2["ANGLE"]; a.UAREA = c->d2["UAREA"];
+  if (cf.lsmag_aniso) { a.DSMIN = c->d2["DSMIN"]; a.FPS = c->d2["F_PERP_SMAG"]; }
+  a.FPARA = c->FPARA; a.FPERP = c->FPERP;
+  a.visc_para = cf.visc_para; a.visc_perp = cf.visc_perp; a.c_para = cf.c_para; a.c_perp = cf.c_perp;
+  a.east = cf.aniso_alignment == 1; a.variable = cf.lvariable_hmix_aniso; a.smag = cf.lsmag_aniso;
+  return a;
+}
+static int phase_hmix_momentum(pop_ctx *c, hipStream_t st = nullptr) {   // del4: first Laplacian of the velocity into d2u; anis: HDU, HDV
+  if (c->h.c.hmix_momentum == 3) { launch_hdiffu_aniso(c->g, aniso_args(c), st ? st : c->stream); return 0; }
   if (c->h.c.hmix_momentum != 4) return 0;
   if (c->d2u_next_valid && c->d2u_next_slot == c->mixt) {   // formed by the previous step's momentum kernel (ghost ring already updated)
     c->d2u_next_valid = false;
@@ -2964,8 +3041,12 @@ static int phase_momentum_rhs(pop_ctx *c, int tj_first = 0, int tj_count = -1, b
                          c->h.c.tmix_opt != 3 && c->uv_ghosts_ok[c->curt];
   if (form_next) { a.D2N[0] = c->d2u_next[0]; a.D2N[1] = c->d2u_next[1]; a.AMF = c->mix.D4AMF; }
   c->d2u_last_formed = form_next;
-  if (c->mom_lds_rows == 8) launch_momentum_lds<8>(c->g, step_params(c), a, c->stream, tj_first, tj_count);
-  else if (c->mom_lds_rows == 4) launch_momentum_lds<4>(c->g, step_params(c), a, c->stream, tj_first, tj_count);
+  const bool pre = c->h.c.hmix_momentum == 3;   // anis: the friction phase_hmix_momentum formed
+  if (pre) { a.HDU = c->HDU; a.HDV = c->HDV; }
+  if (c->mom_lds_rows == 8) launch_momentum_lds<8>(c->g, step_params(c), a, c->stream, tj_first, tj_count, pre);
+  else if (c->mom_lds_rows == 4) launch_momentum_lds<4>(c->g, step_params(c), a, c->stream, tj_first, tj_count, pre);
+  else if (pre && c->g.pbc) hipLaunchKernelGGL((k_momentum_rhs<true, true>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, step_params(c), a);
+  else if (pre) hipLaunchKernelGGL((k_momentum_rhs<true, false>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, step_params(c), a);
   else if (c->g.pbc) hipLaunchKernelGGL((k_momentum_rhs<false, true>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, step_params(c), a);
   else hipLaunchKernelGGL((k_momentum_rhs<false, false>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, step_params(c), a);
   if (form_next && last_piece && !c->phase_timing) {
@@ -3001,20 +3082,20 @@ int pop_baroclinic_driver(pop_ctx *c) {
   ScopedPhase ph(c, "BAROCLINIC");
   if (c->vmixu_deferred) { c->vmixu_deferred = false; if (phase_impvmixu(c, nullptr)) return 1; }   // a driver call that was never followed by its correct_adjust
   const StepParams sp = step_params(c);
-  const bool fork = c->side_del4;
-  if (fork) {   // del4 first Laplacians beside the vertical-mixing coefficients
+  // del4 first Laplacians / the anisotropic friction beside the vertical-mixing coefficients: they read only mix-time fields
+  const bool tr_side = c->side_del4 && c->h.c.hmix_tracer != 3;
+  const bool fork = c->mom_side || tr_side;
+  if (fork) {
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    if (c->h.c.hmix_tracer != 3 && phase_hmix_tracer(c, c->side)) return 1;
+    if (tr_side && phase_hmix_tracer(c, c->side)) return 1;
     HIPCHK(c, hipEventRecord(c->ev_d2t, c->side));
-    if (phase_hmix_momentum(c, c->side)) return 1;
+    if (c->mom_side && phase_hmix_momentum(c, c->side)) return 1;
     HIPCHK(c, hipEventRecord(c->ev_d2u, c->side));
   }
   if (phase_vmix(c)) return 1;
-  if (fork) {
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2t, 0));
-    if (c->h.c.hmix_tracer == 3 && phase_hmix_tracer(c)) return 1;   // Gent-McWilliams reads and adds to the coefficients vmix just formed
-  } else if (phase_hmix_tracer(c)) return 1;
+  if (fork) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2t, 0));
+  if (!tr_side && phase_hmix_tracer(c)) return 1;   // Gent-McWilliams reads and adds to the coefficients vmix just formed
   const bool fwd = sp.pavg && tracer_fwd_fused(c);
   if (phase_tracer_rhs(c, fwd)) return 1;
   // several ranks: the exchange of the new tracers' ghost rows runs on the communication stream while the launch stream
@@ -3029,7 +3110,7 @@ int pop_baroclinic_driver(pop_ctx *c) {
       HaloAsync HA;
       if (halo_many_begin(c, {{c->TR[0][c->newt], c->g.km}, {c->TR[1][c->newt], c->g.km}}, HA)) return 1;
       state_new_rows(c, NGHOST, c->g.nyb - NGHOST);                      // physical rows: own cells + ghosts copied inside the rank
-      if (fork) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2u, 0));
+      if (c->mom_side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2u, 0));
       else if (phase_hmix_momentum(c)) return 1;
       if (phase_momentum_rhs(c, 1, mtiles_j - 2, false)) return 1;      // interior tile rows
       if (halo_many_end(c, HA)) return 1;
@@ -3038,12 +3119,12 @@ int pop_baroclinic_driver(pop_ctx *c) {
     } else {
       if (halo_update_many(c, {{c->TR[0][c->newt], c->g.km}, {c->TR[1][c->newt], c->g.km}})) return 1;
       if (phase_state_new(c)) return 1;
-      if (fork) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2u, 0));
+      if (c->mom_side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2u, 0));
       else if (phase_hmix_momentum(c)) return 1;
       if (phase_momentum_rhs(c)) return 1;
     }
   } else {
-    if (fork) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2u, 0));
+    if (c->mom_side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2u, 0));
     else if (phase_hmix_momentum(c)) return 1;
     if (phase_momentum_rhs(c)) return 1;
   }

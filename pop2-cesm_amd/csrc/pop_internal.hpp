@@ -100,6 +100,7 @@ struct HostModel {
   std::map<std::string, std::vector<double>> f2;   // (nxb,nyb,nblocks)
   std::map<std::string, std::vector<int>> i2;
   std::map<std::string, std::vector<double>> f3;   // (nxb,nyb,km,nblocks), initial state only
+  std::vector<double> aniso_f[2];                  // hmix_momentum = 3 with lvariable_hmix_aniso: F_PARA, F_PERP of ALL blocks (nxb,nyb,km,nblocks_tot)
   double uarea_equator = 0, residualNorm = 0, convergenceCriterion = 0, rcheck = 0, rconst = 0;
   double dtt = 0, dtu = 0, dtp = 0;
   int nsteps_per_interval = 0;

@@ -12,7 +12,7 @@
    integer (c_int), parameter :: POP_CREATE_HOST_ONLY = 1
 
    ! mirrors `struct pop_config` field for field
-   integer (c_int), parameter :: POP_CONFIG_VERSION = 5
+   integer (c_int), parameter :: POP_CONFIG_VERSION = 6
 
    type, bind(C) :: pop_config
       integer (c_int) :: struct_version = POP_CONFIG_VERSION
@@ -52,6 +52,14 @@
       integer (c_int) :: reserved_i(1) = 0
       real (c_double) :: ah_bkg_bottom = 0.0_c_double                           ! hmix_gm_nml ah_bkg_bottom
       real (c_double) :: kappa_depth_1 = 0.0_c_double, kappa_depth_2 = 0.0_c_double, kappa_depth_scale = 0.0_c_double   ! gm_kappa_type = 2
+      ! layout 6: hmix_aniso_nml (hmix_aniso.F90:167-224), read with hmix_momentum = 3 only; 0 = the code default (include/pop_amd.h)
+      integer (c_int) :: aniso_alignment = 0                                    ! hmix_alignment_choice: 0 'grid', 1 'east' ('flow' is refused)
+      integer (c_int) :: lvariable_hmix_aniso = 0, lsmag_aniso = 0, vconst_5 = 0
+      real (c_double) :: visc_para = 0.0_c_double, visc_perp = 0.0_c_double
+      real (c_double) :: c_para = 0.0_c_double, c_perp = 0.0_c_double, u_para = 0.0_c_double, u_perp = 0.0_c_double
+      real (c_double) :: vconst_1 = 0.0_c_double, vconst_2 = 0.0_c_double, vconst_3 = 0.0_c_double, vconst_4 = 0.0_c_double
+      real (c_double) :: vconst_6 = 0.0_c_double, vconst_7 = 0.0_c_double
+      real (c_double) :: smag_lat = 0.0_c_double, smag_lat_fact = 0.0_c_double, smag_lat_gauss = 0.0_c_double
    end type pop_config
 
    ! mirrors `struct pop_grid_input`: the records of horiz_grid_file / topography_file (grid.F90:1314-1542, 2025-2107)
@@ -76,6 +84,7 @@
       integer (c_int) :: pcsi_two_step
       integer (c_int) :: block_sums_relay
       integer (c_int) :: pcsi_evp_fused
+      integer (c_int) :: aniso_side
    end type pop_tuning
 
    type (c_ptr), save :: pop_ctx = c_null_ptr   ! the one model instance of this task
