@@ -25,1530 +25,12 @@
 
 using namespace pop;
 
-#define HIPCHK(ctx, call)                                                                       \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess) {                                                                     \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                           \
-      return 1;                                                                                 \
-    }                                                                                           \
-  } while (0)
-
-struct PhaseTimer { double ms = 0; int calls = 0; };
-
-struct DevPeer { int rank; int *send_src = nullptr, *recv_dst = nullptr; int nsend = 0, nrecv = 0; };
-
-struct pop_ctx {
-  HostModel h;
-  bool host_only = true;
-  std::string err;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  DevGrid g{};
-  std::map<std::string, double *> d2;     // device 2-D fields (local blocks)
-  std::map<std::string, int *> di2;
-  std::vector<void *> allocs;
-  // prognostic state, physical slots; logical levels via oldt/curt/newt
-  double *TR[MAXNT][3] = {}, *U[3] = {}, *V[3] = {}, *RHO[3] = {};
-  double *PS[3] = {}, *GX[3] = {}, *GY[3] = {}, *UB[3] = {}, *VB[3] = {};
-  double *PGUESS = nullptr, *FW = nullptr, *FW_OLD = nullptr, *SHF_QSW = nullptr, *CHL = nullptr;
-  double *STF[MAXNT] = {}, *TFW[MAXNT] = {}, *KPP_SRC[MAXNT] = {}, *VDC[2] = {}, *VVC = nullptr;
-  double *DH = nullptr, *DHU = nullptr, *ZX = nullptr, *ZY = nullptr, *UH = nullptr, *VH = nullptr;
-  double *W3 = nullptr, *W4 = nullptr, *RHS = nullptr, *centerWgt = nullptr;
-  double *E3 = nullptr, *F3 = nullptr, *S3a = nullptr, *S3b = nullptr, *S3c = nullptr, *S3d = nullptr;
-  // del4: the first Laplacians need only the mix-time fields, so they run on a side stream beside the vertical-mixing
-  // coefficients (own output buffers d2t / d2u instead of the shared scratch; POP_DEL4_SIDE=0: in line, scratch reused)
-  double *d2t[2] = {nullptr, nullptr}, *d2u[2] = {nullptr, nullptr};
-  // hmix_momentum = 3: the friction hdiffu_aniso forms (3-D, read by the momentum kernel) and the variable viscosities F_PARA, F_PERP
-  double *HDU = nullptr, *HDV = nullptr, *FPARA = nullptr, *FPERP = nullptr;
-  // del4: the tracer kernel of a step also forms the first Laplacian of its CURRENT tracers -- the mix-time field of the next
-  // (leapfrog) step -- from the tile it has in LDS; d2t_next receives it, d2t_next_slot is the time slot it belongs to
-  double *d2t_next[2] = {nullptr, nullptr};
-  bool d2t_next_valid = false; int d2t_next_slot = -1;
-  // the ghost cells of the tracers in a time slot are copies of their source cells (set-up and every halo update leave them so;
-  // a caller's pop_set_field / a restart file may not): only then is the halo update of the field formed ahead the same arithmetic
-  // as k_del4_d2t on the ghost ring
-  bool tr_ghosts_ok[3] = {true, true, true};
-  // the same for the velocity (k_momentum_rhs_lds forms k_del4_d2u's field for the next step)
-  double *d2u_next[2] = {nullptr, nullptr};
-  bool d2u_next_valid = false; int d2u_next_slot = -1;
-  bool uv_ghosts_ok[3] = {true, true, true};
-  bool d2t_last_formed = false, d2u_last_formed = false;   // did the last tracer / momentum launch write the next step's field (bench accounting)
-  hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_d2t = nullptr, ev_d2u = nullptr, ev_vmixu = nullptr;
-  bool mom_side = false;   // phase_hmix_momentum on the side stream: del4 with side_del4; anis unless pop_tuning.aniso_side = 0
-  bool side_del4 = false, vmixu_pending = false, btrop_added = false, vmixu_deferred = false;   // implicit vertical mixing of U,V in flight on the side stream
-  double *HBLT = nullptr, *HMXL = nullptr, *HMXL_DR = nullptr;
-  MixDev mix{};
-  // KPP look-ahead: the vertical-mixing coefficients of the NEXT step depend only on this step's curtime fields (its
-  // mixtime on a leapfrog step), so pop_step computes them on a third stream beside the barotropic solver (VALU-bound
-  // work beside bandwidth-bound work) into a second set of output fields; the next step swaps the sets in.
-  bool vdc_shared = false;
-  bool kpp_src_user = false;   // the caller wrote KPP_SRC (pop_set_field): read it at every level until KPP has run again
-  bool src_dirty = true, src_dirty_alt = true;   // KPP_SRC / KPPa may hold non-zeros below the KBL stored with them: the next evaluation into that set clears every level
-  double *VDCa[2] = {nullptr, nullptr}, *VVCa = nullptr, *KPPa[MAXNT] = {}, *HBLTa = nullptr, *HMXLa = nullptr, *HMXL_DRa = nullptr;
-  int *KBL = nullptr, *KBLa = nullptr;   // KBL that belongs to KPP_SRC / KPPa (the tracer kernel reads KPP_SRC down to it)
-  hipStream_t ahead = nullptr; hipEvent_t ev_ahead_fork = nullptr, ev_ahead = nullptr;
-  bool ahead_enabled = false, ahead_valid = false; int ahead_slot = -1;
-  // solver
-  double *R = nullptr, *S0 = nullptr, *S1 = nullptr, *Q = nullptr, *Z = nullptr, *AZ = nullptr;
-  double *partial = nullptr, *blocksum = nullptr;
-  SolverScalars *sc = nullptr;
-  int *gid = nullptr, *srcmap = nullptr, *iota = nullptr, *loc_of_gid = nullptr;
-  std::vector<int> opre_host;
-  int *red_act = nullptr, *red_cnt = nullptr; int red_nact = 0;                // chunks with an ocean cell (fused solver launches, land elimination)
-  SolverScalars *host_sc = nullptr;                       // pinned
-  double *host_rr = nullptr;                              // pinned ring of (r,r) check results (k_rr_total)
-  hipEvent_t chk_ev[4] = {};                              // one event per check interval in flight
-  std::vector<std::pair<double *, hipGraphExec_t>> graphs;  // fused-solver interval graphs, keyed by solution array
-  bool no_graph = false, fused_ok = false, evp_fused_ok = false, replicated = false, grid_from_input = false;
-  // land elimination: the first land_full_steps steps after set-up / a restart / a new state run every workgroup (they write
-  // the state-independent values of the land tiles), later steps skip workgroups without an ocean cell (DevGrid::skip)
-  bool land_skip = true; int land_full_steps = 4, full_left = 4, full_seen = 0; double land_fraction = 0.0;
-  bool fpcg_one_cell = false;   // POP_FPCG_B2=0: one cell per thread in step B of the fused pcg even on large grids
-  bool force_presum = false;
-  // the resident pcg of small grids (kernels_pcg_persist.hpp; pop_tuning.pcg_persist): one plan per solver view
-  struct PersistPlan {
-    const void *key = nullptr; bool ok = false; std::string why;
-    int CP = 0, nwg = 0, nwin_max = 0, nslots = 0;
-    int *own_q = nullptr, *halo_off = nullptr, *halo_q = nullptr; unsigned short *nbr = nullptr;
-    PWord *W = nullptr;                                    // [2][nslots] partial words + [2][ncell] z words
-    double *X0 = nullptr;                                  // copy of the first guess (a solve that gave up is repeated by the two-launch form)
-  };
-  unsigned long long persist_epoch = 0;                    // high half of the tags of the next resident solve (never repeats)
-  std::vector<PersistPlan> persist;
-  std::vector<int> h_srcmap;                               // host copy of srcmap (local view)
-  double *persist_out = nullptr;                           // pinned: iterations, (r,r), status, checks
-  int persist_used = 0;                                    // the last pcg solve ran as the resident launch
-  int persist_gave_up = 0;                                 // resident solves that gave up a wait (then never used again in this model)
-  int red_active_total = 0;                                // fused solver kernels: chunks that have work, summed over the local blocks
-  int persist_nwg = 0, persist_cp = 0;                     // shape of the last resident launch
-  bool pcsi_two_cell = false;   // fused P-CSI step with two cells per thread (large grids, even row pitch; POP_PCSI_STEP2=0|1)
-  bool pcsi_two_step = false;   // ... and two iterations per launch (k_pcsi_step_x2; pop_tuning.pcsi_two_step)
-  bool pcsi_two_step_dist = false;   // ... with blocks spread over ranks
-  double *pcsi_raw = nullptr;   // the residual of the pair before a check (k_pcsi_step_x2<true> -> k_pcsi_rr_chunks)
-  int *pcsi_jfold = nullptr;    // tripole: per local block, the first array row beyond the fold (PcsiArgs::jfold)
-  bool pcsi_evp_fused = false;  // P-CSI + EVP: iteration and sub-block solves in one launch (k_pcsi_evp_step; pop_tuning.pcsi_evp_fused)
-  bool reg_thomas_t = true;
-  int trc_lds_rows = 4;                                    // tracer RHS (centred advection): LDS tile rows, 0 = direct loads
-  int mom_lds_rows = 4;                                    // momentum RHS: LDS tile rows (0 = direct-load kernel)
-  bool reg_thomas = true;                                  // column-in-registers Thomas kernels (km = 60, 62)
-  SolveView gv{};                                         // replicated barotropic mode: all blocks
-  double *gTAREA = nullptr; int *gKMT = nullptr;
-  int nchunk = 0, numIterations = 0;
-  double rmsResidual = 0.0;
-  // halo plan on device
-  int *copy_dst = nullptr, *copy_src = nullptr, *fill_dst = nullptr;
-  int ncopy = 0, nfill = 0;
-  std::vector<DevPeer> peers;
-  // all peers concatenated (one pack / unpack launch per halo update)
-  int *sa_src = nullptr, *sa_start = nullptr, *sa_cnt = nullptr, *ra_dst = nullptr, *ra_start = nullptr, *ra_cnt = nullptr;
-  int nsend_all = 0, nrecv_all = 0;
-  // fused distributed solvers: per-cell send entries / receive slots (FusedArgs::sendmap, rmap), nz = 1 message order
-  int *sendmap = nullptr, *send_off = nullptr, *send_slot = nullptr, *rmap = nullptr;
-  int max_blocks_per_rank = 0;                             // over all ranks: choices between collective code paths must not depend on the rank
-  bool halo_ns_only = false;                               // every ghost cell owned by another rank lies in a ghost ROW (j-band shards)
-  pop_exchange_fn xchg_side = nullptr;                     // the same exchange on the communication stream (own communicator), or null
-  hipStream_t comm_side = nullptr;                         // stream of those exchanges (not `side`: impvmixu runs there beside the solver)
-  hipEvent_t ev_sa = nullptr, ev_sx = nullptr;            // solver: z packed (launch stream) / z received (side stream)
-  long long solver_ops = 0, solver_enq = 0;               // stream operations / iterations enqueued by the last distributed solve (incl. look-ahead)
-  // tripole northern boundary, per field location (single rank)
-  int *tp_dst[5] = {}, *tp_a[5] = {}, *tp_b[5] = {}; int tp_n[5] = {}; double *tp_buf = nullptr;
-  // comm hooks
-  double *sendbuf = nullptr, *recvbuf = nullptr, *redbuf = nullptr;
-  long long comm_doubles = 0, red_doubles = 0;
-  pop_exchange_fn xchg = nullptr;
-  pop_allreduce_fn allred = nullptr;
-  void *comm_user = nullptr;
-  EvpDev evp{}; bool use_evp = false;                                                // EVP block preconditioner (preconditioner_choice = 1)
-  double *pcsi_omega = nullptr; int *pcsi_base = nullptr; double pcsi_csy = 0;        // P-CSI: omega_k table, interval base
-  std::vector<std::pair<std::pair<double *, int>, hipGraphExec_t>> pcsi_graphs;   // keyed by (solution array, variant)
-  double rf_S[MAXNT] = {}, rf_S_prev[MAXNT] = {}; bool rf_S_prev_valid[MAXNT] = {};   // Robert filter
-  Upw3Dev upw3{};                                          // tadvect = 2
-  LwDev lw{};                                              // tadvect = 3 (lw_lim): flux-velocity and work fields
-  GmDev gm{};                                              // hmix_tracer = 3 (gm): slopes, tapered diffusivities, GTK
-  RcclTransport *rccl_tr = nullptr;                       // in-library RCCL transport (pop_comm_init_rccl)
-  // time stepping
-  int oldt = 0, curt = 1, newt = 2, mixt = 1;
-  int first_step = 1, leapfrogts = 1, f_euler_ts = 0, avg_ts = 0, nsteps_total = 0, nsteps_this_interval = 0;
-  int eod = 0, eod_last = 0;                               // the step ends a day / the previous one did (time_management.F90:1809, 3586-3592; runs that start at midnight)
-  double c2dtt = 0, c2dtu = 0, c2dtp = 0, beta = 0;
-  std::map<std::string, PhaseTimer> timers;
-  // the barotropic solve bracketed by two events on the launch stream, read back one step later (no synchronisation inside the
-  // step): totals since the last pop_timers_reset / "solver_ms_reset" for the bench's per-iteration figure
-  hipEvent_t ev_solve[2] = {nullptr, nullptr}; bool solve_pending = false; int solve_iters_pending = 0;
-  double solver_ms_total = 0.0; long long solver_iters_total = 0, solver_calls_total = 0;
-  bool timing = false;
-  bool phase_timing = false;   // inside pop_time_phase: kernels only
-  double *op_scratch = nullptr;   // pop_operator_host: four block-sized 2-D arrays
-  bool prio_on = false; int prio_least = 0;   // stream priorities in use; the lowest one
-};
+#include "pop_ctx.hpp"
+#include "launch_halo.hpp"
+#include "launch_solvers.hpp"
 
 namespace {
 
-template <class T>
-int dev_alloc(pop_ctx *c, T **p, size_t n, bool zero = true) {
-  void *v = nullptr;
-  HIPCHK(c, hipMalloc(&v, std::max<size_t>(n, 1) * sizeof(T)));
-  c->allocs.push_back(v);
-  if (zero) HIPCHK(c, hipMemset(v, 0, std::max<size_t>(n, 1) * sizeof(T)));
-  *p = (T *)v;
-  return 0;
-}
-template <class T>
-int dev_upload(pop_ctx *c, T **p, const T *src, size_t n) {
-  if (dev_alloc(c, p, n, false)) return 1;
-  HIPCHK(c, hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
-}
-// extract the local blocks of an all-blocks host field
-template <class T>
-std::vector<T> local_part(const HostModel &h, const std::vector<T> &all) {
-  std::vector<T> out(h.n2 * h.nblocks);
-  for (int lb = 0; lb < h.nblocks; ++lb)
-    std::copy(all.begin() + (size_t)(h.local_ids[lb] - 1) * h.n2, all.begin() + (size_t)h.local_ids[lb] * h.n2, out.begin() + (size_t)lb * h.n2);
-  return out;
-}
-
-// the same for an all-blocks 3-D host field (nxb, nyb, km, nblocks_tot)
-std::vector<double> local_part3(const HostModel &h, const std::vector<double> &all) {
-  std::vector<double> out(h.n3 * h.nblocks);
-  for (int lb = 0; lb < h.nblocks; ++lb)
-    std::copy(all.begin() + (size_t)(h.local_ids[lb] - 1) * h.n3, all.begin() + (size_t)h.local_ids[lb] * h.n3, out.begin() + (size_t)lb * h.n3);
-  return out;
-}
-
-// column kernels: one wave per workgroup; tile order per kernels_common.hpp col_setup
-dim3 grid_cols(const pop_ctx *c) {
-  if (c->g.xcd_remap == 2) return dim3(tile_grid_x(c->g.nxb, c->g.nyb, POP_COL_THREADS, 1), c->g.nblocks);
-  return dim3(col_grid(c->g, POP_COL_THREADS), c->g.nblocks);
-}
-dim3 block_stencil() { return dim3(POP_COL_THREADS, 1); }
-dim3 grid_stencil(const pop_ctx *c) { return grid_cols(c); }
-dim3 grid_2d(const pop_ctx *c) { return dim3(red_grid_x(c->g), c->g.nblocks); }
-dim3 grid_3d(const pop_ctx *c) { return dim3((c->g.n2 + 255) / 256, c->g.km, c->g.nblocks); }
-
-StepParams step_params(const pop_ctx *c) {
-  const pop_config &cf = c->h.c;
-  StepParams s{};
-  s.c2dtu = c->c2dtu; s.c2dtp = c->c2dtp; s.beta = c->beta; s.gamma = 1.0 - 2.0 * (1.0 / 3.0);
-  s.dtp = c->h.dtp; s.grav = GRAV;
-  s.am = cf.am; s.ah = cf.ah; s.bottom_drag = cf.bottom_drag;
-  s.const_vvc = cf.const_vvc; s.const_vdc = cf.const_vdc; s.convect_diff = cf.convect_diff; s.convect_visc = cf.convect_visc;
-  s.aidif = cf.aidif;
-  s.rich_bckgrnd_vvc = cf.rich_bckgrnd_vvc; s.rich_bckgrnd_vdc = cf.rich_bckgrnd_vdc; s.rich_mix = cf.rich_mix;
-  s.leapfrogts = c->leapfrogts; s.pavg = (cf.lpressure_avg && c->leapfrogts) ? 1 : 0;
-  s.impcor = cf.impcor; s.reset_to_freezing = cf.reset_to_freezing;
-  s.nvdc = (cf.vmix_choice == 3) ? 2 : 1;
-  return s;
-}
-
-struct ScopedPhase {   // optional HIP-event timing of a phase on the launch stream
-  pop_ctx *c; const char *name; hipEvent_t e0 = nullptr, e1 = nullptr;
-  ScopedPhase(pop_ctx *c_, const char *n) : c(c_), name(n) {
-    if (c->timing) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, c->stream); }
-  }
-  ~ScopedPhase() {
-    if (c->timing) {
-      hipEventRecord(e1, c->stream); hipEventSynchronize(e1);
-      float ms = 0; hipEventElapsedTime(&ms, e0, e1);
-      auto &t = c->timers[name]; t.ms += ms; t.calls += 1;
-      hipEventDestroy(e0); hipEventDestroy(e1);
-    }
-  }
-};
-
-// ---------------------------------------------------------------------------------------------
-// halo update of a device-resident field with nz levels (mpi/POP_HaloMod.F90:1732-2071 2-D,
-// :2766-3211 3-D): local ghost copies + fills in one launch, then one packed message per peer
-// ---------------------------------------------------------------------------------------------
-// what the transport said about a failed exchange / all-reduce
-std::string tr_err(const pop_ctx *c) { return c->rccl_tr ? ": " + c->rccl_tr->err : std::string(" in the host callback"); }
-// remote part only: one pack launch, the exchange, one unpack launch
-int halo_remote(pop_ctx *c, double *F, int nz) {
-  if (c->peers.empty()) return 0;
-  const int n2 = c->g.n2;
-  if (!c->xchg || !c->sendbuf) { c->err = "halo_update: multi-rank run without pop_set_comm"; return 1; }
-  std::vector<int> peer; std::vector<long long> soff, scnt, roff, rcnt;
-  long long so = 0, ro = 0;
-  for (auto &p : c->peers) {
-    peer.push_back(p.rank); soff.push_back(so); scnt.push_back((long long)p.nsend * nz); roff.push_back(ro); rcnt.push_back((long long)p.nrecv * nz);
-    so += (long long)p.nsend * nz; ro += (long long)p.nrecv * nz;
-  }
-  if (so > c->comm_doubles || ro > c->comm_doubles) { c->err = "halo_update: comm buffer too small"; return 1; }
-  if (c->nsend_all) hipLaunchKernelGGL(k_halo_pack_all, dim3((c->nsend_all + 255) / 256, nz), dim3(256), 0, c->stream, (const double *)F, c->sa_src, c->sa_start, c->sa_cnt, c->nsend_all, c->sendbuf, nz, n2);
-  if (c->xchg(c->comm_user, (int)peer.size(), peer.data(), soff.data(), scnt.data(), roff.data(), rcnt.data())) {
-    c->err = "halo_update: exchange failed" + tr_err(c); return 1;
-  }
-  if (c->nrecv_all) hipLaunchKernelGGL(k_halo_unpack_all, dim3((c->nrecv_all + 255) / 256, nz), dim3(256), 0, c->stream, F, c->ra_dst, c->ra_start, c->ra_cnt, c->nrecv_all, (const double *)c->recvbuf, nz, n2);
-  return 0;
-}
-int halo_update(pop_ctx *c, double *F, int nz, double fill = 0.0, int loc = 0, int kind = 0) {
-  const int n2 = c->g.n2;
-  if (halo_remote(c, F, nz)) return 1;
-  const int nloc = c->ncopy + c->nfill;
-  if (nloc) hipLaunchKernelGGL(k_halo_local, dim3((nloc + 255) / 256, nz), dim3(256), 0, c->stream, F, c->copy_dst, c->copy_src, c->ncopy, c->fill_dst, c->nfill, fill, nz, n2);
-  if (c->h.c.ns_boundary == 2 && c->tp_n[loc]) {   // tripole northern boundary (mpi/POP_HaloMod.F90:1936-2050)
-    const int n = c->tp_n[loc];
-    if (nz > c->h.km + 2) { c->err = "halo_update: too many levels for the tripole buffer"; return 1; }
-    hipLaunchKernelGGL(k_tripole_eval, dim3((n + 255) / 256, nz), dim3(256), 0, c->stream, (const double *)F, c->tp_a[loc], c->tp_b[loc], n, c->tp_buf,
-                       kind == 0 ? 1.0 : -1.0, nz, n2);
-    hipLaunchKernelGGL(k_tripole_store, dim3((n + 255) / 256, nz), dim3(256), 0, c->stream, F, c->tp_dst[loc], n, (const double *)c->tp_buf, nz, n2);
-  }
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-// Several fields, one halo update: ONE message per neighbour rank carrying all of them (pack, exchange, unpack = three
-// stream operations whatever the number of fields) and one launch for the ghost copies / fills inside the rank.
-// Field by field the result is the one halo_update gives (same cells, same values).  fill value 0.
-// loc / kind: POP_HaloUpdate's fieldLoc / fieldKind (0 centre, 1 NE corner, 2 N face, 3 E face; 0 scalar, 1 vector); they matter on a tripole boundary only
-struct HaloItem { double *F; int nz; int loc = 0, kind = 0; };
-int halo_update_many(pop_ctx *c, const std::vector<HaloItem> &items) {
-  if (items.size() == 1 || items.size() > 8 || c->h.c.ns_boundary == 2 || tun_on(c->h.tun.halo_separate)) {
-    for (const HaloItem &it : items) if (halo_update(c, it.F, it.nz, 0.0, it.loc, it.kind)) return 1;
-    return 0;
-  }
-  HaloFields H{};
-  H.nf = (int)items.size();
-  int tot = 0;
-  for (int f = 0; f < H.nf; ++f) { H.F[f] = items[f].F; H.nz[f] = items[f].nz; H.lev0[f] = tot; tot += items[f].nz; }
-  H.nztot = tot;
-  const int n2 = c->g.n2;
-  if (!c->peers.empty()) {
-    if (!c->xchg || !c->sendbuf) { c->err = "halo_update: multi-rank run without pop_set_comm"; return 1; }
-    std::vector<int> peer; std::vector<long long> soff, scnt, roff, rcnt;
-    long long so = 0, ro = 0;
-    for (auto &p : c->peers) {
-      peer.push_back(p.rank); soff.push_back(so); scnt.push_back((long long)p.nsend * tot); roff.push_back(ro); rcnt.push_back((long long)p.nrecv * tot);
-      so += (long long)p.nsend * tot; ro += (long long)p.nrecv * tot;
-    }
-    if (so > c->comm_doubles || ro > c->comm_doubles) {   // buffers of an older host framework: field by field
-      for (const HaloItem &it : items) if (halo_update(c, it.F, it.nz)) return 1;
-      return 0;
-    }
-    if (c->nsend_all) hipLaunchKernelGGL(k_halo_pack_many, dim3((c->nsend_all + 255) / 256, tot), dim3(256), 0, c->stream, H, c->sa_src, c->sa_start, c->sa_cnt, c->nsend_all, c->sendbuf, n2);
-    if (c->xchg(c->comm_user, (int)peer.size(), peer.data(), soff.data(), scnt.data(), roff.data(), rcnt.data())) { c->err = "halo_update: exchange failed" + tr_err(c); return 1; }
-    if (c->nrecv_all) hipLaunchKernelGGL(k_halo_unpack_many, dim3((c->nrecv_all + 255) / 256, tot), dim3(256), 0, c->stream, H, c->ra_dst, c->ra_start, c->ra_cnt, c->nrecv_all, (const double *)c->recvbuf, n2);
-  }
-  const int nloc = c->ncopy + c->nfill;
-  if (nloc) hipLaunchKernelGGL(k_halo_local_many, dim3((nloc + 255) / 256, tot), dim3(256), 0, c->stream, H, c->copy_dst, c->copy_src, c->ncopy, c->fill_dst, c->nfill, 0.0, n2);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-// The same update in two halves around work that does not need the ghost cells of other ranks (north_star: "halo updates
-// ... overlapped with interior stencil work on a second HIP stream").  begin: ghost copies inside the rank, pack, and the
-// exchange on the communication stream (second communicator); end: unpack and the ghost copies again (corner ghosts
-// take values that just arrived; the others are rewritten with the same values).  Between the two the launch stream
-// may run anything that reads only cells this rank owns or ghosts with a source on this rank.
-bool halo_async_ok(const pop_ctx *c) {
-  return !c->peers.empty() && c->halo_ns_only && c->xchg_side && c->comm_side && c->h.c.ns_boundary != 2 && !tun_on(c->h.tun.halo_overlap_off);
-}
-struct HaloAsync { HaloFields H; int tot; };
-int halo_many_begin(pop_ctx *c, const std::vector<HaloItem> &items, HaloAsync &A) {
-  HaloFields &H = A.H;
-  H = HaloFields{};
-  H.nf = (int)items.size();
-  int tot = 0;
-  for (int f = 0; f < H.nf; ++f) { H.F[f] = items[f].F; H.nz[f] = items[f].nz; H.lev0[f] = tot; tot += items[f].nz; }
-  H.nztot = tot; A.tot = tot;
-  const int n2 = c->g.n2, nloc = c->ncopy + c->nfill;
-  std::vector<int> peer; std::vector<long long> soff, scnt, roff, rcnt;
-  long long so = 0, ro = 0;
-  for (auto &p : c->peers) {
-    peer.push_back(p.rank); soff.push_back(so); scnt.push_back((long long)p.nsend * tot); roff.push_back(ro); rcnt.push_back((long long)p.nrecv * tot);
-    so += (long long)p.nsend * tot; ro += (long long)p.nrecv * tot;
-  }
-  if (so > c->comm_doubles || ro > c->comm_doubles) { c->err = "halo_update: comm buffer too small"; return 1; }
-  if (nloc) hipLaunchKernelGGL(k_halo_local_many, dim3((nloc + 255) / 256, tot), dim3(256), 0, c->stream, H, c->copy_dst, c->copy_src, c->ncopy, c->fill_dst, c->nfill, 0.0, n2);
-  if (c->nsend_all) hipLaunchKernelGGL(k_halo_pack_many, dim3((c->nsend_all + 255) / 256, tot), dim3(256), 0, c->stream, H, c->sa_src, c->sa_start, c->sa_cnt, c->nsend_all, c->sendbuf, n2);
-  HIPCHK(c, hipEventRecord(c->ev_sa, c->stream));
-  HIPCHK(c, hipStreamWaitEvent(c->comm_side, c->ev_sa, 0));
-  if (c->xchg_side(c->comm_user, (int)peer.size(), peer.data(), soff.data(), scnt.data(), roff.data(), rcnt.data())) { c->err = "halo_update: exchange failed" + tr_err(c); return 1; }
-  HIPCHK(c, hipEventRecord(c->ev_sx, c->comm_side));
-  return 0;
-}
-int halo_many_end(pop_ctx *c, const HaloAsync &A) {
-  const int n2 = c->g.n2, nloc = c->ncopy + c->nfill;
-  HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_sx, 0));
-  if (c->nrecv_all) hipLaunchKernelGGL(k_halo_unpack_many, dim3((c->nrecv_all + 255) / 256, A.tot), dim3(256), 0, c->stream, A.H, c->ra_dst, c->ra_start, c->ra_cnt, c->nrecv_all, (const double *)c->recvbuf, n2);
-  if (nloc) hipLaunchKernelGGL(k_halo_local_many, dim3((nloc + 255) / 256, A.tot), dim3(256), 0, c->stream, A.H, c->copy_dst, c->copy_src, c->ncopy, c->fill_dst, c->nfill, 0.0, n2);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-// stage 2+3 of a reduction whose partials are already in c->partial
-template <int NF>
-int reduce_finish(pop_ctx *c, int mode) {
-  double *bs = c->blocksum;
-  if (c->h.nranks > 1) {
-    if (!c->allred || !c->redbuf) { c->err = "global sum: multi-rank run without pop_set_comm"; return 1; }
-    bs = c->redbuf;
-    hipLaunchKernelGGL(k_block_sums_global<NF>, dim3(c->h.nblocks_tot), dim3(POP_RED_THREADS), 0, c->stream, c->partial, c->nchunk, c->loc_of_gid, bs);
-  } else hipLaunchKernelGGL(k_block_sums<NF>, dim3(c->g.nblocks), dim3(POP_RED_THREADS), 0, c->stream, c->partial, c->nchunk, c->gid, bs);
-  if (c->h.nranks > 1 && c->allred(c->comm_user, 0, (long long)NF * c->h.nblocks_tot)) { c->err = "global sum: allreduce callback failed" + tr_err(c); return 1; }
-  hipLaunchKernelGGL(k_finalize<NF>, dim3(1), dim3(1), 0, c->stream, bs, c->h.nblocks_tot, c->sc, mode);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-int read_scalars(pop_ctx *c, SolverScalars *out) {
-  HIPCHK(c, hipMemcpyAsync(out, c->sc, sizeof(SolverScalars), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
-}
-
-SolverArgs solver_args(pop_ctx *c) {
-  SolverArgs a{};
-  a.X = c->PS[c->newt]; a.R = c->R; a.S0 = c->S0; a.S1 = c->S1; a.Q = c->Q; a.Z = c->Z; a.AZ = c->AZ;
-  a.Bv = c->RHS; a.C = c->centerWgt; a.partial = c->partial; a.sc = c->sc;
-  return a;
-}
-
-// preconditioner() with preconditionerChoice = 'evp' (:2331-2366): PX <- sub-block solves of X on the physical cells
-// residual: X is a residual of a solver (zero on land): sub-blocks without an ocean cell are not read (k_evp_apply_wave3<true>)
-int evp_apply(pop_ctx *c, const double *X, double *PX, bool residual = true) {
-  const int wave = tun_or(c->h.tun.evp_wave, 3);   // 3 (default): wavefronts, operands in registers, every load up front; 2: the same with the loads behind their conditions; 1: wavefronts, operands in LDS; 0: a thread per sub-block
-  if (wave == 3 && c->evp.C0 && residual)
-    hipLaunchKernelGGL(k_evp_apply_wave3<true>, dim3((unsigned)((c->evp.S + POP_EVP_SB - 1) / POP_EVP_SB)), dim3(64), 0, c->stream, c->evp, c->g.nxb, X, PX);
-  else if (wave == 3 && c->evp.C0)
-    hipLaunchKernelGGL(k_evp_apply_wave3<false>, dim3((unsigned)((c->evp.S + POP_EVP_SB - 1) / POP_EVP_SB)), dim3(64), 0, c->stream, c->evp, c->g.nxb, X, PX);
-  else if (wave == 2 && c->evp.C0)
-    hipLaunchKernelGGL(k_evp_apply_wave2, dim3((unsigned)((c->evp.S + POP_EVP_SB - 1) / POP_EVP_SB)), dim3(64), 0, c->stream, c->evp, c->g.nxb, X, PX);
-  else if (wave != 0)   // anti-diagonal wavefronts: eight lanes per sub-block, eight sub-blocks per wave
-    hipLaunchKernelGGL(k_evp_apply_wave, dim3((unsigned)((c->evp.S + POP_EVP_SB - 1) / POP_EVP_SB)), dim3(64), 0, c->stream, c->evp, c->g.nxb, X, PX);
-  else
-    hipLaunchKernelGGL(k_evp_apply, dim3((unsigned)((c->evp.S + POP_EVP_THREADS - 1) / POP_EVP_THREADS)), dim3(POP_EVP_THREADS), 0, c->stream,
-                       c->evp, c->g.nxb, X, PX);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-// POP_SolversRun -> pcg (POP_SolversMod.F90:1255-1503), diagonal or EVP preconditioner
-int solver_pcg(pop_ctx *c) {
-  const pop_config &cf = c->h.c;
-  const dim3 G = grid_2d(c), B(POP_RED_THREADS);
-  SolverScalars init{}; init.eta0 = 1.0;
-  HIPCHK(c, hipMemcpyAsync(c->sc, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->S0, 0, sizeof(double) * c->g.n2 * c->g.nblocks, c->stream));
-  SolverArgs a = solver_args(c);
-  hipLaunchKernelGGL(k_residual<false>, grid_2d(c), B, 0, c->stream, c->g, a);
-  if (halo_update(c, c->R, 1)) return 1;
-  c->numIterations = cf.max_iterations;
-  double rr = 0.0;
-  bool pending = false;   // x,r update of the previous iteration not yet applied
-  for (int m = 1; m <= cf.max_iterations; ++m) {
-    a = solver_args(c);
-    if (c->use_evp) {   // :1322-1362: z = M^-1 r by sub-block solves, (r,z), halo of z
-      if (pending) hipLaunchKernelGGL(k_pcg_xr, G, B, 0, c->stream, c->g, a);
-      if (evp_apply(c, c->R, c->Z)) return 1;
-      hipLaunchKernelGGL(k_dot_partial, G, B, 0, c->stream, c->g, (const double *)c->R, (const double *)c->Z, c->g.mMask, c->partial);
-      if (halo_update(c, c->Z, 1)) return 1;
-    } else if (pending) hipLaunchKernelGGL(k_pcg_a<true>, G, B, 0, c->stream, c->g, a);
-    else hipLaunchKernelGGL(k_pcg_a<false>, G, B, 0, c->stream, c->g, a);
-    if (reduce_finish<1>(c, FIN_PCG_RZ)) return 1;
-    hipLaunchKernelGGL(k_pcg_b, G, B, 0, c->stream, c->g, a);
-    std::swap(c->S0, c->S1);
-    if (halo_update(c, c->Q, 1)) return 1;
-    if (reduce_finish<1>(c, FIN_PCG_SQ)) return 1;
-    pending = true;
-    if (m % cf.convergence_check_freq == 0) {
-      a = solver_args(c);
-      hipLaunchKernelGGL(k_pcg_xr, G, B, 0, c->stream, c->g, a);
-      pending = false;
-      hipLaunchKernelGGL(k_residual<true>, grid_2d(c), B, 0, c->stream, c->g, a);
-      if (halo_update(c, c->R, 1)) return 1;
-      if (reduce_finish<1>(c, FIN_RR)) return 1;
-      SolverScalars s;
-      if (read_scalars(c, &s)) return 1;
-      rr = s.rr;
-      if (rr < c->h.convergenceCriterion) { c->numIterations = m; break; }
-    }
-  }
-  if (pending) { a = solver_args(c); hipLaunchKernelGGL(k_pcg_xr, G, B, 0, c->stream, c->g, a); }
-  c->rmsResidual = std::sqrt(rr * c->h.residualNorm);
-  HIPCHK(c, hipGetLastError());
-  if (c->numIterations == cf.max_iterations && c->h.convergenceCriterion != 0.0) { c->err = "POP_SolversPCG: solver not converged"; return 2; }
-  return 0;
-}
-
-// pcg, fused form: two launches per iteration, halo folded into the matvec through srcmap, final
-// reduction stage recomputed by the consumer kernel, and one hipGraph replay per
-// convergenceCheckFreq iterations (same arithmetic and summation order as solver_pcg).  It runs on a
-// SolveView: the rank's own blocks (single rank), or -- replicated barotropic mode -- every block
-// of the decomposition on every rank.
-// which forms of step A / step B the fused pcg launches (launch_fpcg_a / launch_fpcg_b)
-static bool fpcg_pair_ok(const pop_ctx *c, const SolveView &v, const FusedArgs &a) {
-  return v.g.red_act && a.presummed && !a.sendmap && (v.g.red_nact % 16) == 0 && !c->fpcg_one_cell && !tun_off(c->h.tun.fpcg_a_pair);
-}
-static bool fpcg_two_ok(const pop_ctx *c, const SolveView &v, const FusedArgs &a) {
-  return a.presummed && (v.g.nxb & 1) == 0 && !v.g.red_tiles && !c->fpcg_one_cell;
-}
-FusedArgs fused_args(pop_ctx *c, const SolveView &v) {
-  FusedArgs a{};
-  a.X = v.X; a.R = v.R; a.Z = v.Z; a.S0 = v.S0; a.S1 = v.S1; a.Q = v.Q;
-  a.Bv = v.RHS; a.C = v.C; a.partA = v.partial; a.partB = v.partial + (size_t)v.nchunk * v.g.nblocks;
-  a.sc = c->sc; a.srcmap = v.srcmap; a.nchunk = v.nchunk; a.nblocks = v.g.nblocks;
-  a.bsA = v.blocksum + 2 * v.nblocks_tot; a.bsB = v.blocksum + 3 * v.nblocks_tot;
-  a.presummed = ((long long)v.nchunk * v.g.nblocks > 2048 || c->force_presum) ? 1 : 0;
-  return a;
-}
-// large grids: ordered block sums of a partial array between solver kernels (view-local block order)
-// (more than 64 terms per accumulator: the four-threads-per-accumulator form, one memory round trip instead of two or three)
-constexpr int POP_RELAY_LMAX = 36;
-static bool presum_relay(const pop_ctx *c, const SolveView &v) {
-  const int terms = (v.nchunk + POP_RED_THREADS - 1) / POP_RED_THREADS;
-  const int t = tun_or(c->h.tun.block_sums_relay, 1);   // 2: wherever it can run (the cross-check on small grids)
-  return (terms > 64 || t == 2) && (terms + 3) / 4 <= POP_RELAY_LMAX && t != 0;
-}
-void presum(pop_ctx *c, const SolveView &v, const double *partial, double *bs) {
-  if (presum_relay(c, v)) hipLaunchKernelGGL((k_block_sums_relay<1, POP_RELAY_LMAX>), dim3(v.g.nblocks), dim3(1024), 0, c->stream, partial, v.nchunk, (const int *)c->iota, bs);
-  else hipLaunchKernelGGL(k_block_sums<1>, dim3(v.g.nblocks), dim3(POP_RED_THREADS), 0, c->stream, partial, v.nchunk, c->iota, bs);
-}
-dim3 view_grid(const SolveView &v) { return dim3(red_grid_x(v.g), v.g.nblocks); }
-// r = b - A x (+ partial (r,r)) of the fused solvers: two cells per thread on large grids, else one
-template <bool WITH_RR>
-void launch_fresidual(pop_ctx *c, const SolveView &v, const FusedArgs &a) {
-  const dim3 G = view_grid(v);
-  if (a.presummed && (v.g.nxb & 1) == 0 && !v.g.red_tiles && !c->fpcg_one_cell)
-    hipLaunchKernelGGL(k_fresidual2<WITH_RR>, G, dim3(POP_RED_THREADS / 2), 0, c->stream, v.g, a);
-  else hipLaunchKernelGGL(k_fresidual<WITH_RR>, G, dim3(POP_RED_THREADS), 0, c->stream, v.g, a);
-}
-// step A of the fused pcg: two chunks per workgroup on compacted launches (single rank), else one
-void launch_fpcg_a(pop_ctx *c, const SolveView &v, const FusedArgs &a, bool update) {
-  const dim3 G = view_grid(v), B(POP_RED_THREADS);
-  const bool pair = fpcg_pair_ok(c, v, a);
-  if (pair) {
-    const dim3 GP(G.x / 2, G.y);
-    if (update) hipLaunchKernelGGL(k_fpcg_a_pair<true>, GP, B, 0, c->stream, v.g, a);
-    else hipLaunchKernelGGL(k_fpcg_a_pair<false>, GP, B, 0, c->stream, v.g, a);
-  } else if (update) hipLaunchKernelGGL(k_fpcg_a<true>, G, B, 0, c->stream, v.g, a);
-  else hipLaunchKernelGGL(k_fpcg_a<false>, G, B, 0, c->stream, v.g, a);
-}
-// step B of the fused pcg: two cells per thread on large grids (presummed block sums, even row pitch), else one
-// xupd: the pending x += alpha s of the previous iteration is applied here (k_fpcg_a<true> ran before and published alpha)
-void launch_fpcg_b(pop_ctx *c, const SolveView &v, const FusedArgs &a, bool xupd) {
-  const dim3 G = view_grid(v);
-  const bool two = fpcg_two_ok(c, v, a);
-  // (occupancy probe, profiles/r03_ab_b2_occupancy.txt: with dynamic LDS holding the kernel to 3 / 2 waves per SIMD instead of its 4
-  // the step costs +2.2 / +7.1 ms; the two-cell form needs 108 VGPRs, a 96- or 80-register budget spills 84 / 140 B)
-  if (two && xupd) hipLaunchKernelGGL(k_fpcg_b2<true>, G, dim3(POP_RED_THREADS / 2), 0, c->stream, v.g, a);
-  else if (two) hipLaunchKernelGGL(k_fpcg_b2<false>, G, dim3(POP_RED_THREADS / 2), 0, c->stream, v.g, a);
-  else if (xupd) hipLaunchKernelGGL(k_fpcg_b<true>, G, dim3(POP_RED_THREADS), 0, c->stream, v.g, a);
-  else hipLaunchKernelGGL(k_fpcg_b<false>, G, dim3(POP_RED_THREADS), 0, c->stream, v.g, a);
-}
-// one check interval: freq iterations, pending update, residual + (r,r) -> host
-int fused_interval(pop_ctx *c, SolveView &v, int freq, bool first_has_pending) {
-  const dim3 G = view_grid(v), B(POP_RED_THREADS);
-  bool pending = first_has_pending;
-  for (int it = 0; it < freq; ++it) {
-    FusedArgs a = fused_args(c, v);
-    launch_fpcg_a(c, v, a, pending);
-    if (a.presummed) presum(c, v, a.partA, (double *)a.bsA);
-    launch_fpcg_b(c, v, a, pending);
-    if (a.presummed) presum(c, v, a.partB, (double *)a.bsB);
-    std::swap(v.S0, v.S1);
-    pending = true;
-  }
-  FusedArgs a = fused_args(c, v);
-  hipLaunchKernelGGL(k_fpcg_xr, G, B, 0, c->stream, v.g, a);
-  launch_fresidual<true>(c, v, a);
-  // the view holds every block it sums (single rank or replicated), in block-id order
-  hipLaunchKernelGGL(k_rr_total, dim3(1), dim3(POP_RED_THREADS), 0, c->stream, (const double *)v.partial, v.nchunk, v.g.nblocks, c->sc, c->host_rr, c->h.convergenceCriterion);
-  return 0;
-}
-// Check intervals with one interval of look-ahead.  `enqueue(i)` puts interval i on the stream (a hipGraph replay or
-// plain launches) and returns whether it ends with a convergence check (k_rr_total).  The host keeps at most two checked
-// intervals in flight and examines them in order; the check that meets the criterion raises the device stop flag, so the
-// interval already enqueued behind it does nothing, and the GPU never idles while the host looks at a residual.
-// Returns the index of the converged interval or -1; rr = last residual seen.
-template <class Enqueue>
-int run_intervals(pop_ctx *c, int nint, Enqueue enqueue, double &rr, int &err) {
-  int next = 0, ring = 0, head = 0;          // ring: checks enqueued; head: checks examined
-  int idx[8] = {};
-  err = 0;
-  auto fill = [&]() {
-    while (next < nint && ring - head < 2) {
-      const int chk = enqueue(next);
-      if (chk < 0) { err = 1; return; }
-      if (chk) {
-        if (hipEventRecord(c->chk_ev[ring & 3], c->stream) != hipSuccess) { err = 1; return; }
-        idx[ring & 7] = next; ++ring;
-      }
-      ++next;
-    }
-  };
-  fill();
-  while (!err && head < ring) {
-    if (hipEventSynchronize(c->chk_ev[head & 3]) != hipSuccess) { err = 1; break; }
-    rr = c->host_rr[head & 7];
-    const int i = idx[head & 7];
-    ++head;
-    if (rr < c->h.convergenceCriterion) return i;
-    fill();
-  }
-  return -1;
-}
-
-// ---- the resident pcg of small grids (kernels_pcg_persist.hpp) ------------------------------------------------------------------
-// Plan of one view: which chunks a workgroup owns, the window index of every stencil neighbour, the halo cells.  Built on the host
-// from the view's source map (ghost -> source cell, -1 = fill), so block boundaries inside the view, the cyclic wrap, closed
-// boundaries and a tripole fold need no case of their own.  Returns nullptr (with the reason kept) when the view does not qualify.
-static pop_ctx::PersistPlan *persist_plan(pop_ctx *c, const SolveView &v) {
-  for (auto &p : c->persist) if (p.key == (const void *)v.srcmap) return p.ok ? &p : nullptr;
-  c->persist.emplace_back();
-  pop_ctx::PersistPlan &pl = c->persist.back();
-  pl.key = (const void *)v.srcmap;
-  const HostModel &h = c->h;
-  const int n2 = (int)h.n2, nxb = h.nxb, nchunk = v.nchunk, nb = v.g.nblocks, nslots = nchunk * nb;
-  const bool global = v.srcmap != c->srcmap;                // the replicated view holds every block of the decomposition
-  auto refuse = [&](const char *why) -> pop_ctx::PersistPlan * { pl.why = why; return nullptr; };
-  if (nb * ((nchunk + POP_RED_THREADS - 1) / POP_RED_THREADS) > POP_PERSIST_MAXP) return refuse("too many partial slots per thread");
-  // chunks per workgroup: the smallest of 1 / 2 / 4 / 8 that needs at most 250 workgroups (one per CU: the waits need every workgroup
-  // resident).  gx1v7 in one block: 246 x 2 (10.7 us per iteration; 123 x 4: 12.0, 62 x 8: 14.1 on the same box, profiles/r04_ab_persist_shape.txt);
-  // gx1v7 in the eight 48-row bands of the 8-rank decomposition (replicated solve): 144 x 4.
-  // measurement only: pop_tuning.pcg_persist = 2 | 4 | 8 forces that many chunks per workgroup
-  std::vector<int> cand;
-  if (c->h.tun.pcg_persist == 2 || c->h.tun.pcg_persist == 4 || c->h.tun.pcg_persist == 8) { if ((nslots + c->h.tun.pcg_persist - 1) / c->h.tun.pcg_persist <= 250) cand.push_back(c->h.tun.pcg_persist); }
-  if (cand.empty())
-    for (int cp : {1, 2, 4, 8}) if ((nslots + cp - 1) / cp <= 250) { cand.push_back(cp); break; }
-  if (cand.empty()) return refuse("more than 2000 chunks");
-  const std::vector<int> sm = global ? global_srcmap(h) : c->h_srcmap;
-  if ((long long)sm.size() != (long long)n2 * nb) return refuse("source map size");
-  const int off[8] = {nxb, -nxb, 1, -1, nxb + 1, -nxb + 1, nxb - 1, -nxb - 1};
-  int CP = 0, nwg = 0, nwin_max = 0;
-  std::vector<int> own, hoff, hq;
-  std::vector<unsigned short> nbr;
-  const char *why = "";
-  for (int cp : cand) {
-    why = "";
-    nwg = (nslots + cp - 1) / cp; nwin_max = 0;
-    const int NOWN = cp * POP_RED_THREADS;
-    own.assign((size_t)nwg * NOWN, -1); hoff.assign(nwg + 1, 0); hq.clear();
-    nbr.assign((size_t)nwg * NOWN * 8, 0);
-    for (int w = 0; w < nwg && !*why; ++w) {
-      std::unordered_map<int, int> where;                    // cell -> window index
-      for (int u = 0; u < cp; ++u) {
-        const int slot = w * cp + u;
-        if (slot >= nslots) break;
-        const int b = slot / nchunk, ch = slot % nchunk;
-        const BlockInfo &B = h.all_blocks[global ? b : h.local_ids[b] - 1];
-        for (int t = 0; t < POP_RED_THREADS; ++t) {
-          const int p2 = ch * POP_RED_THREADS + t;
-          if (p2 >= n2) break;
-          const int i = p2 % nxb + 1, j = p2 / nxb + 1;
-          if (i < B.ib || i > B.ie || j < B.jb || j > B.je) continue;
-          own[(size_t)w * NOWN + u * POP_RED_THREADS + t] = b * n2 + p2;
-          where[b * n2 + p2] = u * POP_RED_THREADS + t;
-        }
-      }
-      const size_t h0 = hq.size();
-      for (int L = 0; L < NOWN; ++L) {
-        const int q = own[(size_t)w * NOWN + L];
-        if (q < 0) continue;
-        for (int n = 0; n < 8; ++n) {
-          const int m = sm[q + off[n]];
-          int idx;
-          if (m < 0) idx = -1;
-          else {
-            auto it = where.find(m);
-            if (it != where.end()) idx = it->second;
-            else { idx = NOWN + (int)(hq.size() - h0); where[m] = idx; hq.push_back(m); }
-          }
-          nbr[((size_t)w * NOWN + L) * 8 + n] = (unsigned short)(idx < 0 ? 0xFFFF : idx);
-        }
-      }
-      const int nhalo = (int)(hq.size() - h0), nwin = NOWN + nhalo + 1;
-      if ((nhalo + POP_RED_THREADS - 1) / POP_RED_THREADS > POP_PERSIST_MAXH) { why = "halo of a workgroup too large"; break; }
-      if (nwin >= 0xFFFF) { why = "window too large"; break; }
-      for (int L = 0; L < NOWN; ++L) for (int n = 0; n < 8; ++n) {
-        unsigned short &x = nbr[((size_t)w * NOWN + L) * 8 + n];
-        if (x == 0xFFFF) x = (unsigned short)(nwin - 1);     // the cell of zeros (fill value of closed boundaries)
-      }
-      hoff[w + 1] = (int)hq.size();
-      nwin_max = std::max(nwin_max, nwin);
-    }
-    if (!*why && (size_t)3 * nwin_max * sizeof(double) > 60000) why = "window does not fit the LDS budget";
-    if (!*why) { CP = cp; break; }
-  }
-  if (!CP) return refuse(why);
-  if (hq.empty()) hq.push_back(0);
-  if (dev_upload(c, &pl.own_q, own.data(), own.size()) || dev_upload(c, &pl.nbr, nbr.data(), nbr.size()) ||
-      dev_upload(c, &pl.halo_off, hoff.data(), hoff.size()) || dev_upload(c, &pl.halo_q, hq.data(), hq.size())) return nullptr;
-  const size_t nwords = 4 * (size_t)nslots + 2 * (size_t)n2 * nb;      // partials [2 buffers][2 fields (ChronGear)][nslots], then z [2][ncell]
-  if (nwords * sizeof(PWord) >= (1ULL << 32)) return refuse("exchange buffer beyond 32-bit offsets");
-  double *p = nullptr;
-  if (dev_alloc(c, &p, 2 * nwords)) return nullptr;          // zero-filled: tag 0 is never waited for (epochs start at 1)
-  pl.W = reinterpret_cast<PWord *>(p);
-  if (dev_alloc(c, &pl.X0, (size_t)n2 * nb)) return nullptr;
-  pl.CP = CP; pl.nwg = nwg; pl.nwin_max = nwin_max; pl.nslots = nslots; pl.ok = true;
-  return &pl;
-}
-int solver_pcg_persist(pop_ctx *c, SolveView &v, const pop_ctx::PersistPlan &pl) {
-  const pop_config &cf = c->h.c;
-  const long long ncell = (long long)v.g.n2 * v.g.nblocks;
-  PersistArgs a{};
-  a.X = v.X; a.Bv = v.RHS; a.C = v.C; a.WNo = v.g.WNo; a.WEa = v.g.WEa; a.WNE = v.g.WNE; a.mMask8 = v.g.mMask8;
-  a.nxb = v.g.nxb; a.nchunk = v.nchunk; a.nblocks = v.g.nblocks; a.nslots = pl.nslots; a.ncell = ncell;
-  a.own_q = pl.own_q; a.nbr = pl.nbr; a.halo_off = pl.halo_off; a.halo_q = pl.halo_q; a.W = pl.W;
-  a.epoch = (++c->persist_epoch) << 32;                    // tags of this solve: no word of an earlier solve can carry one of them
-  a.max_iter = cf.max_iterations; a.freq = cf.convergence_check_freq; a.criterion = c->h.convergenceCriterion; a.out = c->persist_out;
-  a.wait_ticks = 200000000ULL;                             // 2 s
-  HIPCHK(c, hipMemcpyAsync(pl.X0, v.X, sizeof(double) * ncell, hipMemcpyDeviceToDevice, c->stream));   // the first guess, should the solve have to be repeated
-  c->persist_out[0] = -1.0; c->persist_out[1] = 0.0; c->persist_out[2] = 0.0; c->persist_out[3] = 0.0;
-  const size_t lds = (size_t)3 * pl.nwin_max * sizeof(double);
-  const dim3 G(pl.nwg), B(POP_RED_THREADS);
-  switch (pl.CP) {
-    case 1: hipLaunchKernelGGL(k_pcg_persist<1>, G, B, lds, c->stream, a); break;
-    case 2: hipLaunchKernelGGL(k_pcg_persist<2>, G, B, lds, c->stream, a); break;
-    case 4: hipLaunchKernelGGL(k_pcg_persist<4>, G, B, lds, c->stream, a); break;
-    default: hipLaunchKernelGGL(k_pcg_persist<8>, G, B, lds, c->stream, a); break;
-  }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->chk_ev[0], c->stream));
-  HIPCHK(c, hipEventSynchronize(c->chk_ev[0]));
-  if (c->persist_out[2] != 0.0 || c->persist_out[0] < 0.0) {
-    char b[200];
-    snprintf(b, sizeof b, " [iterations %g, status %g, checks %g, %d workgroups x %d chunks, %d blocks]", c->persist_out[0], c->persist_out[2], c->persist_out[3], pl.nwg, pl.CP, v.g.nblocks);
-    c->err = std::string(c->persist_out[0] < 0.0 ? "resident pcg: the launch left no result" : "resident pcg: a wait for another workgroup's data gave up (kernels_pcg_persist.hpp)") + b;
-    return 3;
-  }
-  c->numIterations = (int)c->persist_out[0];
-  c->rmsResidual = std::sqrt(c->persist_out[1] * c->h.residualNorm);
-  c->persist_used = 1; c->persist_nwg = pl.nwg; c->persist_cp = pl.CP;
-  hipLaunchKernelGGL(k_halo_srcmap, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, c->stream, v.X, v.srcmap, ncell);
-  HIPCHK(c, hipGetLastError());
-  const bool conv = c->persist_out[3] > 0.0 && c->persist_out[1] < c->h.convergenceCriterion;
-  if (!conv && c->h.convergenceCriterion != 0.0) { c->err = "POP_SolversPCG: solver not converged"; return 2; }
-  return 0;
-}
-
-// the iterations of the fused ChronGear as one resident launch (k_cg_persist), after the start-up pass of solver_chrongear_fused
-int solver_cg_persist(pop_ctx *c, SolveView &v, const pop_ctx::PersistPlan &pl, const FusedArgs &fa) {
-  const pop_config &cf = c->h.c;
-  const long long ncell = (long long)v.g.n2 * v.g.nblocks;
-  CgPersistArgs ca{};
-  PersistArgs &a = ca.p;
-  a.X = v.X; a.Bv = v.RHS; a.C = v.C; a.WNo = v.g.WNo; a.WEa = v.g.WEa; a.WNE = v.g.WNE; a.mMask8 = v.g.mMask8;
-  a.nxb = v.g.nxb; a.nchunk = v.nchunk; a.nblocks = v.g.nblocks; a.nslots = pl.nslots; a.ncell = ncell;
-  a.own_q = pl.own_q; a.nbr = pl.nbr; a.halo_off = pl.halo_off; a.halo_q = pl.halo_q; a.W = pl.W;
-  a.epoch = (++c->persist_epoch) << 32;
-  a.max_iter = cf.max_iterations; a.freq = cf.convergence_check_freq; a.criterion = c->h.convergenceCriterion; a.out = c->persist_out;
-  a.wait_ticks = 200000000ULL;
-  ca.R = fa.R; ca.S = fa.S0; ca.Q = fa.Q; ca.A0R = fa.A0R; ca.sc = c->sc;
-  c->persist_out[0] = -1.0; c->persist_out[1] = 0.0; c->persist_out[2] = 0.0; c->persist_out[3] = 0.0;
-  HIPCHK(c, hipMemcpyAsync(pl.X0, v.X, sizeof(double) * ncell, hipMemcpyDeviceToDevice, c->stream));   // x after the start-up pass, should the iterations have to be repeated
-  const size_t lds = (size_t)3 * pl.nwin_max * sizeof(double);
-  const dim3 G(pl.nwg), B(POP_RED_THREADS);
-  switch (pl.CP) {
-    case 1: hipLaunchKernelGGL(k_cg_persist<1>, G, B, lds, c->stream, ca); break;
-    case 2: hipLaunchKernelGGL(k_cg_persist<2>, G, B, lds, c->stream, ca); break;
-    case 4: hipLaunchKernelGGL(k_cg_persist<4>, G, B, lds, c->stream, ca); break;
-    default: hipLaunchKernelGGL(k_cg_persist<8>, G, B, lds, c->stream, ca); break;
-  }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->chk_ev[0], c->stream));
-  HIPCHK(c, hipEventSynchronize(c->chk_ev[0]));
-  if (c->persist_out[2] != 0.0 || c->persist_out[0] < 0.0) {
-    char b[200];
-    snprintf(b, sizeof b, " [iterations %g, status %g, checks %g, %d workgroups x %d chunks, %d blocks]", c->persist_out[0], c->persist_out[2], c->persist_out[3], pl.nwg, pl.CP, v.g.nblocks);
-    c->err = std::string("resident ChronGear: a wait for another workgroup's data gave up (kernels_pcg_persist.hpp)") + b;
-    return 3;
-  }
-  c->numIterations = (int)c->persist_out[0];
-  c->rmsResidual = std::sqrt(c->persist_out[1] * c->h.residualNorm);
-  c->persist_used = 1; c->persist_nwg = pl.nwg; c->persist_cp = pl.CP;
-  hipLaunchKernelGGL(k_halo_srcmap, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, c->stream, v.X, v.srcmap, ncell);
-  HIPCHK(c, hipGetLastError());
-  const bool conv = c->persist_out[3] > 0.0 && c->persist_out[1] < c->h.convergenceCriterion;
-  if (!conv && c->h.convergenceCriterion != 0.0) { c->err = "POP_SolversChronGear: solver not converged"; return 2; }
-  return 0;
-}
-
-int solver_pcg_fused(pop_ctx *c, SolveView &v) {
-  const pop_config &cf = c->h.c;
-  c->persist_used = 0;
-  if (!tun_off(c->h.tun.pcg_persist) && !fused_args(c, v).presummed) {   // the rule: wherever the plan qualifies (small views); pop_tuning.pcg_persist = 0 switches it off
-    const pop_ctx::PersistPlan *pl = c->persist_gave_up ? nullptr : persist_plan(c, v);
-    if (pl) {
-      const int e = solver_pcg_persist(c, v, *pl);
-      if (e != 3) return e;
-      // the resident launch did not complete its exchanges (its header: several processes on one GPU): not again in this model; this
-      // solve is repeated from the same first guess with the two launches per iteration -- the same numbers
-      c->persist_gave_up += 1;
-      fprintf(stderr, "libpop_amd: %s -- continuing with the two-launch pcg\n", c->err.c_str());
-      c->err.clear();
-      HIPCHK(c, hipMemcpyAsync(v.X, pl->X0, sizeof(double) * v.g.n2 * v.g.nblocks, hipMemcpyDeviceToDevice, c->stream));
-    }
-  }
-  const dim3 G = view_grid(v), B(POP_RED_THREADS);
-  const int freq = cf.convergence_check_freq;
-  SolverScalars init{}; init.eta0 = 1.0;
-  HIPCHK(c, hipMemcpyAsync(c->sc, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(v.S0, 0, sizeof(double) * v.g.n2 * v.g.nblocks, c->stream));
-  launch_fresidual<false>(c, v, fused_args(c, v));
-  c->numIterations = cf.max_iterations;
-  double rr = 0.0;
-  const bool use_graph = (freq % 2 == 0) && !c->no_graph;
-  int m = 0, lerr = 0;
-  const int nint = cf.max_iterations / freq;
-  const int conv = run_intervals(c, nint, [&](int) -> int {
-    if (use_graph) {
-      // the graph is keyed by the solution array (the time-level rotation cycles three of them)
-      hipGraphExec_t exec = nullptr;
-      for (auto &g : c->graphs) if (g.first == v.X) exec = g.second;
-      if (!exec) {
-        hipGraph_t graph;
-        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return -1;
-        const int e = fused_interval(c, v, freq, false);
-        hipError_t ce = hipStreamEndCapture(c->stream, &graph);
-        if (e || ce != hipSuccess) return -1;
-        if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) return -1;
-        hipGraphDestroy(graph);
-        c->graphs.push_back({v.X, exec});
-      }
-      if (hipGraphLaunch(exec, c->stream) != hipSuccess) return -1;
-    } else if (fused_interval(c, v, freq, false)) return -1;
-    return 1;
-  }, rr, lerr);
-  if (lerr) { c->err = "fused pcg: interval launch failed"; return 1; }
-  if (conv >= 0) c->numIterations = (conv + 1) * freq;
-  m = nint * freq;
-  if (c->numIterations == cf.max_iterations && m < cf.max_iterations) {   // remainder without a check
-    bool pending = false;
-    for (; m < cf.max_iterations; ++m) {
-      FusedArgs a = fused_args(c, v);
-      launch_fpcg_a(c, v, a, pending);
-      if (a.presummed) presum(c, v, a.partA, (double *)a.bsA);
-      launch_fpcg_b(c, v, a, pending);
-      if (a.presummed) presum(c, v, a.partB, (double *)a.bsB);
-      std::swap(v.S0, v.S1);
-      pending = true;
-    }
-    if (pending) hipLaunchKernelGGL(k_fpcg_xr, G, B, 0, c->stream, v.g, fused_args(c, v));
-  }
-  // ghosts of the solution as POP_SolversRun leaves them (every ghost has a source inside the view)
-  const long long ncell = (long long)v.g.n2 * v.g.nblocks;
-  hipLaunchKernelGGL(k_halo_srcmap, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, c->stream, v.X, v.srcmap, ncell);
-  c->rmsResidual = std::sqrt(rr * c->h.residualNorm);
-  HIPCHK(c, hipGetLastError());
-  if (c->numIterations == cf.max_iterations && c->h.convergenceCriterion != 0.0) { c->err = "POP_SolversPCG: solver not converged"; return 2; }
-  return 0;
-}
-SolveView local_view(pop_ctx *c) {
-  SolveView v{};
-  v.g = c->g; v.X = c->PS[c->newt]; v.R = c->R; v.Z = c->Z; v.S0 = c->S0; v.S1 = c->S1; v.Q = c->Q;
-  v.RHS = c->RHS; v.C = c->centerWgt; v.partial = c->partial; v.blocksum = c->blocksum;
-  v.srcmap = c->srcmap; v.gid = c->gid; v.nchunk = c->nchunk; v.nblocks_tot = c->h.nblocks_tot;
-  return v;
-}
-// the same view for the fused pcg / ChronGear kernels: with land elimination active their launches cover only the chunks
-// that hold an ocean cell (DevGrid::red_act); the partials of the chunks left out are zeroed once per solve
-SolveView fused_view(pop_ctx *c) {
-  SolveView v = local_view(c);
-  if (c->g.skip && c->red_act) {
-    v.g.red_act = c->red_act; v.g.red_cnt = c->red_cnt; v.g.red_nact = c->red_nact;
-    hipMemsetAsync(v.partial, 0, (size_t)v.nchunk * v.g.nblocks * 2 * sizeof(double), c->stream);
-  }
-  return v;
-}
-// Replicated barotropic mode (small 2-D problems on several GPUs): the tropic distribution of the
-// reference (domain.F90:433-543, POP_RedistributeBlocks around the solve, POP_SolversMod.F90:390-417,
-// 481) taken to its limit -- every rank gathers RHS and the first guess of ALL blocks with one
-// all-reduce of disjoint contributions, runs the fused solver on the whole 2-D domain with no
-// per-iteration communication, and keeps its own blocks.  Arithmetic and iteration count equal the
-// single-rank run (same blocks, same b4b sums).
-// ---- fused solvers for blocks spread over ranks -------------------------------------------------------------------
-// Ghosts with a source on this rank are read there (srcmap); ghosts owned by another rank need ONE exchange per
-// iteration (z: the search direction and the solution at those ghosts are then advanced locally with the owner's
-// arithmetic, so they never travel).  The message is packed by the kernel that produces z (FusedArgs::sendmap) and read
-// in place from the receive buffer by the kernel that consumes it (rmap): no pack / unpack launches.  The dot products
-// go through the b4b block-sum vector (own blocks' ordered sums, zeros elsewhere) and an all-reduce.  Forming the
-// block sums in the producing kernel (last workgroup by atomic ticket) was measured and rejected: the agent-scope
-// release every workgroup needs costs 20 ns per workgroup (profiles/probes/ticket_probe.hip: 77-88 us against 10 us
-// for the two launches at 4 224 workgroups).
-//   pcg       : k_fpcg_a(+pack) | block sums | all-reduce (launch stream)  ||  exchange z (side stream, own communicator)
-//               k_fpcg_b(reads rbuf) | block sums | all-reduce            = 7 operations, 6 on the critical path
-//   ChronGear : exchange z | k_fcg_a(reads rbuf) | block sums<2> | ONE all-reduce | k_fcg_b(+pack)   = 5 operations
-// Convergence checks keep one interval of look-ahead (run_intervals): the residual lands in pinned host memory, the
-// check that converges raises the device stop flag, and -- the all-reduced sums being the same bits on every rank --
-// all ranks stop at the same check.  Bitwise the same results as the single-rank run.
-struct DistSolve {
-  pop_ctx *c; SolveView v; int nbt;
-  FusedArgs args() const {
-    FusedArgs a = fused_args(c, v);
-    a.presummed = 1; a.nblocks = nbt; a.bsA = c->redbuf; a.bsB = c->redbuf + 2 * nbt;
-    a.sendmap = c->sendmap; a.send_off = c->send_off; a.send_slot = c->send_slot; a.sendbuf = c->sendbuf;
-    a.rmap = c->rmap; a.rbuf = c->recvbuf;
-    return a;
-  }
-  // ordered block sums of every rank -> all ranks; NF interleaved fields at redbuf + off
-  template <int NF> int allsum(const double *partial, long long off) {
-    hipLaunchKernelGGL(k_block_sums_global<NF>, dim3(nbt), dim3(POP_RED_THREADS), 0, c->stream, partial, v.nchunk, c->loc_of_gid, c->redbuf + off);
-    if (c->allred(c->comm_user, off, (long long)NF * nbt)) { c->err = "distributed solver: allreduce failed" + tr_err(c); return 1; }
-    c->solver_ops += 2;
-    return 0;
-  }
-  // the one-level exchange of the buffers the kernels packed: on the side stream beside the all-reduce when the
-  // transport has a second communicator, else in line.  fork: the packed data is complete on the launch stream now.
-  bool overlap = true;
-  bool side() const { return overlap && c->xchg_side && c->comm_side && !tun_on(c->h.tun.solver_overlap_off); }
-  int xchg_begin() {
-    std::vector<int> peer; std::vector<long long> so, sc, ro, rc;
-    long long s0 = 0, r0 = 0;
-    for (auto &p : c->peers) { peer.push_back(p.rank); so.push_back(s0); sc.push_back(p.nsend); ro.push_back(r0); rc.push_back(p.nrecv); s0 += p.nsend; r0 += p.nrecv; }
-    c->solver_ops += 1;
-    if (side()) {
-      if (hipEventRecord(c->ev_sa, c->stream) != hipSuccess || hipStreamWaitEvent(c->comm_side, c->ev_sa, 0) != hipSuccess) { c->err = "distributed solver: event failed"; return 1; }
-      if (c->xchg_side(c->comm_user, (int)peer.size(), peer.data(), so.data(), sc.data(), ro.data(), rc.data())) { c->err = "distributed solver: exchange failed" + tr_err(c); return 1; }
-      if (hipEventRecord(c->ev_sx, c->comm_side) != hipSuccess) { c->err = "distributed solver: event failed"; return 1; }
-      return 0;
-    }
-    if (c->xchg(c->comm_user, (int)peer.size(), peer.data(), so.data(), sc.data(), ro.data(), rc.data())) { c->err = "distributed solver: exchange failed" + tr_err(c); return 1; }
-    return 0;
-  }
-  int xchg_end() {   // the launch stream may read the receive buffer after this
-    if (side() && hipStreamWaitEvent(c->stream, c->ev_sx, 0) != hipSuccess) { c->err = "distributed solver: event failed"; return 1; }
-    return 0;
-  }
-  // residual + (r,r) of all ranks -> device scalars, pinned host ring, stop flag (the check of run_intervals)
-  int check() {
-    launch_fresidual<true>(c, v, args());
-    if (allsum<1>(args().partA, 0)) return 1;
-    hipLaunchKernelGGL(k_rr_blocks, dim3(1), dim3(1), 0, c->stream, (const double *)c->redbuf, nbt, c->sc, c->host_rr, c->h.convergenceCriterion);
-    c->solver_ops += 2;
-    return 0;
-  }
-};
-
-int solver_pcg_fused_dist(pop_ctx *c) {
-  const pop_config &cf = c->h.c;
-  DistSolve D{c, fused_view(c), c->h.nblocks_tot};
-  SolveView &v = D.v;
-  const dim3 G = view_grid(v), B(POP_RED_THREADS);
-  const int nbt = D.nbt, freq = cf.convergence_check_freq;
-  if (!c->allred || !c->xchg || !c->redbuf || !c->sendbuf || c->red_doubles < 4LL * nbt) { c->err = "distributed pcg: no transport / reduce buffer"; return 1; }
-  SolverScalars init{}; init.eta0 = 1.0;
-  HIPCHK(c, hipMemcpyAsync(c->sc, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(v.S0, 0, sizeof(double) * v.g.n2 * v.g.nblocks, c->stream));
-  launch_fresidual<false>(c, v, D.args());
-  c->numIterations = cf.max_iterations;
-  c->solver_ops = 0; c->solver_enq = 0;
-  auto iterations = [&](int n, bool pending) -> int {
-    for (int it = 0; it < n; ++it) {
-      c->solver_enq += 1;
-      FusedArgs a = D.args();
-      if (pending) hipLaunchKernelGGL(k_fpcg_a<true>, G, B, 0, c->stream, v.g, a);
-      else hipLaunchKernelGGL(k_fpcg_a<false>, G, B, 0, c->stream, v.g, a);
-      c->solver_ops += 1;
-      if (D.xchg_begin() || D.allsum<1>(a.partA, 0) || D.xchg_end()) return 1;
-      launch_fpcg_b(c, v, a, pending);
-      c->solver_ops += 1;
-      if (D.allsum<1>(a.partB, 2 * nbt)) return 1;
-      std::swap(v.S0, v.S1);
-      pending = true;
-    }
-    return 0;
-  };
-  double rr = 0.0;
-  int lerr = 0;
-  const int nint = cf.max_iterations / freq;
-  const int conv = run_intervals(c, nint, [&](int) -> int {
-    if (iterations(freq, false)) return -1;
-    hipLaunchKernelGGL(k_fpcg_xr, G, B, 0, c->stream, v.g, D.args());
-    c->solver_ops += 1;
-    if (D.check()) return -1;
-    return 1;
-  }, rr, lerr);
-  if (lerr) { if (c->err.empty()) c->err = "distributed pcg: interval launch failed"; return 1; }
-  if (conv >= 0) c->numIterations = (conv + 1) * freq;
-  if (c->numIterations == cf.max_iterations && nint * freq < cf.max_iterations) {   // remainder without a check
-    if (iterations(cf.max_iterations - nint * freq, false)) return 1;
-    hipLaunchKernelGGL(k_fpcg_xr, G, B, 0, c->stream, v.g, D.args());
-  }
-  // ghosts of the solution as POP_SolversRun leaves them: remote ones were advanced with their owners'
-  // arithmetic, the ones with a source on this rank are copied now (srcmap is the identity on remote ghosts)
-  const long long ncell = (long long)v.g.n2 * v.g.nblocks;
-  hipLaunchKernelGGL(k_halo_srcmap, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, c->stream, v.X, v.srcmap, ncell);
-  c->S0 = v.S0; c->S1 = v.S1;
-  c->rmsResidual = std::sqrt(rr * c->h.residualNorm);
-  HIPCHK(c, hipGetLastError());
-  if (c->numIterations == cf.max_iterations && c->h.convergenceCriterion != 0.0) { c->err = "POP_SolversPCG: solver not converged"; return 2; }
-  return 0;
-}
-
-int solver_pcg_replicated(pop_ctx *c) {
-  SolveView &v = c->gv;
-  const size_t n2 = c->g.n2, NG = n2 * c->h.nblocks_tot;
-  double *PN = c->PS[c->newt];
-  HIPCHK(c, hipMemsetAsync(c->redbuf, 0, sizeof(double) * 2 * NG, c->stream));
-  for (int lb = 0; lb < c->g.nblocks; ++lb) {
-    const size_t go = (size_t)(c->h.local_ids[lb] - 1) * n2;
-    HIPCHK(c, hipMemcpyAsync(c->redbuf + go, c->RHS + lb * n2, n2 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->redbuf + NG + go, PN + lb * n2, n2 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  }
-  if (c->allred(c->comm_user, 0, (long long)(2 * NG))) { c->err = "replicated solve: allreduce callback failed" + tr_err(c); return 1; }
-  HIPCHK(c, hipMemcpyAsync(v.RHS, c->redbuf, NG * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(v.X, c->redbuf + NG, NG * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  hipLaunchKernelGGL(k_center_all, dim3((unsigned)((NG + 255) / 256)), dim3(256), 0, c->stream, v.g, step_params(c), c->gTAREA, c->gKMT, v.C, (long long)NG);
-  const int e = solver_pcg_fused(c, v);
-  if (e) return e;
-  for (int lb = 0; lb < c->g.nblocks; ++lb) {
-    const size_t go = (size_t)(c->h.local_ids[lb] - 1) * n2;
-    HIPCHK(c, hipMemcpyAsync(PN + lb * n2, v.X + go, n2 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  }
-  return 0;
-}
-
-// ChronGear (POP_SolversMod.F90:1960-2266), diagonal or EVP preconditioner
-int solver_chrongear(pop_ctx *c) {
-  const pop_config &cf = c->h.c;
-  const dim3 G = grid_2d(c), B(POP_RED_THREADS);
-  SolverScalars init{};
-  HIPCHK(c, hipMemcpyAsync(c->sc, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  SolverArgs a = solver_args(c);
-  hipLaunchKernelGGL(k_residual<false>, grid_2d(c), B, 0, c->stream, c->g, a);
-  if (halo_update(c, c->R, 1)) return 1;
-  if (c->use_evp) {   // :2009-2032
-    if (evp_apply(c, c->R, c->Z) || halo_update(c, c->Z, 1)) return 1;
-    hipLaunchKernelGGL(k_cg_init<true>, grid_2d(c), B, 0, c->stream, c->g, a);
-  } else hipLaunchKernelGGL(k_cg_init<false>, grid_2d(c), B, 0, c->stream, c->g, a);
-  if (halo_update(c, c->Q, 1)) return 1;
-  if (reduce_finish<2>(c, FIN_CG_INIT)) return 1;
-  hipLaunchKernelGGL(k_cg_update<true>, grid_2d(c), B, 0, c->stream, c->g, a);
-  c->numIterations = cf.max_iterations;
-  double rr = 0.0;
-  for (int m = 1; m <= cf.max_iterations; ++m) {
-    if (c->use_evp) { if (evp_apply(c, c->R, c->Z)) return 1; }
-    else hipLaunchKernelGGL(k_cg_z, G, B, 0, c->stream, c->g, a);
-    if (halo_update(c, c->Z, 1)) return 1;
-    hipLaunchKernelGGL(k_cg_az, G, B, 0, c->stream, c->g, a);
-    if (reduce_finish<2>(c, FIN_CG_ITER)) return 1;
-    hipLaunchKernelGGL(k_cg_update<false>, grid_2d(c), B, 0, c->stream, c->g, a);
-    if (m % cf.convergence_check_freq == 0) {
-      hipLaunchKernelGGL(k_residual<true>, grid_2d(c), B, 0, c->stream, c->g, a);
-      if (halo_update(c, c->R, 1)) return 1;
-      if (reduce_finish<1>(c, FIN_RR)) return 1;
-      SolverScalars s;
-      if (read_scalars(c, &s)) return 1;
-      rr = s.rr;
-      if (rr < c->h.convergenceCriterion) { c->numIterations = m; break; }
-    }
-  }
-  c->rmsResidual = std::sqrt(rr * c->h.residualNorm);
-  HIPCHK(c, hipGetLastError());
-  if (c->numIterations == cf.max_iterations && c->h.convergenceCriterion != 0.0) { c->err = "POP_SolversChronGear: solver not converged"; return 2; }
-  return 0;
-}
-
-// ChronGear, fused form for one rank: the start-up pass as in solver_chrongear, then two launches per iteration
-// (k_fcg_a, k_fcg_b: the z halo folded into the matvec through srcmap, scalar recurrences recomputed by every
-// workgroup from the ordered totals) and one hipGraph replay per check interval.  Same arithmetic and summation
-// order as solver_chrongear: bitwise the same solution and iteration count.
-// compacted launches (DevGrid::red_act): the iterations store pairs of partials, the checks single ones, in the same slots;
-// chunks that are not launched cannot zero theirs, so the slots are cleared whenever the layout changes
-static void cg_clear_partials(pop_ctx *c, const SolveView &v) {
-  if (v.g.red_act) hipMemsetAsync(v.partial, 0, (size_t)v.nchunk * v.g.nblocks * 2 * sizeof(double), c->stream);
-}
-static int cg_fused_iterations(pop_ctx *c, SolveView &v, int n, int &par) {
-  const dim3 G = view_grid(v), B(POP_RED_THREADS);
-  for (int it = 0; it < n; ++it) {
-    FusedArgs a = fused_args(c, v);
-    a.AZ = c->AZ; a.A0R = v.S1;
-    if (a.presummed && (v.g.nxb & 1) == 0 && !v.g.red_tiles && !c->fpcg_one_cell) hipLaunchKernelGGL(k_fcg_a2, G, dim3(POP_RED_THREADS / 2), 0, c->stream, v.g, a);
-    else hipLaunchKernelGGL(k_fcg_a, G, B, 0, c->stream, v.g, a);
-    if (a.presummed && presum_relay(c, v)) hipLaunchKernelGGL((k_block_sums_relay<2, POP_RELAY_LMAX>), dim3(v.g.nblocks, 2), dim3(1024), 0, c->stream, (const double *)a.partA, v.nchunk, (const int *)c->iota, (double *)a.bsA);
-    else if (a.presummed) hipLaunchKernelGGL(k_block_sums<2>, dim3(v.g.nblocks), dim3(POP_RED_THREADS), 0, c->stream, (const double *)a.partA, v.nchunk, (const int *)c->iota, (double *)a.bsA);
-    hipLaunchKernelGGL(k_fcg_b, G, B, 0, c->stream, v.g, a, par);
-    par = 1 - par;
-  }
-  return 0;
-}
-static int cg_fused_interval(pop_ctx *c, SolveView &v, int freq) {
-  int par = 0;
-  cg_fused_iterations(c, v, freq, par);
-  cg_clear_partials(c, v);
-  launch_fresidual<true>(c, v, fused_args(c, v));
-  hipLaunchKernelGGL(k_rr_total, dim3(1), dim3(POP_RED_THREADS), 0, c->stream, (const double *)v.partial, v.nchunk, v.g.nblocks, c->sc, c->host_rr, c->h.convergenceCriterion);
-  cg_clear_partials(c, v);
-  return 0;
-}
-int solver_chrongear_fused(pop_ctx *c) {
-  const pop_config &cf = c->h.c;
-  SolveView v = fused_view(c);
-  const dim3 B(POP_RED_THREADS);
-  const int freq = cf.convergence_check_freq;
-  const long long a2 = (long long)c->g.n2 * c->g.nblocks;
-  SolverScalars init{};
-  HIPCHK(c, hipMemcpyAsync(c->sc, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  SolverArgs a = solver_args(c);
-  hipLaunchKernelGGL(k_residual<false>, grid_2d(c), B, 0, c->stream, c->g, a);
-  if (halo_update(c, c->R, 1)) return 1;
-  hipLaunchKernelGGL(k_cg_init<false>, grid_2d(c), B, 0, c->stream, c->g, a);
-  if (halo_update(c, c->Q, 1)) return 1;
-  if (reduce_finish<2>(c, FIN_CG_INIT)) return 1;
-  hipLaunchKernelGGL(k_cg_update<true>, grid_2d(c), B, 0, c->stream, c->g, a);
-  hipLaunchKernelGGL(k_pcsi_a0r, dim3((unsigned)((a2 + 255) / 256)), dim3(256), 0, c->stream, (const double *)c->centerWgt, v.S1, a2);
-  c->persist_used = 0;
-  {   // small views: the iterations as one resident launch (k_cg_persist); pop_tuning.pcg_persist = 0 switches it off
-    FusedArgs fa = fused_args(c, v);
-    fa.AZ = c->AZ; fa.A0R = v.S1;
-    if (!tun_off(c->h.tun.pcg_persist) && !fa.presummed && !c->persist_gave_up &&
-        v.g.nblocks * ((v.nchunk + POP_RED_THREADS - 1) / POP_RED_THREADS) <= POP_CGP_MAXP) {
-      if (const pop_ctx::PersistPlan *pl = persist_plan(c, v)) {
-        const int e = solver_cg_persist(c, v, *pl, fa);
-        if (e != 3) return e;
-        // the resident launch did not complete its exchanges: not again in this model.  It changed x only at its very end, if at all: x of the
-        // start-up pass is restored; r, s, q and the scalars were only read
-        c->persist_gave_up += 1;
-        fprintf(stderr, "libpop_amd: %s -- continuing with the two-launch ChronGear\n", c->err.c_str());
-        c->err.clear();
-        HIPCHK(c, hipMemcpyAsync(v.X, pl->X0, sizeof(double) * a2, hipMemcpyDeviceToDevice, c->stream));
-      }
-    }
-  }
-  c->numIterations = cf.max_iterations;
-  double rr = 0.0;
-  const bool use_graph = (freq % 2 == 0) && !c->no_graph;   // even: the (rho, sigma) ping-pong ends where it started
-  int m = 0, lerr = 0;
-  const int nint = cf.max_iterations / freq;
-  const int conv = run_intervals(c, nint, [&](int i) -> int {
-    if (use_graph) {
-      hipGraphExec_t exec = nullptr;
-      for (auto &g : c->graphs) if (g.first == v.X) exec = g.second;
-      if (!exec) {
-        hipGraph_t graph;
-        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return -1;
-        const int e = cg_fused_interval(c, v, freq);
-        hipError_t ce = hipStreamEndCapture(c->stream, &graph);
-        if (e || ce != hipSuccess) return -1;
-        if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) return -1;
-        hipGraphDestroy(graph);
-        c->graphs.push_back({v.X, exec});
-      }
-      if (hipGraphLaunch(exec, c->stream) != hipSuccess) return -1;
-    } else {
-      int par = (i * freq) & 1;   // odd freq: the ping-pong slot carries over between intervals
-      cg_fused_iterations(c, v, freq, par);
-      cg_clear_partials(c, v);
-      launch_fresidual<true>(c, v, fused_args(c, v));
-      hipLaunchKernelGGL(k_rr_total, dim3(1), dim3(POP_RED_THREADS), 0, c->stream, (const double *)v.partial, v.nchunk, v.g.nblocks, c->sc, c->host_rr, c->h.convergenceCriterion);
-      cg_clear_partials(c, v);
-    }
-    return 1;
-  }, rr, lerr);
-  if (lerr) { c->err = "fused ChronGear: interval launch failed"; return 1; }
-  if (conv >= 0) c->numIterations = (conv + 1) * freq;
-  m = nint * freq;
-  if (c->numIterations == cf.max_iterations && m < cf.max_iterations) {   // remainder without a check
-    int par = m & 1;
-    cg_fused_iterations(c, v, cf.max_iterations - m, par);
-  }
-  hipLaunchKernelGGL(k_halo_srcmap, dim3((unsigned)((a2 + 255) / 256)), dim3(256), 0, c->stream, v.X, v.srcmap, a2);
-  c->rmsResidual = std::sqrt(rr * c->h.residualNorm);
-  HIPCHK(c, hipGetLastError());
-  if (c->numIterations == cf.max_iterations && c->h.convergenceCriterion != 0.0) { c->err = "POP_SolversChronGear: solver not converged"; return 2; }
-  return 0;
-}
-
-// ChronGear for blocks spread over ranks (see DistSolve): start-up pass as in solver_chrongear, then per iteration
-// exchange z | k_fcg_a | block sums of (r,z), (az,z) | ONE all-reduce | k_fcg_b, which also packs the next z
-int solver_chrongear_fused_dist(pop_ctx *c) {
-  const pop_config &cf = c->h.c;
-  DistSolve D{c, local_view(c), c->h.nblocks_tot};   // whole launches: the (r,r) partials of the checks and the pairs of the iterations share slots
-  D.overlap = false;   // nothing runs beside the exchange here: the next kernel needs it
-  SolveView &v = D.v;
-  const dim3 G = view_grid(v), B(POP_RED_THREADS);
-  const int nbt = D.nbt, freq = cf.convergence_check_freq;
-  const long long a2 = (long long)c->g.n2 * c->g.nblocks;
-  if (!c->allred || !c->xchg || !c->redbuf || !c->sendbuf || c->red_doubles < 4LL * nbt) { c->err = "distributed ChronGear: no transport / reduce buffer"; return 1; }
-  SolverScalars init{};
-  HIPCHK(c, hipMemcpyAsync(c->sc, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  SolverArgs sa = solver_args(c);
-  hipLaunchKernelGGL(k_residual<false>, grid_2d(c), B, 0, c->stream, c->g, sa);
-  if (halo_update(c, c->R, 1)) return 1;
-  hipLaunchKernelGGL(k_cg_init<false>, grid_2d(c), B, 0, c->stream, c->g, sa);
-  if (halo_update(c, c->Q, 1)) return 1;
-  if (reduce_finish<2>(c, FIN_CG_INIT)) return 1;
-  hipLaunchKernelGGL(k_cg_update<true>, grid_2d(c), B, 0, c->stream, c->g, sa);
-  hipLaunchKernelGGL(k_pcsi_a0r, dim3((unsigned)((a2 + 255) / 256)), dim3(256), 0, c->stream, (const double *)c->centerWgt, v.S1, a2);
-  // z of the first iteration at the neighbours' ghosts: z = r*A0R on the whole array, packed and exchanged once
-  hipLaunchKernelGGL(k_cg_z, grid_2d(c), B, 0, c->stream, c->g, sa);
-  if (c->nsend_all) hipLaunchKernelGGL(k_halo_pack_all, dim3((c->nsend_all + 255) / 256, 1), dim3(256), 0, c->stream, (const double *)c->Z, c->sa_src, c->sa_start, c->sa_cnt, c->nsend_all, c->sendbuf, 1, c->g.n2);
-  if (D.xchg_begin()) return 1;
-  c->numIterations = cf.max_iterations;
-  c->solver_ops = 0; c->solver_enq = 0;
-  auto args = [&]() { FusedArgs a = D.args(); a.AZ = c->AZ; a.A0R = v.S1; return a; };
-  auto iterations = [&](int n, int &par) -> int {
-    for (int it = 0; it < n; ++it) {
-      c->solver_enq += 1;
-      FusedArgs a = args();
-      if ((v.g.nxb & 1) == 0 && !v.g.red_tiles && !c->fpcg_one_cell && (long long)v.nchunk * v.g.nblocks > 2048) hipLaunchKernelGGL(k_fcg_a2, G, dim3(POP_RED_THREADS / 2), 0, c->stream, v.g, a);
-      else hipLaunchKernelGGL(k_fcg_a, G, B, 0, c->stream, v.g, a);
-      c->solver_ops += 1;
-      if (D.allsum<2>(a.partA, 0)) return 1;
-      hipLaunchKernelGGL(k_fcg_b, G, B, 0, c->stream, v.g, a, par);
-      c->solver_ops += 1;
-      if (D.xchg_begin()) return 1;
-      par = 1 - par;
-    }
-    return 0;
-  };
-  double rr = 0.0;
-  int lerr = 0;
-  const int nint = cf.max_iterations / freq;
-  const int conv = run_intervals(c, nint, [&](int i) -> int {
-    int par = (i * freq) & 1;
-    if (iterations(freq, par)) return -1;
-    // r = b - A x; its z = r*A0R is packed by the residual kernel and exchanged for the next interval
-    {
-      FusedArgs a = args();
-      const dim3 GG = view_grid(v);
-      if ((v.g.nxb & 1) == 0 && !v.g.red_tiles && !c->fpcg_one_cell && (long long)v.nchunk * v.g.nblocks > 2048) hipLaunchKernelGGL(k_fresidual2<true>, GG, dim3(POP_RED_THREADS / 2), 0, c->stream, v.g, a);
-      else hipLaunchKernelGGL(k_fresidual<true>, GG, dim3(POP_RED_THREADS), 0, c->stream, v.g, a);
-      if (D.allsum<1>(a.partA, 0)) return -1;
-      hipLaunchKernelGGL(k_rr_blocks, dim3(1), dim3(1), 0, c->stream, (const double *)c->redbuf, nbt, c->sc, c->host_rr, c->h.convergenceCriterion);
-      if (D.xchg_begin()) return -1;
-      c->solver_ops += 2;
-    }
-    return 1;
-  }, rr, lerr);
-  if (lerr) { if (c->err.empty()) c->err = "distributed ChronGear: interval launch failed"; return 1; }
-  if (conv >= 0) c->numIterations = (conv + 1) * freq;
-  if (c->numIterations == cf.max_iterations && nint * freq < cf.max_iterations) {   // remainder without a check
-    int par = (nint * freq) & 1;
-    if (iterations(cf.max_iterations - nint * freq, par)) return 1;
-  }
-  hipLaunchKernelGGL(k_halo_srcmap, dim3((unsigned)((a2 + 255) / 256)), dim3(256), 0, c->stream, v.X, v.srcmap, a2);
-  c->rmsResidual = std::sqrt(rr * c->h.residualNorm);
-  HIPCHK(c, hipGetLastError());
-  if (c->numIterations == cf.max_iterations && c->h.convergenceCriterion != 0.0) { c->err = "POP_SolversChronGear: solver not converged"; return 2; }
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// P-CSI (POP_SolversMod.F90:1510-1835), diagonal or EVP preconditioner (EVP: operation-by-operation form only).  kernels_pcsi.hpp describes the
-// fused one-launch-per-iteration form; solver_pcsi is the operation-by-operation form that also
-// serves multi-rank runs (one halo update per iteration, no collective except at the checks).
-// ---------------------------------------------------------------------------------------------
-__global__ void k_set_int(int *p, int v) { *p = v; }
-
-int pcsi_check_start(const pop_ctx *c) { return c->h.c.convergence_check_start > 0 ? c->h.c.convergence_check_start : 60; }   // convergenceCheckStart :636
-
-int solver_pcsi(pop_ctx *c) {
-  const pop_config &cf = c->h.c;
-  const dim3 B(POP_RED_THREADS);
-  const long long a2 = (long long)c->g.n2 * c->g.nblocks;
-  const dim3 G1((unsigned)((a2 + 255) / 256)), B1(256);
-  SolverScalars init{};
-  HIPCHK(c, hipMemcpyAsync(c->sc, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  SolverArgs a = solver_args(c);
-  hipLaunchKernelGGL(k_residual<false>, grid_2d(c), B, 0, c->stream, c->g, a);
-  auto precond = [&]() -> int {   // r' = M^-1 r in place (:1646-1660, :1738-1752)
-    if (c->use_evp) {
-      if (evp_apply(c, c->R, c->Z)) return 1;
-      HIPCHK(c, hipMemcpyAsync(c->R, c->Z, sizeof(double) * a2, hipMemcpyDeviceToDevice, c->stream));
-    } else hipLaunchKernelGGL(k_pcsi_precond, G1, B1, 0, c->stream, c->g, c->R, (const double *)c->centerWgt, a2);
-    return 0;
-  };
-  if (precond()) return 1;
-  if (halo_update(c, c->R, 1)) return 1;
-  hipLaunchKernelGGL(k_pcsi_update<true>, G1, B1, 0, c->stream, (const double *)c->R, c->Q, a.X, a2, (const double *)c->pcsi_omega,
-                     (const int *)c->pcsi_base, 0, c->pcsi_csy);
-  hipLaunchKernelGGL(k_residual<false>, grid_2d(c), B, 0, c->stream, c->g, a);
-  c->numIterations = cf.max_iterations;
-  double rr = 0.0;
-  const int start = pcsi_check_start(c);
-  for (int m = 1; m <= cf.max_iterations; ++m) {
-    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, c->stream, c->pcsi_base, m - 1);
-    if (precond()) return 1;
-    if (halo_update(c, c->R, 1)) return 1;
-    hipLaunchKernelGGL(k_pcsi_update<false>, G1, B1, 0, c->stream, (const double *)c->R, c->Q, a.X, a2, (const double *)c->pcsi_omega,
-                       (const int *)c->pcsi_base, 1, c->pcsi_csy);
-    const bool check = (m % cf.convergence_check_freq == 0) && m >= start;
-    if (check) hipLaunchKernelGGL(k_residual<true>, grid_2d(c), B, 0, c->stream, c->g, a);
-    else hipLaunchKernelGGL(k_residual<false>, grid_2d(c), B, 0, c->stream, c->g, a);
-    if (check) {
-      if (reduce_finish<1>(c, FIN_RR)) return 1;
-      SolverScalars s;
-      if (read_scalars(c, &s)) return 1;
-      rr = s.rr;
-      if (rr < c->h.convergenceCriterion) { c->numIterations = m; break; }
-    }
-  }
-  c->rmsResidual = std::sqrt(rr * c->h.residualNorm);
-  HIPCHK(c, hipGetLastError());
-  if (c->numIterations == cf.max_iterations && c->h.convergenceCriterion != 0.0) { c->err = "POP_SolversPCSI: solver not converged"; return 2; }
-  return 0;
-}
-
-// fused form; state ping-pongs between (X, R, Q) and (Z, AZ, S1)
-struct PcsiBufs { double *X[2], *R[2], *Q[2]; };
-static PcsiArgs pcsi_args(pop_ctx *c, const PcsiBufs &bf, int in, int j) {
-  PcsiArgs a{};
-  a.Xi = bf.X[in]; a.Ri = bf.R[in]; a.Qi = bf.Q[in]; a.Xo = bf.X[1 - in]; a.Ro = bf.R[1 - in]; a.Qo = bf.Q[1 - in];
-  a.Bv = c->RHS; a.C = c->centerWgt; a.A0R = c->S0; a.omega = c->pcsi_omega; a.base = c->pcsi_base; a.srcmap = c->srcmap; a.partial = c->partial; a.sc = c->sc;
-  a.csy = c->pcsi_csy; a.j = j; a.nchunk = c->nchunk;
-  if (c->use_evp) { a.raw_r = 1; a.Ri = c->R; a.Ro = c->AZ; }   // r' = M^-1 r in R (read), the residual itself to AZ (written): evp_apply(AZ -> R) follows every step
-  return a;
-}
-// DevGrid of the single-rank fused P-CSI launches: with land elimination active, the compacted chunk list (DevGrid::red_act)
-static DevGrid pcsi_grid(const pop_ctx *c) {
-  DevGrid g = c->g;
-  if (c->g.skip && c->red_act && c->peers.empty()) { g.red_act = c->red_act; g.red_cnt = c->red_cnt; g.red_nact = c->red_nact; }
-  return g;
-}
-// `freq` steps starting from buffer `in`; the last one also forms (r,r) -> host when with_rr
-// two iterations per launch (k_pcsi_step_x2): how many of the n iterations of an interval go in pairs -- the last two stay single (the check
-// needs the chunk partials of (r, r) of k_pcsi_step2, and a single step before it keeps the pairs aligned for every n)
-// An interval of an even number of iterations goes in pairs throughout: the pair before a check leaves the residual itself in a scratch field
-// and k_pcsi_rr_chunks forms the chunk partials of (r, r) from it.  An odd interval: pairs, then one single step (which carries the check).
-static int pcsi_pairs(const pop_ctx *c, int n) { return c->pcsi_two_step ? n / 2 : 0; }
-// one pair; with_raw: the residual itself to pcsi_raw as well, and the chunk partials of (r, r) from it
-static void pcsi_launch_pair(pop_ctx *c, const DevGrid &gg, PcsiArgs a, bool with_raw) {
-  const int tiles_i = (gg.nxb - 2 * NGHOST + 63) / 64, tiles_j = (gg.nyb - 2 * NGHOST + 7) / 8;
-  const dim3 GT(lds_launch_x<8>(gg, tiles_i, tiles_j), gg.nblocks), TB(64, 8);
-  a.jfold = c->pcsi_jfold;
-  double *raw = with_raw ? c->pcsi_raw : nullptr;
-  if (a.jfold) {
-    if (with_raw) hipLaunchKernelGGL((k_pcsi_step_x2<true, true>), GT, TB, 0, c->stream, gg, a, raw);
-    else hipLaunchKernelGGL((k_pcsi_step_x2<false, true>), GT, TB, 0, c->stream, gg, a, raw);
-  } else if (with_raw) hipLaunchKernelGGL((k_pcsi_step_x2<true, false>), GT, TB, 0, c->stream, gg, a, raw);
-  else hipLaunchKernelGGL((k_pcsi_step_x2<false, false>), GT, TB, 0, c->stream, gg, a, raw);
-  if (with_raw) hipLaunchKernelGGL(k_pcsi_rr_chunks, dim3(red_grid_x(gg), gg.nblocks), dim3(POP_RED_THREADS), 0, c->stream, gg, a, (const double *)raw);
-}
-static int pcsi_launches(const pop_ctx *c, int n) { return n - pcsi_pairs(c, n); }
-static void pcsi_interval(pop_ctx *c, const PcsiBufs &bf, int in, int freq, bool with_rr) {
-  const DevGrid gg = pcsi_grid(c);
-  const dim3 G(red_grid_x(gg), gg.nblocks), B(POP_RED_THREADS);
-  int j0 = 1;
-  if (c->pcsi_evp_fused) {   // EVP: one launch per iteration (the step and the sub-block solves); r' ping-pongs with x and dx
-    const dim3 GE((unsigned)((c->evp.S + POP_EVP_SB - 1) / POP_EVP_SB));
-    for (int j = 1; j <= freq; ++j) {
-      PcsiArgs a = pcsi_args(c, bf, in, j);
-      a.raw_r = 0; a.Ri = bf.R[in]; a.Ro = bf.R[1 - in];
-      if (j == freq && with_rr) {
-        hipLaunchKernelGGL(k_pcsi_evp_step<true>, GE, dim3(64), 0, c->stream, c->evp, gg, a, c->pcsi_raw);
-        hipLaunchKernelGGL(k_pcsi_rr_chunks, G, B, 0, c->stream, gg, a, (const double *)c->pcsi_raw);
-      } else hipLaunchKernelGGL(k_pcsi_evp_step<false>, GE, dim3(64), 0, c->stream, c->evp, gg, a, (double *)nullptr);
-      in = 1 - in;
-    }
-    if (with_rr) hipLaunchKernelGGL(k_rr_total, dim3(1), dim3(POP_RED_THREADS), 0, c->stream, (const double *)c->partial, c->nchunk, c->g.nblocks, c->sc, c->host_rr, c->h.convergenceCriterion);
-    return;
-  }
-  const int npairs = pcsi_pairs(c, freq);
-  for (int p = 0; p < npairs; ++p, j0 += 2) {
-    pcsi_launch_pair(c, gg, pcsi_args(c, bf, in, j0), with_rr && j0 + 1 == freq);   // (the last pair of an even interval that ends in a check)
-    in = 1 - in;
-  }
-  for (int j = j0; j <= freq; ++j) {
-    const PcsiArgs a = pcsi_args(c, bf, in, j);
-    if (c->pcsi_two_cell) {
-      const bool rr = j == freq && with_rr;
-      if (rr && c->use_evp) hipLaunchKernelGGL((k_pcsi_step2<true, true>), G, dim3(POP_RED_THREADS / 2), 0, c->stream, gg, a);
-      else if (c->use_evp) hipLaunchKernelGGL((k_pcsi_step2<false, true>), G, dim3(POP_RED_THREADS / 2), 0, c->stream, gg, a);
-      else if (rr) hipLaunchKernelGGL((k_pcsi_step2<true>), G, dim3(POP_RED_THREADS / 2), 0, c->stream, gg, a);
-      else hipLaunchKernelGGL((k_pcsi_step2<false>), G, dim3(POP_RED_THREADS / 2), 0, c->stream, gg, a);
-    } else if (j == freq && with_rr) hipLaunchKernelGGL((k_pcsi_step<false, true>), G, B, 0, c->stream, gg, a);
-    else hipLaunchKernelGGL((k_pcsi_step<false, false>), G, B, 0, c->stream, gg, a);
-    if (c->use_evp) evp_apply(c, c->AZ, c->R);
-    in = 1 - in;
-  }
-  if (with_rr) {
-    hipLaunchKernelGGL(k_rr_total, dim3(1), dim3(POP_RED_THREADS), 0, c->stream, (const double *)c->partial, c->nchunk, c->g.nblocks, c->sc, c->host_rr, c->h.convergenceCriterion);
-  }
-}
-int solver_pcsi_fused(pop_ctx *c) {
-  const pop_config &cf = c->h.c;
-  const dim3 G = grid_2d(c), B(POP_RED_THREADS);
-  const int freq = cf.convergence_check_freq, start = pcsi_check_start(c);
-  PcsiBufs bf{{c->PS[c->newt], c->Z}, {c->R, c->AZ}, {c->Q, c->S1}};   // (with EVP the residual pair is fixed: pcsi_args)
-  if (c->pcsi_evp_fused) std::swap(bf.R[0], bf.R[1]);   // ... except in the one-launch form: the start-up step leaves r' in R, which is then the half the first iteration reads
-  SolverScalars init{};
-  HIPCHK(c, hipMemcpyAsync(c->sc, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  // r0 = b - A x0 (ghosts of x0 read at their sources), then the start-up step x1 = x0 + r0'/gamma, r1 = b - A x1
-  {
-    SolveView v = local_view(c);
-    const long long a2 = (long long)c->g.n2 * c->g.nblocks;
-    hipLaunchKernelGGL(k_pcsi_a0r, dim3((unsigned)((a2 + 255) / 256)), dim3(256), 0, c->stream, (const double *)c->centerWgt, c->S0, a2);
-    if (c->use_evp) {   // r0 into AZ, r0' = M^-1 r0 by the sub-block solves into R; both start from zero (cells no kernel writes are never read)
-      HIPCHK(c, hipMemsetAsync(c->AZ, 0, sizeof(double) * a2, c->stream));
-      HIPCHK(c, hipMemsetAsync(c->R, 0, sizeof(double) * a2, c->stream));
-      v.R = c->AZ;
-      hipLaunchKernelGGL(k_fresidual<false>, G, B, 0, c->stream, c->g, fused_args(c, v));
-      if (evp_apply(c, c->AZ, c->R)) return 1;
-    } else {
-      hipLaunchKernelGGL(k_fresidual<false>, G, B, 0, c->stream, c->g, fused_args(c, v));
-      hipLaunchKernelGGL(k_pcsi_scale, dim3((c->g.n2 + 255) / 256, c->g.nblocks), dim3(256), 0, c->stream, c->g, c->R, (const double *)c->S0);
-    }
-  }
-  hipLaunchKernelGGL((k_pcsi_step<true, false>), G, B, 0, c->stream, c->g, pcsi_args(c, bf, 0, 0));
-  if (c->use_evp && evp_apply(c, c->AZ, c->R)) return 1;
-  c->persist_used = 0;
-  if (!c->use_evp && !tun_off(c->h.tun.pcg_persist) && !c->persist_gave_up) {
-    // small views: the iterations as one resident launch (k_pcsi_persist: neighbour waits only, grid-wide exchanges at the checks)
-    SolveView v = local_view(c);
-    const FusedArgs fa = fused_args(c, v);
-    const pop_ctx::PersistPlan *pl = fa.presummed ? nullptr : persist_plan(c, v);
-    if (pl) {
-      const long long ncell = (long long)v.g.n2 * v.g.nblocks;
-      PcsiPersistArgs pa{};
-      PersistArgs &a = pa.p;
-      a.X = bf.X[0]; a.Bv = c->RHS; a.C = c->centerWgt; a.WNo = v.g.WNo; a.WEa = v.g.WEa; a.WNE = v.g.WNE; a.mMask8 = v.g.mMask8;
-      a.nxb = v.g.nxb; a.nchunk = v.nchunk; a.nblocks = v.g.nblocks; a.nslots = pl->nslots; a.ncell = ncell;
-      a.own_q = pl->own_q; a.nbr = pl->nbr; a.halo_off = pl->halo_off; a.halo_q = pl->halo_q; a.W = pl->W;
-      a.epoch = (++c->persist_epoch) << 32;
-      a.max_iter = cf.max_iterations; a.freq = freq; a.criterion = c->h.convergenceCriterion; a.out = c->persist_out; a.wait_ticks = 200000000ULL;
-      pa.Xin = bf.X[1]; pa.Rin = bf.R[1]; pa.Qin = bf.Q[1]; pa.A0R = c->S0; pa.omega = c->pcsi_omega; pa.csy = c->pcsi_csy; pa.start = start;
-      c->persist_out[0] = -1.0; c->persist_out[1] = 0.0; c->persist_out[2] = 0.0; c->persist_out[3] = 0.0;
-      const size_t lds = (size_t)3 * pl->nwin_max * sizeof(double);
-      const dim3 GP(pl->nwg);
-      switch (pl->CP) {
-        case 1: hipLaunchKernelGGL(k_pcsi_persist<1>, GP, B, lds, c->stream, pa); break;
-        case 2: hipLaunchKernelGGL(k_pcsi_persist<2>, GP, B, lds, c->stream, pa); break;
-        case 4: hipLaunchKernelGGL(k_pcsi_persist<4>, GP, B, lds, c->stream, pa); break;
-        default: hipLaunchKernelGGL(k_pcsi_persist<8>, GP, B, lds, c->stream, pa); break;
-      }
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipEventRecord(c->chk_ev[0], c->stream));
-      HIPCHK(c, hipEventSynchronize(c->chk_ev[0]));
-      if (c->persist_out[2] == 0.0 && c->persist_out[0] >= 0.0) {
-        c->numIterations = (int)c->persist_out[0];
-        c->rmsResidual = std::sqrt(c->persist_out[1] * c->h.residualNorm);
-        c->persist_used = 1; c->persist_nwg = pl->nwg; c->persist_cp = pl->CP;
-        hipLaunchKernelGGL(k_halo_srcmap, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, c->stream, bf.X[0], c->srcmap, ncell);
-        HIPCHK(c, hipGetLastError());
-        const bool conv = c->persist_out[3] > 0.0 && c->persist_out[1] < c->h.convergenceCriterion;
-        if (!conv && c->h.convergenceCriterion != 0.0) { c->err = "POP_SolversPCSI: solver not converged"; return 2; }
-        return 0;
-      }
-      // a wait gave up: the launch wrote its solution array only at its end (x of the start-up step is still in the other half of the pair,
-      // r', dx were only read): the iterations are repeated by the launches below, and the resident form is not used again in this model
-      c->persist_gave_up += 1;
-      fprintf(stderr, "libpop_amd: resident P-CSI: a wait for another workgroup's data gave up -- continuing with one launch per iteration\n");
-    }
-  }
-  if (pcsi_grid(c).red_act)   // compacted launches from here on: the partials of the chunks that are left out must read as zero
-    HIPCHK(c, hipMemsetAsync(c->partial, 0, (size_t)c->nchunk * c->g.nblocks * 2 * sizeof(double), c->stream));
-  int in = 1;
-  c->numIterations = cf.max_iterations;
-  double rr = 0.0;
-  // intervals of `freq` steps (the last one may be shorter); those that end on a multiple of freq at or after
-  // convergenceCheckStart carry a check.  in_before[i]: ping-pong half interval i starts from
-  const int nint = (cf.max_iterations + freq - 1) / freq;
-  std::vector<int> in_after(nint + 1, in);
-  int lerr = 0;
-  const int conv = run_intervals(c, nint, [&](int i) -> int {
-    const int m = i * freq, n = std::min(freq, cf.max_iterations - m);
-    const bool with_rr = (n == freq) && (m + n >= start);
-    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, c->stream, c->pcsi_base, m);
-    if (!c->no_graph && n == freq) {
-      const int variant = in * 2 + (with_rr ? 1 : 0);
-      hipGraphExec_t exec = nullptr;
-      for (auto &gk : c->pcsi_graphs) if (gk.first.first == bf.X[0] && gk.first.second == variant) exec = gk.second;
-      if (!exec) {
-        hipGraph_t graph;
-        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return -1;
-        pcsi_interval(c, bf, in, n, with_rr);
-        if (hipStreamEndCapture(c->stream, &graph) != hipSuccess) return -1;
-        if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) return -1;
-        hipGraphDestroy(graph);
-        c->pcsi_graphs.push_back({{bf.X[0], variant}, exec});
-      }
-      if (hipGraphLaunch(exec, c->stream) != hipSuccess) return -1;
-    } else pcsi_interval(c, bf, in, n, with_rr);
-    if (pcsi_launches(c, n) % 2) in = 1 - in;
-    in_after[i] = in;
-    return with_rr ? 1 : 0;
-  }, rr, lerr);
-  if (lerr) { c->err = "fused P-CSI: interval launch failed"; return 1; }
-  if (conv >= 0) { c->numIterations = (conv + 1) * freq; in = in_after[conv]; }   // later intervals did nothing on the device
-  const long long ncell = (long long)c->g.n2 * c->g.nblocks;
-  if (in == 1) HIPCHK(c, hipMemcpyAsync(bf.X[0], bf.X[1], sizeof(double) * ncell, hipMemcpyDeviceToDevice, c->stream));
-  hipLaunchKernelGGL(k_halo_srcmap, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, c->stream, bf.X[0], c->srcmap, ncell);
-  c->rmsResidual = std::sqrt(rr * c->h.residualNorm);
-  HIPCHK(c, hipGetLastError());
-  if (c->numIterations == cf.max_iterations && c->h.convergenceCriterion != 0.0) { c->err = "POP_SolversPCSI: solver not converged"; return 2; }
-  return 0;
-}
-
-// fused P-CSI with blocks spread over ranks: one halo exchange (r') and one launch per iteration, a block-sum
-// all-reduce only at the convergence checks
-int solver_pcsi_fused_dist(pop_ctx *c) {
-  const pop_config &cf = c->h.c;
-  const dim3 G = grid_2d(c), B(POP_RED_THREADS);
-  const int freq = cf.convergence_check_freq, start = pcsi_check_start(c), nbt = c->h.nblocks_tot;
-  if (!c->allred || !c->redbuf || c->red_doubles < nbt) { c->err = "distributed P-CSI: no transport / reduce buffer"; return 1; }
-  PcsiBufs bf{{c->PS[c->newt], c->Z}, {c->R, c->AZ}, {c->Q, c->S1}};
-  SolverScalars init{};
-  HIPCHK(c, hipMemcpyAsync(c->sc, &init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  const long long a2 = (long long)c->g.n2 * c->g.nblocks;
-  {
-    SolveView v = local_view(c);
-    hipLaunchKernelGGL(k_pcsi_a0r, dim3((unsigned)((a2 + 255) / 256)), dim3(256), 0, c->stream, (const double *)c->centerWgt, c->S0, a2);
-    hipLaunchKernelGGL(k_fresidual<false>, G, B, 0, c->stream, c->g, fused_args(c, v));
-    hipLaunchKernelGGL(k_pcsi_scale, dim3((c->g.n2 + 255) / 256, c->g.nblocks), dim3(256), 0, c->stream, c->g, c->R, (const double *)c->S0);
-  }
-  auto step = [&](int in, int j, bool first, bool rr) -> int {
-    if (halo_remote(c, bf.R[in], 1)) return 1;
-    PcsiArgs a = pcsi_args(c, bf, in, j);
-    a.remote_ghosts = 1;
-    if (first) hipLaunchKernelGGL((k_pcsi_step<true, false>), G, B, 0, c->stream, c->g, a);
-    else if (c->pcsi_two_cell && rr) hipLaunchKernelGGL((k_pcsi_step2<true>), G, dim3(POP_RED_THREADS / 2), 0, c->stream, c->g, a);
-    else if (c->pcsi_two_cell) hipLaunchKernelGGL((k_pcsi_step2<false>), G, dim3(POP_RED_THREADS / 2), 0, c->stream, c->g, a);
-    else if (rr) hipLaunchKernelGGL((k_pcsi_step<false, true>), G, B, 0, c->stream, c->g, a);
-    else hipLaunchKernelGGL((k_pcsi_step<false, false>), G, B, 0, c->stream, c->g, a);
-    return 0;
-  };
-  if (step(0, 0, true, false)) return 1;
-  int in = 1;
-  c->numIterations = cf.max_iterations;
-  double rr = 0.0;
-  if (c->pcsi_two_step_dist && halo_update_many(c, {{c->RHS, 1}})) return 1;   // the pairs form r at the first ring of ghost cells
-  // two iterations per launch across ranks (k_pcsi_step_x2): x, dx and r' travel two rings wide once per PAIR instead of r' once per
-  // iteration -- half the messages per iteration
-  const bool pairs = c->pcsi_two_step_dist;
-  const DevGrid gg = c->g;
-  for (int m = 1; m <= cf.max_iterations; ++m) {
-    bool check = (m % freq == 0) && m >= start;
-    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, c->stream, c->pcsi_base, m - 1);
-    if (pairs && !check && m + 1 <= cf.max_iterations) {
-      if (halo_update_many(c, {{bf.X[in], 1}, {bf.Q[in], 1}, {bf.R[in], 1}})) return 1;
-      const bool check2 = ((m + 1) % freq == 0) && m + 1 >= start;
-      pcsi_launch_pair(c, gg, pcsi_args(c, bf, in, 1), check2);
-      ++m; check = check2;
-    } else {
-      if (pairs && halo_update_many(c, {{bf.X[in], 1}, {bf.Q[in], 1}})) return 1;   // (the pairs do not advance x, dx at the ghosts of other ranks)
-      if (step(in, 1, false, check)) return 1;
-    }
-    in = 1 - in;
-    if (check) {
-      hipLaunchKernelGGL(k_block_sums_global<1>, dim3(nbt), dim3(POP_RED_THREADS), 0, c->stream, (const double *)c->partial, c->nchunk, c->loc_of_gid, c->redbuf);
-      if (c->allred(c->comm_user, 0, nbt)) { c->err = "distributed P-CSI: allreduce failed" + tr_err(c); return 1; }
-      hipLaunchKernelGGL(k_finalize<1>, dim3(1), dim3(1), 0, c->stream, c->redbuf, nbt, c->sc, (int)FIN_RR);
-      SolverScalars s;
-      if (read_scalars(c, &s)) return 1;
-      rr = s.rr;
-      if (rr < c->h.convergenceCriterion) { c->numIterations = m; break; }
-    }
-  }
-  if (in == 1) HIPCHK(c, hipMemcpyAsync(bf.X[0], bf.X[1], sizeof(double) * a2, hipMemcpyDeviceToDevice, c->stream));
-  if (pairs && halo_remote(c, bf.X[0], 1)) return 1;   // (the single steps keep x current at the ghosts of other ranks; the pairs do not)
-  hipLaunchKernelGGL(k_halo_srcmap, dim3((unsigned)((a2 + 255) / 256)), dim3(256), 0, c->stream, bf.X[0], c->srcmap, a2);
-  c->rmsResidual = std::sqrt(rr * c->h.residualNorm);
-  HIPCHK(c, hipGetLastError());
-  if (c->numIterations == cf.max_iterations && c->h.convergenceCriterion != 0.0) { c->err = "POP_SolversPCSI: solver not converged"; return 2; }
-  return 0;
-}
-
-// elapsed time of the last bracketed solve into the totals (waits for its closing event: at the next solve that is long past)
-void solve_collect(pop_ctx *c) {
-  if (!c->solve_pending) return;
-  c->solve_pending = false;
-  float ms = 0;
-  if (hipEventSynchronize(c->ev_solve[1]) == hipSuccess && hipEventElapsedTime(&ms, c->ev_solve[0], c->ev_solve[1]) == hipSuccess) {
-    c->solver_ms_total += ms; c->solver_iters_total += c->solve_iters_pending; c->solver_calls_total += 1;
-  }
-}
 int need_device(pop_ctx *c) {
   if (!c) return 1;
   if (c->host_only) { c->err = "context was created host-only: no GPU path available (there is no CPU fallback)"; return 1; }
@@ -2244,7 +726,6 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
       c->evp_fused_ok = c->fused_ok && cfg->solver_choice == 3;   // P-CSI + EVP: step kernel + sub-block solves, two launches per iteration (r3)
       c->fused_ok = false;
     }
-    c->no_graph = tun_on(h.tun.solver_nograph);
     c->mom_lds_rows = tun_or(h.tun.momentum_lds, c->mom_lds_rows);
     // tracer RHS through LDS tiles (kernels_tracer_lds.hpp).  Measured against the direct-load kernel: tx0.1v3 15.0 ms ->
     // 12.8 (64x4 tiles) / 13.6 (64x8); gx1v7 0.260 ms -> 0.208 (64x4) / 0.192 (64x8).  POP_TRACER_LDS=0|4|8 overrides.
@@ -2263,9 +744,7 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
       // the scratch-staged ones (the cross-check of the register instantiations)
       c->reg_thomas = false; c->reg_thomas_t = false;
     }
-    c->force_presum = tun_on(h.tun.solver_presum);
-    c->fpcg_one_cell = tun_off(h.tun.fpcg_b2);
-    c->pcsi_two_cell = (h.nxb & 1) == 0 && !g.red_tiles && (long long)c->nchunk * h.nblocks > 2048;
+    c->pcsi_two_cell = two_cell_shape(g, presum_by_size(c->nchunk, h.nblocks));
     // two iterations per launch with a tripole fold: the ghost cells beyond the fold are formed as mirror images of their source cells, which
     // must be cells of this rank (true of any decomposition into bands of whole rows, and of one rank)
     bool fold_local = true;
@@ -2287,7 +766,7 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
     c->pcsi_evp_fused = c->evp_fused_ok && c->evp.C0 && tun_or(h.tun.evp_wave, 3) >= 2 && tun_on(h.tun.pcsi_evp_fused);   // measured slower: off unless asked for
     if (c->pcsi_evp_fused && !c->pcsi_raw && dev_alloc(c, &c->pcsi_raw, a2)) return 1;
     if ((c->pcsi_two_step || c->pcsi_two_step_dist) && cfg->ns_boundary == 2 && dev_upload(c, &c->pcsi_jfold, jfold.data(), jfold.size())) return 1;
-    if (tun_set(h.tun.pcsi_step2)) c->pcsi_two_cell = (h.nxb & 1) == 0 && !g.red_tiles && h.tun.pcsi_step2 != 0;
+    if (tun_set(h.tun.pcsi_step2)) c->pcsi_two_cell = two_cell_shape(g, h.tun.pcsi_step2 != 0);
     c->replicated = !h.halo.peers.empty() && cfg->solver_choice == 1 && !use_evp(*cfg) && h.nblocks_tot <= 8 &&
                     (long long)h.n2 * h.nblocks_tot <= (4LL << 20) && !tun_on(h.tun.solver_distributed);
     if (c->replicated) {
@@ -2366,8 +845,7 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
 int pop_destroy(pop_ctx *c) {
   if (c) for (hipEvent_t &e : c->ev_solve) if (e) { hipEventDestroy(e); e = nullptr; }
   if (!c) return 0;
-  for (auto &g : c->graphs) hipGraphExecDestroy(g.second);
-  for (auto &g : c->pcsi_graphs) hipGraphExecDestroy(g.second);
+  for (auto &g : c->graphs) hipGraphExecDestroy(g.exec);
   if (c->host_sc) hipHostFree(c->host_sc);
   if (c->host_rr) hipHostFree(c->host_rr);
   if (c->persist_out) hipHostFree(c->persist_out);
@@ -2398,7 +876,6 @@ int pop_destroy(pop_ctx *c) {
 }
 const char *pop_last_error(const pop_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
-static int solver_path_code(const pop_ctx *c);
 int pop_get_dim(const pop_ctx *c, const char *name) {
   const std::string n(name);
   if (n == "nx_block") return c->h.nxb;
@@ -2743,9 +1220,8 @@ static void land_skip_for_step(pop_ctx *c) {
   if (want == c->g.skip) return;
   c->g.skip = want;
   if (c->stream) hipStreamSynchronize(c->stream);
-  for (auto &g : c->graphs) hipGraphExecDestroy(g.second);
-  for (auto &g : c->pcsi_graphs) hipGraphExecDestroy(g.second);
-  c->graphs.clear(); c->pcsi_graphs.clear();
+  for (auto &g : c->graphs) hipGraphExecDestroy(g.exec);
+  c->graphs.clear();
 }
 int pop_time_manager(pop_ctx *c) {
   const pop_config &cf = c->h.c;
@@ -3149,49 +1625,9 @@ int pop_baroclinic_driver(pop_ctx *c) {
   return 0;
 }
 
-// which form of the solver pop_solver_run dispatches to (same tests, same order): 1 operation by operation, 2 fused on one rank,
-// 3 fused with the blocks spread over ranks, 4 replicated fused solve on every rank -- reported per rank by bench.py
-static int solver_path_code(const pop_ctx *c) {
-  const bool unf = tun_on(c->h.tun.solver_unfused);
-  if (c->h.c.solver_choice == 2) {
-    if (c->fused_ok && !c->use_evp) return 2;
-    if (c->h.nranks > 1 && c->max_blocks_per_rank <= 16 && !c->use_evp && !unf) return 3;
-    return 1;
-  }
-  if (c->h.c.solver_choice == 3) {
-    if (c->use_evp) return c->evp_fused_ok ? 2 : 1;
-    if (c->fused_ok) return 2;
-    if (c->h.nranks > 1 && !unf) return 3;
-    return 1;
-  }
-  if (c->use_evp) return 1;
-  if (c->replicated) return 4;
-  if (c->fused_ok) return 2;
-  if (c->h.nranks > 1 && c->max_blocks_per_rank <= 16 && !unf) return 3;
-  return 1;
-}
 int pop_solver_run(pop_ctx *c) {
   if (need_device(c)) return 1;
-  if (c->h.c.solver_choice == 2) {
-    if (c->fused_ok && !c->use_evp) return solver_chrongear_fused(c);
-    if (c->h.nranks > 1 && c->max_blocks_per_rank <= 16 && !c->use_evp && !tun_on(c->h.tun.solver_unfused)) return solver_chrongear_fused_dist(c);
-    return solver_chrongear(c);
-  }
-  if (c->h.c.solver_choice == 3) {
-    if (c->use_evp && c->evp_fused_ok) return solver_pcsi_fused(c);
-    if (c->use_evp) return solver_pcsi(c);
-    if (c->fused_ok) return solver_pcsi_fused(c);
-    if (c->h.nranks > 1 && !tun_on(c->h.tun.solver_unfused)) return solver_pcsi_fused_dist(c);
-    return solver_pcsi(c);
-  }
-  if (c->use_evp) return solver_pcg(c);
-  if (c->replicated) {
-    if (!c->allred || !c->redbuf || c->red_doubles < 2LL * c->g.n2 * c->h.nblocks_tot) { c->err = "replicated solve needs pop_set_comm with a reduce buffer of pop_reduce_buffer_doubles()"; return 1; }
-    return solver_pcg_replicated(c);
-  }
-  if (c->fused_ok) { SolveView v = fused_view(c); const int e = solver_pcg_fused(c, v); c->S0 = v.S0; c->S1 = v.S1; return e; }
-  if (c->h.nranks > 1 && c->max_blocks_per_rank <= 16 && !tun_on(c->h.tun.solver_unfused)) return solver_pcg_fused_dist(c);
-  return solver_pcg(c);
+  return solver_run(c);
 }
 int pop_solver_preconditioner(pop_ctx *c, const char *x_name, int x_tl, const char *px_name, int px_tl) {
   if (need_device(c)) return 1;

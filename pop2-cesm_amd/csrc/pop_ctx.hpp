@@ -1,0 +1,236 @@
+// pop_ctx.hpp -- the context of one model instance and the small helpers every launch file uses.
+// Part of the single translation unit pop_amd.hip (included after the kernel headers).
+#pragma once
+
+#define HIPCHK(ctx, call)                                                                       \
+  do {                                                                                          \
+    hipError_t e_ = (call);                                                                     \
+    if (e_ != hipSuccess) {                                                                     \
+      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                           \
+      return 1;                                                                                 \
+    }                                                                                           \
+  } while (0)
+
+struct PhaseTimer { double ms = 0; int calls = 0; };
+
+struct DevPeer { int rank; int *send_src = nullptr, *recv_dst = nullptr; int nsend = 0, nrecv = 0; };
+
+struct pop_ctx {
+  HostModel h;
+  bool host_only = true;
+  std::string err;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  DevGrid g{};
+  std::map<std::string, double *> d2;     // device 2-D fields (local blocks)
+  std::map<std::string, int *> di2;
+  std::vector<void *> allocs;
+  // prognostic state, physical slots; logical levels via oldt/curt/newt
+  double *TR[MAXNT][3] = {}, *U[3] = {}, *V[3] = {}, *RHO[3] = {};
+  double *PS[3] = {}, *GX[3] = {}, *GY[3] = {}, *UB[3] = {}, *VB[3] = {};
+  double *PGUESS = nullptr, *FW = nullptr, *FW_OLD = nullptr, *SHF_QSW = nullptr, *CHL = nullptr;
+  double *STF[MAXNT] = {}, *TFW[MAXNT] = {}, *KPP_SRC[MAXNT] = {}, *VDC[2] = {}, *VVC = nullptr;
+  double *DH = nullptr, *DHU = nullptr, *ZX = nullptr, *ZY = nullptr, *UH = nullptr, *VH = nullptr;
+  double *W3 = nullptr, *W4 = nullptr, *RHS = nullptr, *centerWgt = nullptr;
+  double *E3 = nullptr, *F3 = nullptr, *S3a = nullptr, *S3b = nullptr, *S3c = nullptr, *S3d = nullptr;
+  // del4: the first Laplacians need only the mix-time fields, so they run on a side stream beside the vertical-mixing
+  // coefficients (own output buffers d2t / d2u instead of the shared scratch; POP_DEL4_SIDE=0: in line, scratch reused)
+  double *d2t[2] = {nullptr, nullptr}, *d2u[2] = {nullptr, nullptr};
+  // hmix_momentum = 3: the friction hdiffu_aniso forms (3-D, read by the momentum kernel) and the variable viscosities F_PARA, F_PERP
+  double *HDU = nullptr, *HDV = nullptr, *FPARA = nullptr, *FPERP = nullptr;
+  // del4: the tracer kernel of a step also forms the first Laplacian of its CURRENT tracers -- the mix-time field of the next
+  // (leapfrog) step -- from the tile it has in LDS; d2t_next receives it, d2t_next_slot is the time slot it belongs to
+  double *d2t_next[2] = {nullptr, nullptr};
+  bool d2t_next_valid = false; int d2t_next_slot = -1;
+  // the ghost cells of the tracers in a time slot are copies of their source cells (set-up and every halo update leave them so;
+  // a caller's pop_set_field / a restart file may not): only then is the halo update of the field formed ahead the same arithmetic
+  // as k_del4_d2t on the ghost ring
+  bool tr_ghosts_ok[3] = {true, true, true};
+  // the same for the velocity (k_momentum_rhs_lds forms k_del4_d2u's field for the next step)
+  double *d2u_next[2] = {nullptr, nullptr};
+  bool d2u_next_valid = false; int d2u_next_slot = -1;
+  bool uv_ghosts_ok[3] = {true, true, true};
+  bool d2t_last_formed = false, d2u_last_formed = false;   // did the last tracer / momentum launch write the next step's field (bench accounting)
+  hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_d2t = nullptr, ev_d2u = nullptr, ev_vmixu = nullptr;
+  bool mom_side = false;   // phase_hmix_momentum on the side stream: del4 with side_del4; anis unless pop_tuning.aniso_side = 0
+  bool side_del4 = false, vmixu_pending = false, btrop_added = false, vmixu_deferred = false;   // implicit vertical mixing of U,V in flight on the side stream
+  double *HBLT = nullptr, *HMXL = nullptr, *HMXL_DR = nullptr;
+  MixDev mix{};
+  // KPP look-ahead: the vertical-mixing coefficients of the NEXT step depend only on this step's curtime fields (its
+  // mixtime on a leapfrog step), so pop_step computes them on a third stream beside the barotropic solver (VALU-bound
+  // work beside bandwidth-bound work) into a second set of output fields; the next step swaps the sets in.
+  bool vdc_shared = false;
+  bool kpp_src_user = false;   // the caller wrote KPP_SRC (pop_set_field): read it at every level until KPP has run again
+  bool src_dirty = true, src_dirty_alt = true;   // KPP_SRC / KPPa may hold non-zeros below the KBL stored with them: the next evaluation into that set clears every level
+  double *VDCa[2] = {nullptr, nullptr}, *VVCa = nullptr, *KPPa[MAXNT] = {}, *HBLTa = nullptr, *HMXLa = nullptr, *HMXL_DRa = nullptr;
+  int *KBL = nullptr, *KBLa = nullptr;   // KBL that belongs to KPP_SRC / KPPa (the tracer kernel reads KPP_SRC down to it)
+  hipStream_t ahead = nullptr; hipEvent_t ev_ahead_fork = nullptr, ev_ahead = nullptr;
+  bool ahead_enabled = false, ahead_valid = false; int ahead_slot = -1;
+  // solver
+  double *R = nullptr, *S0 = nullptr, *S1 = nullptr, *Q = nullptr, *Z = nullptr, *AZ = nullptr;
+  double *partial = nullptr, *blocksum = nullptr;
+  SolverScalars *sc = nullptr;
+  int *gid = nullptr, *srcmap = nullptr, *iota = nullptr, *loc_of_gid = nullptr;
+  std::vector<int> opre_host;
+  int *red_act = nullptr, *red_cnt = nullptr; int red_nact = 0;                // chunks with an ocean cell (fused solver launches, land elimination)
+  SolverScalars *host_sc = nullptr;                       // pinned
+  double *host_rr = nullptr;                              // pinned ring of (r,r) check results (k_rr_total)
+  hipEvent_t chk_ev[4] = {};                              // one event per check interval in flight
+  // fused-solver interval graphs, keyed by the solution array and the solver's variant of the interval (graph_for)
+  struct IntervalGraph { const double *key; int variant; hipGraphExec_t exec; };
+  std::vector<IntervalGraph> graphs;
+  bool fused_ok = false, evp_fused_ok = false, replicated = false, grid_from_input = false;
+  // land elimination: the first land_full_steps steps after set-up / a restart / a new state run every workgroup (they write
+  // the state-independent values of the land tiles), later steps skip workgroups without an ocean cell (DevGrid::skip)
+  bool land_skip = true; int land_full_steps = 4, full_left = 4, full_seen = 0; double land_fraction = 0.0;
+  // the resident pcg of small grids (kernels_pcg_persist.hpp; pop_tuning.pcg_persist): one plan per solver view
+  struct PersistPlan {
+    const void *key = nullptr; bool ok = false; std::string why;
+    int CP = 0, nwg = 0, nwin_max = 0, nslots = 0;
+    int *own_q = nullptr, *halo_off = nullptr, *halo_q = nullptr; unsigned short *nbr = nullptr;
+    PWord *W = nullptr;                                    // [2][nslots] partial words + [2][ncell] z words
+    double *X0 = nullptr;                                  // copy of the first guess (a solve that gave up is repeated by the two-launch form)
+  };
+  unsigned long long persist_epoch = 0;                    // high half of the tags of the next resident solve (never repeats)
+  std::vector<PersistPlan> persist;
+  std::vector<int> h_srcmap;                               // host copy of srcmap (local view)
+  double *persist_out = nullptr;                           // pinned: iterations, (r,r), status, checks
+  int persist_used = 0;                                    // the last pcg solve ran as the resident launch
+  int persist_gave_up = 0;                                 // resident solves that gave up a wait (then never used again in this model)
+  int red_active_total = 0;                                // fused solver kernels: chunks that have work, summed over the local blocks
+  int persist_nwg = 0, persist_cp = 0;                     // shape of the last resident launch
+  bool pcsi_two_cell = false;   // fused P-CSI step with two cells per thread (large grids, even row pitch; POP_PCSI_STEP2=0|1)
+  bool pcsi_two_step = false;   // ... and two iterations per launch (k_pcsi_step_x2; pop_tuning.pcsi_two_step)
+  bool pcsi_two_step_dist = false;   // ... with blocks spread over ranks
+  double *pcsi_raw = nullptr;   // the residual of the pair before a check (k_pcsi_step_x2<true> -> k_pcsi_rr_chunks)
+  int *pcsi_jfold = nullptr;    // tripole: per local block, the first array row beyond the fold (PcsiArgs::jfold)
+  bool pcsi_evp_fused = false;  // P-CSI + EVP: iteration and sub-block solves in one launch (k_pcsi_evp_step; pop_tuning.pcsi_evp_fused)
+  bool reg_thomas_t = true;
+  int trc_lds_rows = 4;                                    // tracer RHS (centred advection): LDS tile rows, 0 = direct loads
+  int mom_lds_rows = 4;                                    // momentum RHS: LDS tile rows (0 = direct-load kernel)
+  bool reg_thomas = true;                                  // column-in-registers Thomas kernels (km = 60, 62)
+  SolveView gv{};                                         // replicated barotropic mode: all blocks
+  double *gTAREA = nullptr; int *gKMT = nullptr;
+  int nchunk = 0, numIterations = 0;
+  double rmsResidual = 0.0;
+  // halo plan on device
+  int *copy_dst = nullptr, *copy_src = nullptr, *fill_dst = nullptr;
+  int ncopy = 0, nfill = 0;
+  std::vector<DevPeer> peers;
+  // all peers concatenated (one pack / unpack launch per halo update)
+  int *sa_src = nullptr, *sa_start = nullptr, *sa_cnt = nullptr, *ra_dst = nullptr, *ra_start = nullptr, *ra_cnt = nullptr;
+  int nsend_all = 0, nrecv_all = 0;
+  // fused distributed solvers: per-cell send entries / receive slots (FusedArgs::sendmap, rmap), nz = 1 message order
+  int *sendmap = nullptr, *send_off = nullptr, *send_slot = nullptr, *rmap = nullptr;
+  int max_blocks_per_rank = 0;                             // over all ranks: choices between collective code paths must not depend on the rank
+  bool halo_ns_only = false;                               // every ghost cell owned by another rank lies in a ghost ROW (j-band shards)
+  pop_exchange_fn xchg_side = nullptr;                     // the same exchange on the communication stream (own communicator), or null
+  hipStream_t comm_side = nullptr;                         // stream of those exchanges (not `side`: impvmixu runs there beside the solver)
+  hipEvent_t ev_sa = nullptr, ev_sx = nullptr;            // solver: z packed (launch stream) / z received (side stream)
+  long long solver_ops = 0, solver_enq = 0;               // stream operations / iterations enqueued by the last distributed solve (incl. look-ahead)
+  // tripole northern boundary, per field location (single rank)
+  int *tp_dst[5] = {}, *tp_a[5] = {}, *tp_b[5] = {}; int tp_n[5] = {}; double *tp_buf = nullptr;
+  // comm hooks
+  double *sendbuf = nullptr, *recvbuf = nullptr, *redbuf = nullptr;
+  long long comm_doubles = 0, red_doubles = 0;
+  pop_exchange_fn xchg = nullptr;
+  pop_allreduce_fn allred = nullptr;
+  void *comm_user = nullptr;
+  EvpDev evp{}; bool use_evp = false;                                                // EVP block preconditioner (preconditioner_choice = 1)
+  double *pcsi_omega = nullptr; int *pcsi_base = nullptr; double pcsi_csy = 0;        // P-CSI: omega_k table, interval base
+  double rf_S[MAXNT] = {}, rf_S_prev[MAXNT] = {}; bool rf_S_prev_valid[MAXNT] = {};   // Robert filter
+  Upw3Dev upw3{};                                          // tadvect = 2
+  LwDev lw{};                                              // tadvect = 3 (lw_lim): flux-velocity and work fields
+  GmDev gm{};                                              // hmix_tracer = 3 (gm): slopes, tapered diffusivities, GTK
+  RcclTransport *rccl_tr = nullptr;                       // in-library RCCL transport (pop_comm_init_rccl)
+  // time stepping
+  int oldt = 0, curt = 1, newt = 2, mixt = 1;
+  int first_step = 1, leapfrogts = 1, f_euler_ts = 0, avg_ts = 0, nsteps_total = 0, nsteps_this_interval = 0;
+  int eod = 0, eod_last = 0;                               // the step ends a day / the previous one did (time_management.F90:1809, 3586-3592; runs that start at midnight)
+  double c2dtt = 0, c2dtu = 0, c2dtp = 0, beta = 0;
+  std::map<std::string, PhaseTimer> timers;
+  // the barotropic solve bracketed by two events on the launch stream, read back one step later (no synchronisation inside the
+  // step): totals since the last pop_timers_reset / "solver_ms_reset" for the bench's per-iteration figure
+  hipEvent_t ev_solve[2] = {nullptr, nullptr}; bool solve_pending = false; int solve_iters_pending = 0;
+  double solver_ms_total = 0.0; long long solver_iters_total = 0, solver_calls_total = 0;
+  bool timing = false;
+  bool phase_timing = false;   // inside pop_time_phase: kernels only
+  double *op_scratch = nullptr;   // pop_operator_host: four block-sized 2-D arrays
+  bool prio_on = false; int prio_least = 0;   // stream priorities in use; the lowest one
+};
+
+namespace {
+
+template <class T>
+int dev_alloc(pop_ctx *c, T **p, size_t n, bool zero = true) {
+  void *v = nullptr;
+  HIPCHK(c, hipMalloc(&v, std::max<size_t>(n, 1) * sizeof(T)));
+  c->allocs.push_back(v);
+  if (zero) HIPCHK(c, hipMemset(v, 0, std::max<size_t>(n, 1) * sizeof(T)));
+  *p = (T *)v;
+  return 0;
+}
+template <class T>
+int dev_upload(pop_ctx *c, T **p, const T *src, size_t n) {
+  if (dev_alloc(c, p, n, false)) return 1;
+  HIPCHK(c, hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
+// extract the local blocks of an all-blocks host field
+template <class T>
+std::vector<T> local_part(const HostModel &h, const std::vector<T> &all) {
+  std::vector<T> out(h.n2 * h.nblocks);
+  for (int lb = 0; lb < h.nblocks; ++lb)
+    std::copy(all.begin() + (size_t)(h.local_ids[lb] - 1) * h.n2, all.begin() + (size_t)h.local_ids[lb] * h.n2, out.begin() + (size_t)lb * h.n2);
+  return out;
+}
+
+// the same for an all-blocks 3-D host field (nxb, nyb, km, nblocks_tot)
+std::vector<double> local_part3(const HostModel &h, const std::vector<double> &all) {
+  std::vector<double> out(h.n3 * h.nblocks);
+  for (int lb = 0; lb < h.nblocks; ++lb)
+    std::copy(all.begin() + (size_t)(h.local_ids[lb] - 1) * h.n3, all.begin() + (size_t)h.local_ids[lb] * h.n3, out.begin() + (size_t)lb * h.n3);
+  return out;
+}
+
+// column kernels: one wave per workgroup; tile order per kernels_common.hpp col_setup
+dim3 grid_cols(const pop_ctx *c) {
+  if (c->g.xcd_remap == 2) return dim3(tile_grid_x(c->g.nxb, c->g.nyb, POP_COL_THREADS, 1), c->g.nblocks);
+  return dim3(col_grid(c->g, POP_COL_THREADS), c->g.nblocks);
+}
+dim3 block_stencil() { return dim3(POP_COL_THREADS, 1); }
+dim3 grid_stencil(const pop_ctx *c) { return grid_cols(c); }
+dim3 grid_2d(const pop_ctx *c) { return dim3(red_grid_x(c->g), c->g.nblocks); }
+dim3 grid_3d(const pop_ctx *c) { return dim3((c->g.n2 + 255) / 256, c->g.km, c->g.nblocks); }
+
+StepParams step_params(const pop_ctx *c) {
+  const pop_config &cf = c->h.c;
+  StepParams s{};
+  s.c2dtu = c->c2dtu; s.c2dtp = c->c2dtp; s.beta = c->beta; s.gamma = 1.0 - 2.0 * (1.0 / 3.0);
+  s.dtp = c->h.dtp; s.grav = GRAV;
+  s.am = cf.am; s.ah = cf.ah; s.bottom_drag = cf.bottom_drag;
+  s.const_vvc = cf.const_vvc; s.const_vdc = cf.const_vdc; s.convect_diff = cf.convect_diff; s.convect_visc = cf.convect_visc;
+  s.aidif = cf.aidif;
+  s.rich_bckgrnd_vvc = cf.rich_bckgrnd_vvc; s.rich_bckgrnd_vdc = cf.rich_bckgrnd_vdc; s.rich_mix = cf.rich_mix;
+  s.leapfrogts = c->leapfrogts; s.pavg = (cf.lpressure_avg && c->leapfrogts) ? 1 : 0;
+  s.impcor = cf.impcor; s.reset_to_freezing = cf.reset_to_freezing;
+  s.nvdc = (cf.vmix_choice == 3) ? 2 : 1;
+  return s;
+}
+
+struct ScopedPhase {   // optional HIP-event timing of a phase on the launch stream
+  pop_ctx *c; const char *name; hipEvent_t e0 = nullptr, e1 = nullptr;
+  ScopedPhase(pop_ctx *c_, const char *n) : c(c_), name(n) {
+    if (c->timing) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, c->stream); }
+  }
+  ~ScopedPhase() {
+    if (c->timing) {
+      hipEventRecord(e1, c->stream); hipEventSynchronize(e1);
+      float ms = 0; hipEventElapsedTime(&ms, e0, e1);
+      auto &t = c->timers[name]; t.ms += ms; t.calls += 1;
+      hipEventDestroy(e0); hipEventDestroy(e1);
+    }
+  }
+};
+
+}  // namespace
