@@ -30,10 +30,12 @@ extern "C" {
 /* Run-time configuration: the namelist subset this path reads
  * (domain_nml, grid_nml, time_manager_nml, hmix_*_nml, vertical_mix_nml,
  *  vmix_*_nml, advect_nml, pressure_grad_nml, baroclinic_nml, &solvers). */
-#define POP_CONFIG_VERSION 6   /* layout of pop_config below (4: gm_transition_layer appended; 5: gm_diag_bolus and gm_kappa_bkg_srfbl out of reserved_i,
-                                 * ah_bkg_bottom and kappa_depth_* appended -- added late in round 3 without a new number; 6: the hmix_aniso_nml members appended).
-                                 * pop_create accepts 6 and 5; a version-5 struct is read up to kappa_depth_scale only (its size) and cannot select
-                                 * hmix_momentum = 3.  Any other struct_version is refused. */
+#define POP_CONFIG_VERSION 7   /* layout of pop_config below (4: gm_transition_layer appended; 5: gm_diag_bolus and gm_kappa_bkg_srfbl out of reserved_i,
+                                 * ah_bkg_bottom and kappa_depth_* appended -- added late in round 3 without a new number; 6: the hmix_aniso_nml members appended;
+                                 * 7: lsubmesoscale_mixing and the mix_submeso_nml members appended).
+                                 * pop_create accepts 7, 6 and 5; a version-5 struct is read up to kappa_depth_scale only (its size) and cannot select
+                                 * hmix_momentum = 3, a version-6 struct up to smag_lat_gauss and cannot select lsubmesoscale_mixing.  Any other
+                                 * struct_version is refused. */
 typedef struct pop_config {
   int struct_version;         /* = POP_CONFIG_VERSION (round 3: every option has its own named field) */
   int nx_global, ny_global, km, nt;   /* domain_size.F90 */
@@ -130,6 +132,19 @@ typedef struct pop_config {
   double smag_lat;            /* [degrees], 0 = 20 */
   double smag_lat_fact;       /* no default: 0 with lsmag_aniso is refused (code default 0.98) */
   double smag_lat_gauss;      /* 0 = 98 */
+  /* ---- struct_version 7: the submesoscale mixed-layer eddy scheme of Fox-Kemper, Ferrari and Hallberg (mix_submeso.F90; hmix_nml
+   *      lsubmesoscale_mixing and mix_submeso_nml :164-188).  With lsubmesoscale_mixing = 0 nothing below is read. */
+  int lsubmesoscale_mixing;   /* 1: the restratification tendency of submeso_sf / submeso_flux added to the Gent-McWilliams tendency
+                               * (horizontal_mix.F90:566-581).  Needs hmix_tracer = 3 and no partial_bottom_cells; with KPP the mixed-layer
+                               * depth is HMXL (kpp_ml_diagnostics is switched on), zw(1) otherwise (code default .false.; CESM: .true. on gx grids) */
+  int luse_const_horiz_len_scale;   /* 1: HLS = hor_length_scale everywhere (code default .false.) */
+  int submeso_diag;           /* 1: the diagnostic velocities "USUBM", "VSUBM" (east / north face), "WSUBM" (top of the T cell) (:599-661) and the
+                               * tendency "SUBM_ADV_TEND" (n = 0, 1) of each tracer on its own, readable with pop_get_field.  Always readable with
+                               * the scheme on: "HLS_SUBM", "SUBM_ML_DEPTH", "SUBM_TIME_SCALE"; "GM_GTK" (n = 0, 1, hmix_tracer = 3) is the whole
+                               * mixing tendency the tracer right-hand side reads */
+  double efficiency_factor;   /* 0 = 0.07 */
+  double time_scale_constant; /* [s], 0 = 3.456e5 (4 days, the code default; CESM's namelist default is 8.64e4) */
+  double hor_length_scale;    /* [cm], 0 = 5e5: the floor of the length scale, or the length scale itself with luse_const_horiz_len_scale */
 } pop_config;
 
 typedef struct pop_ctx pop_ctx;
@@ -212,6 +227,8 @@ typedef struct pop_tuning {
                             * default 0 = two launches per iteration (k_pcsi_step2, k_evp_apply_wave2) */
   int aniso_side;          /* hmix_momentum = 3: 0 = the friction k_hdiffu_aniso in line before the momentum right-hand side; default 1 = on the
                             * side stream beside the vertical-mixing coefficients (it reads only the mix-time U, V and fixed coefficients) */
+  int submeso_all_levels;  /* lsubmesoscale_mixing: 1 = k_submeso_flux marches all km levels; default 0 = every tile stops at the last level that
+                            * can hold a non-zero tendency (from the largest mixed-layer depth over the tile and a one-cell rim); bitwise equal */
 } pop_tuning;
 void pop_tuning_init(pop_tuning *t);   /* struct_bytes = sizeof, every field POP_TUNING_UNSET */
 int pop_get_tuning(const pop_ctx *ctx, pop_tuning *resolved);   /* fields still POP_TUNING_UNSET: the size rule applied */

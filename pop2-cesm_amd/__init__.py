@@ -161,6 +161,38 @@ def anisotropic_config(cfg, **hmix_aniso_nml):
     return out
 
 
+SUBMESO_FIELDS = [("lsubmesoscale_mixing", C.c_int), ("luse_const_horiz_len_scale", C.c_int), ("submeso_diag", C.c_int),
+                  ("efficiency_factor", C.c_double), ("time_scale_constant", C.c_double), ("hor_length_scale", C.c_double)]
+_v7_types = {}
+
+
+def submeso_config(cfg, **mix_submeso_nml):
+    """pop_config layout 7 (include/pop_amd.h): a copy of the caller's layout-5 or layout-6 struct `cfg` (any ctypes mirror, such as
+    tests/popcfg.py PopConfig or what anisotropic_config returns) with the lsubmesoscale_mixing / mix_submeso_nml members appended and
+    lsubmesoscale_mixing = 1.  Keywords: the members by name, or any other pop_config field (lsubmesoscale_mixing=0 ...)."""
+    if hasattr(cfg, "lsubmesoscale_mixing"):
+        v6 = type(cfg).__mro__[1]
+    elif hasattr(cfg, "aniso_alignment"):
+        v6 = type(cfg)
+    else:                           # layout 5: the hmix_aniso_nml members appended, all 0
+        base = type(cfg)
+        v6 = _v6_types.get(base)
+        if v6 is None:
+            v6 = _v6_types[base] = type(base.__name__ + "V6", (base,), {"_fields_": ANISO_FIELDS})
+    v7 = _v7_types.get(v6)
+    if v7 is None:
+        v7 = _v7_types[v6] = type(v6.__name__ + "V7", (v6,), {"_fields_": SUBMESO_FIELDS})
+    out = v7()
+    C.memmove(C.addressof(out), C.addressof(cfg), min(C.sizeof(cfg), C.sizeof(out)))
+    out.struct_version = 7
+    out.lsubmesoscale_mixing = 1
+    for k, v in mix_submeso_nml.items():
+        if not hasattr(out, k):
+            raise AttributeError("pop_config has no field %r" % k)
+        setattr(out, k, v)
+    return out
+
+
 class PopGridInput(C.Structure):
     """include/pop_amd.h pop_grid_input"""
     _fields_ = [(n, C.POINTER(C.c_double)) for n in ("ULAT", "ULON", "HTN", "HTE", "HUS", "HUW", "ANGLE")] + [("KMT", C.POINTER(C.c_int)),

@@ -672,6 +672,11 @@ int host_build(HostModel &h) {
       GRBR[p] = r;
     }
   }
+  if (c.lsubmesoscale_mixing) {   // init_submeso (mix_submeso.F90:266-269): TIME_SCALE of every cell of every block, ghost cells included
+    auto &TS = newf("SUBM_TIME_SCALE");
+    const double tsc = (c.time_scale_constant != 0.0) ? c.time_scale_constant : 3.456e5;
+    for (size_t p = 0; p < A2; ++p) TS[p] = 1.0 / std::sqrt(FCORT[p] * FCORT[p] + 1.0 / (tsc * tsc));
+  }
   // ---------------- del2 operator weights, metric advection coefficients ----------------
   auto &AMF = newf("AMF"), &AHF = newf("AHF");
   for (size_t p = 0; p < A2; ++p) { AMF[p] = 1.0; AHF[p] = 1.0; }

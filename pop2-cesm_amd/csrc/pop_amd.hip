@@ -12,6 +12,7 @@
 #include "kernels_thomas_reg.hpp"
 #include "kernels_momentum_lds.hpp"
 #include "kernels_aniso.hpp"
+#include "kernels_submeso.hpp"
 #include "kernels_tracer_lds.hpp"
 #include "kernels_rf.hpp"
 #include "kernels_pcsi.hpp"
@@ -82,6 +83,16 @@ int resolve(pop_ctx *c, const std::string &name, int tl, int n, double **ptr, lo
   if (name == "TLT_DIABATIC_DEPTH") return ok(c->gm.DD, a2);
   if (name == "TLT_THICKNESS") return ok(c->gm.TH, a2);
   if (name == "TLT_INTERIOR_DEPTH") return ok(c->gm.ID, a2);
+  // lsubmesoscale_mixing: the mixed-layer depth and length scale of submeso_sf; with submeso_diag the tendency on its own and the velocities
+  if (name == "SUBM_ML_DEPTH") return ok(c->subm.ML, a2);
+  if (name == "HLS_SUBM") return ok(c->subm.HLS, a2);
+  if (name == "SUBM_BX") return (n == 0 || n == 1) ? ok(c->subm.B[n], a2) : 1;
+  if (name == "SUBM_BY") return (n == 0 || n == 1) ? ok(c->subm.B[2 + n], a2) : 1;
+  if (name == "SUBM_ADV_TEND") return (n == 0 || n == 1) ? ok(c->subm.TD[n], a3) : 1;
+  if (name == "USUBM") return ok(c->subm.US, a3);
+  if (name == "VSUBM") return ok(c->subm.VS, a3);
+  if (name == "WSUBM") return ok(c->subm.WS, a3);
+  if (name == "GM_GTK") return (n == 0 || n == 1) ? ok(c->gm.GTK[n], a3) : 1;   // the mixing tendency the tracer right-hand side reads (hmix_tracer = 3)
   if (name == "HDU") return ok(c->HDU, a3);                   // hmix_momentum = 3: Hdiff(U), Hdiff(V) of hdiffu_aniso at every level
   if (name == "HDV") return ok(c->HDV, a3);
   if (name == "F_PARA") return ok(c->FPARA, a3);              // ... with lvariable_hmix_aniso
@@ -118,7 +129,7 @@ int pop_create_with_grid(const pop_config *cfg, const pop_grid_input *grid, int 
   X(kpp_src_full, "POP_KPP_SRC_FULL") X(solver_unfused, "POP_SOLVER_UNFUSED") X(solver_nograph, "POP_SOLVER_NOGRAPH")                   \
   X(solver_presum, "POP_SOLVER_PRESUM") X(solver_distributed, "POP_SOLVER_DISTRIBUTED") X(solver_overlap_off, "POP_SOLVER_OVERLAP_OFF") \
   X(fpcg_b2, "POP_FPCG_B2") X(pcsi_step2, "POP_PCSI_STEP2") X(halo_separate, "POP_HALO_SEPARATE")                                       \
-  X(halo_overlap_off, "POP_HALO_OVERLAP_OFF") X(rccl_overlap, "POP_RCCL_OVERLAP") X(evp_wave, "POP_EVP_WAVE") X(fpcg_a_pair, "POP_FPCG_A_PAIR") X(stream_priority, "POP_STREAM_PRIORITY") X(kpp_sparse, "POP_KPP_SPARSE") X(pbc_generic_thomas, "POP_PBC_GENERIC_THOMAS") X(pbc_generic_kpp, "POP_PBC_GENERIC_KPP") X(state3d_levels, "POP_STATE3D_LEVELS") X(gm_sf_stored, "POP_GM_SF_STORED") X(pcg_persist, "POP_PCG_PERSIST") X(gm_flux_tile, "POP_GM_FLUX_TILE") X(pcsi_two_step, "POP_PCSI_TWO_STEP") X(block_sums_relay, "POP_BLOCK_SUMS_RELAY") X(pcsi_evp_fused, "POP_PCSI_EVP_FUSED") X(aniso_side, "POP_ANISO_SIDE")
+  X(halo_overlap_off, "POP_HALO_OVERLAP_OFF") X(rccl_overlap, "POP_RCCL_OVERLAP") X(evp_wave, "POP_EVP_WAVE") X(fpcg_a_pair, "POP_FPCG_A_PAIR") X(stream_priority, "POP_STREAM_PRIORITY") X(kpp_sparse, "POP_KPP_SPARSE") X(pbc_generic_thomas, "POP_PBC_GENERIC_THOMAS") X(pbc_generic_kpp, "POP_PBC_GENERIC_KPP") X(state3d_levels, "POP_STATE3D_LEVELS") X(gm_sf_stored, "POP_GM_SF_STORED") X(pcg_persist, "POP_PCG_PERSIST") X(gm_flux_tile, "POP_GM_FLUX_TILE") X(pcsi_two_step, "POP_PCSI_TWO_STEP") X(block_sums_relay, "POP_BLOCK_SUMS_RELAY") X(pcsi_evp_fused, "POP_PCSI_EVP_FUSED") X(aniso_side, "POP_ANISO_SIDE") X(submeso_all_levels, "POP_SUBMESO_ALL_LEVELS")
 void pop_tuning_init(pop_tuning *t) {
   if (!t) return;
   t->struct_bytes = (int)sizeof(pop_tuning);
@@ -166,12 +177,14 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
   if (!cfg_in || !out || nranks < 1 || rank < 0 || rank >= nranks) return 1;
   pop_ctx *c = new pop_ctx();
   *out = c;
-  // a version-5 caller's struct ends at kappa_depth_scale: read that much only (the version-6 members stay 0)
+  // a version-5 caller's struct ends at kappa_depth_scale, a version-6 caller's at smag_lat_gauss: read that much only (the later members stay 0)
   if (cfg_in->struct_version == POP_CONFIG_VERSION) c->h.c = *cfg_in;
+  else if (cfg_in->struct_version == 6) memcpy(&c->h.c, cfg_in, offsetof(pop_config, lsubmesoscale_mixing));
   else memcpy(&c->h.c, cfg_in, offsetof(pop_config, aniso_alignment));
   const pop_config *cfg = &c->h.c;
   c->h.rank = rank; c->h.nranks = nranks;
   if (cfg->hmix_tracer == 3 && cfg->gm_transition_layer == 1 && cfg->vmix_choice == 3) c->h.c.kpp_ml_diagnostics = 1;   // the diabatic depth of the transition layer is the smoothed HMXL (hmix_gm.F90:1226-1228)
+  if (cfg->lsubmesoscale_mixing == 1 && cfg->vmix_choice == 3) c->h.c.kpp_ml_diagnostics = 1;   // ML_DEPTH of submeso_sf is HMXL (mix_submeso.F90:424-426)
   if (tuning && tuning->struct_bytes != (int)sizeof(pop_tuning)) { c->err = "pop_create_tuned: pop_tuning.struct_bytes does not match this library (use pop_tuning_init)"; return 1; }
   tuning_resolve(c->h.tun, tuning);
   c->grid_from_input = grid != nullptr;
@@ -180,7 +193,7 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
   {   // every option this library does not implement is refused here, before anything is built (the reference aborts
       // in the init routine of the option's own module, e.g. vertical_mix.F90:280-296, POP_SolversMod.F90:442-472)
     auto bad = [&](const std::string &m) { c->err = "pop_create: " + m; return 1; };
-    if (cfg->struct_version != POP_CONFIG_VERSION && cfg->struct_version != 5) return bad("pop_config.struct_version is " + std::to_string(cfg->struct_version) + ", this library reads 5 and " + std::to_string(POP_CONFIG_VERSION) + " (include/pop_amd.h)");
+    if (cfg->struct_version != POP_CONFIG_VERSION && cfg->struct_version != 6 && cfg->struct_version != 5) return bad("pop_config.struct_version is " + std::to_string(cfg->struct_version) + ", this library reads 5, 6 and " + std::to_string(POP_CONFIG_VERSION) + " (include/pop_amd.h)");
     if (cfg->reserved_i[0] != 0) return bad("pop_config.reserved_i must be 0");
     if (cfg->gm_kappa_bkg_srfbl != 0 && cfg->gm_kappa_bkg_srfbl != 1) return bad("gm_kappa_bkg_srfbl: 0 or 1");
     if (cfg->ah_bkg_bottom < 0.0) return bad("ah_bkg_bottom: >= 0");
@@ -220,6 +233,18 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
       if (cfg->vconst_7 < 0.0 || cfg->smag_lat_gauss < 0.0) return bad("vconst_7, smag_lat_gauss: > 0 (0 = 45, 98)");
     }
     if (cfg->hmix_tracer != 2 && cfg->hmix_tracer != 4 && cfg->hmix_tracer != 3) return bad("hmix_tracer: 2 (del2), 4 (del4) or 3 (gm)");
+    if (cfg->lsubmesoscale_mixing != 0 && cfg->lsubmesoscale_mixing != 1) return bad("lsubmesoscale_mixing: 0 or 1");
+    if (cfg->lsubmesoscale_mixing) {   // mix_submeso_nml (mix_submeso.F90:164-232); a struct_version < 7 never gets here: its switch is not read
+      if (cfg->hmix_tracer != 3)
+        return bad("lsubmesoscale_mixing with hmix_tracer = 2 | 4 is not built: the reference allows it (horizontal_mix.F90:566-581), CESM never selects it, "
+                   "and the del2 / del4 tracer right-hand-side kernels have no additive tendency input; use hmix_tracer = 3 (gm)");
+      if (cfg->partial_bottom_cells) return bad("lsubmesoscale_mixing with partial_bottom_cells: its fluxes use dz(k), as Gent-McWilliams', which is refused with them");
+      if (cfg->luse_const_horiz_len_scale != 0 && cfg->luse_const_horiz_len_scale != 1) return bad("luse_const_horiz_len_scale: 0 or 1");
+      if (cfg->submeso_diag != 0 && cfg->submeso_diag != 1) return bad("submeso_diag: 0 or 1");
+      if (cfg->efficiency_factor < 0.0) return bad("efficiency_factor: >= 0 (0 = 0.07)");
+      if (cfg->time_scale_constant < 0.0) return bad("time_scale_constant: >= 0 (0 = 3.456e5 s)");
+      if (cfg->hor_length_scale < 0.0) return bad("hor_length_scale: >= 0 (0 = 5e5 cm)");
+    }
     if (cfg->vmix_choice < 1 || cfg->vmix_choice > 3) return bad("vmix_choice: 1 const, 2 rich, 3 kpp");
     if (cfg->tadvect < 1 || cfg->tadvect > 3) return bad("tadvect: 1 centered, 2 upwind3, 3 lw_lim");
     if (cfg->solver_choice < 1 || cfg->solver_choice > 3) return bad("solver_choice: 1 pcg, 2 ChronGear, 3 PCSI");
@@ -514,6 +539,24 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
     G.diff_tapering = G.slm_r != G.slm_b;                              // :964-968
     G.cancellation = !(G.diff_tapering || G.ah != G.ah_bolus) && !G.tlt;   // :970-987 (both kappa types equal)
     if (!G.cancellation && !tun_off(h.tun.gm_sf_stored)) for (int t = 0; t < 8; ++t) if (dev_alloc(c, &G.SF[t], a3g)) return 1;
+  }
+  if (cfg->lsubmesoscale_mixing) {   // submesoscale scheme: six 2-D fields; with submeso_diag the tendency alone and the velocities
+    const size_t a2s = h.n2 * h.nblocks, a3s = h.n3 * h.nblocks;
+    SubmDev &W = c->subm;
+    if (dev_alloc(c, &W.ML, a2s) || dev_alloc(c, &W.HLS, a2s)) return 1;
+    for (int t = 0; t < 4; ++t) if (dev_alloc(c, &W.B[t], a2s)) return 1;
+    if (cfg->submeso_diag) {
+      if (dev_alloc(c, &W.TD[0], a3s) || dev_alloc(c, &W.TD[1], a3s) || dev_alloc(c, &W.US, a3s) || dev_alloc(c, &W.VS, a3s) || dev_alloc(c, &W.WS, a3s)) return 1;
+    }
+    W.GTK[0] = c->gm.GTK[0]; W.GTK[1] = c->gm.GTK[1];
+    W.TS = c->d2["SUBM_TIME_SCALE"]; W.HYX = c->gm.HYX; W.HXY = c->gm.HXY; W.DXT = c->gm.DXT; W.DYT = c->gm.DYT; W.HTE = c->d2["HTE"]; W.HTN = c->d2["HTN"];
+    if (!W.TS || !W.HTE || !W.HTN) { c->err = "submeso: TIME_SCALE / HTE / HTN missing"; return 1; }
+    // mix_submeso_nml (mix_submeso.F90:183-188); 0 = the code default
+    W.eff = (cfg->efficiency_factor != 0.0) ? cfg->efficiency_factor : 0.07;
+    W.hls0 = (cfg->hor_length_scale != 0.0) ? cfg->hor_length_scale : 5.0e5;
+    W.max_hgs = 111.0e5;
+    W.const_hls = cfg->luse_const_horiz_len_scale;
+    W.all_levels = tun_on(h.tun.submeso_all_levels) ? 1 : 0;
   }
 #define GI(f) g.f = c->di2[#f]
   GI(KMT); GI(KMU); GI(KMTN); GI(KMTS); GI(KMTE); GI(KMTW); GI(KMTEE); GI(KMTNN);
@@ -966,7 +1009,8 @@ int pop_local_block_ids(const pop_ctx *c, int *ids) { std::copy(c->h.local_ids.b
 long long pop_field_count(const pop_ctx *c, const char *name) {
   const std::string n(name);
   const long long a2 = (long long)c->h.n2 * c->h.nblocks, a3 = (long long)c->h.n3 * c->h.nblocks;
-  for (const char *s : {"TRACER", "UVEL", "VVEL", "RHO", "KPP_SRC", "VVC", "UISOP", "VISOP", "WISOP", "GM_SF_SLX", "GM_SF_SLY", "HDU", "HDV", "F_PARA", "F_PERP"}) if (n == s) return a3;
+  for (const char *s : {"TRACER", "UVEL", "VVEL", "RHO", "KPP_SRC", "VVC", "UISOP", "VISOP", "WISOP", "GM_SF_SLX", "GM_SF_SLY", "HDU", "HDV", "F_PARA", "F_PERP",
+                        "SUBM_ADV_TEND", "USUBM", "VSUBM", "WSUBM", "GM_GTK"}) if (n == s) return a3;
   if (n == "VDC") return (long long)c->h.n2 * (c->h.km + 2) * c->h.nblocks;
   return a2;
 }
@@ -1306,6 +1350,25 @@ static int kpp_look_ahead(pop_ctx *c) {
   c->ahead_valid = true; c->ahead_slot = c->curt;
   return 0;
 }
+// lsubmesoscale_mixing (horizontal_mix.F90:566-581, mix_submeso.F90:341-1005): the column fields of submeso_sf from the mix-time tracers and this
+// step's HMXL, then the tendency of submeso_flux added to GTK, which k_gm_flux has just written on the same stream
+static int phase_submeso(pop_ctx *c, const double *T, const double *S) {
+  SubmDev W = c->subm;
+  W.HMXL = (c->h.c.vmix_choice == 3) ? c->HMXL : nullptr;    // ML_DEPTH = HMXL | zw(1) (:424-426)
+  W.grav = step_params(c).grav; W.sqrt_grav = std::sqrt(W.grav);
+  const dim3 G2((c->g.n2 + 255) / 256, c->g.nblocks);
+  hipLaunchKernelGGL(k_submeso_column, G2, dim3(256), 0, c->stream, c->g, W, T, S);
+  if (W.TD[0]) {   // the levels below the march hold 0
+    const size_t bytes = (size_t)c->g.n3 * c->g.nblocks * sizeof(double);
+    HIPCHK(c, hipMemsetAsync(W.TD[0], 0, bytes, c->stream));
+    HIPCHK(c, hipMemsetAsync(W.TD[1], 0, bytes, c->stream));
+  }
+  const dim3 GT(((c->g.nxb + POP_SUBM_TX - 1) / POP_SUBM_TX) * ((c->g.nyb + POP_SUBM_TY - 1) / POP_SUBM_TY), c->g.nblocks);
+  hipLaunchKernelGGL(k_submeso_flux, GT, dim3(POP_SUBM_TX, POP_SUBM_TY), 0, c->stream, c->g, W, T, S);
+  if (W.US) hipLaunchKernelGGL(k_submeso_vel, G2, dim3(256), 0, c->stream, c->g, W);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
 // hmix_tracer = 3 (horizontal_mix.F90:549-554, hmix_gm.F90:1102-2226): slopes and tapered diffusivities of the mix-time tracers, the
 // isopycnal part added to VDC (after vmix_coeffs, before the tracer right-hand side reads it), and the tendency GTK of both tracers
 static int phase_hmix_gm(pop_ctx *c) {
@@ -1346,6 +1409,7 @@ static int phase_hmix_gm(pop_ctx *c) {
   } else
   hipLaunchKernelGGL(k_gm_flux, dim3(G3.x, (c->g.km + POP_GM_KC - 1) / POP_GM_KC, G3.z), dim3(256), 0, c->stream, c->g, G, T, S, c->VDC[0], v1);
   HIPCHK(c, hipGetLastError());
+  if (c->h.c.lsubmesoscale_mixing) return phase_submeso(c, T, S);
   return 0;
 }
 static int phase_hmix_tracer(pop_ctx *c, hipStream_t st = nullptr) {   // del4: first Laplacian of the tracers into d2t; gm: the whole tendency

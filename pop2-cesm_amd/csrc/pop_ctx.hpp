@@ -141,6 +141,7 @@ struct pop_ctx {
   double rf_S[MAXNT] = {}, rf_S_prev[MAXNT] = {}; bool rf_S_prev_valid[MAXNT] = {};   // Robert filter
   Upw3Dev upw3{};                                          // tadvect = 2
   LwDev lw{};                                              // tadvect = 3 (lw_lim): flux-velocity and work fields
+  SubmDev subm{};                                          // lsubmesoscale_mixing: the column fields of submeso_sf, diagnostics
   GmDev gm{};                                              // hmix_tracer = 3 (gm): slopes, tapered diffusivities, GTK
   RcclTransport *rccl_tr = nullptr;                       // in-library RCCL transport (pop_comm_init_rccl)
   // time stepping

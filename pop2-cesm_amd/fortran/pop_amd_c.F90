@@ -12,7 +12,7 @@
    integer (c_int), parameter :: POP_CREATE_HOST_ONLY = 1
 
    ! mirrors `struct pop_config` field for field
-   integer (c_int), parameter :: POP_CONFIG_VERSION = 6
+   integer (c_int), parameter :: POP_CONFIG_VERSION = 7
 
    type, bind(C) :: pop_config
       integer (c_int) :: struct_version = POP_CONFIG_VERSION
@@ -60,6 +60,9 @@
       real (c_double) :: vconst_1 = 0.0_c_double, vconst_2 = 0.0_c_double, vconst_3 = 0.0_c_double, vconst_4 = 0.0_c_double
       real (c_double) :: vconst_6 = 0.0_c_double, vconst_7 = 0.0_c_double
       real (c_double) :: smag_lat = 0.0_c_double, smag_lat_fact = 0.0_c_double, smag_lat_gauss = 0.0_c_double
+      ! layout 7: lsubmesoscale_mixing (hmix_nml) and mix_submeso_nml (mix_submeso.F90:164-188); 0 = the code default (include/pop_amd.h)
+      integer (c_int) :: lsubmesoscale_mixing = 0, luse_const_horiz_len_scale = 0, submeso_diag = 0
+      real (c_double) :: efficiency_factor = 0.0_c_double, time_scale_constant = 0.0_c_double, hor_length_scale = 0.0_c_double
    end type pop_config
 
    ! mirrors `struct pop_grid_input`: the records of horiz_grid_file / topography_file (grid.F90:1314-1542, 2025-2107)
@@ -85,6 +88,7 @@
       integer (c_int) :: block_sums_relay
       integer (c_int) :: pcsi_evp_fused
       integer (c_int) :: aniso_side
+      integer (c_int) :: submeso_all_levels
    end type pop_tuning
 
    type (c_ptr), save :: pop_ctx = c_null_ptr   ! the one model instance of this task
