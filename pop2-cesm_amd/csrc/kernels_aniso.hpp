@@ -203,8 +203,7 @@ __global__ void __launch_bounds__(ANI_TX * ANI_TY) k_hdiffu_aniso(DevGrid g, Ani
 
 inline void launch_hdiffu_aniso(const DevGrid &g, const AnisoArgs &a, hipStream_t st) {
   const dim3 B(ANI_TX, ANI_TY), G((g.nxb - 2 * NGHOST + ANI_TX - 1) / ANI_TX, (g.nyb - 2 * NGHOST + ANI_TY - 1) / ANI_TY, g.nblocks);
-  if (g.pbc) hipLaunchKernelGGL((k_hdiffu_aniso<true>), G, B, 0, st, g, a);
-  else hipLaunchKernelGGL((k_hdiffu_aniso<false>), G, B, 0, st, g, a);
+  with_flags([&](auto PBC) { hipLaunchKernelGGL((k_hdiffu_aniso<PBC.value>), G, B, 0, st, g, a); }, g.pbc);
 }
 
 }  // namespace pop

@@ -92,10 +92,10 @@ k_state3d_lv(DevGrid g, const double *__restrict__ T, const double *__restrict__
 }
 inline void launch_state3d(const DevGrid &g, const double *T, const double *S, double *RHO, hipStream_t st) {
   const unsigned gx = (g.n2 + 255) / 256;
-  if (g.state_lv == 4 && g.eosP) hipLaunchKernelGGL(k_state3d_lv<4>, dim3(gx, (g.km + 3) / 4, g.nblocks), dim3(256), 0, st, g, T, S, RHO);
-  else if (g.state_lv == 2 && g.eosP) hipLaunchKernelGGL(k_state3d_lv<2>, dim3(gx, (g.km + 1) / 2, g.nblocks), dim3(256), 0, st, g, T, S, RHO);
-  else if (g.state_lv == 8 && g.eosP) hipLaunchKernelGGL(k_state3d_lv<8>, dim3(gx, (g.km + 7) / 8, g.nblocks), dim3(256), 0, st, g, T, S, RHO);
-  else hipLaunchKernelGGL(k_state3d, dim3(gx, g.km, g.nblocks), dim3(256), 0, st, g, T, S, RHO);
+  const bool lv = with_value<2, 4, 8>(g.eosP ? g.state_lv : 0, [&](auto LV) {
+    hipLaunchKernelGGL(k_state3d_lv<LV.value>, dim3(gx, (g.km + LV.value - 1) / LV.value, g.nblocks), dim3(256), 0, st, g, T, S, RHO);
+  });
+  if (!lv) hipLaunchKernelGGL(k_state3d, dim3(gx, g.km, g.nblocks), dim3(256), 0, st, g, T, S, RHO);
 }
 
 // ------------------------------------------------------------------------------------------

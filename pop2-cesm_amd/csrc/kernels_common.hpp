@@ -1,8 +1,25 @@
 // kernels_common.hpp -- shared device helpers: MWJF equation of state, column indexing.
 #pragma once
 #include "device_types.hpp"
+#include <type_traits>
 
 namespace pop {
+
+// Run-time flags -> template arguments of a launch (host side).  with_flags(f, b0, b1, ...) calls f with one
+// std::bool_constant per flag, so a kernel that is a template over the flags is launched from ONE statement:
+//   with_flags([&](auto PRE, auto PBC) { hipLaunchKernelGGL((k<PRE.value, PBC.value>), G, B, 0, st, args); }, pre, g.pbc);
+// Every combination of the flags is instantiated: where a kernel has no such instantiation, pass the conjunction of
+// flags the selection tests or guard the launch with `if constexpr`.
+template <class F> inline void with_flags(F &&f) { f(); }
+template <class F, class... Bs> inline void with_flags(F &&f, bool b, Bs... bs) {
+  if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, bs...);
+  else with_flags([&](auto... c) { f(std::false_type{}, c...); }, bs...);
+}
+// The same for one integer of a small closed set: with_value<60, 62>(g.km, f) calls f(std::integral_constant<int, 60>{}) or
+// <int, 62>; false (and no call) when v is none of them.
+template <int... Vs, class F> inline bool with_value(int v, F &&f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
 
 #define POP_COL_THREADS 64   // one wavefront per workgroup for column-march kernels
 // waves per SIMD the stencil column kernels are compiled for (second __launch_bounds__ argument)

@@ -94,8 +94,7 @@ inline int mix_hdifft_del4(const HostModel &h, const DevGrid &g, const StepParam
                            double *D0, double *D1, double *, double *, hipStream_t st, std::string &err) {
   const int tile = patch_rows(g, h.tun.del4_tile);
   const dim3 G(patch_grid_x(g, tile), (g.km + POP_DEL4_KC - 1) / POP_DEL4_KC, g.nblocks), B(tile ? 64 * tile : 256);
-  if (g.pbc) hipLaunchKernelGGL(k_del4_d2t<true>, G, B, 0, st, g, m.D4AHF, T0, T1, D0, D1, tile);
-  else hipLaunchKernelGGL(k_del4_d2t<false>, G, B, 0, st, g, m.D4AHF, T0, T1, D0, D1, tile);
+  with_flags([&](auto PBC) { hipLaunchKernelGGL(k_del4_d2t<PBC.value>, G, B, 0, st, g, m.D4AHF, T0, T1, D0, D1, tile); }, g.pbc);
   if (hipGetLastError() != hipSuccess) { err = "del4 tracer kernel launch failed"; return 1; }
   return 0;
 }
@@ -103,8 +102,7 @@ inline int mix_hdiffu_del4(const HostModel &h, const DevGrid &g, const StepParam
                            double *DU, double *DV, double *, double *, hipStream_t st, std::string &err) {
   const int tile = patch_rows(g, h.tun.del4_tile);
   const dim3 G(patch_grid_x(g, tile), (g.km + POP_DEL4_KC - 1) / POP_DEL4_KC, g.nblocks), B(tile ? 64 * tile : 256);
-  if (g.pbc) hipLaunchKernelGGL(k_del4_d2u<true>, G, B, 0, st, g, m.D4AMF, U, V, DU, DV, tile);
-  else hipLaunchKernelGGL(k_del4_d2u<false>, G, B, 0, st, g, m.D4AMF, U, V, DU, DV, tile);
+  with_flags([&](auto PBC) { hipLaunchKernelGGL(k_del4_d2u<PBC.value>, G, B, 0, st, g, m.D4AMF, U, V, DU, DV, tile); }, g.pbc);
   if (hipGetLastError() != hipSuccess) { err = "del4 momentum kernel launch failed"; return 1; }
   return 0;
 }

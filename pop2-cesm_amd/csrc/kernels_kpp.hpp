@@ -1565,120 +1565,95 @@ inline int kpp_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParam
   double *DBLOC = s.S3a, *DBSFC = s.S3b, *WU = s.S3c, *VISC = s.S3d, *RIW = s.E3;
   // level-parallel LDS form (bit 2 of the mask; the default on bandwidth-bound grids, linear column order only)
   const dim3 GL(col_grid_x(g.n2, POP_COL_THREADS), g.nblocks), BL(POP_COL_THREADS, 4);
+
+  // ---- selection: which form of every stage runs (no launch above the pipeline below)
   // bit 3: buoydiff and the interior coefficients in ONE level-parallel launch
   const bool fused_bi = (g_kpp_col & 8) && KH.max_kref <= 20 && g.xcd_remap != 2 && g.km <= 64;
+  const bool lds = (g_kpp_col & 4) && KH.max_kref <= 28 && g.xcd_remap != 2;
   // the surface-layer buoyancy difference on demand inside the boundary-layer-depth march (k_kpp_bldepth<true, .>); POP_KPP_LAZY=0 keeps
   // the full field
   // (with the level-parallel fused kernel and with the plain 3-D buoydiff kernel; the column / LDS buoydiff forms keep the full field)
-  const bool plain3d = !fused_bi && !(g_kpp_col & 4 && KH.max_kref <= 28 && g.xcd_remap != 2) && !(g_kpp_col & 2);
+  const bool plain3d = !fused_bi && !lds && !(g_kpp_col & 2);
   const bool lazy = (fused_bi || plain3d) && KH.max_kref <= 28 && !g_kpp.lcheckekmo && h.c.kpp_ml_diagnostics != 1 &&
                     !tun_off(h.tun.kpp_lazy);
   const bool lazy20 = lazy && KH.max_kref <= 20;
-  // shear kernel limited by the previous evaluation's KBL (k_kpp_ushear_col): only with the on-demand march, which can form a level
-  // that is missing itself (POP_KPP_USHEAR_HINT=0: every level; POP_KPP_USHEAR_MARGIN: levels beyond the hint, default 3)
-  if (lazy && (g_kpp_col & 1) && !tun_off(h.tun.kpp_ushear_hint)) {
-    g_kpp.WUK = KH.wuk;
-    if (tun_set(h.tun.kpp_ushear_margin)) g_kpp.wu_margin = h.tun.kpp_ushear_margin;
-  }
-  // the shear of the velocity against its surface-layer reference needs only U and V: on the side stream it overlaps the
-  // (VALU-bound) buoydiff and the interior kernel; bldepth waits for it
-  const hipStream_t su = KH.side ? KH.side : st;
   // bit 4: buoydiff + interior coefficients as one column march (one smoothing pass, no double diffusion)
   const bool march = lazy && fused_bi && (g_kpp_col & 16) && g_kpp.nsmooth == 1 && !g_kpp.ldbl_diff && g.km >= 3;
-  g_kpp.src_clear_all = s.src_clear_all;
-  if (g.pbc && march && lazy20 && (g_kpp_col & 1) && !tun_on(h.tun.pbc_generic_kpp)) {
-    // partial bottom cells on the production kernel selection (r3): the PBC instantiations of the column-march kernels
-    g_kpp.CONVB = (g.km <= 64 && !tun_off(h.tun.kpp_sparse)) ? KH.convb : nullptr;
-    if (KH.side) { hipEventRecord(KH.ev_fork, st); hipStreamWaitEvent(KH.side, KH.ev_fork, 0); }
-    hipLaunchKernelGGL((k_kpp_ushear_col<24, true>), GC, BC, 0, su, g, g_kpp, s.UMIX, s.VMIX, WU);
-    hipLaunchKernelGGL(k_kpp_buoy_interior_march<true>, GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], s.UMIX, s.VMIX, DBLOC, VISC, s.VDC[0], s.VDC[1]);
-    if (KH.side) { hipEventRecord(KH.ev_bd, st); hipStreamWaitEvent(KH.side, KH.ev_bd, 0); }
-    hipLaunchKernelGGL((k_kpp_bldepth<true, 20, true>), GC, BC, 0, su, g, g_kpp, s.TMIX[0], s.TMIX[1], s.STF[0], s.STF[1], (const double *)DBLOC,
-                       (const double *)DBSFC, (const double *)WU, s.UMIX, s.VMIX);
-    if (KH.side) { hipEventRecord(KH.ev_join, KH.side); hipStreamWaitEvent(st, KH.ev_join, 0); }
-    const bool sp_ = g_kpp.CONVB != nullptr;
-    if (sp_ && g_kpp.vdc_same) hipLaunchKernelGGL((k_kpp_blmix<true, true, true>), GC, BC, 0, st, g, sp, g_kpp, (const double *)DBLOC, s.STF[0], s.STF[1], VISC, s.VDC[0], s.VDC[1], s.KPP_SRC[0], s.KPP_SRC[1], s.HBLT);
-    else if (sp_) hipLaunchKernelGGL((k_kpp_blmix<true, false, true>), GC, BC, 0, st, g, sp, g_kpp, (const double *)DBLOC, s.STF[0], s.STF[1], VISC, s.VDC[0], s.VDC[1], s.KPP_SRC[0], s.KPP_SRC[1], s.HBLT);
-    else if (g_kpp.vdc_same) hipLaunchKernelGGL((k_kpp_blmix<true, true>), GC, BC, 0, st, g, sp, g_kpp, (const double *)DBLOC, s.STF[0], s.STF[1], VISC, s.VDC[0], s.VDC[1], s.KPP_SRC[0], s.KPP_SRC[1], s.HBLT);
-    else hipLaunchKernelGGL((k_kpp_blmix<true, false>), GC, BC, 0, st, g, sp, g_kpp, (const double *)DBLOC, s.STF[0], s.STF[1], VISC, s.VDC[0], s.VDC[1], s.KPP_SRC[0], s.KPP_SRC[1], s.HBLT);
-    launch_kpp_vvc(g, h, st, (const double *)VISC, s.VVC);
-    if (hipGetLastError() != hipSuccess) { err = "KPP kernel launch failed"; return 1; }
-    return 0;
-  }
-  if (g.pbc) {
-    // partial bottom cells (round 3): the 3-D-parallel / scratch-staged kernel forms carry the PBC branches; every level of the
-    // surface-layer buoyancy difference and of the shear is formed (no on-demand march)
-    g_kpp.WUK = nullptr; g_kpp.CONVB = nullptr;
-    hipLaunchKernelGGL(k_kpp_ushear<true>, G3, dim3(256), 0, st, g, g_kpp, s.UMIX, s.VMIX, WU);
-    hipLaunchKernelGGL(k_kpp_buoydiff<true>, G3, dim3(256), 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], DBLOC, DBSFC);
-    hipLaunchKernelGGL(k_kpp_interior<true>, GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], s.UMIX, s.VMIX, (const double *)DBLOC, RIW, VISC, s.VDC[0], s.VDC[1]);
-    hipLaunchKernelGGL((k_kpp_bldepth<false, 20, true>), GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], s.STF[0], s.STF[1], (const double *)DBLOC,
-                       (const double *)DBSFC, (const double *)WU, s.UMIX, s.VMIX);
-    if (g_kpp.vdc_same) hipLaunchKernelGGL((k_kpp_blmix<true, true>), GC, BC, 0, st, g, sp, g_kpp, (const double *)DBLOC, s.STF[0], s.STF[1], VISC, s.VDC[0], s.VDC[1],
-                                            s.KPP_SRC[0], s.KPP_SRC[1], s.HBLT);
-    else hipLaunchKernelGGL((k_kpp_blmix<true, false>), GC, BC, 0, st, g, sp, g_kpp, (const double *)DBLOC, s.STF[0], s.STF[1], VISC, s.VDC[0], s.VDC[1],
-                            s.KPP_SRC[0], s.KPP_SRC[1], s.HBLT);
-    if (h.c.kpp_ml_diagnostics == 1 && s.HMXL && s.HMXL_DR)   // DBSFC holds every level here (the diagnostics switch the on-demand march off)
-      hipLaunchKernelGGL(k_kpp_hmxl, GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], (const double *)DBSFC, s.HMXL, s.HMXL_DR);
-    launch_kpp_vvc(g, h, st, (const double *)VISC, s.VVC);
-    if (hipGetLastError() != hipSuccess) { err = "KPP kernel launch failed"; return 1; }
-    return 0;
-  }
-  if (KH.side) { hipEventRecord(KH.ev_fork, st); hipStreamWaitEvent(KH.side, KH.ev_fork, 0); }
-  if (g_kpp_col & 1) hipLaunchKernelGGL(k_kpp_ushear_col<24>, GC, BC, 0, su, g, g_kpp, s.UMIX, s.VMIX, WU);
-  else hipLaunchKernelGGL(k_kpp_ushear<false>, G3, dim3(256), 0, su, g, g_kpp, s.UMIX, s.VMIX, WU);
+  // partial bottom cells: the PBC instantiations of the production (column-march) selection where it applies (r3), else the
+  // 3-D-parallel / scratch-staged forms, which carry the PBC branches: every level of the surface-layer buoyancy difference and
+  // of the shear formed (no on-demand march), one stream, no sparse mask
+  const bool pbc_generic = g.pbc && !(march && lazy20 && (g_kpp_col & 1) && !tun_on(h.tun.pbc_generic_kpp));
+  struct Sel {
+    bool shear_col;                                          // k_kpp_ushear_col<24, PBC>, else k_kpp_ushear<PBC>
+    enum { MARCH, FUSED_LDS, LDS, COL, PLAIN } buoy;         // MARCH and FUSED_LDS form the interior coefficients too
+    int buoy_kr; bool buoy_sfc, buoy_two_waves;              // <KR> of the LDS / column forms, <SFC> of the fused / plain ones
+    bool depth_lazy; int depth_kr;                           // k_kpp_bldepth<LAZY, KR, PBC>
+    enum { FUSED, REG, GENERIC } interior;
+    bool same, sparse;                                       // k_kpp_blmix<PBC, SAME, SPARSE>
+    bool side, wuk, convb;                                   // the side stream used; KppDev::WUK / CONVB set
+  } sel;
+  sel.shear_col = !pbc_generic && (g_kpp_col & 1);
+  sel.buoy = pbc_generic ? Sel::PLAIN : march ? Sel::MARCH : fused_bi ? Sel::FUSED_LDS : lds ? Sel::LDS : (g_kpp_col & 2) ? Sel::COL : Sel::PLAIN;
+  sel.buoy_kr = KH.max_kref <= 20 ? 20 : (sel.buoy == Sel::LDS ? 28 : 24);
+  sel.buoy_sfc = pbc_generic || !lazy;
   // two waves per SIMD (<= 256 VGPRs, ~80 spilled) beat one wave with everything in registers: the kernel is VALU-bound
   // and a second wave fills the division / dependency stalls of the first (POP_KPP_BUOY_WAVES=1 keeps one wave)
-  const int bw = tun_or(h.tun.kpp_buoy_waves, 2);
-  g_kpp.CONVB = (march && g.km <= 64 && !tun_off(h.tun.kpp_sparse)) ? KH.convb : nullptr;
-  if (march) hipLaunchKernelGGL(k_kpp_buoy_interior_march<false>, GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], s.UMIX, s.VMIX, DBLOC, VISC, s.VDC[0], s.VDC[1]);
-  else if (lazy && fused_bi) hipLaunchKernelGGL((k_kpp_buoy_interior_lds<20, 8, false>), GL, dim3(POP_COL_THREADS, 8), 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], s.UMIX, s.VMIX, DBLOC, DBSFC, VISC, s.VDC[0], s.VDC[1]);
-  else if (fused_bi) hipLaunchKernelGGL((k_kpp_buoy_interior_lds<20, 8>), GL, dim3(POP_COL_THREADS, 8), 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], s.UMIX, s.VMIX, DBLOC, DBSFC, VISC, s.VDC[0], s.VDC[1]);
-  else if ((g_kpp_col & 4) && KH.max_kref <= 20 && g.xcd_remap != 2) hipLaunchKernelGGL((k_kpp_buoydiff_lds<20, 4>), GL, BL, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], DBLOC, DBSFC);
-  else if ((g_kpp_col & 4) && KH.max_kref <= 28 && g.xcd_remap != 2) hipLaunchKernelGGL((k_kpp_buoydiff_lds<28, 4>), GL, BL, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], DBLOC, DBSFC);
-  else if ((g_kpp_col & 2) && KH.max_kref <= 20 && bw == 2) hipLaunchKernelGGL((k_kpp_buoydiff_col<20, 2>), GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], DBLOC, DBSFC);
-  else if ((g_kpp_col & 2) && KH.max_kref <= 20) hipLaunchKernelGGL((k_kpp_buoydiff_col<20, 1>), GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], DBLOC, DBSFC);
-  else if ((g_kpp_col & 2) && bw == 2) hipLaunchKernelGGL((k_kpp_buoydiff_col<24, 2>), GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], DBLOC, DBSFC);
-  else if (g_kpp_col & 2) hipLaunchKernelGGL((k_kpp_buoydiff_col<24, 1>), GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], DBLOC, DBSFC);
-  else if (lazy) hipLaunchKernelGGL(k_kpp_buoydiff<false>, G3, dim3(256), 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], DBLOC, DBSFC);
-  else hipLaunchKernelGGL(k_kpp_buoydiff<true>, G3, dim3(256), 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], DBLOC, DBSFC);
+  sel.buoy_two_waves = tun_or(h.tun.kpp_buoy_waves, 2) == 2;
+  sel.depth_lazy = !pbc_generic && lazy;
+  sel.depth_kr = (sel.depth_lazy && !lazy20) ? 28 : 20;
+  sel.interior = pbc_generic ? Sel::GENERIC : fused_bi ? Sel::FUSED :
+                 (!tun_on(h.tun.kpp_interior_generic) && (g.km == 60 || g.km == 62)) ? Sel::REG : Sel::GENERIC;
+  sel.same = g_kpp.vdc_same;
+  sel.convb = sel.sparse = !pbc_generic && march && g.km <= 64 && !tun_off(h.tun.kpp_sparse);
+  // the shear of the velocity against its surface-layer reference needs only U and V: on the side stream it overlaps the
+  // (VALU-bound) buoydiff and the interior kernel; bldepth waits for it
+  sel.side = KH.side && !pbc_generic;
+  // shear kernel limited by the previous evaluation's KBL (k_kpp_ushear_col): only with the on-demand march, which can form a level
+  // that is missing itself (POP_KPP_USHEAR_HINT=0: every level; POP_KPP_USHEAR_MARGIN: levels beyond the hint, default 3)
+  sel.wuk = sel.depth_lazy && (g_kpp_col & 1) && !tun_off(h.tun.kpp_ushear_hint);
+  g_kpp.WUK = sel.wuk ? KH.wuk : nullptr;
+  if (sel.wuk && tun_set(h.tun.kpp_ushear_margin)) g_kpp.wu_margin = h.tun.kpp_ushear_margin;
+  g_kpp.CONVB = sel.convb ? KH.convb : nullptr;
+  g_kpp.src_clear_all = s.src_clear_all;
+
+  // ---- pipeline: fork, shear, buoyancy (+ interior), depth march, interior, join, blmix, vvc, hmxl
+  const hipStream_t side = sel.side ? KH.side : nullptr, su = side ? side : st;
+  if (side) { hipEventRecord(KH.ev_fork, st); hipStreamWaitEvent(side, KH.ev_fork, 0); }
+  with_flags([&](auto COL, auto PBC) {
+    if constexpr (COL.value) hipLaunchKernelGGL((k_kpp_ushear_col<24, PBC.value>), GC, BC, 0, su, g, g_kpp, s.UMIX, s.VMIX, WU);
+    else hipLaunchKernelGGL(k_kpp_ushear<PBC.value>, G3, dim3(256), 0, su, g, g_kpp, s.UMIX, s.VMIX, WU);
+  }, sel.shear_col, g.pbc);
+  const auto T0 = s.TMIX[0], T1 = s.TMIX[1];
+  if (sel.buoy == Sel::MARCH) with_flags([&](auto PBC) { hipLaunchKernelGGL(k_kpp_buoy_interior_march<PBC.value>, GC, BC, 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, DBLOC, VISC, s.VDC[0], s.VDC[1]); }, g.pbc);
+  else if (sel.buoy == Sel::FUSED_LDS) with_flags([&](auto SFC) { hipLaunchKernelGGL((k_kpp_buoy_interior_lds<20, 8, SFC.value>), GL, dim3(POP_COL_THREADS, 8), 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, DBLOC, DBSFC, VISC, s.VDC[0], s.VDC[1]); }, sel.buoy_sfc);
+  else if (sel.buoy == Sel::LDS) with_value<20, 28>(sel.buoy_kr, [&](auto KR) { hipLaunchKernelGGL((k_kpp_buoydiff_lds<KR.value, 4>), GL, BL, 0, st, g, g_kpp, T0, T1, DBLOC, DBSFC); });
+  else if (sel.buoy == Sel::COL) with_flags([&](auto KR24, auto W2) { hipLaunchKernelGGL((k_kpp_buoydiff_col<KR24.value ? 24 : 20, W2.value ? 2 : 1>), GC, BC, 0, st, g, g_kpp, T0, T1, DBLOC, DBSFC); }, sel.buoy_kr == 24, sel.buoy_two_waves);
+  else with_flags([&](auto SFC) { hipLaunchKernelGGL(k_kpp_buoydiff<SFC.value>, G3, dim3(256), 0, st, g, g_kpp, T0, T1, DBLOC, DBSFC); }, sel.buoy_sfc);
   // the boundary-layer depth (needs buoydiff + shear, writes only the 2-D boundary-layer fields) follows the shear kernel
-  // on the side stream and runs beside the interior coefficients; blmix waits for both
-  if (KH.side) {
-    hipEventRecord(KH.ev_bd, st); hipStreamWaitEvent(KH.side, KH.ev_bd, 0);
-    if (lazy20) hipLaunchKernelGGL((k_kpp_bldepth<true, 20>), GC, BC, 0, KH.side, g, g_kpp, s.TMIX[0], s.TMIX[1], s.STF[0], s.STF[1], (const double *)DBLOC,
-                                   (const double *)DBSFC, (const double *)WU, s.UMIX, s.VMIX);
-    else if (lazy) hipLaunchKernelGGL((k_kpp_bldepth<true, 28>), GC, BC, 0, KH.side, g, g_kpp, s.TMIX[0], s.TMIX[1], s.STF[0], s.STF[1], (const double *)DBLOC,
-                                      (const double *)DBSFC, (const double *)WU, s.UMIX, s.VMIX);
-    else hipLaunchKernelGGL((k_kpp_bldepth<false, 20>), GC, BC, 0, KH.side, g, g_kpp, s.TMIX[0], s.TMIX[1], s.STF[0], s.STF[1], (const double *)DBLOC,
-                            (const double *)DBSFC, (const double *)WU, s.UMIX, s.VMIX);
-    hipEventRecord(KH.ev_join, KH.side);
+  // on the side stream and runs beside the interior coefficients; blmix waits for both.  Without the side stream it follows
+  // the interior coefficients.  KR = 28 exists for the on-demand march without partial bottom cells only.
+  auto depth = [&](hipStream_t sd) {
+    with_flags([&](auto LAZY, auto KR28, auto PBC) {
+      if constexpr (!KR28.value || (LAZY.value && !PBC.value))
+        hipLaunchKernelGGL((k_kpp_bldepth<LAZY.value, KR28.value ? 28 : 20, PBC.value>), GC, BC, 0, sd, g, g_kpp, T0, T1, s.STF[0], s.STF[1], (const double *)DBLOC, (const double *)DBSFC, (const double *)WU, s.UMIX, s.VMIX);
+    }, sel.depth_lazy, sel.depth_kr == 28, g.pbc);
+  };
+  if (side) {
+    hipEventRecord(KH.ev_bd, st); hipStreamWaitEvent(side, KH.ev_bd, 0);
+    depth(side);
+    hipEventRecord(KH.ev_join, side);
   }
-  const bool int_reg = !tun_on(h.tun.kpp_interior_generic);
-  if (fused_bi) {}
-  else if (int_reg && g.km == 60) hipLaunchKernelGGL(k_kpp_interior_reg<60>, GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], s.UMIX, s.VMIX, (const double *)DBLOC, VISC, s.VDC[0], s.VDC[1]);
-  else if (int_reg && g.km == 62) hipLaunchKernelGGL(k_kpp_interior_reg<62>, GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], s.UMIX, s.VMIX, (const double *)DBLOC, VISC, s.VDC[0], s.VDC[1]);
-  else hipLaunchKernelGGL(k_kpp_interior<false>, GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], s.UMIX, s.VMIX, (const double *)DBLOC, RIW, VISC, s.VDC[0], s.VDC[1]);
-  if (KH.side) hipStreamWaitEvent(st, KH.ev_join, 0);
-  else if (lazy20) hipLaunchKernelGGL((k_kpp_bldepth<true, 20>), GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], s.STF[0], s.STF[1], (const double *)DBLOC,
-                                      (const double *)DBSFC, (const double *)WU, s.UMIX, s.VMIX);
-  else if (lazy) hipLaunchKernelGGL((k_kpp_bldepth<true, 28>), GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], s.STF[0], s.STF[1], (const double *)DBLOC,
-                                    (const double *)DBSFC, (const double *)WU, s.UMIX, s.VMIX);
-  else hipLaunchKernelGGL((k_kpp_bldepth<false, 20>), GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], s.STF[0], s.STF[1], (const double *)DBLOC,
-                          (const double *)DBSFC, (const double *)WU, s.UMIX, s.VMIX);
-  const bool sparse = g_kpp.CONVB != nullptr;
-  if (sparse && g_kpp.vdc_same) hipLaunchKernelGGL((k_kpp_blmix<false, true, true>), GC, BC, 0, st, g, sp, g_kpp, (const double *)DBLOC, s.STF[0], s.STF[1], VISC, s.VDC[0], s.VDC[1],
-                                                   s.KPP_SRC[0], s.KPP_SRC[1], s.HBLT);
-  else if (sparse) hipLaunchKernelGGL((k_kpp_blmix<false, false, true>), GC, BC, 0, st, g, sp, g_kpp, (const double *)DBLOC, s.STF[0], s.STF[1], VISC, s.VDC[0], s.VDC[1],
-                                      s.KPP_SRC[0], s.KPP_SRC[1], s.HBLT);
-  else if (g_kpp.vdc_same) hipLaunchKernelGGL((k_kpp_blmix<false, true>), GC, BC, 0, st, g, sp, g_kpp, (const double *)DBLOC, s.STF[0], s.STF[1], VISC, s.VDC[0], s.VDC[1],
-                                          s.KPP_SRC[0], s.KPP_SRC[1], s.HBLT);
-  else hipLaunchKernelGGL((k_kpp_blmix<false, false>), GC, BC, 0, st, g, sp, g_kpp, (const double *)DBLOC, s.STF[0], s.STF[1], VISC, s.VDC[0], s.VDC[1],
-                          s.KPP_SRC[0], s.KPP_SRC[1], s.HBLT);
+  if (sel.interior == Sel::REG) with_value<60, 62>(g.km, [&](auto KM) { hipLaunchKernelGGL(k_kpp_interior_reg<KM.value>, GC, BC, 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, (const double *)DBLOC, VISC, s.VDC[0], s.VDC[1]); });
+  else if (sel.interior == Sel::GENERIC) with_flags([&](auto PBC) { hipLaunchKernelGGL(k_kpp_interior<PBC.value>, GC, BC, 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, (const double *)DBLOC, RIW, VISC, s.VDC[0], s.VDC[1]); }, g.pbc);
+  if (side) hipStreamWaitEvent(st, KH.ev_join, 0);
+  else depth(st);
+  with_flags([&](auto PBC, auto SAME, auto SPARSE) {
+    hipLaunchKernelGGL((k_kpp_blmix<PBC.value, SAME.value, SPARSE.value>), GC, BC, 0, st, g, sp, g_kpp, (const double *)DBLOC, s.STF[0], s.STF[1], VISC, s.VDC[0], s.VDC[1], s.KPP_SRC[0], s.KPP_SRC[1], s.HBLT);
+  }, g.pbc, sel.same, sel.sparse);
   // large grids: 64 x 4 patches (the row j + 1 of the four-point average is read by the same workgroup; 64 x 2 / 8 / 16 measured: vmix 7.54 / 7.65 / 7.97 ms against 7.57)
   launch_kpp_vvc(g, h, st, (const double *)VISC, s.VVC);
-  if (h.c.kpp_ml_diagnostics == 1 && s.HMXL && s.HMXL_DR)
-    hipLaunchKernelGGL(k_kpp_hmxl, GC, BC, 0, st, g, g_kpp, s.TMIX[0], s.TMIX[1], (const double *)DBSFC, s.HMXL, s.HMXL_DR);
+  if (h.c.kpp_ml_diagnostics == 1 && s.HMXL && s.HMXL_DR)   // DBSFC holds every level here (the diagnostics switch the on-demand march off)
+    hipLaunchKernelGGL(k_kpp_hmxl, GC, BC, 0, st, g, g_kpp, T0, T1, (const double *)DBSFC, s.HMXL, s.HMXL_DR);
   if (hipGetLastError() != hipSuccess) { err = "KPP kernel launch failed"; return 1; }
   return 0;
 }

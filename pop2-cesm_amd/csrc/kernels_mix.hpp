@@ -129,8 +129,7 @@ inline int mix_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParam
                            hipStream_t st, std::string &err) {
   const dim3 G3((g.n2 + 255) / 256, g.km, g.nblocks);
   if (h.c.vmix_choice == 2) {
-    if (g.pbc) hipLaunchKernelGGL(k_rich_t<true>, G3, dim3(256), 0, st, g, sp, s, s.S3c);
-    else hipLaunchKernelGGL(k_rich_t<false>, G3, dim3(256), 0, st, g, sp, s, s.S3c);
+    with_flags([&](auto PBC) { hipLaunchKernelGGL(k_rich_t<PBC.value>, G3, dim3(256), 0, st, g, sp, s, s.S3c); }, g.pbc);
     hipLaunchKernelGGL(k_rich_u, G3, dim3(256), 0, st, g, sp, s, (const double *)s.S3c);
     return 0;
   }

@@ -292,10 +292,9 @@ inline void launch_momentum_lds(const DevGrid &g, const StepParams &sp, const Mo
   if (tj_count <= 0) return;
   const bool whole = tj_first == 0 && tj_count == tiles_j;
   const dim3 G(whole ? lds_launch_x<R>(g, tiles_i, tiles_j) : lds_grid_x(g.lds_order, tiles_i, tj_count), g.nblocks), B(POP_COL_THREADS, R);
-  if (pre && g.pbc) hipLaunchKernelGGL((k_momentum_rhs_lds<R, true, true>), G, B, 0, st, g, sp, a, tj_first, tj_count);
-  else if (pre) hipLaunchKernelGGL((k_momentum_rhs_lds<R, false, true>), G, B, 0, st, g, sp, a, tj_first, tj_count);
-  else if (g.pbc) hipLaunchKernelGGL((k_momentum_rhs_lds<R, true>), G, B, 0, st, g, sp, a, tj_first, tj_count);
-  else hipLaunchKernelGGL((k_momentum_rhs_lds<R, false>), G, B, 0, st, g, sp, a, tj_first, tj_count);
+  with_flags([&](auto PBC, auto PRE) {
+    hipLaunchKernelGGL((k_momentum_rhs_lds<R, PBC.value, PRE.value>), G, B, 0, st, g, sp, a, tj_first, tj_count);
+  }, g.pbc, pre);
 }
 
 }  // namespace pop

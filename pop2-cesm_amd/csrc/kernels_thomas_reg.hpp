@@ -285,75 +285,49 @@ k_impvmixu_reg(DevGrid g, StepParams sp, ImpvmixuArgs a) {
   for (int k = 1; k <= KM; ++k) XN[c.base3 + (long long)(k - 1) * n2] = Xa[k - 1];
 }
 
-// dispatch on the level count: register kernels for the production grids, generic otherwise
+// dispatch on the level count: register kernels for the production grids (km = 60 / 62, with or without partial bottom cells),
+// the generic (scratch-staged) kernel otherwise
 template <int MODE, bool PRE, bool POST>
 inline void launch_impvmixt(const DevGrid &g, const StepParams &sp, const ImpvmixtArgs &a, dim3 G, hipStream_t st, bool allow_reg, int pair_tuning) {
   const dim3 B(POP_COL_THREADS);
   const dim3 G2(G.x, G.y, a.nlast - a.nfirst + 1);
+  const bool reg = allow_reg && (g.km == 60 || g.km == 62);
   // both tracers in one thread when they share the diffusivity array (pop_tuning.thomas_pair = 0 | 1 overrides the size rule)
-  const int pair_env = tun_or(pair_tuning, -1);
   // (corrector form only: the predictor's three full register columns + its up-front loads spill ~ 900 B per lane)
-  if (g.pbc) {   // partial bottom cells: the register kernels' PBC instantiations at km = 60 / 62, else the scratch-staged kernel
-    const bool reg = allow_reg && (g.km == 60 || g.km == 62);
-    const bool pairp = MODE == 1 && reg && a.nfirst == 1 && a.nlast == 2 && a.VDC[0] == a.VDC[1] &&
-                       (pair_env >= 0 ? pair_env != 0 : (long long)g.n2 * g.nblocks > (1 << 19));
-    if (!reg) { hipLaunchKernelGGL((k_impvmixt<MODE, PRE, POST, true>), G, B, 0, st, g, sp, a); return; }
-    if (pairp) {
-      if constexpr (MODE == 1) {
-        if (g.km == 60) hipLaunchKernelGGL((k_impvmixt2_reg<60, MODE, PRE, POST, true>), G, B, 0, st, g, sp, a);
-        else hipLaunchKernelGGL((k_impvmixt2_reg<62, MODE, PRE, POST, true>), G, B, 0, st, g, sp, a);
-      }
-    } else if (g.km == 60) hipLaunchKernelGGL((k_impvmixt_reg<60, MODE, PRE, POST, true>), G2, B, 0, st, g, sp, a);
-    else hipLaunchKernelGGL((k_impvmixt_reg<62, MODE, PRE, POST, true>), G2, B, 0, st, g, sp, a);
-    if (POST) launch_state3d(g, a.TNEW[0], a.TNEW[1], a.RHO, st);
-    return;
-  }
-  const bool pair = MODE == 1 && allow_reg && (g.km == 60 || g.km == 62) && a.nfirst == 1 && a.nlast == 2 && a.VDC[0] == a.VDC[1] &&
+  const int pair_env = tun_or(pair_tuning, -1);
+  const bool pair = MODE == 1 && reg && a.nfirst == 1 && a.nlast == 2 && a.VDC[0] == a.VDC[1] &&
                     (pair_env >= 0 ? pair_env != 0 : (long long)g.n2 * g.nblocks > (1 << 19));
-  if (pair) {
-    if constexpr (MODE == 1) {
-      if (g.km == 60) hipLaunchKernelGGL((k_impvmixt2_reg<60, MODE, PRE, POST>), G, B, 0, st, g, sp, a);
-      else hipLaunchKernelGGL((k_impvmixt2_reg<62, MODE, PRE, POST>), G, B, 0, st, g, sp, a);
-    }
-    if (POST) launch_state3d(g, a.TNEW[0], a.TNEW[1], a.RHO, st);
-  } else if (allow_reg && (g.km == 60 || g.km == 62)) {
-    if (g.km == 60) hipLaunchKernelGGL((k_impvmixt_reg<60, MODE, PRE, POST>), G2, B, 0, st, g, sp, a);
-    else hipLaunchKernelGGL((k_impvmixt_reg<62, MODE, PRE, POST>), G2, B, 0, st, g, sp, a);
+  with_flags([&](auto PBC) {
+    if (!reg) { hipLaunchKernelGGL((k_impvmixt<MODE, PRE, POST, PBC.value>), G, B, 0, st, g, sp, a); return; }
+    with_value<60, 62>(g.km, [&](auto KM) {
+      if constexpr (MODE == 1) {
+        if (pair) { hipLaunchKernelGGL((k_impvmixt2_reg<KM.value, MODE, PRE, POST, PBC.value>), G, B, 0, st, g, sp, a); return; }
+      }
+      hipLaunchKernelGGL((k_impvmixt_reg<KM.value, MODE, PRE, POST, PBC.value>), G2, B, 0, st, g, sp, a);
+    });
     // the density of the finished tracers (baroclinic.F90:1468-1475) as its own 3-D-parallel pass
     if (POST) launch_state3d(g, a.TNEW[0], a.TNEW[1], a.RHO, st);
-  } else hipLaunchKernelGGL((k_impvmixt<MODE, PRE, POST>), G, B, 0, st, g, sp, a);
+  }, g.pbc);
+}
+// the register kernel of the velocity solve, km = 60 / 62 only (false otherwise, nothing launched).  WAVES = 2 on small grids, never
+// with partial bottom cells.  ADD: with the barotropic velocity added on the way out (a.UB, a.VB set)
+template <bool ADD>
+inline bool launch_impvmixu_reg(const DevGrid &g, const StepParams &sp, const ImpvmixuArgs &a, dim3 G, hipStream_t st) {
+  const bool two = !g.pbc && (long long)g.n2 * g.nblocks <= (1 << 19);
+  return with_value<60, 62>(g.km, [&](auto KM) {
+    with_flags([&](auto TWO, auto PBC) {
+      if constexpr (!(TWO.value && PBC.value))
+        hipLaunchKernelGGL((k_impvmixu_reg<KM.value, TWO.value ? 2 : 1, ADD, PBC.value>), dim3(G.x, G.y, 2), dim3(POP_COL_THREADS), 0, st, g, sp, a);
+    }, two, g.pbc);
+  });
 }
 inline void launch_impvmixu(const DevGrid &g, const StepParams &sp, const ImpvmixuArgs &a, dim3 G, hipStream_t st, bool allow_reg) {
-  const dim3 B(POP_COL_THREADS);
-  const dim3 G2(G.x, G.y, 2);
-  const bool small = (long long)g.n2 * g.nblocks <= (1 << 19);
-  if (g.pbc) {
-    if (allow_reg && g.km == 60) hipLaunchKernelGGL((k_impvmixu_reg<60, 1, false, true>), G2, B, 0, st, g, sp, a);
-    else if (allow_reg && g.km == 62) hipLaunchKernelGGL((k_impvmixu_reg<62, 1, false, true>), G2, B, 0, st, g, sp, a);
-    else hipLaunchKernelGGL(k_impvmixu_norm<true>, G, B, 0, st, g, sp, a);
-    return;
-  }
-  if (allow_reg && g.km == 60 && small) hipLaunchKernelGGL((k_impvmixu_reg<60, 2>), G2, B, 0, st, g, sp, a);
-  else if (allow_reg && g.km == 60) hipLaunchKernelGGL((k_impvmixu_reg<60, 1>), G2, B, 0, st, g, sp, a);
-  else if (allow_reg && g.km == 62 && small) hipLaunchKernelGGL((k_impvmixu_reg<62, 2>), G2, B, 0, st, g, sp, a);
-  else if (allow_reg && g.km == 62) hipLaunchKernelGGL((k_impvmixu_reg<62, 1>), G2, B, 0, st, g, sp, a);
-  else hipLaunchKernelGGL(k_impvmixu_norm<false>, G, B, 0, st, g, sp, a);
+  if (allow_reg && launch_impvmixu_reg<false>(g, sp, a, G, st)) return;
+  with_flags([&](auto PBC) { hipLaunchKernelGGL(k_impvmixu_norm<PBC.value>, G, dim3(POP_COL_THREADS), 0, st, g, sp, a); }, g.pbc);
 }
-// the register kernel with the barotropic velocity added on the way out (a.UB, a.VB set); km = 60 / 62 only
 inline bool impvmixu_add_available(const DevGrid &g, bool allow_reg) { return allow_reg && (g.km == 60 || g.km == 62); }
 inline void launch_impvmixu_add(const DevGrid &g, const StepParams &sp, const ImpvmixuArgs &a, dim3 G, hipStream_t st) {
-  const dim3 B(POP_COL_THREADS);
-  const dim3 G2(G.x, G.y, 2);
-  const bool small = (long long)g.n2 * g.nblocks <= (1 << 19);
-  if (g.pbc) {
-    if (g.km == 60) hipLaunchKernelGGL((k_impvmixu_reg<60, 1, true, true>), G2, B, 0, st, g, sp, a);
-    else hipLaunchKernelGGL((k_impvmixu_reg<62, 1, true, true>), G2, B, 0, st, g, sp, a);
-    return;
-  }
-  if (g.km == 60 && small) hipLaunchKernelGGL((k_impvmixu_reg<60, 2, true>), G2, B, 0, st, g, sp, a);
-  else if (g.km == 60) hipLaunchKernelGGL((k_impvmixu_reg<60, 1, true>), G2, B, 0, st, g, sp, a);
-  else if (small) hipLaunchKernelGGL((k_impvmixu_reg<62, 2, true>), G2, B, 0, st, g, sp, a);
-  else hipLaunchKernelGGL((k_impvmixu_reg<62, 1, true>), G2, B, 0, st, g, sp, a);
+  launch_impvmixu_reg<true>(g, sp, a, G, st);
 }
 
 }  // namespace pop

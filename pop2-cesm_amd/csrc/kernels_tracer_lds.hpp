@@ -264,14 +264,10 @@ inline void launch_tracer_lds(const DevGrid &g, const StepParams &sp, const Trac
   const int tiles_i = (g.nxb - 2 * NGHOST + POP_COL_THREADS - 1) / POP_COL_THREADS;
   const int tiles_j = (g.nyb - 2 * NGHOST + R - 1) / R;
   const dim3 G(lds_launch_x<R>(g, tiles_i, tiles_j), g.nblocks), B(POP_COL_THREADS, R);
-  if (g.pbc) {
-    if (fwd) hipLaunchKernelGGL((k_tracer_rhs_lds<R, true, true>), G, B, 0, st, g, sp, a);
-    else hipLaunchKernelGGL((k_tracer_rhs_lds<R, false, true>), G, B, 0, st, g, sp, a);
-  } else if (a.HDT[0]) {   // the mixing tendency given (Gent-McWilliams; not with partial bottom cells: refused at create)
-    if (fwd) hipLaunchKernelGGL((k_tracer_rhs_lds<R, true, false, true>), G, B, 0, st, g, sp, a);
-    else hipLaunchKernelGGL((k_tracer_rhs_lds<R, false, false, true>), G, B, 0, st, g, sp, a);
-  } else if (fwd) hipLaunchKernelGGL((k_tracer_rhs_lds<R, true, false>), G, B, 0, st, g, sp, a);
-  else hipLaunchKernelGGL((k_tracer_rhs_lds<R, false, false>), G, B, 0, st, g, sp, a);
+  const bool hdt = a.HDT[0] && !g.pbc;   // the mixing tendency given (Gent-McWilliams; not with partial bottom cells: refused at create)
+  with_flags([&](auto FWD, auto PBC, auto HDT) {
+    if constexpr (!(PBC.value && HDT.value)) hipLaunchKernelGGL((k_tracer_rhs_lds<R, FWD.value, PBC.value, HDT.value>), G, B, 0, st, g, sp, a);
+  }, fwd, g.pbc, hdt);
 }
 
 }  // namespace pop

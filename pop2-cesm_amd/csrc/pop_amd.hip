@@ -1399,13 +1399,11 @@ static int phase_hmix_gm(pop_ctx *c) {
     // or the stream-function terms not stored (gm_sf_stored = 0): the cell-by-cell kernel
     const int R = (c->h.tun.gm_flux_tile == 4) ? 4 : 8;     // rows of the patch: 64 x 8 computing 63 x 7 cells (gm_flux_tile = 4: 64 x 4, measured 2 % of the step slower)
     const dim3 GT(((c->g.nxb + 62) / 63) * ((c->g.nyb + R - 2) / (R - 1)), (c->g.km + POP_GM_KC - 1) / POP_GM_KC, G3.z);
-    if (R == 8) {
-      if (G.cancellation) hipLaunchKernelGGL((k_gm_flux_tile<8, true>), GT, dim3(64, 8), 0, c->stream, c->g, G, T, S, c->VDC[0], v1);
-      else hipLaunchKernelGGL((k_gm_flux_tile<8, false>), GT, dim3(64, 8), 0, c->stream, c->g, G, T, S, c->VDC[0], v1);
-    } else {
-      if (G.cancellation) hipLaunchKernelGGL((k_gm_flux_tile<4, true>), GT, dim3(64, 4), 0, c->stream, c->g, G, T, S, c->VDC[0], v1);
-      else hipLaunchKernelGGL((k_gm_flux_tile<4, false>), GT, dim3(64, 4), 0, c->stream, c->g, G, T, S, c->VDC[0], v1);
-    }
+    with_value<4, 8>(R, [&](auto RV) {
+      with_flags([&](auto CANC) {
+        hipLaunchKernelGGL((k_gm_flux_tile<RV.value, CANC.value>), GT, dim3(64, RV.value), 0, c->stream, c->g, G, T, S, c->VDC[0], v1);
+      }, G.cancellation);
+    });
   } else
   hipLaunchKernelGGL(k_gm_flux, dim3(G3.x, (c->g.km + POP_GM_KC - 1) / POP_GM_KC, G3.z), dim3(256), 0, c->stream, c->g, G, T, S, c->VDC[0], v1);
   HIPCHK(c, hipGetLastError());
@@ -1427,23 +1425,20 @@ static int phase_hmix_tracer(pop_ctx *c, hipStream_t st = nullptr) {   // del4: 
 static int phase_advt_lw_lim(pop_ctx *c) {
   const int km = c->g.km;
   const double *X0 = c->TR[0][c->mixt], *X1 = c->TR[1][c->mixt];
-  if (c->g.pbc) hipLaunchKernelGGL(k_lw_flux<true>, grid_cols(c), dim3(POP_COL_THREADS), 0, c->stream, c->g, c->lw, (const double *)c->U[c->curt], (const double *)c->V[c->curt], (const double *)c->DH);
-  else hipLaunchKernelGGL(k_lw_flux<false>, grid_cols(c), dim3(POP_COL_THREADS), 0, c->stream, c->g, c->lw, (const double *)c->U[c->curt], (const double *)c->V[c->curt], (const double *)c->DH);
+  with_flags([&](auto PBC) {
+    hipLaunchKernelGGL(k_lw_flux<PBC.value>, grid_cols(c), dim3(POP_COL_THREADS), 0, c->stream, c->g, c->lw, (const double *)c->U[c->curt], (const double *)c->V[c->curt], (const double *)c->DH);
+  }, c->g.pbc);
   // UTE: E face, vector; WTKB: centre (comp_flux_vel_ghost :1080-1100).  VTN is not exchanged by the reference: it forms it in
   // the ghost rows from the ghost velocities.  Beyond a tripole fold those are the mirrored velocities with the sign of a
   // vector, so the N-face mirror of VTN with that sign is the same number (the two products are added in the other order);
   // the degenerate top row stays as computed (location 4: N face, ghost rows only).
   if (halo_update_many(c, {{c->lw.UTE, km, 3, 1}, {c->lw.VTN, km, 4, 1}, {c->lw.WTKB, km}})) return 1;
   const dim3 G3((c->g.n2 + 255) / 256, km, c->g.nblocks * 2);
-  if (c->g.pbc) {
-    hipLaunchKernelGGL(k_lw_z<true>, G3, dim3(256), 0, c->stream, c->g, c->lw, X0, X1, c->c2dtt);
-    hipLaunchKernelGGL(k_lw_x<true>, G3, dim3(256), 0, c->stream, c->g, c->lw, X0, X1, c->c2dtt);
-    hipLaunchKernelGGL(k_lw_y<true>, G3, dim3(256), 0, c->stream, c->g, c->lw, X0, X1, c->c2dtt);
-  } else {
-    hipLaunchKernelGGL(k_lw_z<false>, G3, dim3(256), 0, c->stream, c->g, c->lw, X0, X1, c->c2dtt);
-    hipLaunchKernelGGL(k_lw_x<false>, G3, dim3(256), 0, c->stream, c->g, c->lw, X0, X1, c->c2dtt);
-    hipLaunchKernelGGL(k_lw_y<false>, G3, dim3(256), 0, c->stream, c->g, c->lw, X0, X1, c->c2dtt);
-  }
+  with_flags([&](auto PBC) {
+    hipLaunchKernelGGL(k_lw_z<PBC.value>, G3, dim3(256), 0, c->stream, c->g, c->lw, X0, X1, c->c2dtt);
+    hipLaunchKernelGGL(k_lw_x<PBC.value>, G3, dim3(256), 0, c->stream, c->g, c->lw, X0, X1, c->c2dtt);
+    hipLaunchKernelGGL(k_lw_y<PBC.value>, G3, dim3(256), 0, c->stream, c->g, c->lw, X0, X1, c->c2dtt);
+  }, c->g.pbc);
   HIPCHK(c, hipGetLastError());
   return 0;
 }
@@ -1477,7 +1472,7 @@ static int phase_tracer_rhs(pop_ctx *c, bool fwd = false) {
   if (form_next) { a.D2N[0] = c->d2t_next[0]; a.D2N[1] = c->d2t_next[1]; a.AHF = c->mix.D4AHF; }
   c->d2t_last_formed = form_next;
   if (lds_kernel) {
-    if (c->trc_lds_rows == 8) launch_tracer_lds<8>(c->g, sp, a, c->stream, fwd); else launch_tracer_lds<4>(c->g, sp, a, c->stream, fwd);
+    with_value<4, 8>(c->trc_lds_rows, [&](auto R) { launch_tracer_lds<R.value>(c->g, sp, a, c->stream, fwd); });
     if (form_next && !c->phase_timing) {
       if (halo_update_many(c, {{c->d2t_next[0], c->g.km}, {c->d2t_next[1], c->g.km}})) return 1;
       c->d2t_next_valid = true; c->d2t_next_slot = c->curt;
@@ -1485,22 +1480,12 @@ static int phase_tracer_rhs(pop_ctx *c, bool fwd = false) {
     return 0;
   }
   if (fwd) { c->err = "fused forward elimination needs the LDS tracer kernel"; return 1; }
-  if (c->h.c.hmix_tracer == 3) {   // Gent-McWilliams: the tendency formed by phase_hmix_gm in place of del2 mixing
-    a.HDT[0] = c->gm.GTK[0]; a.HDT[1] = c->gm.GTK[1];
-    if (c->h.c.tadvect == 2) {
-      a.up = c->upw3;
-      if (c->g.pbc) hipLaunchKernelGGL((k_tracer_rhs<true, true, true>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, sp, a);
-      else hipLaunchKernelGGL((k_tracer_rhs<true, true>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, sp, a);
-    } else if (c->g.pbc) hipLaunchKernelGGL((k_tracer_rhs<true, false, true>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, sp, a);
-    else hipLaunchKernelGGL((k_tracer_rhs<true, false>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, sp, a);
-    return 0;
-  }
-  if (c->h.c.tadvect == 2) {
-    a.up = c->upw3;
-    if (c->g.pbc) hipLaunchKernelGGL((k_tracer_rhs<false, true, true>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, sp, a);
-    else hipLaunchKernelGGL((k_tracer_rhs<false, true>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, sp, a);
-  } else if (c->g.pbc) hipLaunchKernelGGL((k_tracer_rhs<false, false, true>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, sp, a);
-  else hipLaunchKernelGGL((k_tracer_rhs<false, false>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, sp, a);
+  const bool gm = c->h.c.hmix_tracer == 3, up3 = c->h.c.tadvect == 2;
+  if (gm) { a.HDT[0] = c->gm.GTK[0]; a.HDT[1] = c->gm.GTK[1]; }   // Gent-McWilliams: the tendency formed by phase_hmix_gm in place of del2 mixing
+  if (up3) a.up = c->upw3;
+  with_flags([&](auto GM, auto UP3, auto PBC) {
+    hipLaunchKernelGGL((k_tracer_rhs<GM.value, UP3.value, PBC.value>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, sp, a);
+  }, gm, up3, c->g.pbc);
   return 0;
 }
 static ImpvmixtArgs impvmixt_args(pop_ctx *c, const double *psfc) {
@@ -1583,12 +1568,10 @@ static int phase_momentum_rhs(pop_ctx *c, int tj_first = 0, int tj_count = -1, b
   c->d2u_last_formed = form_next;
   const bool pre = c->h.c.hmix_momentum == 3;   // anis: the friction phase_hmix_momentum formed
   if (pre) { a.HDU = c->HDU; a.HDV = c->HDV; }
-  if (c->mom_lds_rows == 8) launch_momentum_lds<8>(c->g, step_params(c), a, c->stream, tj_first, tj_count, pre);
-  else if (c->mom_lds_rows == 4) launch_momentum_lds<4>(c->g, step_params(c), a, c->stream, tj_first, tj_count, pre);
-  else if (pre && c->g.pbc) hipLaunchKernelGGL((k_momentum_rhs<true, true>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, step_params(c), a);
-  else if (pre) hipLaunchKernelGGL((k_momentum_rhs<true, false>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, step_params(c), a);
-  else if (c->g.pbc) hipLaunchKernelGGL((k_momentum_rhs<false, true>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, step_params(c), a);
-  else hipLaunchKernelGGL((k_momentum_rhs<false, false>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, step_params(c), a);
+  const bool lds = with_value<4, 8>(c->mom_lds_rows, [&](auto R) { launch_momentum_lds<R.value>(c->g, step_params(c), a, c->stream, tj_first, tj_count, pre); });
+  if (!lds) with_flags([&](auto PRE, auto PBC) {
+    hipLaunchKernelGGL((k_momentum_rhs<PRE.value, PBC.value>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, step_params(c), a);
+  }, pre, c->g.pbc);
   if (form_next && last_piece && !c->phase_timing) {
     if (halo_update_many(c, {{c->d2u_next[0], c->g.km, 1, 1}, {c->d2u_next[1], c->g.km, 1, 1}})) return 1;
     c->d2u_next_valid = true; c->d2u_next_slot = c->curt;
@@ -2064,8 +2047,9 @@ int pop_global_extreme(pop_ctx *c, const char *name, int tl, int n, const char *
   if (resolve(c, name, tl, n, &p, &cnt)) { c->err = std::string("unknown field ") + name; return 1; }
   if (mask_name && resolve(c, mask_name, 0, 0, &mk, &cnt)) { c->err = std::string("unknown mask ") + mask_name; return 1; }
   const dim3 G = grid_2d(c);
-  if (want_max) hipLaunchKernelGGL(k_extreme_partial<true>, G, dim3(POP_RED_THREADS), 0, c->stream, c->g, (const double *)p, (const double *)mk, c->partial);
-  else hipLaunchKernelGGL(k_extreme_partial<false>, G, dim3(POP_RED_THREADS), 0, c->stream, c->g, (const double *)p, (const double *)mk, c->partial);
+  with_flags([&](auto MAX) {
+    hipLaunchKernelGGL(k_extreme_partial<MAX.value>, G, dim3(POP_RED_THREADS), 0, c->stream, c->g, (const double *)p, (const double *)mk, c->partial);
+  }, want_max);
   const size_t np = (size_t)G.x * G.y;
   std::vector<double> part(2 * np);
   HIPCHK(c, hipMemcpyAsync(part.data(), c->partial, sizeof(double) * part.size(), hipMemcpyDeviceToHost, c->stream));
