@@ -259,6 +259,42 @@ int pop_read_grid_files(const char *horiz_grid_file, const char *topography_file
 int pop_destroy(pop_ctx *ctx);
 const char *pop_last_error(const pop_ctx *ctx);
 
+/* ---- tidal mixing (tidal_mixing.F90; vmix_kpp.F90:1758-1857): tidal_nml through an entry point of its own, as the
+ *      reference's init_tidal_mixing1 / init_tidal_mixing2 are calls separate from init_vmix_kpp.  The native (lcvmix = .false.)
+ *      Jayne and St. Laurent (2001) method only; the Schmittner and Polzin methods, ltidal_lunar_cycle, ltidal_schmittner_socn,
+ *      lniw_mixing and the CVMix path are not built.  A 0 in a double member stands for the code default. */
+#define POP_MAX_TIDAL_MIN_REGIONS 9   /* tidal_mixing.F90:262 max_tidal_min_regions */
+typedef struct pop_tidal_nml {
+  int struct_bytes;             /* sizeof(pop_tidal_nml) of the caller */
+  int ltidal_mixing;            /* 0: the call succeeds and builds nothing */
+  int tidal_mixing_method;      /* tidal_mixing_method_choice: 0 'jayne'; 1 'schmittner' and 2 'polzin' are refused */
+  int ltidal_max;               /* TIDAL_DIFF limited to tidal_mix_max (code default .true.) */
+  int ltidal_stabc;             /* stability control at the two levels above the bottom (code default .true.) */
+  int lccsm_control_compatible; /* 1 switches the stability control off (tidal_mixing.F90:3117) */
+  int ltidal_min_regions;       /* a floor of the tidal diffusivity near the bottom inside latitude / longitude boxes (code default .false.) */
+  int num_tidal_min_regions;    /* 0 .. POP_MAX_TIDAL_MIN_REGIONS */
+  int tidal_diag;               /* 1: "TIDAL_DIFF", "TIDAL_N2", "KVMIX", "KVMIX_M" of the last evaluation readable with pop_get_field
+                                 * (the KPP look-ahead is then off: the fields belong to the step that has run) */
+  double tidal_local_mixing_fraction;   /* 0 = 0.33 */
+  double tidal_mixing_efficiency;       /* 0 = 0.2 */
+  double vertical_decay_scale;          /* [cm], 0 = 500e2 */
+  double tidal_mix_max;                 /* [cm^2/s], 0 = 100 */
+  double tidal_min_values[POP_MAX_TIDAL_MIN_REGIONS];        /* [cm^2/s] (code default 20) */
+  double tidal_TLATmin_regions[POP_MAX_TIDAL_MIN_REGIONS];   /* degrees */
+  double tidal_TLATmax_regions[POP_MAX_TIDAL_MIN_REGIONS];
+  double tidal_TLONmin_regions[POP_MAX_TIDAL_MIN_REGIONS];   /* degrees east, 0 .. 360; min > max: the box wraps around 360 */
+  double tidal_TLONmax_regions[POP_MAX_TIDAL_MIN_REGIONS];
+  int tidal_min_regions_klevels[POP_MAX_TIDAL_MIN_REGIONS];  /* 2 | 6: levels above the bottom the floor applies to (any other value: none; code default 6) */
+} pop_tidal_nml;
+void pop_tidal_nml_init(pop_tidal_nml *nml);   /* struct_bytes = sizeof, the code defaults of tidal_mixing.F90:670-760 (ltidal_mixing = 0) */
+/* init_tidal_mixing1 / 2 (tidal_mixing.F90:542-1340) for the Jayne method.  energy_flux: the record of tidal_energy_file [W/m^2] on the
+ * local blocks, (nx_block, ny_block, nblocks) as pop_set_field takes a 2-D field; its ghost cells are filled by a halo update (centre,
+ * scalar), so with several ranks the call is collective.  Once per context, before the first pop_time_manager / pop_step / pop_run_phase.
+ * Needs vmix_choice = 3 (initial.F90:1962) and bckgrnd_vdc2 = 0 (:1975).  Works on a host-only context (the fields below that
+ * need no device).  Afterwards pop_get_field serves "TIDAL_ENERGY_FLUX" [g/s^3], "TIDAL_COEF_3D", "TLON" [radians] and, with tidal_diag,
+ * "TIDAL_DIFF", "TIDAL_N2", "KVMIX", "KVMIX_M"; pop_get_ifield serves "TIDAL_REGION_BOX2D".  Restart files carry nothing of it. */
+int pop_init_tidal_mixing(pop_ctx *ctx, const pop_tidal_nml *nml, const double *energy_flux, long long count);
+
 /* ---- blocks.F90:43-63 / get_block (blocks.F90:282-320) ---------------------- */
 int pop_get_dim(const pop_ctx *ctx, const char *name);         /* nx_block, ny_block, km, nt,
                                                                   nblocks (local), nblocks_tot,

@@ -86,6 +86,7 @@ def lib():
         "pop_halo_plan_lists": (ci, [vp, ci, pi, pi]), "pop_halo_plan_local": (ci, [vp, pi, pi, pi]),
         "pop_timers_reset": (ci, [vp]), "pop_timer_ms": (ci, [vp, cs, pd, pi]),
         "pop_time_phase": (ci, [vp, cs, ci, pd]), "pop_device_sync": (ci, [vp]), "pop_run_phase": (ci, [vp, cs]),
+        "pop_tidal_nml_init": (None, [vp]), "pop_init_tidal_mixing": (ci, [vp, vp, pd, ll]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)       # AttributeError here = the library does not export the ABI
@@ -191,6 +192,46 @@ def submeso_config(cfg, **mix_submeso_nml):
             raise AttributeError("pop_config has no field %r" % k)
         setattr(out, k, v)
     return out
+
+
+MAX_TIDAL_MIN_REGIONS = 9
+TIDAL_METHOD = {"jayne": 0, "schmittner": 1, "polzin": 2}
+_TIDAL_REGION_KEYS = {"min_value": "tidal_min_values", "TLATmin": "tidal_TLATmin_regions", "TLATmax": "tidal_TLATmax_regions",
+                      "TLONmin": "tidal_TLONmin_regions", "TLONmax": "tidal_TLONmax_regions", "klevels": "tidal_min_regions_klevels"}
+
+
+class PopTidalNml(C.Structure):
+    """include/pop_amd.h pop_tidal_nml"""
+    _fields_ = [(n, C.c_int) for n in ("struct_bytes", "ltidal_mixing", "tidal_mixing_method", "ltidal_max", "ltidal_stabc",
+                                       "lccsm_control_compatible", "ltidal_min_regions", "num_tidal_min_regions", "tidal_diag")] + \
+        [(n, C.c_double) for n in ("tidal_local_mixing_fraction", "tidal_mixing_efficiency", "vertical_decay_scale", "tidal_mix_max")] + \
+        [(n, C.c_double * MAX_TIDAL_MIN_REGIONS) for n in ("tidal_min_values", "tidal_TLATmin_regions", "tidal_TLATmax_regions",
+                                                           "tidal_TLONmin_regions", "tidal_TLONmax_regions")] + \
+        [("tidal_min_regions_klevels", C.c_int * MAX_TIDAL_MIN_REGIONS)]
+
+
+def tidal_nml(regions=None, **kw):
+    """pop_tidal_nml with the code defaults (pop_tidal_nml_init) and ltidal_mixing = 1, then the keywords: the members by name
+    (tidal_mixing_method may also be 'jayne' | 'schmittner' | 'polzin').  regions: a list of dicts, one per box of ltidal_min_regions,
+    with the keys TLATmin, TLATmax, TLONmin, TLONmax [degrees] and optionally min_value [cm^2/s] and klevels (2 | 6); giving it sets
+    ltidal_min_regions = 1 and num_tidal_min_regions unless the keywords say otherwise."""
+    n = PopTidalNml()
+    lib().pop_tidal_nml_init(C.byref(n))
+    n.ltidal_mixing = 1
+    if regions is not None:
+        if len(regions) > MAX_TIDAL_MIN_REGIONS:
+            raise ValueError("at most %d tidal regions" % MAX_TIDAL_MIN_REGIONS)
+        n.ltidal_min_regions, n.num_tidal_min_regions = 1, len(regions)
+        for r, box in enumerate(regions):
+            for k, v in box.items():
+                getattr(n, _TIDAL_REGION_KEYS[k])[r] = v
+    for k, v in kw.items():
+        if k == "tidal_mixing_method" and isinstance(v, str):
+            v = TIDAL_METHOD[v]
+        if not hasattr(n, k):
+            raise AttributeError("pop_tidal_nml has no field %r" % k)
+        setattr(n, k, v)
+    return n
 
 
 class PopGridInput(C.Structure):
@@ -318,6 +359,15 @@ class PopModel:
         a = np.empty((self.nblocks, self.nyb, self.nxb), dtype=np.int32)
         self._chk(self.L.pop_get_ifield(self.h, name.encode(), a.ctypes.data_as(C.POINTER(C.c_int)), a.size))
         return a
+
+    def init_tidal_mixing(self, energy_flux, regions=None, **nml):
+        """init_tidal_mixing1 / 2 (tidal_mixing.F90) for the Jayne method: energy_flux = the record of tidal_energy_file [W/m^2] on the
+        local blocks (nblocks, ny_block, nx_block); regions and keywords as tidal_nml().  Once, before the first step or phase;
+        collective over the ranks.  Returns the pop_tidal_nml that was passed."""
+        n = tidal_nml(regions, **nml)
+        a = np.ascontiguousarray(energy_flux, dtype=np.float64)
+        self._chk(self.L.pop_init_tidal_mixing(self.h, C.byref(n), a.ctypes.data_as(C.POINTER(C.c_double)), a.size))
+        return n
 
     # ---- step_mod.F90 sequence
     def time_manager(self):

@@ -116,6 +116,7 @@ inline int mix_state_host(const HostModel &h, const DevGrid &g, int kk, const do
 }  // namespace pop
 
 #include "kernels_del4.hpp"
+#include "kernels_tidal.hpp"
 #include "kernels_kpp.hpp"
 
 namespace pop {

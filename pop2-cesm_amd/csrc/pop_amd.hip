@@ -92,6 +92,13 @@ int resolve(pop_ctx *c, const std::string &name, int tl, int n, double **ptr, lo
   if (name == "USUBM") return ok(c->subm.US, a3);
   if (name == "VSUBM") return ok(c->subm.VS, a3);
   if (name == "WSUBM") return ok(c->subm.WS, a3);
+  if (c->tidal.on && c->mix.kpp) {   // tidal_diag: the last evaluation's TIDAL_DIFF, TIDAL_N2, KVMIX, KVMIX_M
+    const TidalDev &td = ((const KppHost *)c->mix.kpp)->tidal;
+    if (name == "TIDAL_DIFF") return ok(td.DIFF, a3);
+    if (name == "TIDAL_N2") return ok(td.N2, a3);
+    if (name == "KVMIX") return ok(td.KV, a3);
+    if (name == "KVMIX_M") return ok(td.KVM, a3);
+  }
   if (name == "GM_GTK") return (n == 0 || n == 1) ? ok(c->gm.GTK[n], a3) : 1;   // the mixing tendency the tracer right-hand side reads (hmix_tracer = 3)
   if (name == "HDU") return ok(c->HDU, a3);                   // hmix_momentum = 3: Hdiff(U), Hdiff(V) of hdiffu_aniso at every level
   if (name == "HDV") return ok(c->HDV, a3);
@@ -1010,7 +1017,7 @@ long long pop_field_count(const pop_ctx *c, const char *name) {
   const std::string n(name);
   const long long a2 = (long long)c->h.n2 * c->h.nblocks, a3 = (long long)c->h.n3 * c->h.nblocks;
   for (const char *s : {"TRACER", "UVEL", "VVEL", "RHO", "KPP_SRC", "VVC", "UISOP", "VISOP", "WISOP", "GM_SF_SLX", "GM_SF_SLY", "HDU", "HDV", "F_PARA", "F_PERP",
-                        "SUBM_ADV_TEND", "USUBM", "VSUBM", "WSUBM", "GM_GTK"}) if (n == s) return a3;
+                        "SUBM_ADV_TEND", "USUBM", "VSUBM", "WSUBM", "GM_GTK", "TIDAL_COEF_3D", "TIDAL_DIFF", "TIDAL_N2", "KVMIX", "KVMIX_M"}) if (n == s) return a3;
   if (n == "VDC") return (long long)c->h.n2 * (c->h.km + 2) * c->h.nblocks;
   return a2;
 }
@@ -1035,6 +1042,17 @@ static int join_side(pop_ctx *c, bool keep_ahead = false) {
 }
 int pop_get_field(pop_ctx *c, const char *name, int tl, int n, double *host, long long count) {
   const std::string nm(name);
+  if (nm == "TIDAL_ENERGY_FLUX" || nm == "TIDAL_COEF_3D" || (nm == "TLON" && c->tidal.on)) {   // init-time fields of pop_init_tidal_mixing (host copies)
+    if (!c->tidal.on) { c->err = nm + " exists after pop_init_tidal_mixing with ltidal_mixing only"; return 1; }
+    const std::vector<double> &v = nm == "TLON" ? c->tidal.f.tlon : nm == "TIDAL_COEF_3D" ? c->tidal.f.coef : c->tidal.f.flux;
+    if ((long long)v.size() != count) { c->err = "count mismatch for " + nm; return 1; }
+    std::copy(v.begin(), v.end(), host);
+    return 0;
+  }
+  if (nm == "TIDAL_DIFF" || nm == "TIDAL_N2" || nm == "KVMIX" || nm == "KVMIX_M") {
+    if (!c->tidal.on || !c->tidal.nml.tidal_diag) { c->err = nm + " exists after pop_init_tidal_mixing with ltidal_mixing and tidal_diag only"; return 1; }
+    if (need_device(c)) return 1;
+  }
   if (c->host_only) {   // host-only contexts expose the init-time 2-D fields of the local blocks (and F_PARA, F_PERP)
     if (nm == "F_PARA" || nm == "F_PERP") {
       const std::vector<double> &all = c->h.aniso_f[nm == "F_PARA" ? 0 : 1];
@@ -1103,6 +1121,12 @@ int pop_get_ifield(pop_ctx *c, const char *name, int *host, long long count) {
     if (count != (long long)c->g.n2 * c->g.nblocks) { c->err = "count mismatch"; return 1; }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(host, c->KBL, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+  }
+  if (!strcmp(name, "TIDAL_REGION_BOX2D")) {   // REGION_BOX2D of ltidal_min_regions (0 everywhere without it)
+    if (!c->tidal.on) { c->err = "TIDAL_REGION_BOX2D exists after pop_init_tidal_mixing with ltidal_mixing only"; return 1; }
+    if ((long long)c->tidal.f.box.size() != count) { c->err = "count mismatch"; return 1; }
+    std::copy(c->tidal.f.box.begin(), c->tidal.f.box.end(), host);
     return 0;
   }
   auto it = c->h.i2.find(name);
@@ -1269,6 +1293,7 @@ static void land_skip_for_step(pop_ctx *c) {
 }
 int pop_time_manager(pop_ctx *c) {
   const pop_config &cf = c->h.c;
+  c->ran = true;
   if (!c->host_only) land_skip_for_step(c);
   c->leapfrogts = 1; c->f_euler_ts = 0; c->avg_ts = 0;
   c->nsteps_total += 1;
@@ -1341,7 +1366,9 @@ static int phase_vmix(pop_ctx *c) {
 static int kpp_look_ahead(pop_ctx *c) {
   // an averaging step rewrites oldtime and curtime in its tail and does not rotate; the Robert filter rewrites curtime
   // (with the mixed-layer-depth diagnostics on, HMXL / HMXL_DR of the step that just ran stay where they are: the look-ahead writes the second pair)
-  if (!c->ahead_enabled || c->h.c.vmix_choice != 3 || c->avg_ts || c->h.c.tmix_opt == 3 || (c->h.c.kpp_ml_diagnostics == 1 && !c->HMXLa)) return 0;
+  // tidal_diag: TIDAL_DIFF ... KVMIX_M have one set of arrays, which holds the step that has run
+  if (!c->ahead_enabled || c->h.c.vmix_choice != 3 || c->avg_ts || c->h.c.tmix_opt == 3 || (c->h.c.kpp_ml_diagnostics == 1 && !c->HMXLa) ||
+      (c->tidal.on && c->tidal.nml.tidal_diag)) return 0;
   HIPCHK(c, hipEventRecord(c->ev_ahead_fork, c->stream));
   HIPCHK(c, hipStreamWaitEvent(c->ahead, c->ev_ahead_fork, 0));
   const MixState ms = kpp_mix_state(c, c->curt, true);
@@ -2334,6 +2361,62 @@ int pop_halo_plan_local(const pop_ctx *c, int *dst, int *src, int *fill_dst) {
   return 0;
 }
 
+// ---- tidal mixing: tidal_nml and the energy-flux record through an entry point of their own (tidal_mixing.F90 init_tidal_mixing1 / 2)
+void pop_tidal_nml_init(pop_tidal_nml *nml) { if (nml) tidal_nml_defaults(*nml); }
+int pop_init_tidal_mixing(pop_ctx *c, const pop_tidal_nml *nml, const double *energy_flux, long long count) {
+  if (!c) return 1;
+  if (!nml || nml->struct_bytes != (int)sizeof(pop_tidal_nml)) { c->err = "pop_init_tidal_mixing: pop_tidal_nml.struct_bytes is not sizeof(pop_tidal_nml) of this library (" + std::to_string(sizeof(pop_tidal_nml)) + ")"; return 1; }
+  if (c->h.plan_only) { c->err = "pop_init_tidal_mixing: the context has no grid fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+  if (c->tidal.inited) { c->err = "pop_init_tidal_mixing: called a second time (once per context)"; return 1; }
+  if (c->ran || c->nsteps_total > 0) { c->err = "pop_init_tidal_mixing: a step or a phase has already run (call it right after pop_create)"; return 1; }
+  if (!nml->ltidal_mixing) { c->tidal.inited = true; c->tidal.nml = *nml; return 0; }   // builds nothing
+  const pop_config &cf = c->h.c;
+  if (cf.vmix_choice != 3) { c->err = "tidal mixing needs vmix_choice = 3 (kpp) (initial.F90:1962)"; return 1; }
+  if (cf.bckgrnd_vdc2 != 0.0) { c->err = "tidal mixing needs bckgrnd_vdc2 = 0 (initial.F90:1975)"; return 1; }
+  pop_tidal_nml n = *nml;
+  if (tidal_nml_resolve(n, c->err)) return 1;
+  const size_t a2 = c->h.n2 * c->h.nblocks, a3 = c->h.n3 * c->h.nblocks;
+  if (!energy_flux || count != (long long)a2) { c->err = "pop_init_tidal_mixing: count mismatch for the energy flux (nx_block * ny_block * nblocks)"; return 1; }
+  std::vector<double> flux(energy_flux, energy_flux + a2);
+  if (pop_halo_update_host_r8_loc(c, flux.data(), 1, 0.0, 0, 0)) return 1;   // centre, scalar: the record is read into the physical cells
+  host_tidal_build(c->h, n, flux.data(), c->tidal.f);
+  if (!c->host_only) {
+    KppHost *K = (KppHost *)c->mix.kpp;
+    TidalDev &td = K->tidal;
+    const int km = c->h.km;
+    double *p; int *pi;
+    if (dev_upload(c, &p, c->tidal.f.coef.data(), a3)) return 1;
+    td.COEF = p;
+    if (n.ltidal_min_regions) { if (dev_upload(c, &pi, c->tidal.f.box.data(), a2)) return 1; td.BOX = pi; }
+    std::vector<double> bvdc(km + 3, 0.0), bvvc_pr(km + 3, 0.0), minval(POP_MAX_TIDAL_MIN_REGIONS + 1, 0.0), zero(km + 3, 0.0);
+    std::vector<int> klev(POP_MAX_TIDAL_MIN_REGIONS + 1, 0);
+    for (int k = 1; k <= km; ++k) {   // as kpp_create forms them (bckgrnd_vdc2 = 0)
+      bvdc[k] = cf.bckgrnd_vdc1 + cf.bckgrnd_vdc2 * std::atan(cf.bckgrnd_vdc_linv * (c->h.zw[k] - cf.bckgrnd_vdc_dpth));
+      bvvc_pr[k] = (cf.Prandtl * bvdc[k]) / cf.Prandtl;   // bckgrnd_vvc(k) / Prandtl (vmix_kpp.F90:1826)
+    }
+    for (int r = 0; r < n.num_tidal_min_regions; ++r) { minval[r + 1] = n.tidal_min_values[r]; klev[r + 1] = n.tidal_min_regions_klevels[r]; }
+    if (dev_upload(c, &p, bvdc.data(), bvdc.size())) return 1;
+    td.bvdc = p;
+    if (dev_upload(c, &p, bvvc_pr.data(), bvvc_pr.size())) return 1;
+    td.bvvc_pr = p;
+    if (dev_upload(c, &p, minval.data(), minval.size())) return 1;
+    td.minval = p;
+    if (dev_upload(c, &pi, klev.data(), klev.size())) return 1;
+    td.klev = pi;
+    if (dev_upload(c, &p, zero.data(), zero.size())) return 1;
+    K->zero_bck = p;
+    td.zgrid = K->dev.zgrid;
+    td.mix_max = n.tidal_mix_max; td.prandtl = cf.Prandtl;
+    td.lmax = n.ltidal_max ? 1 : 0; td.stabc = (n.ltidal_stabc && !n.lccsm_control_compatible) ? 1 : 0;
+    if (n.tidal_diag) {
+      if (dev_alloc(c, &td.DIFF, a3) || dev_alloc(c, &td.N2, a3) || dev_alloc(c, &td.KV, a3) || dev_alloc(c, &td.KVM, a3)) return 1;
+    }
+    K->tidal_on = true;
+  }
+  c->tidal.nml = n; c->tidal.inited = true; c->tidal.on = true;
+  return 0;
+}
+
 int pop_timers_reset(pop_ctx *c) { c->timers.clear(); c->timing = true; return 0; }
 int pop_timer_ms(pop_ctx *c, const char *name, double *ms, int *calls) {
   auto it = c->timers.find(name);
@@ -2379,6 +2462,7 @@ int pop_run_phase(pop_ctx *c, const char *phase) {
   if (need_device(c) || join_side(c)) return 1;
   phase_fn_t fn = phase_by_name(phase ? phase : "");
   if (!fn) { c->err = std::string("unknown phase ") + (phase ? phase : "(null)"); return 1; }
+  c->ran = true;
   if (fn(c)) return 1;
   HIPCHK(c, hipGetLastError());
   return 0;
@@ -2388,6 +2472,7 @@ int pop_time_phase(pop_ctx *c, const char *phase, int reps, double *avg_ms) {
   const std::string p(phase);
   phase_fn_t fn = phase_by_name(p);
   if (!fn) { c->err = "unknown phase " + p; return 1; }
+  c->ran = true;
   struct Events {   // destroyed on every return path
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ~Events() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }

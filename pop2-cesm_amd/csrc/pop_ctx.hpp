@@ -144,6 +144,10 @@ struct pop_ctx {
   SubmDev subm{};                                          // lsubmesoscale_mixing: the column fields of submeso_sf, diagnostics
   GmDev gm{};                                              // hmix_tracer = 3 (gm): slopes, tapered diffusivities, GTK
   RcclTransport *rccl_tr = nullptr;                       // in-library RCCL transport (pop_comm_init_rccl)
+  // Jayne tidal mixing (pop_init_tidal_mixing): the resolved namelist and the init-time fields of the local blocks (host copies serve
+  // pop_get_field; the device copies and the kernel's arguments live in KppHost::tidal)
+  struct Tidal { bool inited = false, on = false; pop_tidal_nml nml{}; TidalFields f; } tidal;
+  bool ran = false;                                        // a step or a phase has run (pop_init_tidal_mixing is refused afterwards)
   // time stepping
   int oldt = 0, curt = 1, newt = 2, mixt = 1;
   int first_step = 1, leapfrogts = 1, f_euler_ts = 0, avg_ts = 0, nsteps_total = 0, nsteps_this_interval = 0;

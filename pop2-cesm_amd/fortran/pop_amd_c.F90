@@ -91,6 +91,17 @@
       integer (c_int) :: submeso_all_levels
    end type pop_tuning
 
+   ! mirrors `struct pop_tidal_nml` (tidal_nml for the Jayne method); fill with pop_tidal_nml_init, then set fields
+   integer (c_int), parameter :: POP_MAX_TIDAL_MIN_REGIONS = 9
+   type, bind(C) :: pop_tidal_nml
+      integer (c_int) :: struct_bytes, ltidal_mixing, tidal_mixing_method, ltidal_max, ltidal_stabc
+      integer (c_int) :: lccsm_control_compatible, ltidal_min_regions, num_tidal_min_regions, tidal_diag
+      real (c_double) :: tidal_local_mixing_fraction, tidal_mixing_efficiency, vertical_decay_scale, tidal_mix_max
+      real (c_double), dimension(POP_MAX_TIDAL_MIN_REGIONS) :: tidal_min_values, tidal_TLATmin_regions, tidal_TLATmax_regions
+      real (c_double), dimension(POP_MAX_TIDAL_MIN_REGIONS) :: tidal_TLONmin_regions, tidal_TLONmax_regions
+      integer (c_int), dimension(POP_MAX_TIDAL_MIN_REGIONS) :: tidal_min_regions_klevels
+   end type pop_tidal_nml
+
    type (c_ptr), save :: pop_ctx = c_null_ptr   ! the one model instance of this task
 
    interface
@@ -369,6 +380,17 @@
       integer (c_int) function pop_comm_selftest(ctx) bind(C, name='pop_comm_selftest')
          import :: c_int, c_ptr
          type (c_ptr), value :: ctx
+      end function
+      subroutine pop_tidal_nml_init(nml) bind(C, name='pop_tidal_nml_init')
+         import :: pop_tidal_nml
+         type (pop_tidal_nml), intent(out) :: nml
+      end subroutine
+      integer (c_int) function pop_init_tidal_mixing(ctx, nml, energy_flux, count) bind(C, name='pop_init_tidal_mixing')
+         import :: c_int, c_ptr, c_double, c_long_long, pop_tidal_nml
+         type (c_ptr), value :: ctx
+         type (pop_tidal_nml), intent(in) :: nml
+         real (c_double), intent(in) :: energy_flux(*)      ! W/m^2, (nx_block, ny_block, nblocks_clinic)
+         integer (c_long_long), value :: count
       end function
    end interface
 
