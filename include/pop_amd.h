@@ -295,6 +295,29 @@ void pop_tidal_nml_init(pop_tidal_nml *nml);   /* struct_bytes = sizeof, the cod
  * "TIDAL_DIFF", "TIDAL_N2", "KVMIX", "KVMIX_M"; pop_get_ifield serves "TIDAL_REGION_BOX2D".  Restart files carry nothing of it. */
 int pop_init_tidal_mixing(pop_ctx *ctx, const pop_tidal_nml *nml, const double *energy_flux, long long count);
 
+/* ---- latitude-varying KPP background diffusivity (lhoriz_varying_bckgrnd of vmix_kpp_nml; vmix_kpp.F90:544-611): the Gregg
+ *      equatorial minimum, the MacKinnon maxima at +-28.9 degrees and the Banda Sea value, through an entry point of its own
+ *      (pop_config keeps its layout).  bckgrnd_vdc1 and Prandtl are pop_config's.  The three doubles are taken literally: 0 is a
+ *      value, not a stand-in for the default.  lniw_mixing and the CVMix path are not built. */
+typedef struct pop_kpp_bckgrnd_nml {
+  int struct_bytes;              /* sizeof(pop_kpp_bckgrnd_nml) of the caller */
+  int lhoriz_varying_bckgrnd;    /* 0: the call succeeds and builds nothing */
+  int larctic_bckgrnd_vdc;       /* 1: bckgrnd_vdc_eq at and north of 70 degrees */
+  double bckgrnd_vdc_eq;         /* [cm^2/s] equatorial value (code default 0.01) */
+  double bckgrnd_vdc_psim;       /* [cm^2/s] amplitude of the maxima at +-28.9 degrees (code default 0.13) */
+  double bckgrnd_vdc_ban;        /* [cm^2/s] Banda Sea value (code default 1.0) */
+} pop_kpp_bckgrnd_nml;
+void pop_kpp_bckgrnd_nml_init(pop_kpp_bckgrnd_nml *nml);   /* struct_bytes = sizeof, the code defaults of vmix_kpp.F90:337-349 (both switches 0) */
+/* The lhoriz_varying_bckgrnd branch of init_vmix_kpp (vmix_kpp.F90:544-611): bckgrnd_vdc from TLAT and TLON on every cell of every
+ * local block, ghost cells included (a ghost cell carries its source cell's latitude and longitude), bckgrnd_vvc = Prandtl *
+ * bckgrnd_vdc.  Once per context, after pop_create* and before the first pop_time_manager / pop_step / pop_run_phase; with several
+ * ranks after the transport is installed and on every rank (TLON takes a halo update).  Before or after pop_init_tidal_mixing: both
+ * orders give the same bits.  Refused: vmix_choice != 3; bckgrnd_vdc2 != 0 (vmix_kpp.F90:518); a negative bckgrnd_vdc_eq / _psim /
+ * _ban; a struct_bytes of another layout; a second call; a call after a step or a phase.  Works on a host-only context.
+ * Afterwards pop_get_field serves "BCKGRND_VDC" and "BCKGRND_VVC" (the reference's tavg fields VDC_BCK / VVC_BCK) as 2-D fields --
+ * ONE level is stored where the reference stores km identical copies -- and "TLON" [radians].  Restart files carry nothing of it. */
+int pop_init_kpp_bckgrnd(pop_ctx *ctx, const pop_kpp_bckgrnd_nml *nml);
+
 /* ---- blocks.F90:43-63 / get_block (blocks.F90:282-320) ---------------------- */
 int pop_get_dim(const pop_ctx *ctx, const char *name);         /* nx_block, ny_block, km, nt,
                                                                   nblocks (local), nblocks_tot,

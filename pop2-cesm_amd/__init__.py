@@ -87,6 +87,7 @@ def lib():
         "pop_timers_reset": (ci, [vp]), "pop_timer_ms": (ci, [vp, cs, pd, pi]),
         "pop_time_phase": (ci, [vp, cs, ci, pd]), "pop_device_sync": (ci, [vp]), "pop_run_phase": (ci, [vp, cs]),
         "pop_tidal_nml_init": (None, [vp]), "pop_init_tidal_mixing": (ci, [vp, vp, pd, ll]),
+        "pop_kpp_bckgrnd_nml_init": (None, [vp]), "pop_init_kpp_bckgrnd": (ci, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)       # AttributeError here = the library does not export the ABI
@@ -234,6 +235,26 @@ def tidal_nml(regions=None, **kw):
     return n
 
 
+class PopKppBckgrndNml(C.Structure):
+    """include/pop_amd.h pop_kpp_bckgrnd_nml"""
+    _fields_ = [(n, C.c_int) for n in ("struct_bytes", "lhoriz_varying_bckgrnd", "larctic_bckgrnd_vdc")] + \
+        [(n, C.c_double) for n in ("bckgrnd_vdc_eq", "bckgrnd_vdc_psim", "bckgrnd_vdc_ban")]
+
+
+def kpp_bckgrnd_nml(**kw):
+    """pop_kpp_bckgrnd_nml with the code defaults (pop_kpp_bckgrnd_nml_init: 0.01, 0.13, 1.0) and lhoriz_varying_bckgrnd = 1, then the
+    keywords: the members by name.  The doubles are taken literally (0 is a value).  CESM's gx grids: bckgrnd_vdc_eq = 0.01,
+    bckgrnd_vdc_psim = 0.13, bckgrnd_vdc_ban = 1.0 with pop_config bckgrnd_vdc1 = 0.16."""
+    n = PopKppBckgrndNml()
+    lib().pop_kpp_bckgrnd_nml_init(C.byref(n))
+    n.lhoriz_varying_bckgrnd = 1
+    for k, v in kw.items():
+        if not hasattr(n, k):
+            raise AttributeError("pop_kpp_bckgrnd_nml has no field %r" % k)
+        setattr(n, k, v)
+    return n
+
+
 class PopGridInput(C.Structure):
     """include/pop_amd.h pop_grid_input"""
     _fields_ = [(n, C.POINTER(C.c_double)) for n in ("ULAT", "ULON", "HTN", "HTE", "HUS", "HUW", "ANGLE")] + [("KMT", C.POINTER(C.c_int)),
@@ -367,6 +388,14 @@ class PopModel:
         n = tidal_nml(regions, **nml)
         a = np.ascontiguousarray(energy_flux, dtype=np.float64)
         self._chk(self.L.pop_init_tidal_mixing(self.h, C.byref(n), a.ctypes.data_as(C.POINTER(C.c_double)), a.size))
+        return n
+
+    def init_kpp_bckgrnd(self, **nml):
+        """The lhoriz_varying_bckgrnd branch of init_vmix_kpp (vmix_kpp.F90:544-611): keywords as kpp_bckgrnd_nml().  Once, before the
+        first step or phase, before or after init_tidal_mixing; on every rank.  Afterwards get("BCKGRND_VDC"), get("BCKGRND_VVC") and
+        get("TLON") serve the 2-D fields.  Returns the pop_kpp_bckgrnd_nml that was passed."""
+        n = kpp_bckgrnd_nml(**nml)
+        self._chk(self.L.pop_init_kpp_bckgrnd(self.h, C.byref(n)))
         return n
 
     # ---- step_mod.F90 sequence

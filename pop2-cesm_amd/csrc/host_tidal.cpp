@@ -1,8 +1,7 @@
 // host_tidal.cpp -- init-time part of Jayne tidal mixing (tidal_mixing.F90 init_tidal_mixing1 / 2 for tidal_mixing_method 'jayne'):
 // the energy flux in g/s^3 (tidal_read_energy_jayne :2246-2295), the vertical decay function and TIDAL_COEF_3D (:1266-1309,
-// tidal_form_qE_2D :2631-2661, tidal_form_coef_jayne :2512-2548), TLON (calc_tpoints, grid.F90:2985-3100; nothing else here needs
-// it) and the region boxes of ltidal_min_regions (:880-1003).  Every cell of every local block, ghost cells included: the KPP
-// kernels run on them.
+// tidal_form_qE_2D :2631-2661, tidal_form_coef_jayne :2512-2548), TLON (calc_tpoints, grid.F90:2985-3100) and the region boxes of ltidal_min_regions
+// (:880-1003).  Every cell of every local block, ghost cells included: the KPP kernels run on them.
 #include <algorithm>
 #include "pop_internal.hpp"
 
@@ -34,16 +33,15 @@ int tidal_nml_resolve(pop_tidal_nml &n, std::string &err) {
   return 0;
 }
 
-// flux: W/m^2 on the local blocks, ghost cells already updated
-void host_tidal_build(const HostModel &h, const pop_tidal_nml &n, const double *flux, TidalFields &out) {
-  const int nxb = h.nxb, nyb = h.nyb, km = h.km, NB = h.nblocks_tot;
-  const size_t n2 = h.n2, n3 = h.n3, a2 = n2 * h.nblocks;
-  const double pi = 4.0 * std::atan(1.0), radian = 180.0 / pi, pi2 = 2.0 * pi;
-  const std::vector<double> &ULAT = h.f2.at("ULAT"), &ULON = h.f2.at("ULON"), &TLATg = h.f2.at("TLAT"), &HTg = h.f2.at("HT"), &RCg = h.f2.at("RCALCT");
-  const std::vector<int> &KMTg = h.i2.at("KMT");
+// TLON of the local blocks (calc_tpoints, grid.F90:2985-3100): Cartesian average of the four surrounding U points, the southernmost
+// row copied from the row north of it, 0 <= TLON < 2 pi, then the halo update.  Shared by pop_init_tidal_mixing (region boxes) and
+// pop_init_kpp_bckgrnd (Banda Sea boxes); nothing else needs it.
+void host_tlon_build(const HostModel &h, std::vector<double> &tlon) {
+  const int nxb = h.nxb, nyb = h.nyb, NB = h.nblocks_tot;
+  const size_t n2 = h.n2;
+  const double pi = 4.0 * std::atan(1.0), pi2 = 2.0 * pi;
+  const std::vector<double> &ULAT = h.f2.at("ULAT"), &ULON = h.f2.at("ULON");
   auto idx = [&](int b, int i, int j) { return (size_t)b * n2 + (size_t)j * nxb + i; };
-  // TLON of every block (calc_tpoints): Cartesian average of the four surrounding U points, the southernmost row copied from the
-  // row north of it, 0 <= TLON < 2 pi, then the halo update
   std::vector<double> TLON(n2 * NB, 0.0);
   for (int b = 0; b < NB; ++b) {
     const BlockInfo &B = h.all_blocks[b];
@@ -66,7 +64,22 @@ void host_tidal_build(const HostModel &h, const pop_tidal_nml &n, const double *
     }
   }
   host_halo_r8_loc(h, TLON.data(), 1, 0.0, 0, 0);
-  out.flux.assign(a2, 0.0); out.tlon.assign(a2, 0.0); out.coef.assign(n3 * h.nblocks, 0.0); out.box.assign(a2, 0);
+  tlon.assign(n2 * h.nblocks, 0.0);
+  for (int lb = 0; lb < h.nblocks; ++lb) {
+    const size_t g0 = (size_t)(h.local_ids[lb] - 1) * n2;
+    std::copy(TLON.begin() + g0, TLON.begin() + g0 + n2, tlon.begin() + (size_t)lb * n2);
+  }
+}
+
+// flux: W/m^2 on the local blocks, ghost cells already updated; tlon: host_tlon_build
+void host_tidal_build(const HostModel &h, const pop_tidal_nml &n, const double *flux, const std::vector<double> &tlon, TidalFields &out) {
+  const int nxb = h.nxb, nyb = h.nyb, km = h.km;
+  const size_t n2 = h.n2, n3 = h.n3, a2 = n2 * h.nblocks;
+  const double pi = 4.0 * std::atan(1.0), radian = 180.0 / pi;
+  const std::vector<double> &TLATg = h.f2.at("TLAT"), &HTg = h.f2.at("HT"), &RCg = h.f2.at("RCALCT");
+  const std::vector<int> &KMTg = h.i2.at("KMT");
+  auto idx = [&](int b, int i, int j) { return (size_t)b * n2 + (size_t)j * nxb + i; };
+  out.flux.assign(a2, 0.0); out.coef.assign(n3 * h.nblocks, 0.0); out.box.assign(a2, 0);
   const double gamma_rhor = n.tidal_mixing_efficiency / 1.0;   // tidal_gamma_rhor = tidal_mixing_efficiency / rho_fw, rho_fw = 1 g/cm^3 (:1181)
   const double decay = n.vertical_decay_scale;
   for (int lb = 0; lb < h.nblocks; ++lb) {
@@ -76,7 +89,6 @@ void host_tidal_build(const HostModel &h, const pop_tidal_nml &n, const double *
       const size_t pg = idx(b, i, j), pl = idx(lb, i, j);
       const int kmt = KMTg[pg];
       const double ht = HTg[pg];
-      out.tlon[pl] = TLON[pg];
       const double ef = 1000.0 * flux[pl];                       // W/m^2 -> g/s^3
       out.flux[pl] = ef;
       const double qe = n.tidal_local_mixing_fraction * ef;      // TIDAL_QE_2D
@@ -94,7 +106,7 @@ void host_tidal_build(const HostModel &h, const pop_tidal_nml &n, const double *
       if (n.ltidal_min_regions && B.i_glob[i] != 0 && B.j_glob[j] != 0) {
         // the box is formed on the global arrays and scattered (:910-962): a ghost cell carries the value of its source cell (its
         // TLAT / TLON are that cell's after the halo update), a cell without a global address 0
-        const double latd = TLATg[pg] * radian, lond = TLON[pg] * radian;
+        const double latd = TLATg[pg] * radian, lond = tlon[pl] * radian;
         int box = 0;
         for (int r = 0; r < n.num_tidal_min_regions; ++r) {
           if (!(latd >= n.tidal_TLATmin_regions[r] && latd <= n.tidal_TLATmax_regions[r])) continue;

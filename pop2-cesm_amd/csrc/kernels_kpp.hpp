@@ -12,6 +12,8 @@
 //                                  + non-local source :1283-1306
 //   k_kpp_vvc        tgrid_to_ugrid of VISC -> VVC    :1253-1262
 //   k_kpp_tidal      ri_iwmix      :1791-1857   Jayne tidal mixing (kernels_tidal.hpp), only after pop_init_tidal_mixing
+//   k_kpp_bckgrnd    ri_iwmix      :1886-1898   bckgrnd_vdc(i,j) of lhoriz_varying_bckgrnd (kernels_bckgrnd.hpp), only after
+//                                  pop_init_kpp_bckgrnd and without tidal mixing (with it k_kpp_tidal<PBC, true> reads the 2-D fields)
 // Selections: no near-inertial-wave / Langmuir mixing, no short-wave penetration
 // (lshort_wave=.false.), lcheckekmo=.false., SMFT available, no partial bottom cells.
 // Integer powers use the usual expansion x**3=(x*x)*x, x**4=(x*x)*(x*x).
@@ -1381,8 +1383,22 @@ inline void launch_kpp_vvc(const DevGrid &g, const HostModel &h, hipStream_t st,
 // per-context KPP state (MixDev::kpp)
 // col: bit 0 = ushear, bit 1 = buoydiff in column form.  side / ev_*: second HIP stream on which the shear kernel (needs only
 // U, V; consumed by bldepth) runs beside buoydiff + interior (POP_KPP_SIDE_STREAM=0 keeps everything on one stream)
-// tidal: set by pop_init_tidal_mixing (tidal_on); zero_bck = km + 3 words of 0, the background the interior kernels then see
-struct KppHost { TidalDev tidal; bool tidal_on = false; const double *zero_bck = nullptr; KppDev dev; int max_kref = 1; int col = 0; int *wuk = nullptr; unsigned long long *convb = nullptr; hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_bd = nullptr; };
+// tidal: set by pop_init_tidal_mixing (tidal_on); bck: set by pop_init_kpp_bckgrnd (bck_on); zero_bck = km + 3 words of 0, the
+// background the interior kernels see with either
+struct KppHost {
+  TidalDev tidal;
+  bool tidal_on = false;
+  BckDev bck;
+  bool bck_on = false;
+  const double *zero_bck = nullptr;
+  KppDev dev;
+  int max_kref = 1;
+  int col = 0;
+  int *wuk = nullptr;
+  unsigned long long *convb = nullptr;
+  hipStream_t side = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_bd = nullptr;
+};
 inline void kpp_destroy(MixDev &m) {
   KppHost *k = (KppHost *)m.kpp;
   if (k) {
@@ -1563,7 +1579,8 @@ inline int kpp_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParam
   g_kpp.vdc_same = (s.VDC[0] == s.VDC[1]) ? 1 : 0;
   // tidal mixing: the interior kernels form the shear and double-diffusion terms on a background of zeros; k_kpp_tidal adds the
   // background and the tidal diffusivity (kernels_tidal.hpp)
-  if (KH.tidal_on) { g_kpp.bckgrnd_vdc = KH.zero_bck; g_kpp.bckgrnd_vvc = KH.zero_bck; }
+  // lhoriz_varying_bckgrnd: the same, and k_kpp_bckgrnd (kernels_bckgrnd.hpp) or k_kpp_tidal<PBC, true> adds the column's background
+  if (KH.tidal_on || KH.bck_on) { g_kpp.bckgrnd_vdc = KH.zero_bck; g_kpp.bckgrnd_vvc = KH.zero_bck; }
   const int g_kpp_col = KH.col;
   const dim3 GC(col_grid(g, POP_COL_THREADS), g.nblocks), BC(POP_COL_THREADS);
   const dim3 G3((g.n2 + 255) / 256, g.km, g.nblocks);
@@ -1652,7 +1669,12 @@ inline int kpp_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParam
   else if (sel.interior == Sel::GENERIC) with_flags([&](auto PBC) { hipLaunchKernelGGL(k_kpp_interior<PBC.value>, GC, BC, 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, (const double *)DBLOC, RIW, VISC, s.VDC[0], s.VDC[1]); }, g.pbc);
   // DBLOC and the interior coefficients of every level are complete on st here in every form (the on-demand forms leave levels of
   // DBSFC and WU unwritten, never of DBLOC), and nothing before k_kpp_blmix reads VISC / VDC
-  if (KH.tidal_on) with_flags([&](auto PBC) { hipLaunchKernelGGL(k_kpp_tidal<PBC.value>, GC, BC, 0, st, g, KH.tidal, (int)g_kpp.vdc_same, (const double *)DBLOC, VISC, s.VDC[0], s.VDC[1]); }, g.pbc);
+  // (the same two conditions hold for k_kpp_bckgrnd, which reads VISC / VDC of the levels k < KMT only: DESIGN.md section 11)
+  if (KH.tidal_on) {
+    TidalDev td = KH.tidal;
+    if (KH.bck_on) { td.B2 = KH.bck.VDC; td.BPR2 = KH.bck.VVC_PR; }
+    with_flags([&](auto PBC, auto HV) { hipLaunchKernelGGL((k_kpp_tidal<PBC.value, HV.value>), GC, BC, 0, st, g, td, (int)g_kpp.vdc_same, (const double *)DBLOC, VISC, s.VDC[0], s.VDC[1]); }, g.pbc, KH.bck_on);
+  } else if (KH.bck_on) hipLaunchKernelGGL(k_kpp_bckgrnd, GC, BC, 0, st, g, KH.bck, (int)g_kpp.vdc_same, VISC, s.VDC[0], s.VDC[1]);
   if (side) hipStreamWaitEvent(st, KH.ev_join, 0);
   else depth(st);
   with_flags([&](auto PBC, auto SAME, auto SPARSE) {

@@ -117,6 +117,7 @@ inline int mix_state_host(const HostModel &h, const DevGrid &g, int kk, const do
 
 #include "kernels_del4.hpp"
 #include "kernels_tidal.hpp"
+#include "kernels_bckgrnd.hpp"
 #include "kernels_kpp.hpp"
 
 namespace pop {

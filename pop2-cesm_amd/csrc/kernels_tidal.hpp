@@ -17,6 +17,7 @@ struct TidalDev {
   const double *COEF = nullptr;     // TIDAL_COEF_3D (nxb, nyb, km, nblocks)
   const int *BOX = nullptr;         // REGION_BOX2D; nullptr without ltidal_min_regions
   CArr zgrid, bvdc, bvvc_pr;        // KPP's zgrid; bckgrnd_vdc(k), bckgrnd_vvc(k) / Prandtl (1..km): wave-uniform index, scalar loads
+  const double *B2 = nullptr, *BPR2 = nullptr;   // lhoriz_varying_bckgrnd (HV): bckgrnd_vdc(i,j), bckgrnd_vvc(i,j) / Prandtl; set at the launch
   CArr minval;                      // tidal_min_values by region, 1-based
   CArrI klev;                       // tidal_min_regions_klevels by region, 1-based
   double mix_max = 0.0, prandtl = 0.0;
@@ -30,7 +31,8 @@ struct TidalDev {
 // level k + 1 are requested before level k is evaluated.  The previous level's final TIDAL_DIFF stays in a register for the
 // stability control.
 struct TidalRaw { double db, co, visc, vd1, vd2; };
-template <bool PBC = false>
+// HV (after pop_init_kpp_bckgrnd): the background is the column's value of the two 2-D fields, loaded once, not the per-level one.
+template <bool PBC = false, bool HV = false>
 __global__ void __launch_bounds__(POP_COL_THREADS)
 k_kpp_tidal(DevGrid g, TidalDev td, int vdc_same, const double *__restrict__ DBLOC, double *__restrict__ VISC,
             double *__restrict__ VDC1, double *__restrict__ VDC2) {
@@ -42,6 +44,8 @@ k_kpp_tidal(DevGrid g, TidalDev td, int vdc_same, const double *__restrict__ DBL
   if (kmt < 2) return;
   const long long vb = ((long long)c.b * (km + 2)) * n2 + c.p2;
   const double dzbc = PBC ? g.DZBC[c.q2] : 0.0;
+  double hb = 0.0, hbpr = 0.0;
+  if constexpr (HV) { hb = td.B2[c.q2]; hbpr = td.BPR2[c.q2]; }
   // region minimum: the levels klo .. KMT - 1 of a column inside a box (REGION_BOX3D, tidal_mixing.F90:986-997)
   double rmin = 0.0; int klo = km + 1;
   if (td.BOX) {
@@ -73,8 +77,8 @@ k_kpp_tidal(DevGrid g, TidalDev td, int vdc_same, const double *__restrict__ DBL
     if (td.stabc && k > 2 && k >= kmt - 2) t = fmax(t, prev);   // k == KMT - 1 or KMT - 2
     if (k >= klo) t = fmax(t, rmin);
     prev = t;
-    const double kv = fmin(td.bvdc[k] + t, td.mix_max);
-    const double kvm = td.prandtl * fmin(td.bvvc_pr[k] + t, td.mix_max);
+    const double kv = fmin((HV ? hb : td.bvdc[k]) + t, td.mix_max);
+    const double kvm = td.prandtl * fmin((HV ? hbpr : td.bvvc_pr[k]) + t, td.mix_max);
     VISC[o] = cu.visc + kvm;
     VDC1[vb + (long long)k * n2] = cu.vd1 + kv;
     if (!vdc_same) VDC2[vb + (long long)k * n2] = cu.vd2 + kv;

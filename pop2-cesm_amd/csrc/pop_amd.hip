@@ -1042,9 +1042,16 @@ static int join_side(pop_ctx *c, bool keep_ahead = false) {
 }
 int pop_get_field(pop_ctx *c, const char *name, int tl, int n, double *host, long long count) {
   const std::string nm(name);
-  if (nm == "TIDAL_ENERGY_FLUX" || nm == "TIDAL_COEF_3D" || (nm == "TLON" && c->tidal.on)) {   // init-time fields of pop_init_tidal_mixing (host copies)
+  if (nm == "BCKGRND_VDC" || nm == "BCKGRND_VVC" || (nm == "TLON" && !c->tlon.empty())) {   // init-time fields of pop_init_kpp_bckgrnd (host copies); TLON of either init call
+    if (nm != "TLON" && !c->bck.on) { c->err = nm + " exists after pop_init_kpp_bckgrnd with lhoriz_varying_bckgrnd only"; return 1; }
+    const std::vector<double> &v = nm == "TLON" ? c->tlon : nm == "BCKGRND_VDC" ? c->bck.f.vdc : c->bck.f.vvc;
+    if ((long long)v.size() != count) { c->err = "count mismatch for " + nm; return 1; }
+    std::copy(v.begin(), v.end(), host);
+    return 0;
+  }
+  if (nm == "TIDAL_ENERGY_FLUX" || nm == "TIDAL_COEF_3D") {   // init-time fields of pop_init_tidal_mixing (host copies)
     if (!c->tidal.on) { c->err = nm + " exists after pop_init_tidal_mixing with ltidal_mixing only"; return 1; }
-    const std::vector<double> &v = nm == "TLON" ? c->tidal.f.tlon : nm == "TIDAL_COEF_3D" ? c->tidal.f.coef : c->tidal.f.flux;
+    const std::vector<double> &v = nm == "TIDAL_COEF_3D" ? c->tidal.f.coef : c->tidal.f.flux;
     if ((long long)v.size() != count) { c->err = "count mismatch for " + nm; return 1; }
     std::copy(v.begin(), v.end(), host);
     return 0;
@@ -2379,7 +2386,8 @@ int pop_init_tidal_mixing(pop_ctx *c, const pop_tidal_nml *nml, const double *en
   if (!energy_flux || count != (long long)a2) { c->err = "pop_init_tidal_mixing: count mismatch for the energy flux (nx_block * ny_block * nblocks)"; return 1; }
   std::vector<double> flux(energy_flux, energy_flux + a2);
   if (pop_halo_update_host_r8_loc(c, flux.data(), 1, 0.0, 0, 0)) return 1;   // centre, scalar: the record is read into the physical cells
-  host_tidal_build(c->h, n, flux.data(), c->tidal.f);
+  if (c->tlon.empty()) host_tlon_build(c->h, c->tlon);
+  host_tidal_build(c->h, n, flux.data(), c->tlon, c->tidal.f);
   if (!c->host_only) {
     KppHost *K = (KppHost *)c->mix.kpp;
     TidalDev &td = K->tidal;
@@ -2403,8 +2411,7 @@ int pop_init_tidal_mixing(pop_ctx *c, const pop_tidal_nml *nml, const double *en
     td.minval = p;
     if (dev_upload(c, &pi, klev.data(), klev.size())) return 1;
     td.klev = pi;
-    if (dev_upload(c, &p, zero.data(), zero.size())) return 1;
-    K->zero_bck = p;
+    if (!K->zero_bck) { if (dev_upload(c, &p, zero.data(), zero.size())) return 1; K->zero_bck = p; }   // pop_init_kpp_bckgrnd may have made it
     td.zgrid = K->dev.zgrid;
     td.mix_max = n.tidal_mix_max; td.prandtl = cf.Prandtl;
     td.lmax = n.ltidal_max ? 1 : 0; td.stabc = (n.ltidal_stabc && !n.lccsm_control_compatible) ? 1 : 0;
@@ -2414,6 +2421,53 @@ int pop_init_tidal_mixing(pop_ctx *c, const pop_tidal_nml *nml, const double *en
     K->tidal_on = true;
   }
   c->tidal.nml = n; c->tidal.inited = true; c->tidal.on = true;
+  return 0;
+}
+
+// ---- latitude-varying KPP background diffusivity (the lhoriz_varying_bckgrnd branch of init_vmix_kpp, vmix_kpp.F90:544-611)
+void pop_kpp_bckgrnd_nml_init(pop_kpp_bckgrnd_nml *nml) { if (nml) kpp_bckgrnd_nml_defaults(*nml); }
+int pop_init_kpp_bckgrnd(pop_ctx *c, const pop_kpp_bckgrnd_nml *nml) {
+  if (!c) return 1;
+  if (!nml || nml->struct_bytes != (int)sizeof(pop_kpp_bckgrnd_nml)) { c->err = "pop_init_kpp_bckgrnd: pop_kpp_bckgrnd_nml.struct_bytes is not sizeof(pop_kpp_bckgrnd_nml) of this library (" + std::to_string(sizeof(pop_kpp_bckgrnd_nml)) + ")"; return 1; }
+  if (c->h.plan_only) { c->err = "pop_init_kpp_bckgrnd: the context has no grid fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+  if (c->bck.inited) { c->err = "pop_init_kpp_bckgrnd: called a second time (once per context)"; return 1; }
+  if (c->ran || c->nsteps_total > 0) { c->err = "pop_init_kpp_bckgrnd: a step or a phase has already run (call it right after pop_create)"; return 1; }
+  if (!nml->lhoriz_varying_bckgrnd) { c->bck.inited = true; c->bck.nml = *nml; return 0; }   // builds nothing
+  const pop_config &cf = c->h.c;
+  if (cf.vmix_choice != 3) { c->err = "lhoriz_varying_bckgrnd needs vmix_choice = 3 (kpp): it is a switch of vmix_kpp_nml"; return 1; }
+  if (cf.bckgrnd_vdc2 != 0.0) { c->err = "lhoriz_varying_bckgrnd needs bckgrnd_vdc2 = 0 (vmix_kpp.F90:518)"; return 1; }
+  if (nml->bckgrnd_vdc_eq < 0.0 || nml->bckgrnd_vdc_psim < 0.0 || nml->bckgrnd_vdc_ban < 0.0) {
+    c->err = "lhoriz_varying_bckgrnd: negative parameter (bckgrnd_vdc_eq, bckgrnd_vdc_psim, bckgrnd_vdc_ban)"; return 1;
+  }
+  const bool own_tlon = c->tlon.empty();
+  if (own_tlon) host_tlon_build(c->h, c->tlon);
+  host_bckgrnd_build(c->h, *nml, c->tlon, c->bck.f);
+  if (!c->host_only) {
+    KppHost *K = (KppHost *)c->mix.kpp;
+    const size_t a2 = c->h.n2 * c->h.nblocks;
+    // a failed upload leaves the context as it was before the call: no host field readable, nothing of KppHost::bck set
+    BckDev bd;
+    const double *zero_bck = K->zero_bck;   // pop_init_tidal_mixing may have made it
+    double *p = nullptr;
+    bool bad = dev_upload(c, &p, c->bck.f.vdc.data(), a2) != 0;
+    bd.VDC = p;
+    bad = bad || dev_upload(c, &p, c->bck.f.vvc.data(), a2);
+    bd.VVC = p;
+    bad = bad || dev_upload(c, &p, c->bck.f.vvc_pr.data(), a2);
+    bd.VVC_PR = p;
+    if (!bad && !zero_bck) {
+      std::vector<double> zero(c->h.km + 3, 0.0);
+      bad = dev_upload(c, &p, zero.data(), zero.size()) != 0;
+      zero_bck = p;
+    }
+    if (bad) {
+      c->bck.f = BckgrndFields();
+      if (own_tlon) c->tlon.clear();
+      return 1;
+    }
+    K->bck = bd; K->zero_bck = zero_bck; K->bck_on = true;
+  }
+  c->bck.nml = *nml; c->bck.inited = true; c->bck.on = true;
   return 0;
 }
 

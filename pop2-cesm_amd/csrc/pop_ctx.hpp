@@ -147,7 +147,10 @@ struct pop_ctx {
   // Jayne tidal mixing (pop_init_tidal_mixing): the resolved namelist and the init-time fields of the local blocks (host copies serve
   // pop_get_field; the device copies and the kernel's arguments live in KppHost::tidal)
   struct Tidal { bool inited = false, on = false; pop_tidal_nml nml{}; TidalFields f; } tidal;
-  bool ran = false;                                        // a step or a phase has run (pop_init_tidal_mixing is refused afterwards)
+  // latitude-varying KPP background (pop_init_kpp_bckgrnd): host copies; the device copies live in KppHost::bck
+  struct Bckgrnd { bool inited = false, on = false; pop_kpp_bckgrnd_nml nml{}; BckgrndFields f; } bck;
+  std::vector<double> tlon;                                // TLON of the local blocks, formed once by whichever of the two init calls comes first
+  bool ran = false;                                        // a step or a phase has run (pop_init_tidal_mixing / pop_init_kpp_bckgrnd are refused afterwards)
   // time stepping
   int oldt = 0, curt = 1, newt = 2, mixt = 1;
   int first_step = 1, leapfrogts = 1, f_euler_ts = 0, avg_ts = 0, nsteps_total = 0, nsteps_this_interval = 0;

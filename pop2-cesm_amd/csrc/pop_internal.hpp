@@ -121,12 +121,17 @@ struct HostModel {
 int host_build(HostModel &h);            // host_setup.cpp
 // ---- Jayne tidal mixing, init-time fields on the local blocks (host_tidal.cpp; tidal_mixing.F90)
 struct TidalFields {
-  std::vector<double> flux, tlon, coef;    // TIDAL_ENERGY_FLUX_2D [g/s^3], TLON [radians], TIDAL_COEF_3D (nxb,nyb,km,nblocks)
+  std::vector<double> flux, coef;          // TIDAL_ENERGY_FLUX_2D [g/s^3], TIDAL_COEF_3D (nxb,nyb,km,nblocks)
   std::vector<int> box;                    // REGION_BOX2D: 1-based region of ltidal_min_regions, 0 = none
 };
 void tidal_nml_defaults(pop_tidal_nml &n);
 int tidal_nml_resolve(pop_tidal_nml &n, std::string &err);
-void host_tidal_build(const HostModel &h, const pop_tidal_nml &n, const double *flux, TidalFields &out);
+void host_tlon_build(const HostModel &h, std::vector<double> &tlon);   // TLON [radians] of the local blocks (calc_tpoints + halo update)
+void host_tidal_build(const HostModel &h, const pop_tidal_nml &n, const double *flux, const std::vector<double> &tlon, TidalFields &out);
+// ---- latitude-varying KPP background diffusivity on the local blocks (host_bckgrnd.cpp; vmix_kpp.F90:544-611)
+struct BckgrndFields { std::vector<double> vdc, vvc, vvc_pr; };   // bckgrnd_vdc, Prandtl * bckgrnd_vdc, (Prandtl * bckgrnd_vdc) / Prandtl: 2-D
+void kpp_bckgrnd_nml_defaults(pop_kpp_bckgrnd_nml &n);
+void host_bckgrnd_build(const HostModel &h, const pop_kpp_bckgrnd_nml &n, const std::vector<double> &tlon, BckgrndFields &out);
 // ---- POP binary restart files (host_restart.cpp; restart.F90, io_binary.F90)
 struct RestartField {
   std::string name, dev; int tl, n, ndims, id;       // file name; device field, time level (0 old, 1 cur), tracer; first record

@@ -102,6 +102,12 @@
       integer (c_int), dimension(POP_MAX_TIDAL_MIN_REGIONS) :: tidal_min_regions_klevels
    end type pop_tidal_nml
 
+   ! mirrors `struct pop_kpp_bckgrnd_nml` (lhoriz_varying_bckgrnd of vmix_kpp_nml); fill with pop_kpp_bckgrnd_nml_init, then set fields
+   type, bind(C) :: pop_kpp_bckgrnd_nml
+      integer (c_int) :: struct_bytes, lhoriz_varying_bckgrnd, larctic_bckgrnd_vdc
+      real (c_double) :: bckgrnd_vdc_eq, bckgrnd_vdc_psim, bckgrnd_vdc_ban
+   end type pop_kpp_bckgrnd_nml
+
    type (c_ptr), save :: pop_ctx = c_null_ptr   ! the one model instance of this task
 
    interface
@@ -391,6 +397,15 @@
          type (pop_tidal_nml), intent(in) :: nml
          real (c_double), intent(in) :: energy_flux(*)      ! W/m^2, (nx_block, ny_block, nblocks_clinic)
          integer (c_long_long), value :: count
+      end function
+      subroutine pop_kpp_bckgrnd_nml_init(nml) bind(C, name='pop_kpp_bckgrnd_nml_init')
+         import :: pop_kpp_bckgrnd_nml
+         type (pop_kpp_bckgrnd_nml), intent(out) :: nml
+      end subroutine
+      integer (c_int) function pop_init_kpp_bckgrnd(ctx, nml) bind(C, name='pop_init_kpp_bckgrnd')
+         import :: c_int, c_ptr, pop_kpp_bckgrnd_nml
+         type (c_ptr), value :: ctx
+         type (pop_kpp_bckgrnd_nml), intent(in) :: nml
       end function
    end interface
 
