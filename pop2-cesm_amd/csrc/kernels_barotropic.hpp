@@ -334,6 +334,11 @@ __global__ void k_finalize(const double *__restrict__ blocksum, int nblocks_tot,
   }
 }
 
+// cell (i,j), 0-based, of local block b belongs to the physical domain
+__device__ __forceinline__ bool interior(const DevGrid &g, int b, int i, int j) {
+  return i + 1 >= g.ib && i + 1 <= blk_ie(g, b) && j + 1 >= g.jb && j + 1 <= blk_je(g, b);
+}
+
 // POP_GlobalMaxval / Minval / Maxloc / Minloc (mpi/POP_ReductionsMod.F90:2670-3223, 4002-4400): per workgroup the
 // extreme value of the physical cells selected by the mask (non-zero = selected) and the smallest cell index that
 // attains it; partial[2*slot] = value, partial[2*slot+1] = cell index within the rank (-1: none selected)
@@ -346,7 +351,7 @@ k_extreme_partial(DevGrid g, const double *__restrict__ A, const double *__restr
   if (p2 < g.n2) {
     const int i = p2 % g.nxb, j = p2 / g.nxb;
     const long long q = (long long)b * g.n2 + p2;
-    if (i + 1 >= g.ib && i + 1 <= blk_ie(g, b) && j + 1 >= g.jb && j + 1 <= blk_je(g, b) && (!M || M[q] != 0.0)) { v = A[q]; idx = (double)q; }
+    if (interior(g, b, i, j) && (!M || M[q] != 0.0)) { v = A[q]; idx = (double)q; }
   }
   sv[t] = v; si[t] = idx;
   __syncthreads();
@@ -368,7 +373,7 @@ k_count_partial(DevGrid g, const double *__restrict__ A, const double *__restric
   if (p2 < g.n2) {
     const int i = p2 % g.nxb, j = p2 / g.nxb;
     const long long q = (long long)b * g.n2 + p2;
-    if (i + 1 >= g.ib && i + 1 <= blk_ie(g, b) && j + 1 >= g.jb && j + 1 <= blk_je(g, b) && A[q] != 0.0 && !(DUP && DUP[q] != 0.0)) v[0] = 1.0;
+    if (interior(g, b, i, j) && A[q] != 0.0 && !(DUP && DUP[q] != 0.0)) v[0] = 1.0;
   }
   wg_reduce_store<1>(v, partial, b * gridDim.x + red_chunk(g));
 }
@@ -381,7 +386,7 @@ k_dot_partial_dup(DevGrid g, const double *__restrict__ A, const double *__restr
   double v[2] = {0.0, 0.0};
   if (p2 < g.n2) {
     const int i = p2 % g.nxb, j = p2 / g.nxb;
-    if (i + 1 >= g.ib && i + 1 <= blk_ie(g, b) && j + 1 >= g.jb && j + 1 <= blk_je(g, b)) {
+    if (interior(g, b, i, j)) {
       const long long q = (long long)b * g.n2 + p2;
       double x = A[q];
       if (M) x = x * M[q];
@@ -431,7 +436,7 @@ k_dot_partial(DevGrid g, const double *__restrict__ A, const double *__restrict_
   double v[1] = {0.0};
   if (p2 < g.n2) {
     const int i = p2 % g.nxb, j = p2 / g.nxb;
-    if (i + 1 >= g.ib && i + 1 <= blk_ie(g, b) && j + 1 >= g.jb && j + 1 <= blk_je(g, b)) {
+    if (interior(g, b, i, j)) {
       const long long q = (long long)b * g.n2 + p2;
       double x = A[q];
       if (Bv) x = x * Bv[q];
@@ -456,9 +461,6 @@ __device__ __forceinline__ double btrop_op(const DevGrid &g, const double *__res
 }
 __device__ __forceinline__ bool op_range(const DevGrid &g, int i, int j) {   // i,j = 2..n-1 (1-based)
   return i >= 1 && i <= g.nxb - 2 && j >= 1 && j <= g.nyb - 2;
-}
-__device__ __forceinline__ bool interior(const DevGrid &g, int b, int i, int j) {
-  return i + 1 >= g.ib && i + 1 <= blk_ie(g, b) && j + 1 >= g.jb && j + 1 <= blk_je(g, b);
 }
 
 struct SolverArgs {

@@ -135,5 +135,26 @@ int read_scalars(pop_ctx *c, SolverScalars *out) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
+// the tail every global sum shares: partials in c->partial -> the total on the host
+template <int NF>
+int finish_sum(pop_ctx *c, int mode, double *result) {
+  if (reduce_finish<NF>(c, mode)) return 1;
+  SolverScalars s;
+  if (read_scalars(c, &s)) return 1;
+  *result = s.sum0;
+  return 0;
+}
+// a tripole grid and an N-face or NE-corner field: the redundant half of the top row counts once (mpi/POP_ReductionsMod.F90:308-341)
+bool top_row_once(const pop_ctx *c, int field_loc) { return c->h.c.ns_boundary == 2 && (field_loc == 1 || field_loc == 2); }
+// b4b global sum of A [* B] [* M] over the physical domain, result on the host.  once: the tripole rule; that kernel has no B operand
+int masked_sum(pop_ctx *c, const double *A, const double *B, const double *M, bool once, double *result) {
+  if (once && B) { c->err = "global sum: the product of two fields has no form with the tripole top-row rule"; return 1; }
+  if (once) {
+    hipLaunchKernelGGL(k_dot_partial_dup, grid_2d(c), dim3(POP_RED_THREADS), 0, c->stream, c->g, A, M, (const double *)c->d2["TRIPOLE_DUP"], c->partial);
+    return finish_sum<2>(c, FIN_TRIPOLE, result);
+  }
+  hipLaunchKernelGGL(k_dot_partial, grid_2d(c), dim3(POP_RED_THREADS), 0, c->stream, c->g, A, B, M, c->partial);
+  return finish_sum<1>(c, FIN_PLAIN, result);
+}
 
 }  // namespace

@@ -38,10 +38,12 @@ int need_device(pop_ctx *c) {
   return 0;
 }
 
+// time level of the ABI (0 old, 1 cur, 2 new) -> index of the rotating arrays
+int time_index(const pop_ctx *c, int tl) { return tl == 0 ? c->oldt : tl == 1 ? c->curt : c->newt; }
 // resolve a named field: device pointer, element count (local), whether tl / n apply
 int resolve(pop_ctx *c, const std::string &name, int tl, int n, double **ptr, long long *count) {
   const long long a2 = (long long)c->g.n2 * c->g.nblocks, a3 = (long long)c->g.n3 * c->g.nblocks;
-  const int t = tl == 0 ? c->oldt : tl == 1 ? c->curt : c->newt;
+  const int t = time_index(c, tl);
   auto ok = [&](double *p, long long cnt) { *ptr = p; *count = cnt; return p ? 0 : 1; };
   if (name == "TRACER") return (n >= 0 && n < c->h.nt) ? ok(c->TR[n][t], a3) : 1;
   if (name == "UVEL") return ok(c->U[t], a3);
@@ -108,6 +110,50 @@ int resolve(pop_ctx *c, const std::string &name, int tl, int n, double **ptr, lo
   if (name == "SMFT") return ok(c->d2[n == 0 ? "SMFT1" : "SMFT2"], a2);
   auto it = c->d2.find(name);
   if (it != c->d2.end()) return ok(it->second, a2);
+  return 1;
+}
+
+// ---- what the entry points do with a named-field argument, stated once
+int unknown(pop_ctx *c, const char *what, const char *name) { c->err = std::string(what) + name; return 1; }
+int field_arg(pop_ctx *c, const char *name, int tl, int n, double **ptr, long long *count) {
+  return resolve(c, name, tl, n, ptr, count) ? unknown(c, "unknown field ", name) : 0;
+}
+int mask_arg(pop_ctx *c, const char *name, double **ptr) {   // optional: no name, no mask
+  long long cnt;
+  *ptr = nullptr;
+  return name && resolve(c, name, 0, 0, ptr, &cnt) ? unknown(c, "unknown mask ", name) : 0;
+}
+int count_is(pop_ctx *c, long long have, long long want, const char *name) {
+  if (have == want) return 0;
+  c->err = name ? std::string("count mismatch for ") + name : std::string("count mismatch");
+  return 1;
+}
+template <class V, class T>
+int copy_out(pop_ctx *c, const V &v, T *host, long long count, const char *name) {   // a host vector to the caller's array
+  if (count_is(c, (long long)v.size(), count, name)) return 1;
+  std::copy(v.begin(), v.end(), host);
+  return 0;
+}
+// The caller has written this field (pop_set_field) or may write it (pop_field_device_ptr): ghost cells and the non-local
+// source are no longer known to be current, and a new prognostic state may carry other values on land, so the next steps
+// run every workgroup again (land elimination).
+void mark_written(pop_ctx *c, const char *name, int tl) {
+  const std::string nm(name);
+  if (nm == "KPP_SRC") { c->kpp_src_user = true; c->src_dirty = true; c->src_dirty_alt = true; }
+  if (nm == "TRACER") c->tr_ghosts_ok[time_index(c, tl)] = false;
+  if (nm == "UVEL" || nm == "VVEL") c->uv_ghosts_ok[time_index(c, tl)] = false;
+  for (const char *f : {"TRACER", "UVEL", "VVEL", "RHO", "PSURF", "GRADPX", "GRADPY", "UBTROP", "VBTROP", "PGUESS", "FW_OLD"})
+    if (nm == f) c->full_left = c->land_full_steps;
+}
+// guards of the host-array halo updates
+int loc_kind_ok(pop_ctx *c, int loc, int kind, const char *text) {
+  if (loc >= 0 && loc <= 3 && kind >= 0 && kind <= 2) return 0;
+  c->err = text;
+  return 1;
+}
+int single_rank_only(pop_ctx *c) {
+  if (c->h.nranks == 1) return 0;
+  c->err = "host halo update needs all blocks on one rank";
   return 1;
 }
 
@@ -1044,17 +1090,11 @@ int pop_get_field(pop_ctx *c, const char *name, int tl, int n, double *host, lon
   const std::string nm(name);
   if (nm == "BCKGRND_VDC" || nm == "BCKGRND_VVC" || (nm == "TLON" && !c->tlon.empty())) {   // init-time fields of pop_init_kpp_bckgrnd (host copies); TLON of either init call
     if (nm != "TLON" && !c->bck.on) { c->err = nm + " exists after pop_init_kpp_bckgrnd with lhoriz_varying_bckgrnd only"; return 1; }
-    const std::vector<double> &v = nm == "TLON" ? c->tlon : nm == "BCKGRND_VDC" ? c->bck.f.vdc : c->bck.f.vvc;
-    if ((long long)v.size() != count) { c->err = "count mismatch for " + nm; return 1; }
-    std::copy(v.begin(), v.end(), host);
-    return 0;
+    return copy_out(c, nm == "TLON" ? c->tlon : nm == "BCKGRND_VDC" ? c->bck.f.vdc : c->bck.f.vvc, host, count, name);
   }
   if (nm == "TIDAL_ENERGY_FLUX" || nm == "TIDAL_COEF_3D") {   // init-time fields of pop_init_tidal_mixing (host copies)
     if (!c->tidal.on) { c->err = nm + " exists after pop_init_tidal_mixing with ltidal_mixing only"; return 1; }
-    const std::vector<double> &v = nm == "TIDAL_COEF_3D" ? c->tidal.f.coef : c->tidal.f.flux;
-    if ((long long)v.size() != count) { c->err = "count mismatch for " + nm; return 1; }
-    std::copy(v.begin(), v.end(), host);
-    return 0;
+    return copy_out(c, nm == "TIDAL_COEF_3D" ? c->tidal.f.coef : c->tidal.f.flux, host, count, name);
   }
   if (nm == "TIDAL_DIFF" || nm == "TIDAL_N2" || nm == "KVMIX" || nm == "KVMIX_M") {
     if (!c->tidal.on || !c->tidal.nml.tidal_diag) { c->err = nm + " exists after pop_init_tidal_mixing with ltidal_mixing and tidal_diag only"; return 1; }
@@ -1064,24 +1104,17 @@ int pop_get_field(pop_ctx *c, const char *name, int tl, int n, double *host, lon
     if (nm == "F_PARA" || nm == "F_PERP") {
       const std::vector<double> &all = c->h.aniso_f[nm == "F_PARA" ? 0 : 1];
       if (all.empty()) { c->err = nm + " exists with hmix_momentum = 3 and lvariable_hmix_aniso only"; return 1; }
-      const std::vector<double> loc = local_part3(c->h, all);
-      if ((long long)loc.size() != count) { c->err = "count mismatch for " + nm; return 1; }
-      std::copy(loc.begin(), loc.end(), host);
-      return 0;
+      return copy_out(c, local_part3(c->h, all), host, count, name);
     }
     std::string key = nm;
     if (nm == "SMF") key = n == 0 ? "SMF1" : "SMF2";
     if (nm == "SMFT") key = n == 0 ? "SMFT1" : "SMFT2";
     auto it = c->h.f2.find(key);
     if (it == c->h.f2.end()) { c->err = "unknown field " + nm; return 1; }
-    auto loc = local_part(c->h, it->second);
-    if ((long long)loc.size() != count) { c->err = "count mismatch for " + nm; return 1; }
-    std::copy(loc.begin(), loc.end(), host);
-    return 0;
+    return copy_out(c, local_part(c->h, it->second), host, count, name);
   }
   double *p; long long cnt;
-  if (resolve(c, nm, tl, n, &p, &cnt)) { c->err = "unknown field " + nm; return 1; }
-  if (cnt != count) { c->err = "count mismatch for " + nm; return 1; }
+  if (field_arg(c, name, tl, n, &p, &cnt) || count_is(c, cnt, count, name)) return 1;
   if (join_side(c)) return 1;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(host, p, cnt * sizeof(double), hipMemcpyDeviceToHost));
@@ -1090,8 +1123,7 @@ int pop_get_field(pop_ctx *c, const char *name, int tl, int n, double *host, lon
 int pop_set_field(pop_ctx *c, const char *name, int tl, int n, const double *host, long long count) {
   if (need_device(c)) return 1;
   double *p; long long cnt;
-  if (resolve(c, name, tl, n, &p, &cnt)) { c->err = std::string("unknown field ") + name; return 1; }
-  if (cnt != count) { c->err = std::string("count mismatch for ") + name; return 1; }
+  if (field_arg(c, name, tl, n, &p, &cnt) || count_is(c, cnt, count, name)) return 1;
   if (join_side(c)) return 1;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(p, host, cnt * sizeof(double), hipMemcpyHostToDevice));
@@ -1113,45 +1145,30 @@ int pop_set_field(pop_ctx *c, const char *name, int tl, int n, const double *hos
     for (long long q = 0; q < cnt; ++q) idx[q] = sw_chl_index(c->h.sw, host[q]);
     HIPCHK(c, hipMemcpy(c->h.sw.CHLI, idx.data(), (size_t)cnt * sizeof(int), hipMemcpyHostToDevice));
   }
-  if (!strcmp(name, "KPP_SRC")) { c->kpp_src_user = true; c->src_dirty = true; c->src_dirty_alt = true; }
-  if (!strcmp(name, "TRACER")) c->tr_ghosts_ok[tl == 0 ? c->oldt : tl == 1 ? c->curt : c->newt] = false;
-  if (!strcmp(name, "UVEL") || !strcmp(name, "VVEL")) c->uv_ghosts_ok[tl == 0 ? c->oldt : tl == 1 ? c->curt : c->newt] = false;
-  // a new prognostic state may carry other values on land: the next steps run every workgroup again (land elimination)
-  for (const char *f : {"TRACER", "UVEL", "VVEL", "RHO", "PSURF", "GRADPX", "GRADPY", "UBTROP", "VBTROP", "PGUESS", "FW_OLD"})
-    if (!strcmp(name, f)) c->full_left = c->land_full_steps;
+  mark_written(c, name, tl);
   return 0;
 }
 int pop_get_ifield(pop_ctx *c, const char *name, int *host, long long count) {
   if (!strcmp(name, "KBL")) {   // KPP: level of the boundary-layer depth that belongs to the current KPP_SRC (device-resident)
     if (need_device(c) || join_side(c)) return 1;
     if (!c->KBL) { c->err = "KBL exists with vmix_choice = 3 only"; return 1; }
-    if (count != (long long)c->g.n2 * c->g.nblocks) { c->err = "count mismatch"; return 1; }
+    if (count_is(c, count, (long long)c->g.n2 * c->g.nblocks, nullptr)) return 1;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(host, c->KBL, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
   }
   if (!strcmp(name, "TIDAL_REGION_BOX2D")) {   // REGION_BOX2D of ltidal_min_regions (0 everywhere without it)
     if (!c->tidal.on) { c->err = "TIDAL_REGION_BOX2D exists after pop_init_tidal_mixing with ltidal_mixing only"; return 1; }
-    if ((long long)c->tidal.f.box.size() != count) { c->err = "count mismatch"; return 1; }
-    std::copy(c->tidal.f.box.begin(), c->tidal.f.box.end(), host);
-    return 0;
+    return copy_out(c, c->tidal.f.box, host, count, nullptr);
   }
   auto it = c->h.i2.find(name);
   if (it == c->h.i2.end()) { c->err = std::string("unknown integer field ") + name; return 1; }
-  auto loc = local_part(c->h, it->second);
-  if ((long long)loc.size() != count) { c->err = "count mismatch"; return 1; }
-  std::copy(loc.begin(), loc.end(), host);
-  return 0;
+  return copy_out(c, local_part(c->h, it->second), host, count, nullptr);
 }
 void *pop_field_device_ptr(pop_ctx *c, const char *name, int tl, int n) {
   if (c->host_only) return nullptr;
-  join_side(c);   // the caller may read the field on the launch stream
-  if (!strcmp(name, "TRACER")) c->tr_ghosts_ok[tl == 0 ? c->oldt : tl == 1 ? c->curt : c->newt] = false;   // ... or write it
-  if (!strcmp(name, "UVEL") || !strcmp(name, "VVEL")) c->uv_ghosts_ok[tl == 0 ? c->oldt : tl == 1 ? c->curt : c->newt] = false;
-  if (!strcmp(name, "KPP_SRC")) { c->kpp_src_user = true; c->src_dirty = true; c->src_dirty_alt = true; }
-  // ... with other values on land: the next steps run every workgroup again, as after pop_set_field
-  for (const char *f : {"TRACER", "UVEL", "VVEL", "RHO", "PSURF", "GRADPX", "GRADPY", "UBTROP", "VBTROP", "PGUESS", "FW_OLD"})
-    if (!strcmp(name, f)) c->full_left = c->land_full_steps;
+  join_side(c);               // the caller may read the field on the launch stream
+  mark_written(c, name, tl);  // ... or write it
   double *p; long long cnt;
   return resolve(c, name, tl, n, &p, &cnt) ? nullptr : (void *)p;
 }
@@ -1714,8 +1731,8 @@ int pop_solver_preconditioner(pop_ctx *c, const char *x_name, int x_tl, const ch
   if (need_device(c)) return 1;
   if (join_side(c)) return 1;
   double *x, *px; long long cnt, a2 = (long long)c->g.n2 * c->g.nblocks;
-  if (resolve(c, x_name, x_tl, 0, &x, &cnt) || cnt != a2) { c->err = std::string("unknown 2-D field ") + x_name; return 1; }
-  if (resolve(c, px_name, px_tl, 0, &px, &cnt) || cnt != a2 || px == x) { c->err = std::string("unknown 2-D field ") + px_name; return 1; }
+  if (resolve(c, x_name, x_tl, 0, &x, &cnt) || cnt != a2) return unknown(c, "unknown 2-D field ", x_name);
+  if (resolve(c, px_name, px_tl, 0, &px, &cnt) || cnt != a2 || px == x) return unknown(c, "unknown 2-D field ", px_name);
   HIPCHK(c, hipMemsetAsync(px, 0, sizeof(double) * a2, c->stream));
   if (c->use_evp) return evp_apply(c, x, px, false);   // (any field the caller names: no assumption about its land values)
   HIPCHK(c, hipMemcpyAsync(px, x, sizeof(double) * a2, hipMemcpyDeviceToDevice, c->stream));
@@ -1731,7 +1748,7 @@ int pop_operator(pop_ctx *c, int op, int k, const char *a_name, const char *b_na
   const long long a2 = (long long)c->g.n2 * c->g.nblocks, a3 = (long long)c->g.n3 * c->g.nblocks;
   auto slab = [&](const char *name, int t, double **p, long long *stride) -> int {
     long long cnt;
-    if (!name || resolve(c, name, t, 0, p, &cnt) || (cnt != a2 && cnt != a3)) { c->err = std::string("pop_operator: unknown field ") + (name ? name : "(null)"); return 1; }
+    if (!name || resolve(c, name, t, 0, p, &cnt) || (cnt != a2 && cnt != a3)) return unknown(c, "pop_operator: unknown field ", name ? name : "(null)");
     *stride = cnt == a3 ? c->g.n3 : c->g.n2;
     if (cnt == a3) *p += (long long)(k - 1) * c->g.n2;
     return 0;
@@ -1837,16 +1854,6 @@ int pop_baroclinic_correct_adjust(pop_ctx *c) {
   return 0;
 }
 
-// b4b global sum of a device array (physical domain) times an optional mask; result on the host
-static int global_sum_dev(pop_ctx *c, const double *p, const double *mask, double *result) {
-  hipLaunchKernelGGL(k_dot_partial, grid_2d(c), dim3(POP_RED_THREADS), 0, c->stream, c->g, p, (const double *)nullptr, mask, c->partial);
-  if (reduce_finish<1>(c, FIN_PLAIN)) return 1;
-  SolverScalars s;
-  if (read_scalars(c, &s)) return 1;
-  *result = s.sum0;
-  return 0;
-}
-
 // step_RF (step_mod.F90:919-1350): Robert-Asselin-Williams filter of curtime (and newtime) with the
 // volume-conserving adjustment of PSURF and the tracers, then the leapfrog index rotation
 static int step_rf(pop_ctx *c) {
@@ -1869,17 +1876,18 @@ static int step_rf(pop_ctx *c) {
   const dim3 GC = grid_cols(c);
   hipLaunchKernelGGL(k_rf_tracer_interior, dim3(GC.x, GC.y, nt), dim3(POP_COL_THREADS), 0, c->stream, c->g, p, ta);
   double svol[MAXNT] = {};
-  for (int n = 0; n < nt; ++n) if (global_sum_dev(c, WORKN[n], nullptr, &svol[n])) return 1;
+  auto sum = [&](const double *F, const double *mask, double *result) { return masked_sum(c, F, nullptr, mask, false, result); };
+  for (int n = 0; n < nt; ++n) if (sum(WORKN[n], nullptr, &svol[n])) return 1;
   hipLaunchKernelGGL(k_rf_surface, dim3((unsigned)((a2 + 255) / 256), nt), dim3(256), 0, c->stream, c->g, p, sa);
-  for (int n = 0; n < nt; ++n) { double s1; if (global_sum_dev(c, WORKN[n], nullptr, &s1)) return 1; svol[n] = svol[n] + s1; }
+  for (int n = 0; n < nt; ++n) { double s1; if (sum(WORKN[n], nullptr, &s1)) return 1; svol[n] = svol[n] + s1; }
   hipLaunchKernelGGL(k_rf_psurf, dim3((unsigned)((a2 + 255) / 256)), dim3(256), 0, c->stream, c->g, p, (const double *)c->PS[o], c->PS[cu], c->PS[nw], WB);
   double rf_sump;
-  if (global_sum_dev(c, WB, c->g.CONSTNT, &rf_sump)) return 1;      // MASK_TRBUDGET(:,:,1) = (KMT >= 1) = CONSTNT
+  if (sum(WB, c->g.CONSTNT, &rf_sump)) return 1;      // MASK_TRBUDGET(:,:,1) = (KMT >= 1) = CONSTNT
   rf_sump = rf_sump / h.bgtarea_t_1;
   hipLaunchKernelGGL(k_rf_psurf_adjust, dim3((unsigned)((a2 + 255) / 256)), dim3(256), 0, c->stream, c->g, p, rf_sump, c->PS[cu], c->PS[nw],
                      c->TR[0][cu], c->TR[0][nw], c->TR[1][cu], c->TR[1][nw], WB);
   double vsurf, vsurf_oo;
-  if (global_sum_dev(c, WB, c->g.CONSTNT, &vsurf) || global_sum_dev(c, WB, c->g.RCALCT, &vsurf_oo)) return 1;
+  if (sum(WB, c->g.CONSTNT, &vsurf) || sum(WB, c->g.RCALCT, &vsurf_oo)) return 1;
   const double rf_ocean_norm = h.open_ocean_volume_2_km + vsurf_oo;   // fully coupled normalisation (:1166-1172)
   (void)vsurf;
   for (int n = 0; n < nt; ++n) {
@@ -1957,16 +1965,16 @@ int pop_halo_update(pop_ctx *c, const char *name, int tl, int n) {
     for (int m = 0; m < c->h.nt; ++m) if (pop_halo_update(c, name, tl, m)) return 1;
     return 0;
   }
-  if (resolve(c, name, tl, n, &p, &cnt)) { c->err = std::string("unknown field ") + name; return 1; }
+  if (field_arg(c, name, tl, n, &p, &cnt)) return 1;
   const int nz = (int)(cnt / ((long long)c->g.n2 * c->g.nblocks));
   return halo_update(c, p, nz);
 }
 int pop_halo_update_loc(pop_ctx *c, const char *name, int tl, int n, int field_loc, int field_kind) {
   if (need_device(c)) return 1;
   if (join_side(c)) return 1;
-  if (field_loc < 0 || field_loc > 3 || field_kind < 0 || field_kind > 2) { c->err = "pop_halo_update_loc: unknown field location / kind"; return 1; }
+  if (loc_kind_ok(c, field_loc, field_kind, "pop_halo_update_loc: unknown field location / kind")) return 1;
   double *p; long long cnt;
-  if (resolve(c, name, tl, n < 0 ? 0 : n, &p, &cnt)) { c->err = std::string("unknown field ") + name; return 1; }
+  if (field_arg(c, name, tl, n < 0 ? 0 : n, &p, &cnt)) return 1;
   const int nz = (int)(cnt / ((long long)c->g.n2 * c->g.nblocks));
   return halo_update(c, p, nz, 0.0, field_loc, field_kind);
 }
@@ -1984,7 +1992,7 @@ static int halo_host_staged(pop_ctx *c, double *array, int nz, double fill, int 
   return 0;
 }
 int pop_halo_update_host_r8_loc(pop_ctx *c, double *array, int nz, double fill, int field_loc, int field_kind) {
-  if (field_loc < 0 || field_loc > 3 || field_kind < 0 || field_kind > 2) { c->err = "unknown field location / kind"; return 1; }
+  if (loc_kind_ok(c, field_loc, field_kind, "unknown field location / kind")) return 1;
   if (c->h.nranks != 1) return halo_host_staged(c, array, nz, fill, field_loc, field_kind);
   host_halo_r8_loc(c->h, array, nz, fill, field_loc, field_kind);
   return 0;
@@ -1999,47 +2007,22 @@ int pop_global_sum_host(pop_ctx *c, const double *array, const double *mask, int
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(c->W3, array, a2 * sizeof(double), hipMemcpyHostToDevice));
   if (mask) HIPCHK(c, hipMemcpy(c->W4, mask, a2 * sizeof(double), hipMemcpyHostToDevice));
-  const double *mk = mask ? c->W4 : nullptr;
-  if (c->h.c.ns_boundary == 2 && (field_loc == 1 || field_loc == 2)) {
-    hipLaunchKernelGGL(k_dot_partial_dup, grid_2d(c), dim3(POP_RED_THREADS), 0, c->stream, c->g, (const double *)c->W3, mk, (const double *)c->d2["TRIPOLE_DUP"], c->partial);
-    if (reduce_finish<2>(c, FIN_TRIPOLE)) return 1;
-  } else {
-    hipLaunchKernelGGL(k_dot_partial, grid_2d(c), dim3(POP_RED_THREADS), 0, c->stream, c->g, (const double *)c->W3, (const double *)nullptr, mk, c->partial);
-    if (reduce_finish<1>(c, FIN_PLAIN)) return 1;
-  }
-  SolverScalars sres;
-  if (read_scalars(c, &sres)) return 1;
-  *result = sres.sum0;
-  return 0;
+  return masked_sum(c, c->W3, nullptr, mask ? c->W4 : nullptr, top_row_once(c, field_loc), result);
 }
 int pop_halo_update_host_i4_loc(pop_ctx *c, int *array, int nz, int fill, int field_loc, int field_kind) {
-  if (c->h.nranks != 1) { c->err = "host halo update needs all blocks on one rank"; return 1; }
-  if (field_loc < 0 || field_loc > 3 || field_kind < 0 || field_kind > 2) { c->err = "unknown field location / kind"; return 1; }
+  if (single_rank_only(c) || loc_kind_ok(c, field_loc, field_kind, "unknown field location / kind")) return 1;
   host_halo_i4_loc(c->h, array, nz, fill, field_loc, field_kind);
   return 0;
 }
 // host-array halo: valid for single-rank decompositions (all blocks local), used at init time
 int pop_halo_update_host_r8(pop_ctx *c, double *array, int nz, double fill) {
-  if (c->h.nranks != 1) { c->err = "host halo update needs all blocks on one rank"; return 1; }
+  if (single_rank_only(c)) return 1;
   host_halo_r8(c->h, array, nz, fill);
   return 0;
 }
 int pop_halo_update_host_i4(pop_ctx *c, int *array, int nz, int fill) {
-  if (c->h.nranks != 1) { c->err = "host halo update needs all blocks on one rank"; return 1; }
+  if (single_rank_only(c)) return 1;
   host_halo_i4(c->h, array, nz, fill);
-  return 0;
-}
-int pop_global_sum(pop_ctx *c, const char *name, int tl, int n, const char *mask_name, double *result) {
-  if (need_device(c)) return 1;
-  if (join_side(c)) return 1;
-  double *p, *mk = nullptr; long long cnt;
-  if (resolve(c, name, tl, n, &p, &cnt)) { c->err = std::string("unknown field ") + name; return 1; }
-  if (mask_name && resolve(c, mask_name, 0, 0, &mk, &cnt)) { c->err = std::string("unknown mask ") + mask_name; return 1; }
-  hipLaunchKernelGGL(k_dot_partial, grid_2d(c), dim3(POP_RED_THREADS), 0, c->stream, c->g, p, (const double *)nullptr, mk, c->partial);
-  if (reduce_finish<1>(c, FIN_PLAIN)) return 1;
-  SolverScalars s;
-  if (read_scalars(c, &s)) return 1;
-  *result = s.sum0;
   return 0;
 }
 // POP_GlobalSum with fieldLoc on a tripole grid (mpi/POP_ReductionsMod.F90:308-341): N-face / NE-corner fields count
@@ -2047,27 +2030,22 @@ int pop_global_sum(pop_ctx *c, const char *name, int tl, int n, const char *mask
 int pop_global_sum_loc(pop_ctx *c, const char *name, int tl, int n, const char *mask_name, int field_loc, double *result) {
   if (need_device(c)) return 1;
   if (join_side(c)) return 1;
-  if (c->h.c.ns_boundary != 2 || (field_loc != 1 && field_loc != 2)) return pop_global_sum(c, name, tl, n, mask_name, result);
-  double *p, *mk = nullptr; long long cnt;
-  if (resolve(c, name, tl, n, &p, &cnt)) { c->err = std::string("unknown field ") + name; return 1; }
-  if (mask_name && resolve(c, mask_name, 0, 0, &mk, &cnt)) { c->err = std::string("unknown mask ") + mask_name; return 1; }
-  hipLaunchKernelGGL(k_dot_partial_dup, grid_2d(c), dim3(POP_RED_THREADS), 0, c->stream, c->g, (const double *)p, (const double *)mk,
-                     (const double *)c->d2["TRIPOLE_DUP"], c->partial);
-  if (reduce_finish<2>(c, FIN_TRIPOLE)) return 1;
-  SolverScalars s;
-  if (read_scalars(c, &s)) return 1;
-  *result = s.sum0;
-  return 0;
+  double *p, *mk; long long cnt;
+  if (field_arg(c, name, tl, n, &p, &cnt) || mask_arg(c, mask_name, &mk)) return 1;
+  return masked_sum(c, p, nullptr, mk, top_row_once(c, field_loc), result);
+}
+int pop_global_sum(pop_ctx *c, const char *name, int tl, int n, const char *mask_name, double *result) {
+  return pop_global_sum_loc(c, name, tl, n, mask_name, 0, result);
 }
 // every rank's `nv` values side by side (slot vector + sum all-reduce; exact because the other slots are zero)
-static int gather_slots(pop_ctx *c, const double *local, int nv, std::vector<double> &all) {
+static int gather_slots(pop_ctx *c, const double *local, int nv, std::vector<double> &all, const char *who = "global reduction") {
   const int nr = c->h.nranks;
   all.assign((size_t)nv * nr, 0.0);
   if (nr == 1) { std::copy(local, local + nv, all.begin()); return 0; }
-  if (!c->allred || !c->redbuf || c->red_doubles < (long long)nv * nr) { c->err = "global reduction: multi-rank run without a transport"; return 1; }
+  if (!c->allred || !c->redbuf || c->red_doubles < (long long)nv * nr) { c->err = std::string(who) + ": multi-rank run without a transport"; return 1; }
   std::copy(local, local + nv, all.begin() + (size_t)nv * c->h.rank);
   HIPCHK(c, hipMemcpyAsync(c->redbuf, all.data(), sizeof(double) * all.size(), hipMemcpyHostToDevice, c->stream));
-  if (c->allred(c->comm_user, 0, (long long)all.size())) { c->err = "global reduction: allreduce failed" + tr_err(c); return 1; }
+  if (c->allred(c->comm_user, 0, (long long)all.size())) { c->err = std::string(who) + ": allreduce failed" + tr_err(c); return 1; }
   HIPCHK(c, hipMemcpyAsync(all.data(), c->redbuf, sizeof(double) * all.size(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
@@ -2077,9 +2055,8 @@ static int gather_slots(pop_ctx *c, const double *local, int nv, std::vector<dou
 int pop_global_extreme(pop_ctx *c, const char *name, int tl, int n, const char *mask_name, int want_max, double *value, int *iloc, int *jloc) {
   if (need_device(c)) return 1;
   if (join_side(c)) return 1;
-  double *p, *mk = nullptr; long long cnt;
-  if (resolve(c, name, tl, n, &p, &cnt)) { c->err = std::string("unknown field ") + name; return 1; }
-  if (mask_name && resolve(c, mask_name, 0, 0, &mk, &cnt)) { c->err = std::string("unknown mask ") + mask_name; return 1; }
+  double *p, *mk; long long cnt;
+  if (field_arg(c, name, tl, n, &p, &cnt) || mask_arg(c, mask_name, &mk)) return 1;
   const dim3 G = grid_2d(c);
   with_flags([&](auto MAX) {
     hipLaunchKernelGGL(k_extreme_partial<MAX.value>, G, dim3(POP_RED_THREADS), 0, c->stream, c->g, (const double *)p, (const double *)mk, c->partial);
@@ -2121,13 +2098,12 @@ int pop_global_count(pop_ctx *c, const char *name, int tl, int n, int field_loc,
   if (need_device(c)) return 1;
   if (join_side(c)) return 1;
   double *p; long long cnt;
-  if (resolve(c, name, tl, n, &p, &cnt)) { c->err = std::string("unknown field ") + name; return 1; }
-  const double *dup = (c->h.c.ns_boundary == 2 && (field_loc == 1 || field_loc == 2)) ? c->d2["TRIPOLE_DUP"] : nullptr;
+  if (field_arg(c, name, tl, n, &p, &cnt)) return 1;
+  const double *dup = top_row_once(c, field_loc) ? c->d2["TRIPOLE_DUP"] : nullptr;
   hipLaunchKernelGGL(k_count_partial, grid_2d(c), dim3(POP_RED_THREADS), 0, c->stream, c->g, (const double *)p, dup, c->partial);
-  if (reduce_finish<1>(c, FIN_PLAIN)) return 1;
-  SolverScalars s;
-  if (read_scalars(c, &s)) return 1;
-  *count = (long long)s.sum0;
+  double ones;
+  if (finish_sum<1>(c, FIN_PLAIN, &ones)) return 1;
+  *count = (long long)ones;
   return 0;
 }
 // POP_GlobalSumProd2DR8 (mpi/POP_ReductionsMod.F90:1395-1618): sum of A*B[*mask] over the physical domain
@@ -2135,16 +2111,9 @@ int pop_global_sum_prod(pop_ctx *c, const char *name_a, int tl_a, int n_a, const
                         const char *mask_name, double *result) {
   if (need_device(c)) return 1;
   if (join_side(c)) return 1;
-  double *pa, *pb, *mk = nullptr; long long cnt;
-  if (resolve(c, name_a, tl_a, n_a, &pa, &cnt)) { c->err = std::string("unknown field ") + name_a; return 1; }
-  if (resolve(c, name_b, tl_b, n_b, &pb, &cnt)) { c->err = std::string("unknown field ") + name_b; return 1; }
-  if (mask_name && resolve(c, mask_name, 0, 0, &mk, &cnt)) { c->err = std::string("unknown mask ") + mask_name; return 1; }
-  hipLaunchKernelGGL(k_dot_partial, grid_2d(c), dim3(POP_RED_THREADS), 0, c->stream, c->g, pa, (const double *)pb, mk, c->partial);
-  if (reduce_finish<1>(c, FIN_PLAIN)) return 1;
-  SolverScalars s;
-  if (read_scalars(c, &s)) return 1;
-  *result = s.sum0;
-  return 0;
+  double *pa, *pb, *mk; long long cnt;
+  if (field_arg(c, name_a, tl_a, n_a, &pa, &cnt) || field_arg(c, name_b, tl_b, n_b, &pb, &cnt) || mask_arg(c, mask_name, &mk)) return 1;
+  return masked_sum(c, pa, pb, mk, false, result);
 }
 // POP_GlobalSumNfields2DR8 (mpi/POP_ReductionsMod.F90:823-1084): several fields, one result each
 int pop_global_sum_nfields(pop_ctx *c, int nf, const char *const *names, const int *tl, const int *n, const char *mask_name, double *results) {
@@ -2158,13 +2127,8 @@ int pop_global_sum_scalar(pop_ctx *c, double local, double *result) {
   const int nr = c->h.nranks;
   if (nr == 1) { *result = local; return 0; }
   if (need_device(c)) return 1;
-  if (!c->allred || !c->redbuf || c->red_doubles < nr) { c->err = "pop_global_sum_scalar: multi-rank run without a transport"; return 1; }
-  std::vector<double> v(nr, 0.0);
-  v[c->h.rank] = local;
-  HIPCHK(c, hipMemcpyAsync(c->redbuf, v.data(), sizeof(double) * nr, hipMemcpyHostToDevice, c->stream));
-  if (c->allred(c->comm_user, 0, nr)) { c->err = "pop_global_sum_scalar: allreduce failed" + tr_err(c); return 1; }
-  HIPCHK(c, hipMemcpyAsync(v.data(), c->redbuf, sizeof(double) * nr, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<double> v;
+  if (gather_slots(c, &local, 1, v, "pop_global_sum_scalar")) return 1;
   double t = 0.0;
   for (int r = 0; r < nr; ++r) t = t + v[r];
   *result = t;

@@ -927,6 +927,69 @@ def test_global_sum_family_and_solver_diagonal(pkg, orclib_built):
     gpu.close(); orc.close()
 
 
+def test_sum_paths_agree_bitwise(pkg):
+    """Every entry point that sums one masked 2-D field runs the same partial kernel and the same ordered finish, so the
+    doubles are equal, not merely close: device-resident, host-staged, product with the mask as second factor, fieldLoc form
+    and NFields form.  On a tripole grid the device-resident and the host-staged form agree on the top-row rule too."""
+    rng = np.random.default_rng(57)
+    for kw, locs in (({}, ()), ({"ns_boundary": 2}, ("Nface", "NEcorner"))):
+        m = pkg.PopModel(named_config("tiny", **kw))
+        shape = (m.nblocks, m.nyb, m.nxb)
+        m.set("DH", rng.standard_normal(shape) * 30.0)
+        m.set("RHS", (rng.random(shape) < 0.6).astype(np.float64))        # the 0/1 mask, as a named field
+        F, M = m.get("DH"), m.get("RHS")
+        ref = m.global_sum("DH", mask="RHS")
+        assert ref != m.global_sum("DH")                                   # the mask takes part
+        assert m.global_sum_host(F, M) == ref
+        assert m.global_sum_prod("DH", "RHS") == ref
+        assert m.global_sum_loc("DH", mask="RHS", loc="center") == ref
+        assert m.global_sum_nfields(["DH"], mask="RHS")[0] == ref
+        for loc in locs:
+            top_once = m.global_sum_loc("DH", mask="RHS", loc=loc)
+            assert top_once == m.global_sum_host(F, M, loc=loc)
+            assert top_once != ref                                         # the redundant half of the top row really is left out
+            with pytest.raises(pkg.PopError, match="unknown field"):
+                m.global_sum_loc("NOPE", mask="RHS", loc=loc)
+            with pytest.raises(pkg.PopError, match="unknown mask"):
+                m.global_sum_loc("DH", mask="NOPE", loc=loc)
+            assert m.global_sum_loc("DH", mask="RHS", loc=loc) == top_once
+        assert m.global_sum_scalar(-7.125) == -7.125                       # one rank: the value itself
+        m.close()
+
+
+def test_write_through_device_pointer_is_bitwise_a_set_field(pkg, monkeypatch):
+    """A caller that writes a prognostic field in place through pop_field_device_ptr gets what pop_set_field gives: the ghost
+    cells are updated again and, with land elimination active, the next steps run every workgroup (the new state carries
+    other values on land)."""
+    import ctypes as C
+    monkeypatch.setenv("POP_LAND_SKIP", "1")
+    monkeypatch.setenv("POP_LAND_FULL_STEPS", "4")
+    cfg = named_config("tiny")
+    a, b = pkg.PopModel(cfg), pkg.PopModel(cfg)
+    for _ in range(6):
+        a.step(); b.step()
+    assert a.dim("land_skip_active") == 1 and b.dim("land_skip_active") == 1
+    T = a.get("TRACER", 1, 0)
+    land = np.arange(a.km)[None, :, None, None] >= a.geti("KMT")[:, None]
+    assert land.any()
+    T[land] = 3.5                                                          # other values on land (and below the bottom)
+    a.set("TRACER", T, tl=1, n=0)
+    ptr = b.L.pop_field_device_ptr(b.h, b"TRACER", 1, 0)
+    assert ptr
+    b.sync()
+
+    hip_memcpy = b.L.hipMemcpy                                               # the HIP runtime the library is linked against
+    hip_memcpy.restype, hip_memcpy.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    assert hip_memcpy(ptr, T.ctypes.data, T.nbytes, 1) == 0                  # 1 = hipMemcpyHostToDevice
+    for _ in range(2):
+        a.step(); b.step()
+        assert a.dim("land_skip_active") == 0 and b.dim("land_skip_active") == 0
+    for name, n in (("TRACER", 0), ("TRACER", 1), ("UVEL", 0), ("PSURF", 0)):
+        for tl in (0, 1, 2):
+            assert np.array_equal(a.get(name, tl, n), b.get(name, tl, n)), (name, n, tl)
+    a.close(); b.close()
+
+
 @pytest.mark.parametrize("wave", ["3", "2", "1", "0"], ids=["wavefront-registers-loads-up-front", "wavefront-registers", "wavefront-lds", "thread-per-sub-block"])
 @pytest.mark.parametrize("name,kw", [("tiny", {}), ("tiny", {"block_size_x": 16, "block_size_y": 20}), ("gx3v7", {}),
                                      ("tiny", {"nx_global": 66, "ny_global": 52, "block_size_x": 33, "block_size_y": 26, "stepped_bathymetry": 1})])
@@ -1068,7 +1131,7 @@ def test_operators_are_bitwise_the_oracle(pkg, orclib_built):
 
 def test_entry_points_fail_loudly(pkg, tmp_path):
     """Error convention of the C ABI (non-zero return + message, no partial work): bad operator arguments, unknown
-    fields, a missing or truncated restart file."""
+    fields and masks, wrong counts, wrong field locations, a missing or truncated restart file."""
     m = pkg.PopModel(named_config("tiny"))
     with pytest.raises(pkg.PopError, match="op 0 grad"):
         m.operator("grad", 0, "PSURF")
@@ -1078,6 +1141,37 @@ def test_entry_points_fail_loudly(pkg, tmp_path):
         m.solver_preconditioner("UVEL", "DH")                    # 3-D field where a 2-D one is required
     with pytest.raises(pkg.PopError, match="cannot open"):
         m.read_restart(str(tmp_path / "missing.bin"))
+    # named-field arguments: (message, the failing call, a good call of the same entry point that must still succeed)
+    import ctypes as C
+    P = C.POINTER(C.c_double)
+    buf = np.zeros((m.nblocks, m.nyb, m.nxb))
+    raw = lambda f, *a: m._chk(f(m.h, *a))
+    named = [
+        ("unknown field", lambda: m.global_sum("NOPE"), lambda: m.global_sum("DH")),
+        ("unknown mask", lambda: m.global_sum("DH", mask="NOPE"), lambda: m.global_sum("DH", mask="mMask")),
+        ("unknown field", lambda: m.global_sum_loc("NOPE", loc="Nface"), lambda: m.global_sum_loc("DH", loc="Nface")),
+        ("unknown mask", lambda: m.global_sum_loc("DH", mask="NOPE", loc="Nface"), lambda: m.global_sum_loc("DH", mask="mMask", loc="Nface")),
+        ("unknown field NOPE", lambda: m.global_sum_prod("NOPE", "DH"), lambda: m.global_sum_prod("DH", "DHU")),
+        ("unknown field NOPE2", lambda: m.global_sum_prod("DH", "NOPE2"), lambda: m.global_sum_prod("DH", "DHU")),
+        ("unknown mask", lambda: m.global_sum_prod("DH", "DHU", mask="NOPE"), lambda: m.global_sum_prod("DH", "DHU", mask="mMask")),
+        ("unknown field", lambda: m.global_extreme("NOPE"), lambda: m.global_extreme("DH")),
+        ("unknown mask", lambda: m.global_extreme("DH", mask="NOPE"), lambda: m.global_extreme("DH", mask="mMask")),
+        ("unknown field", lambda: m.global_count("NOPE"), lambda: m.global_count("DH")),
+        ("unknown field", lambda: m.halo_update("NOPE"), lambda: m.halo_update("DH")),
+        ("unknown field", lambda: m.halo_update_loc("NOPE", loc="Nface"), lambda: m.halo_update_loc("DH", loc="Nface")),
+        ("unknown field", lambda: m.get("NOPE"), lambda: m.get("DH")),
+        ("unknown field", lambda: m.set("NOPE", buf), lambda: m.set("DH", m.get("DH"))),
+        ("count mismatch for PSURF", lambda: raw(m.L.pop_get_field, b"PSURF", 1, 0, buf.ctypes.data_as(P), buf.size - 1), lambda: m.get("PSURF")),
+        ("count mismatch for PSURF", lambda: raw(m.L.pop_set_field, b"PSURF", 1, 0, buf.ctypes.data_as(P), buf.size - 1), lambda: m.set("PSURF", m.get("PSURF"))),
+        ("has no tracer dimension", lambda: m.halo_update("PSURF", n=-1), lambda: m.halo_update("TRACER", n=-1)),
+        ("unknown field location / kind", lambda: raw(m.L.pop_halo_update_loc, b"DH", 1, 0, 7, 0), lambda: m.halo_update_loc("DH")),
+        ("unknown field location / kind", lambda: raw(m.L.pop_halo_update_host_r8_loc, buf.ctypes.data_as(P), 1, 0.0, 7, 0),
+         lambda: m.halo_update_host_loc(buf)),
+    ]
+    for msg, bad, good in named:
+        with pytest.raises(pkg.PopError, match=msg):
+            bad()
+        good()
     m.step()
     path = str(tmp_path / "r.bin")
     m.write_restart(path)
