@@ -63,19 +63,46 @@ static void init_forcing(orc_model *m) {
   }
 }
 
+/* what the device refuses, and what this restatement leaves out (DESIGN.md section 5): NULL = accepted */
+static const char *orc_refuse(const orc_config *cfg) {
+  if (cfg->hmix_momentum == 3) {
+    if (cfg->struct_version < 6) return "hmix_momentum = 3 (anis) needs struct_version 6: the hmix_aniso_nml members";
+    if (cfg->aniso_alignment == 2) return "aniso_alignment 'flow' is refused (as on the device)";
+    if (cfg->aniso_alignment < 0 || cfg->aniso_alignment > 2) return "aniso_alignment: 0 'grid' or 1 'east'";
+    if (cfg->lsmag_aniso) return "lsmag_aniso: the Smagorinsky viscosities are not restated in the oracle (DESIGN.md section 5)";
+  }
+  if (cfg->lsubmesoscale_mixing) {
+    if (cfg->hmix_tracer != 3) return "lsubmesoscale_mixing needs hmix_tracer = 3 (gm): del2 / del4 are refused as on the device";
+    if (cfg->partial_bottom_cells) return "lsubmesoscale_mixing with partial_bottom_cells is refused (as on the device)";
+  }
+  /* init_gm aborts: 'hmix_gm currently incompatible with partial bottom cells' (hmix_gm.F90:782-785); 'depth' profile with
+   * kappa_depth_2 = 0 (:724-730); 'bfre' with kappa_freq 'never' and no N^2 file (:756-780) */
+  if (cfg->hmix_tracer == 3 && cfg->partial_bottom_cells) return "hmix_tracer = 3 (gm) with partial_bottom_cells is refused (hmix_gm.F90:782-785)";
+  if (cfg->hmix_tracer == 3 && cfg->gm_kappa_type == 2 && cfg->kappa_depth_2 == 0.0) return "gm 'depth' kappa profile with kappa_depth_2 = 0 (hmix_gm.F90:724-730)";
+  if (cfg->hmix_tracer == 3 && cfg->gm_kappa_type == 1 && cfg->gm_kappa_freq == 0) return "gm 'bfre' kappa with kappa_freq 'never' (hmix_gm.F90:756-780)";
+  if (cfg->nt < 2 || cfg->nt > 8) return "nt: 2 to 8 tracers";
+  return NULL;
+}
 orc_model *orc_create(const orc_config *cfg) { return orc_create_with_grid(cfg, NULL); }
 orc_model *orc_create_with_grid(const orc_config *cfg, const orc_grid_input *grid) {
-  if (cfg->struct_version != ORC_CONFIG_VERSION) return NULL;   /* layout of orc_config = include/pop_amd.h pop_config of the same version */
-  /* init_gm aborts: 'hmix_gm currently incompatible with partial bottom cells' (hmix_gm.F90:782-785); 'depth' profile with kappa_depth_2 = 0 (:724-730) */
-  if (cfg->hmix_tracer == 3 && cfg->partial_bottom_cells) return NULL;
-  if (cfg->hmix_tracer == 3 && cfg->gm_kappa_type == 2 && cfg->kappa_depth_2 == 0.0) return NULL;
-  if (cfg->hmix_tracer == 3 && cfg->gm_kappa_type == 1 && cfg->gm_kappa_freq == 0) return NULL;   /* hmix_gm.F90:756-780: 'bfre' with kappa_freq 'never' and no N^2 file aborts */
+  /* layout of orc_config = include/pop_amd.h pop_config of the same version; 5 and 6 are read up to their own size, the rest stays 0 */
+  orc_config cfg_full;
+  memset(&cfg_full, 0, sizeof cfg_full);
+  if (cfg->struct_version == 7) cfg_full = *cfg;
+  else if (cfg->struct_version == 6) memcpy(&cfg_full, cfg, offsetof(orc_config, lsubmesoscale_mixing));
+  else if (cfg->struct_version == 5) memcpy(&cfg_full, cfg, offsetof(orc_config, aniso_alignment));
+  else { ORC_FAIL("orc_config.struct_version is %d, this library reads 5, 6 and 7", cfg->struct_version); return NULL; }
+  cfg = &cfg_full;
+  {
+    const char *why = orc_refuse(cfg);
+    if (why) { ORC_FAIL("%s", why); return NULL; }
+  }
   orc_model *m = (orc_model *)calloc(1, sizeof(orc_model));
   m->c = *cfg;
   if (cfg->hmix_tracer == 3 && cfg->gm_transition_layer == 1 && cfg->vmix_choice == 3) m->c.kpp_ml_diagnostics = 1;   /* the diabatic depth is the smoothed HMXL */
+  if (cfg->lsubmesoscale_mixing && cfg->vmix_choice == 3) m->c.kpp_ml_diagnostics = 1;   /* the mixed-layer depth is HMXL (mix_submeso.F90:425-426) */
   m->gin = grid;
   m->km = cfg->km; m->nt = cfg->nt;
-  if (cfg->nt < 2 || cfg->nt > 8) { free(m); return NULL; }
   /* block sizes that do not divide the domain: the last row / column of blocks is padded (blocks.F90:174-265) */
   create_blocks(m);
   int km = m->km;
@@ -85,7 +112,7 @@ orc_model *orc_create_with_grid(const orc_config *cfg, const orc_grid_input *gri
   V1(afac_t); V1(afac_u); V1(hfac);
 #undef V1
 #define A2(x) m->x = dalloc(a2)
-  A2(ULAT); A2(ULON); A2(TLAT); A2(HTN); A2(HTE); A2(HUS); A2(HUW); A2(DXU); A2(DYU); A2(DXT); A2(DYT);
+  A2(ULAT); A2(ULON); A2(TLAT); A2(TLON); A2(ANGLE); A2(HTN); A2(HTE); A2(HUS); A2(HUW); A2(DXU); A2(DYU); A2(DXT); A2(DYT);
   A2(DXUR); A2(DYUR); A2(DXTR); A2(DYTR); A2(UAREA); A2(TAREA); A2(UAREA_R); A2(TAREA_R);
   A2(AU0); A2(AUN); A2(AUE); A2(AUNE); A2(FCOR); A2(FCORT); A2(HU); A2(HUR); A2(HT); A2(RCALCT); A2(RCALCU);
   A2(AMF); A2(AHF); A2(DTN); A2(DTS); A2(DTE); A2(DTW);
@@ -120,9 +147,11 @@ orc_model *orc_create_with_grid(const orc_config *cfg, const orc_grid_input *gri
   init_time(m);
   init_del2(m);
   if (cfg->hmix_momentum == 4 || cfg->hmix_tracer == 4) init_del4(m);
+  if (cfg->hmix_momentum == 3) init_aniso(m);
   if (cfg->tadvect == 2) init_upwind3(m);
   if (cfg->tadvect == 3) init_lw_lim(m);
   if (cfg->hmix_tracer == 3) init_gm(m);
+  if (cfg->lsubmesoscale_mixing) init_submeso(m);
   if (cfg->tmix_opt == 3) init_rf(m);
   init_solver(m);
   if (cfg->preconditioner_choice == 1) { init_center_weight(m); init_evp(m); }   /* POP_SolversPrep :252-290 */
@@ -145,7 +174,7 @@ void orc_destroy(orc_model *m) {
   if (!m) return;
   /* test infrastructure: process-lifetime allocations are released wholesale */
   double **dp[] = {&m->dz, &m->dzw, &m->zt, &m->zw, &m->c2dz, &m->dzr, &m->dz2r, &m->dzwr, &m->pressz, &m->bouss, &m->dt,
-    &m->c2dtt, &m->afac_t, &m->afac_u, &m->hfac, &m->ULAT, &m->ULON, &m->TLAT, &m->HTN, &m->HTE, &m->HUS, &m->HUW, &m->DXU,
+    &m->c2dtt, &m->afac_t, &m->afac_u, &m->hfac, &m->ULAT, &m->ULON, &m->TLAT, &m->TLON, &m->ANGLE, &m->HTN, &m->HTE, &m->HUS, &m->HUW, &m->DXU,
     &m->DYU, &m->DXT, &m->DYT, &m->DXUR, &m->DYUR, &m->DXTR, &m->DYTR, &m->UAREA, &m->TAREA, &m->UAREA_R, &m->TAREA_R,
     &m->AU0, &m->AUN, &m->AUE, &m->AUNE, &m->FCOR, &m->FCORT, &m->HU, &m->HUR, &m->HT, &m->RCALCT, &m->RCALCU, &m->AMF,
     &m->AHF, &m->DTN, &m->DTS, &m->DTE, &m->DTW, &m->DUC, &m->DUN, &m->DUS, &m->DUE, &m->DUW, &m->DMC, &m->DMN, &m->DMS,
@@ -165,6 +194,9 @@ void orc_destroy(orc_model *m) {
   for (int n = 0; n < 2; n++) { free(m->SMF[n]); free(m->SMFT[n]); }
   for (int n = 0; n < m->nt; n++) { free(m->STF[n]); free(m->TFW[n]); free(m->KPP_SRC[n]); }
   free_vmix_kpp(m);
+  free_tidal(m);
+  free_aniso(m);
+  free_submeso(m);
   if (m->sw) { orc_sw *SW = (orc_sw *)m->sw; free(SW->swabs); free(SW->ztr); free(SW->Tr); free(SW); m->sw = NULL; }
   free_lw_lim(m);
   free_gm(m);
@@ -175,7 +207,7 @@ static int tlidx(orc_model *m, int tl) { return tl == 0 ? m->oldtime : tl == 1 ?
 
 double *orc_field(orc_model *m, const char *name, int tl, int n) {
 #define F2(nm) if (!strcmp(name, #nm)) return m->nm;
-  F2(ULAT) F2(ULON) F2(TLAT) F2(HTN) F2(HTE) F2(HUS) F2(HUW) F2(DXU) F2(DYU) F2(DXT) F2(DYT) F2(DXUR) F2(DYUR)
+  F2(ULAT) F2(ULON) F2(TLAT) F2(TLON) F2(ANGLE) F2(HTN) F2(HTE) F2(HUS) F2(HUW) F2(DXU) F2(DYU) F2(DXT) F2(DYT) F2(DXUR) F2(DYUR)
   F2(UAREA) F2(TAREA) F2(UAREA_R) F2(TAREA_R) F2(AU0) F2(AUN) F2(AUE) F2(AUNE) F2(FCOR) F2(FCORT) F2(HU) F2(HUR) F2(HT)
   F2(RCALCT) F2(RCALCU) F2(AMF) F2(AHF) F2(DTN) F2(DTS) F2(DTE) F2(DTW) F2(DUC) F2(DUN) F2(DUS) F2(DUE) F2(DUW)
   F2(DMC) F2(DMN) F2(DMS) F2(DME) F2(DMW) F2(DUM) F2(KXU) F2(KYU) F2(D4_AMF) F2(D4_AHF)
@@ -211,6 +243,14 @@ double *orc_field(orc_model *m, const char *name, int tl, int n) {
 #undef FU
   }
   if (!strcmp(name, "VDC")) return (n == 0 || n == 1) ? m->VDC[n] : NULL; /* (nx,ny,0:km+1,blocks) */
+  if (m->submeso) { double *f = orc_submeso_field(m, name, n); if (f) return f; }
+  if (m->aniso) {
+    const orc_aniso *A = (const orc_aniso *)m->aniso;
+#define FA(nm) if (!strcmp(name, #nm)) return A->nm;
+    FA(HDU) FA(HDV) FA(F_PARA) FA(F_PERP) FA(AMAX_CFL) FA(H1E) FA(H1W) FA(H2N) FA(H2S) FA(K1E) FA(K1W) FA(K2N) FA(K2S)
+#undef FA
+  }
+  if (m->tidal || m->bck) { double *f = orc_tidal_field(m, name); if (f) return f; }
   return NULL;
 }
 int *orc_ifield(orc_model *m, const char *name) {

@@ -174,6 +174,7 @@ static void vmix_coeffs_rich(orc_model *m, int b, int k, double *UTK, double *VT
   }
 }
 
+#include "orc_tidal.inc"
 #include "orc_kpp.inc"
 
 /* ---- hmix_del2.F90:1030-1095 hdifft_del2 ------------------------------- */
@@ -246,6 +247,7 @@ static void hdiffu_del2(orc_model *m, int b, int k, double *HDUK, double *HDVK, 
 #include "orc_del4.inc"
 #define P2(i, j) ((size_t)((j)-1) * nxb + (i)-1)
 #define P3(i, j, k) ((size_t)((k)-1) * n2 + P2(i, j))
+#include "orc_aniso.inc"
 
 /* ---- advection.F90:2068-2127 comp_flux_vel (no lw_lim, no pbc) ---------- */
 static void comp_flux_vel(orc_model *m, int b, int k, const double *WTK, double *UTE, double *UTW,
@@ -306,6 +308,7 @@ static void advt_centered(orc_model *m, int b, int k, double *LTK, const double 
 #include "orc_upwind3.inc"
 #include "orc_lwlim.inc"
 #include "orc_gm.inc"
+#include "orc_submeso.inc"
 
 /* ---- vertical_mix.F90:770-840 vdifft ------------------------------------ */
 static void vdifft(orc_model *m, int b, int k, double *VDTK, double *VTF /* n2*nt carried */) {
@@ -545,6 +548,7 @@ int orc_baroclinic_stages(orc_model *m, int stages);
 int orc_baroclinic_driver(orc_model *m) { return orc_baroclinic_stages(m, 31); }
 int orc_baroclinic_stages(orc_model *m, int stages) {
   DECL_DIMS
+  m->ran = 1;
   const orc_config *c = &m->c;
   const int nt = m->nt;
   /* step_mod.F90:302-320 */
@@ -586,6 +590,12 @@ int orc_baroclinic_stages(orc_model *m, int stages) {
       if (c->hmix_tracer == 2) hdifft_del2(m, b, k, WORKN);
       else if (c->hmix_tracer == 3) hdifft_gm(m, b, k, WORKN);   /* also adds the isopycnal part to VDC(k) before vdifft reads it */
       else hdifft_del4(m, b, k, WORKN);
+      if (c->lsubmesoscale_mixing) {   /* horizontal_mix.F90:566-581: after GM, from the differences GM has just formed */
+        double *TDTK = ((orc_submeso *)m->submeso)->TDTK;
+        if (k == 1) submeso_sf(m, b);
+        submeso_flux(m, b, k, TDTK);
+        for (size_t p = 0; p < n2 * nt; p++) WORKN[p] = WORKN[p] + TDTK[p];
+      }
       for (size_t p = 0; p < n2 * nt; p++) FT[p] = FT[p] + WORKN[p];
       if (k == 1) memcpy(WTK, m->DH + o2, n2 * sizeof(double));
       for (size_t p = 0; p < n2 * nt; p++) LTK[p] = 0.0;
@@ -689,6 +699,7 @@ int orc_baroclinic_stages(orc_model *m, int stages) {
         }
       }
       if (c->hmix_momentum == 2) hdiffu_del2(m, b, k, WX, WY, UMIX + ok, VMIX + ok);
+      else if (c->hmix_momentum == 3) hdiffu_aniso(m, b, k, WX, WY, UMIX + ok, VMIX + ok);   /* horizontal_mix.F90:464-472 */
       else hdiffu_del4(m, b, k, WX, WY, UMIX + ok, VMIX + ok);
       for (size_t p = 0; p < n2; p++) { FX[p] = FX[p] + WX[p]; FY[p] = FY[p] + WY[p]; }
       vdiffu(m, b, k, WX, WY, VUF, VVF);

@@ -27,6 +27,7 @@ typedef struct {
   double *SLX, *SLY, *SF_SLX, *SF_SLY;          /* [2 faces][2 halves][0..km] levels of n2 */
   double *TX, *TY, *TZ;                         /* [nt][0..km] */
   double *RX, *RY;                              /* [2 faces][0..km] */
+  double *RZ_SAVE;                              /* [0..km]: min(RZ, 0) (hmix_gm_submeso_share.F90:398), read by the submesoscale scheme; levels 0, 1 stay 0 */
   double *KAPPA_ISOP, *KAPPA_THIC, *HOR_DIFF;   /* [2 halves][0..km] */
   double *FZTOP;                                /* [nt] */
   double *BL_DEPTH, *W;                         /* 2-D work */
@@ -81,7 +82,7 @@ static void init_gm(orc_model *m) {
   }
   G->SLX = dalloc(4 * lv); G->SLY = dalloc(4 * lv); G->SF_SLX = dalloc(4 * lv); G->SF_SLY = dalloc(4 * lv);
   G->TX = dalloc(nt * lv); G->TY = dalloc(nt * lv); G->TZ = dalloc(nt * lv);
-  G->RX = dalloc(2 * lv); G->RY = dalloc(2 * lv);
+  G->RX = dalloc(2 * lv); G->RY = dalloc(2 * lv); G->RZ_SAVE = dalloc(lv);
   G->KAPPA_ISOP = dalloc(2 * lv); G->KAPPA_THIC = dalloc(2 * lv); G->HOR_DIFF = dalloc(2 * lv);
   G->DIABATIC_DEPTH = dalloc(n2); G->THICKNESS = dalloc(n2); G->INTERIOR_DEPTH = dalloc(n2); G->SLA_SAVE = dalloc(2 * lv);
   G->K_LEVEL = (int *)calloc(n2, sizeof(int)); G->ZTW = (int *)calloc(n2, sizeof(int));
@@ -94,7 +95,7 @@ static void init_gm(orc_model *m) {
 static void free_gm(orc_model *m) {
   orc_gm *G = (orc_gm *)m->gm;
   if (!G) return;
-  double *p[] = {G->HYX, G->HXY, G->HYXW, G->HXYS, G->RBR, G->SLX, G->SLY, G->SF_SLX, G->SF_SLY, G->TX, G->TY, G->TZ, G->RX, G->RY,
+  double *p[] = {G->HYX, G->HXY, G->HYXW, G->HXYS, G->RBR, G->SLX, G->SLY, G->SF_SLX, G->SF_SLY, G->TX, G->TY, G->TZ, G->RX, G->RY, G->RZ_SAVE,
                  G->KAPPA_ISOP, G->KAPPA_THIC, G->HOR_DIFF, G->FZTOP, G->BL_DEPTH, G->W, G->KAPPA_VERTICAL};
   for (size_t i = 0; i < sizeof(p) / sizeof(p[0]); i++) free(p[i]);
   free(G->UIT); free(G->VIT); free(G->WTOP); free(G->WBOT); free(G->UISOP); free(G->VISOP); free(G->WISOP);
@@ -175,6 +176,7 @@ static void gm_tracer_diffs_and_isopyc_slopes(orc_model *m, int b) {
       LEVEL_RXRY(kk + 1, ks);
       for (size_t p = 0; p < n2; p++) {
         double rz = DRDT[p] * TZP[ks][p] + DRDS[p] * TZn(1, kk + 1)[p];            /* :383-385 */
+        G->RZ_SAVE[(size_t)(kk + 1) * n2 + p] = (rz < 0.0) ? rz : 0.0;            /* :398 */
         rz = (rz < -1.0e-20) ? rz : -1.0e-20;
         if (kk + 1 <= KMT[p]) {                                                    /* :395-400 */
           GM4(G->SLX, GM_E, GM_KTP, kk + 1)[p] = GM3(G->RX, GM_E, kk + 1)[p] / rz;

@@ -2,6 +2,8 @@
 #ifndef ORC_INTERNAL_H
 #define ORC_INTERNAL_H
 #include <math.h>
+#include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -17,7 +19,7 @@ struct orc_model {
   double *dz, *dzw, *zt, *zw, *c2dz, *dzr, *dz2r, *dzwr, *pressz, *bouss, *dt, *c2dtt;
   double *afac_t, *afac_u, *hfac;
   /* horizontal grid */
-  double *ULAT, *ULON, *TLAT, *HTN, *HTE, *HUS, *HUW, *DXU, *DYU, *DXT, *DYT;
+  double *ULAT, *ULON, *TLAT, *TLON, *ANGLE, *HTN, *HTE, *HUS, *HUW, *DXU, *DYU, *DXT, *DYT;
   double *DXUR, *DYUR, *DXTR, *DYTR, *UAREA, *TAREA, *UAREA_R, *TAREA_R;
   double *AU0, *AUN, *AUE, *AUNE, *FCOR, *FCORT, *HU, *HUR, *HT, *RCALCT, *RCALCU;
   int *KMT, *KMU, *KMTN, *KMTS, *KMTE, *KMTW, *KMTEE, *KMTNN;
@@ -60,7 +62,15 @@ struct orc_model {
   void *rf;
   void *pcsi;
   void *evp;
+  void *tidal;                /* orc_tidal.inc (orc_init_tidal_mixing) */
+  void *bck;                  /* orc_tidal.inc (orc_init_kpp_bckgrnd) */
+  void *aniso;                /* orc_aniso.inc (hmix_momentum = 3) */
+  void *submeso;              /* orc_submeso.inc (lsubmesoscale_mixing) */
+  int ran;                    /* a step or a phase has run: the init entry points are refused afterwards */
 };
+extern char orc_errbuf[256];
+int orc_fail(const char *fmt, ...);   /* fills orc_errbuf, returns 1 */
+#define ORC_FAIL(...) orc_fail(__VA_ARGS__)
 
 extern const double orc_grav, orc_omega, orc_radius;
 #endif

@@ -1,9 +1,8 @@
 /* orc_kpp.inc -- native KPP vertical mixing of the reference (the `.not. lcvmix` branches of
  * source/vmix_kpp.F90), restated for the CPU oracle.  TEST INFRASTRUCTURE ONLY.
  *
- * Selections (SURVEY.md 8c): lcvmix=.false., ltidal_mixing=.false., lniw_mixing=.false.,
- * linertial=.false., lhoriz_varying_bckgrnd=.false., partial_bottom_cells=.false.,
- * lshort_wave=.false., lcheckekmo=.false., langmuir off, SMFT available (forcing_ws.F90:307).
+ * Selections (SURVEY.md 8c): lcvmix=.false., lniw_mixing=.false., linertial=.false., langmuir off, SMFT available
+ * (forcing_ws.F90:307).  ltidal_mixing (Jayne) and lhoriz_varying_bckgrnd after their init calls: orc_tidal.inc.
  * The CVMix path (the CESM default) lives in an un-vendored third party (CVMix v0.98-beta,
  * Externals_POP.cfg:1-6): parity for it is unpinned; this is the path testmod pop/no_cvmix runs.
  * Diagnostic outputs HMXL, HMXL_DR: with kpp_ml_diagnostics = 1; tavg fields are not computed.
@@ -200,10 +199,10 @@ static void vmix_coeffs_kpp(orc_model *m, int b) {
   double *RHOKM = TK, *RHOK = TK, *RHOAVG = TK, *WORK1 = TK, *WORK2 = TK, *USTAR = TK, *BFSFC = TK, *STABLE = TK;
   double *RHO1 = TK, *TALPHA = TK, *SBETA = TK, *BO = TK, *BOSOL = TK, *ZKL = TK, *HBLT = TK, *UREF = TK, *VREF = TK;
   double *WORK = TK, *VSHEAR = TK, *SIGMA = TK, *WM = TK, *WS = TK, *B_FRQNCY = TK, *CASEA = TK, *F1 = TK, *DELHAT = TK;
-  double *RIB = TK; TK; TK;   /* RI_BULK(:,:,3) */
-  double *GAT1 = TK; TK; TK;
-  double *DAT1 = TK; TK; TK;
-  double *DKM1 = TK; TK; TK;
+  double *RIB = TK; (void)TK; (void)TK;   /* RI_BULK(:,:,3) */
+  double *GAT1 = TK; (void)TK; (void)TK;
+  double *DAT1 = TK; (void)TK; (void)TK;
+  double *DKM1 = TK; (void)TK; (void)TK;
   double *TA2 = TK, *SB2 = TK, *TA3 = TK, *SB3 = TK, *FCON = TK;
   int *KBL = m->KBL + o2, *KN = ialloc(n2);
 
@@ -276,19 +275,63 @@ static void vmix_coeffs_kpp(orc_model *m, int b) {
         L3(FRI, k)[p] = v < 1.0 ? v : 1.0;
       }
   }
-  for (int k = 1; k <= km; k++)
+  /* the background at level k of cell p: the vertical profile, or after orc_init_kpp_bckgrnd the 2-D field the reference copies to every level */
+  const orc_bck *BCK = (const orc_bck *)m->bck;
+  const double *BV2 = (BCK && BCK->VDC) ? BCK->VDC + o2 : NULL, *BM2 = (BCK && BCK->VVC) ? BCK->VVC + o2 : NULL;
+#define BVDC(k, p) (BV2 ? BV2[p] : K->bckgrnd_vdc[k])
+#define BVVC(k, p) (BM2 ? BM2[p] : K->bckgrnd_vvc[k])
+  const orc_tidal *TID = tidal_on(m);
+  double *TD = NULL, *TN2 = NULL, *KVMIX = NULL, *KVMIX_M = NULL;
+  if (TID) {   /* :1758-1759 */
+    TD = TID->DIFF + o3; TN2 = TID->N2 + o3; KVMIX = TID->KVMIX + o3; KVMIX_M = TID->KVMIX_M + o3;
+    for (size_t p = 0; p < n3; p++) { TD[p] = 0.0; TN2[p] = 0.0; KVMIX[p] = 0.0; KVMIX_M[p] = 0.0; }
+  }
+  for (int k = 1; k <= km; k++) {
+    if (TID) {   /* :1791-1857 */
+      for (size_t p = 0; p < n2; p++) {
+        if (PBC) WORK1[p] = L3(DBLOC, k)[p] / (0.5 * (DZL(DZT, p, k) + DZL(DZT, p, k + 1)));
+        else WORK1[p] = L3(DBLOC, k)[p] / (zgrid[k] - zgrid[k + 1]);
+      }
+      tidal_compute_diff(m, TID, b, k, WORK1, TD);
+      const double tidal_mix_max = TID->nml.tidal_mix_max;
+      for (size_t p = 0; p < n2; p++) {
+        const double WORKN = BVVC(k, p);
+        const double sm = WORKN / c->Prandtl + L3(TD, k)[p];
+        const double W1 = c->Prandtl * (sm < tidal_mix_max ? sm : tidal_mix_max);
+        if (k < km) {
+          const double sd = BVDC(k, p) + L3(TD, k)[p];
+          L0(VDC2, k)[p] = sd < tidal_mix_max ? sd : tidal_mix_max;
+          /* the diagnostics KVMIX, KVMIX_M, TIDAL_N2 (:1830, 1841, 1961) hold 0 at and below the bottom level here, as the device's do;
+           * the reference leaves the background sum there, which nothing reads */
+          if (k < KMT[p]) { L3(KVMIX_M, k)[p] = W1; L3(KVMIX, k)[p] = L0(VDC2, k)[p]; L3(TN2, k)[p] = WORK1[p]; }
+        }
+        if (c->lrich) {
+          double f = 1.0 - L3(FRI, k)[p] * L3(FRI, k)[p];
+          double f3 = (f * f) * f;
+          L0(VISC, k)[p] = W1 + c->kpp_rich_mix * f3;
+          if (k < km) { L0(VDC2, k)[p] = L0(VDC2, k)[p] + c->kpp_rich_mix * f3; L0(VDC1, k)[p] = L0(VDC2, k)[p]; }
+        } else {
+          L0(VISC, k)[p] = W1;
+          if (k < km) L0(VDC1, k)[p] = L0(VDC2, k)[p];
+        }
+      }
+    } else
     for (size_t p = 0; p < n2; p++) {
       if (c->lrich) {
         double f = 1.0 - L3(FRI, k)[p] * L3(FRI, k)[p];
         double f3 = (f * f) * f;
-        L0(VISC, k)[p] = K->bckgrnd_vvc[k] + c->kpp_rich_mix * f3;
-        if (k < km) { L0(VDC2, k)[p] = K->bckgrnd_vdc[k] + c->kpp_rich_mix * f3; L0(VDC1, k)[p] = L0(VDC2, k)[p]; }
+        L0(VISC, k)[p] = BVVC(k, p) + c->kpp_rich_mix * f3;
+        if (k < km) { L0(VDC2, k)[p] = BVDC(k, p) + c->kpp_rich_mix * f3; L0(VDC1, k)[p] = L0(VDC2, k)[p]; }
       } else {
-        L0(VISC, k)[p] = K->bckgrnd_vvc[k];
-        if (k < km) { L0(VDC2, k)[p] = K->bckgrnd_vdc[k]; L0(VDC1, k)[p] = L0(VDC2, k)[p]; }
+        L0(VISC, k)[p] = BVVC(k, p);
+        if (k < km) { L0(VDC2, k)[p] = BVDC(k, p); L0(VDC1, k)[p] = L0(VDC2, k)[p]; }
       }
-      if (k >= KMT[p]) { L0(VISC, k)[p] = 0.0; L0(VDC1, k)[p] = 0.0; L0(VDC2, k)[p] = 0.0; }
     }
+    for (size_t p = 0; p < n2; p++)
+      if (k >= KMT[p]) { L0(VISC, k)[p] = 0.0; L0(VDC1, k)[p] = 0.0; L0(VDC2, k)[p] = 0.0; }
+  }
+#undef BVDC
+#undef BVVC
   for (size_t p = 0; p < n2; p++) {
     L0(VISC, 0)[p] = 0.0; L0(VDC1, 0)[p] = 0.0; L0(VDC2, 0)[p] = 0.0;
     L0(VISC, km + 1)[p] = 0.0; L0(VDC1, km + 1)[p] = 0.0; L0(VDC2, km + 1)[p] = 0.0;

@@ -165,6 +165,7 @@ static void lw_lim_tracer(orc_model *m, int b, int k, double adv_dt, const doubl
                           double *TRACER_E, double *TRACER_N, const double *LW_z, const double *MU_z, const double *LW_x, const double *MU_x,
                           const double *LW_y, const double *MU_y, const double *DIV, double *XSTAR) {
   DECL_DIMS DECL_BLK
+  (void)UVEL_E_dt; (void)VVEL_N_dt; (void)WTKBp1;   /* kept in the argument list; not read here */
   zero_ghost_cells(m, b, TRACER_E); zero_ghost_cells(m, b, TRACER_N); zero_ghost_cells(m, b, AUXB);
   for (int j = jb - 2; j <= je + 2; j++) {
     for (int i = ib - 2; i <= ie + 2; i++) {

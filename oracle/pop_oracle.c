@@ -18,6 +18,15 @@
 /* constants: source/pop_constants.F90:40-56, 234-266 (non-CCSMCOUPLED) */
 /* ------------------------------------------------------------------ */
 const double orc_grav = 980.6, orc_omega = 7.292123625e-5, orc_radius = 6370.0e5;
+char orc_errbuf[256];
+const char *orc_last_error(void) { return orc_errbuf; }
+int orc_fail(const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(orc_errbuf, sizeof orc_errbuf, fmt, ap);
+  va_end(ap);
+  return 1;
+}
 
 static double *dalloc(size_t n) {
   double *p = (double *)calloc(n ? n : 1, sizeof(double));
@@ -426,6 +435,7 @@ static void horiz_grid(orc_model *m) {
     scatter_global_r8(m, m->DYU, W, ORC_NECORNER);
     scatter_global_r8(m, m->HUS, gin->HUS, ORC_EFACE);
     scatter_global_r8(m, m->HUW, gin->HUW, ORC_NFACE);
+    if (gin->ANGLE) scatter_global_r8(m, m->ANGLE, gin->ANGLE, ORC_NECORNER);   /* :1524-1525; 0 on the internal grid (:1275) */
 #undef G2
     free(W);
     double *pos[8] = {m->HTN, m->HTE, m->HUS, m->HUW, m->DXU, m->DYU, m->DXT, m->DYT};
@@ -511,8 +521,8 @@ static void horiz_grid(orc_model *m) {
       m->AUE[o + p] = aue * 0.25 * m->UAREA_R[o + p];
       m->AUNE[o + p] = aune * 0.25 * m->UAREA_R[o + p];
     }
-    /* calc_tpoints grid.F90:2984-3062 (TLAT only needed for forcing/FCORT) */
-    double *TLAT = m->TLAT + o;
+    /* calc_tpoints grid.F90:2984-3062 (TLAT for forcing / FCORT; TLON for the Banda Sea boxes of the varying KPP background) */
+    double *TLAT = m->TLAT + o, *TLON = m->TLON + o;
     for (int j = 2; j <= nyb; j++) for (int i = 2; i <= nxb; i++) {
       double zsw = cos(ULAT[P2(i-1,j-1)]), xsw = cos(ULON[P2(i-1,j-1)]) * zsw, ysw = sin(ULON[P2(i-1,j-1)]) * zsw;
       zsw = sin(ULAT[P2(i-1,j-1)]);
@@ -525,11 +535,20 @@ static void horiz_grid(orc_model *m) {
       double tx = 0.25 * (xc + xs + xw + xsw), ty = 0.25 * (yc + ys + yw + ysw), tz = 0.25 * (zc + zs + zw + zsw);
       double da = sqrt(tx * tx + ty * ty + tz * tz);
       TLAT[P2(i, j)] = asin(tz / da);
+      if (tx != 0.0 || ty != 0.0) TLON[P2(i, j)] = atan2(ty, tx); else TLON[P2(i, j)] = 0.0;   /* :3037-3041 */
     }
     if (jgl[jb - 1] == 1)
-      for (int i = ib; i <= ie; i++) TLAT[P2(i, jb)] = 2.0 * TLAT[P2(i, jb + 1)] - TLAT[P2(i, jb + 2)];
+      for (int i = ib; i <= ie; i++) {
+        TLON[P2(i, jb)] = TLON[P2(i, jb + 1)];
+        TLAT[P2(i, jb)] = 2.0 * TLAT[P2(i, jb + 1)] - TLAT[P2(i, jb + 2)];
+      }
+    for (size_t p = 0; p < m->n2; p++) {   /* :3061-3062 */
+      if (TLON[p] > 2.0 * pi) TLON[p] = TLON[p] - 2.0 * pi;
+      if (TLON[p] < 0.0) TLON[p] = TLON[p] + 2.0 * pi;
+    }
   }
   orc_halo(m, m->TLAT, 1, ORC_CENTER, ORC_SCALAR);
+  orc_halo(m, m->TLON, 1, ORC_CENTER, ORC_SCALAR);
   /* partial bottom cells: read_bottom_cell (grid.F90:2116-2186) = the caller's record scattered as a centre scalar.  Without a
    * record (the reference always reads a file): a synthetic thickness in (0.25, 1] dz(KMT) -- TEST EXTENSION, same integer rule
    * as the library (host_setup.cpp) */
@@ -924,6 +943,7 @@ static void init_time(orc_model *m) {
 /* time_manager + set_switches: time_management.F90:1823-1847, 2118-2225 */
 void orc_time_manager(orc_model *m) {
   const orc_config *c = &m->c;
+  m->ran = 1;
   m->leapfrogts = 1; m->f_euler_ts = 0; m->avg_ts = 0;
   m->nsteps_total = m->nsteps_total + 1;
   if (c->tmix_opt == 2) {

@@ -26,14 +26,15 @@ extern "C" {
 
 /* Same field order as include/pop_amd.h's pop_config so one ctypes
  * Structure serves both libraries (declared separately on purpose). */
-#define ORC_CONFIG_VERSION 5   /* = POP_CONFIG_VERSION of include/pop_amd.h */
+#define ORC_CONFIG_VERSION 7   /* = POP_CONFIG_VERSION of include/pop_amd.h; orc_create accepts 7, 6 and 5 as the device does: a version-5 struct is
+                                 * read up to kappa_depth_scale, a version-6 struct up to smag_lat_gauss, the members beyond stay 0 */
 typedef struct {
-  int struct_version;         /* = ORC_CONFIG_VERSION = include/pop_amd.h POP_CONFIG_VERSION; orc_create returns NULL for any other */
+  int struct_version;         /* 5, 6 or 7 (ORC_CONFIG_VERSION); orc_create returns NULL for any other, the reason in orc_last_error() */
   int nx_global, ny_global, km, nt;
   int block_size_x, block_size_y;
   int ew_boundary;            /* 0 closed, 1 cyclic */
   int ns_boundary;            /* 0 closed, 1 cyclic, 2 tripole (time stepping needs orc_create_with_grid) */
-  int hmix_momentum;          /* 2 del2, 4 del4 */
+  int hmix_momentum;          /* 2 del2, 4 del4, 3 anis (struct_version >= 6) */
   int hmix_tracer;            /* 2 del2, 4 del4 */
   int lvariable_hmix;         /* variable hmix coefficients */
   int vmix_choice;            /* 1 const, 2 rich, 3 kpp */
@@ -69,6 +70,23 @@ typedef struct {
   int reserved_i[1];
   double ah_bkg_bottom;
   double kappa_depth_1, kappa_depth_2, kappa_depth_scale;
+  /* struct_version 6: hmix_aniso_nml (hmix_aniso.F90:167-224), read with hmix_momentum = 3; a 0 stands for the code default where the device says so */
+  int aniso_alignment;        /* 0 'grid', 1 'east'; 2 'flow' is refused as on the device */
+  int lvariable_hmix_aniso;   /* F_PARA / F_PERP of compute_ccsm_var_viscosity, tapered to AMAX_CFL */
+  int lsmag_aniso;            /* Smagorinsky viscosities: NOT restated here, refused */
+  int vconst_5;               /* 0 = 3 */
+  double visc_para, visc_perp;
+  double c_para, c_perp;
+  double u_para, u_perp;
+  double vconst_1, vconst_2, vconst_3, vconst_4, vconst_6, vconst_7;   /* 0 = 1e7, 24.5, 0.2, 1e-8, 1e7, 45 */
+  double smag_lat, smag_lat_fact, smag_lat_gauss;
+  /* struct_version 7: lsubmesoscale_mixing and mix_submeso_nml (mix_submeso.F90:164-188) */
+  int lsubmesoscale_mixing;
+  int luse_const_horiz_len_scale;
+  int submeso_diag;           /* 1: "SUBM_ADV_TEND" (n = 0, 1) kept for orc_field */
+  double efficiency_factor;   /* 0 = 0.07 */
+  double time_scale_constant; /* 0 = 3.456e5 */
+  double hor_length_scale;    /* 0 = 5e5 */
 } orc_config;
 
 typedef struct orc_model orc_model;
@@ -82,13 +100,42 @@ typedef struct {
   const double *DZBC;   /* partial_bottom_cells: record of bottom_cell_file (grid.F90:2116-2186), or NULL */
 } orc_grid_input;
 
+/* tidal_nml and the lhoriz_varying_bckgrnd members of vmix_kpp_nml through entry points of their own, with the layouts of
+ * include/pop_amd.h pop_tidal_nml / pop_kpp_bckgrnd_nml (declared separately on purpose, like the config) and the same rules:
+ * one call each, after orc_create* and before the first orc_time_manager / orc_step / phase, in either order.  Both return 0,
+ * or non-zero with the reason in orc_last_error().  Refused as on the device: vmix_choice != 3, bckgrnd_vdc2 != 0, the
+ * Schmittner and Polzin methods, negative parameters.  Refused here only: ltidal_min_regions (not restated). */
+#define ORC_MAX_TIDAL_MIN_REGIONS 9
+typedef struct {
+  int struct_bytes;
+  int ltidal_mixing, tidal_mixing_method, ltidal_max, ltidal_stabc, lccsm_control_compatible, ltidal_min_regions, num_tidal_min_regions;
+  int tidal_diag;               /* accepted; "TIDAL_DIFF", "TIDAL_N2", "KVMIX", "KVMIX_M" are always kept here */
+  double tidal_local_mixing_fraction, tidal_mixing_efficiency, vertical_decay_scale, tidal_mix_max;   /* 0 = 0.33, 0.2, 500e2, 100 */
+  double tidal_min_values[ORC_MAX_TIDAL_MIN_REGIONS], tidal_TLATmin_regions[ORC_MAX_TIDAL_MIN_REGIONS], tidal_TLATmax_regions[ORC_MAX_TIDAL_MIN_REGIONS];
+  double tidal_TLONmin_regions[ORC_MAX_TIDAL_MIN_REGIONS], tidal_TLONmax_regions[ORC_MAX_TIDAL_MIN_REGIONS];
+  int tidal_min_regions_klevels[ORC_MAX_TIDAL_MIN_REGIONS];
+} orc_tidal_nml;
+typedef struct {
+  int struct_bytes;
+  int lhoriz_varying_bckgrnd, larctic_bckgrnd_vdc;
+  double bckgrnd_vdc_eq, bckgrnd_vdc_psim, bckgrnd_vdc_ban;   /* taken literally */
+} orc_kpp_bckgrnd_nml;
+const char *orc_last_error(void);   /* why the last orc_create* returned NULL or the last init call failed */
+
 orc_model *orc_create(const orc_config *cfg);
 orc_model *orc_create_with_grid(const orc_config *cfg, const orc_grid_input *grid);   /* grid = NULL: orc_create */
 void       orc_destroy(orc_model *m);
+/* flux: the record of tidal_energy_file [W/m^2], (nx_block, ny_block, nblocks); its ghost cells are filled by a halo update */
+int orc_init_tidal_mixing(orc_model *m, const orc_tidal_nml *nml, const double *flux, long long count);
+int orc_init_kpp_bckgrnd(orc_model *m, const orc_kpp_bckgrnd_nml *nml);
 
 /* array access by the reference's variable name; tl = 0 old,1 cur,2 new
  * (logical time level, resolved through the rotating indices); n = tracer.
  * Returns pointer to the (nx_block,ny_block[,km],nblocks) array, or NULL. */
+/* Under the device's names, once the scheme is on: "HDU", "HDV" (the friction of the last clinic), "F_PARA", "F_PERP", "AMAX_CFL" (anis);
+ * "SUBM_ML_DEPTH", "HLS_SUBM", "SUBM_TIME_SCALE", "SUBM_ADV_TEND" (n = 0, 1) (submeso); "TIDAL_ENERGY_FLUX", "TIDAL_COEF_3D",
+ * "TIDAL_DIFF", "TIDAL_N2", "KVMIX", "KVMIX_M" (after orc_init_tidal_mixing); "BCKGRND_VDC", "BCKGRND_VVC" (2-D, after
+ * orc_init_kpp_bckgrnd); "TLON", "ANGLE" always. */
 double *orc_field(orc_model *m, const char *name, int tl, int n);
 int    *orc_ifield(orc_model *m, const char *name);
 double *orc_vfield(orc_model *m, const char *name);  /* vertical 1-D arrays */

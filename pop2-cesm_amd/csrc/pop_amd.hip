@@ -988,6 +988,7 @@ int pop_get_dim(const pop_ctx *c, const char *name) {
   if (n == "newtime") return c->newt;
   if (n == "leapfrogts") return c->leapfrogts;
   if (n == "land_skip_active") return c->g.skip;
+  if (n == "kpp_ahead_used") return c->ahead_swaps;   // steps whose KPP coefficients were those of the look-ahead (phase_vmix)
   if (n == "d2t_fused") return c->d2t_next[0] != nullptr;   // the tracer / momentum kernels also form the next step's del4 first Laplacian
   if (n == "d2u_fused") return c->d2u_next[0] != nullptr;
   if (n == "d2t_last_formed") return c->d2t_last_formed;   // ... and whether the last such launch did (not on averaging steps)
@@ -1370,7 +1371,7 @@ static int phase_vmix(pop_ctx *c) {
   else {
     if (c->ahead_valid && c->ahead_slot == c->mixt) {   // computed beside the previous step's solver: swap the output sets in
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ahead, 0));
-      c->ahead_valid = false; c->kpp_src_user = false;
+      c->ahead_valid = false; c->kpp_src_user = false; ++c->ahead_swaps;
       for (int n = 0; n < 2; ++n) { std::swap(c->VDC[n], c->VDCa[n]); std::swap(c->KPP_SRC[n], c->KPPa[n]); }
       std::swap(c->VVC, c->VVCa); std::swap(c->HBLT, c->HBLTa); std::swap(c->KBL, c->KBLa); std::swap(c->src_dirty, c->src_dirty_alt);
       if (c->HMXLa) { std::swap(c->HMXL, c->HMXLa); std::swap(c->HMXL_DR, c->HMXL_DRa); }

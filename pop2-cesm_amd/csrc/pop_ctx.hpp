@@ -65,7 +65,7 @@ struct pop_ctx {
   double *VDCa[2] = {nullptr, nullptr}, *VVCa = nullptr, *KPPa[MAXNT] = {}, *HBLTa = nullptr, *HMXLa = nullptr, *HMXL_DRa = nullptr;
   int *KBL = nullptr, *KBLa = nullptr;   // KBL that belongs to KPP_SRC / KPPa (the tracer kernel reads KPP_SRC down to it)
   hipStream_t ahead = nullptr; hipEvent_t ev_ahead_fork = nullptr, ev_ahead = nullptr;
-  bool ahead_enabled = false, ahead_valid = false; int ahead_slot = -1;
+  bool ahead_enabled = false, ahead_valid = false; int ahead_slot = -1, ahead_swaps = 0;   // ahead_swaps: steps that took their coefficients from the look-ahead
   // solver
   double *R = nullptr, *S0 = nullptr, *S1 = nullptr, *Q = nullptr, *Z = nullptr, *AZ = nullptr;
   double *partial = nullptr, *blocksum = nullptr;

@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 from popcfg import named_config  # noqa: E402
 
 FIELDS = [("TRACER", True), ("UVEL", True), ("VVEL", True), ("RHO", True), ("PSURF", False), ("UBTROP", False)]
-NSTEPS = {"const": 4, "kpp_del4": 4, "upwind3": 5, "robert": 6, "pcsi_evp": 4, "lw_lim": 5, "pbc_kpp_del4": 5, "padded": 5, "gm": 5, "gm_tlt": 5}
+NSTEPS = {"const": 4, "kpp_del4": 4, "upwind3": 5, "robert": 6, "pcsi_evp": 4, "lw_lim": 5, "pbc_kpp_del4": 5, "padded": 5, "gm": 5, "gm_tlt": 5, "cesm_all": 6}
 
 
 def config(case):
@@ -38,6 +38,11 @@ def config(case):
     if case == "gm_tlt":      # ... with the transition layer and the buoyancy-frequency-dependent kappa recomputed every step (the CESM set-up but for kappa_freq)
         return named_config("tiny", hmix_tracer=3, ah=0.8e7, ah_bolus=0.5e7, gm_transition_layer=1, gm_kappa_type=1, gm_kappa_freq=1,
                             vmix_choice=3, stepped_bathymetry=1, **small)
+    if case == "cesm_all":    # every scheme CESM's namelist defaults select on the gx grids (tests/cesm_case.py): anis 'east' with the variable
+        # viscosities, submeso, GM with the transition layer and once-a-day 'bfre' kappa (a day of four steps: step 5 recomputes it), KPP with
+        # double diffusion, upwind3, Robert filter, P-CSI + EVP; tidal mixing and the varying background through their init calls in prepare()
+        import cesm_case
+        return cesm_case.all_on_config(named_config("tiny", **dict(cesm_case.ALL_ON, **small)))
     if case == "upwind3":     # third-order upwind tracer advection + Richardson vmix
         return named_config("tiny", tadvect=2, vmix_choice=2, **small)
     if case == "lw_lim":      # Lax-Wendroff advection with one-dimensional flux limiters + KPP
@@ -56,9 +61,14 @@ def surface_fluxes(tlat):
 def prepare(model, case):
     """Set the surface tracer fluxes (the KPP case needs buoyancy forcing).  `model` is an Oracle or a
     PopModel-like object with f2()/set()."""
-    if case not in ("kpp_del4", "pbc_kpp_del4", "padded", "gm", "gm_tlt"):
+    if case not in ("kpp_del4", "pbc_kpp_del4", "padded", "gm", "gm_tlt", "cesm_all"):
         return
     tlat = model.f2("TLAT") if hasattr(model, "f2") else model.get("TLAT")
+    if case == "cesm_all":    # the tidal energy flux [W/m^2], a smooth function of latitude, and CESM's background values; tidal first
+        from bckgrnd_ref import CESM
+        flux = 0.5 * (1.0 + 0.5 * np.sin(2.0 * tlat))
+        model.init_tidal_mixing(flux)
+        model.init_kpp_bckgrnd(**CESM)
     st, ss = surface_fluxes(tlat)
     if hasattr(model, "f2"):
         model.f2("STF", 1, 0)[...] = st

@@ -14,10 +14,11 @@ def build():
     subprocess.check_call(["make", "-s", "-C", os.path.join(_ROOT, "oracle")])
 
 
-def load():
-    if not os.path.exists(_SO):
+def load(lib=None):
+    """lib: another build of the same source (a path), else POP_ORACLE_LIB or the default build"""
+    if lib is None and not os.path.exists(_SO):
         build()
-    L = C.CDLL(_SO)
+    L = C.CDLL(lib or _SO)
     L.orc_create.restype = C.c_void_p
     L.orc_create.argtypes = [C.POINTER(PopConfig)]
     L.orc_create_with_grid.restype = C.c_void_p
@@ -61,7 +62,64 @@ def load():
     L.orc_operator.restype = None
     L.orc_global_sum.restype = C.c_double
     L.orc_global_sum.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.orc_last_error.restype = C.c_char_p
+    L.orc_init_tidal_mixing.argtypes = [C.c_void_p, C.POINTER(OrcTidalNml), C.POINTER(C.c_double), C.c_longlong]
+    L.orc_init_kpp_bckgrnd.argtypes = [C.c_void_p, C.POINTER(OrcKppBckgrndNml)]
     return L
+
+
+MAX_TIDAL_MIN_REGIONS = 9
+
+
+class OrcTidalNml(C.Structure):
+    """oracle/pop_oracle.h orc_tidal_nml (the layout of include/pop_amd.h pop_tidal_nml)"""
+    _fields_ = [(n, C.c_int) for n in ("struct_bytes", "ltidal_mixing", "tidal_mixing_method", "ltidal_max", "ltidal_stabc",
+                                       "lccsm_control_compatible", "ltidal_min_regions", "num_tidal_min_regions", "tidal_diag")] + \
+        [(n, C.c_double) for n in ("tidal_local_mixing_fraction", "tidal_mixing_efficiency", "vertical_decay_scale", "tidal_mix_max")] + \
+        [(n, C.c_double * MAX_TIDAL_MIN_REGIONS) for n in ("tidal_min_values", "tidal_TLATmin_regions", "tidal_TLATmax_regions",
+                                                           "tidal_TLONmin_regions", "tidal_TLONmax_regions")] + \
+        [("tidal_min_regions_klevels", C.c_int * MAX_TIDAL_MIN_REGIONS)]
+
+
+class OrcKppBckgrndNml(C.Structure):
+    """oracle/pop_oracle.h orc_kpp_bckgrnd_nml (the layout of include/pop_amd.h pop_kpp_bckgrnd_nml)"""
+    _fields_ = [(n, C.c_int) for n in ("struct_bytes", "lhoriz_varying_bckgrnd", "larctic_bckgrnd_vdc")] + \
+        [(n, C.c_double) for n in ("bckgrnd_vdc_eq", "bckgrnd_vdc_psim", "bckgrnd_vdc_ban")]
+
+
+def tidal_nml(**kw):
+    """orc_tidal_nml with the code defaults of tidal_mixing.F90:670-760 and ltidal_mixing = 1, then the members given by name"""
+    n = OrcTidalNml()
+    n.struct_bytes = C.sizeof(OrcTidalNml)
+    n.ltidal_mixing, n.ltidal_max, n.ltidal_stabc = 1, 1, 1
+    n.tidal_local_mixing_fraction, n.tidal_mixing_efficiency, n.vertical_decay_scale, n.tidal_mix_max = 0.33, 0.20, 500.0e2, 100.0
+    for r in range(MAX_TIDAL_MIN_REGIONS):
+        n.tidal_min_values[r], n.tidal_min_regions_klevels[r] = 20.0, 6
+    for k, v in kw.items():
+        if not hasattr(n, k):
+            raise AttributeError("orc_tidal_nml has no field %r" % k)
+        setattr(n, k, v)
+    return n
+
+
+def kpp_bckgrnd_nml(**kw):
+    """orc_kpp_bckgrnd_nml with the code defaults of vmix_kpp.F90:337-349 (0.01, 0.13, 1.0) and lhoriz_varying_bckgrnd = 1"""
+    n = OrcKppBckgrndNml()
+    n.struct_bytes = C.sizeof(OrcKppBckgrndNml)
+    n.lhoriz_varying_bckgrnd, n.bckgrnd_vdc_eq, n.bckgrnd_vdc_psim, n.bckgrnd_vdc_ban = 1, 0.01, 0.13, 1.0
+    for k, v in kw.items():
+        if not hasattr(n, k):
+            raise AttributeError("orc_kpp_bckgrnd_nml has no field %r" % k)
+        setattr(n, k, v)
+    return n
+
+
+def _same_layout(src, cls):
+    """a cls holding the bytes of the ctypes structure src (the device's mirror of the same namelist); struct_bytes travels with them"""
+    assert C.sizeof(src) == C.sizeof(cls), (C.sizeof(src), C.sizeof(cls))
+    out = cls()
+    C.memmove(C.addressof(out), C.addressof(src), C.sizeof(cls))
+    return out
 
 
 class OrcGridInput(C.Structure):
@@ -74,8 +132,8 @@ class Oracle:
     """Thin object wrapper; arrays come back as numpy views in Fortran index order
     reversed, i.e. shape (nblocks, [km,] ny_block, nx_block)."""
 
-    def __init__(self, cfg, grid=None):
-        self.L = load()
+    def __init__(self, cfg, grid=None, lib=None):
+        self.L = load(lib)
         self.cfg = cfg
         if grid is None:
             self.h = self.L.orc_create(C.byref(cfg))
@@ -90,10 +148,26 @@ class Oracle:
             self.h = self.L.orc_create_with_grid(C.byref(cfg), C.cast(C.byref(gin), C.c_void_p))
             del keep
         if not self.h:
-            raise RuntimeError("orc_create failed")
+            raise RuntimeError("orc_create failed: %s" % self.L.orc_last_error().decode())
         d = lambda n: self.L.orc_dim(self.h, n.encode())
         self.nxb, self.nyb, self.km, self.nt, self.nblocks = (d("nx_block"), d("ny_block"), d("km"),
                                                               d("nt"), d("nblocks"))
+
+    def init_tidal_mixing(self, energy_flux, nml=None, **kw):
+        """orc_init_tidal_mixing: energy_flux [W/m^2] (nblocks, ny_block, nx_block); nml: a pop_tidal_nml / orc_tidal_nml of the same
+        layout (its bytes are copied), or None: tidal_nml(**kw).  Returns the orc_tidal_nml that was passed."""
+        n = tidal_nml(**kw) if nml is None else _same_layout(nml, OrcTidalNml)
+        a = np.ascontiguousarray(energy_flux, dtype=np.float64)
+        if self.L.orc_init_tidal_mixing(self.h, C.byref(n), a.ctypes.data_as(C.POINTER(C.c_double)), a.size):
+            raise RuntimeError(self.L.orc_last_error().decode())
+        return n
+
+    def init_kpp_bckgrnd(self, nml=None, **kw):
+        """orc_init_kpp_bckgrnd; nml / keywords as init_tidal_mixing"""
+        n = kpp_bckgrnd_nml(**kw) if nml is None else _same_layout(nml, OrcKppBckgrndNml)
+        if self.L.orc_init_kpp_bckgrnd(self.h, C.byref(n)):
+            raise RuntimeError(self.L.orc_last_error().decode())
+        return n
 
     def close(self):
         if self.h:
@@ -198,3 +272,85 @@ class Oracle:
         if e:
             raise RuntimeError("oracle solver did not converge")
         return self.L.orc_solver_iterations(self.h)
+
+
+_PD = C.POINTER(C.c_double)
+FIELDS_KM2 = ("VDC", "DZT", "DZU")                                                # (nblocks, km + 2, ny, nx)
+FIELDS_3D = ("TRACER", "UVEL", "VVEL", "RHO", "VVC", "KPP_SRC", "TIDAL_COEF_3D", "TIDAL_DIFF", "TIDAL_N2", "KVMIX", "KVMIX_M",
+             "HDU", "HDV", "F_PARA", "F_PERP", "SUBM_ADV_TEND")
+
+
+class AsModel:
+    """what the restatement helpers ask of a device model (pop2-cesm_amd PopModel), served by an Oracle: one rank, every block local"""
+    LOC = {"center": 0, "necorner": 1, "nface": 2, "eface": 3}
+    KIND = {"scalar": 0, "vector": 1, "angle": 2}
+
+    def __init__(self, orc):
+        self.orc, self.cfg = orc, orc.cfg
+        self.km, self.nblocks, self.nyb, self.nxb = orc.km, orc.nblocks, orc.nyb, orc.nxb
+        self.nblocks_tot = orc.nblocks
+        orc.L.orc_state.argtypes = [C.c_void_p, C.c_int, C.c_int, _PD, _PD, _PD, _PD, _PD, C.c_int]
+
+    def local_block_ids(self):
+        return list(range(1, self.nblocks + 1))
+
+    def get_block(self, bid):
+        o, b = self.orc, bid - 1
+        v = lambda n: int(o.ivec(n, o.nblocks)[b])
+        return {"block_id": bid, "local_id": bid, "ib": v("blk_ib"), "ie": v("blk_ie"), "jb": v("blk_jb"), "je": v("blk_je"),
+                "i_glob": o.ivec("i_glob", o.nblocks * o.nxb)[b * o.nxb:(b + 1) * o.nxb].copy(),
+                "j_glob": o.ivec("j_glob", o.nblocks * o.nyb)[b * o.nyb:(b + 1) * o.nyb].copy()}
+
+    def _view(self, name, tl, n):
+        o = self.orc
+        return o.f3p(name) if name in ("DZT", "DZU") else o.vdc(n) if name == "VDC" else o.f3(name, tl, n) if name in FIELDS_3D else o.f2(name, tl, n)
+
+    def get(self, name, tl=1, n=0):
+        if name == "DZUB":      # the device's name for DZU at the bottom U level (0 on land)
+            kmu, dzu = self.orc.i2("KMU"), self.orc.f3p("DZU")
+            return np.where(kmu > 0, np.take_along_axis(dzu, np.maximum(kmu, 0)[:, None], axis=1)[:, 0], 0.0)
+        return self._view(name, tl, n).copy()
+
+    def scalar(self, name):
+        return self.orc.scalar(name)
+
+    def geti(self, name):
+        return self.orc.i2(name).copy()
+
+    def set(self, name, arr, tl=1, n=0):
+        self._view(name, tl, n)[...] = arr
+
+    def halo_update(self, name, tl=1, n=0, loc="center", kind="scalar"):
+        a = self._view(name, tl, n)
+        self.orc.L.orc_halo(self.orc.h, a.ctypes.data_as(_PD), a.size // (self.nblocks * self.nyb * self.nxb), self.LOC[loc], self.KIND[kind])
+
+    def halo_update_loc(self, name, tl, n, loc, kind):
+        self.halo_update(name, tl, n, loc.lower(), kind.lower())
+
+    def halo_update_host_loc(self, a, fill=0, loc="center", kind="scalar"):
+        assert a.dtype == np.float64 and a.flags.c_contiguous and fill == 0
+        self.orc.L.orc_halo(self.orc.h, a.ctypes.data_as(_PD), a.size // (self.nblocks * self.nyb * self.nxb), self.LOC[loc], self.KIND[kind])
+
+    def state(self, kk, T, S, derivs=False):
+        T, S = np.ascontiguousarray(T, dtype=np.float64), np.ascontiguousarray(S, dtype=np.float64)
+        rho, dt_, ds_ = np.empty_like(T), np.empty_like(T), np.empty_like(T)
+        self.orc.L.orc_state(self.orc.h, kk, kk, T.ctypes.data_as(_PD), S.ctypes.data_as(_PD), rho.ctypes.data_as(_PD),
+                             dt_.ctypes.data_as(_PD) if derivs else None, ds_.ctypes.data_as(_PD) if derivs else None, T.size)
+        return (rho, dt_, ds_) if derivs else rho
+
+    def time_manager(self):
+        self.orc.L.orc_time_manager(self.orc.h)
+        self._tracer_stage_done = False
+
+    def run_phase(self, phase):
+        """the oracle forms the vertical-mixing coefficients and the horizontal tracer mixing inside its tracer stage (the reference
+        calls vmix_coeffs and hdifft from the k loop of tracer_update): "vmix" and "hmix_tracer" both stand for that stage, run once"""
+        if phase in ("vmix", "hmix_tracer"):
+            if not self._tracer_stage_done:
+                self.orc.run_phase("tracer_rhs")
+            self._tracer_stage_done = True
+        else:
+            self.orc.run_phase({"hmix_momentum": "momentum_rhs"}.get(phase, phase))
+
+    def close(self):
+        self.orc.close()

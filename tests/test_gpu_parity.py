@@ -53,10 +53,17 @@ def check(gpu, orc, name, tol, tl=1, n=0, three_d=True, inner=True, what=""):
     return e
 
 
-def run_phases(gpu, orc, step, tol_state):
+def run_phases(gpu, orc, step, tol_state, tidal_diag=False, levels_must_differ=False):
+    """one step, phase by phase.  tidal_diag: both models keep the tidal diagnostics (pop_tidal_nml.tidal_diag), compared after the
+    baroclinic driver; levels_must_differ: on a leapfrog step the old and current U and T must differ, so that the comparison tells a
+    kernel that reads curtime from one that reads mixtime (tests/test_gpu_schemes_oracle.py)"""
     L = orc.L
     gpu.time_manager(); L.orc_time_manager(orc.h)
     assert gpu.dim("leapfrogts") == orc.dim("leapfrogts") and gpu.dim("avg_ts") == orc.dim("avg_ts")
+    if levels_must_differ and gpu.dim("leapfrogts"):
+        for name in ("UVEL", "TRACER"):
+            assert not np.array_equal(pick(gpu, gpu.get(name, 0), True), pick(gpu, gpu.get(name, 1), True)), "step %d: %s old = cur" % (step, name)
+            assert not np.array_equal(pick(gpu, orc.f3(name, 0), True), pick(gpu, orc.f3(name, 1), True)), "step %d: oracle %s old = cur" % (step, name)
     gpu.dhdt(); L.orc_dhdt(orc.h)
     w = "step %d dhdt" % step
     check(gpu, orc, "DH", tol_state, three_d=False, inner=False, what=w)
@@ -78,6 +85,18 @@ def run_phases(gpu, orc, step, tol_state):
         check(gpu, orc, "HBLT", tol_state * 10, three_d=False, what=w)
         for n in (0, 1):
             check(gpu, orc, "KPP_SRC", tol_state * 100, n=n, what=w)
+    if gpu.cfg.hmix_momentum == 3:                           # anis: the friction clinic has just formed from the mixtime velocities
+        check(gpu, orc, "HDU", tol_state, what=w)
+        check(gpu, orc, "HDV", tol_state, what=w)
+    # the submesoscale and tidal fields are functions of KPP's output (HMXL; N^2 of the mixtime tracers next to VDC): VDC / HBLT's factor
+    if getattr(gpu.cfg, "lsubmesoscale_mixing", 0):          # needs submeso_diag = 1
+        check(gpu, orc, "SUBM_ML_DEPTH", tol_state * 10, three_d=False, what=w)
+        check(gpu, orc, "HLS_SUBM", tol_state * 10, three_d=False, what=w)
+        for n in (0, 1):
+            check(gpu, orc, "SUBM_ADV_TEND", tol_state * 10, n=n, what=w)
+    if tidal_diag:
+        for f in ("TIDAL_DIFF", "KVMIX", "KVMIX_M"):
+            check(gpu, orc, f, tol_state * 10, what=w)
     gpu.barotropic_driver(); assert L.orc_barotropic_driver(orc.h) == 0
     w = "step %d barotropic_driver" % step
     it_g, rms_g = gpu.solver_diagnostics()
