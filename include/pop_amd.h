@@ -318,6 +318,18 @@ void pop_kpp_bckgrnd_nml_init(pop_kpp_bckgrnd_nml *nml);   /* struct_bytes = siz
  * ONE level is stored where the reference stores km identical copies -- and "TLON" [radians].  Restart files carry nothing of it. */
 int pop_init_kpp_bckgrnd(pop_ctx *ctx, const pop_kpp_bckgrnd_nml *nml);
 
+/* ---- passive tracers (nt = 3 .. 8) and ideal age (iage_mod.F90).  A tracer n >= 3 is a plain passive tracer unless made ideal age
+ *      here: no source, no reset, 0 at the three time levels, STF(n) = TFW(n) = 0 until set with pop_set_field; it is advected and
+ *      mixed as T and S are (cfg.tadvect, the (T, S) mixing schemes, salinity's vertical diffusivity) and feeds nothing back.
+ * pop_init_iage makes tracer n (1-based, 3 .. nt) ideal age: interior source 1 / (365 * 86400) [years/s] at the levels 1 < k <= KMT
+ * (iage_mod.F90:325-355), TRACER(:,:,1) = 0 after the tracer update and after the Robert filter (:386-415), 0 at the three time
+ * levels now.  Once per tracer (several tracers may each be ideal age), after pop_create* and -- with several ranks -- the transport,
+ * before the first pop_time_manager / pop_step / pop_run_phase, in any order with the other pop_init_* calls.  Refused: n outside
+ * 3 .. nt; a second call for the same n; a call after a step or a phase.  Works on a host-only context.
+ * Restart files name the tracer IAGE (IAGE_<n> from the second one on; TRACER<nn> for a plain passive tracer) and do not carry the
+ * marking: make the call again before pop_read_restart. */
+int pop_init_iage(pop_ctx *ctx, int n);
+
 /* ---- blocks.F90:43-63 / get_block (blocks.F90:282-320) ---------------------- */
 int pop_get_dim(const pop_ctx *ctx, const char *name);         /* nx_block, ny_block, km, nt,
                                                                   nblocks (local), nblocks_tot,
@@ -482,7 +494,9 @@ int pop_timer_ms(pop_ctx *ctx, const char *name, double *total_ms, int *calls);
 int pop_time_phase(pop_ctx *ctx, const char *phase, int reps, double *avg_ms);
 /* one phase of baroclinic_driver / baroclinic_correct_adjust on its own (the public routines the reference's drivers
  * call one after the other): "vmix" vmix_coeffs vertical_mix.F90:518, "hmix_tracer" / "hmix_momentum" first Laplacians of
- * hmix_del4.F90:1021 / :730 (no-ops for del2), "tracer_rhs" tracer_update baroclinic.F90:1902, "impvmixt"
+ * hmix_del4.F90:1021 / :730 (no-ops for del2), "tracer_rhs" tracer_update baroclinic.F90:1902 for T and S, "passive_rhs" the
+ * same for the tracers n = 3 .. nt (nothing with nt = 2; after "vmix", "hmix_tracer" and "tracer_rhs", whose flux velocities,
+ * slopes and stream function it uses: with nt > 2 the two phases together are tracer_update), "impvmixt"
  * vertical_mix.F90:1164, "state" state_mod.F90:258 on the new tracers, "momentum_rhs" clinic baroclinic.F90:1635,
  * "impvmixu" vertical_mix.F90:1679 + baroclinic.F90:1077-1129, "correct" impvmixt_correct :1460 with the surface
  * terms of baroclinic.F90:1261-1475, "add_btrop" step_mod.F90:572-600.  Uses the step parameters of the last

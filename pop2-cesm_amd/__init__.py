@@ -88,6 +88,7 @@ def lib():
         "pop_time_phase": (ci, [vp, cs, ci, pd]), "pop_device_sync": (ci, [vp]), "pop_run_phase": (ci, [vp, cs]),
         "pop_tidal_nml_init": (None, [vp]), "pop_init_tidal_mixing": (ci, [vp, vp, pd, ll]),
         "pop_kpp_bckgrnd_nml_init": (None, [vp]), "pop_init_kpp_bckgrnd": (ci, [vp, vp]),
+        "pop_init_iage": (ci, [vp, ci]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)       # AttributeError here = the library does not export the ABI
@@ -397,6 +398,12 @@ class PopModel:
         n = kpp_bckgrnd_nml(**nml)
         self._chk(self.L.pop_init_kpp_bckgrnd(self.h, C.byref(n)))
         return n
+
+    def init_iage(self, n):
+        """Make the passive tracer n (1-based, 3 .. nt) ideal age (iage_mod.F90): interior source 1 / (365 * 86400) below the surface
+        level, surface level reset to 0, 0 at the three time levels now.  Once per tracer, before the first step or phase; on every
+        rank; again before read_restart on a fresh context (the file does not carry the marking)."""
+        self._chk(self.L.pop_init_iage(self.h, n))
 
     # ---- step_mod.F90 sequence
     def time_manager(self):

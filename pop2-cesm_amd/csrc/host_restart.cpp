@@ -18,6 +18,15 @@
 namespace pop {
 
 // fields of the restart file in the order write_restart defines them (restart.F90:1555-1600); varthick surface layer
+// tracer_d(n)%short_name of tracer n (0-based): TEMP, SALT; IAGE for an ideal-age tracer (iage_mod.F90:162; IAGE_<n> from the second
+// one on, n 1-based), TRACER<nn> for a tracer without a module
+std::string restart_tracer_name(const HostModel &h, int n) {
+  if (n < 2) return n == 0 ? "TEMP" : "SALT";
+  char b[32];
+  if (!h.iage[n]) { snprintf(b, sizeof b, "TRACER%02d", n + 1); return b; }
+  for (int m = 2; m < n; ++m) if (h.iage[m]) { snprintf(b, sizeof b, "IAGE_%d", n + 1); return b; }
+  return "IAGE";
+}
 std::vector<RestartField> restart_fields(const HostModel &h) {
   std::vector<RestartField> f;
   int rec = 1;
@@ -46,6 +55,12 @@ std::vector<RestartField> restart_fields(const HostModel &h) {
   add("SALT_CUR", "TRACER", 1, 1, 3, "Salinity at current time", "msu (g/g)", "3111", 4);
   add("TEMP_OLD", "TRACER", 0, 0, 3, "Potential temperature at old time", "degC", "3111", 4);
   add("SALT_OLD", "TRACER", 0, 1, 3, "Salinity at old time", "msu (g/g)", "3111", 4);
+  // passive tracers: <tracer_d(n)%short_name>_CUR for every n, then _OLD (restart.F90:1516-1548), after the records of an nt = 2 file
+  for (int tl = 1; tl >= 0; --tl)
+    for (int n = 2; n < h.nt; ++n) {
+      const std::string sn = restart_tracer_name(h, n);
+      add((sn + (tl ? "_CUR" : "_OLD")).c_str(), "TRACER", tl, n, 3, (sn + (tl ? " at current time" : " at old time")).c_str(), h.iage[n] ? "years" : "", "3111", 4);
+    }
   return f;
 }
 

@@ -174,6 +174,9 @@ struct TracerRhsArgs {
   // forward elimination of the implicit vertical mixing fused into the right-hand side (k_tracer_rhs_lds<R, true>): the
   // elimination coefficients and the reduced right-hand side of tracer n go to E[n], F[n] instead of the RHS to TNEW
   double *E[2], *F[2];
+  // passive form (k_tracer_rhs<., ., ., NP, true>): the interior source of the tracer module (set_interior_passive_tracers,
+  // baroclinic.F90:2151), one value per tracer, applied at 1 < k <= KMT (ideal age: iage_mod.F90:352-353)
+  double isrc[2] = {0.0, 0.0};
 };
 __device__ __forceinline__ double sw_source(const TracerRhsArgs &a, double qsw, int k, int kmt, double dzrk, int chli, double &trans_km1, double dzt_pbc) {
   double top, bot;
@@ -193,7 +196,13 @@ __device__ __forceinline__ double sw_source(const TracerRhsArgs &a, double qsw, 
 // top face (AUX) is carried in a register, and four tracer levels k-1..k+2 are kept in registers.
 // PBC: partial bottom cells (the branches of advection.F90:2040-2062, 2110, 2223-2294, 2380-2385, 2461-2465; hmix_del2.F90:1034-1051;
 // vertical_mix.F90:790-807; sw_absorption.F90:880-921) with DZT / DZU formed from DZBC / DZUB (pbc_dz)
-template <bool DEL4, bool UPW3, bool PBC = false>
+// PASSIVE: tracers n >= 3 (tracer_update with nt > 2), NP = 1 | 2 of them in the slots 0 .. NP-1 of the arguments.  The flux
+// velocities, the mixing coefficients and the upwind weights are the same for every tracer, so a pair shares them as T and S do.
+// Differences from (T, S): both slots read salinity's diffusivity (VDC(:,:,:,min(n, size(VDC,4))), vertical_mix.F90:1260 -- the caller
+// sets VDC[0] = VDC[1]); no short-wave source (add_sw_absorb is temperature's); the module's interior source isrc goes into the source sum
+// ahead of the KPP term (baroclinic.F90:2146-2181); the right-hand side is stored as c2dtt * FT at every level, without the
+// surface-pressure term of the predictor, which is for n = 1, 2 only (:2214-2237).  Every other operation is the (T, S) one, in its order.
+template <bool DEL4, bool UPW3, bool PBC = false, int NP = 2, bool PASSIVE = false>
 __global__ void __launch_bounds__(POP_COL_THREADS, POP_TRC_WAVES)
 k_tracer_rhs(DevGrid g, StepParams sp, TracerRhsArgs a) {
   Col c;
@@ -205,7 +214,7 @@ k_tracer_rhs(DevGrid g, StepParams sp, TracerRhsArgs a) {
   const double dyu00 = g.DYU[c.q2], dyu0m = g.DYU[c.q2 - nxb], dyum0 = g.DYU[c.q2 - 1], dyumm = g.DYU[c.q2 - 1 - nxb];
   const double dxu00 = g.DXU[c.q2], dxu0m = g.DXU[c.q2 - nxb], dxum0 = g.DXU[c.q2 - 1], dxumm = g.DXU[c.q2 - 1 - nxb];
   const double tarear = g.TAREA_R[c.q2];
-  const double psfac = (a.PCUR[c.q2] - a.POLD[c.q2]);
+  const double psfac = PASSIVE ? 0.0 : (a.PCUR[c.q2] - a.POLD[c.q2]);
   double wtk = a.DH[c.q2];
   // partial bottom cells: bottom level / thickness of the four U cells around the T cell and of the T cell and its neighbours
   int kmu00 = 0, kmu0m = 0, kmum0 = 0, kmumm = 0;
@@ -218,7 +227,7 @@ k_tracer_rhs(DevGrid g, StepParams sp, TracerRhsArgs a) {
   double vtf[2];
   double tc_km1[2] = {0.0, 0.0}, tc_k[2], tc_kp1[2], to_k[2], to_kp1[2];
 #pragma unroll
-  for (int n = 0; n < 2; ++n) { tc_k[n] = a.TCUR[n][c.base3]; to_k[n] = a.TOLD[n][c.base3]; }
+  for (int n = 0; n < NP; ++n) { tc_k[n] = a.TCUR[n][c.base3]; to_k[n] = a.TOLD[n][c.base3]; }
   const double sw_q = a.sw_on ? fmax(a.QSW[c.q2], 0.0) : 0.0;
   const int sw_chli = (a.sw_on && a.sw_type == 2) ? a.swCHLI[c.q2] : 0;
   double sw_tkm1 = 1.0;
@@ -238,7 +247,7 @@ k_tracer_rhs(DevGrid g, StepParams sp, TracerRhsArgs a) {
     tarear_w = g.TAREA_R[c.q2 - 1]; tarear_s = g.TAREA_R[c.q2 - nxb];
   }
   const long long vdcbase = ((long long)c.b * (km + 2)) * n2 + c.p2;
-  double *__restrict__ const TNp[2] = {a.TNEW[0], a.TNEW[1]};   // outputs alias no input
+  double *__restrict__ const TNp[2] = {a.TNEW[0], a.TNEW[NP - 1]};   // outputs alias no input
   for (int k = 1; k <= km; ++k) {
     const long long o = c.base3 + (long long)(k - 1) * n2;
     const int kp1 = (k < km) ? k + 1 : km;
@@ -274,7 +283,7 @@ k_tracer_rhs(DevGrid g, StepParams sp, TracerRhsArgs a) {
     const double CC = -(CN + CS + CE + CW);
     const double dz2rk = g.dz2r[k], dzrk = g.dzr[k], dzwrk = g.dzwr[k];
 #pragma unroll
-    for (int n = 0; n < 2; ++n) {
+    for (int n = 0; n < NP; ++n) {
       tc_kp1[n] = a.TCUR[n][okp];
       to_kp1[n] = a.TOLD[n][okp];
       double FT;
@@ -338,10 +347,11 @@ k_tracer_rhs(DevGrid g, StepParams sp, TracerRhsArgs a) {
       FT = FT + vd;
       if (k == 1) FT = FT + g.dzr[1] * a.TFW[n][c.q2];
       double src = 0.0;
+      if (PASSIVE) src = (k > 1 && k <= kmt) ? a.isrc[n] : 0.0;
       if (a.use_kpp_src) src = src + a.KPP_SRC[n][o];
-      if (a.sw_on && n == 0) src = src + sw_source(a, sw_q, k, kmt, dzrk, sw_chli, sw_tkm1, PBC ? dzt : 0.0);
+      if (!PASSIVE && a.sw_on && n == 0) src = src + sw_source(a, sw_q, k, kmt, dzrk, sw_chli, sw_tkm1, PBC ? dzt : 0.0);
       FT = FT + src;
-      if (k == 1 && sp.pavg) {
+      if (!PASSIVE && k == 1 && sp.pavg) {
         if (kmt > 0) TNp[n][o] = a.c2dtt * FT - 2.0 * tc_k[n] * psfac / (sp.grav * g.dz[1]);
       } else {
         TNp[n][o] = (k <= kmt) ? a.c2dtt * FT : 0.0;

@@ -441,7 +441,10 @@ __device__ __forceinline__ Gm2 gm_fz(const DevGrid &g, const GmDev &w, const dou
 // tendency of both tracers at every physical cell (0 elsewhere), and -- the coefficients being in registers -- the isopycnal part
 // of the vertical diffusivity added to VDC(k) at EVERY cell of the block (:1725-1748; VDC1: the second array, nullptr when the two
 // tracer classes share one)
+// ADD = false: the tendency only -- the launches for the passive tracers n >= 3, which take the slopes and diffusivities formed from T and S
+// as they are; the addition to VDC is made once, by the (T, S) launch
 #define POP_GM_KC 4   // levels per thread: the level above / below a level is then mostly the same thread's own earlier / later read
+template <bool ADD = true>
 __global__ void __launch_bounds__(256)
 k_gm_flux(DevGrid g, GmDev w, const double *__restrict__ X0, const double *__restrict__ X1, double *__restrict__ VDC0, double *__restrict__ VDC1) {
   const int p2 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -457,7 +460,7 @@ k_gm_flux(DevGrid g, GmDev w, const double *__restrict__ X0, const double *__res
   if (phys && k0 >= 2) fztop = gm_fz(g, w, X0, X1, k0 - 1, q, (long long)b * g.n3 + (long long)(k0 - 2) * n2 + p2);
   for (int k = k0; k < k0 + POP_GM_KC && k <= km; ++k) {
     const long long o = (long long)b * g.n3 + (long long)(k - 1) * n2 + p2;
-    if (k < km) {
+    if (ADD && k < km) {
       const long long ok = o + n2;
       const double kmask = (k < kmt) ? 1.0 : 0.0;
       auto sq = [](double x) { return x * x; };
@@ -596,7 +599,7 @@ __device__ __forceinline__ Gm2 gmb_fz(const DevGrid &g, const GmDev &w, const do
 // shuffle) and the south flux from the row below through LDS; the first column and the first row only supply those fluxes, so no lane
 // evaluates a second flux and no wave diverges (a first form let lane 0 / row 0 evaluate their neighbour's flux themselves: the whole
 // wave waited for it, slower than k_gm_flux).  The isopycnal part of VDC is added by the thread that computes the cell.
-template <int R, bool CANCEL>
+template <int R, bool CANCEL, bool ADD = true>
 __global__ void __launch_bounds__(64 * R)
 k_gm_flux_tile(DevGrid g, GmDev w, const double *__restrict__ X0, const double *__restrict__ X1, double *__restrict__ VDC0, double *__restrict__ VDC1) {
   __shared__ double fy_a[2][R][64], fy_b[2][R][64];
@@ -630,7 +633,7 @@ k_gm_flux_tile(DevGrid g, GmDev w, const double *__restrict__ X0, const double *
     const long long lev = (long long)b * g.n3 + (long long)(k - 1) * n2;
     const long long o = lev + p2;
     const int buf = k & 1;
-    {
+    if (ADD) {
       const int kq = (k < km) ? k : km - 1;                               // (k = km: computed at the level above and discarded)
       const long long oq = (long long)b * g.n3 + (long long)(kq - 1) * n2 + p2, ok = oq + n2;
       const double kmask = (kq < kmt) ? 1.0 : 0.0;

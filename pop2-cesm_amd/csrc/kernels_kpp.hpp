@@ -52,6 +52,9 @@ struct KppDev {
   const int *CHLI;
   int ksol;
   double *BO, *BOSOL;                // surface buoyancy forcing without / from the short-wave flux (lshort_wave: blmix needs both)
+  // nt > 2 (k_kpp_blmix<., ., ., true>): the bracket of salinity's non-local source, VDC2(k-1) GHAT(k-1) - VDC2(k) GHAT(k), stored wherever that
+  // source is, for the sources of the passive tracers (k_kpp_src_passive); nullptr otherwise
+  double *SRCX = nullptr;
 };
 
 constexpr double KPP_EPSSFC = 0.1, KPP_RIINFTY = 0.8, KPP_RRHO0 = 2.55, KPP_DSFMAX = 1.0, KPP_CSTAR = 10.0;
@@ -1094,7 +1097,8 @@ k_kpp_bldepth(DevGrid g, KppDev kp, const double *__restrict__ T, const double *
 // (the KBL stored with them; every level after a caller wrote KPP_SRC).  A level no lane of the wave has to touch is skipped
 // by the whole wave.  Same values as the streaming form (tests/test_gpu_parity.py).
 struct KppBlRaw { double visc, vd1, vd2, db; };
-template <bool PBC = false, bool SAME = false, bool SPARSE = false>
+// XS: also KppDev::SRCX (passive tracers)
+template <bool PBC = false, bool SAME = false, bool SPARSE = false, bool XS = false>
 __global__ void __launch_bounds__(POP_COL_THREADS)
 k_kpp_blmix(DevGrid g, StepParams sp, KppDev kp, const double *__restrict__ DBLOC, const double *__restrict__ STF1,
             const double *__restrict__ STF2, double *__restrict__ VISC, double *__restrict__ VDC1, double *__restrict__ VDC2,
@@ -1217,6 +1221,7 @@ k_kpp_blmix(DevGrid g, StepParams sp, KppDev kp, const double *__restrict__ DBLO
       if (__any(clr)) {       // +-0 below the boundary layer: stf / dz * (0 - 0); lanes above it are rewritten by part (2)
         const double dzk = (PBC && k > 1) ? dzt_at(k) : g.dz.u(k);
         SRC1[o] = stf1 / dzk * (0.0 - 0.0); SRC2[o] = stf2 / dzk * (0.0 - 0.0);
+        if (XS) kp.SRCX[o] = 0.0 - 0.0;
       }
     }
   } else {
@@ -1246,6 +1251,7 @@ k_kpp_blmix(DevGrid g, StepParams sp, KppDev kp, const double *__restrict__ DBLO
     const double dzk = (PBC && k > 1) ? dzt_at(k) : dz_k;
     const double p1 = (k == 1) ? -fl1 : 0.0 - fl1, p2 = (k == 1) ? -fl2 : 0.0 - fl2;
     SRC1[o] = stf1 / dzk * p1; SRC2[o] = stf2 / dzk * p2;
+    if (XS) kp.SRCX[o] = p2;
   };
   {
     KppBlRaw A = load(1), B;
@@ -1262,8 +1268,8 @@ k_kpp_blmix(DevGrid g, StepParams sp, KppDev kp, const double *__restrict__ DBLO
     const long long o = c.base3 + (long long)(k - 1) * n2;
     const double dzk = (PBC && k > 1) ? dzt_at(k) : g.dz[k];
     if (k == kbl) {     // first level below: its source still feels the flux through its upper face
-      if (k > 1) { SRC1[o] = stf1 / dzk * (flux1_prev - 0.0); SRC2[o] = stf2 / dzk * (flux2_prev - 0.0); }
-      else if (SPARSE) { SRC1[o] = stf1 / dzk * (-(0.0)); SRC2[o] = stf2 / dzk * (-(0.0)); }   // KBL = 1 (land): -(vd * ghat), ghat = 0
+      if (k > 1) { SRC1[o] = stf1 / dzk * (flux1_prev - 0.0); SRC2[o] = stf2 / dzk * (flux2_prev - 0.0); if (XS) kp.SRCX[o] = flux2_prev - 0.0; }
+      else if (SPARSE) { SRC1[o] = stf1 / dzk * (-(0.0)); SRC2[o] = stf2 / dzk * (-(0.0)); if (XS) kp.SRCX[o] = -(0.0); }   // KBL = 1 (land): -(vd * ghat), ghat = 0
       break;
     }
     double sig = (-zgrid[k] + 0.5 * hwide[k]) / hblt;
@@ -1293,8 +1299,8 @@ k_kpp_blmix(DevGrid g, StepParams sp, KppDev kp, const double *__restrict__ DBLO
     VDC1[vb + (long long)k * n2] = vd1;
     if (!SAME) VDC2[vb + (long long)k * n2] = vd2;
     const double fl1 = vd1 * ghat, fl2 = vd2 * ghat;
-    if (k == 1) { SRC1[o] = stf1 / dzk * (-fl1); SRC2[o] = stf2 / dzk * (-fl2); }
-    else { SRC1[o] = stf1 / dzk * (flux1_prev - fl1); SRC2[o] = stf2 / dzk * (flux2_prev - fl2); }
+    if (k == 1) { SRC1[o] = stf1 / dzk * (-fl1); SRC2[o] = stf2 / dzk * (-fl2); if (XS) kp.SRCX[o] = -fl2; }
+    else { SRC1[o] = stf1 / dzk * (flux1_prev - fl1); SRC2[o] = stf2 / dzk * (flux2_prev - fl2); if (XS) kp.SRCX[o] = flux2_prev - fl2; }
     flux1_prev = fl1; flux2_prev = fl2;
   }
 }
@@ -1637,6 +1643,7 @@ inline int kpp_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParam
   if (sel.wuk && tun_set(h.tun.kpp_ushear_margin)) g_kpp.wu_margin = h.tun.kpp_ushear_margin;
   g_kpp.CONVB = sel.convb ? KH.convb : nullptr;
   g_kpp.src_clear_all = s.src_clear_all;
+  g_kpp.SRCX = s.KPP_SRCX;
 
   // ---- pipeline: fork, shear, buoyancy (+ interior), depth march, interior, join, blmix, vvc, hmxl
   const hipStream_t side = sel.side ? KH.side : nullptr, su = side ? side : st;
@@ -1677,9 +1684,9 @@ inline int kpp_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParam
   } else if (KH.bck_on) hipLaunchKernelGGL(k_kpp_bckgrnd, GC, BC, 0, st, g, KH.bck, (int)g_kpp.vdc_same, VISC, s.VDC[0], s.VDC[1]);
   if (side) hipStreamWaitEvent(st, KH.ev_join, 0);
   else depth(st);
-  with_flags([&](auto PBC, auto SAME, auto SPARSE) {
-    hipLaunchKernelGGL((k_kpp_blmix<PBC.value, SAME.value, SPARSE.value>), GC, BC, 0, st, g, sp, g_kpp, (const double *)DBLOC, s.STF[0], s.STF[1], VISC, s.VDC[0], s.VDC[1], s.KPP_SRC[0], s.KPP_SRC[1], s.HBLT);
-  }, g.pbc, sel.same, sel.sparse);
+  with_flags([&](auto PBC, auto SAME, auto SPARSE, auto XS) {
+    hipLaunchKernelGGL((k_kpp_blmix<PBC.value, SAME.value, SPARSE.value, XS.value>), GC, BC, 0, st, g, sp, g_kpp, (const double *)DBLOC, s.STF[0], s.STF[1], VISC, s.VDC[0], s.VDC[1], s.KPP_SRC[0], s.KPP_SRC[1], s.HBLT);
+  }, g.pbc, sel.same, sel.sparse, g_kpp.SRCX != nullptr);
   // large grids: 64 x 4 patches (the row j + 1 of the four-point average is read by the same workgroup; 64 x 2 / 8 / 16 measured: vmix 7.54 / 7.65 / 7.97 ms against 7.57)
   launch_kpp_vvc(g, h, st, (const double *)VISC, s.VVC);
   if (h.c.kpp_ml_diagnostics == 1 && s.HMXL && s.HMXL_DR)   // DBSFC holds every level here (the diagnostics switch the on-demand march off)

@@ -19,6 +19,7 @@ struct MixState {        // per-step field pointers handed to the mixing kernels
   int *KBL = nullptr;        // KPP: level of the boundary-layer depth, paired with KPP_SRC (nullptr: the scheme's own array)
   int src_clear_all = 0;     // KPP: this set's KPP_SRC may hold non-zeros below its KBL (a caller wrote it): clear every level
   double *S3a, *S3b, *S3c, *S3d, *E3, *F3;   // 3-D scratch
+  double *KPP_SRCX = nullptr;   // KPP, nt > 2: KppDev::SRCX of this set of outputs
 };
 
 // ---- vmix_coeffs_rich (vmix_rich.F90:224-400), convection by diffusion

@@ -135,6 +135,11 @@ __device__ __forceinline__ int subm_last_level(const DevGrid &g, double mlmax) {
 #define POP_SUBM_TX 64
 #define POP_SUBM_TY 4
 // the tendency of both tracers on the physical cells of a 64 x 4 tile, added to GTK (submeso_flux)
+// TZ0 (passive tracers n >= 3 while Gent-McWilliams runs its cancellation branch): the vertical differences TZ are 0.  The reference forms
+// TZ(:,:,:,n) of T and S in tracer_diffs_and_isopyc_slopes (hmix_gm_submeso_share.F90:315-316) and of the tracers n > 2 inside hdifft_gm,
+// in the branch `.not. cancellation_occurs` only (hmix_gm.F90:1832, 1851-1852); with cancellation the array keeps the zeros it was
+// allocated with, and submeso_flux (mix_submeso.F90:851-884) reads those: its FX, FY vanish for n > 2, the vertical flux (from TX, TY) does not.
+template <bool TZ0 = false>
 __global__ void __launch_bounds__(POP_SUBM_TX * POP_SUBM_TY)
 k_submeso_flux(DevGrid g, SubmDev w, const double *__restrict__ X0, const double *__restrict__ X1) {
   __shared__ unsigned long long mlmax_bits;
@@ -178,12 +183,13 @@ k_submeso_flux(DevGrid g, SubmDev w, const double *__restrict__ X0, const double
     const double me = subm_mask(k, cc.kmt, ce.kmt), mn = subm_mask(k, cc.kmt, cn.kmt), mw = subm_mask(k, cw.kmt, cc.kmt), ms = subm_mask(k, cs.kmt, cc.kmt);
     const double pe = subm_mask(k + 1, cc.kmt, ce.kmt), pn = subm_mask(k + 1, cc.kmt, cn.kmt), pw = subm_mask(k + 1, cw.kmt, cc.kmt), ps = subm_mask(k + 1, cs.kmt, cc.kmt);
     const double kmask = (k < cc.kmt) ? 1.0 : 0.0;
+    auto tz = [&](const double *__restrict__ X, int kk, long long oo, long long nn) { return TZ0 ? 0.0 : subm_tz(X, kk, oo, nn); };
     auto one = [&](const double *__restrict__ X, double &fztop) {
-      const double tzc = subm_tz(X, k, o, n2), tzc1 = subm_tz(X, kp1, okp, n2);
-      const double fxe = cx * (w1t * bxe * gx * tzc + w1b * bxe * gx * tzc1 + e_t * bxw_e * gxe * subm_tz(X, k, o + 1, n2) + e_b * bxw_e * gxe * subm_tz(X, kp1, okp + 1, n2));
-      const double fxw = cxw * (w_t * bxe_w * gxw * subm_tz(X, k, o - 1, n2) + w_b * bxe_w * gxw * subm_tz(X, kp1, okp - 1, n2) + w1t * bxw * gx * tzc + w1b * bxw * gx * tzc1);
-      const double fyn = cy * (w1t * byn * gy * tzc + w1b * byn * gy * tzc1 + n_t * bys_n * gyn * subm_tz(X, k, o + nxb, n2) + n_b * bys_n * gyn * subm_tz(X, kp1, okp + nxb, n2));
-      const double fys = cys * (s_t * byn_s * gys * subm_tz(X, k, o - nxb, n2) + s_b * byn_s * gys * subm_tz(X, kp1, okp - nxb, n2) + w1t * bys * gy * tzc + w1b * bys * gy * tzc1);
+      const double tzc = tz(X, k, o, n2), tzc1 = tz(X, kp1, okp, n2);
+      const double fxe = cx * (w1t * bxe * gx * tzc + w1b * bxe * gx * tzc1 + e_t * bxw_e * gxe * tz(X, k, o + 1, n2) + e_b * bxw_e * gxe * tz(X, kp1, okp + 1, n2));
+      const double fxw = cxw * (w_t * bxe_w * gxw * tz(X, k, o - 1, n2) + w_b * bxe_w * gxw * tz(X, kp1, okp - 1, n2) + w1t * bxw * gx * tzc + w1b * bxw * gx * tzc1);
+      const double fyn = cy * (w1t * byn * gy * tzc + w1b * byn * gy * tzc1 + n_t * bys_n * gyn * tz(X, k, o + nxb, n2) + n_b * bys_n * gyn * tz(X, kp1, okp + nxb, n2));
+      const double fys = cys * (s_t * byn_s * gys * tz(X, k, o - nxb, n2) + s_b * byn_s * gys * tz(X, kp1, okp - nxb, n2) + w1t * bys * gy * tzc + w1b * bys * gy * tzc1);
       double td;
       if (k < km) {
         const double xc = X[o], xp = X[okp];

@@ -19,6 +19,7 @@
 #include "kernels_evp.hpp"
 #include "kernels_lwlim.hpp"
 #include "kernels_gm.hpp"
+#include "kernels_passive.hpp"
 #include "kernels_pcg_persist.hpp"
 #include <fcntl.h>
 #include <unistd.h>
@@ -90,7 +91,7 @@ int resolve(pop_ctx *c, const std::string &name, int tl, int n, double **ptr, lo
   if (name == "HLS_SUBM") return ok(c->subm.HLS, a2);
   if (name == "SUBM_BX") return (n == 0 || n == 1) ? ok(c->subm.B[n], a2) : 1;
   if (name == "SUBM_BY") return (n == 0 || n == 1) ? ok(c->subm.B[2 + n], a2) : 1;
-  if (name == "SUBM_ADV_TEND") return (n == 0 || n == 1) ? ok(c->subm.TD[n], a3) : 1;
+  if (name == "SUBM_ADV_TEND") return (n == 0 || n == 1) ? ok(c->subm.TD[n], a3) : (n >= 2 && n < c->h.nt) ? ok(c->PTD[n], a3) : 1;
   if (name == "USUBM") return ok(c->subm.US, a3);
   if (name == "VSUBM") return ok(c->subm.VS, a3);
   if (name == "WSUBM") return ok(c->subm.WS, a3);
@@ -101,7 +102,7 @@ int resolve(pop_ctx *c, const std::string &name, int tl, int n, double **ptr, lo
     if (name == "KVMIX") return ok(td.KV, a3);
     if (name == "KVMIX_M") return ok(td.KVM, a3);
   }
-  if (name == "GM_GTK") return (n == 0 || n == 1) ? ok(c->gm.GTK[n], a3) : 1;   // the mixing tendency the tracer right-hand side reads (hmix_tracer = 3)
+  if (name == "GM_GTK") return (n == 0 || n == 1) ? ok(c->gm.GTK[n], a3) : (n >= 2 && n < c->h.nt && c->h.c.hmix_tracer == 3) ? ok(c->PW[n], a3) : 1;   // the mixing tendency the tracer right-hand side reads (hmix_tracer = 3)
   if (name == "HDU") return ok(c->HDU, a3);                   // hmix_momentum = 3: Hdiff(U), Hdiff(V) of hdiffu_aniso at every level
   if (name == "HDV") return ok(c->HDV, a3);
   if (name == "F_PARA") return ok(c->FPARA, a3);              // ... with lvariable_hmix_aniso
@@ -116,7 +117,10 @@ int resolve(pop_ctx *c, const std::string &name, int tl, int n, double **ptr, lo
 // ---- what the entry points do with a named-field argument, stated once
 int unknown(pop_ctx *c, const char *what, const char *name) { c->err = std::string(what) + name; return 1; }
 int field_arg(pop_ctx *c, const char *name, int tl, int n, double **ptr, long long *count) {
-  return resolve(c, name, tl, n, ptr, count) ? unknown(c, "unknown field ", name) : 0;
+  if (!resolve(c, name, tl, n, ptr, count)) return 0;
+  for (const char *f : {"TRACER", "STF", "TFW", "KPP_SRC", "GM_GTK", "SUBM_ADV_TEND"})
+    if (!strcmp(name, f) && (n < 0 || n >= c->h.nt)) { c->err = std::string(name) + ": tracer index " + std::to_string(n) + " is outside 0 .. nt-1 = " + std::to_string(c->h.nt - 1); return 1; }
+  return unknown(c, "unknown field ", name);
 }
 int mask_arg(pop_ctx *c, const char *name, double **ptr) {   // optional: no name, no mask
   long long cnt;
@@ -322,7 +326,6 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
   if (hb) { c->err = c->h.err; return 1; }
   c->host_only = (flags & (POP_CREATE_HOST_ONLY | POP_CREATE_PLAN_ONLY)) != 0;
   if (c->host_only) return 0;
-  if (cfg->nt != 2) { c->err = "device kernels are built for nt = 2 (T,S) in this round"; return 1; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { c->err = "no HIP device available; libpop_amd has no CPU fallback"; return 1; }
   // stream priorities (r3, measured and left OFF: 84.7 ms against 83.2 without, profiles/r03_ab_stream_priority.txt): the launch stream above
@@ -622,6 +625,18 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
   }
   for (int n = 0; n < h.nt; ++n)
     if (dev_alloc(c, &c->STF[n], a2) || dev_alloc(c, &c->TFW[n], a2) || dev_alloc(c, &c->KPP_SRC[n], a3)) return 1;
+  if (h.nt > 2) {   // work fields of the passive tracers (pop_ctx.hpp)
+    if (cfg->hmix_tracer == 3 || cfg->hmix_tracer == 4) {
+      for (int n = 2; n < h.nt; ++n) if (dev_alloc(c, &c->PW[n], a3)) return 1;
+      if ((h.nt & 1) && dev_alloc(c, &c->PWX, a3)) return 1;
+    }
+    if (cfg->tadvect == 3 && (dev_alloc(c, &c->PL[0], a3) || dev_alloc(c, &c->PL[1], a3))) return 1;
+    if (cfg->lsubmesoscale_mixing && cfg->submeso_diag) {
+      for (int n = 2; n < h.nt; ++n) if (dev_alloc(c, &c->PTD[n], a3)) return 1;
+      if ((h.nt & 1) && dev_alloc(c, &c->PTDX, a3)) return 1;
+    }
+    if (cfg->vmix_choice == 3 && dev_alloc(c, &c->KPPX, a3)) return 1;
+  }
   // KPP without double diffusion gives both tracer classes the same diffusivity, value for value (vmix_kpp.F90 ri_iwmix: VDC(:,:,k,2) =
   // VDC(:,:,k,1); blmix applies the same shape function to both): one array then serves both, so the KPP kernels write it once and
   // the tracer kernels find the second read in cache.  pop_get_field("VDC", n) returns it for n = 0 and 1.
@@ -915,6 +930,7 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
   // mixed-layer-depth diagnostics the look-ahead writes a second pair HMXL / HMXL_DR that is swapped in with the rest)
   if (c->ahead_enabled) {
     for (int n = 0; n < 2; ++n) if (dev_alloc(c, &c->KPPa[n], a3)) return 1;
+    if (h.nt > 2 && dev_alloc(c, &c->KPPXa, a3)) return 1;
     if (dev_alloc(c, &c->VDCa[0], (size_t)(h.km + 2) * a2)) return 1;
     if (c->vdc_shared) c->VDCa[1] = c->VDCa[0];
     else if (dev_alloc(c, &c->VDCa[1], (size_t)(h.km + 2) * a2)) return 1;
@@ -1199,10 +1215,8 @@ int pop_write_restart(pop_ctx *c, const char *path) {
       {"nsteps_this_interval", "int", std::to_string(c->nsteps_this_interval)},   // extension: exact restart inside an averaging interval
       {"eod_last", "log", c->eod ? "T" : "F"},   // restart.F90:346: the step that has just finished ended a day (what the next step's eod_last will be, time_management.F90:1809)
     };
-    if (h.c.tmix_opt == 3) {
-      static const char *tn[2] = {"TEMP", "SALT"};
-      for (int n = 0; n < 2; ++n) if (c->rf_S_prev_valid[n]) at.push_back({std::string("rf_S_prev_") + tn[n], "r8", fmt_r8(c->rf_S_prev[n])});
-    }
+    if (h.c.tmix_opt == 3)
+      for (int n = 0; n < h.nt; ++n) if (c->rf_S_prev_valid[n]) at.push_back({"rf_S_prev_" + restart_tracer_name(h, n), "r8", fmt_r8(c->rf_S_prev[n])});
     if (restart_write_header(h, path, at, fields, c->err)) return 1;
   }
   const int fd = open(path, O_WRONLY | O_CREAT, 0644);
@@ -1291,9 +1305,8 @@ int pop_read_restart(pop_ctx *c, const char *path, int flags) {
     HIPCHK(c, hipMemcpy(c->gm.KV, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice));
   }
   if (h.c.tmix_opt == 3) {
-    static const char *tn[2] = {"TEMP", "SALT"};
-    for (int n = 0; n < 2; ++n) {
-      const std::string key = std::string("rf_S_prev_") + tn[n];
+    for (int n = 0; n < h.nt; ++n) {
+      const std::string key = "rf_S_prev_" + restart_tracer_name(h, n);
       c->rf_S_prev_valid[n] = g.count(key) != 0;                     // extract_attrib_file(..., from_file=rf_S_prev_valid) :516-519
       if (c->rf_S_prev_valid[n]) c->rf_S_prev[n] = strtod(g[key].c_str(), nullptr);
     }
@@ -1358,10 +1371,24 @@ static MixState kpp_mix_state(pop_ctx *c, int slot, bool into_alt) {
   ms.VVC = into_alt ? c->VVCa : c->VVC; ms.SHF_QSW = c->SHF_QSW; ms.HBLT = into_alt ? c->HBLTa : c->HBLT;
   ms.HMXL = (into_alt && c->HMXLa) ? c->HMXLa : c->HMXL; ms.HMXL_DR = (into_alt && c->HMXL_DRa) ? c->HMXL_DRa : c->HMXL_DR;
   ms.KBL = into_alt ? c->KBLa : c->KBL;
+  ms.KPP_SRCX = into_alt ? c->KPPXa : c->KPPX;
   ms.src_clear_all = (into_alt ? c->src_dirty_alt : c->src_dirty) ? 1 : 0;
   (into_alt ? c->src_dirty_alt : c->src_dirty) = false;   // the evaluation that follows clears the set
   ms.S3a = c->S3a; ms.S3b = c->S3b; ms.S3c = c->S3c; ms.S3d = c->S3d; ms.E3 = c->E3; ms.F3 = c->F3;
   return ms;
+}
+// KPP's non-local source of the passive tracers from the bracket k_kpp_blmix left in KPPX (kernels_passive.hpp), on the launch stream
+// once the coefficients of this step are in place -- computed here or swapped in from the look-ahead
+static int phase_kpp_src_passive(pop_ctx *c) {
+  for (int n = 2; n < c->h.nt; n += 2) {
+    const int np = std::min(2, c->h.nt - n);
+    KppSrcPassiveArgs a{};
+    for (int s = 0; s < np; ++s) { a.STF[s] = c->STF[n + s]; a.SRC[s] = c->KPP_SRC[n + s]; }
+    const dim3 G((c->g.n2 + 255) / 256, c->g.km, c->g.nblocks * np);
+    with_flags([&](auto PBC) { hipLaunchKernelGGL(k_kpp_src_passive<PBC.value>, G, dim3(256), 0, c->stream, c->g, (const double *)c->KPPX, a, np); }, c->g.pbc);
+  }
+  HIPCHK(c, hipGetLastError());
+  return 0;
 }
 static int phase_vmix(pop_ctx *c) {
   const pop_config &cf = c->h.c;
@@ -1375,12 +1402,14 @@ static int phase_vmix(pop_ctx *c) {
       for (int n = 0; n < 2; ++n) { std::swap(c->VDC[n], c->VDCa[n]); std::swap(c->KPP_SRC[n], c->KPPa[n]); }
       std::swap(c->VVC, c->VVCa); std::swap(c->HBLT, c->HBLTa); std::swap(c->KBL, c->KBLa); std::swap(c->src_dirty, c->src_dirty_alt);
       if (c->HMXLa) { std::swap(c->HMXL, c->HMXLa); std::swap(c->HMXL_DR, c->HMXL_DRa); }
-      return 0;
+      std::swap(c->KPPX, c->KPPXa);
+      return c->h.nt > 2 ? phase_kpp_src_passive(c) : 0;
     }
     if (ahead_cancel(c)) return 1;
     const MixState ms = kpp_mix_state(c, c->mixt, false);
     if (mix_vmix_coeffs(c->h, c->g, sp, c->mix, ms, c->stream, c->err)) return 1;
     c->kpp_src_user = false;
+    if (cf.vmix_choice == 3 && c->h.nt > 2) return phase_kpp_src_passive(c);
   }
   return 0;
 }
@@ -1404,34 +1433,67 @@ static int kpp_look_ahead(pop_ctx *c) {
 }
 // lsubmesoscale_mixing (horizontal_mix.F90:566-581, mix_submeso.F90:341-1005): the column fields of submeso_sf from the mix-time tracers and this
 // step's HMXL, then the tendency of submeso_flux added to GTK, which k_gm_flux has just written on the same stream
-static int phase_submeso(pop_ctx *c, const double *T, const double *S) {
+static SubmDev submeso_dev(pop_ctx *c) {
   SubmDev W = c->subm;
   W.HMXL = (c->h.c.vmix_choice == 3) ? c->HMXL : nullptr;    // ML_DEPTH = HMXL | zw(1) (:424-426)
   W.grav = step_params(c).grav; W.sqrt_grav = std::sqrt(W.grav);
-  const dim3 G2((c->g.n2 + 255) / 256, c->g.nblocks);
-  hipLaunchKernelGGL(k_submeso_column, G2, dim3(256), 0, c->stream, c->g, W, T, S);
+  return W;
+}
+// submeso_flux of the tracer pair (X0, X1) added to W.GTK, from the column fields k_submeso_column formed
+static int submeso_flux_launch(pop_ctx *c, const SubmDev &W, const double *X0, const double *X1, bool tz0 = false) {
   if (W.TD[0]) {   // the levels below the march hold 0
     const size_t bytes = (size_t)c->g.n3 * c->g.nblocks * sizeof(double);
     HIPCHK(c, hipMemsetAsync(W.TD[0], 0, bytes, c->stream));
     HIPCHK(c, hipMemsetAsync(W.TD[1], 0, bytes, c->stream));
   }
   const dim3 GT(((c->g.nxb + POP_SUBM_TX - 1) / POP_SUBM_TX) * ((c->g.nyb + POP_SUBM_TY - 1) / POP_SUBM_TY), c->g.nblocks);
-  hipLaunchKernelGGL(k_submeso_flux, GT, dim3(POP_SUBM_TX, POP_SUBM_TY), 0, c->stream, c->g, W, T, S);
+  with_flags([&](auto TZ0) { hipLaunchKernelGGL(k_submeso_flux<TZ0.value>, GT, dim3(POP_SUBM_TX, POP_SUBM_TY), 0, c->stream, c->g, W, X0, X1); }, tz0);
+  return 0;
+}
+static int phase_submeso(pop_ctx *c, const double *T, const double *S) {
+  const SubmDev W = submeso_dev(c);
+  const dim3 G2((c->g.n2 + 255) / 256, c->g.nblocks);
+  hipLaunchKernelGGL(k_submeso_column, G2, dim3(256), 0, c->stream, c->g, W, T, S);
+  if (submeso_flux_launch(c, W, T, S)) return 1;
   if (W.US) hipLaunchKernelGGL(k_submeso_vel, G2, dim3(256), 0, c->stream, c->g, W);
   HIPCHK(c, hipGetLastError());
   return 0;
 }
 // hmix_tracer = 3 (horizontal_mix.F90:549-554, hmix_gm.F90:1102-2226): slopes and tapered diffusivities of the mix-time tracers, the
 // isopycnal part added to VDC (after vmix_coeffs, before the tracer right-hand side reads it), and the tendency GTK of both tracers
-static int phase_hmix_gm(pop_ctx *c) {
-  const double *T = c->TR[0][c->mixt], *S = c->TR[1][c->mixt];
+// the tendency of the tracer pair (X0, X1) into G.GTK from the slopes and diffusivities in G; add: with the isopycnal part added to VDC
+static void gm_flux_launch(pop_ctx *c, const GmDev &G, const double *X0, const double *X1, bool add) {
+  const dim3 G3((c->g.n2 + 255) / 256, c->g.km, c->g.nblocks);
+  const StepParams sp = step_params(c);
+  double *v1 = (sp.nvdc == 2 && c->VDC[1] != c->VDC[0]) ? c->VDC[1] : nullptr;   // one shared array is added to once
+  if (!tun_off(c->h.tun.gm_flux_tile) && (G.cancellation || G.SF[0])) {
+    // straight-line flux functions, every horizontal face flux formed once (64 x 4 patches computing 63 x 3 cells); pop_tuning.gm_flux_tile = 0,
+    // or the stream-function terms not stored (gm_sf_stored = 0): the cell-by-cell kernel
+    const int R = (c->h.tun.gm_flux_tile == 4) ? 4 : 8;     // rows of the patch: 64 x 8 computing 63 x 7 cells (gm_flux_tile = 4: 64 x 4, measured 2 % of the step slower)
+    const dim3 GT(((c->g.nxb + 62) / 63) * ((c->g.nyb + R - 2) / (R - 1)), (c->g.km + POP_GM_KC - 1) / POP_GM_KC, G3.z);
+    with_value<4, 8>(R, [&](auto RV) {
+      with_flags([&](auto CANC, auto ADD) {
+        hipLaunchKernelGGL((k_gm_flux_tile<RV.value, CANC.value, ADD.value>), GT, dim3(64, RV.value), 0, c->stream, c->g, G, X0, X1, c->VDC[0], v1);
+      }, G.cancellation, add);
+    });
+  } else
+  with_flags([&](auto ADD) {
+    hipLaunchKernelGGL(k_gm_flux<ADD.value>, dim3(G3.x, (c->g.km + POP_GM_KC - 1) / POP_GM_KC, G3.z), dim3(256), 0, c->stream, c->g, G, X0, X1, c->VDC[0], v1);
+  }, add);
+}
+static GmDev gm_dev(pop_ctx *c) {
   GmDev G = c->gm;
   G.HBLT = (c->h.c.vmix_choice == 3) ? c->HBLT : nullptr;            // BL_DEPTH = KPP_HBLT | zw(1) (:1210-1212)
+  if (G.tlt) G.HMXL = (c->h.c.vmix_choice == 3) ? c->HMXL : nullptr;
+  return G;
+}
+static int phase_hmix_gm(pop_ctx *c) {
+  const double *T = c->TR[0][c->mixt], *S = c->TR[1][c->mixt];
+  const GmDev G = gm_dev(c);
   const dim3 G3((c->g.n2 + 255) / 256, c->g.km, c->g.nblocks);
   const dim3 G2(G3.x, c->g.nblocks);
   const bool kappa_now = G.KV && (c->h.c.gm_kappa_freq == 1 || c->nsteps_total == 1 || (c->h.c.gm_kappa_freq == 2 && c->eod_last));   // compute_kappa (:1258-1332): the first step of the run, or every step
   if (G.tlt) {   // :1222-1250, then the tapering with the layer's rules, then merged_streamfunction / apply_vertical_profile (:1668-1674)
-    G.HMXL = (c->h.c.vmix_choice == 3) ? c->HMXL : nullptr;
     hipLaunchKernelGGL(k_gm_diabatic_depth, G2, dim3(256), 0, c->stream, c->g, G);
     hipLaunchKernelGGL(k_gm_coeffs<1>, G3, dim3(256), 0, c->stream, c->g, G, T, S);
     hipLaunchKernelGGL(k_gm_transition_layer, G2, dim3(256), 0, c->stream, c->g, G);
@@ -1442,22 +1504,9 @@ static int phase_hmix_gm(pop_ctx *c) {
     if (kappa_now) hipLaunchKernelGGL(k_gm_kappa_vertical, G2, dim3(256), 0, c->stream, c->g, G, T, S, step_params(c).grav);
     hipLaunchKernelGGL(k_gm_coeffs<0>, G3, dim3(256), 0, c->stream, c->g, G, T, S);
   }
-  const StepParams sp = step_params(c);
-  double *v1 = (sp.nvdc == 2 && c->VDC[1] != c->VDC[0]) ? c->VDC[1] : nullptr;   // one shared array is added to once
   if (G.SF[0]) hipLaunchKernelGGL(k_gm_sf, G3, dim3(256), 0, c->stream, c->g, G);   // without cancellation: SF_SLX, SF_SLY once per half cell
   if (G.UISOP) hipLaunchKernelGGL(k_gm_bolus, G2, dim3(256), 0, c->stream, c->g, G);   // diag_gm_bolus
-  if (!tun_off(c->h.tun.gm_flux_tile) && (G.cancellation || G.SF[0])) {
-    // straight-line flux functions, every horizontal face flux formed once (64 x 4 patches computing 63 x 3 cells); pop_tuning.gm_flux_tile = 0,
-    // or the stream-function terms not stored (gm_sf_stored = 0): the cell-by-cell kernel
-    const int R = (c->h.tun.gm_flux_tile == 4) ? 4 : 8;     // rows of the patch: 64 x 8 computing 63 x 7 cells (gm_flux_tile = 4: 64 x 4, measured 2 % of the step slower)
-    const dim3 GT(((c->g.nxb + 62) / 63) * ((c->g.nyb + R - 2) / (R - 1)), (c->g.km + POP_GM_KC - 1) / POP_GM_KC, G3.z);
-    with_value<4, 8>(R, [&](auto RV) {
-      with_flags([&](auto CANC) {
-        hipLaunchKernelGGL((k_gm_flux_tile<RV.value, CANC.value>), GT, dim3(64, RV.value), 0, c->stream, c->g, G, T, S, c->VDC[0], v1);
-      }, G.cancellation);
-    });
-  } else
-  hipLaunchKernelGGL(k_gm_flux, dim3(G3.x, (c->g.km + POP_GM_KC - 1) / POP_GM_KC, G3.z), dim3(256), 0, c->stream, c->g, G, T, S, c->VDC[0], v1);
+  gm_flux_launch(c, G, T, S, true);
   HIPCHK(c, hipGetLastError());
   if (c->h.c.lsubmesoscale_mixing) return phase_submeso(c, T, S);
   return 0;
@@ -1538,6 +1587,71 @@ static int phase_tracer_rhs(pop_ctx *c, bool fwd = false) {
   with_flags([&](auto GM, auto UP3, auto PBC) {
     hipLaunchKernelGGL((k_tracer_rhs<GM.value, UP3.value, PBC.value>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, sp, a);
   }, gm, up3, c->g.pbc);
+  return 0;
+}
+// tracer_update (baroclinic.F90:1981-2300) for the passive tracers n = 3 .. nt, a pair per launch and one launch of one for an odd count,
+// on the launch stream after the (T, S) right-hand side: k_tracer_rhs<., ., ., NP, true>.  Every tracer uses cfg.tadvect and the (T, S)
+// mixing scheme; the schemes that form a field per tracer ahead of the right-hand side run their (T, S) kernels once more per pair into
+// the passive work fields, from the flux velocities (lw_lim), slopes and diffusivities (Gent-McWilliams) and stream function (submeso)
+// already formed for this step.  No predictor follows (impvmixt(.., 1, 2, ..), baroclinic.F90:885-893, is for T and S).
+static int phase_passive_rhs(pop_ctx *c) {
+  const int nt = c->h.nt;
+  if (nt <= 2) return 0;
+  const pop_config &cf = c->h.c;
+  const StepParams sp = step_params(c);
+  const bool gm = cf.hmix_tracer == 3, up3 = cf.tadvect == 2;
+  for (int n = 2; n < nt; n += 2) {
+    const int np = std::min(2, nt - n);
+    const int m[2] = {n, n + np - 1};   // slot -> tracer; with one tracer slot 1 repeats it as an input and has spare outputs
+    const double *X0 = c->TR[m[0]][c->mixt], *X1 = c->TR[m[1]][c->mixt];
+    double *W[2] = {c->PW[n], np == 2 ? c->PW[n + 1] : c->PWX};
+    TracerRhsArgs a{};
+    if (gm) {
+      GmDev G = gm_dev(c);
+      G.GTK[0] = W[0]; G.GTK[1] = W[1];
+      gm_flux_launch(c, G, X0, X1, false);
+      if (cf.lsubmesoscale_mixing) {
+        SubmDev S = submeso_dev(c);
+        S.GTK[0] = W[0]; S.GTK[1] = W[1];
+        if (S.TD[0]) { S.TD[0] = c->PTD[n]; S.TD[1] = np == 2 ? c->PTD[n + 1] : c->PTDX; }
+        if (submeso_flux_launch(c, S, X0, X1, G.cancellation != 0)) return 1;   // k_submeso_flux<TZ0>: what the reference's TZ holds for n > 2
+      }
+      a.HDT[0] = W[0]; a.HDT[1] = W[1];
+    }
+    if (cf.hmix_tracer == 4 && mix_hdifft_del4(c->h, c->g, sp, c->mix, X0, X1, W[0], W[1], nullptr, nullptr, c->stream, c->err)) return 1;
+    if (cf.tadvect == 3) {   // the three direction passes of phase_advt_lw_lim on this pair; UTE, VTN, WTKB are those of the step
+      LwDev L = c->lw;
+      L.XOUT[0] = c->PL[0]; L.XOUT[1] = c->PL[1];
+      const dim3 G3((c->g.n2 + 255) / 256, c->g.km, c->g.nblocks * 2);
+      with_flags([&](auto PBC) {
+        hipLaunchKernelGGL(k_lw_z<PBC.value>, G3, dim3(256), 0, c->stream, c->g, L, X0, X1, c->c2dtt);
+        hipLaunchKernelGGL(k_lw_x<PBC.value>, G3, dim3(256), 0, c->stream, c->g, L, X0, X1, c->c2dtt);
+        hipLaunchKernelGGL(k_lw_y<PBC.value>, G3, dim3(256), 0, c->stream, c->g, L, X0, X1, c->c2dtt);
+      }, c->g.pbc);
+      a.LTK[0] = c->PL[0]; a.LTK[1] = c->PL[1];
+    }
+    for (int s = 0; s < 2; ++s) {
+      const int t = m[s];
+      a.TCUR[s] = c->TR[t][c->curt]; a.TOLD[s] = c->TR[t][c->oldt]; a.TMIX[s] = c->TR[t][c->mixt]; a.TNEW[s] = c->TR[t][c->newt];
+      a.VDC[s] = c->VDC[sp.nvdc == 2 ? 1 : 0];   // VDC(:,:,:,min(n, size(VDC,4))): salinity's, or the only one (vertical_mix.F90:1260)
+      a.KPP_SRC[s] = c->KPP_SRC[t]; a.STF[s] = c->STF[t]; a.TFW[s] = c->TFW[t];
+      a.isrc[s] = c->h.iage[t] ? 1.0 / (365.0 * 86400.0) : 0.0;   // c1 / seconds_in_year (iage_mod.F90:352-353)
+    }
+    if (cf.hmix_tracer == 4) { a.TMIX[0] = W[0]; a.TMIX[1] = W[1]; }   // del4: second Laplacian acts on D2T
+    a.UCUR = c->U[c->curt]; a.VCUR = c->V[c->curt]; a.DH = c->DH; a.PCUR = c->PS[c->curt]; a.POLD = c->PS[c->oldt];
+    a.c2dtt = c->c2dtt; a.use_kpp_src = (cf.vmix_choice == 3);
+    if (up3) a.up = c->upw3;
+    with_flags([&](auto GM, auto UP3, auto PBC, auto TWO) {
+      hipLaunchKernelGGL((k_tracer_rhs<GM.value, UP3.value, PBC.value, TWO.value ? 2 : 1, true>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, sp, a);
+    }, gm, up3, c->g.pbc, np == 2);
+  }
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+// the surface reset of the tracer modules (reset_passive_tracers; ideal age: TRACER(:,:,1) = 0 over the whole slab, iage_mod.F90:386-415)
+static int passive_reset(pop_ctx *c, int slot) {
+  for (int n = 2; n < c->h.nt; ++n)
+    if (c->h.iage[n]) HIPCHK(c, hipMemset2DAsync(c->TR[n][slot], (size_t)c->g.n3 * sizeof(double), 0, (size_t)c->g.n2 * sizeof(double), c->g.nblocks, c->stream));
   return 0;
 }
 static ImpvmixtArgs impvmixt_args(pop_ctx *c, const double *psfc) {
@@ -1645,7 +1759,19 @@ static int phase_correct(pop_ctx *c) {
   if (!reg_kernel && c->ahead_valid) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ahead, 0));
   if (sp.pavg) launch_impvmixt<1, false, true>(c->g, sp, impvmixt_args(c, c->PS[c->newt]), grid_cols(c), c->stream, c->reg_thomas_t, c->h.tun.thomas_pair);
   else launch_impvmixt<0, true, true>(c->g, sp, impvmixt_args(c, c->PS[c->newt]), grid_cols(c), c->stream, c->reg_thomas_t, c->h.tun.thomas_pair);
-  return 0;
+  // passive tracers: TNEW(1) -= TOLD(1) (PSURF(new) - PSURF(old)) / (grav dz(1)) and the standard solve with PSURF(new) on the left-hand
+  // side, under pressure averaging (baroclinic.F90:1303-1321) as without it (:1328-1344: mixtime = oldtime on a leapfrog step, curtime on
+  // the Euler step, which is what PMIX is) -- the all-tracer form k_impvmixt<0, PRE>, a pair per launch; then reset_passive_tracers (:1458-1460)
+  for (int n = 2; n < c->h.nt; n += 2) {
+    ImpvmixtArgs a = impvmixt_args(c, c->PS[c->newt]);
+    a.nfirst = 1; a.nlast = std::min(2, c->h.nt - n);
+    for (int s = 0; s < a.nlast; ++s) {
+      a.TNEW[s] = c->TR[n + s][c->newt]; a.TOLD[s] = c->TR[n + s][c->oldt]; a.TCUR[s] = c->TR[n + s][c->curt];
+      a.VDC[s] = c->VDC[sp.nvdc == 2 ? 1 : 0];
+    }
+    launch_impvmixt<0, true, false>(c->g, sp, a, grid_cols(c), c->stream, c->reg_thomas_t, c->h.tun.thomas_pair);
+  }
+  return passive_reset(c, c->newt);
 }
 static int phase_add_btrop(pop_ctx *c, hipStream_t st = nullptr) {
   hipLaunchKernelGGL(k_add_barotropic, grid_3d(c), dim3(256), 0, st ? st : c->stream, c->g, c->U[c->newt], c->V[c->newt], c->UB[c->newt], c->VB[c->newt]);
@@ -1672,7 +1798,7 @@ int pop_baroclinic_driver(pop_ctx *c) {
   if (fork) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2t, 0));
   if (!tr_side && phase_hmix_tracer(c)) return 1;   // Gent-McWilliams reads and adds to the coefficients vmix just formed
   const bool fwd = sp.pavg && tracer_fwd_fused(c);
-  if (phase_tracer_rhs(c, fwd)) return 1;
+  if (phase_tracer_rhs(c, fwd) || phase_passive_rhs(c)) return 1;
   // several ranks: the exchange of the new tracers' ghost rows runs on the communication stream while the launch stream
   // forms the density and the momentum right-hand side of every tile that reads no ghost row of another rank; the first
   // and last tile rows follow once the rows have arrived (same kernels on disjoint tiles: bitwise the serial result)
@@ -1869,24 +1995,31 @@ static int step_rf(pop_ctx *c) {
   double *WORKN[2] = {c->W3, c->W4}, *WB = c->UH;          // 2-D work arrays free at this point of the step
   RfTracerArgs ta{};
   RfSurfArgs sa{};
-  for (int n = 0; n < 2; ++n) {
-    ta.TO[n] = c->TR[n][o]; ta.TC[n] = c->TR[n][cu]; ta.TN[n] = c->TR[n][nw]; ta.WORKN[n] = WORKN[n];
-    sa.TO[n] = c->TR[n][o]; sa.TC[n] = c->TR[n][cu]; sa.TN[n] = c->TR[n][nw]; sa.WORKN[n] = WORKN[n];
-  }
   sa.PO = c->PS[o]; sa.PC = c->PS[cu]; sa.PN = c->PS[nw];
   const dim3 GC = grid_cols(c);
-  hipLaunchKernelGGL(k_rf_tracer_interior, dim3(GC.x, GC.y, nt), dim3(POP_COL_THREADS), 0, c->stream, c->g, p, ta);
   double svol[MAXNT] = {};
   auto sum = [&](const double *F, const double *mask, double *result) { return masked_sum(c, F, nullptr, mask, false, result); };
-  for (int n = 0; n < nt; ++n) if (sum(WORKN[n], nullptr, &svol[n])) return 1;
-  hipLaunchKernelGGL(k_rf_surface, dim3((unsigned)((a2 + 255) / 256), nt), dim3(256), 0, c->stream, c->g, p, sa);
-  for (int n = 0; n < nt; ++n) { double s1; if (sum(WORKN[n], nullptr, &s1)) return 1; svol[n] = svol[n] + s1; }
+  // a pair of tracers per pass through the two work arrays: (T, S), then the passive tracers; every pass reads PSURF as it is before its filter
+  for (int n0 = 0; n0 < nt; n0 += 2) {
+    const int np = std::min(2, nt - n0);
+    for (int s = 0; s < np; ++s) {
+      const int n = n0 + s;
+      ta.TO[s] = c->TR[n][o]; ta.TC[s] = c->TR[n][cu]; ta.TN[s] = c->TR[n][nw]; ta.WORKN[s] = WORKN[s];
+      sa.TO[s] = c->TR[n][o]; sa.TC[s] = c->TR[n][cu]; sa.TN[s] = c->TR[n][nw]; sa.WORKN[s] = WORKN[s];
+    }
+    hipLaunchKernelGGL(k_rf_tracer_interior, dim3(GC.x, GC.y, np), dim3(POP_COL_THREADS), 0, c->stream, c->g, p, ta);
+    for (int s = 0; s < np; ++s) if (sum(WORKN[s], nullptr, &svol[n0 + s])) return 1;
+    hipLaunchKernelGGL(k_rf_surface, dim3((unsigned)((a2 + 255) / 256), np), dim3(256), 0, c->stream, c->g, p, sa);
+    for (int s = 0; s < np; ++s) { double s1; if (sum(WORKN[s], nullptr, &s1)) return 1; svol[n0 + s] = svol[n0 + s] + s1; }
+  }
   hipLaunchKernelGGL(k_rf_psurf, dim3((unsigned)((a2 + 255) / 256)), dim3(256), 0, c->stream, c->g, p, (const double *)c->PS[o], c->PS[cu], c->PS[nw], WB);
   double rf_sump;
   if (sum(WB, c->g.CONSTNT, &rf_sump)) return 1;      // MASK_TRBUDGET(:,:,1) = (KMT >= 1) = CONSTNT
   rf_sump = rf_sump / h.bgtarea_t_1;
   hipLaunchKernelGGL(k_rf_psurf_adjust, dim3((unsigned)((a2 + 255) / 256)), dim3(256), 0, c->stream, c->g, p, rf_sump, c->PS[cu], c->PS[nw],
                      c->TR[0][cu], c->TR[0][nw], c->TR[1][cu], c->TR[1][nw], WB);
+  for (int n = 2; n < nt; ++n)
+    hipLaunchKernelGGL(k_rf_surface_div, dim3((unsigned)((a2 + 255) / 256)), dim3(256), 0, c->stream, c->g, p, (const double *)c->PS[cu], (const double *)c->PS[nw], c->TR[n][cu], c->TR[n][nw]);
   double vsurf, vsurf_oo;
   if (sum(WB, c->g.CONSTNT, &vsurf) || sum(WB, c->g.RCALCT, &vsurf_oo)) return 1;
   const double rf_ocean_norm = h.open_ocean_volume_2_km + vsurf_oo;   // fully coupled normalisation (:1166-1172)
@@ -1897,6 +2030,8 @@ static int step_rf(pop_ctx *c) {
     hipLaunchKernelGGL(k_rf_conserve, grid_3d(c), dim3(256), 0, c->stream, c->g, p, factor * h.robert_newtime, factor * h.robert_curtime,
                        c->TR[n][cu], c->TR[n][nw]);
   }
+  // reset_passive_tracers on TRACER(cur) after the filter, on TRACER(new) when it was filtered too (step_mod.F90:1259-1279)
+  if (passive_reset(c, cu) || (h.rf_nonzero_newtime && passive_reset(c, nw))) return 1;
   HIPCHK(c, hipMemcpyAsync(c->FW_OLD, c->FW, a2 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   launch_state3d(c->g, (const double *)c->TR[0][cu], (const double *)c->TR[1][cu], c->RHO[cu], c->stream);
   launch_state3d(c->g, (const double *)c->TR[0][nw], (const double *)c->TR[1][nw], c->RHO[nw], c->stream);
@@ -1930,6 +2065,13 @@ int pop_step_tail(pop_ctx *c) {
     a.UBN = c->UB[nw]; a.VBN = c->VB[nw]; a.GXN = c->GX[nw]; a.GYN = c->GY[nw]; a.PN = c->PS[nw]; a.FW = c->FW;
     for (int n = 0; n < 2; ++n) { a.T1O[n] = c->TR[n][o]; a.T1C[n] = c->TR[n][cu]; a.T1N[n] = c->TR[n][nw]; }
     a.dz1 = c->h.dz[1]; a.grav = GRAV;
+    for (int n = 2; n < c->h.nt; n += 2) {   // passive tracers, ahead of k_avg2d, which averages PSURF in place
+      const int np = std::min(2, c->h.nt - n);
+      AvgPassiveArgs pa{};
+      for (int s = 0; s < np; ++s) { pa.TO[s] = c->TR[n + s][o]; pa.TC[s] = c->TR[n + s][cu]; pa.TN[s] = c->TR[n + s][nw]; }
+      pa.PO = c->PS[o]; pa.PC = c->PS[cu]; pa.PN = c->PS[nw]; pa.dz1 = a.dz1; pa.grav = a.grav;
+      hipLaunchKernelGGL(k_avg_passive, dim3((c->g.n2 + 255) / 256, km, c->g.nblocks * np), dim3(256), 0, c->stream, c->g, pa, np);
+    }
     hipLaunchKernelGGL(k_avg2d, dim3(col_grid(c->g, 256), c->g.nblocks), dim3(256), 0, c->stream, c->g, a);
     Avg3dArgs b{};
     b.UO = c->U[o]; b.UC = c->U[cu]; b.VO = c->V[o]; b.VC = c->V[cu]; b.RO = c->RHO[o]; b.RC = c->RHO[cu]; b.UN = c->U[nw]; b.VN = c->V[nw];
@@ -2436,6 +2578,22 @@ int pop_init_kpp_bckgrnd(pop_ctx *c, const pop_kpp_bckgrnd_nml *nml) {
   return 0;
 }
 
+// ---- ideal age (iage_mod.F90): tracer n (1-based, 3 .. nt) gets the module's interior source and surface reset, and starts from 0
+int pop_init_iage(pop_ctx *c, int n) {
+  if (!c) return 1;
+  if (c->h.plan_only) { c->err = "pop_init_iage: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+  if (n < 3 || n > c->h.nt) { c->err = "pop_init_iage: n is the 1-based number of a passive tracer, 3 .. nt = " + std::to_string(c->h.nt) + " (got " + std::to_string(n) + ")"; return 1; }
+  if (c->h.iage[n - 1]) { c->err = "pop_init_iage: tracer " + std::to_string(n) + " is ideal age already (once per tracer)"; return 1; }
+  if (c->ran || c->nsteps_total > 0) { c->err = "pop_init_iage: a step or a phase has already run (call it right after pop_create)"; return 1; }
+  if (!c->host_only) {   // init_iage with init_iage_option 'startup' (iage_mod.F90:176-180): 0 at every time level
+    const size_t bytes = (size_t)c->g.n3 * c->g.nblocks * sizeof(double);
+    for (int t = 0; t < 3; ++t) HIPCHK(c, hipMemsetAsync(c->TR[n - 1][t], 0, bytes, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  c->h.iage[n - 1] = true;
+  return 0;
+}
+
 int pop_timers_reset(pop_ctx *c) { c->timers.clear(); c->timing = true; return 0; }
 int pop_timer_ms(pop_ctx *c, const char *name, double *ms, int *calls) {
   auto it = c->timers.find(name);
@@ -2456,6 +2614,7 @@ typedef int (*phase_fn_t)(pop_ctx *);
 static phase_fn_t phase_by_name(const std::string &p) {
   if (p == "vmix") return phase_vmix;
   if (p == "tracer_rhs") return [](pop_ctx *x) { return phase_tracer_rhs(x); };
+  if (p == "passive_rhs") return phase_passive_rhs;
   if (p == "tracer_rhs_fwd") return [](pop_ctx *x) { return phase_tracer_rhs(x, true); };
   if (p == "impvmixt_back") return phase_impvmixt_back;
   if (p == "impvmixt") return phase_impvmixt_pred;
@@ -2473,7 +2632,7 @@ static phase_fn_t phase_by_name(const std::string &p) {
 }
 // one phase of baroclinic_driver / baroclinic_correct_adjust on its own, once, on the launch stream with the step
 // parameters pop_time_manager set: the public routines the reference's drivers call (vmix_coeffs vertical_mix.F90:518,
-// tracer_update baroclinic.F90:1902 [tracer_rhs; hmix_tracer = the first Laplacian of hdifft_del4], impvmixt
+// tracer_update baroclinic.F90:1902 [tracer_rhs for T and S, passive_rhs for n = 3 .. nt; hmix_tracer = the first Laplacian of hdifft_del4], impvmixt
 // vertical_mix.F90:1164, state state_mod.F90:258 on the new tracers, clinic baroclinic.F90:1635 [momentum_rhs;
 // hmix_momentum = first Laplacian of hdiffu_del4], impvmixu vertical_mix.F90:1679 + baroclinic.F90:1077-1129,
 // impvmixt_correct :1460 [correct]).  Lets a caller -- and the parity tests -- drive and check the phases one by one.

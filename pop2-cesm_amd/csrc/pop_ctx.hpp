@@ -143,6 +143,10 @@ struct pop_ctx {
   LwDev lw{};                                              // tadvect = 3 (lw_lim): flux-velocity and work fields
   SubmDev subm{};                                          // lsubmesoscale_mixing: the column fields of submeso_sf, diagnostics
   GmDev gm{};                                              // hmix_tracer = 3 (gm): slopes, tapered diffusivities, GTK
+  // passive tracers n = 3 .. nt (0-based 2 .. nt-1).  PW[n]: the horizontal-mixing work field of tracer n -- the Gent-McWilliams (+ submeso)
+  // tendency (GM_GTK) or del4's first Laplacian; PWX: the second output of a pair launch for an odd tracer count; PL: L(T) of lw_lim
+  // of the pair in hand; PTD / PTDX: submeso_diag's tendency (SUBM_ADV_TEND); KPPX / KPPXa: KppDev::SRCX of the two sets of KPP outputs
+  double *PW[MAXNT] = {}, *PWX = nullptr, *PL[2] = {nullptr, nullptr}, *PTD[MAXNT] = {}, *PTDX = nullptr, *KPPX = nullptr, *KPPXa = nullptr;
   RcclTransport *rccl_tr = nullptr;                       // in-library RCCL transport (pop_comm_init_rccl)
   // Jayne tidal mixing (pop_init_tidal_mixing): the resolved namelist and the init-time fields of the local blocks (host copies serve
   // pop_get_field; the device copies and the kernel's arguments live in KppHost::tidal)

@@ -87,6 +87,7 @@ struct HostModel {
   bool plan_only = false;                  // POP_CREATE_PLAN_ONLY: blocks, distribution and halo plan, no fields
   long long ocean_cols_local = -1, ocean_cols_total = -1;   // ocean columns of the physical domain (global KMT rule / record), make_blocks
   int nxb = 0, nyb = 0, km = 0, nt = 2;
+  bool iage[MAXNT] = {};                   // tracer n (0-based) is ideal age (pop_init_iage): interior source, surface reset, restart name
   int nbx = 0, nby = 0, nblocks_tot = 0, nblocks = 0;   // nblocks = local
   size_t n2 = 0, n3 = 0;
   std::vector<BlockInfo> all_blocks;      // every block of the decomposition (1-based id = index+1)
@@ -139,6 +140,7 @@ struct RestartField {
   int mask;                                          // 1 CALCU, 2 CALCT, 3 k > KMU, 4 k > KMT (read_restart :881-935)
 };
 struct RestartAttr { std::string name, type, value; };
+std::string restart_tracer_name(const HostModel &h, int n);
 std::vector<RestartField> restart_fields(const HostModel &h);
 int restart_write_header(const HostModel &h, const std::string &path, const std::vector<RestartAttr> &attrs,
                          const std::vector<RestartField> &fields, std::string &err);

@@ -407,6 +407,11 @@
          type (c_ptr), value :: ctx
          type (pop_kpp_bckgrnd_nml), intent(in) :: nml
       end function
+      integer (c_int) function pop_init_iage(ctx, n) bind(C, name='pop_init_iage')
+         import :: c_int, c_ptr
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: n                        ! 1-based tracer number, 3 .. nt
+      end function
    end interface
 
  contains
