@@ -576,6 +576,10 @@ static void hdifft_gm(orc_model *m, int b, int k, double *GTK) {
       WORK3[p] = KI(GM_KTP, k)[q] * GM4(G->SLX, GM_W, GM_KTP, k)[q] * dz[k] - GM4(G->SF_SLX, GM_W, GM_KTP, k)[q];
       WORK4[p] = KI(GM_KBT, k)[q] * GM4(G->SLX, GM_W, GM_KBT, k)[q] * dz[k] - GM4(G->SF_SLX, GM_W, GM_KBT, k)[q];
     }
+    if (k < km) for (int n = 2; n < nt; n++) {                                                    /* :1851-1852: TZ of the passive tracers is formed here only */
+      const double *Tk = m->TRACER[n][m->mixtime] + o3 + (size_t)(k - 1) * n2, *Tkp = Tk + n2;
+      for (size_t p = 0; p < n2; p++) TZn(n, k + 1)[p] = Tk[p] - Tkp[p];
+    }
     for (int n = 0; n < nt; n++) for (int j = 1; j <= nyb; j++) for (int i = 1; i <= nxb - 1; i++) {
       const size_t p = P2(i, j), q = P2(i + 1, j);
       FX[(size_t)n * n2 + p] = FX[(size_t)n * n2 + p] - CX[p] * (WORK1[p] * TZn(n, k)[p] + WORK2[p] * TZn(n, kp1)[p] + WORK3[p] * TZn(n, k)[q] + WORK4[p] * TZn(n, kp1)[q]);

@@ -1,5 +1,6 @@
-"""Multi-rank check of the passive tracers and ideal age: tests/mr_gpu_check.py with nt = 4, tracer 3 made ideal age (pop_init_iage) and
-tracer 4 given a field on every model it builds, and every tracer compared instead of temperature alone.
+"""Multi-rank check of the passive tracers and ideal age: tests/mr_gpu_check.py with nt >= 4, tracer 3 made ideal age (pop_init_iage) and
+every further passive tracer given a field on every model it builds (tracer 4 F, tracer 5 2 F, ...: cell-by-cell multiples, the same on any
+decomposition), and every tracer compared instead of temperature alone.
 
     python -m torch.distributed.run --nproc-per-node 2 tests/mr_gpu_passive.py --config tiny --steps 3 --no-restart --kw nt=4
 
@@ -23,8 +24,9 @@ def main():
         m.init_iage(3)
         k = np.arange(m.km)[None, :, None, None]
         F = np.where(k < m.geti("KMT")[:, None], get(m, "TRACER", 1, 0) * 0.37 + 1.0, 0.0)     # cell by cell: the same on any decomposition
-        for tl in (0, 1, 2):
-            m.set("TRACER", F, tl=tl, n=3)
+        for n in range(3, m.dim("nt")):                # tracer 4 holds F, tracer 5 2 F, ...: an odd count does not compare a tracer of zeros
+            for tl in (0, 1, 2):
+                m.set("TRACER", F * float(n - 2), tl=tl, n=n)
 
     def init_then_passive(self, cfg, rank=0, nranks=1, **kw):
         init(self, cfg, rank=rank, nranks=nranks, **kw)

@@ -1,6 +1,7 @@
-"""Shared pieces of the passive-tracer tests (tests/test_gpu_passive.py, tests/test_passive_host.py): the passive initial field, the
-state copied from an oracle to a device model, the phase-by-phase step that also checks the tracers n >= 2, and the oracle-side
-emulation of the ideal-age module (iage_mod.F90) through the oracle's phase calls."""
+"""Shared pieces of the passive-tracer tests (tests/test_gpu_passive.py, tests/test_gpu_passive_matrix.py, tests/test_passive_host.py): the
+passive initial field, the state copied from an oracle to a device model, the phase-by-phase step that also checks the tracers n >= 2, the
+oracle-side emulation of the ideal-age module (iage_mod.F90) through the oracle's phase calls, and the salinity twin with the rows
+(topology x scheme) it is run on."""
 import numpy as np
 
 SECONDS_IN_YEAR = 365.0 * 86400.0
@@ -30,6 +31,58 @@ def set_passive(models, fields):
                     m.f3("TRACER", tl, n)[...] = F
                 else:
                     m.set("TRACER", F, tl=tl, n=n)
+
+
+def make_salinity_twin(models, n):
+    """Tracer n (0-based, n >= 2) of every model becomes a twin of salinity: TRACER(tl, 1) at the three time levels, STF(1) and TFW(1)
+    copied into slot n (device PopModel: get / set; Oracle: f3 / f2).  Call it once the state (and force_kpp_case) is in place.  With
+    lpressure_avg = 0 the reference updates every tracer by one loop (baroclinic.F90:1328-1344) and a passive tracer takes salinity's
+    diffusivity (vertical_mix.F90:1260), so the twin must stay salinity bit for bit: assert_twin."""
+    assert n >= 2
+    for m in models:
+        if hasattr(m, "f3"):
+            for tl in (0, 1, 2):
+                m.f3("TRACER", tl, n)[...] = m.f3("TRACER", tl, 1)
+            for f in ("STF", "TFW"):
+                m.f2(f, 1, n)[...] = m.f2(f, 1, 1)
+        else:
+            for tl in (0, 1, 2):
+                m.set("TRACER", m.get("TRACER", tl, 1), tl=tl, n=n)
+            for f in ("STF", "TFW"):
+                m.set(f, m.get(f, n=1), n=n)
+
+
+def assert_twin(m, n, what=""):
+    """tracer n (0-based) is salinity at old and cur on every cell -- ghost cells, land and block padding included, no exceptions --
+    and with KPP its non-local source is salinity's"""
+    orc = hasattr(m, "f3")
+    for tl in (0, 1):
+        a, s = (m.f3("TRACER", tl, n), m.f3("TRACER", tl, 1)) if orc else (m.get("TRACER", tl, n), m.get("TRACER", tl, 1))
+        assert np.array_equal(a, s), "%s: tracer %d is not salinity at tl %d: %d cells differ, max %.3e" % (
+            what, n + 1, tl, int((a != s).sum()), np.nanmax(np.abs(a - s)))
+    if m.cfg.vmix_choice == 3:
+        a, s = (m.f3("KPP_SRC", 1, n), m.f3("KPP_SRC", 1, 1)) if orc else (m.get("KPP_SRC", n=n), m.get("KPP_SRC", n=1))
+        assert np.array_equal(a, s), "%s: KPP_SRC of tracer %d is not salinity's: %d cells differ" % (what, n + 1, int((a != s).sum()))
+
+
+TWINS = (2, 4)          # the layout of the twin tests, nt = 5, 0-based: tracers 3 and 5 twins (a pair slot, the launch of one) ...
+NEIGHBOUR = 3           # ... and tracer 4 passive_field(T), a non-trivial neighbour in the other slot of the pair
+
+
+def twin_layout(models, A):
+    """nt = 5: tracers 3 and 5 salinity twins, tracer 4 the field A at the three time levels"""
+    set_passive(models, {NEIGHBOUR: A})
+    for n in TWINS:
+        make_salinity_twin(models, n)
+
+
+def assert_neighbour(m, what=""):
+    """tracer 4 after the run: finite, not salinity, and not a constant at level 2"""
+    get = (lambda n: m.f3("TRACER", 1, n)) if hasattr(m, "f3") else (lambda n: m.get("TRACER", 1, n))
+    t4 = get(NEIGHBOUR)
+    assert np.isfinite(t4).all(), what
+    assert not np.array_equal(t4, get(1)), what
+    assert np.ptp(t4[:, 1]) > 0.0, what
 
 
 def copy_state(orc, gpu):
@@ -144,3 +197,98 @@ def age_closed_form(kmt, dz, dzw, vdc, psurf, dt):
         M[k - 1, k - 1] += a; M[k, k] += a; M[k - 1, k] -= a; M[k, k - 1] -= a
     M[0, 0] += psurf / (GRAV * dt)
     return np.linalg.solve(M, rhs)
+
+
+# ---- the salinity-twin matrix: tests/test_passive_host.py pins the property on the oracle, tests/test_gpu_passive_matrix.py runs it on the device
+KPP = dict(vmix_choice=3, km=24)
+DEL4 = dict(hmix_tracer=4, ah=-1.0e21)
+SCHEMES = {
+    "default": {},                                   # avgfit
+    "upwind3": {"tadvect": 2},
+    "lw_lim": {"tadvect": 3},
+    "del4": DEL4,
+    "del4-variable": dict(DEL4, lvariable_hmix=1),
+    "kpp": KPP,
+    "kpp-del4": dict(KPP, **DEL4),
+    "gm": {"hmix_tracer": 3},
+    "gm-no-cancellation": {"hmix_tracer": 3, "ah_bolus": 0.4e7},
+    "gm-transition-layer-kpp-submeso": dict(KPP, hmix_tracer=3, gm_transition_layer=1, submeso=True),
+    "robert": {"tmix_opt": 3},
+    "avg": {"tmix_opt": 1, "time_mix_freq": 3},
+    "tidal-bckgrnd": dict(KPP, bckgrnd_vdc1=0.16, tidal=True),
+}
+# condition (b) of tests/test_passive_host.py for a row whose scheme has several parts: the scheme the last part is compared against
+# (the row's S must differ from S with that part alone left out), beside the comparison with the row without any of it
+WITHOUT_LAST_PART = {"kpp-del4": "kpp", "del4-variable": "del4", "gm-no-cancellation": "gm", "gm-transition-layer-kpp-submeso": "gm-transition-layer-kpp"}
+PART_SCHEMES = {"gm-transition-layer-kpp": dict(KPP, hmix_tracer=3, gm_transition_layer=1)}      # run for (b) only, not a row
+PBC = {"partial_bottom_cells": 1, "stepped_bathymetry": 1}
+TOPOLOGIES = {                                       # name -> (config keywords, synthetic_grid?)
+    "dividing": ({}, False),
+    "padded-20x16": ({"block_size_x": 20, "block_size_y": 16}, False),
+    "padded-28x24": ({"block_size_x": 28, "block_size_y": 24}, False),
+    "one-block": ({"block_size_x": 48, "block_size_y": 40}, False),
+    "tripole": ({"ns_boundary": 2}, True),
+    "tripole-padded-20x16": ({"ns_boundary": 2, "block_size_x": 20, "block_size_y": 16}, True),
+    "tripole-padded-28x24": ({"ns_boundary": 2, "block_size_x": 28, "block_size_y": 24}, True),
+    "closed-ew": ({"ew_boundary": 0}, False),
+    "stepped": ({"stepped_bathymetry": 1}, False),
+    "stepped-km60": ({"stepped_bathymetry": 1, "km": 60}, False),    # the register Thomas kernels: nlast = 2 (tracers 3, 4), nlast = 1 (tracer 5)
+    "pbc": (PBC, False),
+    "tripole-pbc": (dict(PBC, ns_boundary=2), True),                                          # DZBC from synthetic_dzbc
+    "tripole-padded-pbc": (dict(PBC, ns_boundary=2, block_size_x=36, block_size_y=40), True),
+}
+# every scheme once on the dividing layout; every topology with default, KPP + del4, Gent-McWilliams and Robert (padded and tripole + padded
+# split the four over their two block sizes; Gent-McWilliams is refused with partial bottom cells, hmix_gm.F90:782)
+TWIN_ROWS = [("dividing", s) for s in SCHEMES] + \
+    [("stepped", s) for s in ("default", "kpp-del4", "gm", "robert")] + [("stepped-km60", "default")] + \
+    [("pbc", s) for s in ("default", "kpp", "kpp-del4", "robert")] + \
+    [("padded-20x16", "default"), ("padded-28x24", "kpp-del4"), ("padded-20x16", "gm"), ("padded-28x24", "robert")] + \
+    [("one-block", s) for s in ("default", "kpp-del4", "gm", "robert")] + \
+    [("tripole", s) for s in ("default", "kpp-del4", "gm", "robert")] + \
+    [("tripole-padded-20x16", "default"), ("tripole-padded-28x24", "kpp-del4"), ("tripole-padded-20x16", "gm"), ("tripole-padded-28x24", "robert")] + \
+    [("tripole-pbc", "default"), ("tripole-padded-pbc", "kpp")] + \
+    [("closed-ew", s) for s in ("default", "kpp-del4", "gm", "robert")]
+TWIN_IDS = ["%s-%s" % r for r in TWIN_ROWS]
+
+
+def twin_row(pkg, topology, scheme, nt=5, lpressure_avg=0, without_scheme=False):
+    """(config, grid, tidal?) of a row of the matrix.  without_scheme: the same row with the scheme's switches left at their defaults
+    (km stays: the state and the vertical grid are the row's)."""
+    from popcfg import named_config, synthetic_grid, synthetic_dzbc
+    tkw, own_grid = TOPOLOGIES[topology]
+    skw = dict({**PART_SCHEMES, **SCHEMES}[scheme])
+    submeso, tidal = skw.pop("submeso", False), skw.pop("tidal", False)
+    if without_scheme:
+        skw, submeso, tidal = {k: v for k, v in skw.items() if k == "km"}, False, False
+    cfg = named_config("tiny", **dict(tkw, nt=nt, lpressure_avg=lpressure_avg, **skw))
+    if submeso:
+        cfg = pkg.submeso_config(cfg)
+    grid = synthetic_grid(cfg) if own_grid else None
+    if grid is not None and cfg.partial_bottom_cells:
+        grid["DZBC"] = synthetic_dzbc(cfg, grid["KMT"])
+    return cfg, grid, tidal
+
+
+def twin_start(orc, models, scheme, tidal):
+    """The state of a row on the oracle and on the device models `models`: force_kpp_case where the row's scheme has KPP (also in its run
+    without the scheme: the same state), tidal mixing and the varying background where it asks for them, then -- with nt = 5 -- the twin
+    layout.  Returns the field of tracer 4."""
+    from orclib import AsModel
+    if {**PART_SCHEMES, **SCHEMES}[scheme].get("vmix_choice") == 3:
+        from test_gpu_parity import force_kpp_case
+        force_kpp_case(NoDevice(), orc)
+    if tidal:
+        from bckgrnd_ref import CESM
+        from test_gpu_tidal import unit_flux
+        orc.init_tidal_mixing(1.0e3 * unit_flux(AsModel(orc)))
+        orc.init_kpp_bckgrnd(**CESM)
+        for m in models:
+            m.init_tidal_mixing(1.0e3 * unit_flux(m))
+            m.init_kpp_bckgrnd(**CESM)
+    for m in models:
+        copy_state(orc, m)
+    if orc.nt < 5:
+        return None
+    A = passive_field(orc.f3("TRACER", 1, 0).copy(), orc.i2("KMT"))
+    twin_layout([orc] + list(models), A)
+    return A

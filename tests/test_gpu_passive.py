@@ -1,6 +1,6 @@
 """Passive tracers (nt = 3 .. 8) and ideal age on the GPU.
 
-A1  phase by phase against the CPU oracle where it runs the all-tracer branch (lpressure_avg = 0): every scheme, nt = 3, 4, 5, 8.
+A1  phase by phase against the CPU oracle where it runs the all-tracer branch (lpressure_avg = 0): every scheme, nt = 3 .. 8.
 A2  properties that need no oracle, bitwise after 4 steps: T, S, U, V, PSURF, RHO and the iteration counts are those of the nt = 2 run;
     tracer 5 (the launch of one) is tracer 3 (a slot of the pair launch); tracer 4, started at twice tracer 3, stays twice tracer 3.
 A3  pressure averaging, the branch the oracle lacks: on a leapfrog step the stored right-hand side and the corrected tracer of a model
@@ -76,6 +76,10 @@ A1 = [
     ("nt3", {}, 3, 3),
     ("nt4", {}, 4, 3),
     ("nt8", {}, 8, 3),
+    ("nt6", {}, 6, 3),                                                   # pair, pair
+    ("nt7", {}, 7, 3),                                                   # pair, pair, the launch of one
+    # without cancellation of the skew-flux terms the reference forms TZ of the tracers n > 2 inside hdifft_gm (hmix_gm.F90:1851-1852)
+    ("gm-no-cancellation", {"hmix_tracer": 3, "ah_bolus": 0.4e7}, 5, 4),
 ]
 
 
@@ -108,7 +112,7 @@ A2 = [
     ("robert", {"tmix_opt": 3}),
     ("avg", {"tmix_opt": 1, "time_mix_freq": 3}),
     # Gent-McWilliams without cancellation of the skew-flux terms (k_gm_flux_tile<R, false, false> / the stored stream function; with the
-    # submeso scheme k_submeso_flux<false>): the oracle leaves TZ of n > 2 at 0 there, so these paths have the bitwise properties only
+    # submeso scheme k_submeso_flux<false>)
     ("gm-no-cancellation", {"hmix_tracer": 3, "ah_bolus": 0.4e7}),
     ("gm-transition-layer-kpp-submeso", dict(KPP, hmix_tracer=3, gm_transition_layer=1, stepped_bathymetry=1, submeso=True)),
 ]
@@ -141,6 +145,31 @@ def test_a2_passive_linear_and_slot_independent(pkg, orclib_built, name, kw):
         assert not np.array_equal(interior(t3), interior(A)) and np.abs(interior(t3) - interior(A)).max() > 1e-6
         assert np.ptp(interior(t3)[:, 1]) > 0.0
     m5.close(); m2.close()
+
+
+@pytest.mark.parametrize("pavg", [0, 1], ids=["all-tracer", "pavg"])
+def test_a2_seven_tracers_slots_are_independent(pkg, orclib_built, pavg):
+    """nt = 7, KPP + Gent-McWilliams: tracers 3, 5, 7 hold A (slot 0 of a pair, slot 0 of a pair, the launch of one) and stay equal to
+    each other; tracers 4, 6 hold 2 A (slot 1 of either pair) and stay twice tracer 3.  Bitwise after 4 steps."""
+    cfg = cfg_of(pkg, dict(KPP, hmix_tracer=3), nt=7, lpressure_avg=pavg)
+    m, orc = pkg.PopModel(cfg), Oracle(cfg)
+    A = start(pkg, cfg, orc, [m])
+    mult = {2: 1.0, 3: 2.0, 4: 1.0, 5: 2.0, 6: 1.0}
+    set_passive([m], {n: f * A for n, f in mult.items()})
+    stf = passive_stf(orc.f2("TLAT"), 2)
+    for n, f in mult.items():
+        m.set("STF", f * stf, n=n)
+    orc.close()
+    for _ in range(4):
+        m.step()
+    for tl in (0, 1):
+        t = {n: m.get("TRACER", tl, n) for n in mult}
+        assert np.array_equal(t[4], t[2]) and np.array_equal(t[6], t[2]), tl
+        assert np.array_equal(t[3], 2.0 * t[2]) and np.array_equal(t[5], 2.0 * t[2]), tl
+        assert np.isfinite(t[2]).all() and np.abs(interior(t[2]) - interior(A)).max() > 1e-6 and np.ptp(interior(t[2])[:, 1]) > 0.0
+    src = [m.get("KPP_SRC", n=n) for n in (2, 4, 6)]
+    assert src[0].any() and np.array_equal(src[1], src[0]) and np.array_equal(src[2], src[0])
+    m.close()
 
 
 @pytest.mark.parametrize("name,kw", [("default", {}), ("kpp", KPP), ("gm", {"hmix_tracer": 3})], ids=["default", "kpp", "gm"])

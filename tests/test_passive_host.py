@@ -11,7 +11,8 @@ import pytest
 
 from orclib import Oracle
 from popcfg import named_config
-from passive_common import (IageEmulation, NoDevice, age_closed_form, passive_field, passive_fields, set_passive)
+from passive_common import (IageEmulation, NoDevice, SCHEMES, TWINS, WITHOUT_LAST_PART, TWIN_IDS, TWIN_ROWS, age_closed_form, assert_neighbour,
+                            assert_twin, passive_field, passive_fields, set_passive, twin_row, twin_start)
 
 
 def test_init_iage_on_a_host_only_context(pkg):
@@ -115,6 +116,60 @@ def test_oracle_first_step_of_ideal_age_is_the_closed_form(orclib_built, kpp, pa
     print("columns %d, worst relative difference %.2e" % (ncol, worst))
     assert ncol > 1000 and worst <= 1e-13
     orc.close()
+
+
+_S_WITHOUT = {}
+
+
+def _twin_oracle_run(pkg, topology, scheme, nt, without_scheme, tidal_off=False):
+    """five steps of a row on the oracle; returns S(cur) at the start and after 4 steps and the mask of the physical ocean cells.
+    tidal_off: the row's configuration without the two init calls"""
+    from orclib import AsModel
+    from test_tidal_host import physical
+    cfg, grid, tidal = twin_row(pkg, topology, scheme, nt=nt, without_scheme=without_scheme)
+    orc = Oracle(cfg, grid=grid)
+    twin_start(orc, [], scheme, tidal and not tidal_off)
+    k = np.arange(orc.km)[None, :, None, None]
+    ocean = physical(AsModel(orc))[:, None] & (k < orc.i2("KMT")[:, None])
+    S0 = orc.f3("TRACER", 1, 1).copy()
+    for s in range(1, 6):
+        orc.step()
+        if nt == 5:
+            for n in TWINS:
+                assert_twin(orc, n, "%s %s step %d" % (topology, scheme, s))
+        if s == 4:
+            S4 = orc.f3("TRACER", 1, 1).copy()
+            if nt == 2:
+                break
+    if nt == 5:
+        assert_neighbour(orc, "%s %s" % (topology, scheme))
+    orc.close()
+    return S0, S4, ocean
+
+
+@pytest.mark.parametrize("topology,scheme", TWIN_ROWS, ids=TWIN_IDS)
+def test_oracle_salinity_twin_stays_salinity(pkg, orclib_built, topology, scheme):
+    """The yardstick of tests/test_gpu_passive_matrix.py B1, row by row: with lpressure_avg = 0 a passive tracer that starts as salinity
+    and carries its STF and TFW stays salinity bit for bit on every cell, in a slot of the pair (tracer 3) and as the launch of one
+    (tracer 5), over five steps.  So that this is not an equality of untouched fields: (a) every physical ocean cell of S has changed
+    after four steps, and (b) where the row names a scheme, S after four steps differs from S of the same row without the scheme -- and,
+    where the scheme has several parts, from S of the row without the last of them (passive_common.WITHOUT_LAST_PART)."""
+    S0, S4, ocean = _twin_oracle_run(pkg, topology, scheme, 5, False)
+    assert ocean.sum() > 1000
+    same = (S4 == S0) & ocean
+    assert not same.any(), "(a): %d of %d ocean cells of S unchanged after 4 steps" % (same.sum(), ocean.sum())
+    if scheme != "default":
+        key = (topology, SCHEMES[scheme].get("km"), SCHEMES[scheme].get("vmix_choice") == 3)
+        if key not in _S_WITHOUT:
+            _S_WITHOUT[key] = _twin_oracle_run(pkg, topology, scheme, 2, True)[1]
+        assert not np.array_equal(S4, _S_WITHOUT[key]), "(b): the scheme leaves S as it is without it"
+    if scheme in WITHOUT_LAST_PART:                  # (b) for the last part of a combined scheme: KPP + del4 against KPP, ...
+        key = (topology, WITHOUT_LAST_PART[scheme])
+        if key not in _S_WITHOUT:
+            _S_WITHOUT[key] = _twin_oracle_run(pkg, topology, WITHOUT_LAST_PART[scheme], 2, False)[1]
+        assert not np.array_equal(S4, _S_WITHOUT[key]), "(b): S is what it is with %s alone" % WITHOUT_LAST_PART[scheme]
+    if scheme == "tidal-bckgrnd":                    # (b) against KPP with the uniform background of the same bckgrnd_vdc1 as well
+        assert not np.array_equal(S4, _twin_oracle_run(pkg, topology, scheme, 2, False, tidal_off=True)[1])
 
 
 def closed_form_worst(age, kmt, dz, dzw, vdc, psurf, dt):
