@@ -330,6 +330,57 @@ int pop_init_kpp_bckgrnd(pop_ctx *ctx, const pop_kpp_bckgrnd_nml *nml);
  * marking: make the call again before pop_read_restart. */
 int pop_init_iage(pop_ctx *ctx, int n);
 
+/* ---- frazil ice formation (ice.F90; ice_nml) through an entry point of its own: pop_config keeps its layout, and a context that
+ *      never makes the call steps exactly as before.  Wherever a cell of the levels 1 .. kmxice is colder than the freezing point the
+ *      cell is warmed to it and salinity adjusted; the heat debt is kept in QICE (this call) and AQICE (accumulated) for the coupler.
+ *      The surface layer is the variable-thickness one (dz(1) + PSURF/grav + eps2), as everywhere in this library.  The doubles are
+ *      taken literally.  The freezing point (shr_frz_mod of CIME, not part of POP) is restated from memory: DESIGN.md section 13. */
+typedef struct pop_ice_nml {
+  int struct_bytes;             /* sizeof(pop_ice_nml) of the caller */
+  int ice_freq_opt;             /* 0 'never', 1 'coupled'; 2 'nyear' .. 7 'nstep' are refused (ice.F90:211-234 set a flag that ice_formation never reads, :424-428) */
+  int licecesm2;                /* 1: ice forms on every step (time_management.F90:1959-1991); 0 with 'coupled' needs tmix_opt robert or avgfit */
+  int kmxice;                   /* ice forms in the levels 1 .. kmxice (code default 1) */
+  int lactive_ice;              /* accepted for namelist parity: nothing on this path reads it */
+  int lfw_as_salt_flx;          /* 1: virtual salt flux (CESM): S += (salref - salice) POTICE cp_over_lhfusion / thickness; 0: the fresh-water form -- the
+                                 * volume-replacement formulas of ice.F90:496-504, 555-557 and FW_FREEZE.  Adding FW_FREEZE to FW / TFW (forcing.F90:425-437) stays
+                                 * with the caller, who owns the surface forcing */
+  int tfreeze_option;           /* 0 'minus1p8', 1 'linear_salt', 2 'mushy' */
+  double sea_ice_salinity;      /* [psu] (4.0) */
+  double ocn_ref_salinity;      /* [psu] (34.7) */
+  double latent_heat_fusion;    /* [erg/g] (3.34e9) */
+  double cp_sw;                 /* [erg/g/K] (3.996e7) */
+  double rho_sw;                /* [g/cm^3] (4.1 / 3.996) */
+  double rho_fw;                /* [g/cm^3] (1.0) */
+} pop_ice_nml;
+void pop_ice_nml_init(pop_ice_nml *nml);   /* struct_bytes = sizeof, the code defaults of ice.F90:158-162, forcing_sfwf.F90:268, pop_constants.F90:239-250 ('never') */
+/* init_ice (ice.F90:98-317).  Once per context, after pop_create* and -- with several ranks -- the transport, before the first
+ * pop_time_manager / pop_step / pop_run_phase, in any order with the other pop_init_* calls.  Works on a host-only context.  Allocates
+ * QICE, AQICE, QFLUX, FW_FREEZE (zeros) and sets tlast_ice = 0; liceform = (ice_freq_opt != 'never').  After the call
+ * pop_baroclinic_correct_adjust adds dtt * time_weight to tlast_ice on every step (increment_tlast_ice, baroclinic.F90:1253: whatever
+ * ice_freq_opt says).  With liceform: the corrector's freeze clamp (reset_to_freezing) is off (baroclinic.F90:1418);
+ * pop_baroclinic_correct_adjust, without the Robert filter, forms ice on TRACER(new) after the corrector; with the Robert filter
+ * pop_step_tail forms ice on TRACER(cur), then TRACER(new), after the filter's conservation adjustment (step_mod.F90:1250-1273).
+ * Without the Robert filter QICE, AQICE and FW_FREEZE take part in pop_step_tail's halo update.  Refused: kmxice outside
+ * 1 .. km; a negative constant; a struct_bytes of another layout; a second call; a call after a step or a phase; 'coupled' with
+ * licecesm2 = 0 unless tmix_opt is robert or avgfit (the pre-CESM2 rule follows the coupler's calendar); ice_freq_opt 'nyear' .. 'nstep'.
+ * Afterwards pop_get_field / pop_set_field serve "QICE", "AQICE", "QFLUX", "FW_FREEZE" and pop_get_scalar "tlast_ice", "time_weight",
+ * "cp_over_lhfusion".  Restart files then carry the AQICE record, the real FW_FREEZE and the attribute tlast_ice (the reference's
+ * QFLUX-instead-of-AQICE record at a coupled time step, restart.F90:680-687, is not built); without the call they are byte for byte
+ * what they were. */
+int pop_init_ice(pop_ctx *ctx, const pop_ice_nml *nml);
+/* ice_formation (ice.F90:357-621) on TRACER(:,:,:,:,tl) and PSURF(:,:,tl), tl = 0 old, 1 cur, 2 new: one kernel launch over every cell
+ * of every local block, ghost cells included.  Legal after pop_init_ice even with 'never': a caller who owns the step sequence decides
+ * when ice forms.  time_weight is that of the step pop_time_manager last set up (0.5 on an averaging step, otherwise 1; 1 before any
+ * step).  QICE is zeroed at the start of the call, AQICE carries over; RHO(tl) is recomputed at the levels 1 .. kmxice. */
+int pop_ice_formation(pop_ctx *ctx, int tl);
+/* ice_flx_to_coupler (ice.F90:625-717) on TRACER(cur), PSURF(cur): AQICE halved for avg, avgfit and robert, QICE = the merged freeze
+ * and melt potential, QFLUX = QICE / tlast_ice / hflux_factor (0 if tlast_ice = 0; hflux_factor = 1000 / (rho_sw cp_sw)) */
+int pop_ice_flx_to_coupler(pop_ctx *ctx);
+/* ocn_import_export.F90:715-717 after the export: tlast_ice = 0, AQICE = 0, QICE = 0 */
+int pop_ice_export_reset(pop_ctx *ctx);
+/* tfreez (ice.F90:725-757) on count host values of salinity [g/g]: the host twin of the device function (one definition) */
+int pop_tfreez_host(pop_ctx *ctx, const double *S, double *TFRZ, long long count);
+
 /* ---- blocks.F90:43-63 / get_block (blocks.F90:282-320) ---------------------- */
 int pop_get_dim(const pop_ctx *ctx, const char *name);         /* nx_block, ny_block, km, nt,
                                                                   nblocks (local), nblocks_tot,
@@ -499,7 +550,8 @@ int pop_time_phase(pop_ctx *ctx, const char *phase, int reps, double *avg_ms);
  * slopes and stream function it uses: with nt > 2 the two phases together are tracer_update), "impvmixt"
  * vertical_mix.F90:1164, "state" state_mod.F90:258 on the new tracers, "momentum_rhs" clinic baroclinic.F90:1635,
  * "impvmixu" vertical_mix.F90:1679 + baroclinic.F90:1077-1129, "correct" impvmixt_correct :1460 with the surface
- * terms of baroclinic.F90:1261-1475, "add_btrop" step_mod.F90:572-600.  Uses the step parameters of the last
+ * terms of baroclinic.F90:1261-1475, "add_btrop" step_mod.F90:572-600, "ice" ice_formation ice.F90:357 on the new tracers (after
+ * pop_init_ice).  Uses the step parameters of the last
  * pop_time_manager call. */
 int pop_run_phase(pop_ctx *ctx, const char *phase);
 int pop_device_sync(pop_ctx *ctx);

@@ -89,6 +89,8 @@ def lib():
         "pop_tidal_nml_init": (None, [vp]), "pop_init_tidal_mixing": (ci, [vp, vp, pd, ll]),
         "pop_kpp_bckgrnd_nml_init": (None, [vp]), "pop_init_kpp_bckgrnd": (ci, [vp, vp]),
         "pop_init_iage": (ci, [vp, ci]),
+        "pop_ice_nml_init": (None, [vp]), "pop_init_ice": (ci, [vp, vp]), "pop_ice_formation": (ci, [vp, ci]),
+        "pop_ice_flx_to_coupler": (ci, [vp]), "pop_ice_export_reset": (ci, [vp]), "pop_tfreez_host": (ci, [vp, pd, pd, ll]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)       # AttributeError here = the library does not export the ABI
@@ -256,6 +258,35 @@ def kpp_bckgrnd_nml(**kw):
     return n
 
 
+class PopIceNml(C.Structure):
+    """include/pop_amd.h pop_ice_nml"""
+    _fields_ = [(n, C.c_int) for n in ("struct_bytes", "ice_freq_opt", "licecesm2", "kmxice", "lactive_ice", "lfw_as_salt_flx",
+                                       "tfreeze_option")] + \
+        [(n, C.c_double) for n in ("sea_ice_salinity", "ocn_ref_salinity", "latent_heat_fusion", "cp_sw", "rho_sw", "rho_fw")]
+
+
+ICE_FREQ_OPT = {"never": 0, "coupled": 1, "nyear": 2, "nmonth": 3, "nday": 4, "nhour": 5, "nsecond": 6, "nstep": 7}
+TFREEZE_OPTION = {"minus1p8": 0, "linear_salt": 1, "mushy": 2}
+
+
+def ice_nml(**kw):
+    """pop_ice_nml with the code defaults (pop_ice_nml_init: 'never', kmxice 1, fresh-water form, 'minus1p8', 4.0, 34.7, 3.34e9,
+    3.996e7, 4.1/3.996, 1.0), then the keywords: the members by name; ice_freq_opt may also be 'never' | 'coupled' | 'nyear' ...,
+    tfreeze_option 'minus1p8' | 'linear_salt' | 'mushy'.  CESM: ice_freq_opt='coupled', licecesm2=1, kmxice=1, lactive_ice=1,
+    lfw_as_salt_flx=1, tfreeze_option='mushy'."""
+    n = PopIceNml()
+    lib().pop_ice_nml_init(C.byref(n))
+    for k, v in kw.items():
+        if k == "ice_freq_opt" and isinstance(v, str):
+            v = ICE_FREQ_OPT[v]
+        if k == "tfreeze_option" and isinstance(v, str):
+            v = TFREEZE_OPTION[v]
+        if not hasattr(n, k):
+            raise AttributeError("pop_ice_nml has no field %r" % k)
+        setattr(n, k, v)
+    return n
+
+
 class PopGridInput(C.Structure):
     """include/pop_amd.h pop_grid_input"""
     _fields_ = [(n, C.POINTER(C.c_double)) for n in ("ULAT", "ULON", "HTN", "HTE", "HUS", "HUW", "ANGLE")] + [("KMT", C.POINTER(C.c_int)),
@@ -404,6 +435,35 @@ class PopModel:
         level, surface level reset to 0, 0 at the three time levels now.  Once per tracer, before the first step or phase; on every
         rank; again before read_restart on a fresh context (the file does not carry the marking)."""
         self._chk(self.L.pop_init_iage(self.h, n))
+
+    def init_ice(self, **nml):
+        """init_ice (ice.F90:98-317): keywords as ice_nml().  Once, before the first step or phase, in any order with the other
+        init_* calls; on every rank.  With ice_freq_opt != 'never' step() forms ice; ice_formation(tl) is legal either way.
+        Afterwards get / set serve "QICE", "AQICE", "QFLUX", "FW_FREEZE" and scalar() "tlast_ice", "time_weight",
+        "cp_over_lhfusion".  Returns the pop_ice_nml that was passed."""
+        n = ice_nml(**nml)
+        self._chk(self.L.pop_init_ice(self.h, C.byref(n)))
+        return n
+
+    def ice_formation(self, tl=2):
+        """ice_formation (ice.F90:357-621) on TRACER(tl), PSURF(tl): tl = 0 old, 1 cur, 2 new"""
+        self._chk(self.L.pop_ice_formation(self.h, tl))
+
+    def ice_flx_to_coupler(self):
+        """ice_flx_to_coupler (ice.F90:625-717): QICE, QFLUX from AQICE and the melt potential of TRACER(cur)"""
+        self._chk(self.L.pop_ice_flx_to_coupler(self.h))
+
+    def ice_export_reset(self):
+        """tlast_ice = 0, AQICE = 0, QICE = 0 once the coupler has QFLUX (ocn_import_export.F90:715-717)"""
+        self._chk(self.L.pop_ice_export_reset(self.h))
+
+    def tfreez(self, S):
+        """freezing point [deg C] of salinity S [g/g] with the tfreeze_option of init_ice (the host twin of the device function)"""
+        a = np.ascontiguousarray(S, dtype=np.float64)
+        out = np.empty_like(a)
+        P = C.POINTER(C.c_double)
+        self._chk(self.L.pop_tfreez_host(self.h, a.ctypes.data_as(P), out.ctypes.data_as(P), a.size))
+        return out
 
     # ---- step_mod.F90 sequence
     def time_manager(self):

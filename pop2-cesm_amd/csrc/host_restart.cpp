@@ -46,7 +46,10 @@ std::vector<RestartField> restart_fields(const HostModel &h) {
   add("GRADPY_OLD", "GRADPY", 0, 0, 2, "sfc press gradient in y at old time", "dyne/cm3", "2220", 1);
   add("PGUESS", "PGUESS", 1, 0, 2, "guess for sfc pressure at new time", "dyne/cm2", "2110", 2);
   add("FW_OLD", "FW_OLD", 1, 0, 2, "fresh water input at old time", "", "2110", 2);
-  add("FW_FREEZE", "", 1, 0, 2, "water flux due to frazil ice formation", "", "2110", 2);   // no ice formation here: zeros
+  // without pop_init_ice there is no ice formation: zeros; with it the field, and the AQICE record after it (restart.F90:1567-1577, the
+  // branch that is not a coupled time step)
+  add("FW_FREEZE", h.ice ? "FW_FREEZE" : "", 1, 0, 2, "water flux due to frazil ice formation", "", "2110", 2);
+  if (h.ice) add("AQICE", "AQICE", 1, 0, 2, "accumulated ice melt/heat", "", "2110", 2);
   add("UVEL_CUR", "UVEL", 1, 0, 3, "U velocity at current time", "cm/s", "3221", 3);
   add("UVEL_OLD", "UVEL", 0, 0, 3, "U velocity at old time", "cm/s", "3221", 3);
   add("VVEL_CUR", "VVEL", 1, 0, 3, "V velocity at current time", "cm/s", "3221", 3);

@@ -20,6 +20,7 @@
 #include "kernels_lwlim.hpp"
 #include "kernels_gm.hpp"
 #include "kernels_passive.hpp"
+#include "kernels_ice.hpp"
 #include "kernels_pcg_persist.hpp"
 #include <fcntl.h>
 #include <unistd.h>
@@ -107,6 +108,10 @@ int resolve(pop_ctx *c, const std::string &name, int tl, int n, double **ptr, lo
   if (name == "HDV") return ok(c->HDV, a3);
   if (name == "F_PARA") return ok(c->FPARA, a3);              // ... with lvariable_hmix_aniso
   if (name == "F_PERP") return ok(c->FPERP, a3);
+  if (name == "QICE") return ok(c->ice.QICE, a2);             // pop_init_ice: this call's and the accumulated heat debt, the coupler's flux, the fresh-water flux
+  if (name == "AQICE") return ok(c->ice.AQICE, a2);
+  if (name == "QFLUX") return ok(c->ice.QFLUX, a2);
+  if (name == "FW_FREEZE") return ok(c->ice.FWF, a2);
   if (name == "SMF") return ok(c->d2[n == 0 ? "SMF1" : "SMF2"], a2);
   if (name == "SMFT") return ok(c->d2[n == 0 ? "SMFT1" : "SMFT2"], a2);
   auto it = c->d2.find(name);
@@ -1057,6 +1062,9 @@ double pop_get_scalar(const pop_ctx *c, const char *name) {
   if (n == "persist_rr") return c->persist_out ? c->persist_out[1] : NAN;
   if (n == "persist_status") return c->persist_out ? c->persist_out[2] : NAN;
   if (n == "persist_checks") return c->persist_out ? c->persist_out[3] : NAN;
+  if (n == "tlast_ice") return c->ice.inited ? c->ice.tlast_ice : NAN;               // pop_init_ice: time since the coupler last took QFLUX
+  if (n == "time_weight") return ice_time_weight(c);
+  if (n == "cp_over_lhfusion") return c->ice.inited ? c->ice.k.cp_over_lhfusion : NAN;
   if (n == "rf_S1") return c->rf_S[0];
   if (n == "rf_S2") return c->rf_S[1];
   // HIP-event time of the barotropic solves (POP_SolversRun) since "solver_ms_reset", the iterations they took and their number
@@ -1215,6 +1223,7 @@ int pop_write_restart(pop_ctx *c, const char *path) {
       {"nsteps_this_interval", "int", std::to_string(c->nsteps_this_interval)},   // extension: exact restart inside an averaging interval
       {"eod_last", "log", c->eod ? "T" : "F"},   // restart.F90:346: the step that has just finished ended a day (what the next step's eod_last will be, time_management.F90:1809)
     };
+    if (h.ice) at.push_back({"tlast_ice", "r8", fmt_r8(c->ice.tlast_ice)});   // restart.F90:1332
     if (h.c.tmix_opt == 3)
       for (int n = 0; n < h.nt; ++n) if (c->rf_S_prev_valid[n]) at.push_back({"rf_S_prev_" + restart_tracer_name(h, n), "r8", fmt_r8(c->rf_S_prev[n])});
     if (restart_write_header(h, path, at, fields, c->err)) return 1;
@@ -1303,6 +1312,10 @@ int pop_read_restart(pop_ctx *c, const char *path, int flags) {
   if (c->gm.KV) {
     std::vector<double> ones((size_t)c->g.n3 * c->g.nblocks, 1.0);
     HIPCHK(c, hipMemcpy(c->gm.KV, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (h.ice) {   // restart.F90:489; QICE belongs to the step that formed it and is not in the file
+    if (!g.count("tlast_ice")) { c->err = "restart: header has no tlast_ice (the file was written without pop_init_ice)"; return 1; }
+    c->ice.tlast_ice = strtod(g["tlast_ice"].c_str(), nullptr);
   }
   if (h.c.tmix_opt == 3) {
     for (int n = 0; n < h.nt; ++n) {
@@ -1773,6 +1786,19 @@ static int phase_correct(pop_ctx *c) {
   }
   return passive_reset(c, c->newt);
 }
+// ice_formation (ice.F90:357-621) on the tracers, surface pressure and density of one time slot
+static int phase_ice(pop_ctx *c, int slot) {
+  if (!c->ice.inited) { c->err = "ice formation needs pop_init_ice"; return 1; }
+  const pop_ctx::Ice &I = c->ice;
+  IceArgs a{};
+  a.T = c->TR[0][slot]; a.S = c->TR[1][slot]; a.RHO = c->RHO[slot]; a.PS = c->PS[slot];
+  a.QICE = I.QICE; a.AQICE = I.AQICE; a.FWF = I.FWF;
+  a.cpl = I.k.cp_over_lhfusion; a.salice = I.k.salice; a.salref = I.k.salref;
+  a.time_weight = ice_time_weight(c); a.dt1 = c->h.dt[1]; a.grav = GRAV;
+  a.kmxice = I.nml.kmxice; a.tfz = I.nml.tfreeze_option; a.salt_flx = I.nml.lfw_as_salt_flx;
+  launch_ice_formation(c->g, a, c->stream);
+  return 0;
+}
 static int phase_add_btrop(pop_ctx *c, hipStream_t st = nullptr) {
   hipLaunchKernelGGL(k_add_barotropic, grid_3d(c), dim3(256), 0, st ? st : c->stream, c->g, c->U[c->newt], c->V[c->newt], c->UB[c->newt], c->VB[c->newt]);
   return 0;
@@ -1977,6 +2003,11 @@ int pop_baroclinic_correct_adjust(pop_ctx *c) {
     c->vmixu_pending = true; c->btrop_added = true;
   }
   if (phase_correct(c)) return 1;
+  // increment_tlast_ice (baroclinic.F90:1253: on every step, whatever ice_freq_opt says), then ice on the new tracers once the corrector
+  // has solved (:1442-1450; under the Robert filter step_rf forms it).  The kernel also leaves the final density of the levels it
+  // changed; reset_passive_tracers, which phase_correct has already done, touches no tracer that ice formation touches.
+  if (c->ice.inited) c->ice.tlast_ice = c->ice.tlast_ice + c->h.dtt * ice_time_weight(c);
+  if (c->ice.liceform && c->h.c.tmix_opt != 3 && phase_ice(c, c->newt)) return 1;
   HIPCHK(c, hipGetLastError());
   return 0;
 }
@@ -2032,6 +2063,9 @@ static int step_rf(pop_ctx *c) {
   }
   // reset_passive_tracers on TRACER(cur) after the filter, on TRACER(new) when it was filtered too (step_mod.F90:1259-1279)
   if (passive_reset(c, cu) || (h.rf_nonzero_newtime && passive_reset(c, nw))) return 1;
+  // ice from the filtered TRACER(cur), then from TRACER(new); AQICE carries from the first call to the second (:1250-1273).  The halo
+  // updates of the tail have run, so every ghost cell holds its source cell's inputs and ends with its bits
+  if (c->ice.liceform && (phase_ice(c, cu) || phase_ice(c, nw))) return 1;
   HIPCHK(c, hipMemcpyAsync(c->FW_OLD, c->FW, a2 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   launch_state3d(c->g, (const double *)c->TR[0][cu], (const double *)c->TR[1][cu], c->RHO[cu], c->stream);
   launch_state3d(c->g, (const double *)c->TR[0][nw], (const double *)c->TR[1][nw], c->RHO[nw], c->stream);
@@ -2050,6 +2084,8 @@ int pop_step_tail(pop_ctx *c) {
   {   // the seven updates of step_mod.F90:467-560 as one message per neighbour
     std::vector<HaloItem> items = {{c->UB[c->newt], 1, 1, 1}, {c->VB[c->newt], 1, 1, 1}, {c->U[c->newt], km, 1, 1}, {c->V[c->newt], km, 1, 1}, {c->RHO[c->newt], km}};
     for (int n = 0; n < c->h.nt; ++n) items.push_back({c->TR[n][c->newt], km});
+    // ice formed on the new tracers before this update (no Robert filter) worked on ghost cells that were not yet current
+    if (c->ice.inited && c->h.c.tmix_opt != 3) { items.push_back({c->ice.QICE, 1}); items.push_back({c->ice.AQICE, 1}); items.push_back({c->ice.FWF, 1}); }
     if (halo_update_many(c, items)) return 1;
     c->tr_ghosts_ok[c->newt] = true; c->uv_ghosts_ok[c->newt] = true;
   }
@@ -2594,6 +2630,69 @@ int pop_init_iage(pop_ctx *c, int n) {
   return 0;
 }
 
+// ---- frazil ice formation (ice.F90)
+void pop_ice_nml_init(pop_ice_nml *nml) { if (nml) ice_nml_defaults(*nml); }
+int pop_init_ice(pop_ctx *c, const pop_ice_nml *nml) {
+  if (!c) return 1;
+  if (!nml || nml->struct_bytes != (int)sizeof(pop_ice_nml)) { c->err = "pop_init_ice: pop_ice_nml.struct_bytes is not sizeof(pop_ice_nml) of this library (" + std::to_string(sizeof(pop_ice_nml)) + ")"; return 1; }
+  if (c->h.plan_only) { c->err = "pop_init_ice: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+  if (c->ice.inited) { c->err = "pop_init_ice: called a second time (once per context)"; return 1; }
+  if (c->ran || c->nsteps_total > 0) { c->err = "pop_init_ice: a step or a phase has already run (call it right after pop_create)"; return 1; }
+  if (ice_nml_check(c->h, *nml, c->err)) return 1;
+  pop_ctx::Ice I;
+  if (!c->host_only) {
+    const size_t a2 = (size_t)c->g.n2 * c->g.nblocks;
+    if (dev_alloc(c, &I.QICE, a2) || dev_alloc(c, &I.AQICE, a2) || dev_alloc(c, &I.QFLUX, a2) || dev_alloc(c, &I.FWF, a2)) return 1;
+  }
+  I.nml = *nml; I.k = ice_consts(*nml); I.tlast_ice = 0.0;
+  I.liceform = nml->ice_freq_opt != 0; I.inited = true;
+  c->ice = I; c->h.ice = true;
+  return 0;
+}
+int pop_ice_formation(pop_ctx *c, int tl) {
+  if (need_device(c)) return 1;
+  if (!c->ice.inited) { c->err = "pop_ice_formation needs pop_init_ice"; return 1; }
+  if (tl < 0 || tl > 2) { c->err = "pop_ice_formation: tl is 0 old, 1 cur or 2 new"; return 1; }
+  // work formed ahead (KPP look-ahead, del4 first Laplacians) read the cur level: it survives ice on the new one only
+  if (join_side(c, tl == 2)) return 1;
+  c->ran = true;
+  if (phase_ice(c, time_index(c, tl))) return 1;
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+int pop_ice_flx_to_coupler(pop_ctx *c) {
+  if (need_device(c)) return 1;
+  if (!c->ice.inited) { c->err = "pop_ice_flx_to_coupler needs pop_init_ice"; return 1; }
+  if (join_side(c, true)) return 1;
+  const pop_ctx::Ice &I = c->ice;
+  IceFlxArgs a{};
+  a.T = c->TR[0][c->curt]; a.S = c->TR[1][c->curt]; a.PS = c->PS[c->curt];
+  a.QICE = I.QICE; a.AQICE = I.AQICE; a.QFLUX = I.QFLUX;
+  a.grav = GRAV; a.tlast_ice = I.tlast_ice; a.hflux_factor = I.k.hflux_factor; a.tfz = I.nml.tfreeze_option;
+  a.halve = (c->h.c.tmix_opt >= 1 && c->h.c.tmix_opt <= 3) ? 1 : 0;   // avg, avgfit, robert (ice.F90:693-697)
+  with_flags([&](auto PBC) {
+    hipLaunchKernelGGL(k_ice_flx_to_coupler<PBC.value>, dim3((c->g.n2 + 255) / 256, c->g.nblocks), dim3(256), 0, c->stream, c->g, a);
+  }, c->g.pbc != 0);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+int pop_ice_export_reset(pop_ctx *c) {   // ocn_import_export.F90:715-717
+  if (need_device(c)) return 1;
+  if (!c->ice.inited) { c->err = "pop_ice_export_reset needs pop_init_ice"; return 1; }
+  const size_t bytes = (size_t)c->g.n2 * c->g.nblocks * sizeof(double);
+  c->ice.tlast_ice = 0.0;
+  HIPCHK(c, hipMemsetAsync(c->ice.AQICE, 0, bytes, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->ice.QICE, 0, bytes, c->stream));
+  return 0;
+}
+int pop_tfreez_host(pop_ctx *c, const double *S, double *TFRZ, long long count) {
+  if (!c) return 1;
+  if (!c->ice.inited) { c->err = "pop_tfreez_host needs pop_init_ice (tfreeze_option)"; return 1; }
+  if (count < 0 || (count > 0 && (!S || !TFRZ))) { c->err = "pop_tfreez_host: bad arguments"; return 1; }
+  for (long long q = 0; q < count; ++q) TFRZ[q] = ice_tfreez(c->ice.nml.tfreeze_option, S[q]);
+  return 0;
+}
+
 int pop_timers_reset(pop_ctx *c) { c->timers.clear(); c->timing = true; return 0; }
 int pop_timer_ms(pop_ctx *c, const char *name, double *ms, int *calls) {
   auto it = c->timers.find(name);
@@ -2623,6 +2722,7 @@ static phase_fn_t phase_by_name(const std::string &p) {
   if (p == "impvmixu") return [](pop_ctx *x) { return phase_impvmixu(x, nullptr); };
   if (p == "correct") return phase_correct;
   if (p == "add_btrop") return [](pop_ctx *x) { return phase_add_btrop(x); };
+  if (p == "ice") return [](pop_ctx *x) { return phase_ice(x, x->newt); };   // ice_formation on the new tracers (after pop_init_ice)
   if (p == "hmix_tracer") return [](pop_ctx *x) { return phase_hmix_tracer(x); };
   if (p == "hmix_momentum") return [](pop_ctx *x) { return phase_hmix_momentum(x); };
   // the ordered block sums between the two kernels of a fused pcg iteration (k_block_sums<1>, one workgroup per block), as the

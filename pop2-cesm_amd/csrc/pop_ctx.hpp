@@ -153,6 +153,10 @@ struct pop_ctx {
   struct Tidal { bool inited = false, on = false; pop_tidal_nml nml{}; TidalFields f; } tidal;
   // latitude-varying KPP background (pop_init_kpp_bckgrnd): host copies; the device copies live in KppHost::bck
   struct Bckgrnd { bool inited = false, on = false; pop_kpp_bckgrnd_nml nml{}; BckgrndFields f; } bck;
+  // frazil ice formation (pop_init_ice): the namelist, the derived constants, tlast_ice and the four 2-D device fields (null on a
+  // host-only context).  liceform: ice forms inside the library's own step and the corrector's freeze clamp is off
+  struct Ice { bool inited = false, liceform = false; pop_ice_nml nml{}; IceConsts k{}; double tlast_ice = 0.0;
+               double *QICE = nullptr, *AQICE = nullptr, *QFLUX = nullptr, *FWF = nullptr; } ice;
   std::vector<double> tlon;                                // TLON of the local blocks, formed once by whichever of the two init calls comes first
   bool ran = false;                                        // a step or a phase has run (pop_init_tidal_mixing / pop_init_kpp_bckgrnd are refused afterwards)
   // time stepping
@@ -225,10 +229,14 @@ StepParams step_params(const pop_ctx *c) {
   s.aidif = cf.aidif;
   s.rich_bckgrnd_vvc = cf.rich_bckgrnd_vvc; s.rich_bckgrnd_vdc = cf.rich_bckgrnd_vdc; s.rich_mix = cf.rich_mix;
   s.leapfrogts = c->leapfrogts; s.pavg = (cf.lpressure_avg && c->leapfrogts) ? 1 : 0;
-  s.impcor = cf.impcor; s.reset_to_freezing = cf.reset_to_freezing;
+  s.impcor = cf.impcor; s.reset_to_freezing = (cf.reset_to_freezing && !c->ice.liceform) ? 1 : 0;   // baroclinic.F90:1418
   s.nvdc = (cf.vmix_choice == 3) ? 2 : 1;
   return s;
 }
+
+// time_weight of increment_tlast_ice (ice.F90:340-346) for the step pop_time_manager last set up: 0.5 on an averaging step (there are
+// no back_to_back steps here), otherwise 1
+double ice_time_weight(const pop_ctx *c) { return c->avg_ts ? 0.5 : 1.0; }
 
 struct ScopedPhase {   // optional HIP-event timing of a phase on the launch stream
   pop_ctx *c; const char *name; hipEvent_t e0 = nullptr, e1 = nullptr;

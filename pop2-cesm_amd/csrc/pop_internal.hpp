@@ -88,6 +88,7 @@ struct HostModel {
   long long ocean_cols_local = -1, ocean_cols_total = -1;   // ocean columns of the physical domain (global KMT rule / record), make_blocks
   int nxb = 0, nyb = 0, km = 0, nt = 2;
   bool iage[MAXNT] = {};                   // tracer n (0-based) is ideal age (pop_init_iage): interior source, surface reset, restart name
+  bool ice = false;                        // pop_init_ice was called: restart files carry AQICE, the real FW_FREEZE and tlast_ice
   int nbx = 0, nby = 0, nblocks_tot = 0, nblocks = 0;   // nblocks = local
   size_t n2 = 0, n3 = 0;
   std::vector<BlockInfo> all_blocks;      // every block of the decomposition (1-based id = index+1)
@@ -133,6 +134,11 @@ void host_tidal_build(const HostModel &h, const pop_tidal_nml &n, const double *
 struct BckgrndFields { std::vector<double> vdc, vvc, vvc_pr; };   // bckgrnd_vdc, Prandtl * bckgrnd_vdc, (Prandtl * bckgrnd_vdc) / Prandtl: 2-D
 void kpp_bckgrnd_nml_defaults(pop_kpp_bckgrnd_nml &n);
 void host_bckgrnd_build(const HostModel &h, const pop_kpp_bckgrnd_nml &n, const std::vector<double> &tlon, BckgrndFields &out);
+// ---- frazil ice formation (host_ice.cpp; ice.F90:98-317)
+struct IceConsts { double cp_over_lhfusion, salice, salref, hflux_factor; };
+void ice_nml_defaults(pop_ice_nml &n);
+int ice_nml_check(const HostModel &h, const pop_ice_nml &n, std::string &err);
+IceConsts ice_consts(const pop_ice_nml &n);
 // ---- POP binary restart files (host_restart.cpp; restart.F90, io_binary.F90)
 struct RestartField {
   std::string name, dev; int tl, n, ndims, id;       // file name; device field, time level (0 old, 1 cur), tracer; first record

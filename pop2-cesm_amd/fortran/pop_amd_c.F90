@@ -108,6 +108,12 @@
       real (c_double) :: bckgrnd_vdc_eq, bckgrnd_vdc_psim, bckgrnd_vdc_ban
    end type pop_kpp_bckgrnd_nml
 
+   ! mirrors `struct pop_ice_nml` (ice_nml and the constants ice formation reads); fill with pop_ice_nml_init, then set fields
+   type, bind(C) :: pop_ice_nml
+      integer (c_int) :: struct_bytes, ice_freq_opt, licecesm2, kmxice, lactive_ice, lfw_as_salt_flx, tfreeze_option
+      real (c_double) :: sea_ice_salinity, ocn_ref_salinity, latent_heat_fusion, cp_sw, rho_sw, rho_fw
+   end type pop_ice_nml
+
    type (c_ptr), save :: pop_ctx = c_null_ptr   ! the one model instance of this task
 
    interface
@@ -411,6 +417,35 @@
          import :: c_int, c_ptr
          type (c_ptr), value :: ctx
          integer (c_int), value :: n                        ! 1-based tracer number, 3 .. nt
+      end function
+      subroutine pop_ice_nml_init(nml) bind(C, name='pop_ice_nml_init')
+         import :: pop_ice_nml
+         type (pop_ice_nml), intent(out) :: nml
+      end subroutine
+      integer (c_int) function pop_init_ice(ctx, nml) bind(C, name='pop_init_ice')
+         import :: c_int, c_ptr, pop_ice_nml
+         type (c_ptr), value :: ctx
+         type (pop_ice_nml), intent(in) :: nml
+      end function
+      integer (c_int) function pop_ice_formation(ctx, tl) bind(C, name='pop_ice_formation')
+         import :: c_int, c_ptr
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: tl                       ! 0 old, 1 cur, 2 new
+      end function
+      integer (c_int) function pop_ice_flx_to_coupler(ctx) bind(C, name='pop_ice_flx_to_coupler')
+         import :: c_int, c_ptr
+         type (c_ptr), value :: ctx
+      end function
+      integer (c_int) function pop_ice_export_reset(ctx) bind(C, name='pop_ice_export_reset')
+         import :: c_int, c_ptr
+         type (c_ptr), value :: ctx
+      end function
+      integer (c_int) function pop_tfreez_host(ctx, S, TFRZ, count) bind(C, name='pop_tfreez_host')
+         import :: c_int, c_ptr, c_double, c_long_long
+         type (c_ptr), value :: ctx
+         real (c_double), intent(in) :: S(*)                ! salinity, g/g
+         real (c_double), intent(out) :: TFRZ(*)
+         integer (c_long_long), value :: count
       end function
    end interface
 

@@ -904,3 +904,78 @@
       errorCode = pop_init_tidal_mixing(pop_ctx, nml, TIDAL_ENERGY_FLUX, int(size(TIDAL_ENERGY_FLUX), c_long_long))
    end subroutine
  end module tidal_mixing
+
+! ice.F90: frazil ice formation.  The caller sets the ice_nml members and the constants below (the reference reads ice_nml itself in
+! init_ice and takes the constants from pop_constants / shr_const) and calls init_ice once; ice_formation takes the logical time level
+! of the TRACER / PSURF slabs the reference's call sites pass (0 oldtime, 1 curtime, 2 newtime) -- the fields are device-resident.
+ module ice
+   use kinds_mod
+   use pop_amd_c
+   implicit none
+   private
+   character (char_len), public :: ice_freq_opt = 'never', tfreeze_option = 'minus1p8'
+   integer (int_kind), public :: kmxice = 1
+   logical (log_kind), public :: lactive_ice = .false., licecesm2 = .false., lfw_as_salt_flx = .false.
+   logical (log_kind), public :: liceform = .false.     ! set by init_ice
+   real (r8), public :: sea_ice_salinity = 4.0_r8, ocn_ref_salinity = 34.7_r8, latent_heat_fusion = 3.34e9_r8
+   real (r8), public :: cp_sw = 3.996e7_r8, rho_sw = 4.1_r8/3.996_r8, rho_fw = 1.0_r8
+   public :: init_ice, ice_formation, ice_flx_to_coupler, ice_export_reset, tfreez, tlast_ice
+ contains
+   subroutine init_ice(errorCode)
+      integer (int_kind), intent(out) :: errorCode
+      type (pop_ice_nml) :: nml
+      call pop_ice_nml_init(nml)
+      select case (trim(ice_freq_opt))
+      case ('never');   nml%ice_freq_opt = 0
+      case ('coupled'); nml%ice_freq_opt = 1
+      case ('nyear');   nml%ice_freq_opt = 2
+      case ('nmonth');  nml%ice_freq_opt = 3
+      case ('nday');    nml%ice_freq_opt = 4
+      case ('nhour');   nml%ice_freq_opt = 5
+      case ('nsecond'); nml%ice_freq_opt = 6
+      case ('nstep');   nml%ice_freq_opt = 7
+      case default;     nml%ice_freq_opt = -1
+      end select
+      select case (trim(tfreeze_option))
+      case ('minus1p8');    nml%tfreeze_option = 0
+      case ('linear_salt'); nml%tfreeze_option = 1
+      case ('mushy');       nml%tfreeze_option = 2
+      case default;         nml%tfreeze_option = -1
+      end select
+      nml%licecesm2 = merge(1, 0, licecesm2); nml%lactive_ice = merge(1, 0, lactive_ice)
+      nml%lfw_as_salt_flx = merge(1, 0, lfw_as_salt_flx); nml%kmxice = kmxice
+      nml%sea_ice_salinity = sea_ice_salinity; nml%ocn_ref_salinity = ocn_ref_salinity
+      nml%latent_heat_fusion = latent_heat_fusion; nml%cp_sw = cp_sw; nml%rho_sw = rho_sw; nml%rho_fw = rho_fw
+      errorCode = pop_init_ice(pop_ctx, nml)
+      if (errorCode == POP_Success) liceform = nml%ice_freq_opt /= 0
+   end subroutine
+   ! ice_formation(TNEW, PNEW, SHF_IN, iblock, this_block, lfw_as_salt_flx) ice.F90:357 on every local block at once
+   subroutine ice_formation(time_level, errorCode)
+      integer (int_kind), intent(in) :: time_level
+      integer (int_kind), intent(out) :: errorCode
+      errorCode = pop_ice_formation(pop_ctx, time_level)
+   end subroutine
+   ! ice_flx_to_coupler(TCUR, bid) ice.F90:625 on every local block at once; QFLUX on request
+   subroutine ice_flx_to_coupler(errorCode, QFLUX)
+      integer (int_kind), intent(out) :: errorCode
+      real (r8), dimension(:,:,:), intent(out), optional :: QFLUX
+      errorCode = pop_ice_flx_to_coupler(pop_ctx)
+      if (errorCode == POP_Success .and. present(QFLUX)) &
+         errorCode = pop_get_field(pop_ctx, cstr('QFLUX'), 1, 0, QFLUX, int(size(QFLUX), c_long_long))
+   end subroutine
+   ! tlast_ice = c0; AQICE = c0; QICE = c0 after the export (ocn_import_export.F90:715-717)
+   subroutine ice_export_reset(errorCode)
+      integer (int_kind), intent(out) :: errorCode
+      errorCode = pop_ice_export_reset(pop_ctx)
+   end subroutine
+   subroutine tfreez(TFRZ, SALT)
+      real (r8), dimension(:,:), intent(out) :: TFRZ
+      real (r8), dimension(:,:), intent(in) :: SALT
+      integer (c_int) :: ierr
+      ierr = pop_tfreez_host(pop_ctx, SALT, TFRZ, int(size(SALT), c_long_long))
+   end subroutine
+   function tlast_ice() result(t)
+      real (r8) :: t
+      t = pop_get_scalar(pop_ctx, cstr('tlast_ice'))
+   end function
+ end module ice
