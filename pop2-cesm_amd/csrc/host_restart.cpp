@@ -89,8 +89,11 @@ int restart_write_header(const HostModel &h, const std::string &path, const std:
   return o.good() ? 0 : 1;
 }
 
-// sections of a header file: name -> (attribute -> value), values trimmed; the type tag is dropped
-int restart_parse_header(const std::string &path, std::map<std::string, std::map<std::string, std::string>> &sec, std::string &err) {
+// sections of a header file: name -> (attribute -> value), values trimmed; the type tag is dropped.  `order` lists the section
+// names as they stand in the file.  As the reference reads it: each line is its first 80 columns ('(a80)', io_binary.F90:229, 985),
+// and of two sections with one name the first counts (define_field_binary searches from the top, :978-989)
+int restart_parse_header(const std::string &path, std::map<std::string, std::map<std::string, std::string>> &sec,
+                         std::vector<std::string> &order, std::string &err) {
   std::ifstream in(path + ".hdr");
   if (!in) { err = "cannot open " + path + ".hdr"; return 1; }
   auto trim = [](std::string s) {
@@ -99,9 +102,14 @@ int restart_parse_header(const std::string &path, std::map<std::string, std::map
   };
   std::string line, cur;
   while (std::getline(in, line)) {
+    if (line.size() > 80) line.resize(80);
     line = trim(line);
     if (line.empty()) continue;
-    if (line[0] == '&') { cur = trim(line.substr(1)); sec[cur]; continue; }
+    if (line[0] == '&') {
+      cur = trim(line.substr(1));
+      if (sec.count(cur)) cur.clear(); else { sec[cur]; order.push_back(cur); }
+      continue;
+    }
     if (line[0] == '/') { cur.clear(); continue; }
     if (cur.empty()) continue;
     const size_t p1 = line.find(':');
@@ -111,6 +119,13 @@ int restart_parse_header(const std::string &path, std::map<std::string, std::map
     sec[cur][trim(line.substr(0, p1))] = trim(line.substr(p2 + 1));
   }
   return 0;
+}
+
+// define_field_binary :979-989: a field's section is the first line of the file that BEGINS with "&<short_name>", so a section
+// whose name merely starts with the one wanted is taken if it comes first.  Empty: no such section.
+std::string restart_find_section(const std::vector<std::string> &order, const std::string &name) {
+  for (const std::string &s : order) if (s.compare(0, name.size(), name) == 0) return s;
+  return std::string();
 }
 
 static inline double bswap(double v) {

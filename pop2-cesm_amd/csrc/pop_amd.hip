@@ -1015,6 +1015,8 @@ int pop_get_dim(const pop_ctx *c, const char *name) {
   if (n == "d2t_last_formed") return c->d2t_last_formed;   // ... and whether the last such launch did (not on averaging steps)
   if (n == "d2u_last_formed") return c->d2u_last_formed;
   if (n == "avg_ts") return c->avg_ts;
+  if (n == "eod") return c->eod;             // time_management.F90: the step just taken ended a day / the one before it did
+  if (n == "eod_last") return c->eod_last;
   if (n == "nsteps_total") return c->nsteps_total;
   if (n == "nsteps_per_interval") return c->h.nsteps_per_interval;
   if (n == "solver_stream_ops") return (int)c->solver_ops;
@@ -1067,6 +1069,8 @@ double pop_get_scalar(const pop_ctx *c, const char *name) {
   if (n == "cp_over_lhfusion") return c->ice.inited ? c->ice.k.cp_over_lhfusion : NAN;
   if (n == "rf_S1") return c->rf_S[0];
   if (n == "rf_S2") return c->rf_S[1];
+  if (n == "rf_S_prev1") return c->rf_S_prev_valid[0] ? c->rf_S_prev[0] : NAN;   // NAN: not valid (no filtered step yet, or a restart file without it)
+  if (n == "rf_S_prev2") return c->rf_S_prev_valid[1] ? c->rf_S_prev[1] : NAN;
   // HIP-event time of the barotropic solves (POP_SolversRun) since "solver_ms_reset", the iterations they took and their number
   if (n == "solver_ms_total") { solve_collect(const_cast<pop_ctx *>(c)); return c->solver_ms_total; }
   if (n == "solver_iterations_total") { solve_collect(const_cast<pop_ctx *>(c)); return (double)c->solver_iters_total; }
@@ -1221,7 +1225,10 @@ int pop_write_restart(pop_ctx *c, const char *path) {
       {"elapsed_days", "int", std::to_string(day)}, {"seconds_this_day", "r8", fmt_r8((double)sod)},
       {"nsteps_total", "int", std::to_string(c->nsteps_total)},
       {"nsteps_this_interval", "int", std::to_string(c->nsteps_this_interval)},   // extension: exact restart inside an averaging interval
-      {"eod_last", "log", c->eod ? "T" : "F"},   // restart.F90:346: the step that has just finished ended a day (what the next step's eod_last will be, time_management.F90:1809)
+      // restart.F90:1313-1314: both flags as they stand after the step that has just finished.  The next time_manager copies eod into
+      // eod_last (time_management.F90:1809) before it resets eod (:2110), so the file's eod decides the first step after the restart
+      {"eod", "log", c->eod ? "T" : "F"}, {"eod_last", "log", c->eod_last ? "T" : "F"},
+      {"lcoupled_ts", "log", "F"},   // restart.F90:1333: never a coupled time step here, so the ice record is AQICE, not QFLUX (:1477-1489)
     };
     if (h.ice) at.push_back({"tlast_ice", "r8", fmt_r8(c->ice.tlast_ice)});   // restart.F90:1332
     if (h.c.tmix_opt == 3)
@@ -1255,10 +1262,21 @@ int pop_read_restart(pop_ctx *c, const char *path, int flags) {
   if (need_device(c) || join_side(c)) return 1;
   const HostModel &h = c->h;
   std::map<std::string, std::map<std::string, std::string>> sec;
-  if (restart_parse_header(path, sec, c->err)) return 1;
+  std::vector<std::string> order;
+  if (restart_parse_header(path, sec, order, c->err)) return 1;
+  std::map<std::string, std::string> &g = sec["GLOBAL"];
+  auto truth = [](const std::string &v) {   // list-directed logical: T, F, .TRUE., .false., ...
+    const size_t k = v.find_first_not_of(" .");
+    return (k != std::string::npos && (v[k] == 'T' || v[k] == 't')) ? 1 : 0;
+  };
   std::vector<RestartField> fields = restart_fields(h);
+  // restart.F90:679-697: a file written at a coupled time step (lcoupled_ts, when CESM writes its restarts) carries QFLUX where the
+  // others carry AQICE.  QFLUX is read, masked and halo-updated as AQICE would be (:886-896, 1041-1055); AQICE is what init_ice left: 0
+  const bool coupled_ts = h.ice && g.count("lcoupled_ts") && truth(g["lcoupled_ts"]);
+  if (coupled_ts)
+    for (RestartField &f : fields) if (f.name == "AQICE") { f.name = "QFLUX"; f.dev = "QFLUX"; }
   for (RestartField &f : fields) {   // record of each field from the header (define_field_binary :1075-1080), not from our own order
-    auto it = sec.find(f.name);
+    auto it = sec.find(restart_find_section(order, f.name));
     if (it == sec.end() || !it->second.count("id")) {
       if (f.dev.empty()) { f.id = -1; continue; }                    // FW_FREEZE is not used here
       c->err = "could not find field in binary header file: " + f.name; return 1;
@@ -1298,15 +1316,17 @@ int pop_read_restart(pop_ctx *c, const char *path, int flags) {
   launch_state3d(c->g, c->TR[0][c->oldt], c->TR[1][c->oldt], c->RHO[c->oldt], c->stream);
   HIPCHK(c, hipGetLastError());
   // scalars: initial.F90:1088 first_step = .false.; time_management.F90:1426 nsteps_this_interval = 0 unless the file says otherwise
-  std::map<std::string, std::string> &g = sec["GLOBAL"];
+  if (coupled_ts) HIPCHK(c, hipMemsetAsync(c->ice.AQICE, 0, a2 * sizeof(double), c->stream));
   if (!g.count("nsteps_total")) { c->err = "restart: header has no nsteps_total"; return 1; }
   c->nsteps_total = atoi(g["nsteps_total"].c_str());
   c->nsteps_this_interval = g.count("nsteps_this_interval") ? atoi(g["nsteps_this_interval"].c_str()) : 0;
   c->first_step = 0;
-  // restart.F90:468: eod_last comes from the file (list-directed logical); time_manager of the next step copies eod into eod_last
-  // (time_management.F90:1809), so the value read is parked in eod.  A file without it (another writer): not the end of a day.
-  c->eod = 0; c->eod_last = 0;
-  if (g.count("eod_last")) { std::string v = g["eod_last"]; size_t k = v.find_first_not_of(" ."); c->eod = (k != std::string::npos && (v[k] == 'T' || v[k] == 't')) ? 1 : 0; }
+  // restart.F90:467-468: eod and eod_last each from its own attribute (list-directed logicals); one the file lacks keeps the default,
+  // false.  time_manager of the next step copies eod into eod_last (time_management.F90:1809): the file's eod decides that step.
+  c->eod = g.count("eod") ? truth(g["eod"]) : 0;
+  c->eod_last = g.count("eod_last") ? truth(g["eod_last"]) : 0;
+  // files this library wrote before it wrote eod: their eod_last held eod
+  if (!g.count("eod") && g.count("history") && g["history"].find("written by libpop_amd") != std::string::npos) { c->eod = c->eod_last; c->eod_last = 0; }
   // module state of hmix_gm that no restart file carries: KAPPA_VERTICAL is 1 until compute_kappa runs again (init_gm, hmix_gm.F90:860) -- with
   // 'once_a_day' that is the first step of a restart written at the end of a day (eod_last), with 'never' it stays 1 (the reference's behaviour too)
   if (c->gm.KV) {

@@ -150,7 +150,9 @@ std::string restart_tracer_name(const HostModel &h, int n);
 std::vector<RestartField> restart_fields(const HostModel &h);
 int restart_write_header(const HostModel &h, const std::string &path, const std::vector<RestartAttr> &attrs,
                          const std::vector<RestartField> &fields, std::string &err);
-int restart_parse_header(const std::string &path, std::map<std::string, std::map<std::string, std::string>> &sec, std::string &err);
+int restart_parse_header(const std::string &path, std::map<std::string, std::map<std::string, std::string>> &sec,
+                         std::vector<std::string> &order, std::string &err);
+std::string restart_find_section(const std::vector<std::string> &order, const std::string &name);
 int restart_slab_io(const HostModel &h, int fd, long long rec, double *loc, size_t blk_stride, bool write, bool swap, std::string &err);
 void restart_mask(const HostModel &h, const RestartField &f, double *loc, const std::vector<int> &KMT, const std::vector<int> &KMU);
 std::vector<double> host_center_init(HostModel &h);                      // centre weight POP_SolversPrep sees (host_pcsi.cpp)

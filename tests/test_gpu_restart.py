@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+import restart_ref
 from popcfg import named_config, synthetic_grid
 
 pytestmark = pytest.mark.gpu
@@ -41,8 +42,9 @@ def parse_hdr(path):
     # Gent-McWilliams with the transition layer: everything it uses is formed from the restart fields each step (kappa every step)
     ({"hmix_tracer": 3, "ah": 0.8e7, "ah_bolus": 0.5e7, "gm_transition_layer": 1, "gm_kappa_type": 1, "gm_kappa_freq": 1, "vmix_choice": 3, "km": 24}, 4, 4),
     # ... with 'bfre' kappa recomputed once a day (the CESM namelist default, `bench.py --gm cesm`): KAPPA_VERTICAL is module state that no restart
-    # file carries (1 after init_gm); the file carries eod_last (restart.F90:346, 468), so a restart written at the END OF A DAY -- when CESM writes
-    # them -- recomputes the profile in its first step exactly as the uninterrupted run does.  (A restart in the middle of a day runs with
+    # file carries (1 after init_gm); the file carries eod (restart.F90:345, 467), which the next time_manager copies to eod_last
+    # (time_management.F90:1809), so a restart written at the END OF A DAY -- when CESM writes them -- recomputes the profile in its first step
+    # exactly as the uninterrupted run does.  (A restart in the middle of a day runs with
     # KAPPA_VERTICAL = 1 until the day ends, in the reference as here: not an exact restart, and not claimed.)
     ({"hmix_tracer": 3, "ah": 0.8e7, "gm_kappa_type": 1, "gm_kappa_freq": 2, "tmix_opt": 0, "steps_per_day": 6, "stepped_bathymetry": 1}, 6, 4),
     ({"hmix_tracer": 3, "ah": 0.8e7, "gm_transition_layer": 1, "gm_kappa_type": 1, "gm_kappa_freq": 2, "vmix_choice": 3, "km": 24, "steps_per_day": 4, "time_mix_freq": 5}, 6, 4),     # avgfit: the fit interval (4 + 2 calls) is the day
@@ -72,7 +74,8 @@ def test_exact_restart(pkg, tmp_path, kw, n1, n2):
     b.write_restart(path)
     b.close()
     if cfg.gm_kappa_freq == 2:
-        assert parse_hdr(path)["GLOBAL"]["eod_last"] == ("log", "T"), "the case must restart at the end of a day"
+        g = parse_hdr(path)["GLOBAL"]
+        assert g["eod"] == ("log", "T") and g["eod_last"] == ("log", "F"), "the case must restart at the end of a day"
     b = model()
     b.step(); b.step()                # reading into a context that has already stepped: its GM module state must not survive
     b.read_restart(path)
@@ -126,10 +129,14 @@ def test_restart_file_layout(pkg, tmp_path):
 
 
 @pytest.mark.parametrize("byteswap", [False, True])
-def test_reads_a_file_from_an_independent_writer(pkg, tmp_path, byteswap):
-    """A restart written the way the reference writes it -- 80-column header lines with list-directed values,
-    fields in another order, attributes this library does not know, values on land -- is read into the right
-    places: land masked (read_restart :881-935), ghosts filled by the halo update, RHO recomputed, leapfrog on."""
+@pytest.mark.parametrize("style", ["gfortran", "compact"])
+def test_reads_a_file_from_an_independent_writer(pkg, tmp_path, byteswap, style):
+    """A restart written the way the reference writes it (tests/restart_ref.py) -- every attribute of restart.F90:1281-1376 grouped by
+    type, the damaged conventions line, 80-column header lines with list-directed values in either style, no "/" after the global
+    attributes (gfortran style: as open_binary leaves it), fields in another order, attributes this library does not know, a char value
+    with colons, values on land -- is read into the right places: land masked (read_restart :881-935), ghosts filled by the halo update,
+    RHO recomputed, leapfrog on.  What lies past column 80 does not count, and a section is the first one whose name BEGINS with the
+    field's (io_binary.F90:979-989)."""
     cfg = named_config("tiny")
     m = pkg.PopModel(cfg)
     nx, ny, km = cfg.nx_global, cfg.ny_global, cfg.km
@@ -144,15 +151,24 @@ def test_reads_a_file_from_an_independent_writer(pkg, tmp_path, byteswap):
     data = np.concatenate(recs)
     path = str(tmp_path / "ref.bin")
     data.astype(">f8" if byteswap else "<f8").tofile(path)
-    with open(path + ".hdr", "w") as h:
-        def line(s):
-            h.write("%-80s\n" % s)
-        line("&GLOBAL"); line("title:char: some run"); line("runid:char: b.e21.test"); line("iyear:int:           7")
-        line("nsteps_total:int:         123"); line("dtt:r8:   3600.00000000000     "); line("precip_fact:r8:   1.00000000000000     "); line("/")
-        for f in order:
-            line("&" + f); line("long_name:char:whatever"); line("id:int: %11d" % ids[f]); line("nfield_dims:int: %11d" % (3 if f in FIELDS_3D else 2)); line("/")
+    attrs = restart_ref.reference_globals(nsteps_total=123, eod=not byteswap, eod_last=byteswap, tlast_ice=0.0, lcoupled_ts=False, dtt=3600.0,
+                                          km=km, runid="b.e21.test")
+    attrs += [("start_time", "char", "0007-01-01 12:30:00 UTC: a value with colons"), ("tidal_ts_data_ind_low", "int", 5),
+              ("some_factor", "r8", -2.5e-7), ("some_switch", "log", True), ("some_real", "r4", 0.5)]
+    fields = [dict(name=f, id=ids[f], ndims=3 if f in FIELDS_3D else 2, long_name="whatever: " + "w" * 100) for f in order]
+    # a section whose name begins with VVEL_CUR, ahead of it and pointing at UVEL_CUR's records: the one the reference takes
+    k = [f["name"] for f in fields].index("VVEL_CUR")
+    fields.insert(k, dict(name="VVEL_CURL", id=ids["UVEL_CUR"], ndims=3))
+    restart_ref.write_header(path, attrs, fields, style=style, title="some run: 12:00", end_global=style == "compact")
+    text = open(path + ".hdr").read().splitlines()
+    k = [ln.split(":")[0] for ln in text].index("nsteps_total")
+    text[k] = "nsteps_total:int:" + " " * 60 + "123999"                 # the reference sees 80 columns: 123
+    open(path + ".hdr", "w").write("\n".join(text) + "\n")
+    hd = restart_ref.read_header(path, fields=order)
+    assert hd.problems == [] and hd.attrs["nsteps_total"] == ("int", 123) and hd.fields["VVEL_CUR"]["id"] == ids["UVEL_CUR"]
+    assert hd.attrs["start_time"] == ("char", "0007-01-01 12:30:00 UTC: a value with colons") and hd.title == "some run: 12:00"
     m.read_restart(path, byteswap=byteswap)
-    assert m.dim("nsteps_total") == 123
+    assert m.dim("nsteps_total") == 123 and m.dim("eod") == int(not byteswap) and m.dim("eod_last") == int(byteswap)
     kmt, kmu = m.geti("KMT"), m.geti("KMU")
 
     def expect(f, mask3=None, mask2=None):
@@ -173,6 +189,7 @@ def test_reads_a_file_from_an_independent_writer(pkg, tmp_path, byteswap):
     assert np.array_equal(p, np.where(kmt >= 1, expect("PSURF_CUR")[:, 0], 0.0))
     gx = m.get("GRADPX", 0)
     assert np.array_equal(gx, np.where(kmu >= 1, expect("GRADPX_OLD")[:, 0], 0.0))
+    assert np.array_equal(m.get("VVEL", 1), np.where(k <= kmu[:, None], expect("UVEL_CUR"), 0.0))      # through the section VVEL_CURL
     # density recomputed from the tracers read; the next step is a leapfrog step
     import ctypes as C
     rho = m.get("RHO", 1)

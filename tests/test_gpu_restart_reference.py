@@ -1,0 +1,325 @@
+"""Restart files against the reference's own header rules (tests/restart_ref.py), not against this library's reader and writer alone:
+files as the reference writes them -- the full attribute list of restart.F90:1281-1376, grouped by type, the damaged conventions line,
+80-column lines, eod AND eod_last, lcoupled_ts, QFLUX for AQICE, rf_Svol_prev_* -- read by the library, and the library's own headers
+read by the reference's rules.  A reference-style file is the library's data file under a header from restart_ref.write_header.
+Every comparison is bit for bit."""
+import os
+
+import numpy as np
+import pytest
+
+import restart_ref as rr
+from ice_common import cold_start, ice_grid
+from popcfg import named_config
+from test_gpu_restart import STATE, parse_hdr
+
+pytestmark = pytest.mark.gpu
+
+# the sections restart.F90 defines (:1400-1548; QFLUX for AQICE at a coupled time step), without the tracers' own
+REFERENCE_SECTIONS = {"UBTROP_CUR", "UBTROP_OLD", "VBTROP_CUR", "VBTROP_OLD", "PSURF_CUR", "PSURF_OLD", "GRADPX_CUR", "GRADPX_OLD", "GRADPY_CUR",
+                      "GRADPY_OLD", "PGUESS", "FW_OLD", "FW_FREEZE", "AQICE", "QFLUX", "UVEL_CUR", "UVEL_OLD", "VVEL_CUR", "VVEL_OLD",
+                      "TEMP_CUR", "TEMP_OLD", "SALT_CUR", "SALT_OLD"}
+EXTENSIONS = {"nsteps_this_interval"}       # attributes of this library's own; sections: TRACER<nn>_CUR / _OLD
+
+
+def reference_header(src, dst, style="gfortran", end_global=False, rename=None, drop=(), extra=(), robert_vol=0.25, **flags):
+    """<dst>.hdr: the header the reference would have written for the data of <src>, a file of this library's (dst becomes a link to the
+    data of src).  Scalars come from src's header; flags override eod, eod_last, lcoupled_ts; rename maps section names; drop lists
+    attributes to leave out; extra is appended.  Returns the attributes written."""
+    sec = parse_hdr(src)
+    g = sec.pop("GLOBAL")
+    km = int(sec["UVEL_OLD"]["id"][1]) - int(sec["UVEL_CUR"]["id"][1])
+    robert = [(n[len("rf_S_prev_"):], float(v[1]), robert_vol) for n, v in g.items() if n.startswith("rf_S_prev_")]
+    attrs = rr.reference_globals(nsteps_total=int(g["nsteps_total"][1]), eod=flags.get("eod", g.get("eod", ("log", "F"))[1] == "T"),
+                                 eod_last=flags.get("eod_last", g.get("eod_last", ("log", "F"))[1] == "T"), tlast_ice=float(g.get("tlast_ice", ("r8", "0"))[1]),
+                                 lcoupled_ts=flags.get("lcoupled_ts", False), dtt=float(g["dtt"][1]), km=km, robert=robert)
+    attrs = [a for a in attrs if a[0] not in drop] + list(extra)
+    fields = [dict(name=(rename or {}).get(n, n), id=int(s["id"][1]), ndims=int(s["nfield_dims"][1]), long_name=s.get("long_name", ("", ""))[1],
+                   units=s.get("units", ("", ""))[1], grid_loc=s.get("grid_loc", ("", ""))[1]) for n, s in sec.items()]
+    if src != dst and not os.path.exists(dst):
+        os.symlink(src, dst)
+    rr.write_header(dst, attrs, fields, style=style, end_global=end_global)
+    return attrs
+
+
+def state(m, nt=2):
+    return {(name, tl, n): m.get(name, tl, n) for name, n in STATE + [("TRACER", n) for n in range(2, nt)] for tl in (0, 1)}
+
+
+def same(a, b, first_step=False):
+    """the entries that differ.  first_step: one step after a read, against the uninterrupted run -- RHO(old) is then the density init_ts
+    recomputed from the tracers read (restart.F90 carries no density), where the uninterrupted run holds what its own step left there; the
+    tracers it belongs to are compared, and two more steps on every level is (test_gpu_restart.test_exact_restart)."""
+    return [k for k in a if not np.array_equal(a[k], b[k]) and not (first_step and k == ("RHO", 0, 0))]
+
+
+def resume(pkg, cfg, path, steps):
+    """a context that has already stepped reads the file and goes on; returns (model, dims after the read)"""
+    m = pkg.PopModel(cfg)
+    m.step(); m.step()
+    m.read_restart(path)
+    dims = {n: m.dim(n) for n in ("nsteps_total", "eod", "eod_last")}
+    for _ in range(steps):
+        m.step()
+    return m, dims
+
+
+# ---- a, b: the end-of-day flags -------------------------------------------------------------------------------------------------
+GM_DAY = dict(hmix_tracer=3, ah=0.8e7, gm_kappa_type=1, gm_kappa_freq=2, tmix_opt=0, steps_per_day=6, stepped_bathymetry=1)
+
+
+@pytest.fixture(scope="module")
+def gm_day(pkg, tmp_path_factory):
+    """'bfre' kappa recomputed once a day, six steps a day: the file after step 6 (the end of a day), the state of the uninterrupted
+    run after steps 7 and 10, and the state one step after reading that file with eod = F, eod_last = F (no recompute)"""
+    cfg = named_config("tiny", **GM_DAY)
+    d = tmp_path_factory.mktemp("gm_day")
+    a = pkg.PopModel(cfg)
+    for _ in range(6):
+        a.step()
+    src = str(d / "own.bin")
+    a.write_restart(src)
+    own = parse_hdr(src)["GLOBAL"]
+    a.step(); s7 = state(a)
+    for _ in range(3):
+        a.step()
+    s10 = state(a)
+    a.close()
+    ff = str(d / "ff.bin")
+    reference_header(src, ff, eod=False, eod_last=False)
+    m, _ = resume(pkg, cfg, ff, 1)
+    sff = state(m)
+    m.close()
+    return dict(cfg=cfg, dir=d, src=src, own=own, s7=s7, s10=s10, sff=sff)
+
+
+def test_a_end_of_day_file_recomputes_kappa_in_its_first_step(pkg, gm_day):
+    """A reference file written at the end of a day, with more than one step a day, carries eod = T, eod_last = F.  The next
+    time_manager copies eod to eod_last (time_management.F90:1809), so the first step recomputes KAPPA_VERTICAL (hmix_gm.F90:1277) as the
+    uninterrupted run does.  (Reading the file's eod_last where eod belongs -- this library before it wrote both -- skips the recompute.)"""
+    path = str(gm_day["dir"] / "tf.bin")
+    reference_header(gm_day["src"], path, eod=True, eod_last=False)
+    b, dims = resume(pkg, gm_day["cfg"], path, 1)
+    assert same(state(b), gm_day["s7"], first_step=True) == []
+    for _ in range(3):
+        b.step()
+    assert same(state(b), gm_day["s10"]) == []
+    b.close()
+    assert dims == {"nsteps_total": 6, "eod": 1, "eod_last": 0}
+    # the guard: the flag decides something.  The same file with eod = F is another run.
+    assert not np.array_equal(gm_day["sff"]["TRACER", 1, 0], gm_day["s7"]["TRACER", 1, 0])
+    # the library's own file says the same as the reference's
+    assert gm_day["own"]["eod"] == ("log", "T") and gm_day["own"]["eod_last"] == ("log", "F") and gm_day["own"]["lcoupled_ts"] == ("log", "F")
+
+
+def test_b_file_from_the_step_after_a_day_s_end_does_not_recompute(pkg, gm_day):
+    """eod = F, eod_last = T: the file's eod_last is overwritten before anything reads it, so the step is that of eod = F, eod_last = F"""
+    path = str(gm_day["dir"] / "ft.bin")
+    reference_header(gm_day["src"], path, eod=False, eod_last=True)
+    b, dims = resume(pkg, gm_day["cfg"], path, 1)
+    sft = state(b)
+    b.close()
+    assert same(sft, gm_day["sff"]) == []
+    assert not np.array_equal(sft["TRACER", 1, 0], gm_day["s7"]["TRACER", 1, 0])
+    assert dims == {"nsteps_total": 6, "eod": 0, "eod_last": 1}
+
+
+def test_own_file_without_eod_keeps_its_old_meaning(pkg, gm_day, tmp_path):
+    """Files this library wrote before it wrote eod hold eod in eod_last.  They are known by their history line and by having no eod; a
+    file of anybody else's without eod is read as the reference reads it: eod keeps its default, F."""
+    lines = [ln for ln in open(gm_day["src"] + ".hdr").read().splitlines() if not ln.startswith(("eod:", "lcoupled_ts:"))]
+    old = [ln.replace("eod_last:log: F", "eod_last:log: T") for ln in lines]
+    assert "history:char: written by libpop_amd" in old and "eod_last:log: T" in old
+    for name, text, want in (("old", old, gm_day["s7"]), ("other", [ln.replace("written by libpop_amd", "written by someone") for ln in old], gm_day["sff"])):
+        path = str(tmp_path / (name + ".bin"))
+        os.symlink(gm_day["src"], path)
+        open(path + ".hdr", "w").write("\n".join(text) + "\n")
+        b, dims = resume(pkg, gm_day["cfg"], path, 1)
+        assert same(state(b), want, first_step=name == "old") == [], name
+        assert dims == {"nsteps_total": 6, "eod": int(name == "old"), "eod_last": int(name == "other")}
+        b.close()
+
+
+# ---- c: our own headers under the reference's reader ----------------------------------------------------------------------------
+NML = dict(kmxice=3, lfw_as_salt_flx=1, tfreeze_option=1)
+OWN_CASES = {
+    "plain": (dict(tmix_opt=0, steps_per_day=6), None),
+    "ice-fw": (dict(steps_per_day=6, time_mix_freq=5), "ice"),                 # avgfit: the fit interval of 6 + 2 steps is the day
+    "robert": (dict(tmix_opt=3, robert_alpha=1.0, steps_per_day=6), None),     # alpha = 1: the filter that uses rf_S_prev (with the
+                                                                               # default 0.53 the new time level is filtered too and it is not)
+    "nt4": (dict(tmix_opt=0, steps_per_day=6, nt=4), "iage"),                  # tracer 3 ideal age, tracer 4 without a module
+    "kpp-del4": (dict(tmix_opt=0, steps_per_day=6, vmix_choice=3, km=24, hmix_momentum=4, hmix_tracer=4, am=-1.0e22, ah=-1.0e21), None),
+}
+
+
+@pytest.mark.parametrize("case", list(OWN_CASES))
+def test_c_own_headers_under_the_reference_reader(pkg, tmp_path, case):
+    kw, extra = OWN_CASES[case]
+    cfg = named_config("tiny", **kw)
+    m = pkg.PopModel(cfg, grid=ice_grid(cfg) if extra == "ice" else None)
+    if extra == "ice":
+        m.init_ice(ice_freq_opt="coupled", licecesm2=1, **dict(NML, lfw_as_salt_flx=0))
+        cold_start(m)
+    if extra == "iage":
+        m.init_iage(3)
+    path = str(tmp_path / "own.bin")
+    seen = set()
+    for step in range(1, 10):
+        m.step()
+        flags = (m.dim("eod"), m.dim("eod_last"))
+        if flags in seen:
+            continue
+        seen.add(flags)
+        m.write_restart(path)
+        raw = open(path + ".hdr").read().splitlines()
+        assert max(len(ln) for ln in raw) <= 80
+        exact = parse_hdr(path)
+        names = [n for n in exact if n != "GLOBAL"]
+        hd = rr.read_header(path, fields=names)
+        assert hd.problems == [] and hd.too_long == [] and hd.ignored == []
+        assert hd.title and "written by libpop_amd" in hd.history and hd.conventions
+        for n in names:                                         # the prefix rule lands where the exact rule does
+            assert hd.fields[n]["section"] == n and hd.fields[n]["id"] == int(exact[n]["id"][1]), n
+            assert hd.fields[n]["nfield_dims"] == int(exact[n]["nfield_dims"][1]) and set(hd.fields[n]) <= {"section", "id", "nfield_dims", "long_name", "units", "grid_loc"}
+        # every value parsed, under the type the reference gives that attribute
+        assert set(hd.attrs) | {"title", "history", "conventions"} == set(exact["GLOBAL"])
+        types = {n: t for n, t, _ in rr.reference_globals(0, 0, 0, 0.0, 0, 1.0, cfg.km)}
+        for n, (t, v) in hd.attrs.items():
+            assert rr.is_reference_name(n) or n in EXTENSIONS, n
+            assert t == types.get(n, "int" if n in EXTENSIONS else "r8"), n
+        assert hd.attrs["eod"] == ("log", bool(flags[0])) and hd.attrs["eod_last"] == ("log", bool(flags[1])) and hd.attrs["lcoupled_ts"] == ("log", False)
+        assert hd.attrs["nsteps_total"] == ("int", step) and hd.attrs["dtt"] == ("r8", m.scalar("dtt"))
+        passive = [n for n in names if n not in REFERENCE_SECTIONS]
+        if case == "nt4":
+            assert passive == ["IAGE_CUR", "TRACER04_CUR", "IAGE_OLD", "TRACER04_OLD"]
+        else:
+            assert passive == []
+        if case == "ice-fw":
+            assert hd.attrs["tlast_ice"] == ("r8", m.scalar("tlast_ice")) and "AQICE" in names and "QFLUX" not in names
+        if case == "robert":
+            assert [n for n in hd.attrs if n.startswith("rf_S")] == ["rf_S_prev_TEMP", "rf_S_prev_SALT"]
+    assert {(1, 0), (0, 1), (0, 0)} <= seen                     # an end-of-day step, the step after it, a mid-day step
+    m.close()
+
+
+# ---- e: the Robert filter's scalars ---------------------------------------------------------------------------------------------
+def test_e_robert_filter_scalars_through_a_reference_header(pkg, tmp_path):
+    """rf_S_prev_<tracer> travels in the header next to rf_Svol_prev_<tracer> (restart.F90:1356-1370), which nothing here reads.  One that
+    is missing switches rf_S_prev_valid off for its tracer alone (:516-519): that tracer's first conservation factor is rf_S, not the mean
+    of rf_S and rf_S_prev (the other tracer's step is the same step).  Validity is read from the scalars rf_S_prev1 / rf_S_prev2, NaN
+    when not valid."""
+    cfg = named_config("tiny", tmix_opt=3, robert_alpha=1.0)      # alpha = 1: only then is rf_S_prev used (time_management.F90:897-927)
+    a = pkg.PopModel(cfg)
+    for _ in range(4):
+        a.step()
+    src = str(tmp_path / "own.bin")
+    a.write_restart(src)
+    a.step(); s5 = state(a)
+    a.step(); a.step(); s7 = state(a)
+    a.close()
+    full, cut = str(tmp_path / "full.bin"), str(tmp_path / "cut.bin")
+    attrs = reference_header(src, full, robert_vol=-0.75)
+    names = [n for n, _, _ in attrs]
+    k = names.index("rf_S_prev_TEMP")
+    assert names[k:k + 4] == ["rf_S_prev_TEMP", "rf_S_prev_SALT", "rf_Svol_prev_TEMP", "rf_Svol_prev_SALT"]
+    want = {n: v for n, _, v in attrs}
+    b = pkg.PopModel(cfg)
+    b.step(); b.step()
+    b.read_restart(full)
+    assert b.dim("nsteps_total") == 4
+    assert b.scalar("rf_S_prev1") == want["rf_S_prev_TEMP"] and b.scalar("rf_S_prev2") == want["rf_S_prev_SALT"]
+    b.step()
+    assert same(state(b), s5, first_step=True) == []
+    b.step(); b.step()
+    assert same(state(b), s7) == []
+    # the same context, which holds a valid rf_S_prev of both tracers by now, reads the file without SALT's
+    reference_header(src, cut, robert_vol=-0.75, drop=("rf_S_prev_SALT",))
+    b.read_restart(cut)
+    assert b.scalar("rf_S_prev1") == want["rf_S_prev_TEMP"] and np.isnan(b.scalar("rf_S_prev2"))
+    b.step()
+    sc = state(b)
+    assert all(np.array_equal(sc["TRACER", tl, 0], s5["TRACER", tl, 0]) for tl in (0, 1))
+    assert b.scalar("rf_S_prev2") == b.scalar("rf_S2")            # valid again after a filtered step
+    b.close()
+
+
+# ---- f: ice ---------------------------------------------------------------------------------------------------------------------
+ICE_FIELDS = ("QICE", "AQICE", "FW_FREEZE")
+
+
+def start_ice(pkg, cfg, nml):
+    m = pkg.PopModel(cfg, grid=ice_grid(cfg))
+    m.init_ice(**nml)
+    cold_start(m)
+    return m
+
+
+@pytest.mark.parametrize("kw,nml", [(dict(), dict(NML, lfw_as_salt_flx=0)), (dict(tmix_opt=3), dict(NML, lfw_as_salt_flx=1))], ids=["avgfit-fw", "robert-salt"])
+def test_f_exact_restart_with_ice_through_a_reference_header(pkg, tmp_path, kw, nml):
+    """test_gpu_ice.test_exact_restart_with_ice with the file as the reference writes it: lcoupled_ts = F, AQICE, tlast_ice.  (avgfit: the
+    position inside the averaging interval is this library's extension nsteps_this_interval; the reference restarts an interval.)"""
+    cfg = named_config("tiny", **kw)
+    nml = dict(nml, ice_freq_opt="coupled", licecesm2=1)
+    ref, a = start_ice(pkg, cfg, nml), start_ice(pkg, cfg, nml)
+    for _ in range(6):
+        ref.step()
+    for _ in range(3):
+        a.step()
+    src, path = str(tmp_path / "own.bin"), str(tmp_path / "ref.bin")
+    a.write_restart(src)
+    own = parse_hdr(src)["GLOBAL"]
+    attrs = reference_header(src, path, extra=[("nsteps_this_interval", "int", int(own["nsteps_this_interval"][1]))] if cfg.tmix_opt == 2 else ())
+    assert ("lcoupled_ts", "log", False) in attrs and ("tlast_ice", "r8", a.scalar("tlast_ice")) in attrs and a.scalar("tlast_ice") > 0.0
+    b = start_ice(pkg, cfg, nml)
+    b.read_restart(path)
+    assert b.scalar("tlast_ice") == a.scalar("tlast_ice")
+    for name in ("AQICE", "FW_FREEZE"):
+        assert np.array_equal(a.get(name), b.get(name)), name
+    assert a.get("AQICE").min() < 0.0
+    for _ in range(3):
+        b.step()
+    assert same(state(ref), state(b)) == []
+    for name in ICE_FIELDS:
+        assert np.array_equal(ref.get(name), b.get(name)), name
+    assert ref.scalar("tlast_ice") == b.scalar("tlast_ice")
+    for m in (ref, a, b):
+        m.close()
+
+
+@pytest.mark.parametrize("byteswap", [False, True])
+def test_f_file_from_a_coupled_time_step_carries_qflux(pkg, tmp_path, byteswap):
+    """lcoupled_ts = T (when CESM writes its restarts): the record where AQICE would be is QFLUX (restart.F90:679-697).  It is read into
+    QFLUX, land masked and ghost cells filled (:886-890, 1041-1047); AQICE is what init_ice made it, zero, whatever the context held."""
+    cfg = named_config("tiny")
+    nml = dict(NML, ice_freq_opt="coupled", licecesm2=1)
+    a = start_ice(pkg, cfg, nml)
+    for _ in range(2):
+        a.step()
+    assert a.get("AQICE").min() < 0.0
+    src, path = str(tmp_path / "own.bin"), str(tmp_path / "cpl.bin")
+    a.write_restart(src)
+    nx, ny = cfg.nx_global, cfg.ny_global
+    data = np.fromfile(src, dtype="<f8").reshape(-1, ny, nx)
+    rec = int(parse_hdr(src)["AQICE"]["id"][1]) - 1
+    q = np.random.default_rng(5).standard_normal((ny, nx))      # on land too
+    data[rec] = q
+    data.astype(">f8" if byteswap else "<f8").tofile(path)
+    reference_header(src, path, rename={"AQICE": "QFLUX"}, lcoupled_ts=True, style="compact" if byteswap else "gfortran")
+    a.read_restart(path, byteswap=byteswap)                     # into the context that holds AQICE < 0
+    kmt = a.geti("KMT")
+    want = np.zeros((a.nblocks, a.nyb, a.nxb))
+    for b in range(a.nblocks):
+        blk = a.get_block(b + 1)
+        jj, ii = np.array(blk["j_glob"]), np.array(blk["i_glob"])
+        ok = (jj[:, None] >= 1) & (ii[None, :] >= 1)
+        want[b] = np.where(ok, q[np.clip(jj, 1, ny) - 1][:, np.clip(ii, 1, nx) - 1], 0.0)
+    want = np.where(kmt >= 1, want, 0.0)
+    assert (kmt == 0).sum() > 0 and np.abs(want).max() > 0.0
+    assert np.array_equal(a.get("QFLUX"), want)
+    assert not a.get("AQICE").any()
+    assert a.scalar("tlast_ice") == float(parse_hdr(src)["GLOBAL"]["tlast_ice"][1])
+    # the other way round is refused by name, not silently: a QFLUX file that says lcoupled_ts = F has no AQICE
+    reference_header(src, path, rename={"AQICE": "QFLUX"}, lcoupled_ts=False)
+    with pytest.raises(pkg.PopError, match="could not find field in binary header file: AQICE"):
+        a.read_restart(path, byteswap=byteswap)
+    a.close()
