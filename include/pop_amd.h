@@ -555,6 +555,52 @@ int pop_time_phase(pop_ctx *ctx, const char *phase, int reps, double *avg_ms);
  * pop_time_manager call. */
 int pop_run_phase(pop_ctx *ctx, const char *phase);
 int pop_device_sync(pop_ctx *ctx);
+
+/* ---- time-averaged output (tavg.F90): accumulation on the device, normalisation, reset, streams and the 'bin' file ------------
+ * A tavg entry is one field of the reference's tavg_contents, by its short name ("TEMP", "SSH2", "HBLT" ...; DESIGN.md section 14
+ * lists them and where in the step each is taken).  A name belongs to one stream, 1 .. POP_TAVG_MAX_STREAMS (tavg.F90
+ * max_avail_tavg_streams); the reference's duplicate names (TEMP_2, SSH_2 ...) let a second stream hold the same quantity.
+ * pop_time_manager adds the weight of the step (dtt, 0.5 dtt on an averaging step; tavg_set_flag, tavg.F90:1549-1557) to tavg_sum of
+ * every stream that is on -- host state, kept on a host-only context too -- and the phases of the step accumulate the entries of
+ * those streams where the reference calls accumulate_tavg_field.  With nothing requested, or every stream off, a step launches,
+ * allocates and moves nothing more than before.  All functions return 0 or set pop_last_error.  pop_tavg_request, pop_tavg_set_on
+ * and pop_tavg_reset are refused between pop_time_manager and pop_step_tail of a step. */
+#define POP_TAVG_MAX_STREAMS 9
+#define POP_TAVG_MAX_FIELDS 64
+/* methods, numbered as tavg.F90:75-80 */
+#define POP_TAVG_METHOD_AVG 1
+#define POP_TAVG_METHOD_MIN 2
+#define POP_TAVG_METHOD_MAX 3
+#define POP_TAVG_METHOD_QFLUX 4
+#define POP_TAVG_METHOD_CONSTANT 5
+/* request an entry for a stream, before the first step or between steps; the buffer is allocated here and starts reset, and the
+ * stream is switched on (tavg_start_opt 'nstep', 0).  Refused with a message: an unknown name, a name the reference knows whose call
+ * site is not built, a name already requested in any stream, an entry whose source the configuration does not produce (the
+ * message names the missing switch), more than POP_TAVG_MAX_FIELDS entries. */
+int pop_tavg_request(pop_ctx *ctx, int stream, const char *name);
+int pop_tavg_set_on(pop_ctx *ctx, int stream, int on);                      /* ltavg_on of the stream */
+/* any entry this configuration knows, requested or not: stream (0: not requested), ndims (2 | 3), levels of the buffer, method.
+ * Any of the four pointers may be NULL. */
+int pop_tavg_info(pop_ctx *ctx, const char *name, int *stream, int *ndims, int *nlevels, int *method);
+int pop_tavg_sums(pop_ctx *ctx, int stream, double *tavg_sum, double *tavg_sum_qflux);
+/* the buffer of a requested entry on the local blocks, in the layout pop_get_field uses: (nx_block, ny_block, [nlevels,] nblocks).
+ * normalize = 1: the values tavg_norm_field_all would leave (avg: buffer * (1 / tavg_sum); qflux: buffer * (1 / tavg_sum_qflux); min,
+ * max, constant: as they are), formed in a copy -- the buffer stays as it is.  tavg_sum = 0 is an error, not an abort. */
+int pop_tavg_get(pop_ctx *ctx, const char *name, int normalize, double *host, long long count);
+void *pop_tavg_device_ptr(pop_ctx *ctx, const char *name);
+/* tavg_reset_field_stream: avg / qflux / constant buffers 0, min +1e30, max -1e30; tavg_sum = 0 (and tavg_sum_qflux where the stream
+ * holds a qflux entry) */
+int pop_tavg_reset(pop_ctx *ctx, int stream);
+/* the entries of a stream as a 'bin' file, the format of the restart files: <path> is direct-access, one nx_global x ny_global r8
+ * record per level of every entry; <path>.hdr holds the global attributes tavg_sum, tavg_sum_qflux, nsteps_total and one section per
+ * entry under its short name.  restart_type = 0: normalise, write, reset the stream; 1: write the sums as they are, reset nothing.
+ * Collective over the ranks (rank 0 writes the header, every rank its own rows). */
+int pop_tavg_write(pop_ctx *ctx, int stream, const char *path, int restart_type);
+/* reads a restart_type = 1 file into a context that has made the same requests for the stream: the sums and the physical cells of
+ * every buffer, then a halo update of each buffer.  A field missing from the file is an error that names it. */
+int pop_tavg_read(pop_ctx *ctx, int stream, const char *path);
+/* pop_run_phase / pop_time_phase also know the sites on their own, each run once with the weight of the last pop_time_manager:
+ * "tavg_forcing", "tavg_state", "tavg_tracer", "tavg_vmix", "tavg_hmix", "tavg_btrop". */
 /* run all launches on the host framework's HIP stream (e.g. torch.cuda.current_stream().cuda_stream) */
 int pop_set_stream(pop_ctx *ctx, void *hip_stream);
 

@@ -91,6 +91,9 @@ def lib():
         "pop_init_iage": (ci, [vp, ci]),
         "pop_ice_nml_init": (None, [vp]), "pop_init_ice": (ci, [vp, vp]), "pop_ice_formation": (ci, [vp, ci]),
         "pop_ice_flx_to_coupler": (ci, [vp]), "pop_ice_export_reset": (ci, [vp]), "pop_tfreez_host": (ci, [vp, pd, pd, ll]),
+        "pop_tavg_request": (ci, [vp, ci, cs]), "pop_tavg_set_on": (ci, [vp, ci, ci]), "pop_tavg_info": (ci, [vp, cs, pi, pi, pi, pi]),
+        "pop_tavg_sums": (ci, [vp, ci, pd, pd]), "pop_tavg_get": (ci, [vp, cs, ci, pd, ll]), "pop_tavg_device_ptr": (vp, [vp, cs]),
+        "pop_tavg_reset": (ci, [vp, ci]), "pop_tavg_write": (ci, [vp, ci, cs, ci]), "pop_tavg_read": (ci, [vp, ci, cs]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)       # AttributeError here = the library does not export the ABI
@@ -464,6 +467,50 @@ class PopModel:
         P = C.POINTER(C.c_double)
         self._chk(self.L.pop_tfreez_host(self.h, a.ctypes.data_as(P), out.ctypes.data_as(P), a.size))
         return out
+
+    # ---- time-averaged output (tavg.F90; include/pop_amd.h pop_tavg_*)
+    TAVG_METHOD = {1: "avg", 2: "min", 3: "max", 4: "qflux", 5: "constant"}
+
+    def tavg_request(self, stream, names):
+        """request_tavg_field for every name (one name or a list) in stream 1 .. 9; the stream is on from the first request"""
+        for name in ([names] if isinstance(names, str) else names):
+            self._chk(self.L.pop_tavg_request(self.h, stream, name.encode()))
+
+    def tavg_on(self, stream, flag=True):
+        """ltavg_on of the stream"""
+        self._chk(self.L.pop_tavg_set_on(self.h, stream, 1 if flag else 0))
+
+    def tavg_info(self, name):
+        """dict(stream, ndims, nlevels, method) of an entry this configuration knows; stream 0: not requested"""
+        s, d, l, m = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._chk(self.L.pop_tavg_info(self.h, name.encode(), C.byref(s), C.byref(d), C.byref(l), C.byref(m)))
+        return {"stream": s.value, "ndims": d.value, "nlevels": l.value, "method": self.TAVG_METHOD[m.value]}
+
+    def tavg_sums(self, stream):
+        """(tavg_sum, tavg_sum_qflux) of the stream"""
+        a, b = C.c_double(), C.c_double()
+        self._chk(self.L.pop_tavg_sums(self.h, stream, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def tavg_get(self, name, normalize=True):
+        """the buffer of a requested entry, (nblocks, [nlevels,] ny_block, nx_block); normalize: as tavg_norm_field_all would leave it
+        (the buffer itself stays untouched)"""
+        inf = self.tavg_info(name)
+        shp = (self.nblocks, self.nyb, self.nxb) if inf["ndims"] == 2 else (self.nblocks, inf["nlevels"], self.nyb, self.nxb)
+        a = np.empty(shp, dtype=np.float64)
+        self._chk(self.L.pop_tavg_get(self.h, name.encode(), 1 if normalize else 0, a.ctypes.data_as(C.POINTER(C.c_double)), a.size))
+        return a
+
+    def tavg_reset(self, stream):
+        self._chk(self.L.pop_tavg_reset(self.h, stream))
+
+    def tavg_write(self, stream, path, restart=False):
+        """<path> + <path>.hdr in the format of the restart files.  restart=False: normalise, write, reset the stream; True: the sums as
+        they are, for tavg_read"""
+        self._chk(self.L.pop_tavg_write(self.h, stream, os.fsencode(path), 1 if restart else 0))
+
+    def tavg_read(self, stream, path):
+        self._chk(self.L.pop_tavg_read(self.h, stream, os.fsencode(path)))
 
     # ---- step_mod.F90 sequence
     def time_manager(self):

@@ -22,6 +22,7 @@
 #include "kernels_passive.hpp"
 #include "kernels_ice.hpp"
 #include "kernels_pcg_persist.hpp"
+#include "kernels_tavg.hpp"
 #include <fcntl.h>
 #include <unistd.h>
 #include "rccl_transport.hpp"
@@ -31,6 +32,7 @@ using namespace pop;
 #include "pop_ctx.hpp"
 #include "launch_halo.hpp"
 #include "launch_solvers.hpp"
+#include "launch_tavg.hpp"
 
 namespace {
 
@@ -1381,6 +1383,8 @@ int pop_time_manager(pop_ctx *c) {
   // step_mod.F90:302-320
   if (c->leapfrogts) { c->mixt = c->oldt; c->beta = 1.0 / 3.0; c->c2dtt = 2.0 * c->h.dt[1]; c->c2dtu = 2.0 * c->h.dtu; c->c2dtp = 2.0 * c->h.dtp; }
   else { c->mixt = c->curt; c->beta = 0.5; c->c2dtt = c->h.dt[1]; c->c2dtu = c->h.dtu; c->c2dtp = c->h.dtp; }
+  tavg_set_flag(c);   // step_mod.F90:260-274: right after time_manager
+  c->tavg.in_step = !c->host_only;
   return 0;
 }
 
@@ -1390,6 +1394,7 @@ int pop_dhdt(pop_ctx *c) {
   hipLaunchKernelGGL(k_dhdt, dim3(col_grid(c->g, 256), c->g.nblocks), dim3(256), 0, c->stream, c->g, step_params(c),
                      c->PS[c->curt], c->PS[c->oldt], c->FW_OLD, c->DH, c->DHU);
   HIPCHK(c, hipGetLastError());
+  if (c->tavg.active && tavg_site(c, TS_FORCING)) return 1;
   return 0;
 }
 
@@ -1829,6 +1834,8 @@ int pop_baroclinic_driver(pop_ctx *c) {
   ScopedPhase ph(c, "BAROCLINIC");
   if (c->vmixu_deferred) { c->vmixu_deferred = false; if (phase_impvmixu(c, nullptr)) return 1; }   // a driver call that was never followed by its correct_adjust
   const StepParams sp = step_params(c);
+  // tavg: the velocities and, unless the Robert filter takes them in step_rf, the tracers of the cur level (baroclinic.F90:772-816)
+  if (c->tavg.active && (tavg_site(c, TS_STATE) || (c->h.c.tmix_opt != 3 && tavg_site(c, TS_TRACER)))) return 1;
   // del4 first Laplacians / the anisotropic friction beside the vertical-mixing coefficients: they read only mix-time fields
   const bool tr_side = c->side_del4 && c->h.c.hmix_tracer != 3;
   const bool fork = c->mom_side || tr_side;
@@ -1841,8 +1848,10 @@ int pop_baroclinic_driver(pop_ctx *c) {
     HIPCHK(c, hipEventRecord(c->ev_d2u, c->side));
   }
   if (phase_vmix(c)) return 1;
+  if (c->tavg.active && tavg_site(c, TS_VMIX)) return 1;   // this step's coefficients, computed or swapped in, before K33 is added
   if (fork) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2t, 0));
   if (!tr_side && phase_hmix_tracer(c)) return 1;   // Gent-McWilliams reads and adds to the coefficients vmix just formed
+  if (c->tavg.active && tavg_site(c, TS_HMIX)) return 1;
   const bool fwd = sp.pavg && tracer_fwd_fused(c);
   if (phase_tracer_rhs(c, fwd) || phase_passive_rhs(c)) return 1;
   // several ranks: the exchange of the new tracers' ghost rows runs on the communication stream while the launch stream
@@ -1996,6 +2005,7 @@ static int barotropic_driver(pop_ctx *c, bool update_zx_zy) {
   hipLaunchKernelGGL(k_btrop_fin1, G, B, 0, c->stream, c->g, a);
   hipLaunchKernelGGL(k_btrop_fin2, G, B, 0, c->stream, c->g, sp, a);
   if (halo_update_many(c, {{c->PS[c->newt], 1}, {c->GX[c->newt], 1, 1, 1}, {c->GY[c->newt], 1, 1, 1}})) return 1;   // barotropic.F90:699-729
+  if (c->tavg.active && tavg_site(c, TS_BTROP)) return 1;   // barotropic.F90:687-693
   HIPCHK(c, hipGetLastError());
   return 0;
 }
@@ -2089,6 +2099,7 @@ static int step_rf(pop_ctx *c) {
   HIPCHK(c, hipMemcpyAsync(c->FW_OLD, c->FW, a2 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   launch_state3d(c->g, (const double *)c->TR[0][cu], (const double *)c->TR[1][cu], c->RHO[cu], c->stream);
   launch_state3d(c->g, (const double *)c->TR[0][nw], (const double *)c->TR[1][nw], c->RHO[nw], c->stream);
+  if (c->tavg.active && tavg_site(c, TS_TRACER)) return 1;   // step_mod.F90:1290-1298: the tracers after the filter, ice and the new density
   hipLaunchKernelGGL(k_pguess, dim3((unsigned)((a2 + 255) / 256)), dim3(256), 0, c->stream, a2, c->PGUESS, c->PS[nw], c->PS[cu], c->PS[o]);
   c->oldt = cu; c->curt = nw; c->newt = o;                              // step_mod.F90:1318-1322
   if (!h.rf_nonzero_newtime) for (int n = 0; n < nt; ++n) { c->rf_S_prev[n] = c->rf_S[n]; c->rf_S_prev_valid[n] = true; }
@@ -2140,6 +2151,7 @@ int pop_step_tail(pop_ctx *c) {
     const int tmp = c->oldt; c->oldt = c->curt; c->curt = c->newt; c->newt = tmp;   // step_mod.F90:827-830
   }
   HIPCHK(c, hipGetLastError());
+  c->tavg.in_step = false;
   return 0;
 }
 
@@ -2694,6 +2706,13 @@ int pop_ice_flx_to_coupler(pop_ctx *c) {
     hipLaunchKernelGGL(k_ice_flx_to_coupler<PBC.value>, dim3((c->g.n2 + 255) / 256, c->g.nblocks), dim3(256), 0, c->stream, c->g, a);
   }, c->g.pbc != 0);
   HIPCHK(c, hipGetLastError());
+  if (c->tavg.active) {   // step_mod.F90:844-849: tavg_increment_sum_qflux(const=tlast_ice), then QFLUX once the flux has been formed
+    if (c->tavg.dirty && tavg_build(c)) return 1;
+    if (c->tavg.site[TS_QFLUX].cols.n) {
+      for (int ns = 1; ns <= TAVG_MAX_STREAMS; ++ns) if (c->tavg.on[ns] && c->tavg.has_qflux[ns]) c->tavg.sum_qflux[ns] = c->tavg.sum_qflux[ns] + I.tlast_ice;
+      if (tavg_site(c, TS_QFLUX)) return 1;
+    }
+  }
   return 0;
 }
 int pop_ice_export_reset(pop_ctx *c) {   // ocn_import_export.F90:715-717
@@ -2747,6 +2766,13 @@ static phase_fn_t phase_by_name(const std::string &p) {
   if (p == "hmix_momentum") return [](pop_ctx *x) { return phase_hmix_momentum(x); };
   // the ordered block sums between the two kernels of a fused pcg iteration (k_block_sums<1>, one workgroup per block), as the
   // solver launches it: timing only (the partial array holds whatever the last solve left)
+  // the tavg sites on their own, each once with the weight of the last pop_time_manager (launch_tavg.hpp)
+  if (p == "tavg_forcing") return [](pop_ctx *x) { return tavg_site(x, TS_FORCING); };
+  if (p == "tavg_state") return [](pop_ctx *x) { return tavg_site(x, TS_STATE); };
+  if (p == "tavg_tracer") return [](pop_ctx *x) { return tavg_site(x, TS_TRACER); };
+  if (p == "tavg_vmix") return [](pop_ctx *x) { return tavg_site(x, TS_VMIX); };
+  if (p == "tavg_hmix") return [](pop_ctx *x) { return tavg_site(x, TS_HMIX); };
+  if (p == "tavg_btrop") return [](pop_ctx *x) { return tavg_site(x, TS_BTROP); };
   if (p == "block_sums") return [](pop_ctx *x) { SolveView v = local_view(x); presum(x, v, v.partial, v.blocksum + 2 * v.nblocks_tot); return 0; };
   return nullptr;
 }
@@ -2787,6 +2813,160 @@ int pop_time_phase(pop_ctx *c, const char *phase, int reps, double *avg_ms) {
   float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
   c->d2t_next_valid = false; c->d2u_next_valid = false;
   *avg_ms = ms / std::max(reps, 1);
+  return 0;
+}
+
+// ---- time-averaged output (tavg.F90; kernels_tavg.hpp, launch_tavg.hpp)
+int pop_tavg_request(pop_ctx *c, int ns, const char *name) {
+  if (!c) return 1;
+  if (!name) { c->err = "pop_tavg_request: no name"; return 1; }
+  if (c->h.plan_only) { c->err = "pop_tavg_request: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+  if (tavg_stream_ok(c, ns, "pop_tavg_request") || tavg_between_steps(c, "pop_tavg_request")) return 1;
+  const std::string nm(name);
+  if (const TavgEntry *e = tavg_find(c, name)) { c->err = "pop_tavg_request: " + nm + " is already requested, in stream " + std::to_string(e->stream) + " (a name belongs to one stream)"; return 1; }
+  for (const char *l : tavg_left_out) if (nm == l) { c->err = "pop_tavg_request: " + nm + " is known to the reference, not built (DESIGN.md section 14)"; return 1; }
+  const std::vector<TavgAvail> avail = tavg_avail(c);
+  const TavgAvail *a = nullptr;
+  for (const TavgAvail &x : avail) if (x.name == nm) a = &x;
+  if (!a) { c->err = "pop_tavg_request: unknown tavg field " + nm; return 1; }
+  const std::string miss = tavg_missing(c, a->need);
+  if (!miss.empty()) { c->err = "pop_tavg_request: " + nm + " needs " + miss + ": this configuration does not produce its source"; return 1; }
+  if ((int)c->tavg.req.size() >= TAVG_MAX_FIELDS) { c->err = "pop_tavg_request: more than POP_TAVG_MAX_FIELDS = " + std::to_string(TAVG_MAX_FIELDS) + " entries (" + nm + ")"; return 1; }
+  TavgEntry e;
+  e.name = nm; e.stream = ns; e.site = a->site; e.ndims = a->ndims; e.method = a->method; e.kmax = a->kmax;
+  e.nlev = a->ndims == 3 ? a->kmax : 1;
+  e.expr = a->expr; e.a = a->a; e.b = a->b; e.cst = a->cst; e.cst2 = a->cst2; e.cells = a->cells; e.vint = a->vint;
+  if (!c->host_only) {
+    if (join_side(c, true)) return 1;
+    if (dev_alloc(c, &e.buf, tavg_count(c, e), false) || tavg_fill(c, e)) return 1;
+  }
+  const bool first = !c->tavg.used[ns];
+  c->tavg.req.push_back(e);
+  if (first) c->tavg.on[ns] = true;   // tavg_start_opt 'nstep', 0: on from the request
+  tavg_refresh_flags(c);
+  return 0;
+}
+int pop_tavg_set_on(pop_ctx *c, int ns, int on) {
+  if (!c) return 1;
+  if (tavg_stream_ok(c, ns, "pop_tavg_set_on") || tavg_between_steps(c, "pop_tavg_set_on")) return 1;
+  c->tavg.on[ns] = on != 0;
+  tavg_refresh_flags(c);
+  return 0;
+}
+int pop_tavg_info(pop_ctx *c, const char *name, int *stream, int *ndims, int *nlevels, int *method) {
+  if (!c) return 1;
+  const std::string nm(name ? name : "");
+  for (const char *l : tavg_left_out) if (nm == l) { c->err = "pop_tavg_info: " + nm + " is known to the reference, not built (DESIGN.md section 14)"; return 1; }
+  for (const TavgAvail &a : tavg_avail(c)) {
+    if (a.name != nm) continue;
+    const TavgEntry *e = tavg_find(c, name);
+    if (stream) *stream = e ? e->stream : 0;
+    if (ndims) *ndims = a.ndims;
+    if (nlevels) *nlevels = a.ndims == 3 ? a.kmax : 1;
+    if (method) *method = a.method;
+    return 0;
+  }
+  c->err = "pop_tavg_info: unknown tavg field " + nm;
+  return 1;
+}
+int pop_tavg_sums(pop_ctx *c, int ns, double *tavg_sum, double *tavg_sum_qflux) {
+  if (!c) return 1;
+  if (tavg_stream_ok(c, ns, "pop_tavg_sums")) return 1;
+  if (tavg_sum) *tavg_sum = c->tavg.sum[ns];
+  if (tavg_sum_qflux) *tavg_sum_qflux = c->tavg.sum_qflux[ns];
+  return 0;
+}
+int pop_tavg_get(pop_ctx *c, const char *name, int normalize, double *host, long long count) {
+  if (need_device(c)) return 1;
+  const TavgEntry *e = tavg_find(c, name ? name : "");
+  if (!e) return unknown(c, "pop_tavg_get: not a requested tavg field: ", name ? name : "(null)");
+  if (count_is(c, (long long)tavg_count(c, *e), count, name) || join_side(c, true)) return 1;
+  return tavg_to_host(c, *e, normalize != 0, host);
+}
+void *pop_tavg_device_ptr(pop_ctx *c, const char *name) {
+  if (!c || c->host_only) return nullptr;
+  const TavgEntry *e = tavg_find(c, name ? name : "");
+  return e ? (void *)e->buf : nullptr;
+}
+int pop_tavg_reset(pop_ctx *c, int ns) {
+  if (!c) return 1;
+  if (tavg_stream_ok(c, ns, "pop_tavg_reset") || tavg_between_steps(c, "pop_tavg_reset")) return 1;
+  return tavg_reset_stream(c, ns);
+}
+int pop_tavg_write(pop_ctx *c, int ns, const char *path, int restart_type) {
+  if (need_device(c) || tavg_stream_ok(c, ns, "pop_tavg_write") || tavg_between_steps(c, "pop_tavg_write") || join_side(c, true)) return 1;
+  if (restart_type != 0 && restart_type != 1) { c->err = "pop_tavg_write: restart_type 0 (normalise, write, reset) or 1 (the sums as they are)"; return 1; }
+  const HostModel &h = c->h;
+  TavgState &T = c->tavg;
+  std::vector<RestartField> fields;
+  std::vector<const TavgEntry *> ent;
+  int rec = 1;
+  for (const TavgEntry &e : T.req) {
+    if (e.stream != ns) continue;
+    fields.push_back(RestartField{e.name, "", 1, 0, e.ndims, rec, "", "", "", 0});
+    ent.push_back(&e);
+    rec += e.nlev;
+  }
+  if (ent.empty()) { c->err = "pop_tavg_write: stream " + std::to_string(ns) + " holds no entry"; return 1; }
+  if (restart_type == 0) { double f; for (const TavgEntry *e : ent) if (tavg_factor(c, *e, &f)) return 1; }   // before anything is written
+  if (h.rank == 0) {
+    const std::vector<RestartAttr> at = {{"title", "char", "POP tavg"}, {"history", "char", "written by libpop_amd"}, {"conventions", "char", "POP binary tavg"},
+                                         {"restart_type", "int", std::to_string(restart_type)},
+                                         {"tavg_sum", "r8", fmt_r8(T.sum[ns])}, {"tavg_sum_qflux", "r8", fmt_r8(T.sum_qflux[ns])},
+                                         {"nsteps_total", "int", std::to_string(c->nsteps_total)}};   // tavg.F90:2003-2007
+    if (restart_write_header(h, path, at, fields, c->err)) return 1;
+  }
+  const int fd = open(path, O_WRONLY | O_CREAT, 0644);
+  if (fd < 0) { c->err = std::string("cannot open ") + path + " for writing"; return 1; }
+  std::vector<double> buf((size_t)h.n3 * h.nblocks);
+  int rc = 0;
+  for (size_t i = 0; i < ent.size() && !rc; ++i) {
+    const TavgEntry &e = *ent[i];
+    rc = tavg_to_host(c, e, restart_type == 0, buf.data());
+    for (int k = 0; k < e.nlev && !rc; ++k)
+      rc = restart_slab_io(h, fd, fields[i].id + k, buf.data() + (size_t)k * h.n2, (size_t)e.nlev * h.n2, true, false, c->err);
+  }
+  if (close(fd) != 0 && !rc) { c->err = "tavg: close failed"; rc = 1; }
+  if (rc) return rc;
+  return restart_type == 0 ? tavg_reset_stream(c, ns) : 0;
+}
+int pop_tavg_read(pop_ctx *c, int ns, const char *path) {
+  if (need_device(c) || tavg_stream_ok(c, ns, "pop_tavg_read") || tavg_between_steps(c, "pop_tavg_read") || join_side(c, true)) return 1;
+  const HostModel &h = c->h;
+  TavgState &T = c->tavg;
+  std::map<std::string, std::map<std::string, std::string>> sec;
+  std::vector<std::string> order;
+  if (restart_parse_header(path, sec, order, c->err)) return 1;
+  std::map<std::string, std::string> &g = sec["GLOBAL"];
+  if (!g.count("tavg_sum") || !g.count("tavg_sum_qflux")) { c->err = "pop_tavg_read: header has no tavg_sum / tavg_sum_qflux"; return 1; }
+  if (g.count("restart_type") && atoi(g["restart_type"].c_str()) != 1) { c->err = "pop_tavg_read: the file holds normalised fields (restart_type 0), not the sums"; return 1; }
+  std::vector<std::pair<TavgEntry *, int>> ent;
+  for (TavgEntry &e : T.req) {
+    if (e.stream != ns) continue;
+    auto it = sec.end();
+    for (const std::string &s : order) if (s == e.name) it = sec.find(s);
+    if (it == sec.end() || !it->second.count("id")) { c->err = "could not find field in binary header file: " + e.name; return 1; }
+    ent.push_back({&e, atoi(it->second["id"].c_str())});
+  }
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) { c->err = std::string("cannot open ") + path; return 1; }
+  std::vector<double> buf((size_t)h.n3 * h.nblocks);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int rc = 0;
+  for (auto &pe : ent) {
+    const TavgEntry &e = *pe.first;
+    const size_t n = tavg_count(c, e);
+    std::fill(buf.begin(), buf.begin() + n, 0.0);
+    for (int k = 0; k < e.nlev && !rc; ++k)
+      rc = restart_slab_io(h, fd, pe.second + k, buf.data() + (size_t)k * h.n2, (size_t)e.nlev * h.n2, false, false, c->err);
+    if (rc) break;
+    if (hipMemcpy(e.buf, buf.data(), n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { c->err = "tavg: device copy failed"; rc = 1; break; }
+    if (halo_update(c, e.buf, e.nlev, 0.0)) { rc = 1; break; }
+  }
+  close(fd);
+  if (rc) return rc;
+  T.sum[ns] = strtod(g["tavg_sum"].c_str(), nullptr);
+  T.sum_qflux[ns] = strtod(g["tavg_sum_qflux"].c_str(), nullptr);
   return 0;
 }
 

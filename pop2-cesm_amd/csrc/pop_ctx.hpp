@@ -15,6 +15,34 @@ struct PhaseTimer { double ms = 0; int calls = 0; };
 
 struct DevPeer { int rank; int *send_src = nullptr, *recv_dst = nullptr; int nsend = 0, nrecv = 0; };
 
+// ---- time-averaged output (tavg.F90; launch_tavg.hpp): the requested entries, the streams and the launch tables of the sites
+enum TavgSite { TS_FORCING = 0, TS_STATE, TS_TRACER, TS_VMIX, TS_HMIX, TS_BTROP, TS_QFLUX, TS_NSITES };
+struct TavgEntry {
+  std::string name;
+  int stream = 0, site = 0, ndims = 2, method = TAVG_AVG;
+  int kmax = 1;              // levels the entry is fed from: km for a 3-D entry, 1 .. 8 for U1_8, km for RHO_VINT
+  int nlev = 1;              // levels of the buffer
+  int expr = TX_X, a = -1, b = -1;   // source ids (launch_tavg.hpp TavgSid)
+  double cst = 0.0, cst2 = 0.0;
+  bool cells = false;        // served by k_tavg_cells (else k_tavg_columns)
+  bool vint = false;         // columns: fed once per level
+  double *buf = nullptr;     // device, (nxb, nyb, nlev, nblocks); null on a host-only context
+};
+struct TavgSiteTab { TavgTable cells{}, cols{}; int sid_cells[TAVG_MAX_SRC] = {}, sid_cols[TAVG_MAX_SRC] = {}; bool vint_psurf = false; };
+struct TavgState {
+  std::vector<TavgEntry> req;
+  bool on[TAVG_MAX_STREAMS + 1] = {};               // ltavg_on
+  bool used[TAVG_MAX_STREAMS + 1] = {};             // the stream holds an entry
+  bool has_qflux[TAVG_MAX_STREAMS + 1] = {};
+  double sum[TAVG_MAX_STREAMS + 1] = {}, sum_qflux[TAVG_MAX_STREAMS + 1] = {};   // tavg_sum, tavg_sum_qflux
+  double dtavg = 0.0;                               // weight of the step pop_time_manager last set up
+  bool active = false;                              // some entry's stream is on: the one flag the sites of a step test
+  bool in_step = false;                             // between pop_time_manager and pop_step_tail
+  bool dirty = true;                                // the tables below are out of date (request list or on/off state changed)
+  TavgSiteTab site[TS_NSITES];
+  double *scratch = nullptr;                        // normalise-into-a-copy: one 3-D field
+};
+
 struct pop_ctx {
   HostModel h;
   bool host_only = true;
@@ -173,6 +201,7 @@ struct pop_ctx {
   bool phase_timing = false;   // inside pop_time_phase: kernels only
   double *op_scratch = nullptr;   // pop_operator_host: four block-sized 2-D arrays
   bool prio_on = false; int prio_least = 0;   // stream priorities in use; the lowest one
+  TavgState tavg;
 };
 
 namespace {

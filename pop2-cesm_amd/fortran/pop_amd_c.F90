@@ -447,6 +447,55 @@
          real (c_double), intent(out) :: TFRZ(*)
          integer (c_long_long), value :: count
       end function
+      ! ---- time-averaged output (tavg.F90)
+      integer (c_int) function pop_tavg_request(ctx, stream, name) bind(C, name='pop_tavg_request')
+         import :: c_int, c_ptr, c_char
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: stream
+         character (kind=c_char), intent(in) :: name(*)
+      end function
+      integer (c_int) function pop_tavg_set_on(ctx, stream, on) bind(C, name='pop_tavg_set_on')
+         import :: c_int, c_ptr
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: stream, on
+      end function
+      integer (c_int) function pop_tavg_info(ctx, name, stream, ndims, nlevels, method) bind(C, name='pop_tavg_info')
+         import :: c_int, c_ptr, c_char
+         type (c_ptr), value :: ctx
+         character (kind=c_char), intent(in) :: name(*)
+         integer (c_int), intent(out) :: stream, ndims, nlevels, method
+      end function
+      integer (c_int) function pop_tavg_sums(ctx, stream, tavg_sum, tavg_sum_qflux) bind(C, name='pop_tavg_sums')
+         import :: c_int, c_ptr, c_double
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: stream
+         real (c_double), intent(out) :: tavg_sum, tavg_sum_qflux
+      end function
+      integer (c_int) function pop_tavg_get(ctx, name, normalize, host, count) bind(C, name='pop_tavg_get')
+         import :: c_int, c_ptr, c_char, c_double, c_long_long
+         type (c_ptr), value :: ctx
+         character (kind=c_char), intent(in) :: name(*)
+         integer (c_int), value :: normalize
+         real (c_double), intent(out) :: host(*)
+         integer (c_long_long), value :: count
+      end function
+      integer (c_int) function pop_tavg_reset(ctx, stream) bind(C, name='pop_tavg_reset')
+         import :: c_int, c_ptr
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: stream
+      end function
+      integer (c_int) function pop_tavg_write(ctx, stream, path, restart_type) bind(C, name='pop_tavg_write')
+         import :: c_int, c_ptr, c_char
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: stream, restart_type
+         character (kind=c_char), intent(in) :: path(*)
+      end function
+      integer (c_int) function pop_tavg_read(ctx, stream, path) bind(C, name='pop_tavg_read')
+         import :: c_int, c_ptr, c_char
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: stream
+         character (kind=c_char), intent(in) :: path(*)
+      end function
    end interface
 
  contains

@@ -979,3 +979,86 @@
       t = pop_get_scalar(pop_ctx, cstr('tlast_ice'))
    end function
  end module ice
+
+!-----------------------------------------------------------------------
+ module tavg                 ! source/tavg.F90: requests, streams, sums and the 'bin' file; the accumulation runs inside the library's step
+   use kinds_mod
+   use pop_amd_c
+   implicit none
+   private
+   integer (int_kind), parameter, public :: max_avail_tavg_streams = 9          ! tavg.F90:83
+   integer (int_kind), parameter, public :: tavg_method_avg = 1, tavg_method_min = 2, tavg_method_max = 3, &
+      tavg_method_qflux = 4, tavg_method_constant = 5                            ! tavg.F90:75-80
+   public :: request_tavg_field, tavg_requested, tavg_set_on, tavg_sum, tavg_sum_qflux, tavg_reset_field_stream, &
+             tavg_field_levels, tavg_get_field, write_tavg, read_tavg
+ contains
+   ! request_tavg_field (tavg.F90:3497): short_name into stream ns; the stream is on from its first request
+   subroutine request_tavg_field(short_name, ns, errorCode)
+      character (*), intent(in) :: short_name
+      integer (int_kind), intent(in) :: ns
+      integer (int_kind), intent(out) :: errorCode
+      errorCode = pop_tavg_request(pop_ctx, ns, cstr(short_name))
+   end subroutine
+   ! tavg_requested(id) of the reference by name
+   function tavg_requested(short_name)
+      character (*), intent(in) :: short_name
+      logical (log_kind) :: tavg_requested
+      integer (c_int) :: ierr, ns, ndims, nlev, method
+      ierr = pop_tavg_info(pop_ctx, cstr(short_name), ns, ndims, nlev, method)
+      tavg_requested = ierr == 0 .and. ns > 0
+   end function
+   ! ltavg_on(ns) = flag, between steps
+   subroutine tavg_set_on(ns, flag, errorCode)
+      integer (int_kind), intent(in) :: ns
+      logical (log_kind), intent(in) :: flag
+      integer (int_kind), intent(out) :: errorCode
+      errorCode = pop_tavg_set_on(pop_ctx, ns, merge(1, 0, flag))
+   end subroutine
+   function tavg_sum(ns)
+      integer (int_kind), intent(in) :: ns
+      real (r8) :: tavg_sum, q
+      integer (c_int) :: ierr
+      ierr = pop_tavg_sums(pop_ctx, ns, tavg_sum, q)
+   end function
+   function tavg_sum_qflux(ns)
+      integer (int_kind), intent(in) :: ns
+      real (r8) :: tavg_sum_qflux, s
+      integer (c_int) :: ierr
+      ierr = pop_tavg_sums(pop_ctx, ns, s, tavg_sum_qflux)
+   end function
+   subroutine tavg_reset_field_stream(ns, errorCode)       ! tavg.F90:3746
+      integer (int_kind), intent(in) :: ns
+      integer (int_kind), intent(out) :: errorCode
+      errorCode = pop_tavg_reset(pop_ctx, ns)
+   end subroutine
+   ! levels of the buffer of an entry (1: a 2-D entry); 0: not an entry
+   function tavg_field_levels(short_name)
+      character (*), intent(in) :: short_name
+      integer (int_kind) :: tavg_field_levels
+      integer (c_int) :: ierr, ns, ndims, method
+      ierr = pop_tavg_info(pop_ctx, cstr(short_name), ns, ndims, tavg_field_levels, method)
+      if (ierr /= 0) tavg_field_levels = 0
+   end function
+   ! the buffer of a requested entry on the local blocks, (nx_block, ny_block, levels, nblocks_clinic); normalized: as
+   ! tavg_norm_field_all would leave it (the buffer itself stays as it is)
+   subroutine tavg_get_field(short_name, normalized, FIELD, errorCode)
+      character (*), intent(in) :: short_name
+      logical (log_kind), intent(in) :: normalized
+      real (r8), dimension(:,:,:,:), intent(out) :: FIELD
+      integer (int_kind), intent(out) :: errorCode
+      errorCode = pop_tavg_get(pop_ctx, cstr(short_name), merge(1, 0, normalized), FIELD, int(size(FIELD), c_long_long))
+   end subroutine
+   ! write_tavg (tavg.F90:1571): restart_type 0 normalises, writes and resets the stream; 1 writes the sums as they are
+   subroutine write_tavg(ns, filename, restart_type, errorCode)
+      integer (int_kind), intent(in) :: ns, restart_type
+      character (*), intent(in) :: filename
+      integer (int_kind), intent(out) :: errorCode
+      errorCode = pop_tavg_write(pop_ctx, ns, cstr(filename), restart_type)
+   end subroutine
+   subroutine read_tavg(ns, filename, errorCode)            ! tavg.F90:2180
+      integer (int_kind), intent(in) :: ns
+      character (*), intent(in) :: filename
+      integer (int_kind), intent(out) :: errorCode
+      errorCode = pop_tavg_read(pop_ctx, ns, cstr(filename))
+   end subroutine
+ end module tavg

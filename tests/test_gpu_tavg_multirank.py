@@ -1,0 +1,15 @@
+"""Time-averaged output over several ranks (tests/mr_gpu_tavg.py): every rank's buffers of TEMP, KE, SSH, HBLT, TEMP_MAX and RHO_VINT
+and the sums of both streams are bit for bit those of the single-rank run, ghost cells included, and the tavg file the ranks write
+together equals the single-rank file byte for byte, header included."""
+import os
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_two_ranks_equal_single_rank():
+    from test_gpu_multirank import _run_check
+    _run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_tavg.py"), "--config", "tiny", "--steps", "3",
+                "--kw", "vmix_choice=3,km=24"], 300)
