@@ -9,10 +9,13 @@
 //                (define_field_binary :760-880); the separator is ':' (io_binary.F90:59)
 // Every rank writes / reads the rows of its own blocks at their place in the global slab (pwrite / pread on the
 // shared file), so no gather is needed; rank 0 writes the header.
+// The tavg files (tavg.F90 write_tavg / read_tavg, 'bin') have the same layout; slab_file_write and slab_file_read below move
+// either kind, and the entry points of pop_amd.hip supply only what a field is on the device.
 #include <fcntl.h>
 #include <unistd.h>
+#include <algorithm>
 #include <fstream>
-#include <sstream>
+#include <utility>
 #include "pop_internal.hpp"
 
 namespace pop {
@@ -31,8 +34,8 @@ std::vector<RestartField> restart_fields(const HostModel &h) {
   std::vector<RestartField> f;
   int rec = 1;
   auto add = [&](const char *name, const char *dev, int tl, int n, int ndims, const char *ln, const char *units, const char *loc, int mask) {
-    f.push_back(RestartField{name, dev, tl, n, ndims, rec, ln, units, loc, mask});
-    rec += ndims == 3 ? h.km : 1;
+    f.push_back(RestartField{name, ndims, ndims == 3 ? h.km : 1, rec, dev, tl, n, mask, ln, units, loc});
+    rec += f.back().nlev;
   };
   add("UBTROP_CUR", "UBTROP", 1, 0, 2, "U barotropic velocity at current time", "cm/s", "2220", 1);
   add("UBTROP_OLD", "UBTROP", 0, 0, 2, "U barotropic velocity at old time", "cm/s", "2220", 1);
@@ -68,9 +71,9 @@ std::vector<RestartField> restart_fields(const HostModel &h) {
 }
 
 static std::string list_directed(const std::string &v) { return " " + v; }   // write(line(n:),*) leaves a leading blank
+std::string fmt_r8(double v) { char b[40]; snprintf(b, sizeof b, "%.17g", v); return b; }
 
-int restart_write_header(const HostModel &h, const std::string &path, const std::vector<RestartAttr> &attrs,
-                         const std::vector<RestartField> &fields, std::string &err) {
+static int restart_write_header(const std::string &path, const std::vector<RestartAttr> &attrs, const std::vector<RestartField> &fields, std::string &err) {
   std::ofstream o(path + ".hdr");
   if (!o) { err = "cannot open " + path + ".hdr for writing"; return 1; }
   o << "&GLOBAL\n";
@@ -85,15 +88,13 @@ int restart_write_header(const HostModel &h, const std::string &path, const std:
     o << "nfield_dims:int:" << list_directed(std::to_string(f.ndims)) << '\n';
     o << "/\n";
   }
-  (void)h;
   return o.good() ? 0 : 1;
 }
 
 // sections of a header file: name -> (attribute -> value), values trimmed; the type tag is dropped.  `order` lists the section
 // names as they stand in the file.  As the reference reads it: each line is its first 80 columns ('(a80)', io_binary.F90:229, 985),
 // and of two sections with one name the first counts (define_field_binary searches from the top, :978-989)
-int restart_parse_header(const std::string &path, std::map<std::string, std::map<std::string, std::string>> &sec,
-                         std::vector<std::string> &order, std::string &err) {
+int restart_parse_header(const std::string &path, RestartHeader &hd, std::string &err) {
   std::ifstream in(path + ".hdr");
   if (!in) { err = "cannot open " + path + ".hdr"; return 1; }
   auto trim = [](std::string s) {
@@ -107,7 +108,7 @@ int restart_parse_header(const std::string &path, std::map<std::string, std::map
     if (line.empty()) continue;
     if (line[0] == '&') {
       cur = trim(line.substr(1));
-      if (sec.count(cur)) cur.clear(); else { sec[cur]; order.push_back(cur); }
+      if (hd.sec.count(cur)) cur.clear(); else { hd.sec[cur]; hd.order.push_back(cur); }
       continue;
     }
     if (line[0] == '/') { cur.clear(); continue; }
@@ -116,16 +117,35 @@ int restart_parse_header(const std::string &path, std::map<std::string, std::map
     if (p1 == std::string::npos) continue;
     const size_t p2 = line.find(':', p1 + 1);
     if (p2 == std::string::npos) continue;
-    sec[cur][trim(line.substr(0, p1))] = trim(line.substr(p2 + 1));
+    hd.sec[cur][trim(line.substr(0, p1))] = trim(line.substr(p2 + 1));
   }
   return 0;
 }
 
-// define_field_binary :979-989: a field's section is the first line of the file that BEGINS with "&<short_name>", so a section
-// whose name merely starts with the one wanted is taken if it comes first.  Empty: no such section.
-std::string restart_find_section(const std::vector<std::string> &order, const std::string &name) {
-  for (const std::string &s : order) if (s.compare(0, name.size(), name) == 0) return s;
-  return std::string();
+const std::string *RestartHeader::attr(const std::string &a) const {
+  const auto g = sec.find("GLOBAL");
+  return g == sec.end() || !g->second.count(a) ? nullptr : &g->second.at(a);
+}
+bool RestartHeader::logical(const std::string &a) const {   // list-directed logical: T, F, .TRUE., .false., ...
+  const std::string v = text(a);
+  const size_t k = v.find_first_not_of(" .");
+  return k != std::string::npos && (v[k] == 'T' || v[k] == 't');
+}
+// First record and nfield_dims (0: the section does not say) of a field; false: no section of that name, or one without "id".
+//   PREFIX  pop_read_restart.  define_field_binary :979-989 takes the first line of the file that BEGINS with "&<short_name>", so a
+//           section whose name merely starts with the one wanted is taken if it comes first; the reference's files are read as it reads them.
+//   EXACT   pop_tavg_read.  TEMP and TEMP_2 are both tavg names and a stream lists them in request order: TEMP_2 must not answer for
+//           TEMP.  Only this library writes these files, so there is no foreign reader to follow.
+bool RestartHeader::find(const std::string &name, Rule rule, int *id, int *ndims) const {
+  for (const std::string &s : order) {
+    if (rule == EXACT ? s != name : s.compare(0, name.size(), name) != 0) continue;
+    const std::map<std::string, std::string> &a = sec.at(s);
+    if (!a.count("id")) return false;
+    *id = atoi(a.at("id").c_str());
+    *ndims = a.count("nfield_dims") ? atoi(a.at("nfield_dims").c_str()) : 0;
+    return true;
+  }
+  return false;
 }
 
 static inline double bswap(double v) {
@@ -137,8 +157,8 @@ static inline double bswap(double v) {
 }
 
 // one slab (record `rec`, 1-based) <-> the physical cells of the local blocks; `loc` points at the level of local
-// block 0 and blocks are `blk_stride` doubles apart (n2 for a 2-D field, n3 for one level of a 3-D field)
-int restart_slab_io(const HostModel &h, int fd, long long rec, double *loc, size_t blk_stride, bool write, bool swap, std::string &err) {
+// block 0 and blocks are `blk_stride` doubles apart.  The texts say "restart" for a tavg file too: they are what callers match.
+static int restart_slab_io(const HostModel &h, int fd, long long rec, double *loc, size_t blk_stride, bool write, bool swap, std::string &err) {
   const long long nx = h.c.nx_global, ny = h.c.ny_global, base = (rec - 1) * nx * ny;
   for (int lb = 0; lb < h.nblocks; ++lb) {
     const BlockInfo &B = h.all_blocks[h.local_ids[lb] - 1];
@@ -164,6 +184,41 @@ int restart_slab_io(const HostModel &h, int fd, long long rec, double *loc, size
     }
   }
   return 0;
+}
+
+struct Fd { int fd; ~Fd() { if (fd >= 0) ::close(fd); } };   // closed on every return path
+// The walk over an open file, either way: for every field zeros in buf, then fn and the records (write) or the records and fn (read).
+// buf is (nxb, nyb, nlev, nblocks): blocks are nlev * n2 apart, which for a 3-D restart field (nlev = km) is n3 (host_setup.cpp:
+// n3 = n2 * km); no field has more than km levels, so one 3-D field bounds it.  The first failure ends the walk.
+static int slab_walk(const HostModel &h, int fd, const std::vector<RestartField> &fields, bool write, bool swap, const SlabFieldFn &fn, std::string &err) {
+  std::vector<double> buf((size_t)h.n3 * h.nblocks);
+  for (size_t i = 0; i < fields.size(); ++i) {
+    const RestartField &f = fields[i];
+    std::fill(buf.begin(), buf.begin() + (size_t)f.nlev * h.n2 * h.nblocks, 0.0);
+    if (write && fn(i, buf.data())) return 1;
+    for (int k = 0; k < f.nlev; ++k)
+      if (restart_slab_io(h, fd, f.id + k, buf.data() + (size_t)k * h.n2, (size_t)f.nlev * h.n2, write, swap, err)) return 1;
+    if (!write && fn(i, buf.data())) return 1;
+  }
+  return 0;
+}
+
+// Header by rank 0, then every rank puts its part of each field into the one file: fetch(i, buf) fills buf with field i (or leaves the
+// zeros it is given), records id .. id + nlev - 1 are written.  The file is never truncated: the other ranks write into it too.
+int slab_file_write(const HostModel &h, const std::string &path, const std::vector<RestartAttr> &attrs, const std::vector<RestartField> &fields, const SlabFieldFn &fetch, const std::string &tag, std::string &err) {
+  if (h.rank == 0 && restart_write_header(path, attrs, fields, err)) return 1;
+  Fd f{open(path.c_str(), O_WRONLY | O_CREAT, 0644)};
+  if (f.fd < 0) { err = "cannot open " + path + " for writing"; return 1; }
+  if (slab_walk(h, f.fd, fields, true, false, fetch, err)) return 1;
+  if (::close(std::exchange(f.fd, -1)) != 0) { err = tag + ": close failed"; return 1; }   // the one close that is checked; f is left with nothing to do
+  return 0;
+}
+// Every field of `wanted` (id: its first record, from the header): its records, then store(i, buf).  What was stored before a failure
+// stays stored -- the reference's reader has no rollback either.
+int slab_file_read(const HostModel &h, const std::string &path, const std::vector<RestartField> &wanted, bool swap, const SlabFieldFn &store, std::string &err) {
+  Fd f{open(path.c_str(), O_RDONLY)};
+  if (f.fd < 0) { err = "cannot open " + path; return 1; }
+  return slab_walk(h, f.fd, wanted, false, swap, store, err);
 }
 
 // read_restart :881-935: values outside the ocean are reset (CALCU / CALCT masks in 2-D, k > KMU / KMT in 3-D)

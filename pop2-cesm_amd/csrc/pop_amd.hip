@@ -23,8 +23,6 @@
 #include "kernels_ice.hpp"
 #include "kernels_pcg_persist.hpp"
 #include "kernels_tavg.hpp"
-#include <fcntl.h>
-#include <unistd.h>
 #include "rccl_transport.hpp"
 
 using namespace pop;
@@ -1205,111 +1203,91 @@ void *pop_field_device_ptr(pop_ctx *c, const char *name, int tl, int n) {
 }
 
 // ---- restart files (restart.F90 write_restart :1095-1715, read_restart :184-1088; 'bin' format of io_binary.F90)
-static std::string fmt_r8(double v) { char b[40]; snprintf(b, sizeof b, "%.17g", v); return b; }
+// The files themselves -- header text, records, each rank's place in them -- are host_restart.cpp's (slab_file_write, slab_file_read); here is
+// what a field is on the device and what state goes with it.
+// device pointer and size of restart field f, checked against what its records hold
+static int restart_field_ptr(pop_ctx *c, const RestartField &f, double **p, size_t *bytes) {
+  long long n;
+  if (resolve(c, f.dev, f.tl, f.n, p, &n) || n != (long long)f.nlev * c->g.n2 * c->g.nblocks) { c->err = "restart: unknown field " + f.dev; return 1; }
+  *bytes = (size_t)n * sizeof(double);
+  return 0;
+}
 int pop_write_restart(pop_ctx *c, const char *path) {
   if (need_device(c) || join_side(c)) return 1;
   const HostModel &h = c->h;
   const std::vector<RestartField> fields = restart_fields(h);
-  if (h.rank == 0) {
-    // calendar of a run that starts 0001-01-01 00:00 with 365-day years (time_management.F90 defaults)
-    const double secs = (double)c->nsteps_total * h.dtt;
-    const long long day = (long long)(secs / 86400.0);
-    const int sod = (int)(secs - 86400.0 * (double)day);
-    static const int mdays[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
-    int doy = (int)(day % 365), month = 1;
-    while (doy >= mdays[month - 1]) { doy -= mdays[month - 1]; ++month; }
-    std::vector<RestartAttr> at = {
-      {"title", "char", "POP restart"}, {"history", "char", "written by libpop_amd"}, {"conventions", "char", "POP binary restart"},
-      {"runid", "char", "pop_amd"}, {"iyear", "int", std::to_string(1 + day / 365)}, {"imonth", "int", std::to_string(month)},
-      {"iday", "int", std::to_string(doy + 1)}, {"ihour", "int", std::to_string(sod / 3600)}, {"iminute", "int", std::to_string(sod % 3600 / 60)},
-      {"isecond", "int", std::to_string(sod % 60)}, {"iyear0", "int", "1"}, {"imonth0", "int", "1"}, {"iday0", "int", "1"},
-      {"ihour0", "int", "0"}, {"iminute0", "int", "0"}, {"isecond0", "int", "0"}, {"dtt", "r8", fmt_r8(h.dtt)},
-      {"elapsed_days", "int", std::to_string(day)}, {"seconds_this_day", "r8", fmt_r8((double)sod)},
-      {"nsteps_total", "int", std::to_string(c->nsteps_total)},
-      {"nsteps_this_interval", "int", std::to_string(c->nsteps_this_interval)},   // extension: exact restart inside an averaging interval
-      // restart.F90:1313-1314: both flags as they stand after the step that has just finished.  The next time_manager copies eod into
-      // eod_last (time_management.F90:1809) before it resets eod (:2110), so the file's eod decides the first step after the restart
-      {"eod", "log", c->eod ? "T" : "F"}, {"eod_last", "log", c->eod_last ? "T" : "F"},
-      {"lcoupled_ts", "log", "F"},   // restart.F90:1333: never a coupled time step here, so the ice record is AQICE, not QFLUX (:1477-1489)
-    };
-    if (h.ice) at.push_back({"tlast_ice", "r8", fmt_r8(c->ice.tlast_ice)});   // restart.F90:1332
-    if (h.c.tmix_opt == 3)
-      for (int n = 0; n < h.nt; ++n) if (c->rf_S_prev_valid[n]) at.push_back({"rf_S_prev_" + restart_tracer_name(h, n), "r8", fmt_r8(c->rf_S_prev[n])});
-    if (restart_write_header(h, path, at, fields, c->err)) return 1;
-  }
-  const int fd = open(path, O_WRONLY | O_CREAT, 0644);
-  if (fd < 0) { c->err = std::string("cannot open ") + path + " for writing"; return 1; }
-  const size_t a2 = (size_t)c->g.n2 * c->g.nblocks, a3 = (size_t)c->g.n3 * c->g.nblocks;
-  std::vector<double> buf(a3);
+  // calendar of a run that starts 0001-01-01 00:00 with 365-day years (time_management.F90 defaults)
+  const double secs = (double)c->nsteps_total * h.dtt;
+  const long long day = (long long)(secs / 86400.0);
+  const int sod = (int)(secs - 86400.0 * (double)day);
+  static const int mdays[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
+  int doy = (int)(day % 365), month = 1;
+  while (doy >= mdays[month - 1]) { doy -= mdays[month - 1]; ++month; }
+  std::vector<RestartAttr> at = {
+    {"title", "char", "POP restart"}, {"history", "char", "written by libpop_amd"}, {"conventions", "char", "POP binary restart"},
+    {"runid", "char", "pop_amd"}, {"iyear", "int", std::to_string(1 + day / 365)}, {"imonth", "int", std::to_string(month)},
+    {"iday", "int", std::to_string(doy + 1)}, {"ihour", "int", std::to_string(sod / 3600)}, {"iminute", "int", std::to_string(sod % 3600 / 60)},
+    {"isecond", "int", std::to_string(sod % 60)}, {"iyear0", "int", "1"}, {"imonth0", "int", "1"}, {"iday0", "int", "1"},
+    {"ihour0", "int", "0"}, {"iminute0", "int", "0"}, {"isecond0", "int", "0"}, {"dtt", "r8", fmt_r8(h.dtt)},
+    {"elapsed_days", "int", std::to_string(day)}, {"seconds_this_day", "r8", fmt_r8((double)sod)},
+    {"nsteps_total", "int", std::to_string(c->nsteps_total)},
+    {"nsteps_this_interval", "int", std::to_string(c->nsteps_this_interval)},   // extension: exact restart inside an averaging interval
+    // restart.F90:1313-1314: both flags as they stand after the step that has just finished.  The next time_manager copies eod into
+    // eod_last (time_management.F90:1809) before it resets eod (:2110), so the file's eod decides the first step after the restart
+    {"eod", "log", c->eod ? "T" : "F"}, {"eod_last", "log", c->eod_last ? "T" : "F"},
+    {"lcoupled_ts", "log", "F"},   // restart.F90:1333: never a coupled time step here, so the ice record is AQICE, not QFLUX (:1477-1489)
+  };
+  if (h.ice) at.push_back({"tlast_ice", "r8", fmt_r8(c->ice.tlast_ice)});   // restart.F90:1332
+  if (h.c.tmix_opt == 3)
+    for (int n = 0; n < h.nt; ++n) if (c->rf_S_prev_valid[n]) at.push_back({"rf_S_prev_" + restart_tracer_name(h, n), "r8", fmt_r8(c->rf_S_prev[n])});
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  int rc = 0;
-  for (const RestartField &f : fields) {
-    const size_t cnt = f.ndims == 3 ? a3 : a2;
-    if (f.dev.empty()) std::fill(buf.begin(), buf.begin() + cnt, 0.0);
-    else {
-      double *p; long long n;
-      if (resolve(c, f.dev, f.tl, f.n, &p, &n) || (size_t)n != cnt) { c->err = "restart: unknown field " + f.dev; rc = 1; break; }
-      if (hipMemcpy(buf.data(), p, cnt * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { c->err = "restart: device copy failed"; rc = 1; break; }
-    }
-    const int nz = f.ndims == 3 ? h.km : 1;
-    for (int k = 0; k < nz && !rc; ++k)
-      rc = restart_slab_io(h, fd, f.id + k, buf.data() + (size_t)k * h.n2, f.ndims == 3 ? h.n3 : h.n2, true, false, c->err);
-    if (rc) break;
-  }
-  if (close(fd) != 0 && !rc) { c->err = "restart: close failed"; rc = 1; }
-  return rc;
+  auto fetch = [&](size_t i, double *buf) {
+    const RestartField &f = fields[i];
+    if (f.dev.empty()) return 0;   // FW_FREEZE without pop_init_ice: the zeros the buffer holds
+    double *p; size_t bytes;
+    if (restart_field_ptr(c, f, &p, &bytes)) return 1;
+    if (hipMemcpy(buf, p, bytes, hipMemcpyDeviceToHost) != hipSuccess) { c->err = "restart: device copy failed"; return 1; }
+    return 0;
+  };
+  return slab_file_write(h, path, at, fields, fetch, "restart", c->err);
 }
 
 int pop_read_restart(pop_ctx *c, const char *path, int flags) {
   if (need_device(c) || join_side(c)) return 1;
   const HostModel &h = c->h;
-  std::map<std::string, std::map<std::string, std::string>> sec;
-  std::vector<std::string> order;
-  if (restart_parse_header(path, sec, order, c->err)) return 1;
-  std::map<std::string, std::string> &g = sec["GLOBAL"];
-  auto truth = [](const std::string &v) {   // list-directed logical: T, F, .TRUE., .false., ...
-    const size_t k = v.find_first_not_of(" .");
-    return (k != std::string::npos && (v[k] == 'T' || v[k] == 't')) ? 1 : 0;
-  };
+  RestartHeader hd;
+  if (restart_parse_header(path, hd, c->err)) return 1;
   std::vector<RestartField> fields = restart_fields(h);
   // restart.F90:679-697: a file written at a coupled time step (lcoupled_ts, when CESM writes its restarts) carries QFLUX where the
   // others carry AQICE.  QFLUX is read, masked and halo-updated as AQICE would be (:886-896, 1041-1055); AQICE is what init_ice left: 0
-  const bool coupled_ts = h.ice && g.count("lcoupled_ts") && truth(g["lcoupled_ts"]);
+  const bool coupled_ts = h.ice && hd.logical("lcoupled_ts");
   if (coupled_ts)
     for (RestartField &f : fields) if (f.name == "AQICE") { f.name = "QFLUX"; f.dev = "QFLUX"; }
+  // Everything the header must give is checked before the first record is read: a header that lacks some of it leaves the context as it was.
   for (RestartField &f : fields) {   // record of each field from the header (define_field_binary :1075-1080), not from our own order
-    auto it = sec.find(restart_find_section(order, f.name));
-    if (it == sec.end() || !it->second.count("id")) {
-      if (f.dev.empty()) { f.id = -1; continue; }                    // FW_FREEZE is not used here
+    int ndims;
+    if (!hd.find(f.name, RestartHeader::PREFIX, &f.id, &ndims)) {
+      if (f.dev.empty()) continue;                                   // FW_FREEZE is not used here
       c->err = "could not find field in binary header file: " + f.name; return 1;
     }
-    f.id = atoi(it->second["id"].c_str());
-    if (it->second.count("nfield_dims") && atoi(it->second["nfield_dims"].c_str()) != f.ndims) { c->err = "restart: wrong rank for " + f.name; return 1; }
+    if (ndims && ndims != f.ndims) { c->err = "restart: wrong rank for " + f.name; return 1; }
   }
-  const int fd = open(path, O_RDONLY);
-  if (fd < 0) { c->err = std::string("cannot open ") + path; return 1; }
+  fields.erase(std::remove_if(fields.begin(), fields.end(), [](const RestartField &f) { return f.dev.empty(); }), fields.end());   // ... and not read
+  if (!hd.has("nsteps_total")) { c->err = "restart: header has no nsteps_total"; return 1; }
+  if (h.ice && !hd.has("tlast_ice")) { c->err = "restart: header has no tlast_ice (the file was written without pop_init_ice)"; return 1; }
   const std::vector<int> KMT = local_part(h, c->h.i2["KMT"]), KMU = local_part(h, c->h.i2["KMU"]);
-  const size_t a2 = (size_t)c->g.n2 * c->g.nblocks, a3 = (size_t)c->g.n3 * c->g.nblocks;
-  std::vector<double> buf(a3);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  int rc = 0;
-  for (const RestartField &f : fields) {
-    if (f.dev.empty() || f.id < 0) continue;
-    const size_t cnt = f.ndims == 3 ? a3 : a2;
-    std::fill(buf.begin(), buf.begin() + cnt, 0.0);
-    const int nz = f.ndims == 3 ? h.km : 1;
-    for (int k = 0; k < nz && !rc; ++k)
-      rc = restart_slab_io(h, fd, f.id + k, buf.data() + (size_t)k * h.n2, f.ndims == 3 ? h.n3 : h.n2, false, (flags & 1) != 0, c->err);
-    if (rc) break;
-    restart_mask(h, f, buf.data(), KMT, KMU);
-    double *p; long long n;
-    if (resolve(c, f.dev, f.tl, f.n, &p, &n) || (size_t)n != cnt) { c->err = "restart: unknown field " + f.dev; rc = 1; break; }
-    if (hipMemcpy(p, buf.data(), cnt * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { c->err = "restart: device copy failed"; rc = 1; break; }
+  auto store = [&](size_t i, double *buf) {
+    const RestartField &f = fields[i];
+    restart_mask(h, f, buf, KMT, KMU);
+    double *p; size_t bytes;
+    if (restart_field_ptr(c, f, &p, &bytes)) return 1;
+    if (hipMemcpy(p, buf, bytes, hipMemcpyHostToDevice) != hipSuccess) { c->err = "restart: device copy failed"; return 1; }
     const int uv = (f.mask == 1 || f.mask == 3) ? 1 : 0;             // U-grid fields: NE corner, vector (restart.F90:969-1014)
-    if (halo_update(c, p, nz, 0.0, uv, uv)) { rc = 1; break; }       // read_restart :960-1040 (fillValue 0)
-  }
-  close(fd);
-  if (rc) return rc;
+    return halo_update(c, p, f.nlev, 0.0, uv, uv);                   // read_restart :960-1040 (fillValue 0)
+  };
+  // a failure during the walk (a short file) leaves the fields stored before it in place, as in the reference: there is no rollback
+  if (slab_file_read(h, path, fields, (flags & 1) != 0, store, c->err)) return 1;
   c->full_left = c->land_full_steps;   // land elimination: the state just read is new
   for (bool &b : c->tr_ghosts_ok) b = false;
   for (bool &b : c->uv_ghosts_ok) b = false;
@@ -1318,32 +1296,28 @@ int pop_read_restart(pop_ctx *c, const char *path, int flags) {
   launch_state3d(c->g, c->TR[0][c->oldt], c->TR[1][c->oldt], c->RHO[c->oldt], c->stream);
   HIPCHK(c, hipGetLastError());
   // scalars: initial.F90:1088 first_step = .false.; time_management.F90:1426 nsteps_this_interval = 0 unless the file says otherwise
-  if (coupled_ts) HIPCHK(c, hipMemsetAsync(c->ice.AQICE, 0, a2 * sizeof(double), c->stream));
-  if (!g.count("nsteps_total")) { c->err = "restart: header has no nsteps_total"; return 1; }
-  c->nsteps_total = atoi(g["nsteps_total"].c_str());
-  c->nsteps_this_interval = g.count("nsteps_this_interval") ? atoi(g["nsteps_this_interval"].c_str()) : 0;
+  if (coupled_ts) HIPCHK(c, hipMemsetAsync(c->ice.AQICE, 0, (size_t)c->g.n2 * c->g.nblocks * sizeof(double), c->stream));
+  c->nsteps_total = hd.integer("nsteps_total", 0);
+  c->nsteps_this_interval = hd.integer("nsteps_this_interval", 0);
   c->first_step = 0;
   // restart.F90:467-468: eod and eod_last each from its own attribute (list-directed logicals); one the file lacks keeps the default,
   // false.  time_manager of the next step copies eod into eod_last (time_management.F90:1809): the file's eod decides that step.
-  c->eod = g.count("eod") ? truth(g["eod"]) : 0;
-  c->eod_last = g.count("eod_last") ? truth(g["eod_last"]) : 0;
+  c->eod = hd.logical("eod");
+  c->eod_last = hd.logical("eod_last");
   // files this library wrote before it wrote eod: their eod_last held eod
-  if (!g.count("eod") && g.count("history") && g["history"].find("written by libpop_amd") != std::string::npos) { c->eod = c->eod_last; c->eod_last = 0; }
+  if (!hd.has("eod") && hd.text("history").find("written by libpop_amd") != std::string::npos) { c->eod = c->eod_last; c->eod_last = 0; }
   // module state of hmix_gm that no restart file carries: KAPPA_VERTICAL is 1 until compute_kappa runs again (init_gm, hmix_gm.F90:860) -- with
   // 'once_a_day' that is the first step of a restart written at the end of a day (eod_last), with 'never' it stays 1 (the reference's behaviour too)
   if (c->gm.KV) {
     std::vector<double> ones((size_t)c->g.n3 * c->g.nblocks, 1.0);
     HIPCHK(c, hipMemcpy(c->gm.KV, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice));
   }
-  if (h.ice) {   // restart.F90:489; QICE belongs to the step that formed it and is not in the file
-    if (!g.count("tlast_ice")) { c->err = "restart: header has no tlast_ice (the file was written without pop_init_ice)"; return 1; }
-    c->ice.tlast_ice = strtod(g["tlast_ice"].c_str(), nullptr);
-  }
+  if (h.ice) c->ice.tlast_ice = hd.real("tlast_ice");   // restart.F90:489; QICE belongs to the step that formed it and is not in the file
   if (h.c.tmix_opt == 3) {
     for (int n = 0; n < h.nt; ++n) {
       const std::string key = "rf_S_prev_" + restart_tracer_name(h, n);
-      c->rf_S_prev_valid[n] = g.count(key) != 0;                     // extract_attrib_file(..., from_file=rf_S_prev_valid) :516-519
-      if (c->rf_S_prev_valid[n]) c->rf_S_prev[n] = strtod(g[key].c_str(), nullptr);
+      c->rf_S_prev_valid[n] = hd.has(key);                           // extract_attrib_file(..., from_file=rf_S_prev_valid) :516-519
+      if (c->rf_S_prev_valid[n]) c->rf_S_prev[n] = hd.real(key);
     }
   }
   return 0;
@@ -2896,77 +2870,51 @@ int pop_tavg_reset(pop_ctx *c, int ns) {
 int pop_tavg_write(pop_ctx *c, int ns, const char *path, int restart_type) {
   if (need_device(c) || tavg_stream_ok(c, ns, "pop_tavg_write") || tavg_between_steps(c, "pop_tavg_write") || join_side(c, true)) return 1;
   if (restart_type != 0 && restart_type != 1) { c->err = "pop_tavg_write: restart_type 0 (normalise, write, reset) or 1 (the sums as they are)"; return 1; }
-  const HostModel &h = c->h;
   TavgState &T = c->tavg;
   std::vector<RestartField> fields;
   std::vector<const TavgEntry *> ent;
   int rec = 1;
   for (const TavgEntry &e : T.req) {
     if (e.stream != ns) continue;
-    fields.push_back(RestartField{e.name, "", 1, 0, e.ndims, rec, "", "", "", 0});
+    fields.push_back(RestartField{e.name, e.ndims, e.nlev, rec});
     ent.push_back(&e);
     rec += e.nlev;
   }
   if (ent.empty()) { c->err = "pop_tavg_write: stream " + std::to_string(ns) + " holds no entry"; return 1; }
   if (restart_type == 0) { double f; for (const TavgEntry *e : ent) if (tavg_factor(c, *e, &f)) return 1; }   // before anything is written
-  if (h.rank == 0) {
-    const std::vector<RestartAttr> at = {{"title", "char", "POP tavg"}, {"history", "char", "written by libpop_amd"}, {"conventions", "char", "POP binary tavg"},
-                                         {"restart_type", "int", std::to_string(restart_type)},
-                                         {"tavg_sum", "r8", fmt_r8(T.sum[ns])}, {"tavg_sum_qflux", "r8", fmt_r8(T.sum_qflux[ns])},
-                                         {"nsteps_total", "int", std::to_string(c->nsteps_total)}};   // tavg.F90:2003-2007
-    if (restart_write_header(h, path, at, fields, c->err)) return 1;
-  }
-  const int fd = open(path, O_WRONLY | O_CREAT, 0644);
-  if (fd < 0) { c->err = std::string("cannot open ") + path + " for writing"; return 1; }
-  std::vector<double> buf((size_t)h.n3 * h.nblocks);
-  int rc = 0;
-  for (size_t i = 0; i < ent.size() && !rc; ++i) {
-    const TavgEntry &e = *ent[i];
-    rc = tavg_to_host(c, e, restart_type == 0, buf.data());
-    for (int k = 0; k < e.nlev && !rc; ++k)
-      rc = restart_slab_io(h, fd, fields[i].id + k, buf.data() + (size_t)k * h.n2, (size_t)e.nlev * h.n2, true, false, c->err);
-  }
-  if (close(fd) != 0 && !rc) { c->err = "tavg: close failed"; rc = 1; }
-  if (rc) return rc;
+  const std::vector<RestartAttr> at = {{"title", "char", "POP tavg"}, {"history", "char", "written by libpop_amd"}, {"conventions", "char", "POP binary tavg"},
+                                       {"restart_type", "int", std::to_string(restart_type)},
+                                       {"tavg_sum", "r8", fmt_r8(T.sum[ns])}, {"tavg_sum_qflux", "r8", fmt_r8(T.sum_qflux[ns])},
+                                       {"nsteps_total", "int", std::to_string(c->nsteps_total)}};   // tavg.F90:2003-2007
+  auto fetch = [&](size_t i, double *buf) { return tavg_to_host(c, *ent[i], restart_type == 0, buf); };
+  if (slab_file_write(c->h, path, at, fields, fetch, "tavg", c->err)) return 1;
   return restart_type == 0 ? tavg_reset_stream(c, ns) : 0;
 }
 int pop_tavg_read(pop_ctx *c, int ns, const char *path) {
   if (need_device(c) || tavg_stream_ok(c, ns, "pop_tavg_read") || tavg_between_steps(c, "pop_tavg_read") || join_side(c, true)) return 1;
-  const HostModel &h = c->h;
   TavgState &T = c->tavg;
-  std::map<std::string, std::map<std::string, std::string>> sec;
-  std::vector<std::string> order;
-  if (restart_parse_header(path, sec, order, c->err)) return 1;
-  std::map<std::string, std::string> &g = sec["GLOBAL"];
-  if (!g.count("tavg_sum") || !g.count("tavg_sum_qflux")) { c->err = "pop_tavg_read: header has no tavg_sum / tavg_sum_qflux"; return 1; }
-  if (g.count("restart_type") && atoi(g["restart_type"].c_str()) != 1) { c->err = "pop_tavg_read: the file holds normalised fields (restart_type 0), not the sums"; return 1; }
-  std::vector<std::pair<TavgEntry *, int>> ent;
-  for (TavgEntry &e : T.req) {
+  RestartHeader hd;
+  if (restart_parse_header(path, hd, c->err)) return 1;
+  if (!hd.has("tavg_sum") || !hd.has("tavg_sum_qflux")) { c->err = "pop_tavg_read: header has no tavg_sum / tavg_sum_qflux"; return 1; }
+  if (hd.integer("restart_type", 1) != 1) { c->err = "pop_tavg_read: the file holds normalised fields (restart_type 0), not the sums"; return 1; }
+  std::vector<RestartField> fields;
+  std::vector<const TavgEntry *> ent;
+  for (const TavgEntry &e : T.req) {
     if (e.stream != ns) continue;
-    auto it = sec.end();
-    for (const std::string &s : order) if (s == e.name) it = sec.find(s);
-    if (it == sec.end() || !it->second.count("id")) { c->err = "could not find field in binary header file: " + e.name; return 1; }
-    ent.push_back({&e, atoi(it->second["id"].c_str())});
+    int id, ndims;
+    if (!hd.find(e.name, RestartHeader::EXACT, &id, &ndims)) { c->err = "could not find field in binary header file: " + e.name; return 1; }
+    fields.push_back(RestartField{e.name, e.ndims, e.nlev, id});
+    ent.push_back(&e);
   }
-  const int fd = open(path, O_RDONLY);
-  if (fd < 0) { c->err = std::string("cannot open ") + path; return 1; }
-  std::vector<double> buf((size_t)h.n3 * h.nblocks);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  int rc = 0;
-  for (auto &pe : ent) {
-    const TavgEntry &e = *pe.first;
-    const size_t n = tavg_count(c, e);
-    std::fill(buf.begin(), buf.begin() + n, 0.0);
-    for (int k = 0; k < e.nlev && !rc; ++k)
-      rc = restart_slab_io(h, fd, pe.second + k, buf.data() + (size_t)k * h.n2, (size_t)e.nlev * h.n2, false, false, c->err);
-    if (rc) break;
-    if (hipMemcpy(e.buf, buf.data(), n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { c->err = "tavg: device copy failed"; rc = 1; break; }
-    if (halo_update(c, e.buf, e.nlev, 0.0)) { rc = 1; break; }
-  }
-  close(fd);
-  if (rc) return rc;
-  T.sum[ns] = strtod(g["tavg_sum"].c_str(), nullptr);
-  T.sum_qflux[ns] = strtod(g["tavg_sum_qflux"].c_str(), nullptr);
+  auto store = [&](size_t i, double *buf) {
+    const TavgEntry &e = *ent[i];
+    if (hipMemcpy(e.buf, buf, tavg_count(c, e) * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { c->err = "tavg: device copy failed"; return 1; }
+    return halo_update(c, e.buf, e.nlev, 0.0);
+  };
+  if (slab_file_read(c->h, path, fields, false, store, c->err)) return 1;
+  T.sum[ns] = hd.real("tavg_sum");   // the sums only once every field is in place
+  T.sum_qflux[ns] = hd.real("tavg_sum_qflux");
   return 0;
 }
 

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -140,20 +141,35 @@ void ice_nml_defaults(pop_ice_nml &n);
 int ice_nml_check(const HostModel &h, const pop_ice_nml &n, std::string &err);
 IceConsts ice_consts(const pop_ice_nml &n);
 // ---- POP binary restart files (host_restart.cpp; restart.F90, io_binary.F90)
+// one field of a restart or tavg file: records id .. id + nlev - 1, held on the host as (nxb, nyb, nlev, nblocks)
 struct RestartField {
-  std::string name, dev; int tl, n, ndims, id;       // file name; device field, time level (0 old, 1 cur), tracer; first record
+  std::string name; int ndims = 2, nlev = 1, id = 0;   // file name; nfield_dims; levels (km or 1 in a restart, 1 .. km in a tavg file); first record
+  // restart files only
+  std::string dev; int tl = 1, n = 0, mask = 0;        // device field (empty: none, zeros are written), time level (0 old, 1 cur), tracer;
+                                                       // mask: 1 CALCU, 2 CALCT, 3 k > KMU, 4 k > KMT (read_restart :881-935)
   std::string long_name, units, grid_loc;
-  int mask;                                          // 1 CALCU, 2 CALCT, 3 k > KMU, 4 k > KMT (read_restart :881-935)
 };
 struct RestartAttr { std::string name, type, value; };
+std::string fmt_r8(double v);                          // value of an r8 attribute
+// a parsed <file>.hdr: typed reads of &GLOBAL and the record of a field
+struct RestartHeader {
+  std::map<std::string, std::map<std::string, std::string>> sec;   // section -> (attribute -> value)
+  std::vector<std::string> order;                                  // section names as they stand in the file
+  const std::string *attr(const std::string &a) const;             // of &GLOBAL; null when absent
+  bool has(const std::string &a) const { return attr(a) != nullptr; }
+  std::string text(const std::string &a) const { return has(a) ? *attr(a) : std::string(); }
+  int integer(const std::string &a, int dflt) const { return has(a) ? atoi(attr(a)->c_str()) : dflt; }
+  double real(const std::string &a) const { return strtod(text(a).c_str(), nullptr); }
+  bool logical(const std::string &a) const;                        // list-directed; false when absent
+  enum Rule { PREFIX, EXACT };
+  bool find(const std::string &name, Rule rule, int *id, int *ndims) const;
+};
+typedef std::function<int(size_t, double *)> SlabFieldFn;          // (index into the field list, host buffer) -> 0, or non-zero with the error set
 std::string restart_tracer_name(const HostModel &h, int n);
 std::vector<RestartField> restart_fields(const HostModel &h);
-int restart_write_header(const HostModel &h, const std::string &path, const std::vector<RestartAttr> &attrs,
-                         const std::vector<RestartField> &fields, std::string &err);
-int restart_parse_header(const std::string &path, std::map<std::string, std::map<std::string, std::string>> &sec,
-                         std::vector<std::string> &order, std::string &err);
-std::string restart_find_section(const std::vector<std::string> &order, const std::string &name);
-int restart_slab_io(const HostModel &h, int fd, long long rec, double *loc, size_t blk_stride, bool write, bool swap, std::string &err);
+int restart_parse_header(const std::string &path, RestartHeader &hd, std::string &err);
+int slab_file_write(const HostModel &h, const std::string &path, const std::vector<RestartAttr> &attrs, const std::vector<RestartField> &fields, const SlabFieldFn &fetch, const std::string &tag, std::string &err);
+int slab_file_read(const HostModel &h, const std::string &path, const std::vector<RestartField> &wanted, bool swap, const SlabFieldFn &store, std::string &err);
 void restart_mask(const HostModel &h, const RestartField &f, double *loc, const std::vector<int> &KMT, const std::vector<int> &KMU);
 std::vector<double> host_center_init(HostModel &h);                      // centre weight POP_SolversPrep sees (host_pcsi.cpp)
 int host_pcsi_prep(HostModel &h, const std::vector<double> &C);         // host_pcsi.cpp

@@ -1150,7 +1150,8 @@ def test_operators_are_bitwise_the_oracle(pkg, orclib_built):
 
 def test_entry_points_fail_loudly(pkg, tmp_path):
     """Error convention of the C ABI (non-zero return + message, no partial work): bad operator arguments, unknown
-    fields and masks, wrong counts, wrong field locations, a missing or truncated restart file."""
+    fields and masks, wrong counts, wrong field locations, a missing or truncated restart file, a restart header that lacks
+    what the reader needs (the state stays bitwise as it was, and so does the step after it)."""
     m = pkg.PopModel(named_config("tiny"))
     with pytest.raises(pkg.PopError, match="op 0 grad"):
         m.operator("grad", 0, "PSURF")
@@ -1194,6 +1195,25 @@ def test_entry_points_fail_loudly(pkg, tmp_path):
     m.step()
     path = str(tmp_path / "r.bin")
     m.write_restart(path)
+    # a header without nsteps_total is refused before any record is read: the state, one step on from the file's, stays as it is
+    m.step()
+    twin = pkg.PopModel(named_config("tiny"))                    # the same steps, never the read
+    twin.step(); twin.step()
+    state = lambda x: [x.get(n, tl, k) for n, k in (("TRACER", 0), ("TRACER", 1), ("UVEL", 0), ("PSURF", 0)) for tl in (0, 1)] + [x.dim("nsteps_total")]
+    same = lambda a, b: len(a) == len(b) and all(np.array_equal(p, q) for p, q in zip(a, b))
+    before = state(m)
+    good_hdr = open(path + ".hdr").read()
+    lines = good_hdr.splitlines(keepends=True)
+    kept = [l for l in lines if not l.startswith("nsteps_total:")]
+    assert len(kept) == len(lines) - 1
+    open(path + ".hdr", "w").write("".join(kept))
+    with pytest.raises(pkg.PopError, match="header has no nsteps_total"):
+        m.read_restart(path)
+    assert same(state(m), before)
+    m.step(); twin.step()
+    assert same(state(m), state(twin))
+    twin.close()
+    open(path + ".hdr", "w").write(good_hdr)
     with open(path, "r+b") as f:
         f.truncate(1000)
     with pytest.raises(pkg.PopError, match="short read"):
