@@ -157,7 +157,9 @@ typedef struct pop_ctx pop_ctx;
                                   * pop_halo_update_host_*, pop_get_dim("ocean_columns_local" | "ocean_columns_total") work; field access does not */
 
 /* ---- tuning: kernel-form and schedule choices.  NONE changes a result: every alternative is tested bitwise equal to the
- *      default (tests/test_gpu_parity.py, test_gpu_land.py, test_gpu_multirank.py); they exist for measurement and for those
+ *      default (tests/test_gpu_parity.py, test_gpu_land.py, test_gpu_land_schemes.py, test_gpu_passive_matrix.py,
+ *      test_gpu_multirank.py; red_tiles regroups the solver's partial sums and is compared to tolerance, see
+ *      test_gpu_passive_matrix.py); they exist for measurement and for those
  *      tests.  Resolved ONCE, at pop_create*: the library's size rules, overridden by the caller's pop_tuning (fields left at
  *      POP_TUNING_UNSET keep the rule), overridden by the environment variable POP_<FIELD NAME IN UPPER CASE> (read at create
  *      only; nothing in the step reads the environment).  pop_get_tuning returns what was resolved. ---------------------- */

@@ -77,9 +77,9 @@ def tidal_branches(orc, nml):
             "stab": int((wet & (lev > 2) & ((lev == KMT - 1) | (lev == KMT - 2)) & (TD > capped)).sum())}
 
 
-def force_kpp_case_above_deep_water(gpu, orc):
-    """force_kpp_case's forcing everywhere, its homogenised upper ocean (eight levels) only where the column is deeper than that layer;
-    a shallower column keeps the initial stratification and the density that goes with it.
+def force_kpp_case_above_deep_water(gpu, orc, min_kmt=8):
+    """force_kpp_case's forcing everywhere, its homogenised upper ocean (eight levels) only where the column is deeper than that layer
+    (KMT >= min_kmt); a shallower column keeps the initial stratification and the density that goes with it.
 
     For grids with 3- and 5-level columns next to deep ones (banda_arctic_grid).  Homogenised to the bottom, such a column leaves
     the boundary layer depth -- the root of the parabola through the last three bulk Richardson numbers, vmix_kpp.F90:2601-2640 --
@@ -89,11 +89,17 @@ def force_kpp_case_above_deep_water(gpu, orc):
     1.4e-13 of the field's maximum, 111 of 1920 HBLT cells above 1e-13 -- so at TOL_LOCAL that state compares the two pow
     implementations, not the kernels.  With this state the same measurement gives HBLT 4.1e-15, VDC 8.9e-15, VVC 4.8e-15, TRACER
     9.7e-15, UVEL 7.9e-16, as on the internal grid (3.7e-15, 8.2e-15, 4.4e-15, 7.4e-15, 6.9e-16), and the boundary layer still takes
-    110 distinct depths between 1250 and 20190 cm."""
+    110 distinct depths between 1250 and 20190 cm.
+
+    min_kmt: a column that ends a level or two below the homogenised layer is as sensitive.  `wide` (km = 16) with stepped bathymetry has
+    columns of 8 .. 16 levels; the same measurement there (first baroclinic driver, pow off by one ulp in half of its calls) gives
+    HBLT 4.9e-10, VDC 9.4e-10, VVC 6.2e-10, TRACER 5.6e-10 with the default, HBLT of 1403 columns (of 8 .. 15
+    levels) off by more than 1e-12, and HBLT 1.2e-14, VDC 2.4e-14, VVC 1.7e-14, TRACER 1.4e-14 with min_kmt = 12 (115 distinct depths, 1250 .. 212344 cm):
+    tests/test_gpu_land_schemes.py."""
     keep = {(f, tl, n): orc.f3(f, tl, n).copy() for f, tls, ns in (("TRACER", (0, 1, 2), (0, 1)), ("RHO", (0, 1), (0,))) for tl in tls for n in ns}
     from test_gpu_parity import force_kpp_case
     force_kpp_case(gpu, orc)
-    shallow = (orc.i2("KMT") < 8)[:, None]
+    shallow = (orc.i2("KMT") < min_kmt)[:, None]
     assert shallow.any() and not shallow.all()
     for (f, tl, n), a in keep.items():
         x = orc.f3(f, tl, n)
