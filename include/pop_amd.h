@@ -603,6 +603,56 @@ int pop_tavg_write(pop_ctx *ctx, int stream, const char *path, int restart_type)
 int pop_tavg_read(pop_ctx *ctx, int stream, const char *path);
 /* pop_run_phase / pop_time_phase also know the sites on their own, each run once with the weight of the last pop_time_manager:
  * "tavg_forcing", "tavg_state", "tavg_tracer", "tavg_vmix", "tavg_hmix", "tavg_btrop". */
+
+/* ---- global and CFL diagnostics (diagnostics.F90), computed on the device -------------------------------------------------------
+ * The reference decides per step whether to diagnose (ldiag_global, ldiag_cfl of diag_init_sums); here the caller does:
+ * pop_diag_arm arms the NEXT step only (one-shot: pop_time_manager takes the arming).  It is refused between pop_time_manager and
+ * pop_step_tail of a step.  An armed step runs three more sites, each one launch plus a small second stage, and copies a few
+ * numbers to pinned host memory without synchronising:
+ *   "diag_global_preupdate"   in pop_step_tail after PGUESS, before the time levels rotate (diag_global_preupdate, step_mod.F90:649)
+ *   "diag_global_afterupdate" at the end of pop_step_tail, after the rotation / the Robert filter (diag_global_afterupdate, :860)
+ *   "diag_cfl"                at the end of pop_baroclinic_driver (cfl_advect, cfl_hdiff, cfl_check; baroclinic.F90:1203)
+ * pop_run_phase / pop_time_phase know the sites by these names: they run when the context is armed or inside an armed step and do
+ * nothing otherwise (run on their own they do not use the arming up).  With nothing armed every site is one test of a host flag.
+ * Results stay readable until the next armed step overwrites them and carry the nsteps_total they belong to.  A host-only context
+ * accepts pop_diag_arm; its getters answer the host-only error.  DESIGN.md section 15 has the rules of summation and the list of
+ * the reference's diagnostics that are not built (asking for one by name says so). */
+#define POP_DIAG_MAX_NT 8
+typedef struct pop_diag_global {
+  int struct_bytes;               /* in: sizeof(pop_diag_global) */
+  int nt, km;
+  int nsteps_total_pre, nsteps_total_after;   /* the step each site last ran in; -1: not yet (its numbers are NaN) */
+  int iterationCount;             /* POP_SolversGetDiagnostics of that step */
+  double rmsResidual;
+  /* afterupdate */
+  double diag_sealevel, diag_ke;
+  double avg_tracer[POP_DIAG_MAX_NT];        /* [1] in ppt (salt_to_ppt) */
+  double sfc_tracer_flux[POP_DIAG_MAX_NT];   /* [0] in W/m^2 (/ hflux_factor), [1] as a fresh-water flux (/ salinity_factor) */
+  /* preupdate */
+  double diag_ws, diag_press_free, diag_ke_free, diag_ke_psfc;
+  double dtracer_avg[POP_DIAG_MAX_NT], dtracer_abs[POP_DIAG_MAX_NT];
+} pop_diag_global;
+int pop_diag_arm(pop_ctx *ctx, int want_global, int want_cfl);
+/* avg_tracer_k: NULL, or km * nt doubles, avg_tracer_k(k, n) at [n * km + k - 1] (count = km * nt) */
+int pop_diag_global_get(pop_ctx *ctx, pop_diag_global *out, double *avg_tracer_k, long long count);
+/* one global diagnostic by the reference's name ("diag_ke", "avg_tracer", "dtracer_abs" ...; n: 0-based tracer index where the
+ * name has one, else 0).  The reference's names whose sources exist only inside the tracer and momentum kernels ("diag_ke_adv",
+ * "diag_pe", "diag_tracer_hdiff" ...) answer "known to the reference, not built". */
+int pop_diag_value(pop_ctx *ctx, const char *name, int n, double *value);
+/* one CFL number: name "advu" | "advv" | "advw" | "advt" | "hdifft" | "hdiffu" | "vdifft" | "vdiffu".  value and ijk[3] = the total
+ * and the global (i, j, k) of its maximum; value_k[km] and ij_k[2 * km] ((i, j) of level k at [2 (k - 1)]) = the level maxima; any
+ * pointer may be NULL.  The first physical cell in (block id, j, i) order that attains a maximum owns the address, whatever the
+ * distribution over ranks.  The vertical-mixing numbers are those of a run with implicit vertical mixing, the only form the
+ * library has: cfl_vdiff is never called (vertical_mix.F90:677-678), so they are 0 with the address (0, 0, 1).
+ * nsteps_total: the step the numbers belong to. */
+int pop_diag_cfl(pop_ctx *ctx, const char *name, double *value, int *ijk, double *value_k, int *ij_k, int *nsteps_total);
+/* check_KE (diagnostics.F90:3260-3290) on the last diag_ke: *exceeded = diag_ke > ke_thresh or diag_ke < 0.  An error while no
+ * armed step has run. */
+int pop_check_ke(pop_ctx *ctx, double ke_thresh, int *exceeded);
+/* grid.F90:1059-1072, formed on the host at create (a host-only context has them too): area_t, volume_t, volume_u and, km doubles
+ * each, area_t_k, volume_t_k.  Any pointer may be NULL. */
+int pop_grid_volumes(pop_ctx *ctx, double *area_t, double *volume_t, double *volume_u, double *area_t_k, double *volume_t_k);
+
 /* run all launches on the host framework's HIP stream (e.g. torch.cuda.current_stream().cuda_stream) */
 int pop_set_stream(pop_ctx *ctx, void *hip_stream);
 

@@ -94,6 +94,9 @@ def lib():
         "pop_tavg_request": (ci, [vp, ci, cs]), "pop_tavg_set_on": (ci, [vp, ci, ci]), "pop_tavg_info": (ci, [vp, cs, pi, pi, pi, pi]),
         "pop_tavg_sums": (ci, [vp, ci, pd, pd]), "pop_tavg_get": (ci, [vp, cs, ci, pd, ll]), "pop_tavg_device_ptr": (vp, [vp, cs]),
         "pop_tavg_reset": (ci, [vp, ci]), "pop_tavg_write": (ci, [vp, ci, cs, ci]), "pop_tavg_read": (ci, [vp, ci, cs]),
+        "pop_diag_arm": (ci, [vp, ci, ci]), "pop_diag_global_get": (ci, [vp, vp, pd, ll]), "pop_diag_value": (ci, [vp, cs, ci, pd]),
+        "pop_diag_cfl": (ci, [vp, cs, pd, pi, pd, pi, pi]), "pop_check_ke": (ci, [vp, cd, pi]),
+        "pop_grid_volumes": (ci, [vp, pd, pd, pd, pd, pd]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)       # AttributeError here = the library does not export the ABI
@@ -288,6 +291,18 @@ def ice_nml(**kw):
             raise AttributeError("pop_ice_nml has no field %r" % k)
         setattr(n, k, v)
     return n
+
+
+DIAG_MAX_NT = 8
+
+
+class PopDiagGlobal(C.Structure):
+    """include/pop_amd.h pop_diag_global"""
+    _fields_ = [(n, C.c_int) for n in ("struct_bytes", "nt", "km", "nsteps_total_pre", "nsteps_total_after", "iterationCount")] + \
+        [(n, C.c_double) for n in ("rmsResidual", "diag_sealevel", "diag_ke")] + \
+        [(n, C.c_double * DIAG_MAX_NT) for n in ("avg_tracer", "sfc_tracer_flux")] + \
+        [(n, C.c_double) for n in ("diag_ws", "diag_press_free", "diag_ke_free", "diag_ke_psfc")] + \
+        [(n, C.c_double * DIAG_MAX_NT) for n in ("dtracer_avg", "dtracer_abs")]
 
 
 class PopGridInput(C.Structure):
@@ -511,6 +526,57 @@ class PopModel:
 
     def tavg_read(self, stream, path):
         self._chk(self.L.pop_tavg_read(self.h, stream, os.fsencode(path)))
+
+    # ---- global and CFL diagnostics (diagnostics.F90; include/pop_amd.h pop_diag_*)
+    CFL_NAMES = ("advu", "advv", "advw", "advt", "hdifft", "hdiffu", "vdifft", "vdiffu")
+
+    def diag_arm(self, want_global=True, want_cfl=True):
+        """arm the next step (one-shot): global diagnostics and / or CFL numbers"""
+        self._chk(self.L.pop_diag_arm(self.h, 1 if want_global else 0, 1 if want_cfl else 0))
+
+    def diag_global(self):
+        """the global diagnostics of the last armed step: a dict of the scalars, of (nt,) arrays avg_tracer, sfc_tracer_flux,
+        dtracer_avg, dtracer_abs and of avg_tracer_k (km, nt); nsteps_total_pre / _after: the step each site ran in (-1: not yet, NaN)"""
+        g = PopDiagGlobal()
+        g.struct_bytes = C.sizeof(PopDiagGlobal)
+        atk = np.empty((self.nt, self.km), dtype=np.float64)
+        self._chk(self.L.pop_diag_global_get(self.h, C.byref(g), atk.ctypes.data_as(C.POINTER(C.c_double)), atk.size))
+        out = {}
+        for name, typ in PopDiagGlobal._fields_:
+            v = getattr(g, name)
+            if name != "struct_bytes":
+                out[name] = np.array(v[:self.nt]) if hasattr(v, "__len__") else v
+        out["avg_tracer_k"] = atk.T.copy()
+        return out
+
+    def diag_value(self, name, n=0):
+        """one global diagnostic by the reference's name (n: 0-based tracer index where it has one)"""
+        r = C.c_double()
+        self._chk(self.L.pop_diag_value(self.h, name.encode(), n, C.byref(r)))
+        return r.value
+
+    def diag_cfl(self, name):
+        """one CFL number of the last armed step: dict(value, ijk = global (i, j, k) of the maximum, value_k (km,), ij_k (km, 2),
+        nsteps_total)"""
+        v, ijk, step = C.c_double(), (C.c_int * 3)(), C.c_int()
+        vk, ijk_k = np.empty(self.km, dtype=np.float64), np.empty((self.km, 2), dtype=np.int32)
+        self._chk(self.L.pop_diag_cfl(self.h, name.encode(), C.byref(v), ijk, vk.ctypes.data_as(C.POINTER(C.c_double)),
+                                      ijk_k.ctypes.data_as(C.POINTER(C.c_int)), C.byref(step)))
+        return {"value": v.value, "ijk": tuple(ijk), "value_k": vk, "ij_k": ijk_k, "nsteps_total": step.value}
+
+    def check_ke(self, ke_thresh):
+        """check_KE (diagnostics.F90:3260-3290) on the last diag_ke"""
+        r = C.c_int()
+        self._chk(self.L.pop_check_ke(self.h, float(ke_thresh), C.byref(r)))
+        return bool(r.value)
+
+    def grid_volumes(self):
+        """dict(area_t, volume_t, volume_u, area_t_k (km,), volume_t_k (km,)) of grid.F90:1059-1072; a host-only context has them too"""
+        a, vt, vu = C.c_double(), C.c_double(), C.c_double()
+        ak, vk = np.empty(self.km, dtype=np.float64), np.empty(self.km, dtype=np.float64)
+        P = C.POINTER(C.c_double)
+        self._chk(self.L.pop_grid_volumes(self.h, C.byref(a), C.byref(vt), C.byref(vu), ak.ctypes.data_as(P), vk.ctypes.data_as(P)))
+        return {"area_t": a.value, "volume_t": vt.value, "volume_u": vu.value, "area_t_k": ak, "volume_t_k": vk}
 
     # ---- step_mod.F90 sequence
     def time_manager(self):

@@ -907,6 +907,28 @@ int host_build(HostModel &h) {
     }
   }
 
+  // ---------------- areas and volumes of the global diagnostics (grid.F90:1059-1072) ----------------
+  {
+    const std::vector<int> &KMTi = h.i2["KMT"];
+    const std::vector<double> &RT = h.f2["RCALCT"], &RU = h.f2["RCALCU"], &HTf = h.f2["HT"], &HUf = h.f2["HU"];
+    std::vector<double> work(A2);
+    h.area_t = host_global_sum_loc(h, TAREA.data(), RT.data(), 0);
+    for (size_t p = 0; p < A2; ++p) work[p] = TAREA[p] * HTf[p];
+    h.volume_t = host_global_sum_loc(h, work.data(), RT.data(), 0);
+    for (size_t p = 0; p < A2; ++p) work[p] = UAREA[p] * HUf[p];
+    h.volume_u = host_global_sum_loc(h, work.data(), RU.data(), 1);
+    h.area_t_k.assign(h.km + 1, 0.0); h.volume_t_k.assign(h.km + 1, 0.0);
+    h.area_t_k[1] = h.area_t;
+    for (size_t p = 0; p < A2; ++p) work[p] = TAREA[p] * h.dz[1];
+    h.volume_t_k[1] = host_global_sum_loc(h, work.data(), RT.data(), 0);
+    for (int k = 2; k <= h.km; ++k) {
+      for (size_t p = 0; p < A2; ++p) work[p] = (k <= KMTi[p]) ? TAREA[p] : 0.0;
+      h.area_t_k[k] = host_global_sum(h, work.data(), nullptr);
+      for (size_t p = 0; p < A2; ++p) work[p] = (k <= KMTi[p]) ? TAREA[p] * h.dz[k] : 0.0;
+      h.volume_t_k[k] = host_global_sum(h, work.data(), nullptr);
+    }
+  }
+
   // ---------------- analytic wind stress ----------------
   auto &SMFX = newf("SMF1"), &SMFY = newf("SMF2"), &SMFTX = newf("SMFT1"), &SMFTY = newf("SMFT2");
   for (size_t p = 0; p < A2; ++p) {

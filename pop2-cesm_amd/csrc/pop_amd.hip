@@ -23,6 +23,7 @@
 #include "kernels_ice.hpp"
 #include "kernels_pcg_persist.hpp"
 #include "kernels_tavg.hpp"
+#include "kernels_diag.hpp"
 #include "rccl_transport.hpp"
 
 using namespace pop;
@@ -31,6 +32,7 @@ using namespace pop;
 #include "launch_halo.hpp"
 #include "launch_solvers.hpp"
 #include "launch_tavg.hpp"
+#include "launch_diag.hpp"
 
 namespace {
 
@@ -84,6 +86,7 @@ int resolve(pop_ctx *c, const std::string &name, int tl, int n, double **ptr, lo
   // without cancellation: n = 2 face + half, face 0 east / north, half 0 top) and the transition layer's depths
   if (name == "GM_SF_SLX") return (n >= 0 && n < 4) ? ok(c->gm.SF[n], a3) : 1;
   if (name == "GM_SF_SLY") return (n >= 0 && n < 4) ? ok(c->gm.SF[4 + n], a3) : 1;
+  if (name == "KAPPA_ISOP") return (n == 0 || n == 1) ? ok(c->gm.KI[n], a3) : 1;   // the tapered isopycnal diffusivity of the top / bottom half (cfl_hdiff of hdifft_gm reads it)
   if (name == "TLT_DIABATIC_DEPTH") return ok(c->gm.DD, a2);
   if (name == "TLT_THICKNESS") return ok(c->gm.TH, a2);
   if (name == "TLT_INTERIOR_DEPTH") return ok(c->gm.ID, a2);
@@ -966,6 +969,10 @@ int pop_destroy(pop_ctx *c) {
   if (c->host_sc) hipHostFree(c->host_sc);
   if (c->host_rr) hipHostFree(c->host_rr);
   if (c->persist_out) hipHostFree(c->persist_out);
+  if (c->diag.h_pre || c->diag.h_after || c->diag.h_cfl) {   // copies of an armed step may still be in flight
+    if (c->stream) hipStreamSynchronize(c->stream);
+    for (double *p : {c->diag.h_pre, c->diag.h_after, c->diag.h_cfl}) if (p) hipHostFree(p);
+  }
   if (c->ev_fork) hipEventDestroy(c->ev_fork);
   if (c->ev_d2t) hipEventDestroy(c->ev_d2t);
   if (c->ev_d2u) hipEventDestroy(c->ev_d2u);
@@ -1092,7 +1099,7 @@ long long pop_field_count(const pop_ctx *c, const char *name) {
   const std::string n(name);
   const long long a2 = (long long)c->h.n2 * c->h.nblocks, a3 = (long long)c->h.n3 * c->h.nblocks;
   for (const char *s : {"TRACER", "UVEL", "VVEL", "RHO", "KPP_SRC", "VVC", "UISOP", "VISOP", "WISOP", "GM_SF_SLX", "GM_SF_SLY", "HDU", "HDV", "F_PARA", "F_PERP",
-                        "SUBM_ADV_TEND", "USUBM", "VSUBM", "WSUBM", "GM_GTK", "TIDAL_COEF_3D", "TIDAL_DIFF", "TIDAL_N2", "KVMIX", "KVMIX_M"}) if (n == s) return a3;
+                        "SUBM_ADV_TEND", "USUBM", "VSUBM", "WSUBM", "GM_GTK", "KAPPA_ISOP", "TIDAL_COEF_3D", "TIDAL_DIFF", "TIDAL_N2", "KVMIX", "KVMIX_M"}) if (n == s) return a3;
   if (n == "VDC") return (long long)c->h.n2 * (c->h.km + 2) * c->h.nblocks;
   return a2;
 }
@@ -1359,6 +1366,9 @@ int pop_time_manager(pop_ctx *c) {
   else { c->mixt = c->curt; c->beta = 0.5; c->c2dtt = c->h.dt[1]; c->c2dtu = c->h.dtu; c->c2dtp = c->h.dtp; }
   tavg_set_flag(c);   // step_mod.F90:260-274: right after time_manager
   c->tavg.in_step = !c->host_only;
+  // diag_init_sums (step_mod.F90:353): the arming of pop_diag_arm holds for this step only
+  c->diag.run_global = c->diag.arm_global; c->diag.run_cfl = c->diag.arm_cfl;
+  c->diag.arm_global = c->diag.arm_cfl = false;
   return 0;
 }
 
@@ -1875,6 +1885,7 @@ int pop_baroclinic_driver(pop_ctx *c) {
     HIPCHK(c, hipEventRecord(c->ev_vmixu, c->side));
     c->vmixu_pending = true;
   } else if (phase_impvmixu(c, nullptr)) return 1;
+  if (c->diag.run_cfl && diag_cfl(c)) return 1;   // cfl_check (baroclinic.F90:1203)
   HIPCHK(c, hipGetLastError());
   return 0;
 }
@@ -2098,6 +2109,7 @@ int pop_step_tail(pop_ctx *c) {
   c->btrop_added = false;
   const long long a2 = (long long)c->g.n2 * c->g.nblocks;
   hipLaunchKernelGGL(k_pguess, dim3((a2 + 255) / 256), dim3(256), 0, c->stream, a2, c->PGUESS, c->PS[c->newt], c->PS[c->curt], c->PS[c->oldt]);
+  if (c->diag.run_global && diag_global_pre(c)) return 1;   // step_mod.F90:649
   if (c->avg_ts) {
     const int o = c->oldt, cu = c->curt, nw = c->newt;
     Avg2dArgs a{};
@@ -2124,8 +2136,10 @@ int pop_step_tail(pop_ctx *c) {
     HIPCHK(c, hipMemcpyAsync(c->FW_OLD, c->FW, a2 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     const int tmp = c->oldt; c->oldt = c->curt; c->curt = c->newt; c->newt = tmp;   // step_mod.F90:827-830
   }
+  if (c->diag.run_global && diag_global_after(c)) return 1;   // step_mod.F90:860
   HIPCHK(c, hipGetLastError());
   c->tavg.in_step = false;
+  c->diag.run_global = c->diag.run_cfl = false;
   return 0;
 }
 
@@ -2747,6 +2761,10 @@ static phase_fn_t phase_by_name(const std::string &p) {
   if (p == "tavg_vmix") return [](pop_ctx *x) { return tavg_site(x, TS_VMIX); };
   if (p == "tavg_hmix") return [](pop_ctx *x) { return tavg_site(x, TS_HMIX); };
   if (p == "tavg_btrop") return [](pop_ctx *x) { return tavg_site(x, TS_BTROP); };
+  // the diagnostic sites on their own (launch_diag.hpp): they run when the context is armed or inside an armed step
+  if (p == "diag_global_preupdate") return diag_phase_pre;
+  if (p == "diag_global_afterupdate") return diag_phase_after;
+  if (p == "diag_cfl") return diag_phase_cfl;
   if (p == "block_sums") return [](pop_ctx *x) { SolveView v = local_view(x); presum(x, v, v.partial, v.blocksum + 2 * v.nblocks_tot); return 0; };
   return nullptr;
 }
@@ -2915,6 +2933,79 @@ int pop_tavg_read(pop_ctx *c, int ns, const char *path) {
   if (slab_file_read(c->h, path, fields, false, store, c->err)) return 1;
   T.sum[ns] = hd.real("tavg_sum");   // the sums only once every field is in place
   T.sum_qflux[ns] = hd.real("tavg_sum_qflux");
+  return 0;
+}
+
+// ---- global and CFL diagnostics (diagnostics.F90; kernels_diag.hpp, launch_diag.hpp)
+int pop_diag_arm(pop_ctx *c, int want_global, int want_cfl) {
+  if (!c) return 1;
+  if (c->h.plan_only) { c->err = "pop_diag_arm: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+  if (c->tavg.in_step) { c->err = "pop_diag_arm: refused between pop_time_manager and pop_step_tail of a step (it arms the next step: call it between steps)"; return 1; }
+  c->diag.arm_global = want_global != 0; c->diag.arm_cfl = want_cfl != 0;
+  return 0;
+}
+int pop_diag_global_get(pop_ctx *c, pop_diag_global *out, double *avg_tracer_k, long long count) {
+  if (need_device(c)) return 1;
+  if (!out || out->struct_bytes != (int)sizeof(pop_diag_global)) { c->err = "pop_diag_global_get: struct_bytes is not sizeof(pop_diag_global)"; return 1; }
+  DiagGlobalOut o;
+  o.g.struct_bytes = out->struct_bytes;
+  if (diag_finish_global(c, "pop_diag_global_get", o)) return 1;
+  if (avg_tracer_k && copy_out(c, o.avg_tracer_k, avg_tracer_k, count, "avg_tracer_k")) return 1;
+  *out = o.g;
+  return 0;
+}
+int pop_diag_value(pop_ctx *c, const char *name, int n, double *value) {
+  if (!c) return 1;
+  const std::string nm(name ? name : "");
+  for (const char *l : diag_left_out) if (nm == l) { c->err = "pop_diag_value: " + nm + " is known to the reference, not built (DESIGN.md section 15)"; return 1; }
+  if (need_device(c)) return 1;
+  DiagGlobalOut o;
+  if (diag_finish_global(c, "pop_diag_value", o)) return 1;
+  const pop_diag_global &g = o.g;
+  const struct { const char *name; const double *p; } arrays[] = {{"avg_tracer", g.avg_tracer}, {"sfc_tracer_flux", g.sfc_tracer_flux},
+                                                                   {"dtracer_avg", g.dtracer_avg}, {"dtracer_abs", g.dtracer_abs}};
+  for (const auto &a : arrays)
+    if (nm == a.name) {
+      if (n < 0 || n >= c->h.nt) { c->err = "pop_diag_value: " + nm + ": tracer index " + std::to_string(n) + " is outside 0 .. nt-1 = " + std::to_string(c->h.nt - 1); return 1; }
+      *value = a.p[n];
+      return 0;
+    }
+  const struct { const char *name; double v; } scalars[] = {{"diag_sealevel", g.diag_sealevel}, {"diag_ke", g.diag_ke}, {"diag_ws", g.diag_ws},
+    {"diag_press_free", g.diag_press_free}, {"diag_ke_free", g.diag_ke_free}, {"diag_ke_psfc", g.diag_ke_psfc}, {"rmsResidual", g.rmsResidual},
+    {"iterationCount", (double)g.iterationCount}};
+  for (const auto &s : scalars) if (nm == s.name) { *value = s.v; return 0; }
+  return unknown(c, "pop_diag_value: unknown diagnostic ", nm.c_str());
+}
+int pop_diag_cfl(pop_ctx *c, const char *name, double *value, int *ijk, double *value_k, int *ij_k, int *nsteps_total) {
+  if (need_device(c)) return 1;
+  const int q = diag_cfl_index(name ? name : "");
+  if (q < 0) return unknown(c, "pop_diag_cfl: unknown CFL number (advu, advv, advw, advt, hdifft, hdiffu, vdifft, vdiffu): ", name ? name : "(null)");
+  DiagCflOut o;
+  if (diag_finish_cfl(c, q, o)) return 1;
+  if (value) *value = o.value;
+  if (ijk) std::copy(o.ijk, o.ijk + 3, ijk);
+  if (value_k) std::copy(o.value_k.begin(), o.value_k.end(), value_k);
+  if (ij_k) std::copy(o.ij_k.begin(), o.ij_k.end(), ij_k);
+  if (nsteps_total) *nsteps_total = c->diag.step_cfl;
+  return 0;
+}
+int pop_check_ke(pop_ctx *c, double ke_thresh, int *exceeded) {
+  if (!c) return 1;
+  if (diag_need_site(c, "pop_check_ke", c->diag.step_after >= 0)) return 1;
+  DiagGlobalOut o;
+  if (diag_finish_global(c, "pop_check_ke", o)) return 1;
+  if (exceeded) *exceeded = (o.g.diag_ke > ke_thresh || o.g.diag_ke < 0) ? 1 : 0;
+  return 0;
+}
+int pop_grid_volumes(pop_ctx *c, double *area_t, double *volume_t, double *volume_u, double *area_t_k, double *volume_t_k) {
+  if (!c) return 1;
+  if (c->h.plan_only) { c->err = "pop_grid_volumes: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+  const HostModel &h = c->h;
+  if (area_t) *area_t = h.area_t;
+  if (volume_t) *volume_t = h.volume_t;
+  if (volume_u) *volume_u = h.volume_u;
+  if (area_t_k) std::copy(h.area_t_k.begin() + 1, h.area_t_k.end(), area_t_k);
+  if (volume_t_k) std::copy(h.volume_t_k.begin() + 1, h.volume_t_k.end(), volume_t_k);
   return 0;
 }
 

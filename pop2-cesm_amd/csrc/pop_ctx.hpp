@@ -43,6 +43,20 @@ struct TavgState {
   double *scratch = nullptr;                        // normalise-into-a-copy: one 3-D field
 };
 
+// ---- global and CFL diagnostics (diagnostics.F90; launch_diag.hpp): arming, work buffers, what the sites left for the getters
+struct DiagState {
+  bool arm_global = false, arm_cfl = false;   // pop_diag_arm: for the next step
+  bool run_global = false, run_cfl = false;   // the step in hand is armed (pop_time_manager took the arming): the flags the sites test
+  // device work space, allocated by the first armed site
+  double *partial = nullptr; size_t partial_n = 0;                            // workgroup partials of the global sums
+  double *vec = nullptr; size_t vec_n = 0;                                    // per-block results of every block of the decomposition
+  double *cfl_val = nullptr; int *cfl_idx = nullptr; size_t cfl_n = 0;        // workgroup (value, cell) pairs
+  // pinned host copies of vec, one per site
+  double *h_pre = nullptr, *h_after = nullptr, *h_cfl = nullptr;
+  int step_pre = -1, step_after = -1, step_cfl = -1;                          // nsteps_total of the step each site last ran in
+  double c2dtt_pre = 0.0, rms_after = 0.0; int iters_after = 0;
+};
+
 struct pop_ctx {
   HostModel h;
   bool host_only = true;
@@ -202,6 +216,7 @@ struct pop_ctx {
   double *op_scratch = nullptr;   // pop_operator_host: four block-sized 2-D arrays
   bool prio_on = false; int prio_least = 0;   // stream priorities in use; the lowest one
   TavgState tavg;
+  DiagState diag;
 };
 
 namespace {

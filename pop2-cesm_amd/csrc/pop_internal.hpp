@@ -110,6 +110,9 @@ struct HostModel {
   // Robert filter (tmix_opt = 3): time_management.F90:897-945, step_mod.F90:1577-1615
   double robert_curtime = 0, robert_newtime = 0, bgtarea_t_1 = 0, rf_volume_2_km = 0, open_ocean_volume_2_km = 0;
   int rf_nonzero_newtime = 0;
+  // areas and volumes of the global diagnostics (grid.F90:1059-1072); the _k arrays are 1-based with slot 0
+  double area_t = 0, volume_t = 0, volume_u = 0;
+  std::vector<double> area_t_k, volume_t_k;
   // P-CSI (solver_choice = 3): Lanczos eigenvalue bounds from host_pcsi_prep (POP_SolversMod.F90:181-320)
   double pcsi_max_eig = 0, pcsi_min_eig = 0;
   int pcsi_lanczos_steps = 0;

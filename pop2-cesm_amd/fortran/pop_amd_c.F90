@@ -496,6 +496,40 @@
          integer (c_int), value :: stream
          character (kind=c_char), intent(in) :: path(*)
       end function
+      ! ---- global and CFL diagnostics (diagnostics.F90)
+      integer (c_int) function pop_diag_arm(ctx, want_global, want_cfl) bind(C, name='pop_diag_arm')
+         import :: c_int, c_ptr
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: want_global, want_cfl
+      end function
+      integer (c_int) function pop_diag_value(ctx, name, n, val) bind(C, name='pop_diag_value')
+         import :: c_int, c_ptr, c_char, c_double
+         type (c_ptr), value :: ctx
+         character (kind=c_char), intent(in) :: name(*)
+         integer (c_int), value :: n
+         real (c_double), intent(out) :: val
+      end function
+      ! value_k, ij_k, nsteps_total: c_null_ptr, or the address of km doubles / 2 km integers / one integer
+      integer (c_int) function pop_diag_cfl(ctx, name, val, ijk, value_k, ij_k, nsteps_total) bind(C, name='pop_diag_cfl')
+         import :: c_int, c_ptr, c_char, c_double
+         type (c_ptr), value :: ctx
+         character (kind=c_char), intent(in) :: name(*)
+         real (c_double), intent(out) :: val
+         integer (c_int), intent(out) :: ijk(3)
+         type (c_ptr), value :: value_k, ij_k, nsteps_total
+      end function
+      integer (c_int) function pop_check_ke(ctx, ke_thresh, exceeded) bind(C, name='pop_check_ke')
+         import :: c_int, c_ptr, c_double
+         type (c_ptr), value :: ctx
+         real (c_double), value :: ke_thresh
+         integer (c_int), intent(out) :: exceeded
+      end function
+      integer (c_int) function pop_grid_volumes(ctx, area_t, volume_t, volume_u, area_t_k, volume_t_k) bind(C, name='pop_grid_volumes')
+         import :: c_int, c_ptr, c_double
+         type (c_ptr), value :: ctx
+         real (c_double), intent(out) :: area_t, volume_t, volume_u
+         real (c_double), intent(out) :: area_t_k(*), volume_t_k(*)
+      end function
    end interface
 
  contains

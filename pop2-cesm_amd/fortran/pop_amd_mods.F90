@@ -1062,3 +1062,147 @@
       errorCode = pop_tavg_read(pop_ctx, ns, cstr(filename))
    end subroutine
  end module tavg
+
+!-----------------------------------------------------------------------
+! source/diagnostics.F90: the global and CFL diagnostics the library forms on the device in an armed step.  The reference decides
+! per step from diag_global_freq / diag_cfl_freq (ldiag_global, ldiag_cfl); here the caller arms the next step with diag_arm.  The
+! getters carry the reference's variable names; tracer indices are 1-based as there.  A getter whose site has not run returns NaN
+! (the real-valued ones) or leaves errorCode set.
+ module diagnostics
+   use kinds_mod
+   use pop_amd_c
+   implicit none
+   private
+   public :: diag_arm, check_KE, diag_ke, diag_sealevel, diag_ws, diag_press_free, diag_ke_free, diag_ke_psfc, &
+             avg_tracer, sfc_tracer_flux, dtracer_avg, dtracer_abs, cfl_number, &
+             cfl_advu, cfl_advv, cfl_advw, cfl_advt, cfl_hdifft, cfl_hdiffu, cfl_vdifft, cfl_vdiffu
+ contains
+   ! ldiag_global / ldiag_cfl of the NEXT step only
+   subroutine diag_arm(ldiag_global, ldiag_cfl, errorCode)
+      logical (log_kind), intent(in) :: ldiag_global, ldiag_cfl
+      integer (int_kind), intent(out) :: errorCode
+      errorCode = pop_diag_arm(pop_ctx, merge(1, 0, ldiag_global), merge(1, 0, ldiag_cfl))
+   end subroutine
+   ! check_KE (diagnostics.F90:3260-3290); .true. as well when no armed step has run, so that a run without its
+   ! diagnostic is stopped rather than trusted
+   function check_KE(ke_thresh)
+      real (r8), intent(in) :: ke_thresh
+      logical (log_kind) :: check_KE
+      integer (c_int) :: ierr, exceeded
+      ierr = pop_check_ke(pop_ctx, ke_thresh, exceeded)
+      check_KE = ierr /= 0 .or. exceeded /= 0
+   end function
+   function diag_named(name, n) result(v)
+      character (*), intent(in) :: name
+      integer (int_kind), intent(in) :: n          ! 0-based tracer index
+      real (r8) :: v
+      integer (c_int) :: ierr
+      ierr = pop_diag_value(pop_ctx, cstr(name), n, v)
+      if (ierr /= 0) v = transfer(-2251799813685248_c_long_long, v)   ! a quiet NaN
+   end function
+   function diag_ke() result(v)
+      real (r8) :: v
+      v = diag_named('diag_ke', 0)
+   end function
+   function diag_sealevel() result(v)
+      real (r8) :: v
+      v = diag_named('diag_sealevel', 0)
+   end function
+   function diag_ws() result(v)
+      real (r8) :: v
+      v = diag_named('diag_ws', 0)
+   end function
+   function diag_press_free() result(v)
+      real (r8) :: v
+      v = diag_named('diag_press_free', 0)
+   end function
+   function diag_ke_free() result(v)
+      real (r8) :: v
+      v = diag_named('diag_ke_free', 0)
+   end function
+   function diag_ke_psfc() result(v)
+      real (r8) :: v
+      v = diag_named('diag_ke_psfc', 0)
+   end function
+   function avg_tracer(n) result(v)
+      integer (int_kind), intent(in) :: n
+      real (r8) :: v
+      v = diag_named('avg_tracer', n - 1)
+   end function
+   function sfc_tracer_flux(n) result(v)
+      integer (int_kind), intent(in) :: n
+      real (r8) :: v
+      v = diag_named('sfc_tracer_flux', n - 1)
+   end function
+   function dtracer_avg(n) result(v)
+      integer (int_kind), intent(in) :: n
+      real (r8) :: v
+      v = diag_named('dtracer_avg', n - 1)
+   end function
+   function dtracer_abs(n) result(v)
+      integer (int_kind), intent(in) :: n
+      real (r8) :: v
+      v = diag_named('dtracer_abs', n - 1)
+   end function
+   ! one CFL number of cfl_check by name ('advu' | 'advv' | 'advw' | 'advt' | 'hdifft' | 'hdiffu' | 'vdifft' | 'vdiffu') with the
+   ! global (i, j, k) of its maximum (cfladd_*)
+   subroutine cfl_number(name, cfl, cfladd, errorCode)
+      character (*), intent(in) :: name
+      real (r8), intent(out) :: cfl
+      integer (int_kind), dimension(3), intent(out) :: cfladd
+      integer (int_kind), intent(out) :: errorCode
+      errorCode = pop_diag_cfl(pop_ctx, cstr(name), cfl, cfladd, c_null_ptr, c_null_ptr, c_null_ptr)
+   end subroutine
+   function cfl_named(name, cfladd) result(v)
+      character (*), intent(in) :: name
+      integer (int_kind), dimension(3), intent(out), optional :: cfladd
+      real (r8) :: v
+      integer (int_kind) :: add(3), ierr
+      call cfl_number(name, v, add, ierr)
+      if (ierr /= 0) then
+         v = transfer(-2251799813685248_c_long_long, v)
+         add = 0
+      endif
+      if (present(cfladd)) cfladd = add
+   end function
+   function cfl_advu(cfladd) result(v)
+      integer (int_kind), dimension(3), intent(out), optional :: cfladd
+      real (r8) :: v
+      v = cfl_named('advu', cfladd)
+   end function
+   function cfl_advv(cfladd) result(v)
+      integer (int_kind), dimension(3), intent(out), optional :: cfladd
+      real (r8) :: v
+      v = cfl_named('advv', cfladd)
+   end function
+   function cfl_advw(cfladd) result(v)
+      integer (int_kind), dimension(3), intent(out), optional :: cfladd
+      real (r8) :: v
+      v = cfl_named('advw', cfladd)
+   end function
+   function cfl_advt(cfladd) result(v)
+      integer (int_kind), dimension(3), intent(out), optional :: cfladd
+      real (r8) :: v
+      v = cfl_named('advt', cfladd)
+   end function
+   function cfl_hdifft(cfladd) result(v)
+      integer (int_kind), dimension(3), intent(out), optional :: cfladd
+      real (r8) :: v
+      v = cfl_named('hdifft', cfladd)
+   end function
+   function cfl_hdiffu(cfladd) result(v)
+      integer (int_kind), dimension(3), intent(out), optional :: cfladd
+      real (r8) :: v
+      v = cfl_named('hdiffu', cfladd)
+   end function
+   function cfl_vdifft(cfladd) result(v)
+      integer (int_kind), dimension(3), intent(out), optional :: cfladd
+      real (r8) :: v
+      v = cfl_named('vdifft', cfladd)
+   end function
+   function cfl_vdiffu(cfladd) result(v)
+      integer (int_kind), dimension(3), intent(out), optional :: cfladd
+      real (r8) :: v
+      v = cfl_named('vdiffu', cfladd)
+   end function
+ end module diagnostics
