@@ -653,6 +653,60 @@ int pop_check_ke(pop_ctx *ctx, double ke_thresh, int *exceeded);
  * each, area_t_k, volume_t_k.  Any pointer may be NULL. */
 int pop_grid_volumes(pop_ctx *ctx, double *area_t, double *volume_t, double *volume_u, double *area_t_k, double *volume_t_k);
 
+/* ---- meridional overturning circulation (diags_on_lat_aux_grid.F90), accumulated on the device ---------------------------------
+ * The reference forms the MOC when it writes a tavg file, from the time means of WVEL, VVEL, WISOP, VISOP, WSUBM, VSUBM
+ * (tavg.F90:7204-7224, compute_moc :942-1288).  compute_moc is linear in them, so the library adds every step's binned sums,
+ * weighted like any tavg entry, into small accumulators on the device and holds no 3-D WVEL.  DESIGN.md section 16 has the rules.
+ *
+ * pop_init_transports: init_lat_aux_grid (:121-597) and init_moc_ts_transport_arrays (:603-936).  Once, after pop_create* (with
+ * several ranks on every rank, with the same arguments), before the first step or phase; a host-only context takes it too.
+ * region_mask_global: REGION_MASK as (ny_global, nx_global), i fastest; NULL = 1 on ocean cells and 0 on land, allowed with
+ * n_transport_reg = 1 only.  Region 1 is REGION_MASK > 0; region 2 is abs(REGION_MASK) in reg2_numbers (the caller resolves
+ * transport_reg2_names to numbers and leaves marginal seas out).  The reference's refusals come back as errors with its reasons. */
+#define POP_MAX_TRANSPORT_REG2 16
+typedef struct pop_transports_nml {
+  int struct_bytes;              /* in: sizeof(pop_transports_nml) */
+  int lat_aux_grid_type;         /* 0 'southern' (default), 1 'full', 2 'user-specified' */
+  int n_lat_aux_grid;            /* 'user-specified' only (default 180); the other types derive it */
+  int n_transport_reg;           /* 1 or 2 (default 2) */
+  int nreg2;                     /* entries of reg2_numbers */
+  int reg2_numbers[POP_MAX_TRANSPORT_REG2];
+  double lat_aux_begin, lat_aux_end;   /* 'user-specified' only: edge latitudes, degrees north (default -90, 90) */
+} pop_transports_nml;
+void pop_transports_nml_init(pop_transports_nml *nml);
+int pop_init_transports(pop_ctx *ctx, const pop_transports_nml *nml, const int *region_mask_global);
+/* lat_aux_edge (n + 1 doubles) and lat_aux_center (n doubles), degrees north; either array may be NULL */
+int pop_lat_aux_grid(pop_ctx *ctx, int *n_lat_aux_grid, double *edge, double *center);
+/* n_lat_aux_grid, km + 1, n_moc_comp (1 Eulerian; 2 + bolus with hmix_tracer = 3 and gm_diag_bolus; 3 + submesoscale with
+ * lsubmesoscale_mixing, which needs submeso_diag = 1) and n_transport_reg.  pop_get_dim "lat_aux_region_start" is the row south of
+ * the southernmost row of region 2 (1-based global j; 0 with one region). */
+int pop_moc_info(pop_ctx *ctx, int *n_lat_aux_grid, int *km1, int *n_moc_comp, int *n_transport_reg);
+/* MASK_LAT_DEPTH(n, k, m) as mask[n - 1][k - 1][m - 1] (m fastest), 1 = .true. = no ocean cell of region m at level k in bin n;
+ * count = n_lat_aux_grid * km * n_transport_reg */
+int pop_moc_mask(pop_ctx *ctx, int *mask, long long count);
+/* the bin of every cell as (ny_global, nx_global): b = 1 .. n_lat_aux_grid when lat_aux_edge(b) <= TLATD < lat_aux_edge(b + 1)
+ * (the reference's loop index n = b + 1), 0 when the cell lies in no bin */
+int pop_moc_bin_map(pop_ctx *ctx, int *bins, long long count);
+/* put the MOC into one tavg stream, 1 .. POP_TAVG_MAX_STREAMS: it follows that stream's ltavg_on, tavg_sum and the weight of the
+ * step, and pop_tavg_reset of the stream zeroes its sums.  A stream without an entry is switched on, as by its first
+ * pop_tavg_request.  Refused between pop_time_manager and pop_step_tail, before pop_init_transports, and a second time.  The
+ * sums are taken at the end of pop_baroclinic_driver (phase "tavg_moc" of pop_run_phase / pop_time_phase). */
+int pop_moc_request(pop_ctx *ctx, int stream);
+/* TAVG_MOC_G(n, k, comp, reg) in Sverdrups as out[n - 1][k - 1][comp - 1][reg - 1] (reg fastest), count = (n_lat_aux_grid + 1) *
+ * (km + 1) * n_moc_comp * n_transport_reg; in r8, where the reference stores r4.  normalize = 1: scaled by 1 / tavg_sum (an error
+ * when that is 0); 0: the sums as they are.  which = 0: the running interval; 1: the snapshot pop_tavg_write(stream, path, 0) took
+ * just before it reset the stream.  Synchronises; with several ranks collective, and the same on every rank. */
+int pop_moc_get(pop_ctx *ctx, int normalize, int which, double *out, long long count);
+/* the reduced unnormalised sums of the running interval, for a caller that carries them across a restart: bins as
+ * [n_lat_aux_grid][km][n_moc_comp][n_transport_reg], then the southern-boundary rows of region 2 as [km][n_moc_comp] (only with two
+ * regions).  pop_moc_sums_set takes such a vector: it replaces the sums of the interval (the device accumulators start from 0) and is
+ * added last when the sums are next read, so a continued run equals the uninterrupted one to rounding, not bit for bit.  The
+ * caller carries tavg_sum of the stream beside it (pop_tavg_write(.., 1) / pop_tavg_read).  Refused between pop_time_manager and
+ * pop_step_tail.  count = pop_moc_sums_count. */
+long long pop_moc_sums_count(pop_ctx *ctx);
+int pop_moc_sums_get(pop_ctx *ctx, double *sums, long long count);
+int pop_moc_sums_set(pop_ctx *ctx, const double *sums, long long count);
+
 /* run all launches on the host framework's HIP stream (e.g. torch.cuda.current_stream().cuda_stream) */
 int pop_set_stream(pop_ctx *ctx, void *hip_stream);
 

@@ -97,6 +97,11 @@ def lib():
         "pop_diag_arm": (ci, [vp, ci, ci]), "pop_diag_global_get": (ci, [vp, vp, pd, ll]), "pop_diag_value": (ci, [vp, cs, ci, pd]),
         "pop_diag_cfl": (ci, [vp, cs, pd, pi, pd, pi, pi]), "pop_check_ke": (ci, [vp, cd, pi]),
         "pop_grid_volumes": (ci, [vp, pd, pd, pd, pd, pd]),
+        "pop_transports_nml_init": (None, [vp]), "pop_init_transports": (ci, [vp, vp, pi]),
+        "pop_lat_aux_grid": (ci, [vp, pi, pd, pd]), "pop_moc_info": (ci, [vp, pi, pi, pi, pi]),
+        "pop_moc_mask": (ci, [vp, pi, ll]), "pop_moc_bin_map": (ci, [vp, pi, ll]), "pop_moc_request": (ci, [vp, ci]),
+        "pop_moc_get": (ci, [vp, ci, ci, pd, ll]), "pop_moc_sums_count": (ll, [vp]),
+        "pop_moc_sums_get": (ci, [vp, pd, ll]), "pop_moc_sums_set": (ci, [vp, pd, ll]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)       # AttributeError here = the library does not export the ABI
@@ -289,6 +294,37 @@ def ice_nml(**kw):
             v = TFREEZE_OPTION[v]
         if not hasattr(n, k):
             raise AttributeError("pop_ice_nml has no field %r" % k)
+        setattr(n, k, v)
+    return n
+
+
+MAX_TRANSPORT_REG2 = 16
+LAT_AUX_GRID_TYPE = {"sou": 0, "ful": 1, "use": 2}       # the reference looks at the first three letters (diags_on_lat_aux_grid.F90:312)
+
+
+class PopTransportsNml(C.Structure):
+    """include/pop_amd.h pop_transports_nml"""
+    _fields_ = [(n, C.c_int) for n in ("struct_bytes", "lat_aux_grid_type", "n_lat_aux_grid", "n_transport_reg", "nreg2")] + \
+        [("reg2_numbers", C.c_int * MAX_TRANSPORT_REG2), ("lat_aux_begin", C.c_double), ("lat_aux_end", C.c_double)]
+
+
+def transports_nml(reg2_numbers=(), **kw):
+    """pop_transports_nml with the code defaults (pop_transports_nml_init: 'southern', -90, 90, 180), then the keywords: the members by
+    name; lat_aux_grid_type may also be 'southern' | 'full' | 'user-specified' (any other string is the reference's unknown choice).
+    reg2_numbers: the REGION_MASK numbers of transport_reg2_names; n_transport_reg defaults to 2 when some are given, else to 1."""
+    n = PopTransportsNml()
+    lib().pop_transports_nml_init(C.byref(n))
+    if len(reg2_numbers) > MAX_TRANSPORT_REG2:
+        raise ValueError("at most %d region numbers" % MAX_TRANSPORT_REG2)
+    n.nreg2 = len(reg2_numbers)
+    for i, r in enumerate(reg2_numbers):
+        n.reg2_numbers[i] = int(r)
+    n.n_transport_reg = 2 if len(reg2_numbers) else 1
+    for k, v in kw.items():
+        if k == "lat_aux_grid_type" and isinstance(v, str):
+            v = LAT_AUX_GRID_TYPE.get(v[:3], -1)
+        if not hasattr(n, k):
+            raise AttributeError("pop_transports_nml has no field %r" % k)
         setattr(n, k, v)
     return n
 
@@ -577,6 +613,72 @@ class PopModel:
         P = C.POINTER(C.c_double)
         self._chk(self.L.pop_grid_volumes(self.h, C.byref(a), C.byref(vt), C.byref(vu), ak.ctypes.data_as(P), vk.ctypes.data_as(P)))
         return {"area_t": a.value, "volume_t": vt.value, "volume_u": vu.value, "area_t_k": ak, "volume_t_k": vk}
+
+    # ---- meridional overturning circulation (diags_on_lat_aux_grid.F90; include/pop_amd.h pop_init_transports, pop_moc_*)
+    def init_transports(self, region_mask=None, reg2_numbers=(), **nml):
+        """init_lat_aux_grid and init_moc_ts_transport_arrays: region_mask = REGION_MASK as a global (ny_global, nx_global) integer
+        array, or None (1 on ocean cells, one region only); reg2_numbers and keywords as transports_nml().  Once, before the first
+        step or phase; on every rank.  Returns the pop_transports_nml that was passed."""
+        n = transports_nml(reg2_numbers, **nml)
+        rm = None
+        if region_mask is not None:
+            rm = np.ascontiguousarray(region_mask, dtype=np.int32)
+            if rm.shape != (self.cfg.ny_global, self.cfg.nx_global):
+                raise ValueError("region_mask: shape %s, expected (ny_global, nx_global)" % (rm.shape,))
+        self._chk(self.L.pop_init_transports(self.h, C.byref(n), rm.ctypes.data_as(C.POINTER(C.c_int)) if rm is not None else None))
+        return n
+
+    def moc_info(self):
+        """dict(n_lat_aux_grid, km1 = km + 1, n_moc_comp, n_transport_reg, lat_aux_region_start)"""
+        v = [C.c_int() for _ in range(4)]
+        self._chk(self.L.pop_moc_info(self.h, *[C.byref(x) for x in v]))
+        out = dict(zip(("n_lat_aux_grid", "km1", "n_moc_comp", "n_transport_reg"), [x.value for x in v]))
+        out["lat_aux_region_start"] = self.dim("lat_aux_region_start")
+        return out
+
+    def lat_aux_grid(self):
+        """(lat_aux_edge (n + 1,), lat_aux_center (n,)) in degrees north"""
+        n = self.moc_info()["n_lat_aux_grid"]
+        e, c = np.empty(n + 1, dtype=np.float64), np.empty(n, dtype=np.float64)
+        P = C.POINTER(C.c_double)
+        self._chk(self.L.pop_lat_aux_grid(self.h, None, e.ctypes.data_as(P), c.ctypes.data_as(P)))
+        return e, c
+
+    def moc_mask(self):
+        """MASK_LAT_DEPTH as a bool array (n_lat_aux_grid, km, n_transport_reg)"""
+        inf = self.moc_info()
+        a = np.empty((inf["n_lat_aux_grid"], self.km, inf["n_transport_reg"]), dtype=np.int32)
+        self._chk(self.L.pop_moc_mask(self.h, a.ctypes.data_as(C.POINTER(C.c_int)), a.size))
+        return a != 0
+
+    def moc_bin_map(self):
+        """(ny_global, nx_global): the 1-based bin of every cell, 0 = in no bin"""
+        a = np.empty((self.cfg.ny_global, self.cfg.nx_global), dtype=np.int32)
+        self._chk(self.L.pop_moc_bin_map(self.h, a.ctypes.data_as(C.POINTER(C.c_int)), a.size))
+        return a
+
+    def moc_request(self, stream):
+        """put the MOC into tavg stream 1 .. 9 (its ltavg_on, tavg_sum and reset)"""
+        self._chk(self.L.pop_moc_request(self.h, stream))
+
+    def moc_get(self, normalize=True, snapshot=False):
+        """TAVG_MOC_G in Sverdrups as (n_lat_aux_grid + 1, km + 1, n_moc_comp, n_transport_reg); snapshot: the one tavg_write took
+        before it reset the stream"""
+        inf = self.moc_info()
+        a = np.empty((inf["n_lat_aux_grid"] + 1, inf["km1"], inf["n_moc_comp"], inf["n_transport_reg"]), dtype=np.float64)
+        self._chk(self.L.pop_moc_get(self.h, 1 if normalize else 0, 1 if snapshot else 0, a.ctypes.data_as(C.POINTER(C.c_double)), a.size))
+        return a
+
+    def moc_sums(self, values=None):
+        """the reduced unnormalised sums of the running interval as one vector (bins (n, km, comp, reg), then the boundary row of
+        region 2 (km, comp)); with `values` such a vector replaces the sums (it is added last when they are next read)"""
+        if values is not None:
+            v = np.ascontiguousarray(values, dtype=np.float64)
+            self._chk(self.L.pop_moc_sums_set(self.h, v.ctypes.data_as(C.POINTER(C.c_double)), v.size))
+            return v
+        a = np.empty(max(self.L.pop_moc_sums_count(self.h), 0), dtype=np.float64)
+        self._chk(self.L.pop_moc_sums_get(self.h, a.ctypes.data_as(C.POINTER(C.c_double)), a.size))
+        return a
 
     # ---- step_mod.F90 sequence
     def time_manager(self):

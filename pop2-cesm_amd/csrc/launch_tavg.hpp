@@ -42,7 +42,7 @@ const char *const tavg_left_out[] = {
   "UPV", "VPV", "UQ", "VQ", "UTE_POS", "UTE_NEG", "VTN_POS", "VTN_NEG", "WTK_POS", "WTK_NEG", "UEU", "VNU", "UEV", "VNV", "WTU", "WTV",
   "ADVU", "ADVV", "GRADX", "GRADY", "HDIFFU", "HDIFFV", "VDIFFU", "VDIFFV", "UDP",
   "HDIFT", "HDIFS", "DIA_IMPVF_TEMP", "DIA_IMPVF_SALT", "RF_TEND_TEMP", "RF_TEND_SALT", "RESID_T", "RESID_S",
-  "TEMP_27", "TEMP_43", "BSF", "MOC", "N_HEAT", "N_SALT", "U2_2", "V2_2", "VDC_BCK", "VVC_BCK", "TFW_T", "TFW_S", "SFWF_WRST",
+  "TEMP_27", "TEMP_43", "BSF", "N_HEAT", "N_SALT", "U2_2", "V2_2", "VDC_BCK", "VVC_BCK", "TFW_T", "TFW_S", "SFWF_WRST",
   "TEMP_z_t_150m", "SALT_z_t_150m", "UVEL_z_t_150m", "VVEL_z_t_150m"};
 
 // every entry this configuration knows.  Host logic only: a host-only context answers pop_tavg_info from it too
@@ -272,6 +272,7 @@ int tavg_reset_stream(pop_ctx *c, int ns) {
   for (const TavgEntry &e : T.req) if (e.stream == ns && tavg_fill(c, e)) return 1;
   T.sum[ns] = 0.0;
   if (T.has_qflux[ns]) T.sum_qflux[ns] = 0.0;
+  if (c->moc.requested && c->moc.stream == ns && moc_reset(c)) return 1;
   return 0;
 }
 void tavg_refresh_flags(pop_ctx *c) {
@@ -280,6 +281,8 @@ void tavg_refresh_flags(pop_ctx *c) {
   for (int ns = 1; ns <= TAVG_MAX_STREAMS; ++ns) { T.used[ns] = false; T.has_qflux[ns] = false; }
   for (const TavgEntry &e : T.req) { T.used[e.stream] = true; if (e.method == TAVG_QFLUX) T.has_qflux[e.stream] = true; if (T.on[e.stream]) T.active = true; }
   T.dirty = true;
+  if (c->moc.requested) T.used[c->moc.stream] = true;   // the stream of pop_moc_request holds the MOC
+  c->moc.active = c->moc.requested && T.on[c->moc.stream];
 }
 TavgEntry *tavg_find(pop_ctx *c, const char *name) {
   for (TavgEntry &e : c->tavg.req) if (e.name == name) return &e;

@@ -24,6 +24,7 @@
 #include "kernels_pcg_persist.hpp"
 #include "kernels_tavg.hpp"
 #include "kernels_diag.hpp"
+#include "kernels_moc.hpp"
 #include "rccl_transport.hpp"
 
 using namespace pop;
@@ -31,6 +32,7 @@ using namespace pop;
 #include "pop_ctx.hpp"
 #include "launch_halo.hpp"
 #include "launch_solvers.hpp"
+#include "launch_moc.hpp"
 #include "launch_tavg.hpp"
 #include "launch_diag.hpp"
 
@@ -1045,6 +1047,8 @@ int pop_get_dim(const pop_ctx *c, const char *name) {
   if (n == "max_blocks_per_rank") return c->max_blocks_per_rank;
   if (n == "ocean_columns_local") return (int)c->h.ocean_cols_local;     // POP_CREATE_PLAN_ONLY contexts (-1 otherwise)
   if (n == "ocean_columns_total") return (int)c->h.ocean_cols_total;
+  if (n == "lat_aux_region_start") return (c->moc.aux.inited && c->moc.aux.n_reg > 1) ? c->moc.aux.region_start[1] : 0;   // pop_init_transports
+  if (n == "moc_stream") return c->moc.requested ? c->moc.stream : 0;
   return -1;
 }
 double pop_get_scalar(const pop_ctx *c, const char *name) {
@@ -1886,6 +1890,7 @@ int pop_baroclinic_driver(pop_ctx *c) {
     c->vmixu_pending = true;
   } else if (phase_impvmixu(c, nullptr)) return 1;
   if (c->diag.run_cfl && diag_cfl(c)) return 1;   // cfl_check (baroclinic.F90:1203)
+  if (c->moc.active && moc_site(c)) return 1;     // the binned sums of compute_moc from the U, V, DH advt saw
   HIPCHK(c, hipGetLastError());
   return 0;
 }
@@ -2765,6 +2770,7 @@ static phase_fn_t phase_by_name(const std::string &p) {
   if (p == "diag_global_preupdate") return diag_phase_pre;
   if (p == "diag_global_afterupdate") return diag_phase_after;
   if (p == "diag_cfl") return diag_phase_cfl;
+  if (p == "tavg_moc") return moc_phase;   // the MOC site on its own, with the weight of the last pop_time_manager (launch_moc.hpp)
   if (p == "block_sums") return [](pop_ctx *x) { SolveView v = local_view(x); presum(x, v, v.partial, v.blocksum + 2 * v.nblocks_tot); return 0; };
   return nullptr;
 }
@@ -2815,6 +2821,7 @@ int pop_tavg_request(pop_ctx *c, int ns, const char *name) {
   if (c->h.plan_only) { c->err = "pop_tavg_request: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
   if (tavg_stream_ok(c, ns, "pop_tavg_request") || tavg_between_steps(c, "pop_tavg_request")) return 1;
   const std::string nm(name);
+  if (nm == "MOC") { c->err = "pop_tavg_request: MOC is not a slab field: it is requested with pop_moc_request(stream) and read with pop_moc_get"; return 1; }
   if (const TavgEntry *e = tavg_find(c, name)) { c->err = "pop_tavg_request: " + nm + " is already requested, in stream " + std::to_string(e->stream) + " (a name belongs to one stream)"; return 1; }
   for (const char *l : tavg_left_out) if (nm == l) { c->err = "pop_tavg_request: " + nm + " is known to the reference, not built (DESIGN.md section 14)"; return 1; }
   const std::vector<TavgAvail> avail = tavg_avail(c);
@@ -2848,6 +2855,7 @@ int pop_tavg_set_on(pop_ctx *c, int ns, int on) {
 int pop_tavg_info(pop_ctx *c, const char *name, int *stream, int *ndims, int *nlevels, int *method) {
   if (!c) return 1;
   const std::string nm(name ? name : "");
+  if (nm == "MOC") { c->err = "pop_tavg_info: MOC is not a slab field: it is requested with pop_moc_request(stream) and read with pop_moc_get"; return 1; }
   for (const char *l : tavg_left_out) if (nm == l) { c->err = "pop_tavg_info: " + nm + " is known to the reference, not built (DESIGN.md section 14)"; return 1; }
   for (const TavgAvail &a : tavg_avail(c)) {
     if (a.name != nm) continue;
@@ -2906,6 +2914,7 @@ int pop_tavg_write(pop_ctx *c, int ns, const char *path, int restart_type) {
                                        {"nsteps_total", "int", std::to_string(c->nsteps_total)}};   // tavg.F90:2003-2007
   auto fetch = [&](size_t i, double *buf) { return tavg_to_host(c, *ent[i], restart_type == 0, buf); };
   if (slab_file_write(c->h, path, at, fields, fetch, "tavg", c->err)) return 1;
+  if (restart_type == 0 && c->moc.requested && c->moc.stream == ns && moc_snapshot(c)) return 1;   // write, then reset: the MOC of the interval stays readable
   return restart_type == 0 ? tavg_reset_stream(c, ns) : 0;
 }
 int pop_tavg_read(pop_ctx *c, int ns, const char *path) {
@@ -3006,6 +3015,89 @@ int pop_grid_volumes(pop_ctx *c, double *area_t, double *volume_t, double *volum
   if (volume_u) *volume_u = h.volume_u;
   if (area_t_k) std::copy(h.area_t_k.begin() + 1, h.area_t_k.end(), area_t_k);
   if (volume_t_k) std::copy(h.volume_t_k.begin() + 1, h.volume_t_k.end(), volume_t_k);
+  return 0;
+}
+
+// ---- meridional overturning circulation (diags_on_lat_aux_grid.F90; host_lat_aux.cpp, kernels_moc.hpp, launch_moc.hpp)
+void pop_transports_nml_init(pop_transports_nml *nml) { if (nml) transports_nml_defaults(*nml); }
+int pop_init_transports(pop_ctx *c, const pop_transports_nml *nml, const int *region_mask_global) {
+  if (!c) return 1;
+  if (!nml || nml->struct_bytes != (int)sizeof(pop_transports_nml)) { c->err = "pop_init_transports: struct_bytes is not sizeof(pop_transports_nml)"; return 1; }
+  if (c->h.plan_only) { c->err = "pop_init_transports: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+  if (c->moc.aux.inited) { c->err = "pop_init_transports: called twice"; return 1; }
+  if (c->ran) { c->err = "pop_init_transports: call it before the first step or phase"; return 1; }
+  LatAux aux;
+  if (host_lat_aux_build(c->h, *nml, region_mask_global, aux, c->err)) return 1;
+  c->moc.aux = std::move(aux);
+  return 0;
+}
+int pop_lat_aux_grid(pop_ctx *c, int *n, double *edge, double *center) {
+  if (!c || moc_inited(c, "pop_lat_aux_grid")) return 1;
+  const LatAux &A = c->moc.aux;
+  if (n) *n = A.n_lat;
+  if (edge) std::copy(A.edge.begin(), A.edge.end(), edge);
+  if (center) std::copy(A.center.begin(), A.center.end(), center);
+  return 0;
+}
+int pop_moc_info(pop_ctx *c, int *n_lat, int *km1, int *n_comp, int *n_reg) {
+  if (!c || moc_inited(c, "pop_moc_info")) return 1;
+  if (n_lat) *n_lat = c->moc.aux.n_lat;
+  if (km1) *km1 = c->h.km + 1;
+  if (n_comp) *n_comp = c->moc.aux.n_comp;
+  if (n_reg) *n_reg = c->moc.aux.n_reg;
+  return 0;
+}
+int pop_moc_mask(pop_ctx *c, int *mask, long long count) {
+  if (!c || moc_inited(c, "pop_moc_mask")) return 1;
+  return copy_out(c, c->moc.aux.mask, mask, count, "MASK_LAT_DEPTH");
+}
+int pop_moc_bin_map(pop_ctx *c, int *bins, long long count) {
+  if (!c || moc_inited(c, "pop_moc_bin_map")) return 1;
+  return copy_out(c, c->moc.aux.bin_map, bins, count, "the bin map");
+}
+int pop_moc_request(pop_ctx *c, int ns) {
+  if (!c) return 1;
+  if (c->h.plan_only) { c->err = "pop_moc_request: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+  if (tavg_stream_ok(c, ns, "pop_moc_request") || tavg_between_steps(c, "pop_moc_request") || moc_inited(c, "pop_moc_request")) return 1;
+  if (c->moc.requested) { c->err = "pop_moc_request: MOC is already requested, in stream " + std::to_string(c->moc.stream); return 1; }
+  if (!c->host_only && (join_side(c, true) || moc_alloc(c))) return 1;
+  const bool first = !c->tavg.used[ns];
+  c->moc.requested = true; c->moc.stream = ns;
+  if (first) c->tavg.on[ns] = true;   // as the first pop_tavg_request of a stream
+  tavg_refresh_flags(c);
+  return 0;
+}
+int pop_moc_get(pop_ctx *c, int normalize, int which, double *out, long long count) {
+  if (need_device(c) || moc_inited(c, "pop_moc_get")) return 1;
+  if (!c->moc.requested) { c->err = "pop_moc_get: pop_moc_request has not been called"; return 1; }
+  if (which != 0 && which != 1) { c->err = "pop_moc_get: which 0 (the running interval) or 1 (the snapshot of pop_tavg_write)"; return 1; }
+  if (count_is(c, (long long)moc_n_out(c), count, "MOC")) return 1;
+  if (which == 1) {
+    if (!c->moc.have_snap) { c->err = "pop_moc_get: no snapshot yet: pop_tavg_write(stream, path, 0) of the MOC's stream takes it"; return 1; }
+    std::copy(c->moc.snap.begin(), c->moc.snap.end(), out);
+    return 0;
+  }
+  double factor;
+  std::vector<double> sums;
+  if (moc_factor(c, normalize, &factor) || join_side(c, true) || moc_reduce(c, sums)) return 1;
+  moc_finish(c, sums, factor, out);
+  return 0;
+}
+long long pop_moc_sums_count(pop_ctx *c) { return (c && c->moc.aux.inited) ? (long long)moc_n_sums(c) : -1; }
+int pop_moc_sums_get(pop_ctx *c, double *sums, long long count) {
+  if (need_device(c) || moc_inited(c, "pop_moc_sums_get")) return 1;
+  if (!c->moc.requested) { c->err = "pop_moc_sums_get: pop_moc_request has not been called"; return 1; }
+  std::vector<double> s;
+  if (count_is(c, (long long)moc_n_sums(c), count, "the MOC sums") || join_side(c, true) || moc_reduce(c, s)) return 1;
+  std::copy(s.begin(), s.end(), sums);
+  return 0;
+}
+int pop_moc_sums_set(pop_ctx *c, const double *sums, long long count) {
+  if (need_device(c) || moc_inited(c, "pop_moc_sums_set")) return 1;
+  if (!c->moc.requested) { c->err = "pop_moc_sums_set: pop_moc_request has not been called"; return 1; }
+  if (tavg_between_steps(c, "pop_moc_sums_set") || count_is(c, (long long)moc_n_sums(c), count, "the MOC sums")) return 1;
+  if (moc_reset(c)) return 1;   // the vector replaces the sums of the interval
+  c->moc.set_sums.assign(sums, sums + count);
   return 0;
 }
 

@@ -57,6 +57,19 @@ struct DiagState {
   double c2dtt_pre = 0.0, rms_after = 0.0; int iters_after = 0;
 };
 
+// ---- meridional overturning circulation (diags_on_lat_aux_grid.F90; host_lat_aux.cpp, launch_moc.hpp)
+struct MocState {
+  LatAux aux;                                       // pop_init_transports
+  bool requested = false; int stream = 0;           // pop_moc_request
+  bool active = false;                              // requested and the stream is on: the one flag the site of a step tests
+  std::vector<int> loc_list, loc_blist;             // the lists of aux.lists / aux.blists that belong to this rank's blocks
+  // device: the local lists (block = local index), their cells, the accumulators and the scratch field of k_moc_w
+  MocList *d_lists = nullptr, *d_blists = nullptr; int *d_cells = nullptr, *d_bcells = nullptr;
+  double *ACC = nullptr, *BACC = nullptr, *WE = nullptr, *gather = nullptr;
+  std::vector<double> set_sums;                     // pop_moc_sums_set: added last when the sums are read
+  std::vector<double> snap; bool have_snap = false; // the normalised result pop_tavg_write took before it reset the stream
+};
+
 struct pop_ctx {
   HostModel h;
   bool host_only = true;
@@ -217,6 +230,7 @@ struct pop_ctx {
   bool prio_on = false; int prio_least = 0;   // stream priorities in use; the lowest one
   TavgState tavg;
   DiagState diag;
+  MocState moc;
 };
 
 namespace {

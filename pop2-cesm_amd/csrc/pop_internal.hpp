@@ -143,6 +143,25 @@ struct IceConsts { double cp_over_lhfusion, salice, salref, hflux_factor; };
 void ice_nml_defaults(pop_ice_nml &n);
 int ice_nml_check(const HostModel &h, const pop_ice_nml &n, std::string &err);
 IceConsts ice_consts(const pop_ice_nml &n);
+// ---- auxiliary latitude grid and transport regions of the MOC (host_lat_aux.cpp; diags_on_lat_aux_grid.F90:121-936)
+// A cell list holds the physical ocean cells of one block that lie in one bin and in some region, in (j, i) order, as
+// p2 | flag << MOC_FLAG_SHIFT (p2 = j * nxb + i inside the block; flag bit 0: region 1, bit 1: region 2).  Lists are numbered over
+// ALL blocks in (block id, bin) order, so every rank knows where another rank's sums belong.
+constexpr int MOC_FLAG_SHIFT = 29;
+struct MocList { int block, bin, off, cnt; };      // block: 0-based global id; bin: 0-based (the reference's n - 2)
+struct LatAux {
+  bool inited = false;
+  pop_transports_nml nml{};
+  int n_lat = 0, n_reg = 1, n_comp = 1, j_southern = 0;
+  std::vector<double> edge, center;                // lat_aux_edge (n_lat + 1), lat_aux_center (n_lat)
+  std::vector<int> region_start;                   // lat_aux_region_start(m), slot m - 1
+  std::vector<int> mask;                           // MASK_LAT_DEPTH as [n][k][m], 1 = .true.
+  std::vector<int> bin_map;                        // (ny_global, nx_global): 1-based bin, 0 = none
+  std::vector<MocList> lists; std::vector<int> cells;       // the bins
+  std::vector<MocList> blists; std::vector<int> bcells;     // row lat_aux_region_start(2) (bin unused): plain p2
+};
+void transports_nml_defaults(pop_transports_nml &n);
+int host_lat_aux_build(const HostModel &h, const pop_transports_nml &nml, const int *region_mask_global, LatAux &out, std::string &err);
 // ---- POP binary restart files (host_restart.cpp; restart.F90, io_binary.F90)
 // one field of a restart or tavg file: records id .. id + nlev - 1, held on the host as (nxb, nyb, nlev, nblocks)
 struct RestartField {

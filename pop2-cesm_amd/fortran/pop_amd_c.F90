@@ -113,6 +113,13 @@
       integer (c_int) :: struct_bytes, ice_freq_opt, licecesm2, kmxice, lactive_ice, lfw_as_salt_flx, tfreeze_option
       real (c_double) :: sea_ice_salinity, ocn_ref_salinity, latent_heat_fusion, cp_sw, rho_sw, rho_fw
    end type pop_ice_nml
+   ! mirrors `struct pop_transports_nml` (transports_nml); fill with pop_transports_nml_init, then set fields
+   integer (c_int), parameter :: POP_MAX_TRANSPORT_REG2 = 16
+   type, bind(C) :: pop_transports_nml
+      integer (c_int) :: struct_bytes, lat_aux_grid_type, n_lat_aux_grid, n_transport_reg, nreg2
+      integer (c_int) :: reg2_numbers(POP_MAX_TRANSPORT_REG2)
+      real (c_double) :: lat_aux_begin, lat_aux_end
+   end type pop_transports_nml
 
    type (c_ptr), save :: pop_ctx = c_null_ptr   ! the one model instance of this task
 
@@ -529,6 +536,40 @@
          type (c_ptr), value :: ctx
          real (c_double), intent(out) :: area_t, volume_t, volume_u
          real (c_double), intent(out) :: area_t_k(*), volume_t_k(*)
+      end function
+      ! ---- meridional overturning circulation (diags_on_lat_aux_grid.F90)
+      subroutine pop_transports_nml_init(nml) bind(C, name='pop_transports_nml_init')
+         import :: pop_transports_nml
+         type (pop_transports_nml), intent(out) :: nml
+      end subroutine
+      ! region_mask_global: c_null_ptr, or the address of REGION_MASK as (nx_global, ny_global) integers
+      integer (c_int) function pop_init_transports(ctx, nml, region_mask_global) bind(C, name='pop_init_transports')
+         import :: c_int, c_ptr, pop_transports_nml
+         type (c_ptr), value :: ctx, region_mask_global
+         type (pop_transports_nml), intent(in) :: nml
+      end function
+      ! edge, center: c_null_ptr, or the address of n + 1 / n doubles
+      integer (c_int) function pop_lat_aux_grid(ctx, n, edge, center) bind(C, name='pop_lat_aux_grid')
+         import :: c_int, c_ptr
+         type (c_ptr), value :: ctx, edge, center
+         integer (c_int), intent(out) :: n
+      end function
+      integer (c_int) function pop_moc_info(ctx, n_lat, km1, n_comp, n_reg) bind(C, name='pop_moc_info')
+         import :: c_int, c_ptr
+         type (c_ptr), value :: ctx
+         integer (c_int), intent(out) :: n_lat, km1, n_comp, n_reg
+      end function
+      integer (c_int) function pop_moc_request(ctx, stream) bind(C, name='pop_moc_request')
+         import :: c_int, c_ptr
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: stream
+      end function
+      integer (c_int) function pop_moc_get(ctx, normalize, which, moc, count) bind(C, name='pop_moc_get')
+         import :: c_int, c_ptr, c_double, c_long_long
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: normalize, which
+         real (c_double), intent(out) :: moc(*)             ! [n][k][comp][reg], reg fastest
+         integer (c_long_long), value :: count
       end function
    end interface
 

@@ -25,7 +25,7 @@
  module kinds_mod            ! source/kinds_mod.F90:31-38
    use, intrinsic :: iso_c_binding
    implicit none
-   integer, parameter, public :: int_kind = c_int, log_kind = kind(.true.), r8 = c_double, char_len = 256
+   integer, parameter, public :: int_kind = c_int, log_kind = kind(.true.), r8 = c_double, r4 = c_float, char_len = 256
    integer, parameter, public :: POP_i4 = c_int, POP_r8 = c_double, POP_r4 = c_float, POP_logical = kind(.true.), POP_Success = 0, POP_Fail = 1
  end module kinds_mod
 
@@ -1062,6 +1062,80 @@
       errorCode = pop_tavg_read(pop_ctx, ns, cstr(filename))
    end subroutine
  end module tavg
+
+!-----------------------------------------------------------------------
+! source/diags_on_lat_aux_grid.F90: the auxiliary latitude grid, the transport regions and the MOC.  The reference reads transports_nml
+! in init_lat_aux_grid and finds REGION_MASK in its grid module; here the caller fills `transports` (and REGION_MASK_G, where
+! there are two regions) before init_lat_aux_grid, which only checks them; init_moc_ts_transport_arrays builds the grid, the regions
+! and the cell lists in the library and puts the MOC into tavg stream moc_stream.  The sums are taken inside the library's step, so
+! compute_moc has no arguments: it fills TAVG_MOC_G from what the stream has accumulated (r4, as the reference stores it).
+ module diags_on_lat_aux_grid
+   use kinds_mod
+   use pop_amd_c
+   implicit none
+   private
+   public :: init_lat_aux_grid, init_moc_ts_transport_arrays, compute_moc
+   real (r8), dimension(:), allocatable, public :: lat_aux_center, lat_aux_edge
+   integer (int_kind), public :: n_lat_aux_grid = 0, n_transport_reg = 0, n_moc_comp = 0
+   real (r4), dimension(:,:,:,:), allocatable, public :: TAVG_MOC_G          ! (n_lat_aux_grid+1, km+1, n_moc_comp, n_transport_reg)
+   type (pop_transports_nml), public :: transports                            ! transports_nml; defaults from init_transports_nml
+   integer (int_kind), dimension(:,:), allocatable, target, public :: REGION_MASK_G   ! (nx_global, ny_global); unallocated: ocean cells
+   integer (int_kind), public :: moc_stream = 1
+   logical (log_kind), public :: moc_requested = .true.
+   public :: init_transports_nml
+ contains
+   subroutine init_transports_nml
+      call pop_transports_nml_init(transports)
+   end subroutine
+   ! the checks of the namelist that need no grid (:312-340); the grid itself is built by init_moc_ts_transport_arrays
+   subroutine init_lat_aux_grid(errorCode)
+      integer (int_kind), intent(out) :: errorCode
+      errorCode = 0
+      if (transports%struct_bytes == 0) call pop_transports_nml_init(transports)
+      if (transports%lat_aux_grid_type < 0 .or. transports%lat_aux_grid_type > 2) errorCode = 1
+   end subroutine
+   subroutine init_moc_ts_transport_arrays(errorCode)
+      integer (int_kind), intent(out) :: errorCode
+      integer (c_int) :: km1
+      if (transports%struct_bytes == 0) call pop_transports_nml_init(transports)
+      if (allocated(REGION_MASK_G)) then
+         errorCode = pop_init_transports(pop_ctx, transports, c_loc(REGION_MASK_G))
+      else
+         errorCode = pop_init_transports(pop_ctx, transports, c_null_ptr)
+      endif
+      if (errorCode /= 0) return
+      errorCode = pop_moc_info(pop_ctx, n_lat_aux_grid, km1, n_moc_comp, n_transport_reg)
+      if (errorCode /= 0) return
+      allocate(lat_aux_edge(n_lat_aux_grid+1), lat_aux_center(n_lat_aux_grid), TAVG_MOC_G(n_lat_aux_grid+1, km1, n_moc_comp, n_transport_reg))
+      call get_grid(lat_aux_edge, lat_aux_center, errorCode)
+      if (errorCode /= 0) return
+      if (moc_requested) errorCode = pop_moc_request(pop_ctx, moc_stream)
+   end subroutine
+   subroutine get_grid(edge, center, errorCode)
+      real (r8), dimension(:), target, intent(out) :: edge, center
+      integer (int_kind), intent(out) :: errorCode
+      integer (c_int) :: n
+      errorCode = pop_lat_aux_grid(pop_ctx, n, c_loc(edge), c_loc(center))
+   end subroutine
+   ! TAVG_MOC_G of the running interval of moc_stream, normalised by its tavg_sum
+   subroutine compute_moc(errorCode)
+      integer (int_kind), intent(out) :: errorCode
+      real (r8), allocatable :: W(:,:,:,:)
+      integer (int_kind) :: n, k, c, m
+      allocate(W(n_transport_reg, n_moc_comp, size(TAVG_MOC_G, 2), n_lat_aux_grid+1))     ! the library's order, region fastest
+      errorCode = pop_moc_get(pop_ctx, 1, 0, W, int(size(W), c_long_long))
+      if (errorCode /= 0) return
+      do m = 1, n_transport_reg
+      do c = 1, n_moc_comp
+      do k = 1, size(TAVG_MOC_G, 2)
+      do n = 1, n_lat_aux_grid+1
+         TAVG_MOC_G(n,k,c,m) = real(W(m,c,k,n), r4)
+      end do
+      end do
+      end do
+      end do
+   end subroutine
+ end module diags_on_lat_aux_grid
 
 !-----------------------------------------------------------------------
 ! source/diagnostics.F90: the global and CFL diagnostics the library forms on the device in an armed step.  The reference decides

@@ -1,0 +1,13 @@
+"""The MOC over several ranks (tests/mr_gpu_moc.py): every value of pop_moc_get and of pop_moc_sums_get is, bit for bit and on every
+rank, that of the single-rank run of the same block decomposition."""
+import os
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_two_ranks_equal_single_rank():
+    from test_gpu_multirank import _run_check
+    _run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_moc.py"), "--case", "gm_submeso", "--steps", "3"], 300)
