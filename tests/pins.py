@@ -9,10 +9,19 @@ NOT a third restatement of the reference's loops but what the routines are suppo
     closed form g * a * bouss-weighted trapezoid sum / DXU for a density linear in the i index;
   * horizontal tracer diffusion (hmix_del2.F90:1040-1100, hmix_del4.F90:988-1059): for a field quadratic in the i index the
     Laplacian on the uniform interior of the lat-lon grid is 2a * (east coefficient), a function of j only, so the
-    biharmonic operator reduces to a three-point formula in j.
+    biharmonic operator reduces to a three-point formula in j;
+  * the 2-D elliptic system of the barotropic mode (barotropic.F90:417-548, POP_SolversMod.F90; reference statement in
+    tests/btrop_ref.py): the solvers' solution against a sparse direct solve of div(HU grad) + centre term assembled from HU, DXU,
+    DYU, KMT, KMU alone (check_btrop_solve_against_direct); adjointness of div and grad, sum div = 0, zcurl grad = 0 through the
+    operator entry points (check_btrop_operator_properties); the EVP preconditioner as the exact inverse of the five-point operator
+    on every solved sub-block, r / centre on the others, and symmetric (check_evp_is_the_local_inverse); the P-CSI eigenvalue
+    interval against a dense eigensolve (check_pcsi_interval_contains_the_spectrum, host only); the area-mean surface pressure over
+    12 steps (check_mean_sea_level_is_conserved).  Not pinned: the tripole fold (see tests/btrop_ref.py).
 
 The same functions run against the CPU oracle (tests/test_pins_oracle.py, no GPU) and against the device library through the
 C ABI (tests/test_gpu_pins.py): `A` is an adapter with get / set / run_phase (see OracleAdapter, GpuAdapter)."""
+import math
+
 import numpy as np
 from scipy.linalg import solve_banded
 
@@ -68,6 +77,43 @@ class OracleAdapter:
     def leapfrog(self):
         return self.o.dim("leapfrogts")
 
+    # ---- the 2-D elliptic system: host arrays (nblocks, ny_block, nx_block) in, host arrays out
+    def blocks(self):
+        """get_block of every block: ib, ie, jb, je (1-based, inclusive), i_glob, j_glob"""
+        from orclib import AsModel
+        am = AsModel(self.o)
+        return [am.get_block(b) for b in am.local_block_ids()]
+
+    def halo(self, a):
+        return self.o.halo(a)
+
+    def solver_run(self, x0, b):
+        """-> (return code, solution, iterations)"""
+        rc, x = self.o.solver_run(x0, b)
+        return rc, x, self.o.L.orc_solver_iterations(self.o.h)
+
+    def preconditioner(self, r):
+        return self.o.preconditioner(r)
+
+    def operator(self, op, k, a, b=None):
+        return self.o.operator(op, k, a, b)
+
+    def btrop_operator(self, x):
+        """the nine-point operator on its own (the device library applies it inside its solver kernels only)"""
+        return self.o.btrop_operator(x)
+
+    def evp_info(self):
+        """the partition and the land flags the implementation holds: (x ranges, y ranges, {(block, jpiece, ipiece): land})"""
+        o = self.o
+        xnb, ynb = o.evp_info(0), o.evp_info(1)
+        xi = [o.evp_info(2, i) for i in range(1, xnb + 2)]
+        yi = [o.evp_info(3, j) for j in range(1, ynb + 2)]
+        land = {(b, j, i): bool(o.evp_info(4, (b * ynb + j) * xnb + i)) for b in range(o.nblocks) for j in range(ynb) for i in range(xnb)}
+        return list(zip(xi[:-1], xi[1:])), list(zip(yi[:-1], yi[1:])), land
+
+    def solver_form(self):
+        return None
+
     def close(self):
         self.o.close()
 
@@ -76,10 +122,10 @@ class GpuAdapter:
     """the device library through the C ABI; vertical grid arrays come from a host-only oracle of the same configuration
     (they are init-time data, compared bit for bit in tests/test_host_grid_parity.py)"""
 
-    def __init__(self, pkg, cfg, grid=None):
+    def __init__(self, pkg, cfg, grid=None, tuning=None):
         from orclib import Oracle
-        self.m = pkg.PopModel(cfg, grid=grid)
-        self.cfg = cfg
+        self.m = pkg.PopModel(cfg, grid=grid, tuning=tuning)
+        self.pkg, self.cfg = pkg, cfg
         self.km, self.nblocks = self.m.km, self.m.nblocks
         o = Oracle(cfg, grid=grid)
         self._vert = {k: o.v1(k).copy() for k in ("dz", "dzw", "dzwr", "bouss", "afac_t", "afac_u", "zt", "zw")}
@@ -118,6 +164,45 @@ class GpuAdapter:
 
     def leapfrog(self):
         return self.m.dim("leapfrogts")
+
+    # ---- the 2-D elliptic system: host arrays in, host arrays out, the work done by the device entry points on named fields
+    def blocks(self):
+        return [self.m.get_block(b) for b in self.m.local_block_ids()]
+
+    def halo(self, a):
+        a = np.array(a, dtype=np.float64, order="C")
+        self.m.halo_update_host(a)
+        return a
+
+    def solver_run(self, x0, b):
+        """POP_SolversRun on RHS and PSURF(newtime) in whatever form the model dispatches to (see solver_form)"""
+        self.m.set("RHS", b)
+        self.m.set("PSURF", x0, 2)
+        try:
+            self.m.solver_run()
+            rc = 0
+        except self.pkg.PopError:
+            rc = 1
+        return rc, self.m.get("PSURF", 2), self.m.solver_diagnostics()[0]
+
+    def preconditioner(self, r):
+        self.m.set("RHS", r)
+        self.m.solver_preconditioner("RHS", "DH")
+        return self.m.get("DH")
+
+    def operator(self, op, k, a, b=None):
+        if op == "grad":
+            self.m.set("PSURF", a)
+            self.m.operator("grad", k, "PSURF", o1="GRADPX", o2="GRADPY")
+            return self.m.get("GRADPX"), self.m.get("GRADPY")
+        self.m.set("UBTROP", a)
+        self.m.set("VBTROP", b)
+        self.m.operator(op, k, "UBTROP", "VBTROP", o1="DH")
+        return self.m.get("DH")
+
+    def solver_form(self):
+        """(solver_path, pcg_persist_used) of the last solve: 1 operation by operation / 2 fused; the resident launch or not"""
+        return self.m.dim("solver_path"), self.m.dim("pcg_persist_used")
 
     def close(self):
         self.m.close()
@@ -1190,3 +1275,331 @@ def check_kpp_hblt_two_layer_pbc(A, kstar, frac, tol=2e-7):
     assert s1 <= 1e-13 * s0, "thickness-weighted non-local source does not sum to zero: %.3e" % (s1 / s0)
     assert wrong > 1e-4 * s0
     return err, s1 / s0
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the 2-D elliptic system of the barotropic mode (barotropic.F90:417-548, POP_SolversMod.F90) against tests/btrop_ref.py
+# ------------------------------------------------------------------------------------------------------------------
+# The cases, shared by the oracle and the device runs: the 48 x 40 "tiny" domain (1204 ocean cells; every dense or sparse reference
+# solve takes well under a second).  name -> (configuration, the EVP sub-blocks the partition rule solves on this bathymetry, the
+# full 8 x 8 ones among them, blocks)
+BTROP_LAYOUTS = {
+    "blocks-12x10": (dict(), 20, 0, 16),                                                                  # 64 sub-blocks of 6 x 5
+    "one-block": (dict(block_size_x=48, block_size_y=40), 5, 5, 1),                                       # cyclic rim reads; 30 sub-blocks of 8 x 8
+    "closed-stepped-24x20": (dict(block_size_x=24, block_size_y=20, ew_boundary=0, stepped_bathymetry=1), 4, 1, 4),
+    "padded-28x24": (dict(block_size_x=28, block_size_y=24), 5, 5, 4),                                    # last block column / row short
+    "stepped-partial-bottom-cells": (dict(stepped_bathymetry=1, partial_bottom_cells=1), 20, 0, 16),      # HU from the partial cells
+}
+BTROP_SOLVERS = {"pcg": 1, "chrongear": 2, "pcsi": 3}
+BTROP_PRECONDITIONERS = {"diagonal": 0, "evp": 1}
+
+
+def btrop_config(layout, solver="pcg", precond="diagonal", **kw):
+    from popcfg import named_config
+    return named_config("tiny", solver_choice=BTROP_SOLVERS[solver], precond_choice=BTROP_PRECONDITIONERS[precond], **dict(BTROP_LAYOUTS[layout][0], **kw))
+
+
+def _btrop_geometry(A):
+    """numbering of the ocean cells (cross-checked against get_block's global indices) and div(HU grad) assembled from grid fields"""
+    import btrop_ref as br
+    kmt, kmu = A.geti("KMT"), A.geti("KMU")
+    blocks = A.blocks()
+    idx, wet, n = br.number_cells(kmt, blocks, A.halo)
+    nghost = br.check_numbering(idx, wet, blocks)
+    assert nghost > 0, "no ghost cell carries an ocean cell's number: the halo update did nothing"
+    G = br.assemble_div_hu_grad(idx, wet, A.get("HU"), A.get("DXU"), A.get("DYU"), kmu)
+    return dict(kmt=kmt, kmu=kmu, blocks=blocks, idx=idx, wet=wet, n=n, G=G, tarea=A.get("TAREA"), dtp=A.scalar("dtp"))
+
+
+def _btrop_system(A):
+    """A_ref of the step just taken: div(HU grad) + the centre term in closed form, asserted symmetric and asserted to carry the
+    centre term the library formed (centerWgt - centerWgtIndep)"""
+    import btrop_ref as br
+    S = _btrop_geometry(A)
+    beta, c2dtp = br.step_parameters(A.leapfrog(), S["dtp"])
+    c = br.centre_term(S["tarea"][S["wet"]], beta, c2dtp, S["dtp"])
+    lib = (A.get("centerWgt") - A.get("centerWgtIndep"))[S["wet"]]
+    assert np.abs(lib - c).max() <= 1e-15 * np.abs(c).max(), "centre term: %.3e of the closed form" % (np.abs(lib - c).max() / np.abs(c).max())
+    S["M"], S["centre"] = br.system_matrix(S["G"], c), c
+    asym = br.asymmetry(S["M"])
+    assert asym <= 1e-15, "the assembled operator is not symmetric: %.3e" % asym
+    return S
+
+
+def _field(S, A, vec):
+    """numbered vector -> halo-updated field"""
+    f = np.zeros(S["wet"].shape)
+    f[S["wet"]] = vec
+    return A.halo(f)
+
+
+def check_btrop_solve_against_direct(A, oracle=None, form=None):
+    """One step (a forward step: beta = 1/2, c2dtp = dtp, centre term -2 TAREA / (dtp^2 grav)), then POP_SolversRun on a random
+    right-hand side of size 1e9 on the ocean cells (solutions of a few 1e3: centimetres of sea level times grav) from a zero first
+    guess, convergence_criterion = 1e-13.  Asserted on either side, with r = b - A_ref x formed by scipy from the matrix of
+    tests/btrop_ref.py and x_direct its sparse direct solve:
+      * return code 0 and the symmetry of A_ref, its centre term equal to the library's (_btrop_system);
+      * ||r||_2 <= sqrt(convergenceCriterion) + 1e-13 ||b||_2: the solver stopped because ITS residual, summed over the same cells,
+        was below that number; an operator that differs from A_ref by a relative delta leaves delta ||b||;
+      * max |x - x_direct| <= ||r||_2 / min |centre term|: -A_ref = -div(HU grad) + |centre|, the first part positive semi-definite
+        (check_pcsi_interval_contains_the_spectrum asserts A_ref negative definite), so ||A_ref^-1||_2 <= 1 / min |centre|;
+      * on the oracle, whose nine-point operator is an entry point of its own: A x = A_ref x to 1e-14 for a random x.
+    With `oracle` = what this check returned for the oracle in the same case (tests/test_gpu_btrop_pins.py): both numbers
+    <= 10 x the oracle's, floored at 1e-13 (the factor covers another summation order in the reductions), and the oracle's iteration
+    count.  `form`: the (solver_path, pcg_persist_used) the case must run in.
+
+    Measured on the oracle, ||r|| / ||b|| and max |x - x_direct| / max |x_direct| (iterations): default 12 x 10 blocks pcg 7.0e-9,
+    1.5e-8 (30); ChronGear 3.9e-9, 7.2e-9 (30); P-CSI 4.8e-14, 3.8e-14 (60); P-CSI + EVP 1.6e-14, 1.2e-14 (60); pcg + EVP 4.3e-9,
+    6.3e-9 (30).  One 48 x 40 block: 1.0e-8, 1.5e-8 / 5.6e-9, 9.1e-9 / 4.9e-14, 5.1e-14 / 4.7e-14, 3.9e-14.  Closed 24 x 20 stepped:
+    pcg 2.6e-10, 5.0e-10 (30); ChronGear 1.8e-7, 3.4e-7 (20); P-CSI 2.4e-16, 3.9e-16.  Padded 28 x 24: 9.1e-9, 1.8e-8 / 5.2e-9,
+    9.5e-9 / 4.8e-14, 4.6e-14.  Stepped with partial bottom cells: pcg 2.7e-7, 5.3e-7 (20); P-CSI 2.1e-16, 4.1e-16.  The nine-point
+    operator itself agrees with A_ref to 2-3e-16 on every layout; max |A_ref - A_ref^T| is exactly 0."""
+    import btrop_ref as br
+    A.step()
+    S = _btrop_system(A)
+    rng = np.random.default_rng(7)
+    bv = 1.0e9 * rng.standard_normal(S["n"])
+    b = _field(S, A, bv)
+    rc, x, its = A.solver_run(np.zeros_like(b), b)
+    assert rc == 0, "the solver did not converge"
+    if form is not None:
+        assert A.solver_form() == form, "the solve ran as %r, the case is about %r" % (A.solver_form(), form)
+    xv = x[S["wet"]]
+    xd = br.direct_solve(S["M"], bv)
+    rnorm, bnorm = br.norm2(bv - S["M"] @ xv), br.norm2(bv)
+    res, err = rnorm / bnorm, float(np.abs(xv - xd).max() / np.abs(xd).max())
+    print("btrop solve: residual %.3e, error against the direct solve %.3e, %d iterations" % (res, err, its))
+    assert rnorm <= np.sqrt(A.scalar("convergenceCriterion")) + 1e-13 * bnorm, "independent residual %.3e of the right-hand side" % res
+    assert np.abs(xv - xd).max() <= rnorm / np.abs(S["centre"]).min() + 1e-13 * np.abs(xd).max(), "differs from the direct solve by %.3e" % err
+    if hasattr(A, "btrop_operator"):         # where the nine-point operator is an entry point of its own: A_ref x directly
+        xr = _field(S, A, rng.standard_normal(S["n"]))
+        got, exp = A.btrop_operator(xr)[S["wet"]], S["M"] @ xr[S["wet"]]
+        assert np.abs(got - exp).max() <= 1e-14 * np.abs(exp).max(), "the nine-point operator differs from div(HU grad) + centre by %.3e" % (np.abs(got - exp).max() / np.abs(exp).max())
+    if oracle is not None:
+        assert its == oracle["iterations"], "%d iterations, the oracle takes %d" % (its, oracle["iterations"])
+        assert res <= max(10.0 * oracle["residual"], 1e-13), "independent residual %.3e, the oracle's is %.3e" % (res, oracle["residual"])
+        assert err <= max(10.0 * oracle["error"], 1e-13), "error against the direct solve %.3e, the oracle's is %.3e" % (err, oracle["error"])
+    return dict(residual=res, error=err, iterations=its)
+
+
+def _fsum(a):
+    """the exactly rounded sum: the summation order of the check itself must not enter a 1e-13 comparison"""
+    return math.fsum(np.asarray(a, dtype=np.float64).reshape(-1).tolist())
+
+
+def check_btrop_operator_properties(A, tol=1e-13):
+    """operators.F90 div / grad / zcurl through the operator entry points only, at level 1 and at a level below the shallowest sill
+    (where there is one: the k <= KMU / KMT masks then differ from the level-1 masks), sums over the owned cells formed exactly:
+      * adjointness: sum_T psi div(u, v) = - sum_U DXU DYU (u grad_x psi + v grad_y psi) for u, v that vanish where k > KMU (div is
+        area-integrated, so the U-point sum carries the area DXU DYU) -- what makes div(HU grad) symmetric;
+      * sum_T div(u, v) = 0 for such a field: every U point feeds two cells with + and two with -;
+      * zcurl(grad psi) = 0 on T cells whose four corner U points are ocean at that level.
+    Each to `tol` = 1e-13 of the LARGEST TERM of the sum (of one term of the curl): a wrong sign or metric is O(1).
+    Measured on the oracle on the five layouts, both levels: adjointness 0 .. 1.4e-15, sum of div 4e-16 .. 7e-15, curl of grad
+    1.4e-16 .. 2.2e-16."""
+    import btrop_ref as br
+    kmt, kmu = A.geti("KMT"), A.geti("KMU")
+    own = br.owned_mask(kmt.shape, A.blocks())
+    dxu, dyu = A.get("DXU"), A.get("DYU")
+    rng = np.random.default_rng(19)
+    ksill = min(A.km, int(kmt[own & (kmt > 0)].min()) + 1)
+    worst = {}
+    for k in (1, ksill):
+        wet_u = kmu >= k
+        psi = A.halo(rng.standard_normal(kmt.shape))
+        u = A.halo(np.where(wet_u & own, rng.standard_normal(kmt.shape), 0.0))
+        v = A.halo(np.where(wet_u & own, rng.standard_normal(kmt.shape), 0.0))
+        div = A.operator("div", k, u, v)
+        gx, gy = A.operator("grad", k, psi)
+        lhs_terms = (psi * div)[own]
+        rhs_terms = (dxu * dyu * (u * gx + v * gy))[own]
+        scale = max(np.abs(lhs_terms).max(), np.abs(rhs_terms).max())
+        assert scale > 0.0 and np.abs(div[own]).max() > 0.0
+        adj = abs(_fsum(lhs_terms) + _fsum(rhs_terms)) / scale
+        dsum = abs(_fsum(div[own])) / np.abs(0.5 * u * dyu).max()
+        curl = A.operator("zcurl", k, gx, gy)
+        wet4 = np.zeros(kmt.shape, dtype=bool)
+        wet4[:, 1:, 1:] = wet_u[:, 1:, 1:] & wet_u[:, :-1, 1:] & wet_u[:, 1:, :-1] & wet_u[:, :-1, :-1]
+        wet4 &= own
+        assert wet4.sum() > 100 and (own & (kmt >= k) & ~wet4).any()
+        czero = np.abs(curl[wet4]).max() / np.abs(gx * dxu).max()
+        # the masks: nothing is formed below the bottom
+        assert np.all(div[own & (kmt < k)] == 0.0) and np.all(gx[own & ~wet_u] == 0.0) and np.all(gy[own & ~wet_u] == 0.0)
+        print("operators at k = %d: adjointness %.2e, sum div %.2e, curl grad %.2e" % (k, adj, dsum, czero))
+        assert adj <= tol, "k = %d: div and grad are not adjoint: %.3e of the largest term" % (k, adj)
+        assert dsum <= tol, "k = %d: sum of div(u, v) is %.3e of the largest term" % (k, dsum)
+        assert czero <= tol, "k = %d: zcurl(grad) is %.3e of a term" % (k, czero)
+        worst[k] = (adj, dsum, czero)
+    if A.cfg.stepped_bathymetry:
+        assert ksill > 1 and ((kmu >= 1) & (kmu < ksill) & own).any(), "no sill above level %d" % ksill
+    return worst
+
+
+def _evp_reference(A, S):
+    """the five-point operator of EVP's preprocessing (centre + four north-east weights, tests/btrop_ref.py) and the sub-blocks with
+    their land flags, from grid fields and the partition rule; the north-east weight is also read off A_ref's own entries and
+    compared with the library's btropWgtNE"""
+    import btrop_ref as br
+    wne = br.north_east_weight(A.get("HU"), A.get("DXU"), A.get("DYU"), S["kmu"])
+    centre = br.five_point_centre(wne, S["kmt"], S["tarea"], S["dtp"])
+    b, j, i = np.nonzero(S["wet"] & (S["kmu"] > 0))
+    in_matrix = np.asarray(S["G"][S["idx"][b, j, i], S["idx"][b, j + 1, i + 1]]).reshape(-1)
+    assert np.abs(in_matrix - wne[b, j, i]).max() <= 1e-15 * np.abs(wne).max()
+    lib = A.get("btropWgtNE")
+    own = br.owned_mask(wne.shape, S["blocks"])
+    assert np.abs(lib - wne)[own].max() <= 1e-15 * np.abs(wne).max(), "btropWgtNE: %.3e" % (np.abs(lib - wne)[own].max() / np.abs(wne).max())
+    return wne, centre, br.evp_subblocks(wne.shape, S["blocks"], wne)
+
+
+def check_evp_is_the_local_inverse(A, min_solved, min_full=0):
+    """The EVP preconditioner (preconditioner_choice = 1; POP_SolversMod.F90:2268-2369, 2434-2696) applied to a random field, before
+    any step (its coefficients are those of the initial centre weight, barotropic.F90:236-238), sub-block by sub-block against
+    tests/btrop_ref.py:
+      * the partition and the land flags (rule of :2992-3040 and :2478-2487 restated there; on the oracle also compared with the
+        tables it holds);
+      * solved sub-blocks: numpy.linalg.solve of the dense five-point operator with a zero rim, to 1e-8 of the largest value of the
+        sub-block -- the reference's own acceptance bound for the inverse of the influence matrix (:2594-2614);
+      * land sub-blocks: r / centre (0 where the centre weight is 0), element by element to 1e-15; ghost cells 0;
+      * at least `min_solved` solved sub-blocks, `min_full` of them full 8 x 8 ones: the counts follow from the bathymetry and the
+        rule alone (20 of 64 with 12 x 10 blocks, 5 of 30 with one 48 x 40 block), and a run that meets only land sub-blocks fails;
+      * symmetry: <y, P x> = <x, P y> to 1e-12 for positive x, y (P is the inverse of an M-matrix times -1: no cancellation).
+    Measured on the oracle, worst solved sub-block: 6 x 5 sub-blocks (12 x 10 blocks) 5e-13, 1.0e-12 with partial bottom cells; full
+    8 x 8 ones 1.8e-10 (one block), 2.5e-10 (closed stepped), 4.2e-10 (padded) -- the marching is ill-conditioned there; the smaller
+    solved sub-blocks of the closed stepped layout 3.7e-11; land sub-blocks 3.8e-16 .. 6.0e-16; symmetry 3e-16 (12 x 10 blocks), 2e-13
+    (one block), 9e-14 (padded), 9.4e-13 (closed stepped).  The 1e-12 holds with a wide margin where the sub-blocks are 6 x 5 (at most
+    7e-15 over six other pairs of vectors); on the three layouts with full 8 x 8 sub-blocks it holds only just: P is the exact inverse
+    to 2e-10 .. 4e-10 there and no more symmetric than that in general -- other pairs of positive vectors give 4e-14 .. 1.3e-12, pairs
+    of mixed sign (standard normal) 1e-13 .. 6e-10.  That is the reference's method (its own acceptance bound is 1e-8), not a
+    defect of either implementation; the vectors were fixed before these figures were taken."""
+    import btrop_ref as br
+    assert A.cfg.preconditioner_choice == 1
+    S = _btrop_geometry(A)
+    wne, centre, subs = _evp_reference(A, S)
+    if hasattr(A, "evp_info"):
+        xr, yr, land = A.evp_info()
+        ny, nx = wne.shape[1:]
+        assert xr == br.evp_partition(nx - 4) and yr == br.evp_partition(ny - 4)
+        for b, j0, j1, i0, i1, ld in subs:
+            assert land[(b, [y[0] for y in yr].index(j0), [x[0] for x in xr].index(i0))] == ld, (b, j0, i0)
+    rng = np.random.default_rng(23)
+    r = rng.standard_normal(wne.shape)
+    pr = A.preconditioner(r)
+    ref = br.evp_apply(centre, wne, subs, r)
+    ghost = np.ones(wne.shape[1:], dtype=bool)
+    ghost[2:-2, 2:-2] = False
+    assert np.all(pr[:, ghost] == 0.0)
+    n_solved = n_full = n_land = 0
+    worst = {"solved": 0.0, "full": 0.0, "land": 0.0}
+    for b, j0, j1, i0, i1, land in subs:
+        got, exp = pr[b, j0:j1, i0:i1], ref[b, j0:j1, i0:i1]
+        if land:
+            n_land += 1
+            e = float((np.abs(got - exp) / np.where(exp != 0.0, np.abs(exp), 1.0)).max())
+            worst["land"] = max(worst["land"], e)
+            assert e <= 1e-15, "land sub-block (%d, %d, %d): differs from r / centre by %.3e" % (b, j0, i0, e)
+        else:
+            full = (j1 - j0, i1 - i0) == (br.EVP_SIZE, br.EVP_SIZE)
+            n_solved += 1
+            n_full += int(full)
+            e = float(np.abs(got - exp).max() / np.abs(exp).max())
+            worst["full" if full else "solved"] = max(worst["full" if full else "solved"], e)
+            assert e <= 1e-8, "sub-block (%d, %d, %d) of %d x %d cells: differs from the dense solve by %.3e" % (b, j0, i0, i1 - i0, j1 - j0, e)
+    assert n_solved >= min_solved and n_full >= min_full and n_land > 0, "sub-blocks solved: %d (%d full), land: %d" % (n_solved, n_full, n_land)
+    x, y = (rng.uniform(0.5, 1.5, wne.shape) for _ in range(2))
+    own = br.owned_mask(wne.shape, S["blocks"])
+    ypx, xpy = _fsum((y * A.preconditioner(x))[own]), _fsum((x * A.preconditioner(y))[own])
+    sym = abs(ypx - xpy) / max(abs(ypx), abs(xpy))
+    print("EVP: %d solved (%d full), %d land; worst %r; symmetry %.2e" % (n_solved, n_full, n_land, worst, sym))
+    assert sym <= 1e-12, "the preconditioner is not symmetric: %.3e" % sym
+    return dict(solved=n_solved, full=n_full, land=n_land, worst=worst, symmetry=sym)
+
+
+def check_pcsi_interval_contains_the_spectrum(A):
+    """Host side only (the device's PcsiMaxEigs / PcsiMinEigs are compared with the oracle's bit for bit in
+    tests/test_host_grid_parity.py and tests/test_gpu_parity.py).  The Chebyshev iteration of P-CSI converges on [PcsiMinEigs,
+    PcsiMaxEigs] and DIVERGES for eigenvalues of P A above PcsiMaxEigs.  Dense generalised eigensolve (scipy.linalg.eigh) of
+    (-A_ref) v = lambda (-P^-1) v with A_ref of the initial centre weight (what PcsiLanczos sees) and P^-1 = the diagonal of A_ref, or,
+    with the EVP preconditioner, the block-diagonal matrix of the local five-point operators of check_evp_is_the_local_inverse;
+    both are asserted symmetric positive definite on the way (eigh's Cholesky factorisation of -P^-1, lambda_min > 0).
+      * asserted: lambda_max <= PcsiMaxEigs, for the initial centre weight (alpha: also that of every leapfrog step) and for the
+        larger one of forward steps (theta), which the solver meets with the same interval;
+      * recorded, not asserted: PcsiMinEigs <= lambda_min.  It holds on NO layout: the Lanczos estimate of the low end is a Ritz value,
+        which lies inside the spectrum, and the reference accepts it once it moves by less than 10 % (:2970-2976).  The price is a
+        slower rate for the lowest modes, not divergence.
+    Measured on the oracle, [PcsiMinEigs, PcsiMaxEigs] against the true [lambda_min, lambda_max] (leapfrog; forward): 12 x 10 blocks,
+    one block and padded, diagonal [0.1775, 2.8614] / [0.1774, 2.6364]; [0.2188, 2.5537]; 12 x 10 blocks EVP [0.1893, 2.8441] /
+    [0.1886, 2.6354]; closed stepped [0.2443, 2.7508] / [0.2419, 2.5589]; partial bottom cells [0.2542, 2.7246] / [0.2508, 2.5421],
+    EVP [0.2585, 2.7482] / [0.2513, 2.5419].  lambda_max / PcsiMaxEigs = 0.92 .. 0.93, lambda_min / PcsiMinEigs = 0.972 .. 0.9999."""
+    import btrop_ref as br
+    from scipy.linalg import eigh
+    assert A.cfg.solver_choice == 3
+    S = _btrop_geometry(A)
+    c0 = br.initial_centre_term(S["tarea"][S["wet"]], S["dtp"])
+    M = br.system_matrix(S["G"], c0)
+    assert br.asymmetry(M) <= 1e-15
+    Ad = -M.toarray()
+    if A.cfg.preconditioner_choice == 1:
+        wne, centre, subs = _evp_reference(A, S)
+        Pinv = -br.evp_inverse_matrix(centre, wne, subs, S["idx"], S["n"])
+        assert np.abs(Pinv - Pinv.T).max() == 0.0
+    else:
+        Pinv = np.diag(np.diag(Ad))
+    lam = eigh(Ad, Pinv, eigvals_only=True)
+    assert np.linalg.eigvalsh(Ad).min() > 0.0, "A_ref is not negative definite"
+    lo, hi = A.scalar("PcsiMinEigs"), A.scalar("PcsiMaxEigs")
+    print("P-CSI interval [%.4f, %.4f], spectrum [%.4f, %.4f]: lambda_max / PcsiMaxEigs = %.4f, lambda_min / PcsiMinEigs = %.4f"
+          % (lo, hi, lam[0], lam[-1], lam[-1] / hi, lam[0] / lo))
+    assert lam[0] > 0.0
+    assert lam[-1] <= hi, "the largest eigenvalue %.6f of P A lies above PcsiMaxEigs = %.6f: the Chebyshev iteration diverges" % (lam[-1], hi)
+    # forward steps: the same interval, the centre term of beta = theta, c2dtp = dtp; the diagonal preconditioner follows it, EVP does not
+    cf = br.centre_term(S["tarea"][S["wet"]], *br.step_parameters(0, S["dtp"]), S["dtp"])
+    Af = -br.system_matrix(S["G"], cf).toarray()
+    lamf = eigh(Af, Pinv if A.cfg.preconditioner_choice == 1 else np.diag(np.diag(Af)), eigvals_only=True)
+    print("forward steps: spectrum [%.4f, %.4f]" % (lamf[0], lamf[-1]))
+    assert lamf[0] > 0.0 and lamf[-1] <= hi, "forward steps: the largest eigenvalue %.6f lies above PcsiMaxEigs = %.6f" % (lamf[-1], hi)
+    return dict(interval=(lo, hi), spectrum=(float(lam[0]), float(lam[-1])), forward=(float(lamf[0]), float(lamf[-1])))
+
+
+def check_mean_sea_level_is_conserved(A, oracle=None, form=None, nsteps=12):
+    """The area mean of the surface pressure, <PSURF> = sum TAREA PSURF / sum TAREA over the owned ocean cells (formed exactly), over
+    12 steps of the wind-driven spin-up.  Summing the rows of A x = b - r: the columns of div(HU grad) sum to zero (sum_T div = 0,
+    check_btrop_operator_properties), so sum (centre term x) = sum b - sum r with the centre term proportional to TAREA: the elliptic
+    system fixes the area mean of the new pressure up to the sum of the solver's residual, and the right-hand side (a divergence,
+    plus the centre term times the old pressure, no fresh-water flux) carries the old mean.  Returned: the largest |<PSURF> - <PSURF>(0)|
+    and max |PSURF|.
+      * P-CSI (it iterates to rounding: at least convergence_check_start = 60 iterations): drift <= 1e-12 max |PSURF|; a conservation
+        error -- a centre term or an area that differs between the right-hand side and the operator -- is O(1e-3);
+      * pcg / ChronGear: the drift is the solver's residual.  |sum r| <= sqrt(n) ||r||_2 < sqrt(n convergenceCriterion) per step, so
+        drift <= nsteps sqrt(n convergenceCriterion) (beta c2dtp dtp grav) / sum TAREA (leapfrog values, the larger ones); with
+        `oracle` (the device runs): <= 10 x the oracle's drift in the same case, as the summation order of the reductions moves the
+        residual the iteration stops at.
+    Measured on the oracle, in pressure units (980.6 = 1 cm of sea level; max |PSURF| = 1.7e3 .. 2.5e3, about 2 cm): P-CSI, diagonal and
+    EVP, 2e-14 .. 2e-13 on every layout (1e-17 .. 1e-16 of max |PSURF|); pcg 9e-6 .. 1.7e-4 (1e-8 .. 2e-7 cm); ChronGear 1.2e-5 .. 1.4e-4,
+    and 1.4e-3 / 5e-4 (diagonal / EVP) with partial bottom cells; the bound for the two is 0.098."""
+    import btrop_ref as br
+    S = _btrop_geometry(A)
+    wet, ta = S["wet"], S["tarea"][S["wet"]]
+    area = _fsum(ta)
+
+    def mean():
+        return _fsum(ta * A.get("PSURF", 1)[wet]) / area
+
+    m0, drift, pmax, forms = mean(), 0.0, 0.0, set()
+    for _ in range(nsteps):
+        A.step()
+        drift = max(drift, abs(mean() - m0))
+        pmax = max(pmax, float(np.abs(A.get("PSURF", 1)[wet]).max()))
+        forms.add(A.solver_form())
+    if form is not None:
+        assert forms == {form}, "the solves ran as %r, the case is about %r" % (forms, form)
+    print("mean sea level: drift %.3e, max |PSURF| %.3e" % (drift, pmax))
+    assert pmax > 100.0, "no sea-level signal"
+    if A.cfg.solver_choice == 3:
+        assert drift <= 1e-12 * pmax, "the mean surface pressure drifts by %.3e (max |PSURF| %.3e)" % (drift, pmax)
+    else:
+        dtp = S["dtp"]
+        bound = nsteps * np.sqrt(S["n"] * A.scalar("convergenceCriterion")) * (br.ALPHA * 2.0 * dtp * dtp * br.GRAV) / area
+        assert drift <= bound, "the mean surface pressure drifts by %.3e, more than the solver's residual allows (%.3e)" % (drift, bound)
+        if oracle is not None:
+            assert drift <= 10.0 * oracle["drift"], "the mean surface pressure drifts by %.3e, the oracle's by %.3e" % (drift, oracle["drift"])
+    return dict(drift=drift, pmax=pmax)
