@@ -16,10 +16,24 @@ NOT a third restatement of the reference's loops but what the routines are suppo
     operator entry points (check_btrop_operator_properties); the EVP preconditioner as the exact inverse of the five-point operator
     on every solved sub-block, r / centre on the others, and symmetric (check_evp_is_the_local_inverse); the P-CSI eigenvalue
     interval against a dense eigensolve (check_pcsi_interval_contains_the_spectrum, host only); the area-mean surface pressure over
-    12 steps (check_mean_sea_level_is_conserved).  Not pinned: the tripole fold (see tests/btrop_ref.py).
+    12 steps (check_mean_sea_level_is_conserved).  Not pinned: the tripole fold (see tests/btrop_ref.py);
+  * the momentum right-hand side term by term (advection.F90:1250-1491 advu, baroclinic.F90:1758-1790, hmix_del2.F90:892-927,
+    hmix_del4.F90:730-857, vertical_mix.F90:935-1010): advection + Coriolis against the ADVECTIVE form built from the 12-point
+    face transports and the column integral of their divergence (check_advu_advective_form: flat, stepped, partial bottom cells with
+    DZU weights, implicit Coriolis with different old and current fields), closed forms for uniform and linearly sheared flows
+    (check_advu_closed_forms), wind stress and bottom drag (check_wind_stress_and_bottom_drag), del2 / del4 friction of a i^2 and its
+    mirror image (check_hdiffu) and of a solid-body rotation, whose truncation figure the metric term DUM sets (check_hdiffu_solid_body);
+  * tracer advection, every scheme (advection.F90:2068-2127, :2243-2301, :2313-2676, :2684-3280): a constant stays constant above the
+    bottom cell for any flow and everywhere for a flow with no transport through any floor, and such a flow conserves the domain
+    sum of a random tracer (check_advt_constant_and_conservation: multi-block, padded, partial bottom cells, passive tracers); the
+    upwind3 face values in i, j and k for either flow direction against Lagrange interpolation from positions
+    (check_upwind3_face_values).  Not pinned: what lw_lim's limiter does to a field beyond constancy, conservation and
+    check_lw_lim_monotone; the tripole fold; hdiffu and the closed forms of advu with partial bottom cells other than through whole
+    cells (the min(DZU) / DZU weights of hmix_del2.F90:852-886 act at the bottom level of a stepped neighbourhood only).
 
-The same functions run against the CPU oracle (tests/test_pins_oracle.py, no GPU) and against the device library through the
-C ABI (tests/test_gpu_pins.py): `A` is an adapter with get / set / run_phase (see OracleAdapter, GpuAdapter)."""
+The same functions run against the CPU oracle (tests/test_pins_oracle.py, tests/test_btrop_pins_oracle.py, tests/test_dyn_pins_oracle.py,
+no GPU) and against the device library through the C ABI (tests/test_gpu_pins.py, tests/test_gpu_btrop_pins.py,
+tests/test_gpu_dyn_pins.py): `A` is an adapter with get / set / run_phase (see OracleAdapter, GpuAdapter)."""
 import math
 
 import numpy as np
@@ -39,7 +53,7 @@ class OracleAdapter:
     def _arr(self, name, tl, n):
         if name == "VDC":
             return self.o.vdc(n)
-        name = {"D4AHF": "D4_AHF"}.get(name, name)
+        name = {"D4AHF": "D4_AHF", "D4AMF": "D4_AMF"}.get(name, name)
         return (self.o.f3 if name in THREE_D else self.o.f2)(name, tl, n)
 
     def get(self, name, tl=1, n=0):
@@ -67,8 +81,8 @@ class OracleAdapter:
         self.o.L.orc_dhdt(self.o.h)
 
     def run_phase(self, phase):
-        if phase in ("vmix", "hmix_tracer", "hmix_momentum"):
-            return                            # the oracle forms them inside tracer_rhs / momentum_rhs
+        if phase in ("vmix", "hmix_tracer", "hmix_momentum", "passive_rhs"):
+            return                            # the oracle forms them inside tracer_rhs (every tracer) / momentum_rhs
         self.o.run_phase(phase)
 
     def correct(self):
@@ -259,20 +273,24 @@ def _thickness(A, kind):
     """level thicknesses per interior column, (km, ncol): dz(k), or with partial bottom cells (grid.F90:926-951) DZT = DZBC at
     the bottom level of a T column, and DZU = the minimum of the four surrounding DZT at a U column -- formed here from KMT and
     DZBC alone, independently of what either implementation stores"""
+    return _cols(_thickness4(A, kind))
+
+
+def _thickness4(A, kind):
+    """_thickness as (nblocks, km, ny, nx), ghost cells included (DZU: all but the last ghost row and column)"""
     km = A.km
     dz = A.vert("dz")[1:km + 1]
     kmt = A.geti("KMT")
     if not A.cfg.partial_bottom_cells:
-        ncol = interior(kmt).size
-        return np.repeat(dz[:, None], ncol, axis=1)
+        return np.broadcast_to(dz[None, :, None, None], (kmt.shape[0], km) + kmt.shape[1:]).copy()
     dzbc = A.get("DZBC")
     k = np.arange(1, km + 1)[None, :, None, None]
     dzt = np.where(k == kmt[:, None], dzbc[:, None], dz[None, :, None, None])          # (nblocks, km, ny, nx), ghosts included
     if kind == "T":
-        return _cols(dzt)
+        return dzt
     dzu = dzt.copy()
     dzu[..., :-1, :-1] = np.minimum(np.minimum(dzt[..., :-1, :-1], dzt[..., :-1, 1:]), np.minimum(dzt[..., 1:, :-1], dzt[..., 1:, 1:]))
-    return _cols(dzu)
+    return dzu
 
 
 def _faces(dzc, coef):
@@ -1603,3 +1621,511 @@ def check_mean_sea_level_is_conserved(A, oracle=None, form=None, nsteps=12):
         if oracle is not None:
             assert drift <= 10.0 * oracle["drift"], "the mean surface pressure drifts by %.3e, the oracle's by %.3e" % (drift, oracle["drift"])
     return dict(drift=drift, pmax=pmax)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The momentum right-hand side term by term (advection.F90 advu, baroclinic.F90 clinic, hmix_del2 / hmix_del4.F90 hdiffu,
+# vertical_mix.F90 vdiffu) and tracer advection (advection.F90 advt_centered / advt_upwind3 / advt_lw_lim): identities and closed
+# forms that neither the reference nor either implementation evaluates in this form.
+# Bounds: these are rounding-level checks.  Every docstring gives the figure the check returns on the oracle (the worst of the cases of
+# tests/test_dyn_pins_oracle.py, rounded up); the oracle's bound is that figure and the device's 10 x the figure; where the figure is
+# below 1e-13, both are the floor 1e-12.
+# ------------------------------------------------------------------------------------------------------------------
+DYN_PIN = dict(const_vvc=0.0, convect_visc=0.0, const_vdc=0.0, convect_diff=0.0, bottom_drag=0.0)    # no vertical mixing of the OLD level, no drag
+GAMMA = 1.0 - 2.0 * (1.0 / 3.0)                 # time_management.F90:437-439: alpha = 1/3, gamma = 1 - 2 alpha
+# configurations of the two test modules (tests/test_dyn_pins_oracle.py, tests/test_gpu_dyn_pins.py), on top of "tiny"
+ONE = dict(block_size_x=48, block_size_y=40)                       # one block
+STEPPED = dict(stepped_bathymetry=1)
+PBC = dict(stepped_bathymetry=1, partial_bottom_cells=1)
+DYN_LAYOUTS = {"one-block": ONE, "blocks-12x10": {}, "padded-28x24": dict(block_size_x=28, block_size_y=24)}
+MOMENTUM = dict(am=0.0, impcor=0, **DYN_PIN)                       # advection + Coriolis alone
+FRICTION = dict(impcor=0, **DYN_PIN)                               # horizontal friction alone
+ADVECTION = dict(ah=0.0, **DYN_PIN)                                # tracer advection alone
+DEL4 = dict(hmix_momentum=4, am=-1.0e19)
+SOLID_BODY_TINY = {2: 1.29e-4, 4: 2.40e-5}                         # check_hdiffu_solid_body on the oracle, tiny: del2, del4
+
+
+def _dyn_tol(A, figure):
+    """the bound for a check whose oracle figure is `figure`: the floor only where the figure is below 1e-13"""
+    if figure < 1.0e-13:
+        return 1.0e-12
+    return (10.0 if isinstance(A, GpuAdapter) else 1.0) * figure
+
+
+def _sh(a, di, dj):
+    """a(i + di, j + dj) (cyclic: callers read the interior only, and no stencil here is wider than the two ghost cells)"""
+    return np.roll(np.roll(a, -di, axis=-1), -dj, axis=-2)
+
+
+def _global_index(A):
+    """global (i, j) of every cell, 1-based, ghost cells included, (nblocks, ny, nx) each: i is periodic, j is 0 outside a closed boundary"""
+    bl = A.blocks()
+    ig = np.stack([np.asarray(b["i_glob"]) for b in bl])[:, None, :]
+    jg = np.stack([np.asarray(b["j_glob"]) for b in bl])[:, :, None]
+    return ig + 0 * jg, jg + 0 * ig
+
+
+def _owned(A, a):
+    """the cells the blocks own (ib .. ie, jb .. je: a short last block of a padded layout owns fewer than its array holds) of a
+    (nblocks, [km,] ny, nx) array, as ([km,] ncells)"""
+    own = np.zeros(a.shape[:1] + a.shape[-2:], dtype=bool)
+    for n, b in enumerate(A.blocks()):
+        own[n, b["jb"] - 1:b["je"], b["ib"] - 1:b["ie"]] = True
+    return a[own] if a.ndim == 3 else np.moveaxis(a, 1, 0)[:, own]
+
+
+def _smooth_flow(A, kbot, column_balanced=False, th=None):
+    """a smooth (u, v) at U points from the GLOBAL indices -- the same number in a ghost cell and in the cell it copies, periodic in
+    i --, different at every level, 0 where k > kbot.  column_balanced: every column's own depth integral sum_k u(k) th(k) is zero
+    (no flow through the floor of any T column, whatever the bathymetry)"""
+    km = A.km
+    ig, jg = _global_index(A)
+    x = (2.0 * np.pi * ig / A.cfg.nx_global)[:, None]
+    y = (np.pi * jg / A.cfg.ny_global)[:, None]
+    lev = np.arange(1, km + 1, dtype=np.float64)[None, :, None, None]
+    wet = lev <= kbot[:, None]
+    if column_balanced:
+        g = np.cos(np.pi * (lev - 0.5) / km) + 0.3 * np.sin(3.0 * lev) + np.zeros(wet.shape)
+        depth = np.where(wet, th, 0.0).sum(axis=1)
+        mean = np.where(wet, g * th, 0.0).sum(axis=1) / np.where(depth > 0.0, depth, 1.0)
+        g = g - A.halo(mean)[:, None]                       # DZU of the last ghost row and column is not formed here: the owners' value
+        u = (6.0 * np.cos(x + 0.4) * np.sin(y) + 3.0 * np.sin(2.0 * x) * np.cos(2.0 * y) + 2.0) * g
+        v = (5.0 * np.sin(x - 0.2) * np.sin(2.0 * y) - 2.5 * np.cos(3.0 * x)) * g
+    else:
+        u = (6.0 * np.cos(x + 0.4) * np.sin(y) + 3.0 * np.sin(2.0 * x) * np.cos(2.0 * y) + 2.0) * np.cos(1.3 * np.pi * lev / km)
+        v = (5.0 * np.sin(x - 0.2) * np.sin(2.0 * y) - 2.5 * np.cos(3.0 * x)) * (1.0 - 0.8 * np.sin(0.9 * np.pi * lev / km))
+    return np.where(wet, u, 0.0), np.where(wet, v, 0.0)
+
+
+def _momentum_setup(A):
+    """leapfrog step parameters, no flow, flat sea surface (DHU = 0), no wind, horizontally uniform density (no pressure force, exactly:
+    check_gradp), no vertical friction of the old level, no drag unless the check is about it"""
+    assert A.cfg.const_vvc == 0.0 and A.cfg.convect_visc == 0.0 and A.cfg.vmix_choice == 1
+    c2dt = _prepare(A)
+    _quiet(A)
+    km = A.km
+    shp = A.get("RHO", 1).shape
+    prof = 1.0 + np.round(40.0 * np.arange(km) / km) * 2.0 ** -10
+    for tl in range(3):
+        A.set("RHO", np.broadcast_to(prof[None, :, None, None], shp).copy(), tl)
+    A.dhdt()
+    return c2dt, shp
+
+
+def _momentum_run(A, c2dt):
+    A.run_phase("hmix_momentum")
+    A.run_phase("momentum_rhs")
+    return _forces(A, c2dt)
+
+
+def _advu_expected(A, u, v, fv, fu):
+    """-(L(u) + u v KYU - v^2 KXU) + f fv, -(L(v) + u v KXU - u^2 KYU) - f fu with L in ADVECTIVE form, on every cell (see
+    check_advu_advective_form), and the share of the ocean U cells that lie above their column's bottom cell"""
+    km = A.km
+    dxu, dyu, uarea = (A.get(n)[:, None] for n in ("DXU", "DYU", "UAREA"))
+    kxu, kyu, fcor = (A.get(n)[:, None] for n in ("KXU", "KYU", "FCOR"))
+    kmu = A.geti("KMU")
+    th = _thickness4(A, "U")
+    ud, vd = u * dyu * th, v * dxu * th                      # transports of the U cells' own faces
+    uuw = 0.25 * (ud + _sh(ud, -1, 0)) + 0.125 * (_sh(ud, 0, -1) + _sh(ud, -1, -1) + _sh(ud, 0, 1) + _sh(ud, -1, 1))
+    uue = 0.25 * (_sh(ud, 1, 0) + ud) + 0.125 * (_sh(ud, 1, -1) + _sh(ud, 0, -1) + _sh(ud, 1, 1) + _sh(ud, 0, 1))
+    vus = 0.25 * (vd + _sh(vd, 0, -1)) + 0.125 * (_sh(vd, -1, 0) + _sh(vd, -1, -1) + _sh(vd, 1, 0) + _sh(vd, 1, -1))
+    vun = 0.25 * (_sh(vd, 0, 1) + vd) + 0.125 * (_sh(vd, -1, 1) + _sh(vd, -1, 0) + _sh(vd, 1, 1) + _sh(vd, 1, 0))
+    wukb = np.cumsum((vun - vus + uue - uuw) / uarea, axis=1)                     # through the bottom face of level k, positive upwards
+    wuk = np.concatenate([np.zeros_like(wukb[:, :1]), wukb[:, :-1]], axis=1)      # through its top face; 0 at the surface (DHU = 0)
+
+    def L(al):
+        up = np.concatenate([al[:, :1], al[:, :-1]], axis=1)
+        dn = np.concatenate([al[:, 1:], al[:, -1:]], axis=1)
+        h = (uue * (_sh(al, 1, 0) - al) + uuw * (al - _sh(al, -1, 0)) + vun * (_sh(al, 0, 1) - al) + vus * (al - _sh(al, 0, -1))) / (2.0 * uarea * th)
+        z = (wuk * (up - al) + wukb * (al - dn)) / (2.0 * th)
+        # level km has no bottom-face term (advection.F90:1461): what its flux form leaves is the transport through the floor times alpha
+        z[:, km - 1] = (wuk * (up - al))[:, km - 1] / (2.0 * th[:, km - 1]) + (al * wukb / th)[:, km - 1]
+        return h + z
+
+    lev = np.arange(1, km + 1)[None, :, None, None]
+    ocean = lev <= kmu[:, None]
+    fx = np.where(ocean, -(L(u) + u * v * kyu - v * v * kxu) + fcor * fv, 0.0)
+    fy = np.where(ocean, -(L(v) + u * v * kxu - u * u * kyu) - fcor * fu, 0.0)
+    share = float(_owned(A, lev < kmu[:, None]).sum()) / float(_owned(A, ocean).sum())
+    return fx, fy, share
+
+
+def check_advu_advective_form(A):
+    """advu (advection.F90:1250-1491) + Coriolis (baroclinic.F90:1758-1790) with nothing else acting (am = 0, uniform density, no vertical
+    friction, no drag, DHU = 0): a smooth level-dependent (u, v) on the CURRENT level, built from the global indices, 0 below KMU.
+    Transports of the U cell's faces from the 12-point averages of u DYU th, v DXU th (:1310-1336; th = dz(k), or DZU with partial
+    bottom cells :1250-1300):
+        div = (VUN - VUS + UUE - UUW) / UAREA,   WUKB(k) = sum_{m <= k} div(m),   WUK(k) = WUKB(k-1), WUK(1) = 0
+        L(a) = [UUE (a_E - a) + UUW (a - a_W) + VUN (a_N - a) + VUS (a - a_S)] / (2 UAREA th) + [WUK (a(k-1) - a) + WUKB (a - a(k+1))] / (2 th)
+        FX = -(L(u) + u v KYU - v^2 KXU) + f v',    FY = -(L(v) + u v KXU - u^2 KYU) - f u'
+    L is the ADVECTIVE form; the reference and the kernels evaluate the flux form, and the two agree only if the vertical velocity
+    the kernel carries down the column is the integral of the divergence of the very transports it advects with.  At k = km the
+    flux form has no bottom face (:1461) and leaves a WUKB(km) / th instead of the last term.  (u', v') = (u, v) with explicit Coriolis,
+    gamma (u, v) + (1 - gamma) (u, v)(old) with impcor (baroclinic.F90:1766-1769, gamma = 1/3) -- the old level then holds a DIFFERENT
+    smooth field, so gamma and 1 - gamma cannot be exchanged.  Asserted on EVERY interior cell (0 on land); the cells above their
+    column's bottom cell are >= 85 % of the ocean U cells.
+    Oracle, largest |difference| / largest |F|: <= 4e-16 -- one 48 x 40 x 16 block flat, stepped, with partial bottom cells (the
+    DZU-weighted identity holds as derived) and with impcor, 1.5e-16 .. 2.5e-16; the 12 x 10 and the padded blocks the same; 60 levels
+    1.5e-16; the 'wide' grid 3.1e-16."""
+    assert A.cfg.am == 0.0 and A.cfg.bottom_drag == 0.0
+    c2dt, shp = _momentum_setup(A)
+    kmu = A.geti("KMU")
+    u, v = _smooth_flow(A, kmu)
+    A.set("UVEL", u, 1)
+    A.set("VVEL", v, 1)
+    fu, fv = u, v
+    if A.cfg.impcor:
+        uo, vo = 1.0 - 1.5 * v, 0.8 * u - 2.0
+        lev = np.arange(1, A.km + 1)[None, :, None, None]
+        uo, vo = np.where(lev <= kmu[:, None], uo, 0.0), np.where(lev <= kmu[:, None], vo, 0.0)
+        A.set("UVEL", uo, 0)
+        A.set("VVEL", vo, 0)
+        fu, fv = GAMMA * u + (1.0 - GAMMA) * uo, GAMMA * v + (1.0 - GAMMA) * vo
+    fx, fy = _momentum_run(A, c2dt)
+    ex, ey, share = _advu_expected(A, u, v, fv, fu)
+    scale = max(np.abs(_owned(A, ex)).max(), np.abs(_owned(A, ey)).max())
+    err = max(np.abs(_owned(A, fx - ex)).max(), np.abs(_owned(A, fy - ey)).max()) / scale
+    print("advu advective form: %.3e of %.3e, %.1f %% of the ocean U cells above the bottom cell" % (err, scale, 100.0 * share))
+    assert share >= 0.85
+    assert (_owned(A, kmu) == 0).any() and (_owned(A, kmu) == A.km).any()
+    assert err <= _dyn_tol(A, 4e-16), "advu + Coriolis differ from the advective form by %.3e" % err
+    return err
+
+
+def check_advu_closed_forms(A):
+    """advu + explicit Coriolis on the open-ocean patch, levels above km (indices within the block), against forms that hold no sum:
+      * uniform (u0, v0): L = 0, only the metric terms and f remain: FX = -(u0 v0 KYU - v0^2 KXU) + f v0, FY = -(u0 v0 KXU - u0^2 KYU) - f u0;
+      * u = u0 + s i, v = 0: L(u) = u s D / UAREA with D = (2 DYU(j) + DYU(j-1) + DYU(j+1)) / 4; the divergence is the same at every level,
+        so a level-independent u feels no vertical advection:  FX = -L(u), FY = u^2 KYU - f u;
+      * v = v0 + t j, u = 0: L(v) = t (m(j+1) + 2 m(j) + m(j-1)) / (4 UAREA), m = v DXU:  FX = v^2 KXU + f v, FY = -L(v).
+    With partial bottom cells the levels above km of a full-depth neighbourhood have whole cells: the same forms.
+    Oracle: 7e-17 / 2e-16 / 3e-17 of the largest |F|."""
+    assert A.cfg.am == 0.0 and A.cfg.bottom_drag == 0.0 and A.cfg.impcor == 0
+    c2dt, shp = _momentum_setup(A)
+    km = A.km
+    ok = _patch(A.geti("KMT"), km)
+    kmu = A.geti("KMU")
+    assert (kmu[ok] == km).all()
+    lev = np.arange(1, km + 1)[None, :, None, None]
+    wet = lev <= kmu[:, None]
+    dxu, dyu, uarea, kxu, kyu, fcor = (A.get(n) for n in ("DXU", "DYU", "UAREA", "KXU", "KYU", "FCOR"))
+    assert np.abs(dyu - np.roll(dyu, 1, axis=2))[ok].max() <= 1e-14 * dyu[ok].max()           # the premise: metrics uniform in i
+    ii = np.arange(shp[-1], dtype=np.float64)[None, None, None, :] + np.zeros(shp)
+    jj = np.arange(shp[-2], dtype=np.float64)[None, None, :, None] + np.zeros(shp)
+    u0, v0, s, t = 7.0, -4.0, 0.125, 0.25
+    D = 0.25 * (2.0 * dyu + np.roll(dyu, 1, axis=1) + np.roll(dyu, -1, axis=1))
+    worst = []
+    for case in ("uniform", "shear-i", "shear-j"):
+        u = {"uniform": u0 + 0.0 * ii, "shear-i": u0 + s * ii, "shear-j": 0.0 * ii}[case]
+        v = {"uniform": v0 + 0.0 * ii, "shear-i": 0.0 * ii, "shear-j": v0 + t * jj}[case]
+        A.set("UVEL", np.where(wet, u, 0.0), 1)
+        A.set("VVEL", np.where(wet, v, 0.0), 1)
+        fx, fy = _momentum_run(A, c2dt)
+        u2, v2 = u[:, 0], v[:, 0]
+        if case == "uniform":
+            ex, ey = -(u2 * v2 * kyu - v2 * v2 * kxu) + fcor * v2, -(u2 * v2 * kxu - u2 * u2 * kyu) - fcor * u2
+        elif case == "shear-i":
+            ex, ey = -(u2 * s * D / uarea), u2 * u2 * kyu - fcor * u2
+        else:
+            m = v2 * dxu
+            ex, ey = v2 * v2 * kxu + fcor * v2, -(t * (np.roll(m, -1, axis=1) + 2.0 * m + np.roll(m, 1, axis=1)) / (4.0 * uarea))
+        scale = max(np.abs(ex)[ok].max(), np.abs(ey)[ok].max())
+        e = max(max(np.abs(fx[:, k] - ex)[ok].max(), np.abs(fy[:, k] - ey)[ok].max()) for k in range(km - 1)) / scale
+        print("advu closed form %s: %.3e of %.3e" % (case, e, scale))
+        assert e <= _dyn_tol(A, 3e-16), "advu of the %s flow differs from the closed form by %.3e" % (case, e)
+        worst.append(e)
+    return max(worst)
+
+
+def check_wind_stress_and_bottom_drag(A):
+    """vdiffu (vertical_mix.F90:935-1010) with no viscosity: the surface level receives SMF / th(1), the bottom level of every U column
+    loses bottom_drag |U_old| U_old / th(KMU) -- the OLD level, with the CURRENT one at rest here --, every other level nothing
+    (th = dz, or DZU with partial bottom cells :946-995).  Oracle: 3e-16 of the largest |F|."""
+    assert A.cfg.am == 0.0 and A.cfg.bottom_drag > 0.0 and A.cfg.impcor == 0
+    c2dt, shp = _momentum_setup(A)
+    km = A.km
+    kmu = A.geti("KMU")
+    ig, jg = _global_index(A)
+    x, y = 2.0 * np.pi * ig / A.cfg.nx_global, np.pi * jg / A.cfg.ny_global
+    smf = [0.8 * np.cos(x - 0.3) * np.sin(y) + 0.3, 0.5 * np.sin(2.0 * x) * np.sin(y) - 0.2]
+    for n in range(2):
+        A.set("SMF", smf[n], 1, n)
+    uo, vo = _smooth_flow(A, kmu)
+    A.set("UVEL", uo, 0)
+    A.set("VVEL", vo, 0)
+    fx, fy = _momentum_run(A, c2dt)
+    th = _thickness4(A, "U")
+    lev = np.arange(1, km + 1)[None, :, None, None]
+    mag = A.cfg.bottom_drag * np.sqrt(uo * uo + vo * vo)
+    worst = 0.0
+    for f, tau, old in ((fx, smf[0], uo), (fy, smf[1], vo)):
+        exp = np.where((lev == 1) & (kmu[:, None] >= 1), tau[:, None] / th, 0.0) - np.where(lev == kmu[:, None], mag * old / th, 0.0)
+        worst = max(worst, np.abs(_owned(A, f - exp)).max() / np.abs(_owned(A, exp)).max())
+        assert np.abs(_owned(A, np.where(lev == kmu[:, None], mag * old / th, 0.0))).max() > 1e-3 * np.abs(_owned(A, exp)).max()      # the drag is visible
+    print("wind stress and bottom drag: %.3e" % worst)
+    assert worst <= _dyn_tol(A, 3e-16), "wind stress / bottom drag differ from the closed form by %.3e" % worst
+    return worst
+
+
+def _five_point(c, a):
+    """c = (centre, north, south, east, west) weights: sum over the five-point stencil of a"""
+    return c[0] * a + c[1] * _sh(a, 0, 1) + c[2] * _sh(a, 0, -1) + c[3] * _sh(a, 1, 0) + c[4] * _sh(a, -1, 0)
+
+
+def check_hdiffu(A):
+    """Horizontal friction with nothing else acting (no flow on the current level, uniform density, explicit Coriolis, no vertical friction):
+    the velocity stands on the OLD level only (the mixing level of a leapfrog step).  u = a i^2, v = 0 (i = index within the block) on
+    the open-ocean patch, where the lat-lon grid's coefficients do not depend on i (DUE = DUW, DMW = -DME, asserted):
+      del2 (hmix_del2.F90:892-927):  HDUK = am (2 a DUE + DUM u),   HDVK = -am (DME 4 a i + (DMC + DMN + DMS) u)
+    and the mirrored field u = 0, v = a i^2:  HDUK = am (DME 4 a i + (DMC + DMN + DMS) v),  HDVK = am (2 a DUE + DUM v).
+      del4 (hmix_del4.F90:730-857): the same closed forms with the d4* coefficients, times D4AMF with lvariable_hmix, are the FIRST
+    Laplacian (d2u, d2v); the second one is the five-point sums of (d2u, d2v) with (DUC + DUM, DUN, DUS, DUE, DUW) and (DMC .. DMW), times am.
+    Oracle, worst of both fields and components, of the largest |HD.K|: del2 9.2e-14, bound 1e-13 (u_E + u_W - 2u cancels i^2 / 2 of its
+    digits); del4 1.9e-12 with 16 and with 60 levels, bound 2e-12; del4 with variable coefficients 1.91e-11, bound 2e-11 (the second
+    Laplacian differences first ones that agree to 1e-3 between neighbouring rows).  None is below 1e-13, so no floor applies: the
+    device's bounds are 1e-12, 2e-11 and 2e-10."""
+    assert A.cfg.impcor == 0 and A.cfg.bottom_drag == 0.0
+    c2dt, shp = _momentum_setup(A)
+    km = A.km
+    del4 = A.cfg.hmix_momentum == 4
+    pre = "d4" if del4 else ""
+    duc, dun, dus, due, duw, dmc, dmn, dms, dme, dmw, dum = (A.get(pre + n) for n in ("DUC", "DUN", "DUS", "DUE", "DUW", "DMC", "DMN", "DMS", "DME", "DMW", "DUM"))
+    ok = _patch(A.geti("KMT"), km)
+    assert np.abs(due - duw)[ok].max() <= 1e-14 * np.abs(due)[ok].max() and np.abs(dmw + dme)[ok].max() <= 1e-14 * np.abs(dme)[ok].max()
+    assert np.abs(dme)[ok].max() > 0.0 and np.abs(dum)[ok].max() > 0.0
+    a = 2.0 ** -6
+    i2 = np.arange(shp[-1], dtype=np.float64)[None, None, :] + np.zeros(shp[:1] + shp[2:])
+    q = a * i2 * i2
+    lap = 2.0 * a * due + dum * q                                  # the diagonal operator on a i^2
+    crs = dme * 4.0 * a * i2 + (dmc + dmn + dms) * q                # the cross operator on a i^2
+    am = A.cfg.am
+    amf = A.get("D4AMF") if (del4 and A.cfg.lvariable_hmix) else 1.0
+    fig = (2e-11 if A.cfg.lvariable_hmix else 2e-12) if del4 else 1e-13
+    worst = 0.0
+    for mirrored in (False, True):
+        d2u, d2v = (crs, lap) if mirrored else (lap, -crs)
+        if del4:
+            d2u, d2v = amf * d2u, amf * d2v
+            cu, cm = (duc + dum, dun, dus, due, duw), (dmc, dmn, dms, dme, dmw)
+            eu, ev = am * (_five_point(cu, d2u) + _five_point(cm, d2v)), am * (_five_point(cu, d2v) - _five_point(cm, d2u))
+        else:
+            eu, ev = am * d2u, am * d2v
+        f3 = q[:, None] + np.zeros(shp)
+        A.set("UVEL", 0.0 * f3 if mirrored else f3, 0)
+        A.set("VVEL", f3 if mirrored else 0.0 * f3, 0)
+        fx, fy = _momentum_run(A, c2dt)
+        scale = max(np.abs(eu)[ok].max(), np.abs(ev)[ok].max())
+        e = max(max(np.abs(fx[:, k] - eu)[ok].max(), np.abs(fy[:, k] - ev)[ok].max()) for k in range(km)) / scale
+        assert min(np.abs(eu)[ok].max(), np.abs(ev)[ok].max()) > 1e-4 * scale                      # both components are there
+        print("hdiffu %s %s: %.3e of %.3e" % ("del4" if del4 else "del2", "v = a i^2" if mirrored else "u = a i^2", e, scale))
+        assert e <= _dyn_tol(A, fig), "hdiffu of a quadratic field differs from the closed form by %.3e" % e
+        worst = max(worst, e)
+    return worst
+
+
+def check_hdiffu_solid_body(A, bound):
+    """Friction of the solid-body rotation u = c cos(ULAT), v = 0 (old level): a rigid rotation is not strained, so the exact
+    operator gives zero; the discrete one leaves a truncation error, |HDUK| <= bound am DUN |u| on the open-ocean patch.  A
+    discretisation figure, not a rounding one: measured on the oracle 1.29e-4 on tiny (dphi = 4.5 degrees) and 2.77e-5 on twice the
+    resolution (96 x 80, dphi = 2.25 degrees): O(dphi^2).  The metric term DUM cancels the five-point sum to two orders of magnitude (a
+    uniform u leaves 1.1e-2), so a missing or doubled term in DUM shows as ~100 x the figure.
+    del4 (hmix_momentum = 4, constant coefficients), of |am| DUN^2 |u|: 2.40e-5 on tiny, 2.46e-6 on 96 x 80; a uniform u leaves 1.9e-3.  `bound` = 2 x the oracle's figure for the grid."""
+    assert A.cfg.impcor == 0 and A.cfg.bottom_drag == 0.0 and A.cfg.hmix_momentum in (2, 4) and not A.cfg.lvariable_hmix
+    c2dt, shp = _momentum_setup(A)
+    km = A.km
+    ok = _patch(A.geti("KMT"), km)
+    u2 = 10.0 * np.cos(A.get("ULAT"))
+    kmu = A.geti("KMU")
+    lev = np.arange(1, km + 1)[None, :, None, None]
+    A.set("UVEL", np.where(lev <= kmu[:, None], u2[:, None], 0.0), 0)
+    fx, fy = _momentum_run(A, c2dt)
+    del4 = A.cfg.hmix_momentum == 4
+    ref = abs(A.cfg.am) * A.get("d4DUN" if del4 else "DUN") ** (2 if del4 else 1) * np.abs(u2)
+    fig = float(max((np.abs(fx[:, k])[ok] / ref[ok]).max() for k in range(km)))
+    print("hdiffu of a solid-body rotation: %.3e of am DUN |u|" % fig)
+    assert fig <= bound, "friction of a solid-body rotation: %.3e of am DUN |u| (del4: |am| DUN^2 |u|), expected <= %.3e" % (fig, bound)
+    return fig
+
+
+# ---- tracer advection ------------------------------------------------------------------------------------------------------
+def varying_grid(cfg):
+    """popcfg.synthetic_grid without steps, its cell widths varying with j as well as with i (the internal grid's are uniform in both
+    index directions, so its upwind3 weights are the same numbers everywhere).  TEST DATA."""
+    from popcfg import synthetic_grid
+    g = synthetic_grid(cfg, stepped=False)
+    row = 1.0 + 0.05 * np.cos(2.0 * np.pi * np.arange(1, cfg.ny_global + 1, dtype=np.float64) / cfg.ny_global)[:, None]
+    g["HTE"], g["HUW"] = np.ascontiguousarray(g["HTE"] * row), np.ascontiguousarray(g["HUW"] * row)
+    return g
+
+
+def _tracer_setup(A, nsteps=2):
+    """leapfrog step parameters, no flow, flat sea surface (DH = 0), no surface fluxes; advection alone: no horizontal or vertical diffusion"""
+    assert A.cfg.ah == 0.0 and A.cfg.const_vdc == 0.0 and A.cfg.convect_diff == 0.0 and A.cfg.vmix_choice == 1
+    c2dt = _prepare(A, nsteps)
+    _quiet(A)
+    kmt = A.geti("KMT")
+    for n in range(A.cfg.nt):
+        A.set("STF", np.zeros(kmt.shape), 1, n)
+    return c2dt, kmt, A.get("TRACER", 1, 0).shape
+
+
+def _tracer_run(A, c2dt):
+    """-> -LTK of every tracer"""
+    A.dhdt()
+    A.run_phase("vmix")
+    A.run_phase("hmix_tracer")
+    A.run_phase("tracer_rhs")
+    if A.cfg.nt > 2:
+        A.run_phase("passive_rhs")
+    return [A.get("TRACER", 2, n) / c2dt for n in range(A.cfg.nt)]
+
+
+def _set_flow(A, u, v):
+    for tl in range(3):
+        A.set("UVEL", u, tl)
+        A.set("VVEL", v, tl)
+
+
+def check_advt_constant_and_conservation(A, nsteps=2):
+    """Tracer advection (tadvect 1 centred, 2 upwind3, 3 lw_lim) with nothing else acting (ah = 0, no vertical diffusion, no fluxes,
+    flat sea surface), a smooth level-dependent flow built from the global indices, every tracer of the configuration:
+      (a) any such flow, tracers constant on the ocean cells and 0 on land: LTK = 0 in every cell ABOVE the bottom cell of its column
+          (the bottom cell carries the flow through the floor, the reference's rule advection.F90:2110-2127).  Weights that do not sum to
+          1 -- any land branch of hupw3 (:2560-2640), the boundary levels of the vertical weights (:444-488, :2399-2445) -- break it;
+      (b) a flow whose depth integral sum_k u th is zero in every U column (so nothing crosses any floor), tracers 1, 3: constant, LTK = 0
+          in EVERY ocean cell; tracers 0, 2: random numbers from the global indices (periodic-consistent, 0 on land):
+          sum TAREA th LTK = 0 over the closed, zonally periodic domain.  Each cell forms its own east and west face value; a
+          mismatch between neighbours breaks the sum.
+    th = dz, or DZT / DZU with partial bottom cells.
+    Oracle (of c max|u| / min DXT, and of sum |TAREA th LTK|): (a) <= 3e-16, (b) <= 4e-16 and <= 5e-18, every scheme, flat, stepped,
+    partial bottom cells, 12 x 10 and padded blocks, four tracers, 16 and 60 levels, the 'wide' grid."""
+    c2dt, kmt, shp = _tracer_setup(A, nsteps)
+    kmu = A.geti("KMU")
+    nt, km = A.cfg.nt, A.km
+    lev = np.arange(1, km + 1)[None, :, None, None]
+    wet = lev <= kmt[:, None]
+    above = lev < kmt[:, None]
+    tht, thu = _thickness4(A, "T"), _thickness4(A, "U")
+    tarea, dxt = A.get("TAREA"), A.get("DXT")
+    const = [2.0, 0.035, 17.0, -3.0][:nt]
+    ig, jg = _global_index(A)
+    G = np.random.default_rng(5).random((nt, km, A.cfg.ny_global + 1, A.cfg.nx_global + 1))
+    worst = {}
+    for part in ("a", "b"):
+        u, v = _smooth_flow(A, kmu, column_balanced=(part == "b"), th=thu)
+        _set_flow(A, u, v)
+        scale = max(np.abs(u).max(), np.abs(v).max()) / _owned(A, dxt).min()
+        field = [np.where(wet, c, 0.0) + np.zeros(shp) for c in const]
+        if part == "b":
+            for n in range(0, nt, 2):
+                field[n] = np.where(wet, 1.0 + G[n][:, jg, ig].transpose(1, 0, 2, 3), 0.0)
+        for n in range(nt):
+            for tl in range(3):
+                A.set("TRACER", field[n], tl, n)
+        out = _tracer_run(A, c2dt)
+        for n in range(nt):
+            if part == "b" and n % 2 == 0:
+                w = _owned(A, np.where(wet, tarea[:, None] * tht * out[n], 0.0))
+                e = abs(_fsum(w)) / _fsum(np.abs(w))
+                assert _fsum(np.abs(w)) > 0.0
+                key = "conservation"
+            else:
+                cells = above if part == "a" else wet
+                e = np.abs(_owned(A, np.where(cells, out[n], 0.0))).max() / (abs(const[n]) * scale)
+                key = "constant-" + part
+            worst[key] = max(worst.get(key, 0.0), float(e))
+            assert e <= _dyn_tol(A, 4e-16), "tracer %d, part (%s), %s: %.3e" % (n, part, key, e)
+        if part == "a":      # the flow does cross the floor somewhere: the rule is needed, and (b) is a different statement
+            assert max(np.abs(_owned(A, np.where(wet & ~above, out[n], 0.0))).max() for n in range(nt)) > 1e-6 * abs(const[0]) * scale
+    print("advt constant / conservation: %r" % worst)
+    assert (_owned(A, kmt) == 0).any()
+    return worst
+
+
+def _lagrange3(x, p, f):
+    """the quadratic through (p[m], f[m]), m = 0, 1, 2, at x"""
+    return (f[0] * (x - p[1]) * (x - p[2]) / ((p[0] - p[1]) * (p[0] - p[2])) + f[1] * (x - p[0]) * (x - p[2]) / ((p[1] - p[0]) * (p[1] - p[2])) +
+            f[2] * (x - p[0]) * (x - p[1]) / ((p[2] - p[0]) * (p[2] - p[1])))
+
+
+def check_upwind3_face_values(A, direction, sign):
+    """tadvect = 2: the value at a face is the quadratic through the three upstream-biased cell centres, evaluated at the face
+    (advection.F90:2313-2676).  The Lagrange weights are formed here from POSITIONS -- cumulative sums of the cell widths DXT, DYT, and
+    zt / zw -- not from TALFXP ... tdelzm.  ah = 0, no vertical diffusion, open-ocean patch, indices within the block.
+      direction 'i' / 'j': a uniform zonal (poloidal) velocity sign * 3 at every U point, T quartic in i (j) and independent of depth.  With F_E,
+        F_W the transports of the cell's faces (comp_flux_vel :2068-2127) and T* the face values -- from (i-1, i, i+1) at the east face
+        of i for F > 0, from (i, i+1, i+2) for F < 0 --, and because the vertical face values of a depth-independent tracer are T itself,
+            -LTK = -[F_E (T*_E - T) - F_W (T*_W - T)] / TAREA        (levels above km; the divergence of F goes into the vertical)
+      direction 'k': u = s i, v = 0: the same divergence D = s HTE_eff / TAREA at every level, w(k) = D sum_{m <= k} dz(m) through the bottom
+        face of level k (upwards for s > 0), T = T(z) cubic in zt: the horizontal face values are T(k), and
+            LTK = T(k) D + (w(k-1) T*(k-1) - w(k) T*(k)) / dz(k),   T*(k) from (k, k+1, k+2) for upward flow, (k-1, k, k+1) for downward
+        flow (:2418-2426), levels 3 .. km-3 (the boundary levels: check_advt_constant_and_conservation).
+    Oracle, of the largest |LTK|: i and j, both signs, <= 9e-15 on the internal grid (16 and 60 levels) and on varying_grid, whose widths vary with i and j;
+    the centred scheme differs from these forms by 5e-4.  k: 2e-14 in either direction (4e-14 with 60 levels); the centred scheme differs by 1.2e-2."""
+    assert A.cfg.tadvect == 2
+    c2dt, kmt, shp = _tracer_setup(A)
+    km = A.km
+    ok = _patch(kmt, km)
+    kmu = A.geti("KMU")
+    lev = np.arange(1, km + 1)[None, :, None, None]
+    wetu = lev <= kmu[:, None]
+    dxu, dyu, tarea = A.get("DXU"), A.get("DYU"), A.get("TAREA")
+    ii = np.arange(shp[-1], dtype=np.float64)[None, None, None, :] + np.zeros(shp)
+    jj = np.arange(shp[-2], dtype=np.float64)[None, None, :, None] + np.zeros(shp)
+    zero = np.zeros(shp)
+    if direction in ("i", "j"):
+        ax = -1 if direction == "i" else -2
+        w = A.get("DXT" if direction == "i" else "DYT")
+        face = np.cumsum(w, axis=ax)                        # position of the east (north) face
+        ctr = face - 0.5 * w
+        t = ((ii if direction == "i" else jj) - 0.5 * shp[ax]) / 8.0
+        T3 = 1.0 + 0.2 * t ** 4 + t ** 3 - 0.5 * t * t + 0.3 * t    # a quartic: on a uniform grid the two stencils differ by a CONSTANT for a cubic
+        u0 = 3.0 * sign
+        _set_flow(A, np.where(wetu, u0, 0.0) + zero if direction == "i" else zero, np.where(wetu, u0, 0.0) + zero if direction == "j" else zero)
+        if direction == "i":
+            F = u0 * 0.5 * (dyu + _sh(dyu, 0, -1))
+            sh = lambda a, d: _sh(a, d, 0)
+        else:
+            F = u0 * 0.5 * (dxu + _sh(dxu, -1, 0))
+            sh = lambda a, d: _sh(a, 0, d)
+        T2 = T3[:, 0]
+        m = (-1, 0, 1) if sign > 0 else (0, 1, 2)
+        star = _lagrange3(face, [sh(ctr, d) for d in m], [sh(T2, d) for d in m])     # at the east (north) face of every cell
+        expect = -(F * (star - T2) - sh(F, -1) * (sh(star, -1) - T2)) / tarea
+        levels = range(km - 1)
+        fig = 9e-15
+    else:
+        s = 0.1 * sign
+        _set_flow(A, np.where(wetu, s * ii, 0.0), zero)
+        assert np.abs(dyu - np.roll(dyu, 1, axis=2))[ok].max() <= 1e-14 * dyu[ok].max()
+        D = s * 0.5 * (dyu + _sh(dyu, 0, -1)) / tarea
+        dz, zt, zw = A.vert("dz"), A.vert("zt"), A.vert("zw")
+        Tz = np.zeros(km + 3)
+        zeta = zt[1:km + 1] / zt[km]
+        Tz[1:km + 1] = 20.0 - 15.0 * zeta + 6.0 * zeta ** 2 - 4.0 * zeta ** 3
+        T3 = Tz[1:km + 1][None, :, None, None] + zero
+        depth = np.cumsum(dz[1:km + 1])
+        expect = np.zeros(shp)
+        for k in range(3, km - 2):                          # 1-based levels 3 .. km-3
+
+            def star(kf):                                   # the value at the bottom face of level kf
+                mm = (kf, kf + 1, kf + 2) if s > 0 else (kf - 1, kf, kf + 1)
+                return _lagrange3(zw[kf], [zt[q] for q in mm], [Tz[q] for q in mm])
+            expect[:, k - 1] = -(Tz[k] * D + (depth[k - 2] * D * star(k - 1) - depth[k - 1] * D * star(k)) / dz[k])
+        levels = range(2, km - 3)
+        fig = 4e-14
+    fields = [T3, 0.5 * T3 + 0.01]
+    for n in range(2):
+        for tl in range(3):
+            A.set("TRACER", fields[n], tl, n)
+    out = _tracer_run(A, c2dt)
+    if expect.ndim == 3:
+        expect = expect[:, None] + zero
+    worst = 0.0
+    for n, fac in ((0, 1.0), (1, 0.5)):                     # the constant part of the second field is advected to nothing in either form
+        got, exp = (np.moveaxis(a[:, list(levels)], 1, 0)[:, ok] for a in (out[n], fac * expect))
+        worst = max(worst, float(np.abs(got - exp).max() / np.abs(exp).max()))
+    print("upwind3 face values, %s, sign %+d: %.3e" % (direction, sign, worst))
+    assert worst <= _dyn_tol(A, fig), "upwind3 face values (%s, sign %+d) differ from Lagrange interpolation by %.3e" % (direction, sign, worst)
+    return worst
