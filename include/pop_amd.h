@@ -158,8 +158,7 @@ typedef struct pop_ctx pop_ctx;
 
 /* ---- tuning: kernel-form and schedule choices.  NONE changes a result: every alternative is tested bitwise equal to the
  *      default (tests/test_gpu_parity.py, test_gpu_land.py, test_gpu_land_schemes.py, test_gpu_passive_matrix.py,
- *      test_gpu_multirank.py; red_tiles regroups the solver's partial sums and is compared to tolerance, see
- *      test_gpu_passive_matrix.py); they exist for measurement and for those
+ *      test_gpu_multirank.py); they exist for measurement and for those
  *      tests.  Resolved ONCE, at pop_create*: the library's size rules, overridden by the caller's pop_tuning (fields left at
  *      POP_TUNING_UNSET keep the rule), overridden by the environment variable POP_<FIELD NAME IN UPPER CASE> (read at create
  *      only; nothing in the step reads the environment).  pop_get_tuning returns what was resolved. ---------------------- */
@@ -168,8 +167,8 @@ typedef struct pop_tuning {
   int struct_bytes;        /* sizeof(pop_tuning) of the caller */
   int land_skip;           /* 0: every workgroup runs (no land elimination at tile granularity) */
   int land_full_steps;     /* steps after set-up / restart / a new state that run every workgroup (default 4) */
-  int xcd_remap;           /* column kernels: workgroup order 0 linear, 1 XCD bands, 2 XCD-strided 2-D tiles */
-  int red_tiles, red_band; /* 2-D reduction / solver kernels: 64x4 tiles | XCD-banded chunk order */
+  int xcd_remap;           /* column kernels: workgroup order 0 linear, 1 XCD bands; any other value is refused at create */
+  int red_band;            /* 2-D reduction / solver kernels: XCD-banded chunk order */
   int lds_order;           /* LDS-tiled stencil kernels: 1 = XCD patch order */
   int momentum_lds;        /* momentum right-hand side: LDS tile rows 8 | 4, 0 = direct-load kernel */
   int tracer_lds;          /* tracer right-hand side (centred advection): LDS tile rows 8 | 4, 0 = direct-load kernel */
@@ -186,12 +185,12 @@ typedef struct pop_tuning {
   int vmixu_inline;        /* 1: implicit vertical mixing of U, V on the launch stream */
   int btrop_inline;        /* 1: barotropic velocity added in the step tail (the reference's order) */
   int kpp_ahead;           /* KPP of the next step beside the barotropic solver */
-  int kpp_col;             /* KPP kernel forms, bit mask: 1 ushear column, 2 buoydiff column, 4 buoydiff LDS, 8 buoydiff + interior fused, 16 the two as one column march */
+  int kpp_col;             /* KPP kernel forms, bit mask: 1 ushear column, 4 buoydiff LDS, 8 buoydiff + interior fused, 16 the two as one column march;
+                            * 2 is unused and accepted: a mask with it selects what the same mask without it selects */
   int kpp_lazy;            /* 0: surface-layer buoyancy difference at every level */
   int kpp_ushear_hint;     /* 0: shear kernel forms every level */
   int kpp_ushear_margin;   /* levels beyond the previous boundary-layer level (default 3; may be negative) */
   int kpp_side_stream;     /* 0: KPP kernels on one stream */
-  int kpp_buoy_waves;      /* column buoydiff: waves per SIMD 1 | 2 */
   int kpp_interior_generic;/* 1: scratch-staged interior kernel even at km = 60 / 62 */
   int kpp_src_full;        /* 1: the tracer kernel reads KPP_SRC at every level */
   int solver_unfused;      /* 1: one kernel per solver operation */
@@ -204,9 +203,9 @@ typedef struct pop_tuning {
   int halo_separate;       /* 1: one message per field instead of one per neighbour */
   int halo_overlap_off;    /* 1: mid-step tracer halo in line instead of beside interior tiles */
   int rccl_overlap;        /* second communicator: 0 none, 1 (default) own stream, 2 ... */
-  int evp_wave;            /* EVP block preconditioner: 0 one thread per sub-block, 1 anti-diagonal wavefronts (8 lanes per sub-block) with the
-                            * operands in LDS, 2 with the operands in registers and the coefficients read from their 2-D fields, 3 (default) = 2 with
-                            * every load of the front end issued up front (unconditional at clamped addresses; the conditions select values) */
+  int evp_wave;            /* EVP block preconditioner: 0 one thread per sub-block; 3 (default) anti-diagonal wavefronts (8 lanes per sub-block), the
+                            * operands in registers, the coefficients read from their 2-D fields and every load of the front end issued up front
+                            * (unconditional at clamped addresses; the conditions select values); any other value is refused at create */
   int fpcg_a_pair;         /* 0: one chunk per workgroup in step A of the fused pcg even on compacted launches */
   int kpp_sparse;          /* 0: KPP boundary-layer kernel streams every level even when the interior kernel formed the convection mask */
   int pbc_generic_thomas;  /* 1: partial bottom cells with the scratch-staged Thomas kernels even at km = 60 / 62 */
@@ -218,7 +217,7 @@ typedef struct pop_tuning {
   int pcg_persist;         /* pcg, ChronGear and P-CSI with the diagonal preconditioner on small 2-D systems (<= 2000 chunks of 256 cells in <= 8 blocks, single rank or the replicated solve):
                             * 1 (the default where it applies) = the whole solve as ONE resident launch, vectors in LDS / registers, workgroups exchanging partials and halo z through
                             * tagged 16-byte memory words (kernels_pcg_persist.hpp); 0 = the two-launch fused iteration; 2 | 4 | 8: measurement only, that many chunks per workgroup */
-  int gm_flux_tile;        /* 0: Gent-McWilliams fluxes cell by cell (every horizontal face flux evaluated in both cells that share it) instead of once per face in 64 x 4 tiles */
+  int gm_flux_tile;        /* 0: Gent-McWilliams fluxes cell by cell (every horizontal face flux evaluated in both cells that share it); default 1 = once per face in 64 x 8 tiles */
   int pcsi_two_step;       /* fused P-CSI (diagonal preconditioner; one rank or blocks spread over ranks; through a tripole fold whose partners are on the rank): 1 = two iterations per pass over the state where no check follows
                             * (k_pcsi_step_x2; the default on large grids), 0 = one launch per iteration */
   int block_sums_relay;    /* ordered block sums of more than 64 x 256 chunk partials (the fused pcg / ChronGear of large grids): 0 = 256 threads, each adding
@@ -226,7 +225,7 @@ typedef struct pop_tuning {
                             * requested at once and the quarters added in turn (k_block_sums_relay: the same additions in the same order); 2 = also below 64 terms (cross-check) */
   int pcsi_evp_fused;      /* fused P-CSI with the EVP preconditioner: 1 = the iteration (dx, x, r = b - A x) and the sub-block solves r' = M^-1 r in ONE
                             * launch (k_pcsi_evp_step; bitwise, but measured slower: its loads are issued by the few waves of the sub-block solve);
-                            * default 0 = two launches per iteration (k_pcsi_step2, k_evp_apply_wave2) */
+                            * default 0 = two launches per iteration (k_pcsi_step2, k_evp_apply_wave3); not with evp_wave = 0 */
   int aniso_side;          /* hmix_momentum = 3: 0 = the friction k_hdiffu_aniso in line before the momentum right-hand side; default 1 = on the
                             * side stream beside the vertical-mixing coefficients (it reads only the mix-time U, V and fixed coefficients) */
   int submeso_all_levels;  /* lsubmesoscale_mixing: 1 = k_submeso_flux marches all km levels; default 0 = every tile stops at the last level that

@@ -544,8 +544,10 @@ k_pcg_b(DevGrid g, SolverArgs a) {
 
 // ---- ChronGear (POP_SolversMod.F90:2040-2210) -----------------------------------------------
 // init: z = r*A0R (EXTZ: z already in a.Z, halo included -- EVP preconditioner); s = z; q = A s; partial (r,z), (s,q)
+// (8 waves per SIMD asked for: left alone the scheduler takes 68 VGPRs for <false>, one wave fewer, whichever way red_cell forms
+// the cell index; the bound keeps the kernel's earlier occupancy and has not been timed -- the kernel runs once per unfused ChronGear solve)
 template <bool EXTZ>
-__global__ void __launch_bounds__(POP_RED_THREADS)
+__global__ void __launch_bounds__(POP_RED_THREADS, 8)
 k_cg_init(DevGrid g, SolverArgs a) {
   const int p2 = red_cell(g), b = blockIdx.y;
   double v[2] = {0.0, 0.0};

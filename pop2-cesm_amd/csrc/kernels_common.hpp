@@ -48,36 +48,6 @@ struct Col {
   long long q2;           // b*n2 + p2
   long long base3;        // b*n3 + p2   (+ (k-1)*n2 for level k)
 };
-// XCD-aware tile order.  The hardware deals workgroups round-robin over the 8 XCDs (workgroup w runs on
-// XCD w % 8, each with its own 4 MB L2; MI355X_MICROARCH.md), so with the natural order the rows j+-1 a
-// stencil re-reads were fetched by workgroups of OTHER XCDs and every L2 fetches them again.
-//   g.xcd_remap == 1 (small grids, everything co-resident): XCD x owns one contiguous band of the
-//     linear tile order.
-//   g.xcd_remap == 2 (large grids): tiles are blockDim.x wide, blockDim.y rows high; XCD x owns the
-//     tile COLUMNS ti = x (mod 8) and walks them row by row, so all XCDs stream the same rows at the
-//     same time (DRAM page locality of the natural order is kept) and the vertical neighbour of a
-//     tile is the tile the same XCD touched a few workgroups earlier.  The ntx % 8 left-over columns
-//     are dealt out tile by tile so every XCD gets the same number of workgroups.
-// The launch grid's x size comes from tile_grid_x(); surplus workgroups idle.
-struct TileId { int ti, tj; bool valid; };
-__host__ __device__ inline int tile_grid_x(int nxb, int nyb, int tw, int th) {
-  const int ntx = (nxb + tw - 1) / tw, nty = (nyb + th - 1) / th;
-  const int full = ntx >> 3, rem = ntx & 7;
-  return 8 * (full * nty + (rem * nty + 7) / 8);
-}
-__device__ __forceinline__ TileId tile_of_block(int nxb, int nyb, int tw, int th) {
-  const int ntx = (nxb + tw - 1) / tw, nty = (nyb + th - 1) / th;
-  const int full = ntx >> 3, rem = ntx & 7;
-  const int x = blockIdx.x & 7, seq = blockIdx.x >> 3;
-  TileId t;
-  if (seq < full * nty) { t.tj = seq / full; t.ti = x + 8 * (seq % full); t.valid = true; }
-  else {
-    const int r = (seq - full * nty) * 8 + x;
-    t.valid = r < rem * nty;
-    t.tj = t.valid ? r / rem : 0; t.ti = t.valid ? 8 * full + r % rem : 0;
-  }
-  return t;
-}
 // Workgroup -> tile of the LDS-tiled stencil kernels (64 x R column tiles, ntx x nty of them per block).
 // lds_order 1: the tiles are numbered patch by patch (patches of 4 x 8 tiles, row-major inside a patch, patches
 // row-major), and runs of 32 consecutive numbers are dealt to the XCDs in turn (workgroup w runs on XCD w % 8, 32
@@ -162,28 +132,22 @@ __device__ __forceinline__ bool land_run(const DevGrid &g, int b, long long p0, 
   const int p1 = (p0 + n < g.n2) ? (int)(p0 + n) : g.n2;
   return ocean_cells(g, b, (int)p0, p1) == 0;
 }
+// XCD-aware tile order.  The hardware deals workgroups round-robin over the 8 XCDs (workgroup w runs on
+// XCD w % 8, each with its own 4 MB L2; MI355X_MICROARCH.md), so with the natural order the rows j+-1 a
+// stencil re-reads were fetched by workgroups of OTHER XCDs and every L2 fetches them again.
+// g.xcd_remap == 1 (small grids, everything co-resident): XCD x owns one contiguous band of the linear tile
+// order.  The launch grid's x size comes from col_grid_x() (a multiple of 8); surplus workgroups idle.
 __host__ __device__ inline int col_grid_x(int n2, int threads) { const int nt = (n2 + threads - 1) / threads; return 8 * ((nt + 7) / 8); }
 // launch grid x for a col_setup kernel with `threads` x 1 workgroups
-__host__ inline int col_grid(const DevGrid &g, int threads) {
-  return g.xcd_remap == 2 ? tile_grid_x(g.nxb, g.nyb, threads, 1) : col_grid_x(g.n2, threads);
-}
+__host__ inline int col_grid(const DevGrid &g, int threads) { return col_grid_x(g.n2, threads); }
 __device__ __forceinline__ bool col_setup(const DevGrid &g, Col &c, bool interior_only) {
   c.b = blockIdx.y;
-  if (g.xcd_remap == 2) {
-    const TileId t = tile_of_block(g.nxb, g.nyb, blockDim.x, blockDim.y);
-    c.i = t.ti * blockDim.x + threadIdx.x;
-    c.j = t.tj * blockDim.y + threadIdx.y;
-    if (!t.valid || c.i >= g.nxb || c.j >= g.nyb) return false;
-    if (land_tile(g, c.b, t.ti * blockDim.x, blockDim.x, t.tj * blockDim.y, blockDim.y)) return false;
-    c.p2 = c.j * g.nxb + c.i;
-  } else {
-    const int tile = g.xcd_remap ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
-    c.p2 = tile * blockDim.x + threadIdx.x;
-    if (c.p2 >= g.n2) return false;
-    if (land_run(g, c.b, (long long)tile * blockDim.x, blockDim.x)) return false;
-    c.i = c.p2 % g.nxb;
-    c.j = c.p2 / g.nxb;
-  }
+  const int tile = g.xcd_remap ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+  c.p2 = tile * blockDim.x + threadIdx.x;
+  if (c.p2 >= g.n2) return false;
+  if (land_run(g, c.b, (long long)tile * blockDim.x, blockDim.x)) return false;
+  c.i = c.p2 % g.nxb;
+  c.j = c.p2 / g.nxb;
   if (interior_only && (c.i + 1 < g.ib || c.i + 1 > blk_ie(g, c.b) || c.j + 1 < g.jb || c.j + 1 > blk_je(g, c.b))) return false;
   c.q2 = (long long)c.b * g.n2 + c.p2;
   c.base3 = (long long)c.b * g.n3 + c.p2;
@@ -214,10 +178,9 @@ __host__ inline unsigned patch_grid_x(const DevGrid &g, int tile) {
   return tile ? (unsigned)(((g.nxb + 63) / 64) * ((g.nyb + tile - 1) / tile)) : (unsigned)((g.n2 + 255) / 256);
 }
 // 2-D reduction kernels (POP_RED_THREADS = 256 threads, one partial per workgroup): cell of this thread,
-// or g.n2 (not a cell) for surplus threads.  Large grids use 64 x 4 tiles in the XCD-strided column order.
+// or g.n2 (not a cell) for surplus threads.
 __host__ inline int red_grid_x(const DevGrid &g) {
   if (g.red_act) return g.red_nact;
-  if (g.red_tiles) return tile_grid_x(g.nxb, g.nyb, 64, 4);
   const int nc = (g.n2 + 255) / 256;
   return g.red_band ? 8 * ((nc + 7) / 8) : nc;
 }
@@ -229,37 +192,24 @@ __device__ __forceinline__ int red_chunk(const DevGrid &g) {
   return g.red_band ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
 }
 __device__ __forceinline__ int red_cell(const DevGrid &g) {
-  if (g.red_tiles) {
-    const TileId t = tile_of_block(g.nxb, g.nyb, 64, 4);
-    const int i = t.ti * 64 + (threadIdx.x & 63), j = t.tj * 4 + (threadIdx.x >> 6);
-    return (t.valid && i < g.nxb && j < g.nyb) ? j * g.nxb + i : g.n2;
-  }
   const long long p2 = (long long)red_chunk(g) * blockDim.x + threadIdx.x;
   return p2 < g.n2 ? (int)p2 : g.n2;
 }
 
-// 2-D reduction / fused solver kernels: does the chunk (or 64 x 4 tile) of this workgroup hold no ocean cell?  Every solver
+// 2-D reduction / fused solver kernels: does the chunk of this workgroup hold no ocean cell?  Every solver
 // vector stays exactly 0 there (right-hand side, weights and the first guess are), so the workgroup only writes its zero
 // partial(s).  Workgroup (0,0) never says so: it publishes the scalars of the iteration.
-// deep: the tile must also lie at least NGHOST cells inside the physical domain (blocks spread over ranks: the cells
+// deep: the chunk must also lie at least NGHOST cells inside the physical domain (blocks spread over ranks: the cells
 // nearer the edge are packed for / advanced on behalf of other ranks by the same kernels, which a skipped workgroup would not do)
 __device__ __forceinline__ bool red_land(const DevGrid &g, bool deep = false) {
   if (!g.skip || (blockIdx.x == 0 && blockIdx.y == 0)) return false;
   if (g.red_act)   // compacted launch: entry w = (x % 8) * (red_nact / 8) + x / 8 of the sorted sequence, which land chunks only pad
     return (int)((blockIdx.x & 7) * (g.red_nact >> 3) + (blockIdx.x >> 3)) >= g.red_cnt[blockIdx.y];
-  int i0, i1, j0, j1;   // inclusive, 0-based
-  if (g.red_tiles) {
-    const TileId t = tile_of_block(g.nxb, g.nyb, 64, 4);
-    if (!t.valid) return false;
-    i0 = t.ti * 64; i1 = i0 + 63; j0 = t.tj * 4; j1 = j0 + 3;
-    if (!land_tile(g, blockIdx.y, i0, 64, j0, 4)) return false;
-  } else {
-    const long long p0 = (long long)red_chunk(g) * 256;
-    if (!land_run(g, blockIdx.y, p0, 256)) return false;
-    const long long p1 = (p0 + 255 < g.n2) ? p0 + 255 : g.n2 - 1;
-    j0 = (int)(p0 / g.nxb); j1 = (int)(p1 / g.nxb);
-    i0 = (j0 == j1) ? (int)(p0 % g.nxb) : 0; i1 = (j0 == j1) ? (int)(p1 % g.nxb) : g.nxb - 1;
-  }
+  const long long p0 = (long long)red_chunk(g) * 256;
+  if (!land_run(g, blockIdx.y, p0, 256)) return false;
+  const long long p1 = (p0 + 255 < g.n2) ? p0 + 255 : g.n2 - 1;
+  const int j0 = (int)(p0 / g.nxb), j1 = (int)(p1 / g.nxb);   // inclusive, 0-based
+  const int i0 = (j0 == j1) ? (int)(p0 % g.nxb) : 0, i1 = (j0 == j1) ? (int)(p1 % g.nxb) : g.nxb - 1;
   if (deep && !(i0 >= g.ib - 1 + NGHOST && i1 <= blk_ie(g, blockIdx.y) - 1 - NGHOST && j0 >= g.jb - 1 + NGHOST && j1 <= blk_je(g, blockIdx.y) - 1 - NGHOST)) return false;
   return true;
 }

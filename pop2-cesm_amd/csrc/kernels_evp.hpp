@@ -19,7 +19,7 @@ struct EvpDev {
   const int4 *meta;               // x: cell index of (1,1) of the sub-block with rim; y: n | m << 8; z: land (diagonal scaling); w: not a single ocean cell
   const double *cc, *ne, *icc, *ine;   // [EVP_LD*EVP_LD][S]
   const double *rinv;             // [EVP_LE*EVP_LE][S]
-  const double *C0, *WNE;         // r3: the 2-D fields cc and ne are copies of (centre weight at set-up, NE weight), for k_evp_apply_wave2
+  const double *C0, *WNE;         // the 2-D fields cc and ne are copies of (centre weight at set-up, NE weight), for k_evp_apply_wave3
 };
 
 __global__ void __launch_bounds__(POP_EVP_THREADS)
@@ -63,212 +63,29 @@ k_evp_apply(EvpDev e, int nxb, const double *__restrict__ X, double *__restrict_
   for (int c = 2; c <= m - 1; ++c) for (int a = 2; a <= n - 1; ++a) PX[cell(a, c)] = y(a, c);
 }
 
-
-// ---- the same solve with the marching sweeps as anti-diagonal wavefronts (round 3) ------------------------------------------
+// ---- the same solve with the marching sweeps as anti-diagonal wavefronts ----------------------------------------------------
 // y(i+1,j+1) is formed from y(i,j), y(i+1,j-1), y(i-1,j+1) (all on the anti-diagonal i + j) and y(i-1,j-1) (two diagonals
 // back): every cell of an anti-diagonal can be formed at once, 2 (n - 2) - 1 <= 15 steps per sweep instead of (n - 2)^2 <= 64.
-// Eight lanes own a sub-block (one per cell of the diagonal; a diagonal holds at most eight), eight sub-blocks share a
-// wave; the coefficients (cc, ne, 1/ne), X and y of the sub-block sit in LDS, loaded with the eight sub-blocks side by side
-// (64-byte segments), and the 13 x 13 correction between the sweeps is spread over the lanes row by row, each row summed in
-// the reference's order.  Every value is formed by the expression of k_evp_apply with the same operands: bitwise equal
-// (tests/test_gpu_parity.py).  A workgroup is exactly one wavefront; its barriers only order the LDS traffic.
-#define POP_EVP_SB 8
-constexpr int EVP_CELLS = EVP_LD * EVP_LD, EVP_PAD = EVP_CELLS + 5;
-__global__ void __launch_bounds__(64)
-k_evp_apply_wave(EvpDev e, int nxb, const double *__restrict__ X, double *__restrict__ PX) {
-  __shared__ double ys[POP_EVP_SB][EVP_PAD], xs[POP_EVP_SB][EVP_PAD];
-  __shared__ double ccs[POP_EVP_SB][EVP_PAD], nes[POP_EVP_SB][EVP_PAD], ins[POP_EVP_SB][EVP_PAD];
-  __shared__ double rs[POP_EVP_SB][EVP_LE + 1];
-  const int t = threadIdx.x, w = t >> 3, l = t & 7;
-  const long long s0 = (long long)blockIdx.x * POP_EVP_SB, s = s0 + w;
-  const bool live = s < e.S;
-  int4 mt = make_int4(0, 3 | (3 << 8), 1, 0);
-  if (live) mt = e.meta[s];
-  const int n = mt.y & 255, m = mt.y >> 8;
-  const bool solve = live && !mt.z;
-  auto cell = [&](int a, int c) { return (long long)mt.x + (long long)(c - 1) * nxb + (a - 1); };
-  auto at = [](int a, int c) { return (a - 1) + EVP_LD * (c - 1); };
-  // coefficients: cell q of the eight sub-blocks of this workgroup lies at q * S + s0 .. + 7: lane (q8, sb) = (t >> 3, t & 7)
-  {
-    const int sb = t & 7, q8 = t >> 3;
-    const bool ok = s0 + sb < e.S;
-    for (int q = q8; q < EVP_CELLS; q += 8) {
-      double c0 = 0.0, c1 = 0.0, c2 = 0.0;
-      if (ok) { const long long o = (long long)q * e.S + s0 + sb; c0 = e.cc[o]; c1 = e.ne[o]; c2 = e.ine[o]; }
-      ccs[sb][q] = c0; nes[sb][q] = c1; ins[sb][q] = c2; ys[sb][q] = 0.0;
-    }
-  }
-  // X of the interior, row by row (lane = column); sub-blocks with land are scaled by the diagonal at once (:2344-2348)
-  const int a0 = 2 + l;
-  for (int c = 2; c <= EVP_LD - 1; ++c) {
-    if (live && c <= m - 1 && a0 <= n - 1) {
-      const double x = X[cell(a0, c)];
-      xs[w][at(a0, c)] = x;
-      if (mt.z) PX[cell(a0, c)] = x * e.icc[(long long)at(a0, c) * e.S + s];
-    }
-  }
-  // rows of the correction this lane sums (row index jj = 1 .. n + m - 5; see below), requested before the first sweep
-  const int nm = n + m - 5;
-  double rv0[EVP_LE], rv1[EVP_LE];
-  const int row0 = 1 + l, row1 = 9 + l;
-#pragma unroll
-  for (int k = 1; k <= EVP_LE; ++k) {
-    rv0[k - 1] = (solve && row0 <= nm && k <= nm) ? e.rinv[(long long)((k - 1) + EVP_LE * (row0 - 1)) * e.S + s] : 0.0;
-    rv1[k - 1] = (solve && row1 <= nm && k <= nm) ? e.rinv[(long long)((k - 1) + EVP_LE * (row1 - 1)) * e.S + s] : 0.0;
-  }
-  __syncthreads();
-  auto sweep = [&](int imax, int jmax) {
-    for (int d = 4; d <= 2 * (EVP_LD - 1); ++d) {
-      const int ilo = (d - jmax > 2) ? d - jmax : 2, ihi = (d - 2 < imax) ? d - 2 : imax;
-      const int i = ilo + l, j = d - i;
-      const bool on = solve && d <= imax + jmax && i <= ihi;
-      double v = 0.0;
-      if (on)
-        v = (xs[w][at(i, j)] - ccs[w][at(i, j)] * ys[w][at(i, j)] - nes[w][at(i, j - 1)] * ys[w][at(i + 1, j - 1)] -
-             nes[w][at(i - 1, j)] * ys[w][at(i - 1, j + 1)] - nes[w][at(i - 1, j - 1)] * ys[w][at(i - 1, j - 1)]) * ins[w][at(i, j)];
-      if (on) ys[w][at(i + 1, j + 1)] = v;
-      __syncthreads();
-    }
-  };
-  sweep(n - 1, m - 1);
-  // what reached the north / east rim (:2667-2680)
-  for (int k = 1 + l; k <= EVP_LE; k += 8)
-    if (solve && k <= nm) rs[w][k] = (k <= n - 2) ? ys[w][at(k + 2, m)] : ys[w][at(n, m - (k - (n - 2)))];
-  __syncthreads();
-  // corrected values on the west column (rows jj = 1 .. m-2 -> y(2, m-jj)) and the south row (jj = m-2+ii -> y(ii+2, 2))
-  auto target = [&](int jj) { return (jj <= m - 2) ? at(2, m - jj) : at(jj - (m - 2) + 2, 2); };
-  if (solve && row0 <= nm) {
-    double acc = ys[w][target(row0)];
-#pragma unroll
-    for (int k = 1; k <= EVP_LE; ++k) if (k <= nm) acc = acc + rv0[k - 1] * rs[w][k];
-    ys[w][target(row0)] = acc;
-  }
-  if (solve && row1 <= nm) {
-    double acc = ys[w][target(row1)];
-#pragma unroll
-    for (int k = 1; k <= EVP_LE; ++k) if (k <= nm) acc = acc + rv1[k - 1] * rs[w][k];
-    ys[w][target(row1)] = acc;
-  }
-  __syncthreads();
-  sweep(n - 2, m - 2);
-  for (int c = 2; c <= EVP_LD - 1; ++c)
-    if (solve && c <= m - 1 && a0 <= n - 1) PX[cell(a0, c)] = ys[w][at(a0, c)];
-}
-
-
-// ---- wavefront form, second version (r3): more waves per CU, fewer bytes ---------------------------------------------------
-// k_evp_apply_wave keeps five coefficient / operand arrays of the eight sub-blocks in LDS (34.6 KB): four one-wave workgroups per
-// CU, i.e. one wave per SIMD on a kernel that is a chain of ~80 dependent LDS steps -- 352 us per application at tx0.1v3 for
-// ~130 us of bytes.  Here a lane owns one COLUMN of the marching index (i = 2 + lane) and meets the anti-diagonal d = i + j at
+// Eight lanes own a sub-block, eight sub-blocks share a wave; a workgroup is exactly one wavefront, its barriers only order
+// the LDS traffic.  A lane owns one COLUMN of the marching index (i = 2 + lane) and meets the anti-diagonal d = i + j at
 // step d: what it needs at that step -- cc(i,j), X(i,j), 1/ne(i,j) -- depends on the lane only through d, so it sits in
-// registers indexed by the step (15 slots each), loaded up front; only y and ne (read at three neighbours) stay in LDS (14 KB: eleven
-// workgroups per CU).  cc and ne are read from the 2-D fields they were copied from (C0, WNE: 64 cells + rim through the cache
-// instead of 2 x 100 duplicated words per sub-block) and 1/ne is formed here (IEEE division: the bits of the host's table), so a
-// sub-block costs 169 (correction matrix) + ~130 coefficient words instead of 469.  Same expressions, same operands: bitwise
-// k_evp_apply (tests/test_gpu_parity.py).
-constexpr int EVP_STEPS = 2 * (EVP_LD - 1) - 3;   // anti-diagonals d = 4 .. 2 (EVP_LD - 1)
-__global__ void __launch_bounds__(64)
-k_evp_apply_wave2(EvpDev e, int nxb, const double *__restrict__ X, double *__restrict__ PX) {
-  __shared__ double ys[POP_EVP_SB][EVP_PAD], nes[POP_EVP_SB][EVP_PAD];
-  __shared__ double rs[POP_EVP_SB][EVP_LE + 1];
-  const int t = threadIdx.x, w = t >> 3, l = t & 7;
-  const long long s = (long long)blockIdx.x * POP_EVP_SB + w;
-  const bool live = s < e.S;
-  int4 mt = make_int4(0, 3 | (3 << 8), 1, 0);
-  if (live) mt = e.meta[s];
-  const int n = mt.y & 255, m = mt.y >> 8;
-  const bool solve = live && !mt.z;
-  auto cell = [&](int a, int c) { return (long long)mt.x + (long long)(c - 1) * nxb + (a - 1); };
-  auto at = [](int a, int c) { return (a - 1) + EVP_LD * (c - 1); };
-  // ne of the sub-block with its rim (rows c = 1 .. m; lane = column, lanes 0 and 1 also take columns 9 and 10), y = 0
-  for (int c = 1; c <= EVP_LD; ++c) {
-    const int a1 = 1 + l, a2 = 9 + l;
-    double v1 = 0.0, v2 = 0.0;
-    if (live && c <= m && a1 <= n) v1 = e.WNE[cell(a1, c)];
-    if (live && c <= m && l < 2 && a2 <= n) v2 = e.WNE[cell(a2, c)];
-    nes[w][at(a1, c)] = v1; ys[w][at(a1, c)] = 0.0;
-    if (l < 2) { nes[w][at(a2, c)] = v2; ys[w][at(a2, c)] = 0.0; }
-  }
-  // sub-blocks with land: diagonal scaling (:2344-2348), row by row
-  const int a0 = 2 + l;
-  if (live && mt.z) {
-    for (int c = 2; c <= EVP_LD - 1; ++c)
-      if (c <= m - 1 && a0 <= n - 1) {
-        const double cc = e.C0[cell(a0, c)];
-        PX[cell(a0, c)] = X[cell(a0, c)] * ((cc != 0.0) ? 1.0 / cc : 0.0);
-      }
-  }
-  // the operands this lane (column i = 2 + l) meets at step d = i + j: X(i,j), cc(i,j) in registers indexed by the step
-  const int i = 2 + l;
-  double xx[EVP_STEPS], cs[EVP_STEPS];
-#pragma unroll
-  for (int q = 0; q < EVP_STEPS; ++q) {
-    const int j = q + 4 - i;
-    const bool ok = solve && j >= 2 && j <= m - 1 && i <= n - 1;
-    xx[q] = ok ? X[cell(i, j)] : 0.0;
-    cs[q] = ok ? e.C0[cell(i, j)] : 0.0;
-  }
-  const int nm = n + m - 5;
-  double rv0[EVP_LE], rv1[EVP_LE];
-  const int row0 = 1 + l, row1 = 9 + l;
-#pragma unroll
-  for (int k = 1; k <= EVP_LE; ++k) {
-    rv0[k - 1] = (solve && row0 <= nm && k <= nm) ? e.rinv[(long long)((k - 1) + EVP_LE * (row0 - 1)) * e.S + s] : 0.0;
-    rv1[k - 1] = (solve && row1 <= nm && k <= nm) ? e.rinv[(long long)((k - 1) + EVP_LE * (row1 - 1)) * e.S + s] : 0.0;
-  }
-  __syncthreads();
-  double in[EVP_STEPS];         // 1 / ne(i, j) of the step (host: ine = 1 / ne where ne != 0, else 0)
-#pragma unroll
-  for (int q = 0; q < EVP_STEPS; ++q) {
-    const int j = q + 4 - i;
-    const bool ok = solve && j >= 2 && j <= m - 1 && i <= n - 1;
-    const double nv = ok ? nes[w][at(i, j)] : 0.0;
-    in[q] = (nv != 0.0) ? 1.0 / nv : 0.0;
-  }
-  auto sweep = [&](int imax, int jmax) {
-#pragma unroll
-    for (int q = 0; q < EVP_STEPS; ++q) {
-      const int j = q + 4 - i;
-      const bool on = solve && j >= 2 && j <= jmax && i <= imax;
-      double v = 0.0;
-      if (on)
-        v = (xx[q] - cs[q] * ys[w][at(i, j)] - nes[w][at(i, j - 1)] * ys[w][at(i + 1, j - 1)] -
-             nes[w][at(i - 1, j)] * ys[w][at(i - 1, j + 1)] - nes[w][at(i - 1, j - 1)] * ys[w][at(i - 1, j - 1)]) * in[q];
-      if (on) ys[w][at(i + 1, j + 1)] = v;
-      __syncthreads();
-    }
-  };
-  sweep(n - 1, m - 1);
-  for (int k = 1 + l; k <= EVP_LE; k += 8)
-    if (solve && k <= nm) rs[w][k] = (k <= n - 2) ? ys[w][at(k + 2, m)] : ys[w][at(n, m - (k - (n - 2)))];
-  __syncthreads();
-  auto target = [&](int jj) { return (jj <= m - 2) ? at(2, m - jj) : at(jj - (m - 2) + 2, 2); };
-  if (solve && row0 <= nm) {
-    double acc = ys[w][target(row0)];
-#pragma unroll
-    for (int k = 1; k <= EVP_LE; ++k) if (k <= nm) acc = acc + rv0[k - 1] * rs[w][k];
-    ys[w][target(row0)] = acc;
-  }
-  if (solve && row1 <= nm) {
-    double acc = ys[w][target(row1)];
-#pragma unroll
-    for (int k = 1; k <= EVP_LE; ++k) if (k <= nm) acc = acc + rv1[k - 1] * rs[w][k];
-    ys[w][target(row1)] = acc;
-  }
-  __syncthreads();
-  sweep(n - 2, m - 2);
-  for (int c = 2; c <= EVP_LD - 1; ++c)
-    if (solve && c <= m - 1 && a0 <= n - 1) PX[cell(a0, c)] = ys[w][at(a0, c)];
-}
-
-// ---- wavefront form, third version (r4): the same solve with every load of the front end issued up front ------------------------------------
-// k_evp_apply_wave2 requests its operands behind their conditions: one row of ne, one step's X and cc, one entry of the correction matrix
-// at a time, each `if (...) v = load` a branch with its own s_waitcnt -- ~50 dependent round trips before the first marching step
-// (90 s_waitcnt vmcnt in the ISA; gx1v7: 11.6 us per application for ~3 us of marching).  Here every load is unconditional at a clamped
-// address and the conditions select values (the rewriting of the solver kernels' rim paths, 3d); X and cc of the interior are loaded once for
-// both uses (the solve and the diagonal scaling of sub-blocks with land).  Same expressions on the same operands: bitwise.
+// registers indexed by the step (15 slots each); only y and ne (read at three neighbours) are in LDS (14 KB: eleven
+// workgroups per CU; with the coefficients and X in LDS as well it was 34.6 KB, one wave per SIMD on a chain of ~80 dependent
+// LDS steps).  cc and ne are read from the 2-D fields they were copied from (C0, WNE: 64 cells + rim through the cache instead
+// of 2 x 100 duplicated words per sub-block) and 1/ne is formed here (IEEE division: the bits of the host's table), so a
+// sub-block costs 169 (correction matrix) + ~130 coefficient words instead of 469.  The 13 x 13 correction between the sweeps
+// is spread over the lanes row by row, each row summed in the reference's order.
+// Every load of the front end is issued up front, unconditional at a clamped address, and the conditions select values (the
+// rewriting of the solver kernels' rim paths): requested behind their conditions -- one row of ne, one step's X and cc, one
+// entry of the correction matrix at a time, each a branch with its own wait -- they were ~50 dependent round trips before the
+// first marching step (gx1v7: 11.6 us per application for ~3 us of marching).  X and cc of the interior are loaded once for
+// both uses (the solve and the diagonal scaling of sub-blocks with land).
+// Every value is formed by the expression of k_evp_apply with the same operands: bitwise equal (tests/test_gpu_parity.py).
 // RESIDUAL: X is a residual of the solvers -- exactly zero on land, so a sub-block without a single ocean cell (meta.w) yields zeros (x * icc
 // of the diagonal scaling): its loads are not issued, and a wave whose eight sub-blocks are all of that kind stores its zeros and leaves.
+#define POP_EVP_SB 8
+constexpr int EVP_CELLS = EVP_LD * EVP_LD, EVP_PAD = EVP_CELLS + 5;
+constexpr int EVP_STEPS = 2 * (EVP_LD - 1) - 3;   // anti-diagonals d = 4 .. 2 (EVP_LD - 1)
 template <bool RESIDUAL>
 __global__ void __launch_bounds__(64)
 k_evp_apply_wave3(EvpDev e, int nxb, const double *__restrict__ X, double *__restrict__ PX) {
@@ -397,12 +214,13 @@ k_evp_apply_wave3(EvpDev e, int nxb, const double *__restrict__ X, double *__res
 }
 
 // ---- P-CSI iteration + sub-block solves in ONE launch (round 4) ---------------------------------------------------------------------------
-// With the EVP preconditioner a P-CSI iteration was two launches: k_pcsi_step2 (dx, x, r = b - A x; the residual itself to memory) and
-// k_evp_apply_wave2 (r' = M^-1 r, sub-block by sub-block).  Here the wave that solves eight sub-blocks first forms what the step kernel forms
+// With the EVP preconditioner a P-CSI iteration is two launches: k_pcsi_step2 (dx, x, r = b - A x; the residual itself to memory) and
+// k_evp_apply_wave3<true> (r' = M^-1 r, sub-block by sub-block).  Here the wave that solves eight sub-blocks first forms what the step kernel forms
 // for them: x_new = x + (omega r' + (csy omega - 1) dx) on every sub-block WITH its rim (100 cells; a rim cell that is a ghost cell of the block
 // is formed at its source cell, the fill value where there is none) into the LDS array the marching sweeps use afterwards, then r = b - A x_new on
-// the 8 x 8 interior -- lane = column, so r(i, j) lands in the register slot of the anti-diagonal step that consumes it -- and then the solve of
-// k_evp_apply_wave2.  The expressions and their order are those of k_pcsi_step2 / k_evp_apply_wave2: bitwise the two launches
+// the 8 x 8 interior -- lane = column, so r(i, j) lands in the register slot of the anti-diagonal step that consumes it -- and then the wavefront
+// solve, here with its operands requested row by row behind their conditions (not up front at clamped addresses as in k_evp_apply_wave3).
+// The expressions and their order are those of k_pcsi_step2 / k_evp_apply_wave3: bitwise the two launches
 // (tests/test_gpu_parity.py).  r' ping-pongs like x and dx (a neighbouring sub-block still reads the old one).  RAW: the residual itself also
 // goes to `raw`, from which k_pcsi_rr_chunks forms the chunk partials of (r, r) for the check.
 // MEASURED SLOWER than the two launches (gx1v7 28.9 against 22.7 us per iteration, tx0.1v3 515 against 283): the step's loads -- issued by
@@ -451,7 +269,7 @@ k_pcsi_evp_step(EvpDev e, DevGrid g, PcsiArgs a, double *__restrict__ raw) {
     advance(1 + l, c);
     if (l < 2) advance(9 + l, c);
   }
-  // the correction rows of this lane (as in k_evp_apply_wave2), requested before the first barrier
+  // the correction rows of this lane (the rows k_evp_apply_wave3 takes), requested before the first barrier
   const int i = 2 + l;
   const int nm = n + m - 5;
   double rv0[EVP_LE], rv1[EVP_LE];
@@ -484,7 +302,7 @@ k_pcsi_evp_step(EvpDev e, DevGrid g, PcsiArgs a, double *__restrict__ raw) {
     xx[q] = solve ? r : 0.0; cs[q] = solve ? c0 : 0.0;
   }
   __syncthreads();
-  // ---- the solve of k_evp_apply_wave2 from here on (y = 0 first: the array held x_new)
+  // ---- the wavefront solve (the expressions of k_evp_apply_wave3) from here on (y = 0 first: the array held x_new)
   for (int c = 1; c <= EVP_LD; ++c) {
     ys[w][at(1 + l, c)] = 0.0;
     if (l < 2) ys[w][at(9 + l, c)] = 0.0;

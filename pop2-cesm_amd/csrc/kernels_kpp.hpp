@@ -164,68 +164,16 @@ k_kpp_buoydiff(DevGrid g, KppDev kp, const double *__restrict__ T, const double 
   if (k == km) DBLOC[o] = 0.0;
 }
 
-// ---- buoydiff, column form for bandwidth-bound grids ------------------------------------------
-// The 3-D-parallel kernel re-reads the top kref levels of T and S for every level (66 GB through the
-// fabric at tx0.1v3 for 17 GB of algorithmic traffic) and repeats the pressure-independent half of
-// every equation-of-state evaluation.  Here one thread owns a column: the clamped T, 1000*S and the
-// pressure-independent second term of the denominator (mwjf_prep2) of the top KR levels sit in registers
-// (KR >= max kref, checked by the host), every field is read once, and only the pressure-dependent
-// polynomials are re-evaluated.  Same operations in the same order as k_kpp_buoydiff.
-template <int KR, int WAVES>
-__global__ void __launch_bounds__(POP_COL_THREADS, WAVES)
-k_kpp_buoydiff_col(DevGrid g, KppDev kp, const double *__restrict__ T, const double *__restrict__ S,
-                   double *__restrict__ DBLOC, double *__restrict__ DBSFC) {
-  Col c;
-  if (!col_setup(g, c, false)) return;
-  const int km = g.km;
-  const long long n2 = g.n2;
-  const int kmt = g.KMT[c.q2];
-  MwjfTS2 top[KR + 1];
-#pragma unroll
-  for (int t = 1; t <= KR; ++t) {
-    const int kk = (t <= km) ? t : km;
-    const long long o = c.base3 + (long long)(kk - 1) * n2;
-    top[t] = mwjf_prep2(tmask(T[o]), S[o]);
-  }
-  DBSFC[c.base3] = 0.0;
-  MwjfTS2 xkm = top[1];
-  for (int k = 2; k <= km; ++k) {
-    const long long o = c.base3 + (long long)(k - 1) * n2;
-    const MwjfTS2 xk = mwjf_prep2(tmask(T[o]), S[o]);
-    const MwjfP P = mwjf_level(g.pressz[k]);
-    const double rhokm = mwjf_eval2(P, xkm);
-    const double rhok = mwjf_eval2(P, xk);
-    const double surfthick = KPP_EPSSFC * g.zt[k];
-    const int kref = kp.kref[k];
-    // kref is wave-uniform: the predicated iterations below are skipped as a whole
-    MwjfTS2 xr = top[1];
-#pragma unroll
-    for (int t = 2; t <= KR; ++t) if (t == kref) xr = top[t];
-    double rhoavg = mwjf_eval2(P, xr);
-    if (kref != 1) {
-      rhoavg = rhoavg * (surfthick - g.zw[kref - 1]);
-#pragma unroll
-      for (int kt = 1; kt <= KR - 1; ++kt)
-        if (kt <= kref - 1) rhoavg = rhoavg + g.dz[kt] * mwjf_eval2(P, top[kt]);
-      rhoavg = rhoavg / surfthick;
-    }
-    double dbs = 0.0, dbl = 0.0;
-    if (rhok != 0.0) { dbs = GRAV * (1.0 - rhoavg / rhok); dbl = GRAV * (1.0 - rhokm / rhok); }
-    if (k - 1 >= kmt) dbl = 0.0;
-    DBSFC[o] = dbs;
-    DBLOC[o - n2] = dbl;
-    if (k == km) DBLOC[o] = 0.0;
-    xkm = xk;
-  }
-}
-
 // ---- buoydiff, level-parallel form with the surface layer in LDS ---------------------------------------------------
-// The column form above is VALU-bound at one or two waves per SIMD (60 register doubles for the prepared surface-layer
-// levels).  Here a workgroup owns 64 columns and NG waves share them: the prepared top KR levels (clamped T, 1000 S,
-// pressure-independent denominator term) are formed once into LDS (KR * 3 * 512 B = 30 KB for KR = 20), and wave g takes the
+// The 3-D-parallel kernel re-reads the top kref levels of T and S for every level (66 GB through the fabric at tx0.1v3 for
+// 17 GB of algorithmic traffic) and repeats the pressure-independent half of every equation-of-state evaluation; a thread
+// that owns a whole column with the prepared top levels in registers (60 doubles) is VALU-bound at one or two waves per SIMD.
+// Here a workgroup owns 64 columns and NG waves share them: the prepared top KR levels (clamped T, 1000 S,
+// pressure-independent denominator term, mwjf_prep2; KR >= max kref, checked by the host) are formed once into LDS
+// (KR * 3 * 512 B = 30 KB for KR = 20), and wave g takes the
 // levels k = 2 + g, 2 + g + NG, ... (interleaved: the work per level grows with kref).  A thread keeps no column state, so
 // five workgroups fit a CU and the divisions of one wave hide behind the others.  Every (i,j,k) value is formed by the same
-// operations in the same order as in k_kpp_buoydiff / k_kpp_buoydiff_col: bitwise equal (tested).
+// operations in the same order as in k_kpp_buoydiff: bitwise equal (tested).
 template <int KR, int NG>
 __global__ void __launch_bounds__(POP_COL_THREADS * NG)
 k_kpp_buoydiff_lds(DevGrid g, KppDev kp, const double *__restrict__ T, const double *__restrict__ S,
@@ -282,7 +230,7 @@ k_kpp_buoydiff_lds(DevGrid g, KppDev kp, const double *__restrict__ T, const dou
 // k +- 1 -- are evaluated level-parallel from it.  T, S, U, V are read and DBLOC, DBSFC, VISC, VDC written once; the
 // Richardson scratch field and the second pass over T, S, U, V of the column kernels are gone.  All loops stay rolled (a
 // fully unrolled variant was 153 KB of code and ran at instruction-cache speed: 20 ms instead of 9).  Same operations
-// in the same order per value as k_kpp_buoydiff_col + k_kpp_interior(_reg): bitwise equal (tested).  km <= 64.
+// in the same order per value as k_kpp_buoydiff_lds + k_kpp_interior(_reg): bitwise equal (tested).  km <= 64.
 // SFC = false: DBSFC is not formed here (k_kpp_bldepth_lazy evaluates it on demand, level by level, until the boundary-layer
 // depth is found); the surface-layer levels are then not prepared and the rhoavg sums -- most of this kernel's arithmetic -- are gone.
 template <int KR, int NG, bool SFC = true>
@@ -1387,7 +1335,7 @@ inline void launch_kpp_vvc(const DevGrid &g, const HostModel &h, hipStream_t st,
 
 // ---- host side ---------------------------------------------------------------------------------
 // per-context KPP state (MixDev::kpp)
-// col: bit 0 = ushear, bit 1 = buoydiff in column form.  side / ev_*: second HIP stream on which the shear kernel (needs only
+// col: the mask of kernel forms (pop_tuning.kpp_col).  side / ev_*: second HIP stream on which the shear kernel (needs only
 // U, V; consumed by bldepth) runs beside buoydiff + interior (POP_KPP_SIDE_STREAM=0 keeps everything on one stream)
 // tidal: set by pop_init_tidal_mixing (tidal_on); bck: set by pop_init_kpp_bckgrnd (bck_on); zero_bck = km + 3 words of 0, the
 // background the interior kernels see with either
@@ -1563,12 +1511,9 @@ inline int kpp_create(HostModel &h, const DevGrid &g, MixDev &m, std::vector<voi
   K->max_kref = 1;
   for (int kk = 1; kk <= km; ++kk) K->max_kref = std::max(K->max_kref, kref[kk]);
   // column (register) forms: bandwidth-bound grids only -- below ~2^19 columns the 3-D-parallel forms win on
-  // parallelism.  Measured at tx0.1v3: ushear 11.2 -> 2.7 ms; buoydiff 16.1 -> 14.3 ms (VALU-bound either way:
-  // the column form halves the instruction count by hoisting the pressure-independent half of the equation of
-  // state, but its 3 x 20 register doubles leave one wave per SIMD).  POP_KPP_COL = bit mask (1 ushear,
-  // 2 buoydiff) overrides.
+  // parallelism.  Measured at tx0.1v3: ushear 11.2 -> 2.7 ms.  POP_KPP_COL = bit mask overrides.
   K->col = (K->max_kref <= 24) ? ((h.n2 * h.nblocks > (1u << 19)) ? 31 : 1) : 0;   // ushear: column form at every size (gx1v7 vmix 0.716 -> 0.692 ms)
-  if (tun_set(h.tun.kpp_col)) K->col = (K->max_kref <= 24) ? h.tun.kpp_col : 0;   // bit 0 ushear column form, bit 1 buoydiff column form, bit 2 buoydiff LDS form, bit 3 buoydiff + interior fused, bit 4 as one column march
+  if (tun_set(h.tun.kpp_col)) K->col = (K->max_kref <= 24) ? h.tun.kpp_col : 0;   // bit 0 ushear column form, bit 1 unused, bit 2 buoydiff LDS form, bit 3 buoydiff + interior fused, bit 4 as one column march
   (void)m;
   return 0;
 }
@@ -1591,17 +1536,17 @@ inline int kpp_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParam
   const dim3 GC(col_grid(g, POP_COL_THREADS), g.nblocks), BC(POP_COL_THREADS);
   const dim3 G3((g.n2 + 255) / 256, g.km, g.nblocks);
   double *DBLOC = s.S3a, *DBSFC = s.S3b, *WU = s.S3c, *VISC = s.S3d, *RIW = s.E3;
-  // level-parallel LDS form (bit 2 of the mask; the default on bandwidth-bound grids, linear column order only)
+  // level-parallel LDS form (bit 2 of the mask; the default on bandwidth-bound grids)
   const dim3 GL(col_grid_x(g.n2, POP_COL_THREADS), g.nblocks), BL(POP_COL_THREADS, 4);
 
   // ---- selection: which form of every stage runs (no launch above the pipeline below)
   // bit 3: buoydiff and the interior coefficients in ONE level-parallel launch
-  const bool fused_bi = (g_kpp_col & 8) && KH.max_kref <= 20 && g.xcd_remap != 2 && g.km <= 64;
-  const bool lds = (g_kpp_col & 4) && KH.max_kref <= 28 && g.xcd_remap != 2;
+  const bool fused_bi = (g_kpp_col & 8) && KH.max_kref <= 20 && g.km <= 64;
+  const bool lds = (g_kpp_col & 4) && KH.max_kref <= 28;
   // the surface-layer buoyancy difference on demand inside the boundary-layer-depth march (k_kpp_bldepth<true, .>); POP_KPP_LAZY=0 keeps
   // the full field
-  // (with the level-parallel fused kernel and with the plain 3-D buoydiff kernel; the column / LDS buoydiff forms keep the full field)
-  const bool plain3d = !fused_bi && !lds && !(g_kpp_col & 2);
+  // (with the level-parallel fused kernel and with the plain 3-D buoydiff kernel; the LDS buoydiff form keeps the full field)
+  const bool plain3d = !fused_bi && !lds;
   const bool lazy = (fused_bi || plain3d) && KH.max_kref <= 28 && !g_kpp.lcheckekmo && h.c.kpp_ml_diagnostics != 1 &&
                     !tun_off(h.tun.kpp_lazy);
   const bool lazy20 = lazy && KH.max_kref <= 20;
@@ -1613,20 +1558,17 @@ inline int kpp_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParam
   const bool pbc_generic = g.pbc && !(march && lazy20 && (g_kpp_col & 1) && !tun_on(h.tun.pbc_generic_kpp));
   struct Sel {
     bool shear_col;                                          // k_kpp_ushear_col<24, PBC>, else k_kpp_ushear<PBC>
-    enum { MARCH, FUSED_LDS, LDS, COL, PLAIN } buoy;         // MARCH and FUSED_LDS form the interior coefficients too
-    int buoy_kr; bool buoy_sfc, buoy_two_waves;              // <KR> of the LDS / column forms, <SFC> of the fused / plain ones
+    enum { MARCH, FUSED_LDS, LDS, PLAIN } buoy;         // MARCH and FUSED_LDS form the interior coefficients too
+    int buoy_kr; bool buoy_sfc;                              // <KR> of the LDS form, <SFC> of the fused / plain ones
     bool depth_lazy; int depth_kr;                           // k_kpp_bldepth<LAZY, KR, PBC>
     enum { FUSED, REG, GENERIC } interior;
     bool same, sparse;                                       // k_kpp_blmix<PBC, SAME, SPARSE>
     bool side, wuk, convb;                                   // the side stream used; KppDev::WUK / CONVB set
   } sel;
   sel.shear_col = !pbc_generic && (g_kpp_col & 1);
-  sel.buoy = pbc_generic ? Sel::PLAIN : march ? Sel::MARCH : fused_bi ? Sel::FUSED_LDS : lds ? Sel::LDS : (g_kpp_col & 2) ? Sel::COL : Sel::PLAIN;
-  sel.buoy_kr = KH.max_kref <= 20 ? 20 : (sel.buoy == Sel::LDS ? 28 : 24);
+  sel.buoy = pbc_generic ? Sel::PLAIN : march ? Sel::MARCH : fused_bi ? Sel::FUSED_LDS : lds ? Sel::LDS : Sel::PLAIN;
+  sel.buoy_kr = KH.max_kref <= 20 ? 20 : 28;
   sel.buoy_sfc = pbc_generic || !lazy;
-  // two waves per SIMD (<= 256 VGPRs, ~80 spilled) beat one wave with everything in registers: the kernel is VALU-bound
-  // and a second wave fills the division / dependency stalls of the first (POP_KPP_BUOY_WAVES=1 keeps one wave)
-  sel.buoy_two_waves = tun_or(h.tun.kpp_buoy_waves, 2) == 2;
   sel.depth_lazy = !pbc_generic && lazy;
   sel.depth_kr = (sel.depth_lazy && !lazy20) ? 28 : 20;
   sel.interior = pbc_generic ? Sel::GENERIC : fused_bi ? Sel::FUSED :
@@ -1656,7 +1598,6 @@ inline int kpp_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParam
   if (sel.buoy == Sel::MARCH) with_flags([&](auto PBC) { hipLaunchKernelGGL(k_kpp_buoy_interior_march<PBC.value>, GC, BC, 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, DBLOC, VISC, s.VDC[0], s.VDC[1]); }, g.pbc);
   else if (sel.buoy == Sel::FUSED_LDS) with_flags([&](auto SFC) { hipLaunchKernelGGL((k_kpp_buoy_interior_lds<20, 8, SFC.value>), GL, dim3(POP_COL_THREADS, 8), 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, DBLOC, DBSFC, VISC, s.VDC[0], s.VDC[1]); }, sel.buoy_sfc);
   else if (sel.buoy == Sel::LDS) with_value<20, 28>(sel.buoy_kr, [&](auto KR) { hipLaunchKernelGGL((k_kpp_buoydiff_lds<KR.value, 4>), GL, BL, 0, st, g, g_kpp, T0, T1, DBLOC, DBSFC); });
-  else if (sel.buoy == Sel::COL) with_flags([&](auto KR24, auto W2) { hipLaunchKernelGGL((k_kpp_buoydiff_col<KR24.value ? 24 : 20, W2.value ? 2 : 1>), GC, BC, 0, st, g, g_kpp, T0, T1, DBLOC, DBSFC); }, sel.buoy_kr == 24, sel.buoy_two_waves);
   else with_flags([&](auto SFC) { hipLaunchKernelGGL(k_kpp_buoydiff<SFC.value>, G3, dim3(256), 0, st, g, g_kpp, T0, T1, DBLOC, DBSFC); }, sel.buoy_sfc);
   // the boundary-layer depth (needs buoydiff + shear, writes only the 2-D boundary-layer fields) follows the shear kernel
   // on the side stream and runs beside the interior coefficients; blmix waits for both.  Without the side stream it follows

@@ -31,7 +31,7 @@ struct PcsiArgs {
   int j;                           // step inside the interval (1-based); j = 0: start-up step
   int remote_ghosts;               // multi-rank: also advance dx, x at ghosts owned by other ranks
   int nchunk;                      // stride of the partial slots per block (the launch may be compacted: DevGrid::red_act)
-  int raw_r;                       // EVP preconditioner (r3): Ro receives the residual itself; k_evp_apply_wave2 turns it into r' for the next step
+  int raw_r;                       // EVP preconditioner: Ro receives the residual itself; the sub-block solves that follow (evp_apply) turn it into r' for the next step
   const int *jfold;                // k_pcsi_step_x2<., true>: per block, the first array row (0-based) beyond a tripole fold; nyb where the block does not touch it
 };
 

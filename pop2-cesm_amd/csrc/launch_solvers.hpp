@@ -14,18 +14,12 @@ SolverArgs solver_args(pop_ctx *c) {
 // preconditioner() with preconditionerChoice = 'evp' (:2331-2366): PX <- sub-block solves of X on the physical cells
 // residual: X is a residual of a solver (zero on land): sub-blocks without an ocean cell are not read (k_evp_apply_wave3<true>)
 int evp_apply(pop_ctx *c, const double *X, double *PX, bool residual = true) {
-  const int wave = tun_or(c->h.tun.evp_wave, 3);   // 3 (default): wavefronts, operands in registers, every load up front; 2: the same with the loads behind their conditions; 1: wavefronts, operands in LDS; 0: a thread per sub-block
-  if (wave == 3 && c->evp.C0 && residual)
-    hipLaunchKernelGGL(k_evp_apply_wave3<true>, dim3((unsigned)((c->evp.S + POP_EVP_SB - 1) / POP_EVP_SB)), dim3(64), 0, c->stream, c->evp, c->g.nxb, X, PX);
-  else if (wave == 3 && c->evp.C0)
-    hipLaunchKernelGGL(k_evp_apply_wave3<false>, dim3((unsigned)((c->evp.S + POP_EVP_SB - 1) / POP_EVP_SB)), dim3(64), 0, c->stream, c->evp, c->g.nxb, X, PX);
-  else if (wave == 2 && c->evp.C0)
-    hipLaunchKernelGGL(k_evp_apply_wave2, dim3((unsigned)((c->evp.S + POP_EVP_SB - 1) / POP_EVP_SB)), dim3(64), 0, c->stream, c->evp, c->g.nxb, X, PX);
-  else if (wave != 0)   // anti-diagonal wavefronts: eight lanes per sub-block, eight sub-blocks per wave
-    hipLaunchKernelGGL(k_evp_apply_wave, dim3((unsigned)((c->evp.S + POP_EVP_SB - 1) / POP_EVP_SB)), dim3(64), 0, c->stream, c->evp, c->g.nxb, X, PX);
-  else
+  const dim3 GW((unsigned)((c->evp.S + POP_EVP_SB - 1) / POP_EVP_SB));
+  if (tun_off(c->h.tun.evp_wave))   // pop_tuning.evp_wave = 0: a thread per sub-block, the plain statement in the reference's order
     hipLaunchKernelGGL(k_evp_apply, dim3((unsigned)((c->evp.S + POP_EVP_THREADS - 1) / POP_EVP_THREADS)), dim3(POP_EVP_THREADS), 0, c->stream,
                        c->evp, c->g.nxb, X, PX);
+  else   // 3 (the default): anti-diagonal wavefronts, eight lanes per sub-block, eight sub-blocks per wave
+    with_flags([&](auto RES) { hipLaunchKernelGGL(k_evp_apply_wave3<RES.value>, GW, dim3(64), 0, c->stream, c->evp, c->g.nxb, X, PX); }, residual);
   HIPCHK(c, hipGetLastError());
   return 0;
 }
@@ -105,7 +99,7 @@ static bool presum_by_size(long long nchunk, long long nblocks) { return nchunk 
 // two cells per thread: where the block sums are presummed (large grids), the row pitch is even and the launch is not tiled.  two_cell_shape
 // is the whole rule for the P-CSI step (pop_create_tuned: pcsi_two_cell); the fused pcg / ChronGear kernels also honour
 // pop_tuning.fpcg_b2 = 0 (POP_FPCG_B2=0: one cell per thread even on large grids)
-static bool two_cell_shape(const DevGrid &g, bool presummed) { return presummed && (g.nxb & 1) == 0 && !g.red_tiles; }
+static bool two_cell_shape(const DevGrid &g, bool presummed) { return presummed && (g.nxb & 1) == 0; }
 static bool two_cell_ok(const pop_ctx *c, const DevGrid &g, bool presummed) { return two_cell_shape(g, presummed) && !tun_off(c->h.tun.fpcg_b2); }
 FusedArgs fused_args(pop_ctx *c, const SolveView &v) {
   FusedArgs a{};

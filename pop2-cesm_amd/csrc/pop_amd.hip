@@ -185,14 +185,14 @@ int pop_create_with_grid(const pop_config *cfg, const pop_grid_input *grid, int 
 
 // ---- tuning switches (include/pop_amd.h pop_tuning): one table of (field, environment variable)
 #define POP_TUNING_FIELDS(X)                                                                                                            \
-  X(land_skip, "POP_LAND_SKIP") X(land_full_steps, "POP_LAND_FULL_STEPS") X(xcd_remap, "POP_XCD_REMAP") X(red_tiles, "POP_RED_TILES")   \
+  X(land_skip, "POP_LAND_SKIP") X(land_full_steps, "POP_LAND_FULL_STEPS") X(xcd_remap, "POP_XCD_REMAP")   \
   X(red_band, "POP_RED_BAND") X(lds_order, "POP_LDS_ORDER") X(momentum_lds, "POP_MOMENTUM_LDS") X(tracer_lds, "POP_TRACER_LDS")         \
   X(generic_thomas, "POP_GENERIC_THOMAS") X(reg_thomas_t, "POP_REG_THOMAS_T") X(thomas_pair, "POP_THOMAS_PAIR")                         \
   X(tracer_fwd, "POP_TRACER_FWD") X(vdc_shared, "POP_VDC_SHARED") X(side_stream, "POP_SIDE_STREAM") X(del4_side, "POP_DEL4_SIDE")       \
   X(del4_tile, "POP_DEL4_TILE") X(d2t_fuse, "POP_D2T_FUSE") X(d2u_fuse, "POP_D2U_FUSE") X(vmixu_defer, "POP_VMIXU_DEFER")               \
   X(vmixu_inline, "POP_VMIXU_INLINE") X(btrop_inline, "POP_BTROP_INLINE") X(kpp_ahead, "POP_KPP_AHEAD") X(kpp_col, "POP_KPP_COL")       \
   X(kpp_lazy, "POP_KPP_LAZY") X(kpp_ushear_hint, "POP_KPP_USHEAR_HINT") X(kpp_ushear_margin, "POP_KPP_USHEAR_MARGIN")                   \
-  X(kpp_side_stream, "POP_KPP_SIDE_STREAM") X(kpp_buoy_waves, "POP_KPP_BUOY_WAVES") X(kpp_interior_generic, "POP_KPP_INTERIOR_GENERIC") \
+  X(kpp_side_stream, "POP_KPP_SIDE_STREAM") X(kpp_interior_generic, "POP_KPP_INTERIOR_GENERIC") \
   X(kpp_src_full, "POP_KPP_SRC_FULL") X(solver_unfused, "POP_SOLVER_UNFUSED") X(solver_nograph, "POP_SOLVER_NOGRAPH")                   \
   X(solver_presum, "POP_SOLVER_PRESUM") X(solver_distributed, "POP_SOLVER_DISTRIBUTED") X(solver_overlap_off, "POP_SOLVER_OVERLAP_OFF") \
   X(fpcg_b2, "POP_FPCG_B2") X(pcsi_step2, "POP_PCSI_STEP2") X(halo_separate, "POP_HALO_SEPARATE")                                       \
@@ -329,6 +329,10 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
     if (cfg->lsw_absorb != 0 && (cfg->sw_absorption_type < 0 || cfg->sw_absorption_type > 2)) return bad("lsw_absorb: sw_absorption_type 0 top-layer, 1 jerlov, 2 chlorophyll");
     if (cfg->vmix_choice == 3 && cfg->num_v_smooth_Ri < 1) return bad("KPP: num_v_smooth_Ri must be >= 1 (the reference leaves FRI unset otherwise)");
     if (!(cfg->convergence_criterion >= 0.0)) return bad("convergence_criterion must be >= 0");
+    // pop_tuning: the switches whose other values named kernel forms that no longer exist
+    const pop_tuning &tun = c->h.tun;
+    if (tun_set(tun.xcd_remap) && tun.xcd_remap != 0 && tun.xcd_remap != 1) return bad("pop_tuning.xcd_remap is " + std::to_string(tun.xcd_remap) + ": 0 linear or 1 XCD bands");
+    if (tun_set(tun.evp_wave) && tun.evp_wave != 0 && tun.evp_wave != 3) return bad("pop_tuning.evp_wave is " + std::to_string(tun.evp_wave) + ": 0 one thread per sub-block or 3 wavefronts");
   }
   c->h.plan_only = (flags & POP_CREATE_PLAN_ONLY) != 0;
   const int hb = host_build(c->h);
@@ -353,13 +357,11 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
   g.n2 = (int)h.n2; g.n3 = (long long)h.n3;
   // workgroup order (kernels_common.hpp).  Measured on MI355X: the XCD-banded order cuts fabric re-fetch of
   // the stencil kernels from 3.2x to 1.3x of the algorithmic reads at gx1v7 (-6% time) but costs +20% at
-  // tx0.1v3; row-aligned tile columns (mode 2 / POP_RED_TILES) lose 128-B alignment of the rows
-  // (nx_block*8 B is not a multiple of 128) and cost +10% (columns) / +2% (solver) at tx0.1v3, where
-  // the 256 MB infinity cache already absorbs the re-fetch.  Large grids therefore keep the natural
-  // linear order; the other orders stay selectable (POP_XCD_REMAP=0|1|2, POP_RED_TILES=0|1) and tested.
+  // tx0.1v3, where the 256 MB infinity cache already absorbs the re-fetch (row-aligned 2-D tile columns, tried
+  // for both the column and the reduction kernels, lost 128-B alignment of the rows and cost +10% / +2% there).
+  // Large grids therefore keep the natural linear order; either order stays selectable (POP_XCD_REMAP=0|1) and tested.
   g.xcd_remap = (h.n2 * h.nblocks <= (1u << 19)) ? 1 : 0;
   g.xcd_remap = tun_or(h.tun.xcd_remap, g.xcd_remap);
-  g.red_tiles = tun_or(h.tun.red_tiles, 0);
   // 2-D solver / reduction kernels: XCD-banded chunk order (same chunks, same partial order, only the workgroup ->
   // chunk assignment changes, so results are bitwise unchanged): gx1v7 4.31 -> 4.01 ms per step (the 9-point
   // matvec finds its j+-1 rows in the XCD's own L2), tx0.1v3 177.1 -> 175.2.  POP_RED_BAND=0 restores the natural order.
@@ -683,7 +685,7 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
   }
   c->mom_side = cfg->hmix_momentum == 3 ? (c->side != nullptr && !tun_off(h.tun.aniso_side)) : c->side_del4;
   c->nchunk = red_grid_x(g);
-  if (!g.red_tiles) {   // DevGrid::red_act: the chunks (256 consecutive cells) the fused solver kernels have to visit
+  {   // DevGrid::red_act: the chunks (256 consecutive cells) the fused solver kernels have to visit
     const int nc = (int)((h.n2 + 255) / 256);
     const bool multi = h.nranks > 1;
     std::vector<std::vector<int>> act(h.nblocks), land(h.nblocks);
@@ -880,11 +882,11 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
           if (c->h_srcmap[cell] == cell) fold_local = false;
         }
       }
-    const bool two_ok = !use_evp(*cfg) && !g.red_tiles && fold_local, two_on = tun_set(h.tun.pcsi_two_step) ? h.tun.pcsi_two_step != 0 : c->pcsi_two_cell;
+    const bool two_ok = !use_evp(*cfg) && fold_local, two_on = tun_set(h.tun.pcsi_two_step) ? h.tun.pcsi_two_step != 0 : c->pcsi_two_cell;
     c->pcsi_two_step = two_ok && two_on && h.halo.peers.empty();
     c->pcsi_two_step_dist = two_ok && two_on && !h.halo.peers.empty();
     if ((c->pcsi_two_step || c->pcsi_two_step_dist) && dev_alloc(c, &c->pcsi_raw, a2)) return 1;
-    c->pcsi_evp_fused = c->evp_fused_ok && c->evp.C0 && tun_or(h.tun.evp_wave, 3) >= 2 && tun_on(h.tun.pcsi_evp_fused);   // measured slower: off unless asked for
+    c->pcsi_evp_fused = c->evp_fused_ok && !tun_off(h.tun.evp_wave) && tun_on(h.tun.pcsi_evp_fused);   // measured slower: off unless asked for
     if (c->pcsi_evp_fused && !c->pcsi_raw && dev_alloc(c, &c->pcsi_raw, a2)) return 1;
     if ((c->pcsi_two_step || c->pcsi_two_step_dist) && cfg->ns_boundary == 2 && dev_upload(c, &c->pcsi_jfold, jfold.data(), jfold.size())) return 1;
     if (tun_set(h.tun.pcsi_step2)) c->pcsi_two_cell = two_cell_shape(g, h.tun.pcsi_step2 != 0);
@@ -1493,15 +1495,13 @@ static void gm_flux_launch(pop_ctx *c, const GmDev &G, const double *X0, const d
   const StepParams sp = step_params(c);
   double *v1 = (sp.nvdc == 2 && c->VDC[1] != c->VDC[0]) ? c->VDC[1] : nullptr;   // one shared array is added to once
   if (!tun_off(c->h.tun.gm_flux_tile) && (G.cancellation || G.SF[0])) {
-    // straight-line flux functions, every horizontal face flux formed once (64 x 4 patches computing 63 x 3 cells); pop_tuning.gm_flux_tile = 0,
-    // or the stream-function terms not stored (gm_sf_stored = 0): the cell-by-cell kernel
-    const int R = (c->h.tun.gm_flux_tile == 4) ? 4 : 8;     // rows of the patch: 64 x 8 computing 63 x 7 cells (gm_flux_tile = 4: 64 x 4, measured 2 % of the step slower)
+    // straight-line flux functions, every horizontal face flux formed once (64 x 8 patches computing 63 x 7 cells; 64 x 4 measured 2 % of the step
+    // slower); pop_tuning.gm_flux_tile = 0, or the stream-function terms not stored (gm_sf_stored = 0): the cell-by-cell kernel
+    constexpr int R = 8;     // rows of the patch
     const dim3 GT(((c->g.nxb + 62) / 63) * ((c->g.nyb + R - 2) / (R - 1)), (c->g.km + POP_GM_KC - 1) / POP_GM_KC, G3.z);
-    with_value<4, 8>(R, [&](auto RV) {
-      with_flags([&](auto CANC, auto ADD) {
-        hipLaunchKernelGGL((k_gm_flux_tile<RV.value, CANC.value, ADD.value>), GT, dim3(64, RV.value), 0, c->stream, c->g, G, X0, X1, c->VDC[0], v1);
-      }, G.cancellation, add);
-    });
+    with_flags([&](auto CANC, auto ADD) {
+      hipLaunchKernelGGL((k_gm_flux_tile<R, CANC.value, ADD.value>), GT, dim3(64, R), 0, c->stream, c->g, G, X0, X1, c->VDC[0], v1);
+    }, G.cancellation, add);
   } else
   with_flags([&](auto ADD) {
     hipLaunchKernelGGL(k_gm_flux<ADD.value>, dim3(G3.x, (c->g.km + POP_GM_KC - 1) / POP_GM_KC, G3.z), dim3(256), 0, c->stream, c->g, G, X0, X1, c->VDC[0], v1);

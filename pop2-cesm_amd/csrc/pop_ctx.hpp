@@ -268,10 +268,7 @@ std::vector<double> local_part3(const HostModel &h, const std::vector<double> &a
 }
 
 // column kernels: one wave per workgroup; tile order per kernels_common.hpp col_setup
-dim3 grid_cols(const pop_ctx *c) {
-  if (c->g.xcd_remap == 2) return dim3(tile_grid_x(c->g.nxb, c->g.nyb, POP_COL_THREADS, 1), c->g.nblocks);
-  return dim3(col_grid(c->g, POP_COL_THREADS), c->g.nblocks);
-}
+dim3 grid_cols(const pop_ctx *c) { return dim3(col_grid(c->g, POP_COL_THREADS), c->g.nblocks); }
 dim3 block_stencil() { return dim3(POP_COL_THREADS, 1); }
 dim3 grid_stencil(const pop_ctx *c) { return grid_cols(c); }
 dim3 grid_2d(const pop_ctx *c) { return dim3(red_grid_x(c->g), c->g.nblocks); }

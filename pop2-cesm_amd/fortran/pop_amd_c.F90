@@ -74,11 +74,11 @@
    end type pop_grid_input
    ! pop_tuning (include/pop_amd.h): kernel-form and schedule choices, none changes a result; fill with pop_tuning_init, then set fields
    type, bind(C) :: pop_tuning
-      integer (c_int) :: struct_bytes, land_skip, land_full_steps, xcd_remap, red_tiles, red_band
+      integer (c_int) :: struct_bytes, land_skip, land_full_steps, xcd_remap, red_band
       integer (c_int) :: lds_order, momentum_lds, tracer_lds, generic_thomas, reg_thomas_t, thomas_pair
       integer (c_int) :: tracer_fwd, vdc_shared, side_stream, del4_side, del4_tile, d2t_fuse
       integer (c_int) :: d2u_fuse, vmixu_defer, vmixu_inline, btrop_inline, kpp_ahead, kpp_col
-      integer (c_int) :: kpp_lazy, kpp_ushear_hint, kpp_ushear_margin, kpp_side_stream, kpp_buoy_waves, kpp_interior_generic
+      integer (c_int) :: kpp_lazy, kpp_ushear_hint, kpp_ushear_margin, kpp_side_stream, kpp_interior_generic
       integer (c_int) :: kpp_src_full, solver_unfused, solver_nograph, solver_presum, solver_distributed, solver_overlap_off
       integer (c_int) :: fpcg_b2, pcsi_step2, halo_separate, halo_overlap_off, rccl_overlap, evp_wave
       integer (c_int) :: fpcg_a_pair, kpp_sparse, pbc_generic_thomas, pbc_generic_kpp, stream_priority, gm_sf_stored, state3d_levels

@@ -41,7 +41,7 @@ print("child ok")
 """
 
 # the kernels whose launches go through the dispatcher
-KERNELS = ("k_kpp_ushear", "k_kpp_ushear_col", "k_kpp_buoy_interior_march", "k_kpp_buoy_interior_lds", "k_kpp_buoydiff_lds", "k_kpp_buoydiff_col",
+KERNELS = ("k_kpp_ushear", "k_kpp_ushear_col", "k_kpp_buoy_interior_march", "k_kpp_buoy_interior_lds", "k_kpp_buoydiff_lds",
            "k_kpp_buoydiff", "k_kpp_bldepth", "k_kpp_interior_reg", "k_kpp_interior", "k_kpp_blmix", "k_impvmixt", "k_impvmixt_reg", "k_impvmixt2_reg",
            "k_impvmixu_reg", "k_impvmixu_norm", "k_tracer_rhs_lds", "k_tracer_rhs", "k_momentum_rhs_lds", "k_momentum_rhs", "k_hdiffu_aniso",
            "k_del4_d2t", "k_del4_d2u", "k_rich_t", "k_state3d_lv", "k_state3d", "k_gm_flux_tile", "k_lw_flux", "k_lw_x", "k_lw_y", "k_lw_z",
@@ -91,7 +91,7 @@ def cfgs():
     add("del4", dict(DEL4, lvariable_hmix=1))
     add("del4-pbc", dict(DEL4, **PBC))
     # Gent-McWilliams: flux tiles 0 / 4 / 8, with and without cancellation; the tracer kernels with the tendency given
-    for tile in ("0", "4", "8"):
+    for tile in ("0", "8"):
         add("gm-tile%s" % tile, GM, {"POP_GM_FLUX_TILE": tile, "POP_TRACER_LDS": "8" if tile == "8" else "4"})
         add("gm-tile%s-nocanc" % tile, dict(GM, **NOCANC), {"POP_GM_FLUX_TILE": tile})
     add("gm-tadvect2", dict(GM, tadvect=2))
@@ -99,7 +99,6 @@ def cfgs():
     # KPP, flat bottom: every form of every stage
     for col in ("0", "1", "3", "7", "15", "31"):
         add("kpp-km24-col%s" % col, K(24), {"POP_KPP_COL": col, "POP_XCD_REMAP": "0"})
-    add("kpp-km24-col3-waves1", K(24), {"POP_KPP_COL": "3", "POP_KPP_BUOY_WAVES": "1"})
     add("kpp-km24-col1-lazy0", K(24), {"POP_KPP_COL": "1", "POP_KPP_LAZY": "0"})
     add("kpp-km24-col15-lazy0", K(24), {"POP_KPP_COL": "15", "POP_KPP_LAZY": "0", "POP_XCD_REMAP": "0"})
     add("kpp-km24-col15-dbl-noside", K(24, ldbl_diff=1), {"POP_KPP_COL": "15", "POP_KPP_SIDE_STREAM": "0"})
@@ -133,7 +132,6 @@ def cfgs():
     # more levels ("km levels cannot span zmax"); the kernels that band selects are all reached by the configurations above
     add("kpp-km70", K(70))
     add("kpp-km70-col3", K(70), {"POP_KPP_COL": "3"})
-    add("kpp-km70-col3-waves1", K(70), {"POP_KPP_COL": "3", "POP_KPP_BUOY_WAVES": "1"})
     add("kpp-km70-col7", K(70), {"POP_KPP_COL": "7", "POP_XCD_REMAP": "0"})
     # the most rewritten launch paths first, the untested vertical grids last (a --budget cuts the list at its end)
     order = lambda x: 2 if x["id"].startswith("kpp-km70") else 0 if x["id"].startswith(("kpp", "big")) else 1

@@ -1,6 +1,6 @@
 """The independent pins of the momentum right-hand side and of tracer advection (tests/pins.py; tests/test_dyn_pins_oracle.py runs them on
 the CPU oracle) against the DEVICE library through the C ABI, in every form of the kernels a grid this small can select: the LDS-tiled and
-the direct-load momentum and tracer kernels, the 60-level column, the del4 first-Laplacian forms, the large-grid tile order, land elimination,
+the direct-load momentum and tracer kernels, the 60-level column, the del4 first-Laplacian forms, the large-grid workgroup order, land elimination,
 the passive-tracer launches.  Bounds: 10 x the oracle's figure or the 1e-12 floor (pins._dyn_tol)."""
 import pytest
 
@@ -10,7 +10,7 @@ from popcfg import named_config
 
 pytestmark = pytest.mark.gpu
 
-BIG = {"POP_XCD_REMAP": "2", "POP_RED_TILES": "1"}     # the tile orders production uses above 2^19 columns
+BIG = {"POP_XCD_REMAP": "0"}     # the linear workgroup order the size rule gives above 2^19 columns (`wide` alone would get the XCD bands)
 MOMENTUM_FORMS = ("8", "0")                            # POP_MOMENTUM_LDS: LDS-tiled and direct-load kernels
 TRACER_FORMS = ("4", "0")                              # POP_TRACER_LDS: read by centred advection only (upwind3 and lw_lim have one kernel each)
 
@@ -93,7 +93,7 @@ def test_advection_keeps_a_constant_and_conserves(kw, tadvect, pkg, monkeypatch)
 
 @pytest.mark.parametrize("tadvect", [1, 2, 3], ids=["centred", "upwind3", "lw_lim"])
 def test_advection_in_the_large_grid_tile_order_with_land_elimination(tadvect, pkg, monkeypatch):
-    """'wide' with the tile order of large grids; the step the check stands in skips the land tiles (its six steps let every time level pass
+    """'wide' with the workgroup order of large grids; the step the check stands in skips the land tiles (its six steps let every time level pass
     through a full step), and only ocean cells are read"""
     for k, v in dict(BIG, POP_LAND_SKIP="1", POP_LAND_FULL_STEPS="4", POP_TRACER_LDS="4").items():
         monkeypatch.setenv(k, v)

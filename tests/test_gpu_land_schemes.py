@@ -1,6 +1,6 @@
 """Land elimination (tests/test_gpu_land.py) with the schemes that were added after it: Gent-McWilliams, the submesoscale scheme,
 anisotropic viscosity, Jayne tidal mixing and the latitude-varying background inside the KPP look-ahead, frazil ice, partial bottom
-cells, time-averaged output, the exact restart -- and the six pop_tuning fields no other test names.
+cells, time-averaged output, the exact restart -- and the five pop_tuning fields no other test names.
 
 From the fifth step after set-up, a restart or a new state every workgroup whose tile or 256-cell run holds no ocean cell returns at
 once (kernels_common.hpp col_setup, patch_cell, land_tile, land_run, red_land).  That rests on one claim: what the full kernels write
@@ -338,31 +338,29 @@ def test_exact_restart_across_the_switch(pkg, tmp_path, fresh):
     a.close(); b.close()
 
 
-# ---- 5. the six tuning fields without a test -------------------------------------------------------------------------------------------
+# ---- 5. the five tuning fields without a test ------------------------------------------------------------------------------------------
 KM60 = dict(vmix_choice=3, km=60, stepped_bathymetry=1)
 KPP24 = dict(vmix_choice=3, km=24)
 WIDE_KPP_DEL4 = dict(DEL4, vmix_choice=3)
 # (grid, pop_config keywords, tuning both models share, [tuning of each X], pop_get_dim values on D that show the replaced form in use,
 #  steps).  Where the library reads the field:
-#   red_band      pop_amd.hip:362 -> kernels_common.hpp red_grid_x / red_chunk: which workgroup takes which 256-cell chunk of the 2-D reduction
+#   red_band      pop_amd.hip:369 -> kernels_common.hpp red_grid_x / red_chunk: which workgroup takes which 256-cell chunk of the 2-D reduction
 #                 and fused solver kernels.  pcg on `wide` (165 chunks) with the resident solve off, so that the fused two-launch iteration
-#                 runs; without land elimination neither red_tiles nor the compacted chunk list is active, with it (past step 5) red_land
+#                 runs; without land elimination the compacted chunk list is not active, with it (past step 5) red_land
 #                 derives the cells of its chunk from red_chunk
-#   lds_order     pop_amd.hip:361 -> kernels_common.hpp lds_tile / lds_launch_x: the LDS-tiled momentum and tracer right-hand sides, and the
-#                 order in which the compacted tile lists lds_act4 / lds_act8 are built (pop_amd.hip:493-517), used past step 5
-#   vmixu_inline  pop_amd.hip:1868-1871: at km = 60 with the register Thomas kernel the implicit vertical mixing of U, V runs on the side
+#   lds_order     pop_amd.hip:368 -> kernels_common.hpp lds_tile / lds_launch_x: the LDS-tiled momentum and tracer right-hand sides, and the
+#                 order in which the compacted tile lists lds_act4 / lds_act8 are built (pop_amd.hip:497-527), used past step 5
+#   vmixu_inline  pop_amd.hip:1882-1885: at km = 60 with the register Thomas kernel the implicit vertical mixing of U, V runs on the side
 #                 stream beside the solver; 1 puts it on the launch stream
-#   btrop_inline  pop_amd.hip:1868, :2002: the barotropic velocity is added on the side stream beside the tracer corrector; 1 adds it in the
+#   btrop_inline  pop_amd.hip:1882, :2018: the barotropic velocity is added on the side stream beside the tracer corrector; 1 adds it in the
 #                 step tail
-#   kpp_buoy_waves  kernels_kpp.hpp:1629 -> :1659: launch bounds of k_kpp_buoydiff_col, which runs with kpp_col = 2 (the column buoydiff form)
-#   stream_priority pop_amd.hip:340: the launch stream created above the side streams
-# All six are bitwise neutral in whole (none regroups a sum), so every row is compared with np.array_equal.
+#   stream_priority pop_amd.hip:345: the launch stream created above the side streams
+# All five are bitwise neutral in whole (none regroups a sum), so every row is compared with np.array_equal.
 TUNING = {
     "red_band": ("wide", {}, {"pcg_persist": 0, "land_skip": 0}, [{"red_band": 0}], {"pcg_persist_used": 0, "land_skip_active": 0}, 5),
     "red_band-tiles-skipped": ("wide", {}, dict(SKIP, pcg_persist=0), [{"red_band": 0}], {"pcg_persist_used": 0, "land_skip_active": 1}, 7),
     "lds_order": ("wide", {}, SKIP, [{"lds_order": 0, "momentum_lds": r, "tracer_lds": r} for r in (4, 8)], {"land_skip_active": 1}, 7),
     "vmixu_inline-btrop_inline": ("tiny", KM60, {}, [{"vmixu_inline": 1}, {"btrop_inline": 1}], {"thomas_register_velocity": 1}, 5),
-    "kpp_buoy_waves": ("tiny", KPP24, {"kpp_col": 2}, [{"kpp_buoy_waves": 1}], {}, 5),
     "stream_priority": ("tiny", KPP24, {}, [{"stream_priority": 1}], {}, 5),
 }
 

@@ -376,28 +376,6 @@ def test_tripole_without_grid_input_refuses_to_step(pkg):
     m.close()
 
 
-@pytest.mark.parametrize("kw,nsteps", [
-    ({}, 3),
-    ({"block_size_x": 1056}, 3),                                           # two blocks side by side
-    ({"vmix_choice": 3, "hmix_momentum": 4, "hmix_tracer": 4, "am": -1.0e19, "ah": -1.0e18}, 3),   # KPP + del4
-])
-def test_large_grid_tile_order_matches_oracle(pkg, orclib_built, monkeypatch, kw, nsteps):
-    """POP_XCD_REMAP=2 forces the tile-column workgroup order production uses above 2^19 columns
-    (kernels_common.hpp) on a grid small enough for the oracle: full 8-column groups, left-over
-    columns and surplus workgroups all occur (2116 = 33 x 64 + 4 = 8 x 256 + 68)."""
-    monkeypatch.setenv("POP_XCD_REMAP", "2")
-    monkeypatch.setenv("POP_RED_TILES", "1")
-    cfg = named_config("wide", **kw)
-    gpu, orc = pkg.PopModel(cfg), Oracle(cfg)
-    if cfg.vmix_choice == 3:
-        force_kpp_case(gpu, orc)
-    tol = TOL_LOCAL
-    for s in range(1, nsteps + 1):
-        run_phases(gpu, orc, s, tol)
-        tol = TOL_SOLVE
-    gpu.close(); orc.close()
-
-
 def test_state_known_answer_and_derivatives(pkg, orclib_built):
     """state_mod.F90:413-414: rho(S=35 psu, theta=20 C, p=200 bar) -- the comment quotes
     1.033213242; the reference's own coefficient set evaluates to 1.0332133866 (see
@@ -865,9 +843,10 @@ def test_production_level_counts_match_oracle(pkg, orclib_built, monkeypatch, kw
 @pytest.mark.parametrize("kw", [{"vmix_choice": 3, "km": 24}, {"vmix_choice": 3, "km": 24, "ldbl_diff": 1, "block_size_x": 48, "block_size_y": 40},
                                 {"vmix_choice": 3, "km": 62, "stepped_bathymetry": 1, "num_v_smooth_Ri": 2, "ldbl_diff": 1}])
 def test_kpp_column_kernels_agree_bitwise(pkg, orclib_built, monkeypatch, kw):
-    """buoydiff / ushear exist in a 3-D-parallel form (small grids) and a column form with the top
-    reference levels in registers (large grids; POP_KPP_COL is a bit mask that forces either): same operations in the same
-    order, so every output of the step must be identical to the last bit."""
+    """ushear exists in a 3-D-parallel form and a column form with the top reference levels in registers, buoydiff in a 3-D-parallel
+    form, a level-parallel form with those levels in LDS and one fused with the interior coefficients (POP_KPP_COL is a bit mask that
+    forces them; bit 1 selects nothing, so "3" is "1"): same operations in the same order, so every output of the step must be identical
+    to the last bit."""
     cfg = named_config("tiny", **kw)
     out = {}
     for mode in ("3", "0", "7", "15"):
@@ -1009,7 +988,7 @@ def test_write_through_device_pointer_is_bitwise_a_set_field(pkg, monkeypatch):
     a.close(); b.close()
 
 
-@pytest.mark.parametrize("wave", ["3", "2", "1", "0"], ids=["wavefront-registers-loads-up-front", "wavefront-registers", "wavefront-lds", "thread-per-sub-block"])
+@pytest.mark.parametrize("wave", ["3", "0"], ids=["wavefront-registers-loads-up-front", "thread-per-sub-block"])
 @pytest.mark.parametrize("name,kw", [("tiny", {}), ("tiny", {"block_size_x": 16, "block_size_y": 20}), ("gx3v7", {}),
                                      ("tiny", {"nx_global": 66, "ny_global": 52, "block_size_x": 33, "block_size_y": 26, "stepped_bathymetry": 1})])
 def test_evp_preconditioner_is_bitwise_the_oracle(pkg, orclib_built, monkeypatch, name, kw, wave):
@@ -1049,10 +1028,10 @@ def test_evp_preconditioner_is_bitwise_the_oracle(pkg, orclib_built, monkeypatch
 ])
 def test_evp_without_reading_land_sub_blocks_is_bitwise(pkg, monkeypatch, name, kw):
     """k_evp_apply_wave3<true> (the solvers' applications: the operand is a residual, zero on land) does not read sub-blocks without an ocean
-    cell and lets waves that hold nothing else leave at once; k_evp_apply_wave2 reads and scales every sub-block.  Iteration counts and
-    fields equal (np.array_equal: a zero is a zero)."""
+    cell and lets waves that hold nothing else leave at once; k_evp_apply (pop_tuning.evp_wave = 0, a thread per sub-block) reads and scales
+    every sub-block.  Iteration counts and fields equal (np.array_equal: a zero is a zero)."""
     cfg = named_config(name, preconditioner_choice=1, **kw)
-    a = pkg.PopModel(cfg, tuning={"evp_wave": 2})
+    a = pkg.PopModel(cfg, tuning={"evp_wave": 0})
     b = pkg.PopModel(cfg, tuning={"evp_wave": 3})
     for step in range(3):
         a.step(); b.step()
@@ -1249,7 +1228,7 @@ def test_fused_pcsi_is_bitwise_the_unfused_pcsi(pkg, monkeypatch, precond):
     """P-CSI: the one-launch-per-iteration form (neighbour updates recomputed in the matvec, ping-pong state,
     hipGraph per check interval) against the operation-by-operation form with explicit halo updates.  With the EVP block
     preconditioner the fused form is two launches per iteration: the step kernel leaves the residual itself, the sub-block solves
-    (k_evp_apply_wave2) turn it into r' for the next step -- no halo update, no copy."""
+    (evp_apply) turn it into r' for the next step -- no halo update, no copy."""
     cfg = named_config("tiny", block_size_x=24, block_size_y=20, solver_choice=3, precond_choice=precond)
     a = pkg.PopModel(cfg)
     monkeypatch.setenv("POP_SOLVER_UNFUSED", "1")
@@ -1311,7 +1290,7 @@ def test_fused_solver_is_bitwise_the_unfused_solver(pkg, monkeypatch, kw):
 ])
 def test_one_launch_pcsi_evp_is_bitwise_the_two_launch_form(pkg, name, kw):
     """pop_tuning.pcsi_evp_fused: a P-CSI iteration with the EVP preconditioner as ONE launch (k_pcsi_evp_step: the wave that solves eight
-    sub-blocks first forms dx, x and r = b - A x for them) against k_pcsi_step2 + k_evp_apply_wave2.  Same expressions in the same order:
+    sub-blocks first forms dx, x and r = b - A x for them) against k_pcsi_step2 + k_evp_apply_wave3.  Same expressions in the same order:
     iteration counts and fields bit for bit."""
     cfg = named_config(name, solver_choice=3, preconditioner_choice=1, **kw)
     grid = synthetic_grid(cfg) if cfg.ns_boundary == 2 else None

@@ -17,8 +17,7 @@ B3  land elimination is invisible with passive tracers
 B5  the 4-D halo update of five tracers; exact restart
 B6  gx1v7, the kernel selection the library makes on its own
 (B4, the tracer counts 6 and 7, is in tests/test_gpu_passive.py; B7, several ranks, in tests/test_gpu_passive_multirank.py.)
-Every comparison is np.array_equal over all cells, except the halo rule on padded blocks (the cells that exist) and the one row of B2
-whose solver sums in another order (red_tiles; the reason stands next to the row)."""
+Every comparison is np.array_equal over all cells, except the halo rule on padded blocks (the cells that exist)."""
 import numpy as np
 import pytest
 
@@ -27,7 +26,6 @@ from popcfg import named_config, synthetic_grid
 from passive_common import (DEL4, KPP, TWINS, TWIN_IDS, TWIN_ROWS, assert_neighbour, assert_twin, make_salinity_twin,
                             passive_field, set_passive, twin_layout, twin_row, twin_start)
 from test_gpu_padded import block_masks
-from test_gpu_parity import TOL_LOCAL, TOL_SOLVE, relerr
 
 pytestmark = pytest.mark.gpu
 NSTEPS = 5
@@ -92,17 +90,16 @@ KM60 = dict(vmix_choice=3, km=60, stepped_bathymetry=1)
 KPP_DEL4 = dict(KPP, **DEL4)
 GM = {"hmix_tracer": 3}
 AT_LEAST_2 = -2
-WIDE_KPP_DEL4 = {"vmix_choice": 3, "hmix_momentum": 4, "hmix_tracer": 4, "am": -1.0e19, "ah": -1.0e18}
 # (configuration, its keywords, pop_tuning fields of model X, pop_get_dim values that show the form in use on X -- "D:" on D -- where the
 # library has one).  pop_get_tuning returns the request, so for the fields without such a value the row was checked against the code: the
-# field alters a launch on the row's configuration.  Where it reads a field: tracer_lds pop_amd.hip:844 / :1570 (4 is the default),
-# vdc_shared :643, side_stream :654, del4_side :660, del4_tile kernels_common.hpp:209 (0 is the default here), d2t_fuse :665, kpp_col
-# kernels_kpp.hpp:1571 (1 is the default here), kpp_src_full pop_amd.hip:1561, kpp_side_stream kernels_kpp.hpp:1519, gm_flux_tile
-# pop_amd.hip:1469 / :1569, gm_sf_stored :597, submeso_all_levels :615, halo_separate launch_halo.hpp:65, xcd_remap / red_tiles :351-352.
+# field alters a launch on the row's configuration.  Where it reads a field: tracer_lds pop_amd.hip:856 / :1602 (4 is the default),
+# vdc_shared :655, side_stream :666, del4_side :672, del4_tile kernels_common.hpp:174 (0 is the default here), d2t_fuse :677, kpp_col
+# kernels_kpp.hpp:1516 (1 is the default here), kpp_src_full pop_amd.hip:1587, kpp_side_stream kernels_kpp.hpp:1467, gm_flux_tile
+# pop_amd.hip:1497 / :1595, gm_sf_stored :609, submeso_all_levels :627, halo_separate launch_halo.hpp:65.
 B2 = ([("tiny", {}, {"tracer_lds": v}, {}) for v in (0, 4, 8)] +
      [("tiny", KM60, {"reg_thomas_t": v}, {"thomas_register_tracers": v}) for v in (0, 1)] +
      # thomas_pair acts at one site only, the (T, S) corrector under pressure averaging (launch_impvmixt<1, ., .>, kernels_thomas_reg.hpp
-     # :298; pop_amd.hip:1760), with the register kernels and one shared diffusivity array (KPP): these two rows run with lpressure_avg = 1,
+     # :291; pop_amd.hip:1786), with the register kernels and one shared diffusivity array (KPP): these two rows run with lpressure_avg = 1,
      # X against D bitwise and P2 / P3 in place of the twin.  0 is also what the size rule chooses on `tiny`; 1 is k_impvmixt2_reg.
      [("tiny", KM60, {"thomas_pair": v}, {"thomas_register_tracers": 1, "pavg": 1}) for v in (0, 1)] +
      [("tiny", KPP, {"vdc_shared": 0}, {}),
@@ -115,24 +112,17 @@ B2 = ([("tiny", {}, {"tracer_lds": v}, {}) for v in (0, 4, 8)] +
       ("tiny", DEL4, {"d2t_fuse": 1, "del4_side": 0}, {"d2t_fused": 0})] +
      [("tiny", KPP, {"kpp_col": v}, {}) for v in (1, 2, 4, 8, 16, 31)] +
      [("tiny", KPP, {"kpp_src_full": 1}, {}),
-      # kpp_sparse is read where the column march runs (kernels_kpp.hpp:1635: sparse = march && ...; march needs bits 3 and 4 of kpp_col,
+      # kpp_sparse is read where the column march runs (kernels_kpp.hpp:1577: sparse = march && ...; march needs bits 3 and 4 of kpp_col,
       # which the size rule leaves off here): the march with the streaming boundary-layer kernel, against the defaults
       ("tiny", KPP, {"kpp_col": 31, "kpp_sparse": 0}, {}),
       ("tiny", KPP, {"kpp_side_stream": 0}, {}),
-      # one block: there the size rule switches the look-ahead on (beside the resident solve, pop_amd.hip:925-927), so D runs it
+      # one block: there the size rule switches the look-ahead on (beside the resident solve, pop_amd.hip:937-939), so D runs it
       ("tiny", dict(KPP, block_size_x=48, block_size_y=40), {"kpp_ahead": 0}, {"kpp_ahead_used": 0, "D:kpp_ahead_used": AT_LEAST_2}),
       ("tiny", KPP, {"kpp_ahead": 1}, {"kpp_ahead_used": AT_LEAST_2}),     # five steps with nothing read in between: twins through the look-ahead
       ("tiny", GM, {"gm_flux_tile": 0}, {}),
       ("tiny", {"hmix_tracer": 3, "ah_bolus": 0.4e7}, {"gm_sf_stored": 0}, {}),
       ("tiny", dict(KPP, hmix_tracer=3, gm_transition_layer=1, stepped_bathymetry=1, submeso=True), {"submeso_all_levels": 1}, {}),
-      ("tiny", KPP_DEL4, {"halo_separate": 1}, {}),
-      # the tile orders of large grids, forced onto the `wide` grid: the column kernels' order alone is bitwise neutral ...
-      ("wide", WIDE_KPP_DEL4, {"xcd_remap": 2}, {}),
-      # ... red_tiles is the one field here that is not: a workgroup of the 2-D reduction kernels then sums a 64 x 4 tile instead of 256
-      # consecutive cells (kernels_common.hpp red_cell, :231-239, against the chunk order of red_chunk, :227-230), so the partials
-      # of the solver's dot products group other cells and round differently -- a deliberately different, equivalent order.  This row
-      # is compared with the default to TOL_LOCAL before the first solve and TOL_SOLVE after it; the twin on X stays bitwise.
-      ("wide", WIDE_KPP_DEL4, {"xcd_remap": 2, "red_tiles": 1}, {})])
+      ("tiny", KPP_DEL4, {"halo_separate": 1}, {})])
 
 
 def _b2_id(row):
@@ -189,20 +179,11 @@ def test_b2_kernel_forms_are_neutral_with_passive_tracers(pkg, orclib_built, row
     else:
         for m in (X, D):
             _own_twins(m)
-    reordered = "red_tiles" in tuning                            # see the row: the solver's sums are formed in another order
-    same = (lambda a, b: relerr(a, b) <= TOL_SOLVE) if reordered else np.array_equal
+    same = np.array_equal
     iters = {0: [], 1: []}
     for s in range(NSTEPS):
-        if reordered and s == 0:                                 # the first step by phases: nothing differs before the first solve
-            for m in (X, D):
-                m.time_manager(); m.dhdt(); m.baroclinic_driver()
-            for n in range(5):
-                assert relerr(X.get("TRACER", 2, n), D.get("TRACER", 2, n)) <= TOL_LOCAL, n
-            for m in (X, D):
-                m.barotropic_driver(); m.baroclinic_correct_adjust(); m.step_tail()
         for i, m in enumerate((X, D)):
-            if not (reordered and s == 0):
-                m.step()
+            m.step()
             iters[i].append(m.solver_diagnostics()[0])
     for d, v in dims.items():
         got = D.dim(d[2:]) if d.startswith("D:") else X.dim(d)

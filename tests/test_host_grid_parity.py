@@ -220,6 +220,21 @@ def test_unsupported_options_are_refused_at_create(pkg, field, value):
     assert "pop_create" in str(e.value)
 
 
+@pytest.mark.parametrize("field,value,allowed", [("evp_wave", 1, ("0", "3")), ("evp_wave", 2, ("0", "3")), ("xcd_remap", 2, ("0", "1"))])
+def test_tuning_values_without_a_kernel_form_are_refused_at_create(pkg, field, value, allowed):
+    """pop_tuning.evp_wave keeps 0 and 3, pop_tuning.xcd_remap 0 and 1: any other value fails in pop_create (host-only contexts included)
+    with a message that names the field, the value and the allowed values; the allowed values themselves are taken"""
+    cfg = named_config("tiny", solver_choice=3, precond_choice=1)
+    with pytest.raises(pkg.PopError) as e:
+        pkg.PopModel(cfg, host_only=True, tuning={field: value})
+    msg = str(e.value)
+    assert "pop_create" in msg and "pop_tuning.%s is %d" % (field, value) in msg
+    said = msg[msg.index(" is %d" % value) + len(" is %d" % value):]
+    assert all(a in said.replace(",", " ").replace(":", " ").split() for a in allowed), msg
+    for ok in allowed:
+        pkg.PopModel(cfg, host_only=True, tuning={field: int(ok)}).close()
+
+
 @pytest.mark.parametrize("kw", [{"block_size_x": 20, "block_size_y": 16, "solver_choice": 3}, {"block_size_x": 28, "block_size_y": 24, "solver_choice": 3, "precond_choice": 1},
                                 {"block_size_x": 20, "block_size_y": 16, "ns_boundary": 2, "solver_choice": 3, "precond_choice": 1}])
 def test_padded_blocks_solver_set_up_bit_exact(pkg, orclib_built, kw):
