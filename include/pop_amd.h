@@ -159,9 +159,11 @@ typedef struct pop_ctx pop_ctx;
 /* ---- tuning: kernel-form and schedule choices.  NONE changes a result: every alternative is tested bitwise equal to the
  *      default (tests/test_gpu_parity.py, test_gpu_land.py, test_gpu_land_schemes.py, test_gpu_passive_matrix.py,
  *      test_gpu_multirank.py); they exist for measurement and for those
- *      tests.  Resolved ONCE, at pop_create*: the library's size rules, overridden by the caller's pop_tuning (fields left at
- *      POP_TUNING_UNSET keep the rule), overridden by the environment variable POP_<FIELD NAME IN UPPER CASE> (read at create
- *      only; nothing in the step reads the environment).  pop_get_tuning returns what was resolved. ---------------------- */
+ *      tests.  Resolved ONCE, at pop_create*, into one plan (csrc/forms.hpp resolve_forms): the library's size rules, overridden by
+ *      the caller's pop_tuning (fields left at POP_TUNING_UNSET keep the rule), overridden by the environment variable
+ *      POP_<FIELD NAME IN UPPER CASE> (read at create only; nothing in the step reads the environment or the request).
+ *      pop_get_tuning returns the REQUEST (struct and environment merged; POP_TUNING_UNSET = the rule applied);
+ *      pop_get_dim("form_<entry of the plan>") returns the OUTCOME, on host-only contexts too. ---------------------- */
 #define POP_TUNING_UNSET (-2147483647 - 1)
 typedef struct pop_tuning {
   int struct_bytes;        /* sizeof(pop_tuning) of the caller */
@@ -210,7 +212,6 @@ typedef struct pop_tuning {
   int kpp_sparse;          /* 0: KPP boundary-layer kernel streams every level even when the interior kernel formed the convection mask */
   int pbc_generic_thomas;  /* 1: partial bottom cells with the scratch-staged Thomas kernels even at km = 60 / 62 */
   int pbc_generic_kpp;     /* 1: partial bottom cells with the 3-D-parallel / scratch-staged KPP kernels on large grids too */
-  int stream_priority;     /* 1: the launch stream above the gap-filling side streams (default 0: measured slower) */
   int gm_sf_stored;        /* 0: Gent-McWilliams without cancellation: the stream-function terms SF_SLX / SF_SLY re-derived in the flux kernel instead of stored */
   int state3d_levels;      /* density of a whole 3-D array: levels per thread, 4 (default) | 2 | 8 with the per-level EOS coefficients read from
                             * a table, 1 = one cell per thread with the coefficients formed in place */
@@ -223,16 +224,13 @@ typedef struct pop_tuning {
   int block_sums_relay;    /* ordered block sums of more than 64 x 256 chunk partials (the fused pcg / ChronGear of large grids): 0 = 256 threads, each adding
                             * its accumulator's terms in batches (two or three memory round trips); default 1 = 1024 threads, four per accumulator, every term
                             * requested at once and the quarters added in turn (k_block_sums_relay: the same additions in the same order); 2 = also below 64 terms (cross-check) */
-  int pcsi_evp_fused;      /* fused P-CSI with the EVP preconditioner: 1 = the iteration (dx, x, r = b - A x) and the sub-block solves r' = M^-1 r in ONE
-                            * launch (k_pcsi_evp_step; bitwise, but measured slower: its loads are issued by the few waves of the sub-block solve);
-                            * default 0 = two launches per iteration (k_pcsi_step2, k_evp_apply_wave3); not with evp_wave = 0 */
   int aniso_side;          /* hmix_momentum = 3: 0 = the friction k_hdiffu_aniso in line before the momentum right-hand side; default 1 = on the
                             * side stream beside the vertical-mixing coefficients (it reads only the mix-time U, V and fixed coefficients) */
   int submeso_all_levels;  /* lsubmesoscale_mixing: 1 = k_submeso_flux marches all km levels; default 0 = every tile stops at the last level that
                             * can hold a non-zero tendency (from the largest mixed-layer depth over the tile and a one-cell rim); bitwise equal */
 } pop_tuning;
 void pop_tuning_init(pop_tuning *t);   /* struct_bytes = sizeof, every field POP_TUNING_UNSET */
-int pop_get_tuning(const pop_ctx *ctx, pop_tuning *resolved);   /* fields still POP_TUNING_UNSET: the size rule applied */
+int pop_get_tuning(const pop_ctx *ctx, pop_tuning *resolved);   /* the request; fields still POP_TUNING_UNSET: the size rule applied */
 
 /* ---- lifecycle (no reference counterpart: the reference's state is module
  *      global, initial.F90:133-699 builds it) -------------------------------- */

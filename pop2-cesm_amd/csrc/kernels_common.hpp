@@ -1,6 +1,7 @@
 // kernels_common.hpp -- shared device helpers: MWJF equation of state, column indexing.
 #pragma once
 #include "device_types.hpp"
+#include "forms.hpp"
 #include <type_traits>
 
 namespace pop {
@@ -169,20 +170,14 @@ __device__ __forceinline__ bool patch_cell(const DevGrid &g, int tile, int b, in
   p2 = j * g.nxb + i;
   return true;
 }
-// bandwidth-bound grids: 64 x 4 patches (tx0.1v3: -0.5 ms per step); pop_tuning.del4_tile = 0 | 2 | 4 | 8 | 16 overrides
-__host__ inline int patch_rows(const DevGrid &g, int tile_tuning) {
-  if (tun_set(tile_tuning)) { const int r = tile_tuning; return (r == 2 || r == 4 || r == 8 || r == 16) ? r : 0; }
-  return ((long long)g.n2 * g.nblocks > (1 << 19)) ? 4 : 0;
-}
+// tile: the patch rows of the plan (Forms::del4_tile_rows)
 __host__ inline unsigned patch_grid_x(const DevGrid &g, int tile) {
   return tile ? (unsigned)(((g.nxb + 63) / 64) * ((g.nyb + tile - 1) / tile)) : (unsigned)((g.n2 + 255) / 256);
 }
 // 2-D reduction kernels (POP_RED_THREADS = 256 threads, one partial per workgroup): cell of this thread,
 // or g.n2 (not a cell) for surplus threads.
 __host__ inline int red_grid_x(const DevGrid &g) {
-  if (g.red_act) return g.red_nact;
-  const int nc = (g.n2 + 255) / 256;
-  return g.red_band ? 8 * ((nc + 7) / 8) : nc;
+  return g.red_act ? g.red_nact : chunks_per_block(g.n2, g.red_band);
 }
 // chunk (= partial slot) of this workgroup.  red_band: XCD x takes one contiguous band of chunks, so the rows
 // j+-1 of a 9-point stencil were touched by the same XCD a few workgroups earlier; the chunk -> cells map and the

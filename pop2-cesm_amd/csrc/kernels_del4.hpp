@@ -90,17 +90,16 @@ __global__ void k_del4_d2u(DevGrid g, const double *__restrict__ AMF, const doub
 
 inline int del4_create(HostModel &, const DevGrid &, MixDev &, std::vector<void *> &, std::string &) { return 0; }
 
-inline int mix_hdifft_del4(const HostModel &h, const DevGrid &g, const StepParams &, const MixDev &m, const double *T0, const double *T1,
+// tile: the patch rows of the plan (Forms::del4_tile_rows)
+inline int mix_hdifft_del4(int tile, const DevGrid &g, const StepParams &, const MixDev &m, const double *T0, const double *T1,
                            double *D0, double *D1, double *, double *, hipStream_t st, std::string &err) {
-  const int tile = patch_rows(g, h.tun.del4_tile);
   const dim3 G(patch_grid_x(g, tile), (g.km + POP_DEL4_KC - 1) / POP_DEL4_KC, g.nblocks), B(tile ? 64 * tile : 256);
   with_flags([&](auto PBC) { hipLaunchKernelGGL(k_del4_d2t<PBC.value>, G, B, 0, st, g, m.D4AHF, T0, T1, D0, D1, tile); }, g.pbc);
   if (hipGetLastError() != hipSuccess) { err = "del4 tracer kernel launch failed"; return 1; }
   return 0;
 }
-inline int mix_hdiffu_del4(const HostModel &h, const DevGrid &g, const StepParams &, const MixDev &m, const double *U, const double *V,
+inline int mix_hdiffu_del4(int tile, const DevGrid &g, const StepParams &, const MixDev &m, const double *U, const double *V,
                            double *DU, double *DV, double *, double *, hipStream_t st, std::string &err) {
-  const int tile = patch_rows(g, h.tun.del4_tile);
   const dim3 G(patch_grid_x(g, tile), (g.km + POP_DEL4_KC - 1) / POP_DEL4_KC, g.nblocks), B(tile ? 64 * tile : 256);
   with_flags([&](auto PBC) { hipLaunchKernelGGL(k_del4_d2u<PBC.value>, G, B, 0, st, g, m.D4AMF, U, V, DU, DV, tile); }, g.pbc);
   if (hipGetLastError() != hipSuccess) { err = "del4 momentum kernel launch failed"; return 1; }

@@ -57,7 +57,7 @@ struct KppDev {
   double *SRCX = nullptr;
 };
 
-constexpr double KPP_EPSSFC = 0.1, KPP_RIINFTY = 0.8, KPP_RRHO0 = 2.55, KPP_DSFMAX = 1.0, KPP_CSTAR = 10.0;
+constexpr double KPP_RIINFTY = 0.8, KPP_RRHO0 = 2.55, KPP_DSFMAX = 1.0, KPP_CSTAR = 10.0;
 constexpr double KPP_ZETA_M = -0.2, KPP_ZETA_S = -1.0, KPP_C_M = 8.38, KPP_C_S = 98.96, KPP_A_M = 1.26, KPP_A_S = -28.86;
 constexpr double KPP_CONCV = 1.7, KPP_VONKAR = 0.4, KPP_EPS = 1.0e-10, KPP_EPS2 = 1.0e-20, KPP_RICR = 0.3;
 
@@ -1326,17 +1326,16 @@ __global__ void k_kpp_vvc(DevGrid g, const double *__restrict__ VISC, double *__
   }
 }
 
-// VVC from VISC in 64 x R patches on bandwidth-bound grids (a row-marching form that fetches every VISC value once was measured slower:
+// VVC from VISC in 64 x vp patches (vp: Forms::del4_tile_rows; a row-marching form that fetches every VISC value once was measured slower:
 // profiles/r04_ab_kpp_vvc_rows.txt)
-inline void launch_kpp_vvc(const DevGrid &g, const HostModel &h, hipStream_t st, const double *VISC, double *VVC) {
-  const int vp = patch_rows(g, h.tun.del4_tile);
+inline void launch_kpp_vvc(const DevGrid &g, int vp, hipStream_t st, const double *VISC, double *VVC) {
   hipLaunchKernelGGL(k_kpp_vvc, dim3(patch_grid_x(g, vp), (g.km + POP_VVC_KC - 1) / POP_VVC_KC, g.nblocks), dim3(vp ? 64 * vp : 256), 0, st, g, VISC, VVC, vp);
 }
 
 // ---- host side ---------------------------------------------------------------------------------
 // per-context KPP state (MixDev::kpp)
-// col: the mask of kernel forms (pop_tuning.kpp_col).  side / ev_*: second HIP stream on which the shear kernel (needs only
-// U, V; consumed by bldepth) runs beside buoydiff + interior (POP_KPP_SIDE_STREAM=0 keeps everything on one stream)
+// side / ev_*: second HIP stream on which the shear kernel (needs only U, V; consumed by bldepth) runs beside buoydiff + interior
+// (created where the plan says so: Forms::kpp_side)
 // tidal: set by pop_init_tidal_mixing (tidal_on); bck: set by pop_init_kpp_bckgrnd (bck_on); zero_bck = km + 3 words of 0, the
 // background the interior kernels see with either
 struct KppHost {
@@ -1346,8 +1345,6 @@ struct KppHost {
   bool bck_on = false;
   const double *zero_bck = nullptr;
   KppDev dev;
-  int max_kref = 1;
-  int col = 0;
   int *wuk = nullptr;
   unsigned long long *convb = nullptr;
   hipStream_t side = nullptr;
@@ -1439,23 +1436,20 @@ inline int sw_tables_create(HostModel &h, std::vector<void *> &allocs, std::stri
   }
   return 0;
 }
-inline int kpp_create(HostModel &h, const DevGrid &g, MixDev &m, std::vector<void *> &allocs, std::string &err) {
+inline int kpp_create(HostModel &h, const Forms &f, const DevGrid &g, MixDev &m, std::vector<void *> &allocs, std::string &err) {
   const pop_config &c = h.c;
   if (c.lshort_wave && (c.sw_absorption_type < 0 || c.sw_absorption_type > 2)) { err = "KPP: sw_absorption_type: 0 top-layer, 1 jerlov, 2 chlorophyll"; return 1; }
   if (c.jerlov_water_type < 0 || c.jerlov_water_type > 5) { err = "KPP: jerlov_water_type: 1..5 (0 = 3)"; return 1; }
   if (c.num_v_smooth_Ri < 1) { err = "KPP: num_v_smooth_Ri must be >= 1 (the reference leaves FRI unset otherwise)"; return 1; }
   const int km = h.km;
   std::vector<double> zgrid(km + 3, 0.0), hwide(km + 3, 0.0), bvdc(km + 3, 0.0), bvvc(km + 3, 0.0);
-  std::vector<int> kref(km + 3, 1);
+  const std::vector<int> kref = kpp_kref(h);
   zgrid[0] = KPP_EPS; hwide[0] = KPP_EPS;
   for (int k = 1; k <= km; ++k) { zgrid[k] = -h.zt[k]; hwide[k] = h.dz[k]; }
   zgrid[km + 1] = -h.zw[km]; hwide[km + 1] = KPP_EPS;
   for (int k = 1; k <= km; ++k) {
     bvdc[k] = c.bckgrnd_vdc1 + c.bckgrnd_vdc2 * std::atan(c.bckgrnd_vdc_linv * (h.zw[k] - c.bckgrnd_vdc_dpth));
     bvvc[k] = c.Prandtl * bvdc[k];
-    const double surfthick = KPP_EPSSFC * h.zt[k];
-    kref[k] = k;
-    for (int kt = 1; kt <= k; ++kt) if (h.zw[kt] >= surfthick) { kref[k] = kt; break; }
   }
   auto up = [&](const void *src, size_t bytes, void **dst) -> int {
     if (hipMalloc(dst, bytes) != hipSuccess) return 1;
@@ -1464,7 +1458,7 @@ inline int kpp_create(HostModel &h, const DevGrid &g, MixDev &m, std::vector<voi
   };
   KppHost *K = new KppHost();
   m.kpp = K;
-  if (!tun_off(h.tun.kpp_side_stream)) {
+  if (f.kpp_side) {
     if (hipStreamCreateWithFlags(&K->side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&K->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&K->ev_join, hipEventDisableTiming) != hipSuccess ||
@@ -1508,20 +1502,13 @@ inline int kpp_create(HostModel &h, const DevGrid &g, MixDev &m, std::vector<voi
     if (sw_tables_create(h, allocs, err)) return 1;
     k.ztr = h.sw.ztr; k.Tr = h.sw.Tr; k.ksol = h.sw.ksol; k.CHLI = h.sw.CHLI;
   }
-  K->max_kref = 1;
-  for (int kk = 1; kk <= km; ++kk) K->max_kref = std::max(K->max_kref, kref[kk]);
-  // column (register) forms: bandwidth-bound grids only -- below ~2^19 columns the 3-D-parallel forms win on
-  // parallelism.  Measured at tx0.1v3: ushear 11.2 -> 2.7 ms.  POP_KPP_COL = bit mask overrides.
-  K->col = (K->max_kref <= 24) ? ((h.n2 * h.nblocks > (1u << 19)) ? 31 : 1) : 0;   // ushear: column form at every size (gx1v7 vmix 0.716 -> 0.692 ms)
-  if (tun_set(h.tun.kpp_col)) K->col = (K->max_kref <= 24) ? h.tun.kpp_col : 0;   // bit 0 ushear column form, bit 1 unused, bit 2 buoydiff LDS form, bit 3 buoydiff + interior fused, bit 4 as one column march
-  (void)m;
   return 0;
 }
 
 // KBL of the last evaluation (the tracer kernel reads KPP_SRC down to it only)
 inline const int *mix_kpp_kbl(const MixDev &m) { return m.kpp ? ((const KppHost *)m.kpp)->dev.KBL : nullptr; }
 
-inline int kpp_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParams &sp, const MixDev &m, const MixState &s,
+inline int kpp_vmix_coeffs(const HostModel &h, const Forms &f, const DevGrid &g, const StepParams &sp, const MixDev &m, const MixState &s,
                            hipStream_t st, std::string &err) {
   const KppHost &KH = *(const KppHost *)m.kpp;
   KppDev g_kpp = KH.dev;
@@ -1532,57 +1519,26 @@ inline int kpp_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParam
   // background and the tidal diffusivity (kernels_tidal.hpp)
   // lhoriz_varying_bckgrnd: the same, and k_kpp_bckgrnd (kernels_bckgrnd.hpp) or k_kpp_tidal<PBC, true> adds the column's background
   if (KH.tidal_on || KH.bck_on) { g_kpp.bckgrnd_vdc = KH.zero_bck; g_kpp.bckgrnd_vvc = KH.zero_bck; }
-  const int g_kpp_col = KH.col;
   const dim3 GC(col_grid(g, POP_COL_THREADS), g.nblocks), BC(POP_COL_THREADS);
   const dim3 G3((g.n2 + 255) / 256, g.km, g.nblocks);
   double *DBLOC = s.S3a, *DBSFC = s.S3b, *WU = s.S3c, *VISC = s.S3d, *RIW = s.E3;
   // level-parallel LDS form (bit 2 of the mask; the default on bandwidth-bound grids)
   const dim3 GL(col_grid_x(g.n2, POP_COL_THREADS), g.nblocks), BL(POP_COL_THREADS, 4);
 
-  // ---- selection: which form of every stage runs (no launch above the pipeline below)
-  // bit 3: buoydiff and the interior coefficients in ONE level-parallel launch
-  const bool fused_bi = (g_kpp_col & 8) && KH.max_kref <= 20 && g.km <= 64;
-  const bool lds = (g_kpp_col & 4) && KH.max_kref <= 28;
-  // the surface-layer buoyancy difference on demand inside the boundary-layer-depth march (k_kpp_bldepth<true, .>); POP_KPP_LAZY=0 keeps
-  // the full field
-  // (with the level-parallel fused kernel and with the plain 3-D buoydiff kernel; the LDS buoydiff form keeps the full field)
-  const bool plain3d = !fused_bi && !lds;
-  const bool lazy = (fused_bi || plain3d) && KH.max_kref <= 28 && !g_kpp.lcheckekmo && h.c.kpp_ml_diagnostics != 1 &&
-                    !tun_off(h.tun.kpp_lazy);
-  const bool lazy20 = lazy && KH.max_kref <= 20;
-  // bit 4: buoydiff + interior coefficients as one column march (one smoothing pass, no double diffusion)
-  const bool march = lazy && fused_bi && (g_kpp_col & 16) && g_kpp.nsmooth == 1 && !g_kpp.ldbl_diff && g.km >= 3;
-  // partial bottom cells: the PBC instantiations of the production (column-march) selection where it applies (r3), else the
-  // 3-D-parallel / scratch-staged forms, which carry the PBC branches: every level of the surface-layer buoyancy difference and
-  // of the shear formed (no on-demand march), one stream, no sparse mask
-  const bool pbc_generic = g.pbc && !(march && lazy20 && (g_kpp_col & 1) && !tun_on(h.tun.pbc_generic_kpp));
+  // ---- selection: which form of every stage runs (no launch above the pipeline below): the plan's (forms.hpp), plus what only this
+  // call knows -- vdc_same, src_clear_all and the tidal / background flags
   struct Sel {
     bool shear_col;                                          // k_kpp_ushear_col<24, PBC>, else k_kpp_ushear<PBC>
-    enum { MARCH, FUSED_LDS, LDS, PLAIN } buoy;         // MARCH and FUSED_LDS form the interior coefficients too
+    int buoy;                                                // KPP_BUOY_*
     int buoy_kr; bool buoy_sfc;                              // <KR> of the LDS form, <SFC> of the fused / plain ones
     bool depth_lazy; int depth_kr;                           // k_kpp_bldepth<LAZY, KR, PBC>
-    enum { FUSED, REG, GENERIC } interior;
+    int interior;                                            // KPP_INTERIOR_*
     bool same, sparse;                                       // k_kpp_blmix<PBC, SAME, SPARSE>
     bool side, wuk, convb;                                   // the side stream used; KppDev::WUK / CONVB set
-  } sel;
-  sel.shear_col = !pbc_generic && (g_kpp_col & 1);
-  sel.buoy = pbc_generic ? Sel::PLAIN : march ? Sel::MARCH : fused_bi ? Sel::FUSED_LDS : lds ? Sel::LDS : Sel::PLAIN;
-  sel.buoy_kr = KH.max_kref <= 20 ? 20 : 28;
-  sel.buoy_sfc = pbc_generic || !lazy;
-  sel.depth_lazy = !pbc_generic && lazy;
-  sel.depth_kr = (sel.depth_lazy && !lazy20) ? 28 : 20;
-  sel.interior = pbc_generic ? Sel::GENERIC : fused_bi ? Sel::FUSED :
-                 (!tun_on(h.tun.kpp_interior_generic) && (g.km == 60 || g.km == 62)) ? Sel::REG : Sel::GENERIC;
-  sel.same = g_kpp.vdc_same;
-  sel.convb = sel.sparse = !pbc_generic && march && g.km <= 64 && !tun_off(h.tun.kpp_sparse);
-  // the shear of the velocity against its surface-layer reference needs only U and V: on the side stream it overlaps the
-  // (VALU-bound) buoydiff and the interior kernel; bldepth waits for it
-  sel.side = KH.side && !pbc_generic;
-  // shear kernel limited by the previous evaluation's KBL (k_kpp_ushear_col): only with the on-demand march, which can form a level
-  // that is missing itself (POP_KPP_USHEAR_HINT=0: every level; POP_KPP_USHEAR_MARGIN: levels beyond the hint, default 3)
-  sel.wuk = sel.depth_lazy && (g_kpp_col & 1) && !tun_off(h.tun.kpp_ushear_hint);
+  } sel{f.kpp_shear_col, f.kpp_buoy, f.kpp_buoy_kr, f.kpp_buoy_sfc, f.kpp_depth_lazy, f.kpp_depth_kr, f.kpp_interior,
+        g_kpp.vdc_same != 0, f.kpp_sparse, f.kpp_side, f.kpp_wuk, f.kpp_sparse};
   g_kpp.WUK = sel.wuk ? KH.wuk : nullptr;
-  if (sel.wuk && tun_set(h.tun.kpp_ushear_margin)) g_kpp.wu_margin = h.tun.kpp_ushear_margin;
+  g_kpp.wu_margin = f.kpp_wuk_margin;
   g_kpp.CONVB = sel.convb ? KH.convb : nullptr;
   g_kpp.src_clear_all = s.src_clear_all;
   g_kpp.SRCX = s.KPP_SRCX;
@@ -1595,9 +1551,9 @@ inline int kpp_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParam
     else hipLaunchKernelGGL(k_kpp_ushear<PBC.value>, G3, dim3(256), 0, su, g, g_kpp, s.UMIX, s.VMIX, WU);
   }, sel.shear_col, g.pbc);
   const auto T0 = s.TMIX[0], T1 = s.TMIX[1];
-  if (sel.buoy == Sel::MARCH) with_flags([&](auto PBC) { hipLaunchKernelGGL(k_kpp_buoy_interior_march<PBC.value>, GC, BC, 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, DBLOC, VISC, s.VDC[0], s.VDC[1]); }, g.pbc);
-  else if (sel.buoy == Sel::FUSED_LDS) with_flags([&](auto SFC) { hipLaunchKernelGGL((k_kpp_buoy_interior_lds<20, 8, SFC.value>), GL, dim3(POP_COL_THREADS, 8), 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, DBLOC, DBSFC, VISC, s.VDC[0], s.VDC[1]); }, sel.buoy_sfc);
-  else if (sel.buoy == Sel::LDS) with_value<20, 28>(sel.buoy_kr, [&](auto KR) { hipLaunchKernelGGL((k_kpp_buoydiff_lds<KR.value, 4>), GL, BL, 0, st, g, g_kpp, T0, T1, DBLOC, DBSFC); });
+  if (sel.buoy == KPP_BUOY_MARCH) with_flags([&](auto PBC) { hipLaunchKernelGGL(k_kpp_buoy_interior_march<PBC.value>, GC, BC, 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, DBLOC, VISC, s.VDC[0], s.VDC[1]); }, g.pbc);
+  else if (sel.buoy == KPP_BUOY_FUSED_LDS) with_flags([&](auto SFC) { hipLaunchKernelGGL((k_kpp_buoy_interior_lds<20, 8, SFC.value>), GL, dim3(POP_COL_THREADS, 8), 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, DBLOC, DBSFC, VISC, s.VDC[0], s.VDC[1]); }, sel.buoy_sfc);
+  else if (sel.buoy == KPP_BUOY_LDS) with_value<20, 28>(sel.buoy_kr, [&](auto KR) { hipLaunchKernelGGL((k_kpp_buoydiff_lds<KR.value, 4>), GL, BL, 0, st, g, g_kpp, T0, T1, DBLOC, DBSFC); });
   else with_flags([&](auto SFC) { hipLaunchKernelGGL(k_kpp_buoydiff<SFC.value>, G3, dim3(256), 0, st, g, g_kpp, T0, T1, DBLOC, DBSFC); }, sel.buoy_sfc);
   // the boundary-layer depth (needs buoydiff + shear, writes only the 2-D boundary-layer fields) follows the shear kernel
   // on the side stream and runs beside the interior coefficients; blmix waits for both.  Without the side stream it follows
@@ -1613,8 +1569,8 @@ inline int kpp_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParam
     depth(side);
     hipEventRecord(KH.ev_join, side);
   }
-  if (sel.interior == Sel::REG) with_value<60, 62>(g.km, [&](auto KM) { hipLaunchKernelGGL(k_kpp_interior_reg<KM.value>, GC, BC, 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, (const double *)DBLOC, VISC, s.VDC[0], s.VDC[1]); });
-  else if (sel.interior == Sel::GENERIC) with_flags([&](auto PBC) { hipLaunchKernelGGL(k_kpp_interior<PBC.value>, GC, BC, 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, (const double *)DBLOC, RIW, VISC, s.VDC[0], s.VDC[1]); }, g.pbc);
+  if (sel.interior == KPP_INTERIOR_REG) with_value<60, 62>(g.km, [&](auto KM) { hipLaunchKernelGGL(k_kpp_interior_reg<KM.value>, GC, BC, 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, (const double *)DBLOC, VISC, s.VDC[0], s.VDC[1]); });
+  else if (sel.interior == KPP_INTERIOR_GENERIC) with_flags([&](auto PBC) { hipLaunchKernelGGL(k_kpp_interior<PBC.value>, GC, BC, 0, st, g, g_kpp, T0, T1, s.UMIX, s.VMIX, (const double *)DBLOC, RIW, VISC, s.VDC[0], s.VDC[1]); }, g.pbc);
   // DBLOC and the interior coefficients of every level are complete on st here in every form (the on-demand forms leave levels of
   // DBSFC and WU unwritten, never of DBLOC), and nothing before k_kpp_blmix reads VISC / VDC
   // (the same two conditions hold for k_kpp_bckgrnd, which reads VISC / VDC of the levels k < KMT only: DESIGN.md section 11)
@@ -1628,8 +1584,7 @@ inline int kpp_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParam
   with_flags([&](auto PBC, auto SAME, auto SPARSE, auto XS) {
     hipLaunchKernelGGL((k_kpp_blmix<PBC.value, SAME.value, SPARSE.value, XS.value>), GC, BC, 0, st, g, sp, g_kpp, (const double *)DBLOC, s.STF[0], s.STF[1], VISC, s.VDC[0], s.VDC[1], s.KPP_SRC[0], s.KPP_SRC[1], s.HBLT);
   }, g.pbc, sel.same, sel.sparse, g_kpp.SRCX != nullptr);
-  // large grids: 64 x 4 patches (the row j + 1 of the four-point average is read by the same workgroup; 64 x 2 / 8 / 16 measured: vmix 7.54 / 7.65 / 7.97 ms against 7.57)
-  launch_kpp_vvc(g, h, st, (const double *)VISC, s.VVC);
+  launch_kpp_vvc(g, f.del4_tile_rows, st, (const double *)VISC, s.VVC);
   if (h.c.kpp_ml_diagnostics == 1 && s.HMXL && s.HMXL_DR)   // DBSFC holds every level here (the diagnostics switch the on-demand march off)
     hipLaunchKernelGGL(k_kpp_hmxl, GC, BC, 0, st, g, g_kpp, T0, T1, (const double *)DBSFC, s.HMXL, s.HMXL_DR);
   if (hipGetLastError() != hipSuccess) { err = "KPP kernel launch failed"; return 1; }

@@ -123,12 +123,12 @@ inline int mix_state_host(const HostModel &h, const DevGrid &g, int kk, const do
 
 namespace pop {
 
-inline int mix_create(HostModel &h, const DevGrid &g, MixDev &m, std::vector<void *> &allocs, std::string &err) {
+inline int mix_create(HostModel &h, const Forms &f, const DevGrid &g, MixDev &m, std::vector<void *> &allocs, std::string &err) {
   if ((h.c.hmix_momentum == 4 || h.c.hmix_tracer == 4) && del4_create(h, g, m, allocs, err)) return 1;
-  if (h.c.vmix_choice == 3 && kpp_create(h, g, m, allocs, err)) return 1;
+  if (h.c.vmix_choice == 3 && kpp_create(h, f, g, m, allocs, err)) return 1;
   return 0;
 }
-inline int mix_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParams &sp, const MixDev &m, const MixState &s,
+inline int mix_vmix_coeffs(const HostModel &h, const Forms &f, const DevGrid &g, const StepParams &sp, const MixDev &m, const MixState &s,
                            hipStream_t st, std::string &err) {
   const dim3 G3((g.n2 + 255) / 256, g.km, g.nblocks);
   if (h.c.vmix_choice == 2) {
@@ -136,7 +136,7 @@ inline int mix_vmix_coeffs(const HostModel &h, const DevGrid &g, const StepParam
     hipLaunchKernelGGL(k_rich_u, G3, dim3(256), 0, st, g, sp, s, (const double *)s.S3c);
     return 0;
   }
-  if (h.c.vmix_choice == 3) return kpp_vmix_coeffs(h, g, sp, m, s, st, err);
+  if (h.c.vmix_choice == 3) return kpp_vmix_coeffs(h, f, g, sp, m, s, st, err);
   err = "unknown vmix_choice";
   return 1;
 }

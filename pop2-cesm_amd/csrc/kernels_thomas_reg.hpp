@@ -285,18 +285,13 @@ k_impvmixu_reg(DevGrid g, StepParams sp, ImpvmixuArgs a) {
   for (int k = 1; k <= KM; ++k) XN[c.base3 + (long long)(k - 1) * n2] = Xa[k - 1];
 }
 
-// dispatch on the level count: register kernels for the production grids (km = 60 / 62, with or without partial bottom cells),
-// the generic (scratch-staged) kernel otherwise
+// reg: the register kernels of the production level counts (Forms::reg_thomas_t, with or without partial bottom cells), else the generic
+// (scratch-staged) kernel; pair_form: both tracers in one thread (Forms::thomas_pair) where this launch has two that share the diffusivity array
 template <int MODE, bool PRE, bool POST>
-inline void launch_impvmixt(const DevGrid &g, const StepParams &sp, const ImpvmixtArgs &a, dim3 G, hipStream_t st, bool allow_reg, int pair_tuning) {
+inline void launch_impvmixt(const DevGrid &g, const StepParams &sp, const ImpvmixtArgs &a, dim3 G, hipStream_t st, bool reg, bool pair_form) {
   const dim3 B(POP_COL_THREADS);
   const dim3 G2(G.x, G.y, a.nlast - a.nfirst + 1);
-  const bool reg = allow_reg && (g.km == 60 || g.km == 62);
-  // both tracers in one thread when they share the diffusivity array (pop_tuning.thomas_pair = 0 | 1 overrides the size rule)
-  // (corrector form only: the predictor's three full register columns + its up-front loads spill ~ 900 B per lane)
-  const int pair_env = tun_or(pair_tuning, -1);
-  const bool pair = MODE == 1 && reg && a.nfirst == 1 && a.nlast == 2 && a.VDC[0] == a.VDC[1] &&
-                    (pair_env >= 0 ? pair_env != 0 : (long long)g.n2 * g.nblocks > (1 << 19));
+  const bool pair = MODE == 1 && reg && pair_form && a.nfirst == 1 && a.nlast == 2 && a.VDC[0] == a.VDC[1];
   with_flags([&](auto PBC) {
     if (!reg) { hipLaunchKernelGGL((k_impvmixt<MODE, PRE, POST, PBC.value>), G, B, 0, st, g, sp, a); return; }
     with_value<60, 62>(g.km, [&](auto KM) {
@@ -309,25 +304,23 @@ inline void launch_impvmixt(const DevGrid &g, const StepParams &sp, const Impvmi
     if (POST) launch_state3d(g, a.TNEW[0], a.TNEW[1], a.RHO, st);
   }, g.pbc);
 }
-// the register kernel of the velocity solve, km = 60 / 62 only (false otherwise, nothing launched).  WAVES = 2 on small grids, never
-// with partial bottom cells.  ADD: with the barotropic velocity added on the way out (a.UB, a.VB set)
+// the register kernel of the velocity solve (Forms::reg_thomas_u).  waves: per workgroup (Forms::impvmixu_waves; 2 never with partial
+// bottom cells).  ADD: with the barotropic velocity added on the way out (a.UB, a.VB set)
 template <bool ADD>
-inline bool launch_impvmixu_reg(const DevGrid &g, const StepParams &sp, const ImpvmixuArgs &a, dim3 G, hipStream_t st) {
-  const bool two = !g.pbc && (long long)g.n2 * g.nblocks <= (1 << 19);
-  return with_value<60, 62>(g.km, [&](auto KM) {
+inline void launch_impvmixu_reg(const DevGrid &g, const StepParams &sp, const ImpvmixuArgs &a, dim3 G, hipStream_t st, int waves) {
+  with_value<60, 62>(g.km, [&](auto KM) {
     with_flags([&](auto TWO, auto PBC) {
       if constexpr (!(TWO.value && PBC.value))
         hipLaunchKernelGGL((k_impvmixu_reg<KM.value, TWO.value ? 2 : 1, ADD, PBC.value>), dim3(G.x, G.y, 2), dim3(POP_COL_THREADS), 0, st, g, sp, a);
-    }, two, g.pbc);
+    }, waves == 2, g.pbc);
   });
 }
-inline void launch_impvmixu(const DevGrid &g, const StepParams &sp, const ImpvmixuArgs &a, dim3 G, hipStream_t st, bool allow_reg) {
-  if (allow_reg && launch_impvmixu_reg<false>(g, sp, a, G, st)) return;
+inline void launch_impvmixu(const DevGrid &g, const StepParams &sp, const ImpvmixuArgs &a, dim3 G, hipStream_t st, bool reg, int waves) {
+  if (reg) { launch_impvmixu_reg<false>(g, sp, a, G, st, waves); return; }
   with_flags([&](auto PBC) { hipLaunchKernelGGL(k_impvmixu_norm<PBC.value>, G, dim3(POP_COL_THREADS), 0, st, g, sp, a); }, g.pbc);
 }
-inline bool impvmixu_add_available(const DevGrid &g, bool allow_reg) { return allow_reg && (g.km == 60 || g.km == 62); }
-inline void launch_impvmixu_add(const DevGrid &g, const StepParams &sp, const ImpvmixuArgs &a, dim3 G, hipStream_t st) {
-  launch_impvmixu_reg<true>(g, sp, a, G, st);
+inline void launch_impvmixu_add(const DevGrid &g, const StepParams &sp, const ImpvmixuArgs &a, dim3 G, hipStream_t st, int waves) {
+  launch_impvmixu_reg<true>(g, sp, a, G, st, waves);
 }
 
 }  // namespace pop

@@ -62,7 +62,7 @@ HaloFields halo_fields(const std::vector<HaloItem> &items) {
   return H;
 }
 int halo_update_many(pop_ctx *c, const std::vector<HaloItem> &items) {
-  if (items.size() == 1 || items.size() > 8 || c->h.c.ns_boundary == 2 || tun_on(c->h.tun.halo_separate)) {
+  if (items.size() == 1 || items.size() > 8 || c->h.c.ns_boundary == 2 || c->f.halo_separate) {
     for (const HaloItem &it : items) if (halo_update(c, it.F, it.nz, 0.0, it.loc, it.kind)) return 1;
     return 0;
   }
@@ -91,7 +91,7 @@ int halo_update_many(pop_ctx *c, const std::vector<HaloItem> &items) {
 // take values that just arrived; the others are rewritten with the same values).  Between the two the launch stream
 // may run anything that reads only cells this rank owns or ghosts with a source on this rank.
 bool halo_async_ok(const pop_ctx *c) {
-  return !c->peers.empty() && c->halo_ns_only && c->xchg_side && c->comm_side && c->h.c.ns_boundary != 2 && !tun_on(c->h.tun.halo_overlap_off);
+  return !c->peers.empty() && c->halo_ns_only && c->xchg_side && c->comm_side && c->h.c.ns_boundary != 2 && c->f.halo_overlap;
 }
 struct HaloAsync { HaloFields H; int tot; };
 int halo_many_begin(pop_ctx *c, const std::vector<HaloItem> &items, HaloAsync &A) {

@@ -15,7 +15,7 @@ SolverArgs solver_args(pop_ctx *c) {
 // residual: X is a residual of a solver (zero on land): sub-blocks without an ocean cell are not read (k_evp_apply_wave3<true>)
 int evp_apply(pop_ctx *c, const double *X, double *PX, bool residual = true) {
   const dim3 GW((unsigned)((c->evp.S + POP_EVP_SB - 1) / POP_EVP_SB));
-  if (tun_off(c->h.tun.evp_wave))   // pop_tuning.evp_wave = 0: a thread per sub-block, the plain statement in the reference's order
+  if (c->f.evp_wave == 0)   // a thread per sub-block, the plain statement in the reference's order
     hipLaunchKernelGGL(k_evp_apply, dim3((unsigned)((c->evp.S + POP_EVP_THREADS - 1) / POP_EVP_THREADS)), dim3(POP_EVP_THREADS), 0, c->stream,
                        c->evp, c->g.nxb, X, PX);
   else   // 3 (the default): anti-diagonal wavefronts, eight lanes per sub-block, eight sub-blocks per wave
@@ -90,38 +90,34 @@ int solver_pcg(pop_ctx *c) {
 // convergenceCheckFreq iterations (same arithmetic and summation order as solver_pcg).  It runs on a
 // SolveView: the rank's own blocks (single rank), or -- replicated barotropic mode -- every block
 // of the decomposition on every rank.
+// The rules below depend on the solver view (the local and the replicated view differ in size): functions of the view that take the plan's
+// switch values (Forms; presum_by_size and two_cell_shape are in forms.hpp, which applies them to the local view for P-CSI).
 // which forms of step A / step B the fused pcg launches (launch_fpcg_a / launch_fpcg_b)
-static bool fpcg_pair_ok(const pop_ctx *c, const SolveView &v, const FusedArgs &a) {
-  return v.g.red_act && a.presummed && !a.sendmap && (v.g.red_nact % 16) == 0 && !tun_off(c->h.tun.fpcg_b2) && !tun_off(c->h.tun.fpcg_a_pair);
+static bool fpcg_pair_ok(const Forms &f, const SolveView &v, const FusedArgs &a) {
+  return v.g.red_act && a.presummed && !a.sendmap && (v.g.red_nact % 16) == 0 && f.fpcg_b2 && f.fpcg_a_pair;
 }
-// the size rule of the large-grid forms: more chunk partials than a consumer workgroup should sum -> block sums by a launch of their own
-static bool presum_by_size(long long nchunk, long long nblocks) { return nchunk * nblocks > 2048; }
-// two cells per thread: where the block sums are presummed (large grids), the row pitch is even and the launch is not tiled.  two_cell_shape
-// is the whole rule for the P-CSI step (pop_create_tuned: pcsi_two_cell); the fused pcg / ChronGear kernels also honour
-// pop_tuning.fpcg_b2 = 0 (POP_FPCG_B2=0: one cell per thread even on large grids)
-static bool two_cell_shape(const DevGrid &g, bool presummed) { return presummed && (g.nxb & 1) == 0; }
-static bool two_cell_ok(const pop_ctx *c, const DevGrid &g, bool presummed) { return two_cell_shape(g, presummed) && !tun_off(c->h.tun.fpcg_b2); }
+// two cells per thread in the fused pcg / ChronGear kernels: the shape rule, unless the plan says one cell per thread even on large grids
+static bool two_cell_ok(const Forms &f, const DevGrid &g, bool presummed) { return two_cell_shape(g.nxb, presummed) && f.fpcg_b2; }
 FusedArgs fused_args(pop_ctx *c, const SolveView &v) {
   FusedArgs a{};
   a.X = v.X; a.R = v.R; a.Z = v.Z; a.S0 = v.S0; a.S1 = v.S1; a.Q = v.Q;
   a.Bv = v.RHS; a.C = v.C; a.partA = v.partial; a.partB = v.partial + (size_t)v.nchunk * v.g.nblocks;
   a.sc = c->sc; a.srcmap = v.srcmap; a.nchunk = v.nchunk; a.nblocks = v.g.nblocks;
   a.bsA = v.blocksum + 2 * v.nblocks_tot; a.bsB = v.blocksum + 3 * v.nblocks_tot;
-  a.presummed = (presum_by_size(v.nchunk, v.g.nblocks) || tun_on(c->h.tun.solver_presum)) ? 1 : 0;
+  a.presummed = (presum_by_size(v.nchunk, v.g.nblocks) || c->f.presum_forced) ? 1 : 0;
   return a;
 }
 // large grids: ordered block sums of a partial array between solver kernels (view-local block order)
 // (more than 64 terms per accumulator: the four-threads-per-accumulator form, one memory round trip instead of two or three)
 constexpr int POP_RELAY_LMAX = 36;
-static bool presum_relay(const pop_ctx *c, const SolveView &v) {
+static bool presum_relay(int relay, const SolveView &v) {   // relay: Forms::block_sums_relay
   const int terms = (v.nchunk + POP_RED_THREADS - 1) / POP_RED_THREADS;
-  const int t = tun_or(c->h.tun.block_sums_relay, 1);   // 2: wherever it can run (the cross-check on small grids)
-  return (terms > 64 || t == 2) && (terms + 3) / 4 <= POP_RELAY_LMAX && t != 0;
+  return (terms > 64 || relay == 2) && (terms + 3) / 4 <= POP_RELAY_LMAX && relay != 0;
 }
 // NF interleaved fields per chunk (pcg 1, ChronGear 2)
 template <int NF = 1>
 void presum(pop_ctx *c, const SolveView &v, const double *partial, double *bs) {
-  if (presum_relay(c, v)) hipLaunchKernelGGL((k_block_sums_relay<NF, POP_RELAY_LMAX>), dim3(v.g.nblocks, NF), dim3(1024), 0, c->stream, partial, v.nchunk, (const int *)c->iota, bs);
+  if (presum_relay(c->f.block_sums_relay, v)) hipLaunchKernelGGL((k_block_sums_relay<NF, POP_RELAY_LMAX>), dim3(v.g.nblocks, NF), dim3(1024), 0, c->stream, partial, v.nchunk, (const int *)c->iota, bs);
   else hipLaunchKernelGGL(k_block_sums<NF>, dim3(v.g.nblocks), dim3(POP_RED_THREADS), 0, c->stream, partial, v.nchunk, (const int *)c->iota, bs);
 }
 dim3 view_grid(const SolveView &v) { return dim3(red_grid_x(v.g), v.g.nblocks); }
@@ -130,7 +126,7 @@ dim3 view_grid(const SolveView &v) { return dim3(red_grid_x(v.g), v.g.nblocks); 
 template <bool WITH_RR>
 void launch_fresidual(pop_ctx *c, const SolveView &v, const FusedArgs &a, bool presummed) {
   const dim3 G = view_grid(v);
-  if (two_cell_ok(c, v.g, presummed)) hipLaunchKernelGGL(k_fresidual2<WITH_RR>, G, dim3(POP_RED_THREADS / 2), 0, c->stream, v.g, a);
+  if (two_cell_ok(c->f, v.g, presummed)) hipLaunchKernelGGL(k_fresidual2<WITH_RR>, G, dim3(POP_RED_THREADS / 2), 0, c->stream, v.g, a);
   else hipLaunchKernelGGL(k_fresidual<WITH_RR>, G, dim3(POP_RED_THREADS), 0, c->stream, v.g, a);
 }
 template <bool WITH_RR>
@@ -138,7 +134,7 @@ void launch_fresidual(pop_ctx *c, const SolveView &v, const FusedArgs &a) { laun
 // step A of the fused pcg: two chunks per workgroup on compacted launches (single rank), else one
 void launch_fpcg_a(pop_ctx *c, const SolveView &v, const FusedArgs &a, bool update) {
   const dim3 G = view_grid(v), B(POP_RED_THREADS);
-  const bool pair = fpcg_pair_ok(c, v, a);
+  const bool pair = fpcg_pair_ok(c->f, v, a);
   if (pair) {
     const dim3 GP(G.x / 2, G.y);
     if (update) hipLaunchKernelGGL(k_fpcg_a_pair<true>, GP, B, 0, c->stream, v.g, a);
@@ -150,7 +146,7 @@ void launch_fpcg_a(pop_ctx *c, const SolveView &v, const FusedArgs &a, bool upda
 // xupd: the pending x += alpha s of the previous iteration is applied here (k_fpcg_a<true> ran before and published alpha)
 void launch_fpcg_b(pop_ctx *c, const SolveView &v, const FusedArgs &a, bool xupd) {
   const dim3 G = view_grid(v);
-  const bool two = two_cell_ok(c, v.g, a.presummed != 0);
+  const bool two = two_cell_ok(c->f, v.g, a.presummed != 0);
   // (occupancy probe, profiles/r03_ab_b2_occupancy.txt: with dynamic LDS holding the kernel to 3 / 2 waves per SIMD instead of its 4
   // the step costs +2.2 / +7.1 ms; the two-cell form needs 108 VGPRs, a 96- or 80-register budget spills 84 / 140 B)
   if (two && xupd) hipLaunchKernelGGL(k_fpcg_b2<true>, G, dim3(POP_RED_THREADS / 2), 0, c->stream, v.g, a);
@@ -249,9 +245,9 @@ static pop_ctx::PersistPlan *persist_plan(pop_ctx *c, const SolveView &v) {
   // chunks per workgroup: the smallest of 1 / 2 / 4 / 8 that needs at most 250 workgroups (one per CU: the waits need every workgroup
   // resident).  gx1v7 in one block: 246 x 2 (10.7 us per iteration; 123 x 4: 12.0, 62 x 8: 14.1 on the same box, profiles/r04_ab_persist_shape.txt);
   // gx1v7 in the eight 48-row bands of the 8-rank decomposition (replicated solve): 144 x 4.
-  // measurement only: pop_tuning.pcg_persist = 2 | 4 | 8 forces that many chunks per workgroup
+  // measurement only: Forms::persist = 2 | 4 | 8 forces that many chunks per workgroup
   std::vector<int> cand;
-  if (c->h.tun.pcg_persist == 2 || c->h.tun.pcg_persist == 4 || c->h.tun.pcg_persist == 8) { if ((nslots + c->h.tun.pcg_persist - 1) / c->h.tun.pcg_persist <= 250) cand.push_back(c->h.tun.pcg_persist); }
+  if (c->f.persist > 1 && (nslots + c->f.persist - 1) / c->f.persist <= 250) cand.push_back(c->f.persist);
   if (cand.empty())
     for (int cp : {1, 2, 4, 8}) if ((nslots + cp - 1) / cp <= 250) { cand.push_back(cp); break; }
   if (cand.empty()) return refuse("more than 2000 chunks");
@@ -392,7 +388,7 @@ int persist_keep_x0(pop_ctx *c, const SolveView &v, const pop_ctx::PersistPlan &
 int solver_pcg_fused(pop_ctx *c, SolveView &v) {
   const pop_config &cf = c->h.c;
   c->persist_used = 0;
-  if (!tun_off(c->h.tun.pcg_persist) && !fused_args(c, v).presummed) {   // the rule: wherever the plan qualifies (small views); pop_tuning.pcg_persist = 0 switches it off
+  if (c->f.persist && !fused_args(c, v).presummed) {   // wherever the persist plan qualifies (small views)
     const pop_ctx::PersistPlan *pl = c->persist_gave_up ? nullptr : persist_plan(c, v);
     if (pl) {   // from the first guess; should it give up, the launches below repeat the solve from the same guess -- the same numbers
       static void (*const kern[4])(PersistArgs) = {k_pcg_persist<1>, k_pcg_persist<2>, k_pcg_persist<4>, k_pcg_persist<8>};
@@ -409,7 +405,7 @@ int solver_pcg_fused(pop_ctx *c, SolveView &v) {
   launch_fresidual<false>(c, v, fused_args(c, v));
   c->numIterations = cf.max_iterations;
   double rr = 0.0;
-  const bool use_graph = (freq % 2 == 0) && !tun_on(c->h.tun.solver_nograph);   // even: S0 / S1 end an interval where they started it
+  const bool use_graph = (freq % 2 == 0) && c->f.graph;   // even: S0 / S1 end an interval where they started it
   int lerr = 0;
   const int nint = cf.max_iterations / freq;
   const int conv = run_intervals(c, nint, [&](int) -> int {
@@ -485,7 +481,7 @@ struct DistSolve {
   // the one-level exchange of the buffers the kernels packed: on the side stream beside the all-reduce when the
   // transport has a second communicator, else in line.  fork: the packed data is complete on the launch stream now.
   bool overlap = true;
-  bool side() const { return overlap && c->xchg_side && c->comm_side && !tun_on(c->h.tun.solver_overlap_off); }
+  bool side() const { return overlap && c->xchg_side && c->comm_side && c->f.overlap; }
   int xchg_begin() {
     PeerSpans ps(c, 1);
     c->solver_ops += 1;
@@ -646,7 +642,7 @@ static void cg_clear_partials(pop_ctx *c, const SolveView &v) {
 static FusedArgs cg_args(pop_ctx *c, const SolveView &v, FusedArgs a) { a.AZ = c->AZ; a.A0R = v.S1; return a; }
 // step A of the fused ChronGear: two cells per thread on large grids, else one
 static void launch_fcg_a(pop_ctx *c, const SolveView &v, const FusedArgs &a, bool presummed) {
-  if (two_cell_ok(c, v.g, presummed)) hipLaunchKernelGGL(k_fcg_a2, view_grid(v), dim3(POP_RED_THREADS / 2), 0, c->stream, v.g, a);
+  if (two_cell_ok(c->f, v.g, presummed)) hipLaunchKernelGGL(k_fcg_a2, view_grid(v), dim3(POP_RED_THREADS / 2), 0, c->stream, v.g, a);
   else hipLaunchKernelGGL(k_fcg_a, view_grid(v), dim3(POP_RED_THREADS), 0, c->stream, v.g, a);
 }
 // n iterations; par: the (rho, sigma) ping-pong slot the first one reads
@@ -673,8 +669,8 @@ int solver_chrongear_fused(pop_ctx *c) {
   const int freq = cf.convergence_check_freq;
   if (cg_startup(c, true)) return 1;
   c->persist_used = 0;
-  // small views: the iterations as one resident launch (k_cg_persist); pop_tuning.pcg_persist = 0 switches it off
-  if (!tun_off(c->h.tun.pcg_persist) && !fused_args(c, v).presummed && !c->persist_gave_up &&
+  // small views: the iterations as one resident launch (k_cg_persist)
+  if (c->f.persist &&!fused_args(c, v).presummed && !c->persist_gave_up &&
       v.g.nblocks * ((v.nchunk + POP_RED_THREADS - 1) / POP_RED_THREADS) <= POP_CGP_MAXP) {
     if (const pop_ctx::PersistPlan *pl = persist_plan(c, v)) {
       static void (*const kern[4])(CgPersistArgs) = {k_cg_persist<1>, k_cg_persist<2>, k_cg_persist<4>, k_cg_persist<8>};
@@ -690,7 +686,7 @@ int solver_chrongear_fused(pop_ctx *c) {
   c->numIterations = cf.max_iterations;
   double rr = 0.0;
   // a graph holds the ping-pong slots of its iterations: valid for every interval only when freq is even (each then starts at slot 0)
-  const bool use_graph = (freq % 2 == 0) && !tun_on(c->h.tun.solver_nograph);
+  const bool use_graph = (freq % 2 == 0) && c->f.graph;
   int lerr = 0;
   const int nint = cf.max_iterations / freq;
   const int conv = run_intervals(c, nint, [&](int i) -> int {
@@ -835,7 +831,7 @@ static DevGrid pcsi_grid(const pop_ctx *c) {
 // needs the chunk partials of (r, r) of k_pcsi_step2, and a single step before it keeps the pairs aligned for every n)
 // An interval of an even number of iterations goes in pairs throughout: the pair before a check leaves the residual itself in a scratch field
 // and k_pcsi_rr_chunks forms the chunk partials of (r, r) from it.  An odd interval: pairs, then one single step (which carries the check).
-static int pcsi_pairs(const pop_ctx *c, int n) { return c->pcsi_two_step ? n / 2 : 0; }
+static int pcsi_pairs(const pop_ctx *c, int n) { return c->f.pcsi_two_step ? n / 2 : 0; }
 // one pair; with_raw: the residual itself to pcsi_raw as well, and the chunk partials of (r, r) from it
 static void pcsi_launch_pair(pop_ctx *c, const DevGrid &gg, PcsiArgs a, bool with_raw) {
   const int tiles_i = (gg.nxb - 2 * NGHOST + 63) / 64, tiles_j = (gg.nyb - 2 * NGHOST + 7) / 8;
@@ -854,20 +850,6 @@ static void pcsi_interval(pop_ctx *c, const PcsiBufs &bf, int in, int freq, bool
   const DevGrid gg = pcsi_grid(c);
   const dim3 G(red_grid_x(gg), gg.nblocks), B(POP_RED_THREADS);
   int j0 = 1;
-  if (c->pcsi_evp_fused) {   // EVP: one launch per iteration (the step and the sub-block solves); r' ping-pongs with x and dx
-    const dim3 GE((unsigned)((c->evp.S + POP_EVP_SB - 1) / POP_EVP_SB));
-    for (int j = 1; j <= freq; ++j) {
-      PcsiArgs a = pcsi_args(c, bf, in, j);
-      a.raw_r = 0; a.Ri = bf.R[in]; a.Ro = bf.R[1 - in];
-      if (j == freq && with_rr) {
-        hipLaunchKernelGGL(k_pcsi_evp_step<true>, GE, dim3(64), 0, c->stream, c->evp, gg, a, c->pcsi_raw);
-        hipLaunchKernelGGL(k_pcsi_rr_chunks, G, B, 0, c->stream, gg, a, (const double *)c->pcsi_raw);
-      } else hipLaunchKernelGGL(k_pcsi_evp_step<false>, GE, dim3(64), 0, c->stream, c->evp, gg, a, (double *)nullptr);
-      in = 1 - in;
-    }
-    if (with_rr) hipLaunchKernelGGL(k_rr_total, dim3(1), dim3(POP_RED_THREADS), 0, c->stream, (const double *)c->partial, c->nchunk, c->g.nblocks, c->sc, c->host_rr, c->h.convergenceCriterion);
-    return;
-  }
   const int npairs = pcsi_pairs(c, freq);
   for (int p = 0; p < npairs; ++p, j0 += 2) {
     pcsi_launch_pair(c, gg, pcsi_args(c, bf, in, j0), with_rr && j0 + 1 == freq);   // (the last pair of an even interval that ends in a check)
@@ -875,7 +857,7 @@ static void pcsi_interval(pop_ctx *c, const PcsiBufs &bf, int in, int freq, bool
   }
   for (int j = j0; j <= freq; ++j) {
     const PcsiArgs a = pcsi_args(c, bf, in, j);
-    if (c->pcsi_two_cell) {
+    if (c->f.pcsi_two_cell) {
       const bool rr = j == freq && with_rr;
       if (rr && c->use_evp) hipLaunchKernelGGL((k_pcsi_step2<true, true>), G, dim3(POP_RED_THREADS / 2), 0, c->stream, gg, a);
       else if (c->use_evp) hipLaunchKernelGGL((k_pcsi_step2<false, true>), G, dim3(POP_RED_THREADS / 2), 0, c->stream, gg, a);
@@ -895,7 +877,6 @@ int solver_pcsi_fused(pop_ctx *c) {
   const dim3 G = grid_2d(c), B(POP_RED_THREADS);
   const int freq = cf.convergence_check_freq, start = pcsi_check_start(c);
   PcsiBufs bf{{c->PS[c->newt], c->Z}, {c->R, c->AZ}, {c->Q, c->S1}};   // (with EVP the residual pair is fixed: pcsi_args)
-  if (c->pcsi_evp_fused) std::swap(bf.R[0], bf.R[1]);   // ... except in the one-launch form: the start-up step leaves r' in R, which is then the half the first iteration reads
   if (solver_begin(c)) return 1;
   // r0 = b - A x0 (ghosts of x0 read at their sources), then the start-up step x1 = x0 + r0'/gamma, r1 = b - A x1
   {
@@ -916,7 +897,7 @@ int solver_pcsi_fused(pop_ctx *c) {
   hipLaunchKernelGGL((k_pcsi_step<true, false>), G, B, 0, c->stream, c->g, pcsi_args(c, bf, 0, 0));
   if (c->use_evp && evp_apply(c, c->AZ, c->R)) return 1;
   c->persist_used = 0;
-  if (!c->use_evp && !tun_off(c->h.tun.pcg_persist) && !c->persist_gave_up) {
+  if (!c->use_evp && c->f.persist && !c->persist_gave_up) {
     // small views: the iterations as one resident launch (k_pcsi_persist: neighbour waits only, grid-wide exchanges at the checks)
     const SolveView v = local_view(c);   // (v.X is bf.X[0])
     const pop_ctx::PersistPlan *pl = fused_args(c, v).presummed ? nullptr : persist_plan(c, v);
@@ -946,7 +927,7 @@ int solver_pcsi_fused(pop_ctx *c) {
     const int m = i * freq, n = std::min(freq, cf.max_iterations - m);
     const bool with_rr = (n == freq) && (m + n >= start);
     hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, c->stream, c->pcsi_base, m);
-    if (!tun_on(c->h.tun.solver_nograph) && n == freq) {   // one graph per ping-pong half the interval starts from, with and without the check
+    if (c->f.graph && n == freq) {   // one graph per ping-pong half the interval starts from, with and without the check
       hipGraphExec_t exec = graph_for(c, bf.X[0], in * 2 + (with_rr ? 1 : 0), [&]() { pcsi_interval(c, bf, in, n, with_rr); return 0; });
       if (!exec || hipGraphLaunch(exec, c->stream) != hipSuccess) return -1;
     } else pcsi_interval(c, bf, in, n, with_rr);
@@ -982,8 +963,8 @@ int solver_pcsi_fused_dist(pop_ctx *c) {
     PcsiArgs a = pcsi_args(c, bf, in, j);
     a.remote_ghosts = 1;
     if (first) hipLaunchKernelGGL((k_pcsi_step<true, false>), G, B, 0, c->stream, c->g, a);
-    else if (c->pcsi_two_cell && rr) hipLaunchKernelGGL((k_pcsi_step2<true>), G, dim3(POP_RED_THREADS / 2), 0, c->stream, c->g, a);
-    else if (c->pcsi_two_cell) hipLaunchKernelGGL((k_pcsi_step2<false>), G, dim3(POP_RED_THREADS / 2), 0, c->stream, c->g, a);
+    else if (c->f.pcsi_two_cell && rr) hipLaunchKernelGGL((k_pcsi_step2<true>), G, dim3(POP_RED_THREADS / 2), 0, c->stream, c->g, a);
+    else if (c->f.pcsi_two_cell) hipLaunchKernelGGL((k_pcsi_step2<false>), G, dim3(POP_RED_THREADS / 2), 0, c->stream, c->g, a);
     else if (rr) hipLaunchKernelGGL((k_pcsi_step<false, true>), G, B, 0, c->stream, c->g, a);
     else hipLaunchKernelGGL((k_pcsi_step<false, false>), G, B, 0, c->stream, c->g, a);
     return 0;
@@ -992,10 +973,10 @@ int solver_pcsi_fused_dist(pop_ctx *c) {
   int in = 1;
   c->numIterations = cf.max_iterations;
   double rr = 0.0;
-  if (c->pcsi_two_step_dist && halo_update_many(c, {{c->RHS, 1}})) return 1;   // the pairs form r at the first ring of ghost cells
+  if (c->f.pcsi_two_step_dist && halo_update_many(c, {{c->RHS, 1}})) return 1;   // the pairs form r at the first ring of ghost cells
   // two iterations per launch across ranks (k_pcsi_step_x2): x, dx and r' travel two rings wide once per PAIR instead of r' once per
   // iteration -- half the messages per iteration
-  const bool pairs = c->pcsi_two_step_dist;
+  const bool pairs = c->f.pcsi_two_step_dist;
   const DevGrid gg = c->g;
   for (int m = 1; m <= cf.max_iterations; ++m) {
     bool check = (m % freq == 0) && m >= start;
@@ -1035,30 +1016,10 @@ void solve_collect(pop_ctx *c) {
   }
 }
 
-// which form of the solver solver_run dispatches to: 1 operation by operation, 2 fused on one rank,
-// 3 fused with the blocks spread over ranks, 4 replicated fused solve on every rank -- reported per rank by bench.py
-static int solver_path_code(const pop_ctx *c) {
-  const bool unf = tun_on(c->h.tun.solver_unfused);
-  if (c->h.c.solver_choice == 2) {
-    if (c->fused_ok && !c->use_evp) return 2;
-    if (c->h.nranks > 1 && c->max_blocks_per_rank <= 16 && !c->use_evp && !unf) return 3;
-    return 1;
-  }
-  if (c->h.c.solver_choice == 3) {
-    if (c->use_evp) return c->evp_fused_ok ? 2 : 1;
-    if (c->fused_ok) return 2;
-    if (c->h.nranks > 1 && !unf) return 3;
-    return 1;
-  }
-  if (c->use_evp) return 1;
-  if (c->replicated) return 4;
-  if (c->fused_ok) return 2;
-  if (c->h.nranks > 1 && c->max_blocks_per_rank <= 16 && !unf) return 3;
-  return 1;
-}
-// POP_SolversRun: the driver of the configured solver (1 pcg, 2 ChronGear, 3 P-CSI) in the form solver_path_code names
+// POP_SolversRun: the driver of the configured solver (1 pcg, 2 ChronGear, 3 P-CSI) in the form the plan names (Forms::path: 1 operation
+// by operation, 2 fused on one rank, 3 fused with the blocks spread over ranks, 4 replicated fused solve on every rank)
 int solver_run(pop_ctx *c) {
-  const int path = solver_path_code(c), choice = c->h.c.solver_choice;
+  const int path = c->f.path, choice = c->h.c.solver_choice;
   if (choice == 2) return path == 2 ? solver_chrongear_fused(c) : path == 3 ? solver_chrongear_fused_dist(c) : solver_chrongear(c);
   if (choice == 3) return path == 2 ? solver_pcsi_fused(c) : path == 3 ? solver_pcsi_fused_dist(c) : solver_pcsi(c);
   switch (path) {

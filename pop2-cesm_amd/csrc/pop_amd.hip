@@ -157,7 +157,7 @@ void mark_written(pop_ctx *c, const char *name, int tl) {
   if (nm == "TRACER") c->tr_ghosts_ok[time_index(c, tl)] = false;
   if (nm == "UVEL" || nm == "VVEL") c->uv_ghosts_ok[time_index(c, tl)] = false;
   for (const char *f : {"TRACER", "UVEL", "VVEL", "RHO", "PSURF", "GRADPX", "GRADPY", "UBTROP", "VBTROP", "PGUESS", "FW_OLD"})
-    if (nm == f) c->full_left = c->land_full_steps;
+    if (nm == f) c->full_left = c->f.land_full_steps;
 }
 // guards of the host-array halo updates
 int loc_kind_ok(pop_ctx *c, int loc, int kind, const char *text) {
@@ -183,7 +183,8 @@ int pop_create_with_grid(const pop_config *cfg, const pop_grid_input *grid, int 
   return pop_create_tuned(cfg, grid, nullptr, rank, nranks, flags, out);
 }
 
-// ---- tuning switches (include/pop_amd.h pop_tuning): one table of (field, environment variable)
+// ---- tuning switches (include/pop_amd.h pop_tuning): one table of (field, environment variable).  What is merged here is the REQUEST;
+// forms.hpp resolve_forms turns it into the plan (pop_ctx::f), once, in pop_create_tuned
 #define POP_TUNING_FIELDS(X)                                                                                                            \
   X(land_skip, "POP_LAND_SKIP") X(land_full_steps, "POP_LAND_FULL_STEPS") X(xcd_remap, "POP_XCD_REMAP")   \
   X(red_band, "POP_RED_BAND") X(lds_order, "POP_LDS_ORDER") X(momentum_lds, "POP_MOMENTUM_LDS") X(tracer_lds, "POP_TRACER_LDS")         \
@@ -196,7 +197,7 @@ int pop_create_with_grid(const pop_config *cfg, const pop_grid_input *grid, int 
   X(kpp_src_full, "POP_KPP_SRC_FULL") X(solver_unfused, "POP_SOLVER_UNFUSED") X(solver_nograph, "POP_SOLVER_NOGRAPH")                   \
   X(solver_presum, "POP_SOLVER_PRESUM") X(solver_distributed, "POP_SOLVER_DISTRIBUTED") X(solver_overlap_off, "POP_SOLVER_OVERLAP_OFF") \
   X(fpcg_b2, "POP_FPCG_B2") X(pcsi_step2, "POP_PCSI_STEP2") X(halo_separate, "POP_HALO_SEPARATE")                                       \
-  X(halo_overlap_off, "POP_HALO_OVERLAP_OFF") X(rccl_overlap, "POP_RCCL_OVERLAP") X(evp_wave, "POP_EVP_WAVE") X(fpcg_a_pair, "POP_FPCG_A_PAIR") X(stream_priority, "POP_STREAM_PRIORITY") X(kpp_sparse, "POP_KPP_SPARSE") X(pbc_generic_thomas, "POP_PBC_GENERIC_THOMAS") X(pbc_generic_kpp, "POP_PBC_GENERIC_KPP") X(state3d_levels, "POP_STATE3D_LEVELS") X(gm_sf_stored, "POP_GM_SF_STORED") X(pcg_persist, "POP_PCG_PERSIST") X(gm_flux_tile, "POP_GM_FLUX_TILE") X(pcsi_two_step, "POP_PCSI_TWO_STEP") X(block_sums_relay, "POP_BLOCK_SUMS_RELAY") X(pcsi_evp_fused, "POP_PCSI_EVP_FUSED") X(aniso_side, "POP_ANISO_SIDE") X(submeso_all_levels, "POP_SUBMESO_ALL_LEVELS")
+  X(halo_overlap_off, "POP_HALO_OVERLAP_OFF") X(rccl_overlap, "POP_RCCL_OVERLAP") X(evp_wave, "POP_EVP_WAVE") X(fpcg_a_pair, "POP_FPCG_A_PAIR") X(kpp_sparse, "POP_KPP_SPARSE") X(pbc_generic_thomas, "POP_PBC_GENERIC_THOMAS") X(pbc_generic_kpp, "POP_PBC_GENERIC_KPP") X(state3d_levels, "POP_STATE3D_LEVELS") X(gm_sf_stored, "POP_GM_SF_STORED") X(pcg_persist, "POP_PCG_PERSIST") X(gm_flux_tile, "POP_GM_FLUX_TILE") X(pcsi_two_step, "POP_PCSI_TWO_STEP") X(block_sums_relay, "POP_BLOCK_SUMS_RELAY") X(aniso_side, "POP_ANISO_SIDE") X(submeso_all_levels, "POP_SUBMESO_ALL_LEVELS")
 void pop_tuning_init(pop_tuning *t) {
   if (!t) return;
   t->struct_bytes = (int)sizeof(pop_tuning);
@@ -329,44 +330,25 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
     if (cfg->lsw_absorb != 0 && (cfg->sw_absorption_type < 0 || cfg->sw_absorption_type > 2)) return bad("lsw_absorb: sw_absorption_type 0 top-layer, 1 jerlov, 2 chlorophyll");
     if (cfg->vmix_choice == 3 && cfg->num_v_smooth_Ri < 1) return bad("KPP: num_v_smooth_Ri must be >= 1 (the reference leaves FRI unset otherwise)");
     if (!(cfg->convergence_criterion >= 0.0)) return bad("convergence_criterion must be >= 0");
-    // pop_tuning: the switches whose other values named kernel forms that no longer exist
-    const pop_tuning &tun = c->h.tun;
-    if (tun_set(tun.xcd_remap) && tun.xcd_remap != 0 && tun.xcd_remap != 1) return bad("pop_tuning.xcd_remap is " + std::to_string(tun.xcd_remap) + ": 0 linear or 1 XCD bands");
-    if (tun_set(tun.evp_wave) && tun.evp_wave != 0 && tun.evp_wave != 3) return bad("pop_tuning.evp_wave is " + std::to_string(tun.evp_wave) + ": 0 one thread per sub-block or 3 wavefronts");
   }
   c->h.plan_only = (flags & POP_CREATE_PLAN_ONLY) != 0;
   const int hb = host_build(c->h);
   c->h.gin = nullptr;
   if (hb) { c->err = c->h.err; return 1; }
   c->host_only = (flags & (POP_CREATE_HOST_ONLY | POP_CREATE_PLAN_ONLY)) != 0;
+  // the plan: every kernel-form and schedule choice, once (a plan-only context has no vertical grid and no plan)
+  if (!c->h.plan_only && resolve_forms(c->h, c->f, c->err)) return 1;
   if (c->host_only) return 0;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { c->err = "no HIP device available; libpop_amd has no CPU fallback"; return 1; }
-  // stream priorities (r3, measured and left OFF: 84.7 ms against 83.2 without, profiles/r03_ab_stream_priority.txt): the launch stream above
-  // the streams that only fill its gaps (KPP of the next step), so that the
-  // one-workgroup block sums between the solver's kernels are dispatched ahead of KPP workgroups waiting in the other queues
-  int prio_least = 0, prio_greatest = 0;
-  const bool prio = tun_on(c->h.tun.stream_priority) && hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) == hipSuccess && prio_least != prio_greatest;
-  if (prio) HIPCHK(c, hipStreamCreateWithPriority(&c->stream, hipStreamDefault, prio_greatest));
-  else HIPCHK(c, hipStreamCreate(&c->stream));
-  c->prio_least = prio ? prio_least : 0; c->prio_on = prio;
+  HIPCHK(c, hipStreamCreate(&c->stream));
   c->own_stream = true;
+  const Forms &f = c->f;
   HostModel &h = c->h;
   DevGrid &g = c->g;
   g.nxb = h.nxb; g.nyb = h.nyb; g.km = h.km; g.nt = h.nt; g.nblocks = h.nblocks;
   g.n2 = (int)h.n2; g.n3 = (long long)h.n3;
-  // workgroup order (kernels_common.hpp).  Measured on MI355X: the XCD-banded order cuts fabric re-fetch of
-  // the stencil kernels from 3.2x to 1.3x of the algorithmic reads at gx1v7 (-6% time) but costs +20% at
-  // tx0.1v3, where the 256 MB infinity cache already absorbs the re-fetch (row-aligned 2-D tile columns, tried
-  // for both the column and the reduction kernels, lost 128-B alignment of the rows and cost +10% / +2% there).
-  // Large grids therefore keep the natural linear order; either order stays selectable (POP_XCD_REMAP=0|1) and tested.
-  g.xcd_remap = (h.n2 * h.nblocks <= (1u << 19)) ? 1 : 0;
-  g.xcd_remap = tun_or(h.tun.xcd_remap, g.xcd_remap);
-  // 2-D solver / reduction kernels: XCD-banded chunk order (same chunks, same partial order, only the workgroup ->
-  // chunk assignment changes, so results are bitwise unchanged): gx1v7 4.31 -> 4.01 ms per step (the 9-point
-  // matvec finds its j+-1 rows in the XCD's own L2), tx0.1v3 177.1 -> 175.2.  POP_RED_BAND=0 restores the natural order.
-  g.lds_order = tun_or(h.tun.lds_order, 1);
-  g.red_band = tun_or(h.tun.red_band, 1);
+  g.xcd_remap = f.xcd_remap; g.lds_order = f.lds_order; g.red_band = f.red_band;   // workgroup orders (kernels_common.hpp)
   g.ib = NGHOST + 1; g.ie = h.nxb - NGHOST; g.jb = NGHOST + 1; g.je = h.nyb - NGHOST;
   {   // padded blocks (blocks.F90:174-265): per-block last physical column / row, only when some local block ends early
     std::vector<int> ieb(h.nblocks), jeb(h.nblocks);
@@ -398,7 +380,7 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
       HIPCHK(c, hipDeviceSynchronize());
       g.eosP = p;
     }
-    g.state_lv = tun_or(h.tun.state3d_levels, 4);
+    g.state_lv = f.state3d_levels;
   }
   // 2-D fields: upload the local blocks of every host field
   for (auto &kv : h.f2) {
@@ -527,9 +509,7 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
       if (R == 4) { g.lds_act4 = dl; g.lds_n4 = (int)longest; } else { g.lds_act8 = dl; g.lds_n8 = (int)longest; }
     }
     c->land_fraction = tiles ? (double)land / (double)tiles : 0.0;
-    c->land_skip = !tun_off(h.tun.land_skip);
-    c->land_full_steps = tun_or(h.tun.land_full_steps, 4);
-    c->full_left = c->land_full_steps;
+    c->full_left = f.land_full_steps;
   }
   g.WNE = c->d2["btropWgtNE"]; g.WEa = c->d2["btropWgtEast"]; g.WNo = c->d2["btropWgtNorth"]; g.WC0 = c->d2["centerWgtIndep"];
   g.XW = c->d2["btropXW"]; g.YW = c->d2["btropYW"];
@@ -606,7 +586,7 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
     G.kappa_bkg = cfg->gm_kappa_bkg_srfbl == 1; G.ah_bkg_bottom = cfg->ah_bkg_bottom;
     G.diff_tapering = G.slm_r != G.slm_b;                              // :964-968
     G.cancellation = !(G.diff_tapering || G.ah != G.ah_bolus) && !G.tlt;   // :970-987 (both kappa types equal)
-    if (!G.cancellation && !tun_off(h.tun.gm_sf_stored)) for (int t = 0; t < 8; ++t) if (dev_alloc(c, &G.SF[t], a3g)) return 1;
+    if (!G.cancellation && f.gm_sf_stored) for (int t = 0; t < 8; ++t) if (dev_alloc(c, &G.SF[t], a3g)) return 1;
   }
   if (cfg->lsubmesoscale_mixing) {   // submesoscale scheme: six 2-D fields; with submeso_diag the tendency alone and the velocities
     const size_t a2s = h.n2 * h.nblocks, a3s = h.n3 * h.nblocks;
@@ -624,7 +604,7 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
     W.hls0 = (cfg->hor_length_scale != 0.0) ? cfg->hor_length_scale : 5.0e5;
     W.max_hgs = 111.0e5;
     W.const_hls = cfg->luse_const_horiz_len_scale;
-    W.all_levels = tun_on(h.tun.submeso_all_levels) ? 1 : 0;
+    W.all_levels = f.submeso_all_levels ? 1 : 0;
   }
 #define GI(f) g.f = c->di2[#f]
   GI(KMT); GI(KMU); GI(KMTN); GI(KMTS); GI(KMTE); GI(KMTW); GI(KMTEE); GI(KMTNN);
@@ -649,12 +629,9 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
     }
     if (cfg->vmix_choice == 3 && dev_alloc(c, &c->KPPX, a3)) return 1;
   }
-  // KPP without double diffusion gives both tracer classes the same diffusivity, value for value (vmix_kpp.F90 ri_iwmix: VDC(:,:,k,2) =
-  // VDC(:,:,k,1); blmix applies the same shape function to both): one array then serves both, so the KPP kernels write it once and
-  // the tracer kernels find the second read in cache.  pop_get_field("VDC", n) returns it for n = 0 and 1.
-  c->vdc_shared = cfg->vmix_choice == 3 && !cfg->ldbl_diff && !tun_off(h.tun.vdc_shared);
+  // Forms::vdc_shared: one array serves both tracer classes; pop_get_field("VDC", n) returns it for n = 0 and 1
   if (dev_alloc(c, &c->VDC[0], (size_t)(h.km + 2) * a2)) return 1;
-  if (c->vdc_shared) c->VDC[1] = c->VDC[0];
+  if (f.vdc_shared) c->VDC[1] = c->VDC[0];
   else if (dev_alloc(c, &c->VDC[1], (size_t)(h.km + 2) * a2)) return 1;
   double **two[] = {&c->PGUESS, &c->FW, &c->FW_OLD, &c->SHF_QSW, &c->CHL, &c->DH, &c->DHU, &c->ZX, &c->ZY, &c->UH, &c->VH, &c->W3, &c->W4, &c->RHS,
                     &c->R, &c->S0, &c->S1, &c->Q, &c->Z, &c->AZ, &c->HBLT, &c->HMXL, &c->HMXL_DR};
@@ -663,27 +640,16 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
   double **three[] = {&c->VVC, &c->E3, &c->F3, &c->S3a, &c->S3b, &c->S3c, &c->S3d};
   for (auto p : three) if (dev_alloc(c, p, a3)) return 1;
   c->d2t[0] = c->S3a; c->d2t[1] = c->S3b; c->d2u[0] = c->S3a; c->d2u[1] = c->S3b;
-  if (!tun_off(h.tun.side_stream)) {
+  if (f.side_stream) {
     HIPCHK(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
     HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
     HIPCHK(c, hipEventCreateWithFlags(&c->ev_d2t, hipEventDisableTiming));
     HIPCHK(c, hipEventCreateWithFlags(&c->ev_d2u, hipEventDisableTiming));
     HIPCHK(c, hipEventCreateWithFlags(&c->ev_vmixu, hipEventDisableTiming));
-    if ((cfg->hmix_tracer == 4 || cfg->hmix_momentum == 4) && !tun_off(h.tun.del4_side)) {
-      if (dev_alloc(c, &c->d2t[0], a3) || dev_alloc(c, &c->d2t[1], a3) || dev_alloc(c, &c->d2u[0], a3) || dev_alloc(c, &c->d2u[1], a3)) return 1;
-      c->side_del4 = true;
-      // no tripole fold (the ghost ring of the field comes from a halo update, which is the same arithmetic only where ghost cells are
-      // plain copies), centred advection through the LDS kernel, bandwidth-bound grids; POP_D2T_FUSE=0|1 overrides the size rule
-      const int fuse_env = tun_or(h.tun.d2t_fuse, -1);
-      if (cfg->hmix_tracer == 4 && cfg->ns_boundary != 2 && cfg->tadvect == 1 &&
-          (fuse_env >= 0 ? fuse_env != 0 : (long long)h.n2 * h.nblocks > (1 << 19)))
-        if (dev_alloc(c, &c->d2t_next[0], a3) || dev_alloc(c, &c->d2t_next[1], a3)) return 1;
-      if (cfg->hmix_momentum == 4 && cfg->ns_boundary != 2 && !tun_off(h.tun.d2u_fuse) &&
-          (fuse_env >= 0 ? fuse_env != 0 : (long long)h.n2 * h.nblocks > (1 << 19)))
-        if (dev_alloc(c, &c->d2u_next[0], a3) || dev_alloc(c, &c->d2u_next[1], a3)) return 1;
-    }
   }
-  c->mom_side = cfg->hmix_momentum == 3 ? (c->side != nullptr && !tun_off(h.tun.aniso_side)) : c->side_del4;
+  if (f.del4_side && (dev_alloc(c, &c->d2t[0], a3) || dev_alloc(c, &c->d2t[1], a3) || dev_alloc(c, &c->d2u[0], a3) || dev_alloc(c, &c->d2u[1], a3))) return 1;
+  if (f.d2t_fuse && (dev_alloc(c, &c->d2t_next[0], a3) || dev_alloc(c, &c->d2t_next[1], a3))) return 1;
+  if (f.d2u_fuse && (dev_alloc(c, &c->d2u_next[0], a3) || dev_alloc(c, &c->d2u_next[1], a3))) return 1;
   c->nchunk = red_grid_x(g);
   {   // DevGrid::red_act: the chunks (256 consecutive cells) the fused solver kernels have to visit
     const int nc = (int)((h.n2 + 255) / 256);
@@ -785,26 +751,12 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
     if (c->nrecv_all && (dev_upload(c, &c->ra_dst, rd.data(), rd.size()) || dev_upload(c, &c->ra_start, rt.data(), rt.size()) || dev_upload(c, &c->ra_cnt, rc.data(), rc.size()))) return 1;
   }
   {   // source map for the fused solver path: ghost cell -> local source cell, -1 = fill value
-    std::vector<int> sm(a2);
-    for (size_t p = 0; p < a2; ++p) sm[p] = (int)p;
-    for (size_t i = 0; i < h.halo.copy_dst.size(); ++i) sm[h.halo.copy_dst[i]] = h.halo.copy_src[i];
-    for (int d : h.halo.fill_dst) sm[d] = -1;
-    if (cfg->ns_boundary == 2) {   // centre scalars beyond the fold are plain mirrored copies of physical cells (TripolePlan loc 0: no symmetrised row)
-      const TripolePlan &T = h.halo.tripole[0];
-      for (size_t e = 0; e < T.dst.size(); ++e) sm[T.dst[e]] = T.a[e];
-    }
-    if (dev_upload(c, &c->srcmap, sm.data(), sm.size())) return 1;
-    c->h_srcmap = sm;
+    c->h_srcmap = local_srcmap(h);
+    if (dev_upload(c, &c->srcmap, c->h_srcmap.data(), c->h_srcmap.size())) return 1;
     HIPCHK(c, hipHostMalloc((void **)&c->persist_out, 4 * sizeof(double)));
     HIPCHK(c, hipHostMalloc((void **)&c->host_sc, sizeof(SolverScalars)));
     HIPCHK(c, hipHostMalloc((void **)&c->host_rr, 8 * sizeof(double)));
     for (auto &e : c->chk_ev) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    {
-      std::vector<int> per(h.nranks, 0);
-      for (int o : h.block_owner) if (o >= 0 && o < h.nranks) per[o]++;
-      c->max_blocks_per_rank = *std::max_element(per.begin(), per.end());
-    }
-    c->fused_ok = h.halo.peers.empty() && h.nblocks <= 8 && !tun_on(h.tun.solver_unfused);
     if (cfg->solver_choice == 3) {   // omega_k of P-CSI (POP_SolversMod.F90:1617-1620, 1695): a function of the eigenvalue bounds only
       const double csalpha = 2.0 / (h.pcsi_max_eig - h.pcsi_min_eig);
       const double csbeta = (h.pcsi_max_eig + h.pcsi_min_eig) / (h.pcsi_max_eig - h.pcsi_min_eig);
@@ -846,53 +798,14 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
           dev_upload(c, &d2, icc.data(), icc.size()) || dev_upload(c, &d3, ine.data(), ine.size()) || dev_upload(c, &d4, rinv.data(), rinv.size())) return 1;
       c->evp = EvpDev{(long long)S, dm, d0, d1, d2, d3, d4, c->d2["evpC0"], c->d2["btropWgtNE"]};
       c->use_evp = true;
-      c->evp_fused_ok = c->fused_ok && cfg->solver_choice == 3;   // P-CSI + EVP: step kernel + sub-block solves, two launches per iteration (r3)
-      c->fused_ok = false;
     }
-    c->mom_lds_rows = tun_or(h.tun.momentum_lds, c->mom_lds_rows);
-    // tracer RHS through LDS tiles (kernels_tracer_lds.hpp).  Measured against the direct-load kernel: tx0.1v3 15.0 ms ->
-    // 12.8 (64x4 tiles) / 13.6 (64x8); gx1v7 0.260 ms -> 0.208 (64x4) / 0.192 (64x8).  POP_TRACER_LDS=0|4|8 overrides.
-    c->trc_lds_rows = 4;   // round 3 (branch-free kernels, two waves per SIMD): 64 x 4 tiles at every size (gx1v7 0.149 vs 0.156 ms, tx0.1v3 7.6 vs 8.0)
-    c->trc_lds_rows = tun_or(h.tun.tracer_lds, c->trc_lds_rows);
-    c->reg_thomas = !tun_on(h.tun.generic_thomas);
-    // tracer solve: the register kernel keeps the elimination coefficients of a column in VGPRs instead of writing them to
-    // scratch fields and reading them back (the generic corrector moves 46 GB at the L2 for 19 GB of algorithmic traffic).
-    // gx1v7: 0.19 vs 0.30 ms.  tx0.1v3: round 1 measured the generic march faster for the predictor (9.9 vs 11.6 ms, whole
-    // grid); with land elimination the register form wins for both (same box, A/B twice: corrector 6.3 vs 8.1-8.6 ms,
-    // predictor 7.2 vs 7.5-8.1, step -1.2 .. -1.6 ms).  The velocity solve is faster in registers at both sizes.
-    c->reg_thomas_t = c->reg_thomas;
-    if (tun_set(h.tun.reg_thomas_t)) c->reg_thomas_t = h.tun.reg_thomas_t != 0;
-    if (cfg->partial_bottom_cells && tun_on(h.tun.pbc_generic_thomas)) {
-      // partial bottom cells (round 3): every Thomas kernel form carries the PBC branches; pop_tuning.pbc_generic_thomas = 1 keeps
-      // the scratch-staged ones (the cross-check of the register instantiations)
-      c->reg_thomas = false; c->reg_thomas_t = false;
+    if (f.pcsi_two_step || f.pcsi_two_step_dist) {   // two P-CSI iterations per launch: the raw residual of a pair, the fold rows of a tripole
+      if (dev_alloc(c, &c->pcsi_raw, a2)) return 1;
+      std::vector<int> jfold;
+      pcsi_fold_local(h, c->h_srcmap, jfold);
+      if (cfg->ns_boundary == 2 && dev_upload(c, &c->pcsi_jfold, jfold.data(), jfold.size())) return 1;
     }
-    c->pcsi_two_cell = two_cell_shape(g, presum_by_size(c->nchunk, h.nblocks));
-    // two iterations per launch with a tripole fold: the ghost cells beyond the fold are formed as mirror images of their source cells, which
-    // must be cells of this rank (true of any decomposition into bands of whole rows, and of one rank)
-    bool fold_local = true;
-    std::vector<int> jfold(h.nblocks, h.nyb);
-    if (cfg->ns_boundary == 2)
-      for (int lb = 0; lb < h.nblocks; ++lb) {
-        const BlockInfo &B = h.all_blocks[h.local_ids[lb] - 1];
-        if (!(B.j_glob[B.je] < 0)) continue;
-        jfold[lb] = B.je;
-        for (int j = B.je; j < h.nyb; ++j) for (int i = 0; i < h.nxb; ++i) {
-          const int cell = lb * (int)h.n2 + j * h.nxb + i;
-          if (c->h_srcmap[cell] == cell) fold_local = false;
-        }
-      }
-    const bool two_ok = !use_evp(*cfg) && fold_local, two_on = tun_set(h.tun.pcsi_two_step) ? h.tun.pcsi_two_step != 0 : c->pcsi_two_cell;
-    c->pcsi_two_step = two_ok && two_on && h.halo.peers.empty();
-    c->pcsi_two_step_dist = two_ok && two_on && !h.halo.peers.empty();
-    if ((c->pcsi_two_step || c->pcsi_two_step_dist) && dev_alloc(c, &c->pcsi_raw, a2)) return 1;
-    c->pcsi_evp_fused = c->evp_fused_ok && !tun_off(h.tun.evp_wave) && tun_on(h.tun.pcsi_evp_fused);   // measured slower: off unless asked for
-    if (c->pcsi_evp_fused && !c->pcsi_raw && dev_alloc(c, &c->pcsi_raw, a2)) return 1;
-    if ((c->pcsi_two_step || c->pcsi_two_step_dist) && cfg->ns_boundary == 2 && dev_upload(c, &c->pcsi_jfold, jfold.data(), jfold.size())) return 1;
-    if (tun_set(h.tun.pcsi_step2)) c->pcsi_two_cell = two_cell_shape(g, h.tun.pcsi_step2 != 0);
-    c->replicated = !h.halo.peers.empty() && cfg->solver_choice == 1 && !use_evp(*cfg) && h.nblocks_tot <= 8 &&
-                    (long long)h.n2 * h.nblocks_tot <= (4LL << 20) && !tun_on(h.tun.solver_distributed);
-    if (c->replicated) {
+    if (f.replicated) {
       const size_t NG = h.n2 * h.nblocks_tot;
       SolveView &v = c->gv;
       v.g = c->g; v.g.nblocks = h.nblocks_tot;
@@ -923,33 +836,25 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
     HIPCHK(c, hipMemcpy(c->VDC[0], v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->VVC, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
   }
-  if (mix_create(c->h, c->g, c->mix, c->allocs, c->err)) return 1;
+  if (mix_create(c->h, f, c->g, c->mix, c->allocs, c->err)) return 1;
   c->KBL = const_cast<int *>(mix_kpp_kbl(c->mix));
   if (cfg->lsw_absorb != 0 && sw_tables_create(c->h, c->allocs, c->err)) return 1;   // lsw_absorb without KPP's lshort_wave
   if (c->h.sw.CHLI) {   // the default chlorophyll amount the table index was built for
     std::vector<double> chl((size_t)c->g.n2 * c->g.nblocks, 0.25);
     HIPCHK(c, hipMemcpy(c->CHL, chl.data(), chl.size() * sizeof(double), hipMemcpyHostToDevice));
   }
-  // KPP look-ahead (bandwidth-bound grids; POP_KPP_AHEAD=0|1 overrides): second set of KPP outputs, own stream
-  // ... and (round 4) small grids whose pcg solve is the one resident launch: that launch keeps at most one workgroup per CU busy waiting
-  // on memory for 2 ms, the KPP kernels of the next step fill the rest (gx1v7: 3.26 -> 3.09, 3.36 -> 3.18 ms per step, A/B on one box)
-  // (pcg and P-CSI -- 1.85 -> 1.81 ms there; beside the resident ChronGear the look-ahead costs more than it hides: 3.08 -> 3.34 ms per step)
-  const bool resident_solve = (cfg->solver_choice == 1 || cfg->solver_choice == 3) && !use_evp(*cfg) && !tun_off(h.tun.pcg_persist) && h.nranks == 1 && h.nblocks <= 8 &&
-                              h.n2 * h.nblocks <= 250u * 8u * 256u;
-  c->ahead_enabled = cfg->vmix_choice == 3 && c->side && (h.n2 * h.nblocks > (1u << 19) || resident_solve);
-  if (tun_set(h.tun.kpp_ahead)) c->ahead_enabled = cfg->vmix_choice == 3 && c->side && h.tun.kpp_ahead != 0;
+  // KPP look-ahead (Forms::kpp_ahead): second set of KPP outputs, own stream
   // (Gent-McWilliams adds its isopycnal part to VDC after vmix_coeffs -- to the arrays swapped in, at the step they belong to; with the
   // mixed-layer-depth diagnostics the look-ahead writes a second pair HMXL / HMXL_DR that is swapped in with the rest)
-  if (c->ahead_enabled) {
+  if (f.kpp_ahead) {
     for (int n = 0; n < 2; ++n) if (dev_alloc(c, &c->KPPa[n], a3)) return 1;
     if (h.nt > 2 && dev_alloc(c, &c->KPPXa, a3)) return 1;
     if (dev_alloc(c, &c->VDCa[0], (size_t)(h.km + 2) * a2)) return 1;
-    if (c->vdc_shared) c->VDCa[1] = c->VDCa[0];
+    if (f.vdc_shared) c->VDCa[1] = c->VDCa[0];
     else if (dev_alloc(c, &c->VDCa[1], (size_t)(h.km + 2) * a2)) return 1;
     if (dev_alloc(c, &c->VVCa, a3) || dev_alloc(c, &c->HBLTa, a2) || dev_alloc(c, &c->KBLa, a2)) return 1;
     if (c->h.c.kpp_ml_diagnostics == 1 && (dev_alloc(c, &c->HMXLa, a2) || dev_alloc(c, &c->HMXL_DRa, a2))) return 1;
-    if (c->prio_on) HIPCHK(c, hipStreamCreateWithPriority(&c->ahead, hipStreamNonBlocking, c->prio_least));
-    else HIPCHK(c, hipStreamCreateWithFlags(&c->ahead, hipStreamNonBlocking));
+    HIPCHK(c, hipStreamCreateWithFlags(&c->ahead, hipStreamNonBlocking));
     HIPCHK(c, hipEventCreateWithFlags(&c->ev_ahead_fork, hipEventDisableTiming));
     HIPCHK(c, hipEventCreateWithFlags(&c->ev_ahead, hipEventDisableTiming));
   }
@@ -1021,8 +926,8 @@ int pop_get_dim(const pop_ctx *c, const char *name) {
   if (n == "leapfrogts") return c->leapfrogts;
   if (n == "land_skip_active") return c->g.skip;
   if (n == "kpp_ahead_used") return c->ahead_swaps;   // steps whose KPP coefficients were those of the look-ahead (phase_vmix)
-  if (n == "d2t_fused") return c->d2t_next[0] != nullptr;   // the tracer / momentum kernels also form the next step's del4 first Laplacian
-  if (n == "d2u_fused") return c->d2u_next[0] != nullptr;
+  if (n == "d2t_fused") return c->f.d2t_fuse;   // the tracer / momentum kernels also form the next step's del4 first Laplacian
+  if (n == "d2u_fused") return c->f.d2u_fuse;
   if (n == "d2t_last_formed") return c->d2t_last_formed;   // ... and whether the last such launch did (not on averaging steps)
   if (n == "d2u_last_formed") return c->d2u_last_formed;
   if (n == "avg_ts") return c->avg_ts;
@@ -1039,18 +944,18 @@ int pop_get_dim(const pop_ctx *c, const char *name) {
   if (n == "solver_chunks_active") return c->red_active_total;          // chunks with an ocean cell (or work for another rank), all local blocks
   if (n == "pcg_persist_used") return c->persist_used;
   if (n == "pcg_persist_gave_up") return c->persist_gave_up;
-  if (n == "pcsi_evp_fused") return c->pcsi_evp_fused ? 1 : 0;   // P-CSI + EVP: one launch per iteration (k_pcsi_evp_step) in use
-  if (n == "pcsi_two_step") return (c->pcsi_two_step || c->pcsi_two_step_dist) ? 1 : 0;   // P-CSI: two iterations per launch (k_pcsi_step_x2) in use
+  if (n == "pcsi_two_step") return (c->f.pcsi_two_step || c->f.pcsi_two_step_dist) ? 1 : 0;   // P-CSI: two iterations per launch (k_pcsi_step_x2) in use
   if (n == "pcg_persist_workgroups") return c->persist_nwg;
   if (n == "pcg_persist_chunks_per_workgroup") return c->persist_cp;
-  if (n == "solver_path") return c->host_only ? 0 : solver_path_code(c);   // 1 per operation, 2 fused, 3 fused distributed, 4 replicated fused
-  if (n == "thomas_register_tracers") return c->reg_thomas_t && (c->g.km == 60 || c->g.km == 62);    // column-in-registers Thomas kernels in use
-  if (n == "thomas_register_velocity") return c->reg_thomas && (c->g.km == 60 || c->g.km == 62);
-  if (n == "max_blocks_per_rank") return c->max_blocks_per_rank;
+  if (n == "solver_path") return c->h.plan_only ? 0 : c->f.path;   // 1 per operation, 2 fused, 3 fused distributed, 4 replicated fused
+  if (n == "thomas_register_tracers") return c->f.reg_thomas_t;    // column-in-registers Thomas kernels in use
+  if (n == "thomas_register_velocity") return c->f.reg_thomas_u;
+  if (n == "max_blocks_per_rank") return max_blocks_per_rank(c->h);
   if (n == "ocean_columns_local") return (int)c->h.ocean_cols_local;     // POP_CREATE_PLAN_ONLY contexts (-1 otherwise)
   if (n == "ocean_columns_total") return (int)c->h.ocean_cols_total;
   if (n == "lat_aux_region_start") return (c->moc.aux.inited && c->moc.aux.n_reg > 1) ? c->moc.aux.region_start[1] : 0;   // pop_init_transports
   if (n == "moc_stream") return c->moc.requested ? c->moc.stream : 0;
+  if (n.compare(0, 5, "form_") == 0 && !c->h.plan_only) return forms_get(c->f, n.substr(5));   // any entry of the plan (forms.hpp)
   return -1;
 }
 double pop_get_scalar(const pop_ctx *c, const char *name) {
@@ -1301,7 +1206,7 @@ int pop_read_restart(pop_ctx *c, const char *path, int flags) {
   };
   // a failure during the walk (a short file) leaves the fields stored before it in place, as in the reference: there is no rollback
   if (slab_file_read(h, path, fields, (flags & 1) != 0, store, c->err)) return 1;
-  c->full_left = c->land_full_steps;   // land elimination: the state just read is new
+  c->full_left = c->f.land_full_steps;   // land elimination: the state just read is new
   for (bool &b : c->tr_ghosts_ok) b = false;
   for (bool &b : c->uv_ghosts_ok) b = false;
   // init_ts :1665-1681: density of both time levels from the tracers just read
@@ -1341,8 +1246,8 @@ int pop_read_restart(pop_ctx *c, const char *path, int flags) {
 static void land_skip_for_step(pop_ctx *c) {
   // every one of the three rotating time levels must have been the `new` one in a step that ran every workgroup (averaging
   // steps do not rotate: with a short averaging period four steps may not get round), and POP_LAND_FULL_STEPS steps at least
-  if (c->full_left == c->land_full_steps) c->full_seen = 0;      // a reset (set-up, restart, new state) starts the count again
-  const int want = (c->land_skip && c->full_left == 0 && (c->full_seen == 7 || c->land_full_steps == 0)) ? 1 : 0;
+  if (c->full_left == c->f.land_full_steps) c->full_seen = 0;      // a reset (set-up, restart, new state) starts the count again
+  const int want = (c->f.land_skip && c->full_left == 0 && (c->full_seen == 7 || c->f.land_full_steps == 0)) ? 1 : 0;
   if (!want) c->full_seen |= 1 << c->newt;
   if (c->full_left > 0) --c->full_left;
   if (want == c->g.skip) return;
@@ -1435,7 +1340,7 @@ static int phase_vmix(pop_ctx *c) {
     }
     if (ahead_cancel(c)) return 1;
     const MixState ms = kpp_mix_state(c, c->mixt, false);
-    if (mix_vmix_coeffs(c->h, c->g, sp, c->mix, ms, c->stream, c->err)) return 1;
+    if (mix_vmix_coeffs(c->h, c->f, c->g, sp, c->mix, ms, c->stream, c->err)) return 1;
     c->kpp_src_user = false;
     if (cf.vmix_choice == 3 && c->h.nt > 2) return phase_kpp_src_passive(c);
   }
@@ -1449,12 +1354,12 @@ static int kpp_look_ahead(pop_ctx *c) {
   // an averaging step rewrites oldtime and curtime in its tail and does not rotate; the Robert filter rewrites curtime
   // (with the mixed-layer-depth diagnostics on, HMXL / HMXL_DR of the step that just ran stay where they are: the look-ahead writes the second pair)
   // tidal_diag: TIDAL_DIFF ... KVMIX_M have one set of arrays, which holds the step that has run
-  if (!c->ahead_enabled || c->h.c.vmix_choice != 3 || c->avg_ts || c->h.c.tmix_opt == 3 || (c->h.c.kpp_ml_diagnostics == 1 && !c->HMXLa) ||
+  if (!c->f.kpp_ahead || c->avg_ts || c->h.c.tmix_opt == 3 || (c->h.c.kpp_ml_diagnostics == 1 && !c->HMXLa) ||
       (c->tidal.on && c->tidal.nml.tidal_diag)) return 0;
   HIPCHK(c, hipEventRecord(c->ev_ahead_fork, c->stream));
   HIPCHK(c, hipStreamWaitEvent(c->ahead, c->ev_ahead_fork, 0));
   const MixState ms = kpp_mix_state(c, c->curt, true);
-  if (mix_vmix_coeffs(c->h, c->g, step_params(c), c->mix, ms, c->ahead, c->err)) return 1;
+  if (mix_vmix_coeffs(c->h, c->f, c->g, step_params(c), c->mix, ms, c->ahead, c->err)) return 1;
   HIPCHK(c, hipEventRecord(c->ev_ahead, c->ahead));
   c->ahead_valid = true; c->ahead_slot = c->curt;
   return 0;
@@ -1494,9 +1399,7 @@ static void gm_flux_launch(pop_ctx *c, const GmDev &G, const double *X0, const d
   const dim3 G3((c->g.n2 + 255) / 256, c->g.km, c->g.nblocks);
   const StepParams sp = step_params(c);
   double *v1 = (sp.nvdc == 2 && c->VDC[1] != c->VDC[0]) ? c->VDC[1] : nullptr;   // one shared array is added to once
-  if (!tun_off(c->h.tun.gm_flux_tile) && (G.cancellation || G.SF[0])) {
-    // straight-line flux functions, every horizontal face flux formed once (64 x 8 patches computing 63 x 7 cells; 64 x 4 measured 2 % of the step
-    // slower); pop_tuning.gm_flux_tile = 0, or the stream-function terms not stored (gm_sf_stored = 0): the cell-by-cell kernel
+  if (c->f.gm_lds && (G.cancellation || G.SF[0])) {   // every horizontal face flux formed once in 64 x 8 patches; else (or the stream-function terms not stored) cell by cell
     constexpr int R = 8;     // rows of the patch
     const dim3 GT(((c->g.nxb + 62) / 63) * ((c->g.nyb + R - 2) / (R - 1)), (c->g.km + POP_GM_KC - 1) / POP_GM_KC, G3.z);
     with_flags([&](auto CANC, auto ADD) {
@@ -1546,7 +1449,7 @@ static int phase_hmix_tracer(pop_ctx *c, hipStream_t st = nullptr) {   // del4: 
     return 0;
   }
   c->d2t_next_valid = false;
-  return mix_hdifft_del4(c->h, c->g, step_params(c), c->mix, c->TR[0][c->mixt], c->TR[1][c->mixt], c->d2t[0], c->d2t[1], c->S3c, c->S3d, st ? st : c->stream, c->err);
+  return mix_hdifft_del4(c->f.del4_tile_rows, c->g, step_params(c), c->mix, c->TR[0][c->mixt], c->TR[1][c->mixt], c->d2t[0], c->d2t[1], c->S3c, c->S3d, st ? st : c->stream, c->err);
 }
 // advt with tadvect = 3 (advection.F90:1667-1708, 2684-3280; comp_flux_vel_ghost :1014-1120): L(T) of both tracers into lw.XOUT
 static int phase_advt_lw_lim(pop_ctx *c) {
@@ -1584,22 +1487,22 @@ static int phase_tracer_rhs(pop_ctx *c, bool fwd = false) {
   if (c->h.c.hmix_tracer == 4) { a.TMIX[0] = c->d2t[0]; a.TMIX[1] = c->d2t[1]; }   // del4: second Laplacian acts on D2T
   a.UCUR = c->U[c->curt]; a.VCUR = c->V[c->curt]; a.DH = c->DH; a.PCUR = c->PS[c->curt]; a.POLD = c->PS[c->oldt];
   a.c2dtt = c->c2dtt; a.use_kpp_src = (c->h.c.vmix_choice == 3);
-  if (a.use_kpp_src && !c->kpp_src_user && !tun_on(c->h.tun.kpp_src_full)) a.KBL = c->KBL;
+  if (a.use_kpp_src && !c->kpp_src_user && !c->f.kpp_src_full) a.KBL = c->KBL;
   if (c->h.c.lsw_absorb != 0) {   // lsw_absorb: penetrating short wave (add_sw_absorb)
     a.sw_on = 1; a.sw_type = c->h.c.sw_absorption_type; a.sw_ksol = c->h.sw.ksol;
     a.QSW = c->SHF_QSW; a.swabs = c->h.sw.swabs; a.swTr = c->h.sw.Tr; a.swCHLI = c->h.sw.CHLI;
   }
   // the next step's first Laplacian: valid when that step is a leapfrog step whose mix time is this step's current time and nothing
   // rewrites the current tracers before then (no averaging step, no Robert filter) -- the rule of the KPP look-ahead
-  // Gent-McWilliams (r4): the LDS kernel with the mixing tendency given (k_tracer_rhs_lds<., ., false, true>); pop_tuning.gm_flux_tile = 0: the generic kernel
-  const bool gm_lds = c->h.c.hmix_tracer == 3 && !c->g.pbc && !tun_off(c->h.tun.gm_flux_tile);
-  const bool lds_kernel = c->h.c.tadvect == 1 && (c->h.c.hmix_tracer != 3 || gm_lds) && (c->trc_lds_rows == 8 || c->trc_lds_rows == 4);
+  // Gent-McWilliams (r4): the LDS kernel with the mixing tendency given (k_tracer_rhs_lds<., ., false, true>)
+  const bool gm_lds = c->h.c.hmix_tracer == 3 && !c->g.pbc && c->f.gm_lds;
+  const bool lds_kernel = c->h.c.tadvect == 1 && (c->h.c.hmix_tracer != 3 || gm_lds) && (c->f.tracer_lds_rows == 8 || c->f.tracer_lds_rows == 4);
   if (lds_kernel && gm_lds) { a.HDT[0] = c->gm.GTK[0]; a.HDT[1] = c->gm.GTK[1]; }
-  const bool form_next = lds_kernel && !gm_lds && c->d2t_next[0] && !c->avg_ts && c->h.c.tmix_opt != 3 && c->tr_ghosts_ok[c->curt];
+  const bool form_next = lds_kernel && !gm_lds && c->f.d2t_fuse && !c->avg_ts && c->h.c.tmix_opt != 3 && c->tr_ghosts_ok[c->curt];
   if (form_next) { a.D2N[0] = c->d2t_next[0]; a.D2N[1] = c->d2t_next[1]; a.AHF = c->mix.D4AHF; }
   c->d2t_last_formed = form_next;
   if (lds_kernel) {
-    with_value<4, 8>(c->trc_lds_rows, [&](auto R) { launch_tracer_lds<R.value>(c->g, sp, a, c->stream, fwd); });
+    with_value<4, 8>(c->f.tracer_lds_rows, [&](auto R) { launch_tracer_lds<R.value>(c->g, sp, a, c->stream, fwd); });
     if (form_next && !c->phase_timing) {
       if (halo_update_many(c, {{c->d2t_next[0], c->g.km}, {c->d2t_next[1], c->g.km}})) return 1;
       c->d2t_next_valid = true; c->d2t_next_slot = c->curt;
@@ -1644,7 +1547,7 @@ static int phase_passive_rhs(pop_ctx *c) {
       }
       a.HDT[0] = W[0]; a.HDT[1] = W[1];
     }
-    if (cf.hmix_tracer == 4 && mix_hdifft_del4(c->h, c->g, sp, c->mix, X0, X1, W[0], W[1], nullptr, nullptr, c->stream, c->err)) return 1;
+    if (cf.hmix_tracer == 4 && mix_hdifft_del4(c->f.del4_tile_rows, c->g, sp, c->mix, X0, X1, W[0], W[1], nullptr, nullptr, c->stream, c->err)) return 1;
     if (cf.tadvect == 3) {   // the three direction passes of phase_advt_lw_lim on this pair; UTE, VTN, WTKB are those of the step
       LwDev L = c->lw;
       L.XOUT[0] = c->PL[0]; L.XOUT[1] = c->PL[1];
@@ -1688,13 +1591,8 @@ static ImpvmixtArgs impvmixt_args(pop_ctx *c, const double *psfc) {
   a.E = c->E3; a.F = c->F3; a.RHO = c->RHO[c->newt]; a.c2dtt = c->c2dtt; a.nfirst = 1; a.nlast = 2;
   return a;
 }
-// predictor with the forward elimination inside the right-hand-side kernel: bandwidth-bound grids, centred advection
-// through the LDS kernel, generic (scratch-staged) solve -- POP_TRACER_FWD=0|1 overrides
-static bool tracer_fwd_fused(const pop_ctx *c) {
-  const bool can = c->h.c.tadvect == 1 && c->h.c.hmix_tracer != 3 && (c->trc_lds_rows == 4 || c->trc_lds_rows == 8) && c->h.c.lpressure_avg && c->leapfrogts;
-  if (tun_set(c->h.tun.tracer_fwd)) return can && c->h.tun.tracer_fwd != 0;
-  return can && !c->reg_thomas_t;
-}
+// predictor with the forward elimination inside the right-hand-side kernel (Forms::tracer_fwd) on a leapfrog step
+static bool tracer_fwd_fused(const pop_ctx *c) { return c->f.tracer_fwd && c->leapfrogts; }
 static int phase_impvmixt_back(pop_ctx *c) {
   ImpvmixtBackArgs b{};
   for (int n = 0; n < 2; ++n) { b.TNEW[n] = c->TR[n][c->newt]; b.TOLD[n] = c->TR[n][c->oldt]; }
@@ -1704,7 +1602,7 @@ static int phase_impvmixt_back(pop_ctx *c) {
   return 0;
 }
 static int phase_impvmixt_pred(pop_ctx *c) {
-  launch_impvmixt<0, false, false>(c->g, step_params(c), impvmixt_args(c, c->PS[c->curt]), grid_cols(c), c->stream, c->reg_thomas_t, c->h.tun.thomas_pair);
+  launch_impvmixt<0, false, false>(c->g, step_params(c), impvmixt_args(c, c->PS[c->curt]), grid_cols(c), c->stream, c->f.reg_thomas_t, c->f.thomas_pair);
   return 0;
 }
 static int phase_state_new(pop_ctx *c) {
@@ -1741,7 +1639,7 @@ static int phase_hmix_momentum(pop_ctx *c, hipStream_t st = nullptr) {   // del4
     return 0;
   }
   c->d2u_next_valid = false;
-  return mix_hdiffu_del4(c->h, c->g, step_params(c), c->mix, c->U[c->mixt], c->V[c->mixt], c->d2u[0], c->d2u[1], c->S3c, c->S3d, st ? st : c->stream, c->err);
+  return mix_hdiffu_del4(c->f.del4_tile_rows, c->g, step_params(c), c->mix, c->U[c->mixt], c->V[c->mixt], c->d2u[0], c->d2u[1], c->S3c, c->S3d, st ? st : c->stream, c->err);
 }
 static int phase_momentum_rhs(pop_ctx *c, int tj_first = 0, int tj_count = -1, bool last_piece = true) {
   MomentumRhsArgs a{};
@@ -1749,18 +1647,17 @@ static int phase_momentum_rhs(pop_ctx *c, int tj_first = 0, int tj_count = -1, b
   a.RHOOLD = c->RHO[c->oldt]; a.RHOCUR = c->RHO[c->curt]; a.RHONEW = c->RHO[c->newt]; a.VVC = c->VVC; a.DHU = c->DHU;
   if (c->h.c.hmix_momentum == 4) { a.UMIX = c->d2u[0]; a.VMIX = c->d2u[1]; }   // del4: second Laplacian acts on D2U, D2V
   a.UNEW = c->U[c->newt]; a.VNEW = c->V[c->newt]; a.ZX = c->ZX; a.ZY = c->ZY;
-  // 3x3 stencils staged through LDS (kernels_momentum_lds.hpp): 64x8 tiles measured -11 % (tx0.1v3) / -12 % (gx1v7)
-  // against the direct-load kernel, 64x4 +8 %; POP_MOMENTUM_LDS=0|4|8 selects (read at pop_create)
+  // 3x3 stencils staged through LDS (kernels_momentum_lds.hpp; Forms::momentum_lds_rows)
   // the next step's first Laplacian of the velocity (see phase_tracer_rhs; whole-domain launches of the LDS kernel only)
   // (several ranks launch the kernel in three pieces -- interior tile rows, then the rim rows: every piece writes its tiles, the halo
   // update follows the last one)
-  const bool form_next = (c->mom_lds_rows == 8 || c->mom_lds_rows == 4) && c->d2u_next[0] && !c->avg_ts &&
+  const bool form_next = (c->f.momentum_lds_rows == 8 || c->f.momentum_lds_rows == 4) && c->f.d2u_fuse && !c->avg_ts &&
                          c->h.c.tmix_opt != 3 && c->uv_ghosts_ok[c->curt];
   if (form_next) { a.D2N[0] = c->d2u_next[0]; a.D2N[1] = c->d2u_next[1]; a.AMF = c->mix.D4AMF; }
   c->d2u_last_formed = form_next;
   const bool pre = c->h.c.hmix_momentum == 3;   // anis: the friction phase_hmix_momentum formed
   if (pre) { a.HDU = c->HDU; a.HDV = c->HDV; }
-  const bool lds = with_value<4, 8>(c->mom_lds_rows, [&](auto R) { launch_momentum_lds<R.value>(c->g, step_params(c), a, c->stream, tj_first, tj_count, pre); });
+  const bool lds = with_value<4, 8>(c->f.momentum_lds_rows, [&](auto R) { launch_momentum_lds<R.value>(c->g, step_params(c), a, c->stream, tj_first, tj_count, pre); });
   if (!lds) with_flags([&](auto PRE, auto PBC) {
     hipLaunchKernelGGL((k_momentum_rhs<PRE.value, PBC.value>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, step_params(c), a);
   }, pre, c->g.pbc);
@@ -1772,7 +1669,7 @@ static int phase_momentum_rhs(pop_ctx *c, int tj_first = 0, int tj_count = -1, b
 }
 static int phase_impvmixu(pop_ctx *c, hipStream_t st) {
   ImpvmixuArgs a{c->U[c->newt], c->V[c->newt], c->E3, c->U[c->oldt], c->V[c->oldt], c->VVC};
-  launch_impvmixu(c->g, step_params(c), a, grid_cols(c), st ? st : c->stream, c->reg_thomas);
+  launch_impvmixu(c->g, step_params(c), a, grid_cols(c), st ? st : c->stream, c->f.reg_thomas_u, c->f.impvmixu_waves);
   return 0;
 }
 
@@ -1780,11 +1677,10 @@ static int phase_correct(pop_ctx *c) {
   const StepParams sp = step_params(c);
   // the generic Thomas kernel stages E, F through the shared 3-D scratch (E3, F3), which a KPP look-ahead in flight on its own
   // stream also uses (E3 = the Richardson column of the generic k_kpp_interior): the corrector then follows the look-ahead.
-  // The register kernels (km = 60 / 62) touch no scratch and run beside it.
-  const bool reg_kernel = c->reg_thomas_t && (c->g.km == 60 || c->g.km == 62);
-  if (!reg_kernel && c->ahead_valid) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ahead, 0));
-  if (sp.pavg) launch_impvmixt<1, false, true>(c->g, sp, impvmixt_args(c, c->PS[c->newt]), grid_cols(c), c->stream, c->reg_thomas_t, c->h.tun.thomas_pair);
-  else launch_impvmixt<0, true, true>(c->g, sp, impvmixt_args(c, c->PS[c->newt]), grid_cols(c), c->stream, c->reg_thomas_t, c->h.tun.thomas_pair);
+  // The register kernels touch no scratch and run beside it.
+  if (!c->f.reg_thomas_t && c->ahead_valid) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ahead, 0));
+  if (sp.pavg) launch_impvmixt<1, false, true>(c->g, sp, impvmixt_args(c, c->PS[c->newt]), grid_cols(c), c->stream, c->f.reg_thomas_t, c->f.thomas_pair);
+  else launch_impvmixt<0, true, true>(c->g, sp, impvmixt_args(c, c->PS[c->newt]), grid_cols(c), c->stream, c->f.reg_thomas_t, c->f.thomas_pair);
   // passive tracers: TNEW(1) -= TOLD(1) (PSURF(new) - PSURF(old)) / (grav dz(1)) and the standard solve with PSURF(new) on the left-hand
   // side, under pressure averaging (baroclinic.F90:1303-1321) as without it (:1328-1344: mixtime = oldtime on a leapfrog step, curtime on
   // the Euler step, which is what PMIX is) -- the all-tracer form k_impvmixt<0, PRE>, a pair per launch; then reset_passive_tracers (:1458-1460)
@@ -1795,7 +1691,7 @@ static int phase_correct(pop_ctx *c) {
       a.TNEW[s] = c->TR[n + s][c->newt]; a.TOLD[s] = c->TR[n + s][c->oldt]; a.TCUR[s] = c->TR[n + s][c->curt];
       a.VDC[s] = c->VDC[sp.nvdc == 2 ? 1 : 0];
     }
-    launch_impvmixt<0, true, false>(c->g, sp, a, grid_cols(c), c->stream, c->reg_thomas_t, c->h.tun.thomas_pair);
+    launch_impvmixt<0, true, false>(c->g, sp, a, grid_cols(c), c->stream, c->f.reg_thomas_t, c->f.thomas_pair);
   }
   return passive_reset(c, c->newt);
 }
@@ -1825,14 +1721,14 @@ int pop_baroclinic_driver(pop_ctx *c) {
   // tavg: the velocities and, unless the Robert filter takes them in step_rf, the tracers of the cur level (baroclinic.F90:772-816)
   if (c->tavg.active && (tavg_site(c, TS_STATE) || (c->h.c.tmix_opt != 3 && tavg_site(c, TS_TRACER)))) return 1;
   // del4 first Laplacians / the anisotropic friction beside the vertical-mixing coefficients: they read only mix-time fields
-  const bool tr_side = c->side_del4 && c->h.c.hmix_tracer != 3;
-  const bool fork = c->mom_side || tr_side;
+  const bool tr_side = c->f.del4_side && c->h.c.hmix_tracer != 3;
+  const bool fork = c->f.mom_side || tr_side;
   if (fork) {
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
     if (tr_side && phase_hmix_tracer(c, c->side)) return 1;
     HIPCHK(c, hipEventRecord(c->ev_d2t, c->side));
-    if (c->mom_side && phase_hmix_momentum(c, c->side)) return 1;
+    if (c->f.mom_side && phase_hmix_momentum(c, c->side)) return 1;
     HIPCHK(c, hipEventRecord(c->ev_d2u, c->side));
   }
   if (phase_vmix(c)) return 1;
@@ -1845,7 +1741,7 @@ int pop_baroclinic_driver(pop_ctx *c) {
   // several ranks: the exchange of the new tracers' ghost rows runs on the communication stream while the launch stream
   // forms the density and the momentum right-hand side of every tile that reads no ghost row of another rank; the first
   // and last tile rows follow once the rows have arrived (same kernels on disjoint tiles: bitwise the serial result)
-  const int mrows = c->mom_lds_rows;
+  const int mrows = c->f.momentum_lds_rows;
   const bool overlap = sp.pavg && halo_async_ok(c) && (mrows == 4 || mrows == 8) && !c->h.c.ns_boundary;
   const int mtiles_j = overlap ? (c->g.nyb - 2 * NGHOST + mrows - 1) / mrows : 0;
   if (sp.pavg) {
@@ -1854,7 +1750,7 @@ int pop_baroclinic_driver(pop_ctx *c) {
       HaloAsync HA;
       if (halo_many_begin(c, {{c->TR[0][c->newt], c->g.km}, {c->TR[1][c->newt], c->g.km}}, HA)) return 1;
       state_new_rows(c, NGHOST, c->g.nyb - NGHOST);                      // physical rows: own cells + ghosts copied inside the rank
-      if (c->mom_side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2u, 0));
+      if (c->f.mom_side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2u, 0));
       else if (phase_hmix_momentum(c)) return 1;
       if (phase_momentum_rhs(c, 1, mtiles_j - 2, false)) return 1;      // interior tile rows
       if (halo_many_end(c, HA)) return 1;
@@ -1863,26 +1759,20 @@ int pop_baroclinic_driver(pop_ctx *c) {
     } else {
       if (halo_update_many(c, {{c->TR[0][c->newt], c->g.km}, {c->TR[1][c->newt], c->g.km}})) return 1;
       if (phase_state_new(c)) return 1;
-      if (c->mom_side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2u, 0));
+      if (c->f.mom_side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2u, 0));
       else if (phase_hmix_momentum(c)) return 1;
       if (phase_momentum_rhs(c)) return 1;
     }
   } else {
-    if (c->mom_side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2u, 0));
+    if (c->f.mom_side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2u, 0));
     else if (phase_hmix_momentum(c)) return 1;
     if (phase_momentum_rhs(c)) return 1;
   }
-  // the implicit vertical mixing of U, V is not needed before the step tail: with the register kernel (no shared scratch)
-  // it runs on the side stream beside the barotropic solver, whose one-workgroup reduction kernels leave the GPU idle
-  // bandwidth-bound grids: held back until the barotropic solve has finished and launched then with the barotropic velocity added on
-  // the way out (k_impvmixu_reg<., ., true>): the separate k_add_barotropic pass over U, V(new) is gone.  Nothing between here and
+  // the implicit vertical mixing of U, V is not needed before the step tail (Forms::vmixu): on the side stream beside the barotropic solver,
+  // or held back until the solve has finished and launched then with the barotropic velocity added on the way out.  Nothing between here and
   // baroclinic_correct_adjust reads U, V(new); a caller that does (any field access: join_side) gets the plain kernel first.
-  // Not across a tripole fold (the sum follows the halo update there).  POP_VMIXU_DEFER=0|1 overrides the size rule.
-  const int defer_env = tun_or(c->h.tun.vmixu_defer, -1);
-  const bool defer = c->side && impvmixu_add_available(c->g, c->reg_thomas) && c->h.c.ns_boundary != 2 && !tun_on(c->h.tun.btrop_inline) &&
-                     !tun_on(c->h.tun.vmixu_inline) && (defer_env >= 0 ? defer_env != 0 : (long long)c->g.n2 * c->g.nblocks > (1 << 19));
-  if (defer) c->vmixu_deferred = true;
-  else if (c->side && c->reg_thomas && (c->g.km == 60 || c->g.km == 62) && !tun_on(c->h.tun.vmixu_inline)) {
+  if (c->f.vmixu == VMIXU_DEFERRED) c->vmixu_deferred = true;
+  else if (c->f.vmixu == VMIXU_SIDE) {
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
     if (phase_impvmixu(c, c->side)) return 1;
@@ -2012,10 +1902,10 @@ int pop_baroclinic_correct_adjust(pop_ctx *c) {
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
     ImpvmixuArgs a{c->U[c->newt], c->V[c->newt], c->E3, c->U[c->oldt], c->V[c->oldt], c->VVC, c->UB[c->newt], c->VB[c->newt]};
-    launch_impvmixu_add(c->g, step_params(c), a, grid_cols(c), c->side);
+    launch_impvmixu_add(c->g, step_params(c), a, grid_cols(c), c->side, c->f.impvmixu_waves);
     HIPCHK(c, hipEventRecord(c->ev_vmixu, c->side));
     c->vmixu_pending = true; c->btrop_added = true;
-  } else if (c->side && !tun_on(c->h.tun.btrop_inline) && c->h.c.ns_boundary != 2) {
+  } else if (!c->f.btrop_inline) {
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
     if (phase_add_btrop(c, c->side)) return 1;
@@ -2406,8 +2296,8 @@ int pop_comm_init_rccl(pop_ctx *c, const unsigned char *id128) {
   // rank 0 and travels over the first communicator, one byte per double (exact under the sum with the other ranks'
   // zeros), so the host has nothing more to broadcast.  POP_RCCL_OVERLAP=0 keeps everything on one communicator.
   // (POP_RCCL_OVERLAP=2 also creates it on a single rank, so that the whole set-up can be checked against the real librccl)
-  const int want2 = tun_or(c->h.tun.rccl_overlap, 1);
-  if (c->side && want2 != 0 && (c->h.nranks > 1 || want2 == 2)) {
+  const int want2 = c->f.rccl_overlap;
+  if (c->f.side_stream && want2 != 0 && (c->h.nranks > 1 || want2 == 2)) {
     std::vector<double> enc(128, 0.0);
     RcclApi::UniqueId id2;
     if (c->h.rank == 0) {
@@ -2492,7 +2382,7 @@ int pop_comm_selftest(pop_ctx *c) {
 int pop_set_reduce_buffer(pop_ctx *c, void *dev_redbuf, long long doubles) { c->redbuf = (double *)dev_redbuf; c->red_doubles = doubles; return 0; }
 long long pop_reduce_buffer_doubles(const pop_ctx *c) {
   long long n = 4LL * c->h.nblocks_tot;
-  if (c->replicated) n = std::max(n, 2LL * (long long)c->h.n2 * c->h.nblocks_tot);
+  if (c->f.replicated) n = std::max(n, 2LL * (long long)c->h.n2 * c->h.nblocks_tot);
   return n;
 }
 int pop_set_stream(pop_ctx *c, void *hip_stream) {   // run on the host framework's stream (e.g. torch's current stream)

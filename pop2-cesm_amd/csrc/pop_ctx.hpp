@@ -72,6 +72,7 @@ struct MocState {
 
 struct pop_ctx {
   HostModel h;
+  Forms f;                                // the plan: every kernel-form and schedule choice, resolved once at create (forms.hpp)
   bool host_only = true;
   std::string err;
   hipStream_t stream = nullptr;
@@ -88,8 +89,7 @@ struct pop_ctx {
   double *DH = nullptr, *DHU = nullptr, *ZX = nullptr, *ZY = nullptr, *UH = nullptr, *VH = nullptr;
   double *W3 = nullptr, *W4 = nullptr, *RHS = nullptr, *centerWgt = nullptr;
   double *E3 = nullptr, *F3 = nullptr, *S3a = nullptr, *S3b = nullptr, *S3c = nullptr, *S3d = nullptr;
-  // del4: the first Laplacians need only the mix-time fields, so they run on a side stream beside the vertical-mixing
-  // coefficients (own output buffers d2t / d2u instead of the shared scratch; POP_DEL4_SIDE=0: in line, scratch reused)
+  // del4: the first Laplacians on the side stream (Forms::del4_side) write own output buffers d2t / d2u; in line they reuse the shared scratch
   double *d2t[2] = {nullptr, nullptr}, *d2u[2] = {nullptr, nullptr};
   // hmix_momentum = 3: the friction hdiffu_aniso forms (3-D, read by the momentum kernel) and the variable viscosities F_PARA, F_PERP
   double *HDU = nullptr, *HDV = nullptr, *FPARA = nullptr, *FPERP = nullptr;
@@ -107,20 +107,18 @@ struct pop_ctx {
   bool uv_ghosts_ok[3] = {true, true, true};
   bool d2t_last_formed = false, d2u_last_formed = false;   // did the last tracer / momentum launch write the next step's field (bench accounting)
   hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_d2t = nullptr, ev_d2u = nullptr, ev_vmixu = nullptr;
-  bool mom_side = false;   // phase_hmix_momentum on the side stream: del4 with side_del4; anis unless pop_tuning.aniso_side = 0
-  bool side_del4 = false, vmixu_pending = false, btrop_added = false, vmixu_deferred = false;   // implicit vertical mixing of U,V in flight on the side stream
+  bool vmixu_pending = false, btrop_added = false, vmixu_deferred = false;   // implicit vertical mixing of U,V in flight on the side stream
   double *HBLT = nullptr, *HMXL = nullptr, *HMXL_DR = nullptr;
   MixDev mix{};
-  // KPP look-ahead: the vertical-mixing coefficients of the NEXT step depend only on this step's curtime fields (its
-  // mixtime on a leapfrog step), so pop_step computes them on a third stream beside the barotropic solver (VALU-bound
-  // work beside bandwidth-bound work) into a second set of output fields; the next step swaps the sets in.
-  bool vdc_shared = false;
+  // KPP look-ahead (Forms::kpp_ahead): the vertical-mixing coefficients of the NEXT step depend only on this step's curtime fields (its
+  // mixtime on a leapfrog step), so pop_step computes them on a third stream beside the barotropic solver into a second set of output
+  // fields; the next step swaps the sets in.
   bool kpp_src_user = false;   // the caller wrote KPP_SRC (pop_set_field): read it at every level until KPP has run again
   bool src_dirty = true, src_dirty_alt = true;   // KPP_SRC / KPPa may hold non-zeros below the KBL stored with them: the next evaluation into that set clears every level
   double *VDCa[2] = {nullptr, nullptr}, *VVCa = nullptr, *KPPa[MAXNT] = {}, *HBLTa = nullptr, *HMXLa = nullptr, *HMXL_DRa = nullptr;
   int *KBL = nullptr, *KBLa = nullptr;   // KBL that belongs to KPP_SRC / KPPa (the tracer kernel reads KPP_SRC down to it)
   hipStream_t ahead = nullptr; hipEvent_t ev_ahead_fork = nullptr, ev_ahead = nullptr;
-  bool ahead_enabled = false, ahead_valid = false; int ahead_slot = -1, ahead_swaps = 0;   // ahead_swaps: steps that took their coefficients from the look-ahead
+  bool ahead_valid = false; int ahead_slot = -1, ahead_swaps = 0;   // ahead_swaps: steps that took their coefficients from the look-ahead
   // solver
   double *R = nullptr, *S0 = nullptr, *S1 = nullptr, *Q = nullptr, *Z = nullptr, *AZ = nullptr;
   double *partial = nullptr, *blocksum = nullptr;
@@ -134,11 +132,11 @@ struct pop_ctx {
   // fused-solver interval graphs, keyed by the solution array and the solver's variant of the interval (graph_for)
   struct IntervalGraph { const double *key; int variant; hipGraphExec_t exec; };
   std::vector<IntervalGraph> graphs;
-  bool fused_ok = false, evp_fused_ok = false, replicated = false, grid_from_input = false;
-  // land elimination: the first land_full_steps steps after set-up / a restart / a new state run every workgroup (they write
+  bool grid_from_input = false;
+  // land elimination (Forms::land_skip, land_full_steps): the first land_full_steps steps after set-up / a restart / a new state run every workgroup (they write
   // the state-independent values of the land tiles), later steps skip workgroups without an ocean cell (DevGrid::skip)
-  bool land_skip = true; int land_full_steps = 4, full_left = 4, full_seen = 0; double land_fraction = 0.0;
-  // the resident pcg of small grids (kernels_pcg_persist.hpp; pop_tuning.pcg_persist): one plan per solver view
+  int full_left = 4, full_seen = 0; double land_fraction = 0.0;
+  // the resident pcg of small grids (kernels_pcg_persist.hpp; Forms::persist): one plan per solver view
   struct PersistPlan {
     const void *key = nullptr; bool ok = false; std::string why;
     int CP = 0, nwg = 0, nwin_max = 0, nslots = 0;
@@ -154,16 +152,8 @@ struct pop_ctx {
   int persist_gave_up = 0;                                 // resident solves that gave up a wait (then never used again in this model)
   int red_active_total = 0;                                // fused solver kernels: chunks that have work, summed over the local blocks
   int persist_nwg = 0, persist_cp = 0;                     // shape of the last resident launch
-  bool pcsi_two_cell = false;   // fused P-CSI step with two cells per thread (large grids, even row pitch; POP_PCSI_STEP2=0|1)
-  bool pcsi_two_step = false;   // ... and two iterations per launch (k_pcsi_step_x2; pop_tuning.pcsi_two_step)
-  bool pcsi_two_step_dist = false;   // ... with blocks spread over ranks
-  double *pcsi_raw = nullptr;   // the residual of the pair before a check (k_pcsi_step_x2<true> -> k_pcsi_rr_chunks)
+  double *pcsi_raw = nullptr;   // P-CSI, two iterations per launch: the residual of the pair before a check (k_pcsi_step_x2<true> -> k_pcsi_rr_chunks)
   int *pcsi_jfold = nullptr;    // tripole: per local block, the first array row beyond the fold (PcsiArgs::jfold)
-  bool pcsi_evp_fused = false;  // P-CSI + EVP: iteration and sub-block solves in one launch (k_pcsi_evp_step; pop_tuning.pcsi_evp_fused)
-  bool reg_thomas_t = true;
-  int trc_lds_rows = 4;                                    // tracer RHS (centred advection): LDS tile rows, 0 = direct loads
-  int mom_lds_rows = 4;                                    // momentum RHS: LDS tile rows (0 = direct-load kernel)
-  bool reg_thomas = true;                                  // column-in-registers Thomas kernels (km = 60, 62)
   SolveView gv{};                                         // replicated barotropic mode: all blocks
   double *gTAREA = nullptr; int *gKMT = nullptr;
   int nchunk = 0, numIterations = 0;
@@ -177,7 +167,6 @@ struct pop_ctx {
   int nsend_all = 0, nrecv_all = 0;
   // fused distributed solvers: per-cell send entries / receive slots (FusedArgs::sendmap, rmap), nz = 1 message order
   int *sendmap = nullptr, *send_off = nullptr, *send_slot = nullptr, *rmap = nullptr;
-  int max_blocks_per_rank = 0;                             // over all ranks: choices between collective code paths must not depend on the rank
   bool halo_ns_only = false;                               // every ghost cell owned by another rank lies in a ghost ROW (j-band shards)
   pop_exchange_fn xchg_side = nullptr;                     // the same exchange on the communication stream (own communicator), or null
   hipStream_t comm_side = nullptr;                         // stream of those exchanges (not `side`: impvmixu runs there beside the solver)
@@ -227,7 +216,6 @@ struct pop_ctx {
   bool timing = false;
   bool phase_timing = false;   // inside pop_time_phase: kernels only
   double *op_scratch = nullptr;   // pop_operator_host: four block-sized 2-D arrays
-  bool prio_on = false; int prio_least = 0;   // stream priorities in use; the lowest one
   TavgState tavg;
   DiagState diag;
   MocState moc;

@@ -81,12 +81,11 @@
       integer (c_int) :: kpp_lazy, kpp_ushear_hint, kpp_ushear_margin, kpp_side_stream, kpp_interior_generic
       integer (c_int) :: kpp_src_full, solver_unfused, solver_nograph, solver_presum, solver_distributed, solver_overlap_off
       integer (c_int) :: fpcg_b2, pcsi_step2, halo_separate, halo_overlap_off, rccl_overlap, evp_wave
-      integer (c_int) :: fpcg_a_pair, kpp_sparse, pbc_generic_thomas, pbc_generic_kpp, stream_priority, gm_sf_stored, state3d_levels
+      integer (c_int) :: fpcg_a_pair, kpp_sparse, pbc_generic_thomas, pbc_generic_kpp, gm_sf_stored, state3d_levels
       integer (c_int) :: pcg_persist
       integer (c_int) :: gm_flux_tile
       integer (c_int) :: pcsi_two_step
       integer (c_int) :: block_sums_relay
-      integer (c_int) :: pcsi_evp_fused
       integer (c_int) :: aniso_side
       integer (c_int) :: submeso_all_levels
    end type pop_tuning

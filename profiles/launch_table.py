@@ -133,8 +133,23 @@ def cfgs():
     add("kpp-km70", K(70))
     add("kpp-km70-col3", K(70), {"POP_KPP_COL": "3"})
     add("kpp-km70-col7", K(70), {"POP_KPP_COL": "7", "POP_XCD_REMAP": "0"})
+    # the barotropic solvers: every path of solver_run on four blocks of `tiny` (the fused forms need <= 8 blocks), the resident launch and
+    # the two-launch iteration behind it, with and without the interval graphs; on `wide` (165 chunks, land) with the compacted chunk list
+    # in use from the first step
+    four = {"block_size_x": 24, "block_size_y": 20}
+    no_persist = {"POP_PCG_PERSIST": "0"}
+    add("solver-chrongear", dict(four, solver_choice=2))
+    add("solver-pcsi", dict(four, solver_choice=3))
+    add("solver-pcsi-evp", dict(four, solver_choice=3, preconditioner_choice=1))
+    add("solver-pcg-evp", dict(four, preconditioner_choice=1))
+    add("solver-pcg-persist0", four, no_persist)
+    add("solver-pcg-unfused", four, {"POP_SOLVER_UNFUSED": "1"})
+    add("solver-pcg-nograph", four, dict(no_persist, POP_SOLVER_NOGRAPH="1"))
+    add("solver-pcsi-two-step", dict(four, solver_choice=3), dict(no_persist, POP_PCSI_TWO_STEP="1"))
+    for name, choice in (("pcg", 1), ("chrongear", 2), ("pcsi", 3)):
+        add("solver-wide-%s-list" % name, {"solver_choice": choice}, dict(no_persist, POP_LAND_FULL_STEPS="0"), base="wide")
     # the most rewritten launch paths first, the untested vertical grids last (a --budget cuts the list at its end)
-    order = lambda x: 2 if x["id"].startswith("kpp-km70") else 0 if x["id"].startswith(("kpp", "big")) else 1
+    order = lambda x: 2 if x["id"].startswith("kpp-km70") else 0 if x["id"].startswith(("kpp", "big", "solver")) else 1
     return sorted(c, key=order)
 
 

@@ -1,6 +1,6 @@
 """Land elimination (tests/test_gpu_land.py) with the schemes that were added after it: Gent-McWilliams, the submesoscale scheme,
 anisotropic viscosity, Jayne tidal mixing and the latitude-varying background inside the KPP look-ahead, frazil ice, partial bottom
-cells, time-averaged output, the exact restart -- and the five pop_tuning fields no other test names.
+cells, time-averaged output, the exact restart -- and the four pop_tuning fields no other test names.
 
 From the fifth step after set-up, a restart or a new state every workgroup whose tile or 256-cell run holds no ocean cell returns at
 once (kernels_common.hpp col_setup, patch_cell, land_tile, land_run, red_land).  That rests on one claim: what the full kernels write
@@ -338,30 +338,26 @@ def test_exact_restart_across_the_switch(pkg, tmp_path, fresh):
     a.close(); b.close()
 
 
-# ---- 5. the five tuning fields without a test ------------------------------------------------------------------------------------------
+# ---- 5. the four tuning fields without a test ------------------------------------------------------------------------------------------
 KM60 = dict(vmix_choice=3, km=60, stepped_bathymetry=1)
-KPP24 = dict(vmix_choice=3, km=24)
 WIDE_KPP_DEL4 = dict(DEL4, vmix_choice=3)
-# (grid, pop_config keywords, tuning both models share, [tuning of each X], pop_get_dim values on D that show the replaced form in use,
-#  steps).  Where the library reads the field:
-#   red_band      pop_amd.hip:369 -> kernels_common.hpp red_grid_x / red_chunk: which workgroup takes which 256-cell chunk of the 2-D reduction
-#                 and fused solver kernels.  pcg on `wide` (165 chunks) with the resident solve off, so that the fused two-launch iteration
-#                 runs; without land elimination the compacted chunk list is not active, with it (past step 5) red_land
-#                 derives the cells of its chunk from red_chunk
-#   lds_order     pop_amd.hip:368 -> kernels_common.hpp lds_tile / lds_launch_x: the LDS-tiled momentum and tracer right-hand sides, and the
-#                 order in which the compacted tile lists lds_act4 / lds_act8 are built (pop_amd.hip:497-527), used past step 5
-#   vmixu_inline  pop_amd.hip:1882-1885: at km = 60 with the register Thomas kernel the implicit vertical mixing of U, V runs on the side
-#                 stream beside the solver; 1 puts it on the launch stream
-#   btrop_inline  pop_amd.hip:1882, :2018: the barotropic velocity is added on the side stream beside the tracer corrector; 1 adds it in the
-#                 step tail
-#   stream_priority pop_amd.hip:345: the launch stream created above the side streams
-# All five are bitwise neutral in whole (none regroups a sum), so every row is compared with np.array_equal.
+# (grid, pop_config keywords, tuning both models share, [tuning of each X], pop_get_dim values, steps).  A plain value holds on D and on every
+# X: it shows the replaced form in use.  A pair (value on D, [value on each X]) is the entry of the library's plan that the row's field
+# governs (pop_get_dim("form_*")): the request changed the form that runs.
+#   red_band      which workgroup takes which 256-cell chunk of the 2-D reduction and fused solver kernels.  pcg on `wide` (165 chunks) with
+#                 the resident solve off, so that the fused two-launch iteration runs; without land elimination the compacted chunk list is
+#                 not active, with it (past step 5) red_land derives the cells of its chunk from red_chunk
+#   lds_order     the LDS-tiled momentum and tracer right-hand sides, and the order in which the compacted tile lists are built, used past step 5
+#   vmixu_inline  at km = 60 with the register Thomas kernel the implicit vertical mixing of U, V runs on the side stream beside the solver
+#                 (form_vmixu 1); 1 puts it on the launch stream (0)
+#   btrop_inline  the barotropic velocity is added on the side stream beside the tracer corrector; 1 adds it in the step tail
+# All four are bitwise neutral in whole (none regroups a sum), so every row is compared with np.array_equal.
 TUNING = {
-    "red_band": ("wide", {}, {"pcg_persist": 0, "land_skip": 0}, [{"red_band": 0}], {"pcg_persist_used": 0, "land_skip_active": 0}, 5),
-    "red_band-tiles-skipped": ("wide", {}, dict(SKIP, pcg_persist=0), [{"red_band": 0}], {"pcg_persist_used": 0, "land_skip_active": 1}, 7),
-    "lds_order": ("wide", {}, SKIP, [{"lds_order": 0, "momentum_lds": r, "tracer_lds": r} for r in (4, 8)], {"land_skip_active": 1}, 7),
-    "vmixu_inline-btrop_inline": ("tiny", KM60, {}, [{"vmixu_inline": 1}, {"btrop_inline": 1}], {"thomas_register_velocity": 1}, 5),
-    "stream_priority": ("tiny", KPP24, {}, [{"stream_priority": 1}], {}, 5),
+    "red_band": ("wide", {}, {"pcg_persist": 0, "land_skip": 0}, [{"red_band": 0}], {"pcg_persist_used": 0, "land_skip_active": 0, "form_red_band": (1, [0])}, 5),
+    "red_band-tiles-skipped": ("wide", {}, dict(SKIP, pcg_persist=0), [{"red_band": 0}], {"pcg_persist_used": 0, "land_skip_active": 1, "form_red_band": (1, [0])}, 7),
+    "lds_order": ("wide", {}, SKIP, [{"lds_order": 0, "momentum_lds": r, "tracer_lds": r} for r in (4, 8)], {"land_skip_active": 1, "form_lds_order": (1, [0, 0])}, 7),
+    "vmixu_inline-btrop_inline": ("tiny", KM60, {}, [{"vmixu_inline": 1}, {"btrop_inline": 1}],
+                                  {"thomas_register_velocity": 1, "form_vmixu": (1, [0, 1]), "form_btrop_inline": (0, [0, 1])}, 5),
 }
 
 
@@ -383,7 +379,7 @@ def test_tuning_field_is_bitwise_neutral(pkg, row):
         out = {(f, n, tl): m.get(f, tl, n) for f, n in FIELDS for tl in (0, 1)}
         return m, iters, out
     defaults = {}
-    for xt in xs:
+    for ix, xt in enumerate(xs):
         shared = dict(common, **{f: v for f, v in xt.items() if f in ("momentum_lds", "tracer_lds")})
         own = {f: v for f, v in xt.items() if f not in shared}
         key = tuple(sorted(shared.items()))
@@ -393,7 +389,7 @@ def test_tuning_field_is_bitwise_neutral(pkg, row):
             for f in own:
                 assert default[f] is None, "%s is set from outside the test (environment): %r" % (f, default[f])
             for d, v in dims.items():
-                assert D.dim(d) == v, (d, D.dim(d))
+                assert D.dim(d) == (v[0] if isinstance(v, tuple) else v), (d, D.dim(d))
             if "land_skip" in shared:
                 assert D.scalar("land_tile_fraction") > 0.05
             D.close()
@@ -404,7 +400,7 @@ def test_tuning_field_is_bitwise_neutral(pkg, row):
         for f, v in dict(shared, **own).items():
             assert resolved[f] == v, "%s: asked for %d, the library holds %r" % (f, v, resolved[f])
         for d, v in dims.items():
-            assert X.dim(d) == v, (d, X.dim(d))
+            assert X.dim(d) == (v[1][ix] if isinstance(v, tuple) else v), (d, X.dim(d))
         assert it_x == it_d, xt
         assert not [k for k in out_d if not np.array_equal(out_x[k], out_d[k])], xt
         assert np.isfinite(out_x[("TRACER", 0, 1)]).all() and np.ptp(out_x[("UVEL", 0, 1)]) > 0.0

@@ -90,39 +90,36 @@ KM60 = dict(vmix_choice=3, km=60, stepped_bathymetry=1)
 KPP_DEL4 = dict(KPP, **DEL4)
 GM = {"hmix_tracer": 3}
 AT_LEAST_2 = -2
-# (configuration, its keywords, pop_tuning fields of model X, pop_get_dim values that show the form in use on X -- "D:" on D -- where the
-# library has one).  pop_get_tuning returns the request, so for the fields without such a value the row was checked against the code: the
-# field alters a launch on the row's configuration.  Where it reads a field: tracer_lds pop_amd.hip:856 / :1602 (4 is the default),
-# vdc_shared :655, side_stream :666, del4_side :672, del4_tile kernels_common.hpp:174 (0 is the default here), d2t_fuse :677, kpp_col
-# kernels_kpp.hpp:1516 (1 is the default here), kpp_src_full pop_amd.hip:1587, kpp_side_stream kernels_kpp.hpp:1467, gm_flux_tile
-# pop_amd.hip:1497 / :1595, gm_sf_stored :609, submeso_all_levels :627, halo_separate launch_halo.hpp:65.
-B2 = ([("tiny", {}, {"tracer_lds": v}, {}) for v in (0, 4, 8)] +
+# (configuration, its keywords, pop_tuning fields of model X, pop_get_dim values that show the form in use on X -- "D:" on D).
+# pop_get_tuning returns the request; what ran is the library's plan, one entry per choice, which pop_get_dim("form_<entry>") returns: every row
+# names the entry its field governs with the value X must hold (and D's where the row's point is that they differ).  tracer_lds 4, del4_tile 0,
+# kpp_col 1 and thomas_pair 0 are also what the rules choose on this grid.
+B2 = ([("tiny", {}, {"tracer_lds": v}, {"form_tracer_lds_rows": v}) for v in (0, 4, 8)] +
      [("tiny", KM60, {"reg_thomas_t": v}, {"thomas_register_tracers": v}) for v in (0, 1)] +
-     # thomas_pair acts at one site only, the (T, S) corrector under pressure averaging (launch_impvmixt<1, ., .>, kernels_thomas_reg.hpp
-     # :291; pop_amd.hip:1786), with the register kernels and one shared diffusivity array (KPP): these two rows run with lpressure_avg = 1,
+     # thomas_pair acts at one site only, the (T, S) corrector under pressure averaging (launch_impvmixt<1, ., .>), with the register kernels and one shared diffusivity array (KPP): these two rows run with lpressure_avg = 1,
      # X against D bitwise and P2 / P3 in place of the twin.  0 is also what the size rule chooses on `tiny`; 1 is k_impvmixt2_reg.
-     [("tiny", KM60, {"thomas_pair": v}, {"thomas_register_tracers": 1, "pavg": 1}) for v in (0, 1)] +
-     [("tiny", KPP, {"vdc_shared": 0}, {}),
-      ("tiny", KPP_DEL4, {"side_stream": 0}, {"kpp_ahead_used": 0}),
-      ("tiny", DEL4, {"del4_side": 0}, {})] +
-     [("tiny", DEL4, {"del4_tile": v}, {}) for v in (0, 2, 16)] +
+     [("tiny", KM60, {"thomas_pair": v}, {"thomas_register_tracers": 1, "pavg": 1, "form_thomas_pair": v}) for v in (0, 1)] +
+     [("tiny", KPP, {"vdc_shared": 0}, {"form_vdc_shared": 0, "D:form_vdc_shared": 1}),
+      ("tiny", KPP_DEL4, {"side_stream": 0}, {"kpp_ahead_used": 0, "form_side_stream": 0, "D:form_side_stream": 1}),
+      ("tiny", DEL4, {"del4_side": 0}, {"form_del4_side": 0, "D:form_del4_side": 1})] +
+     [("tiny", DEL4, {"del4_tile": v}, {"form_del4_tile_rows": v}) for v in (0, 2, 16)] +
      [("tiny", DEL4, {"d2t_fuse": 1}, {"d2t_fused": 1}),
       # the buffers of the first Laplacian formed ahead belong to the side-stream form (pop_create_tuned allocates them under del4_side):
       # asked for together with del4_side = 0 the library keeps k_del4_d2t in line, and says so
       ("tiny", DEL4, {"d2t_fuse": 1, "del4_side": 0}, {"d2t_fused": 0})] +
-     [("tiny", KPP, {"kpp_col": v}, {}) for v in (1, 2, 4, 8, 16, 31)] +
-     [("tiny", KPP, {"kpp_src_full": 1}, {}),
-      # kpp_sparse is read where the column march runs (kernels_kpp.hpp:1577: sparse = march && ...; march needs bits 3 and 4 of kpp_col,
-      # which the size rule leaves off here): the march with the streaming boundary-layer kernel, against the defaults
-      ("tiny", KPP, {"kpp_col": 31, "kpp_sparse": 0}, {}),
-      ("tiny", KPP, {"kpp_side_stream": 0}, {}),
-      # one block: there the size rule switches the look-ahead on (beside the resident solve, pop_amd.hip:937-939), so D runs it
+     [("tiny", KPP, {"kpp_col": v}, {"form_kpp_col": v}) for v in (1, 2, 4, 8, 16, 31)] +
+     [("tiny", KPP, {"kpp_src_full": 1}, {"form_kpp_src_full": 1, "D:form_kpp_src_full": 0}),
+      # kpp_sparse acts where the column march runs (sparse = march && ...; march needs bits 3 and 4 of kpp_col, which the size rule leaves
+      # off here): the march with the streaming boundary-layer kernel, against the defaults
+      ("tiny", KPP, {"kpp_col": 31, "kpp_sparse": 0}, {"form_kpp_march": 1, "form_kpp_sparse": 0, "D:form_kpp_march": 0}),
+      ("tiny", KPP, {"kpp_side_stream": 0}, {"form_kpp_side": 0, "D:form_kpp_side": 1}),
+      # one block: there the size rule switches the look-ahead on (beside the resident solve), so D runs it
       ("tiny", dict(KPP, block_size_x=48, block_size_y=40), {"kpp_ahead": 0}, {"kpp_ahead_used": 0, "D:kpp_ahead_used": AT_LEAST_2}),
       ("tiny", KPP, {"kpp_ahead": 1}, {"kpp_ahead_used": AT_LEAST_2}),     # five steps with nothing read in between: twins through the look-ahead
-      ("tiny", GM, {"gm_flux_tile": 0}, {}),
-      ("tiny", {"hmix_tracer": 3, "ah_bolus": 0.4e7}, {"gm_sf_stored": 0}, {}),
-      ("tiny", dict(KPP, hmix_tracer=3, gm_transition_layer=1, stepped_bathymetry=1, submeso=True), {"submeso_all_levels": 1}, {}),
-      ("tiny", KPP_DEL4, {"halo_separate": 1}, {})])
+      ("tiny", GM, {"gm_flux_tile": 0}, {"form_gm_lds": 0, "D:form_gm_lds": 1}),
+      ("tiny", {"hmix_tracer": 3, "ah_bolus": 0.4e7}, {"gm_sf_stored": 0}, {"form_gm_sf_stored": 0, "D:form_gm_sf_stored": 1}),
+      ("tiny", dict(KPP, hmix_tracer=3, gm_transition_layer=1, stepped_bathymetry=1, submeso=True), {"submeso_all_levels": 1}, {"form_submeso_all_levels": 1, "D:form_submeso_all_levels": 0}),
+      ("tiny", KPP_DEL4, {"halo_separate": 1}, {"form_halo_separate": 1, "D:form_halo_separate": 0})])
 
 
 def _b2_id(row):
@@ -164,7 +161,7 @@ def test_b2_kernel_forms_are_neutral_with_passive_tracers(pkg, orclib_built, row
     X, D = pkg.PopModel(cfg, tuning=tuning), pkg.PopModel(cfg)
     resolved, default = X.tuning(), D.tuning()
     for f, v in tuning.items():
-        assert resolved[f] == v, "%s: asked for %d, the library holds %r" % (f, v, resolved[f])      # the request arrived; see above B2
+        assert resolved[f] == v, "%s: asked for %d, the library holds %r" % (f, v, resolved[f])      # the request arrived; the outcome: dims
         assert default[f] is None, "%s is set from outside the test (environment): %r" % (f, default[f])
     if name == "tiny":
         orc = Oracle(cfg)
