@@ -29,11 +29,23 @@ NOT a third restatement of the reference's loops but what the routines are suppo
     upwind3 face values in i, j and k for either flow direction against Lagrange interpolation from positions
     (check_upwind3_face_values).  Not pinned: what lw_lim's limiter does to a field beyond constancy, conservation and
     check_lw_lim_monotone; the tripole fold; hdiffu and the closed forms of advu with partial bottom cells other than through whole
-    cells (the min(DZU) / DZU weights of hmix_del2.F90:852-886 act at the bottom level of a stepped neighbourhood only).
+    cells (the min(DZU) / DZU weights of hmix_del2.F90:852-886 act at the bottom level of a stepped neighbourhood only);
+  * KPP below the boundary layer and the equation of state under it (vmix_kpp.F90:3575-3621 buoydiff, :1505-1603 and :1774-1986 ri_iwmix,
+    :3404-3497 ddmix, :1218-1262 the convective term, :3797-3870 smooth_hblt; state_mod.F90:418-560), against the 40-digit MWJF of
+    tests/eos_ref.py (mpmath; derivatives by mpmath.diff of that density) and the closed forms of LMD94: rho, d rho / d T and d rho / d S
+    at clipped and unclipped arguments and along the density maximum (check_state_against_mpmath); the displaced-density buoyancy
+    difference, the gradient Richardson number, the carry below the bottom, the 1-2-1 smoothing with its end rules, LMD94 (28) and the
+    convective term with its strict N2 > 0 test, in VDC of both classes and through tgrid_to_ugrid in VVC, flat, stepped and above a
+    partial bottom cell (check_kpp_interior_richardson); both double-diffusion branches on either side of their switches
+    (check_kpp_double_diffusion); the 5-point filter of the boundary-layer depth next to land, its bottom clamp and KBL
+    (check_kpp_hblt_smoothing).  Not pinned: short-wave absorption and lcheckekmo; the blending of interface KBL - 1 (LMD94 appendix D);
+    the floor of HBLT at zt(1) (no closed-form column reaches it); the tidal and latitude-varying backgrounds (NumPy restatements in
+    tests/test_gpu_tidal.py, tests/test_gpu_bckgrnd.py); the tripole fold.
 
 The same functions run against the CPU oracle (tests/test_pins_oracle.py, tests/test_btrop_pins_oracle.py, tests/test_dyn_pins_oracle.py,
-no GPU) and against the device library through the C ABI (tests/test_gpu_pins.py, tests/test_gpu_btrop_pins.py,
-tests/test_gpu_dyn_pins.py): `A` is an adapter with get / set / run_phase (see OracleAdapter, GpuAdapter)."""
+tests/test_kpp_interior_pins_oracle.py, no GPU) and against the device library through the C ABI (tests/test_gpu_pins.py,
+tests/test_gpu_btrop_pins.py, tests/test_gpu_dyn_pins.py, tests/test_gpu_kpp_interior_pins.py): `A` is an adapter with get / set /
+run_phase (see OracleAdapter, GpuAdapter)."""
 import math
 
 import numpy as np
@@ -90,6 +102,11 @@ class OracleAdapter:
 
     def leapfrog(self):
         return self.o.dim("leapfrogts")
+
+    def state(self, kk, T, S):
+        """(rho, d rho / d T, d rho / d S) of the points (T, S) at the pressure of level kk"""
+        from orclib import AsModel
+        return AsModel(self.o).state(kk, T, S, derivs=True)
 
     # ---- the 2-D elliptic system: host arrays (nblocks, ny_block, nx_block) in, host arrays out
     def blocks(self):
@@ -178,6 +195,9 @@ class GpuAdapter:
 
     def leapfrog(self):
         return self.m.dim("leapfrogts")
+
+    def state(self, kk, T, S):
+        return self.m.state(kk, T, S, derivs=True)
 
     # ---- the 2-D elliptic system: host arrays in, host arrays out, the work done by the device entry points on named fields
     def blocks(self):
@@ -669,7 +689,9 @@ def check_kpp_scales_and_shape(A, regime, nu0=0.0, tol=1e-7):
     dG(1) = 0 for a depth-independent interior nu (LMD94 (17), (18), (D5)): a2 = -2 + 3 G(1), a3 = 1 - 2 G(1).
     Non-local term of the tracer equation (LMD94 (20)): K_s gamma_s = C* kappa (c_s kappa eps)^1/3 G(sigma) * surface flux in
     unstable forcing, none in stable forcing.  `regime`: 'stable' | 'weak' | 'strong' picks the forcing; the similarity regime
-    reached (the branch of phi) is asserted.  Interior: no shear-instability term (lrich = 0), uniform background nu0."""
+    reached (the branch of phi) is asserted.  Interior: no shear-instability term (lrich = 0), uniform background nu0; the shear-instability
+    term, the convective term and double diffusion below the boundary layer are pinned by check_kpp_interior_richardson and
+    check_kpp_double_diffusion."""
     km = A.km
     kstar = 9
     ustar, stf = {"stable": (0.5, 1.0e-4), "weak": (2.0, -1.0e-3), "strong": (0.6, -6.0e-3)}[regime]
@@ -2129,3 +2151,443 @@ def check_upwind3_face_values(A, direction, sign):
     print("upwind3 face values, %s, sign %+d: %.3e" % (direction, sign, worst))
     assert worst <= _dyn_tol(A, fig), "upwind3 face values (%s, sign %+d) differ from Lagrange interpolation by %.3e" % (direction, sign, worst)
     return worst
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# KPP below the boundary layer (vmix_kpp.F90 buoydiff, ri_iwmix, ddmix, the convective term, smooth_hblt) and the equation of
+# state under it, against tests/eos_ref.py (40-digit MWJF) and the closed forms of Large, McWilliams & Doney (1994).  Nothing
+# below takes a density, a buoyancy difference or an expansion coefficient from the model.
+# ------------------------------------------------------------------------------------------------------------------
+RI_INFTY, RRHO0, DSFMAX = 0.8, 2.55, 1.0        # LMD94 (28), (31)
+KPP_INTERIOR = dict(vmix_choice=3, bckgrnd_vdc2=0.0, block_size_x=48, block_size_y=40)
+# the oracle's figures (tests/test_kpp_interior_pins_oracle.py prints them); the device bound is 10 x (pins._dyn_tol)
+STATE_FIGURE = 9.7e-15                           # check_state_against_mpmath: below 1e-13, so the 1e-12 floor is the bound
+RICHARDSON_FIGURE = {20: 5.2e-13, 60: 1.0e-12}   # check_kpp_interior_richardson by km, of kpp_rich_mix: the worst of flat, stepped, partial cells, 1-3 passes
+DOUBLE_DIFFUSION_FIGURE = 1.15e-14               # check_kpp_double_diffusion, cm^2/s (km = 60; 3.0e-15 at km = 20): the floor is the bound
+HBLT_SMOOTHING_FIGURE = 8.0e-12                  # check_kpp_hblt_smoothing, relative, the worst of pins.HBLT_LAYOUTS
+
+
+def _density_maximum_row(pbar, salts):
+    """(T, S) on the density maximum d rho / d T = 0 at pbar, by bisection of eos_ref's derivative on -2 .. 8 deg C: for every
+    salinity that has one there the root and a point 1e-3 deg C to either side"""
+    import eos_ref
+    T, S = [], []
+    for s in salts:
+        f = lambda t: float(eos_ref.rho_derivs(t, s, pbar)[1])
+        lo, hi = -2.0, 8.0
+        if not (f(lo) > 0.0 > f(hi)):
+            continue
+        for _ in range(50):
+            mid = 0.5 * (lo + hi)
+            lo, hi = (mid, hi) if f(mid) > 0.0 else (lo, mid)
+        T += [lo, lo - 1.0e-3, lo + 1.0e-3]
+        S += [s] * 3
+    return np.array(T), np.array(S)
+
+
+def check_state_against_mpmath(A, npts=200):
+    """state (state_mod.F90:418-560, MWJF, 'enforce') at levels 1, km / 2, km against tests/eos_ref.py: rho relatively; d rho / d T and
+    d rho / d S absolutely, scaled by the largest |derivative| of the sample (near the density maximum d rho / d T passes through zero).
+    Sample: T in [-3, 32] and S in [-0.001, 0.042] (both clips hit), the exact clip values T = -2 and S = 0, and a row along the
+    density maximum.  Oracle against eos_ref (km 16, 20, 60): rho 4.4e-16, d rho / d T 9.7e-15, d rho / d S 1.6e-15 (the coefficients are doubles in
+    the model and decimal strings in eos_ref)."""
+    import eos_ref
+    km = A.km
+    pz = eos_ref.pressz(km)
+    rng = np.random.default_rng(7)
+    worst = {"rho": 0.0, "drhodt": 0.0, "drhods": 0.0}
+    for kk in (1, km // 2, km):
+        Tm, Sm = _density_maximum_row(pz[kk], (0.0, 0.004, 0.008, 0.012, 0.016, 0.02))
+        T = np.concatenate([rng.uniform(-3.0, 32.0, npts), [-2.0, -2.0, -2.5, 10.0, 10.0, -2.0], Tm])
+        S = np.concatenate([rng.uniform(-0.001, 0.042, npts), [0.035, 0.0, 0.02, 0.0, -0.0005, -0.001], Sm])
+        if kk == 1:
+            assert Tm.size >= 9, "no density maximum in the sample"
+        assert (T < -2.0).any() and (S < 0.0).any() and (T == -2.0).any() and (S == 0.0).any()
+        r, dt, ds = eos_ref.rho_derivs(T, S, pz[kk])
+        if Tm.size:
+            assert dt.min() < 0.0 < dt.max()                       # the sign change of d rho / d T is inside the sample
+        gr, gdt, gds = A.state(kk, T, S)
+        worst["rho"] = max(worst["rho"], float(np.abs(gr / r - 1.0).max()))
+        worst["drhodt"] = max(worst["drhodt"], float(np.abs(gdt - dt).max() / np.abs(dt).max()))
+        worst["drhods"] = max(worst["drhods"], float(np.abs(gds - ds).max() / np.abs(ds).max()))
+    print("state against 40 digits: rho %.3e, drho/dT %.3e, drho/dS %.3e" % (worst["rho"], worst["drhodt"], worst["drhods"]))
+    fig = max(worst.values())
+    assert fig <= _dyn_tol(A, STATE_FIGURE), "the equation of state differs from the 40-digit evaluation: %r" % worst
+    return fig
+
+
+def _deep_neighbourhood(kmt):
+    """ocean columns of the blocks' interiors whose 3 x 3 T neighbourhood is at least as deep as themselves: the four U columns
+    around them then reach their bottom, and a horizontally uniform velocity profile has a horizontally uniform shear there"""
+    ok = kmt > 0
+    for dj in (-1, 0, 1):
+        for di in (-1, 0, 1):
+            ok &= np.roll(np.roll(kmt, dj, axis=1), di, axis=2) >= kmt
+    ok[:, :2, :] = False; ok[:, -2:, :] = False; ok[:, :, :2] = False; ok[:, :, -2:] = False
+    return ok
+
+
+def _set_column(A, T, S, U):
+    """the same profiles T, S, (U, 0) (1-based, slot 0 unused) in every column and at every time level; no velocity below KMU"""
+    km = A.km
+    shp = A.get("TRACER", 1, 0).shape
+    lev = np.arange(1, km + 1)[None, :, None, None]
+    kmu = A.geti("KMU")[:, None]
+    zero = np.zeros(shp)
+    Uf = np.where(lev <= kmu, U[1:km + 1][None, :, None, None], 0.0) + zero
+    for tl in range(3):
+        A.set("TRACER", T[1:km + 1][None, :, None, None] + zero, tl, 0)
+        A.set("TRACER", S[1:km + 1][None, :, None, None] + zero, tl, 1)
+        A.set("UVEL", Uf, tl)
+        A.set("VVEL", zero, tl)
+
+
+def _column_db(T, S, pz, km):
+    """db(k) / g = 1 - rho(T_k, S_k, p_{k+1}) / rho(T_{k+1}, S_{k+1}, p_{k+1}), k = 1 .. km-1 (buoydiff, vmix_kpp.F90:3575-3621: the upper
+    water displaced to the lower level; T below -2 is raised to -2 first (:3567), which eos_ref's range rule does as well)"""
+    import eos_ref
+    db = np.zeros(km + 1)
+    for k in range(1, km):
+        db[k] = GRAV * eos_ref.one_minus_ratio(T[k], S[k], T[k + 1], S[k + 1], pz[k + 1])
+    return db
+
+
+CAP_JUMP, CAP_USTAR, CAP_STF = 10.0, 0.05, 5.0e-3     # levels 1, 2 warmer by 10 deg C, weak wind, stable (heating) surface flux
+# one interface after the other below the cap, cyclically: the target gradient Richardson number; negative: statically unstable; None: neutral
+# (three neighbours above 0.8, so that an interface stays there through three smoothing passes)
+RI_CYCLE = (0.07, -0.3, 0.45, 0.76, None, 0.25, -0.6, 0.62, 1.3, 1.25, 1.2)
+
+
+def _richardson_column(km, zt, pz, kcap):
+    """T, S, U (1-based) of the column of check_kpp_interior_richardson.  kcap = 3: the unsheared jump between levels 2 and 3, the cycle from
+    interface 3 on.  kcap = 2: no jump; a stable step of 1 deg C between levels 1 and 2 sheared to a gradient Richardson number of 0.5 -- the
+    bulk Richardson number of level 2 is then 0.95 zt(2) / (zt(2) - zt(1)) times that, above critical --, the cycle from interface 2 on"""
+    import eos_ref
+    T, S, U = np.zeros(km + 1), np.full(km + 1, 0.035), np.zeros(km + 1)
+    T[kcap] = 16.0
+    T[1:kcap] = T[kcap] + (CAP_JUMP if kcap == 3 else 1.0)
+    for k in range(kcap - 1 if kcap == 2 else kcap, km):
+        tgt = 0.5 if k < kcap else RI_CYCLE[(k - kcap) % len(RI_CYCLE)]
+        if k >= kcap:
+            T[k + 1] = T[k] if tgt is None else T[k] - 1.0 if tgt > 0.0 else T[k] + 4.0   # 8 x -1 + 2 x 4 = 0 over a cycle
+        if tgt is None:
+            du = 3.0
+        else:
+            db = GRAV * float(eos_ref.one_minus_ratio(T[k], S[k], T[k + 1], S[k + 1], pz[k + 1]))
+            du = np.round(64.0 * math.sqrt(abs(db) * (zt[k + 1] - zt[k]) / abs(tgt))) / 64.0
+        U[k + 1] = U[k] + (du if k % 2 else -du)
+    return T, S, U
+
+
+def _smoothed_ri(ri, kb, km, npass):
+    """the 1-2-1 smoothing of ri_iwmix (vmix_kpp.F90:1573-1603) of a column with bottom level kb: ri (1-based) holds the local values
+    at k < kb; 0 at k = kb (no buoyancy difference across the floor), carried to every level below; then npass passes of 1/4, 1/2, 1/4
+    with the level's own value standing in above level 1 and below level km -- none where the column has fewer than 3 levels"""
+    w = np.zeros(km + 2)
+    w[1:kb] = ri[1:kb]
+    w[kb:km + 1] = w[kb]
+    for _ in range(npass):
+        if kb >= 3:
+            old = w.copy()
+            old[0], old[km + 1] = old[1], old[km]
+            w[1:km + 1] = 0.25 * old[0:km] + 0.5 * old[1:km + 1] + 0.25 * old[2:km + 2]
+    return w
+
+
+def _t_to_u(A, f):
+    """tgrid_to_ugrid (grid.F90): the area-weighted mean of the four T cells around a U point, 0.25 (sum of TAREA f) / UAREA"""
+    ta, ua = A.get("TAREA"), A.get("UAREA")
+    if f.ndim == 4:
+        ta, ua = ta[:, None], ua[:, None]
+    g = ta * f
+    return 0.25 * (g + _sh(g, 1, 0) + _sh(g, 0, 1) + _sh(g, 1, 1)) / ua
+
+
+def _profiles_to_field(table, kmt):
+    """table[kb] = a profile (length n) of a column with bottom level kb -> (nblocks, n, ny, nx)"""
+    return np.moveaxis(table[np.maximum(kmt, 0)], -1, 1)
+
+
+def check_kpp_interior_richardson(A, kcap=3, figure=None):
+    """Below the boundary layer VDC and VVC hold the interior value of ri_iwmix plus the convective term, untouched by blmix (which
+    rewrites k < KBL only).  A horizontally uniform column: levels 1, 2 warmer by 10 deg C than level 3 with no shear across the jump,
+    weak wind and stable forcing, which ends the boundary layer right below the jump (KBL = 3, asserted); below it one temperature step
+    per interface (-1 deg C stable, +4 unstable, 0 neutral) and a zig-zag velocity with |du_k| = sqrt(|db_k| dzw_k / Ri_target_k)
+    rounded to 1/64 cm/s, targets RI_CYCLE.  Expected, on every ocean column whose 3 x 3 T neighbourhood is at least as deep as itself
+    and for KBL <= k < KMT:
+        db_k = g (1 - rho(T_k, S_k, p_{k+1}) / rho(T_{k+1}, S_{k+1}, p_{k+1}))            buoydiff, densities of tests/eos_ref.py
+        Ri_k = db_k (zt_{k+1} - zt_k) / (du_k^2 + eps)                                    vmix_kpp.F90:1564; eps = 1e-10 (:104) is the reference's
+                                                                                          regularisation of the shear, written in as it is
+             = db_k h / (du_k^2 + eps), h = (DZT_k + DZT_{k+1}) / 2                       partial bottom cells (:1531-1563: shear / h^2, eps / h^2)
+        Ri = 0 at k = KMT, carried below; num_v_smooth_Ri passes of 1/4, 1/2, 1/4          _smoothed_ri
+        nu_k = bckgrnd + kpp_rich_mix (1 - min(max(Ri_k, 0) / 0.8, 1)^2)^3                LMD94 (28)
+        + convect_diff / convect_visc where db_k <= 0                                      :1218-1262: N2 > 0 is the stable case, so a neutral
+                                                                                          interface is convective
+    VDC(k) of both tracer classes is that; VVC(k) is tgrid_to_ugrid of the viscosity (bckgrnd_vvc = Prandtl bckgrnd_vdc) where the four
+    T columns around the U point all qualify.  kcap = 2 replaces the jump by a step of 1 deg C between levels 1 and 2 sheared to Ri = 0.5
+    (KBL = 2, asserted): the smoothing's rule above level 1 then reaches the asserted interfaces with moderate numbers from the second pass
+    on, where the unsheared jump (Ri ~ 1e13) hides it.  Every branch must have been met: convective, Ri >= 0.8, in between, and (stepped or
+    partial cells) columns shallower than km.  Returns the worst difference in units of kpp_rich_mix.  The oracle's figures: 5.2e-13 at
+    km = 20 and 1.0e-12 at km = 60, the worst of flat, stepped, partial bottom cells, 1, 2, 3 passes and both caps (RICHARDSON_FIGURE).  They are the
+    model's own cancellation: it forms 1 - rho_a / rho_b in float64, an absolute error of 1e-16 in a db / g of 1e-4 .. 1e-3, while
+    eos_ref forms the difference in 40 digits."""
+    import eos_ref
+    km, cfg = A.km, A.cfg
+    assert cfg.lrich == 1 and cfg.bckgrnd_vdc2 == 0.0
+    kmt = _kpp_setup(A, kcap, 26.0, 16.0, CAP_USTAR, CAP_STF, salt=0.035)
+    zt, dz, pz = A.vert("zt"), A.vert("dz"), eos_ref.pressz(km)
+    T, S, U = _richardson_column(km, zt, pz, kcap)
+    _set_column(A, T, S, U)
+    _kpp_run(A)
+    ok = _deep_neighbourhood(kmt)
+    kbl = A.geti("KBL")
+    assert (kbl[ok] == kcap).all(), "the boundary layer does not end at the cap: KBL %d .. %d" % (kbl[ok].min(), kbl[ok].max())
+    KB = kcap
+    db = _column_db(T, S, pz, km)
+    du2 = np.zeros(km + 1)
+    du2[1:km] = (U[1:km] - U[2:km + 1]) ** 2
+    neutral = [k for k in range(KB, km) if T[k] == T[k + 1]]
+    assert neutral and all(db[k] == 0.0 for k in neutral)
+    assert all(abs(db[k]) >= 1.0e-4 * GRAV for k in range(KB, km) if k not in neutral), "a buoyancy step too small for its sign to be safe"
+    dzbc = None
+    if cfg.partial_bottom_cells:
+        dzbc = A.get("DZBC")[ok]
+        assert np.ptp(dzbc) <= 1e-9 * dzbc.max() and np.ptp(kmt[ok]) == 0          # the grid of pbc_flat_grid
+        dzbc = float(dzbc.flat[0])
+    vdc_t, visc_t, ri_t = np.zeros((km + 1, km + 2)), np.zeros((km + 1, km + 2)), np.zeros((km + 1, km + 2))
+    bvdc, bvvc = cfg.bckgrnd_vdc1, cfg.Prandtl * cfg.bckgrnd_vdc1
+    for kb in np.unique(kmt[ok]):
+        h = np.zeros(km + 1)
+        h[1:km] = zt[2:km + 1] - zt[1:km]
+        if dzbc is not None:
+            h[kb - 1] = 0.5 * (dz[kb - 1] + dzbc)
+        ri = _smoothed_ri(db * h / (du2 + KPP_EPS), kb, km, cfg.num_v_smooth_Ri)
+        f = (1.0 - np.minimum(np.maximum(ri, 0.0) / RI_INFTY, 1.0) ** 2) ** 3
+        for k in range(KB, kb):
+            conv = 1.0 if db[k] <= 0.0 else 0.0
+            vdc_t[kb, k] = bvdc + cfg.kpp_rich_mix * f[k] + cfg.convect_diff * conv
+            visc_t[kb, k] = bvvc + cfg.kpp_rich_mix * f[k] + cfg.convect_visc * conv
+        ri_t[kb] = ri
+    lev = np.arange(km + 2)[None, :, None, None]
+    sel = ok[:, None] & (lev >= KB) & (lev < kmt[:, None])                       # the asserted (column, interface) pairs of VDC (levels 0 .. km+1)
+    expect, ri_f = _profiles_to_field(vdc_t, kmt), _profiles_to_field(ri_t, kmt)
+    worst = 0.0
+    for n in range(2):
+        worst = max(worst, float(np.abs(A.get("VDC", 1, n) - expect)[sel].max() / cfg.kpp_rich_mix))
+    conv_f = np.broadcast_to((np.concatenate([db, [0.0]]) <= 0.0)[None, :, None, None], sel.shape)
+    counts = {"convective": int((sel & conv_f).sum()), "background-only": int((sel & (ri_f >= RI_INFTY)).sum()),
+              "between": int((sel & (ri_f > 0.0) & (ri_f < RI_INFTY)).sum()), "neutral": int((sel & (lev == neutral[0])).sum()),
+              "columns": int(ok.sum())}
+    if cfg.stepped_bathymetry or cfg.partial_bottom_cells:
+        counts["shallower-than-km"] = int((sel & (kmt[:, None] < km)).sum())
+    assert all(v > 0 for v in counts.values()), "a branch was not met: %r" % counts
+    # VVC: U points whose four T columns all qualify, KBL <= k < KMU
+    kmu = A.geti("KMU")
+    oku = ok & _sh(ok, 1, 0) & _sh(ok, 0, 1) & _sh(ok, 1, 1)
+    levu = np.arange(1, km + 1)[None, :, None, None]
+    selu = oku[:, None] & (levu >= KB) & (levu < kmu[:, None])
+    assert selu.sum() > 0
+    expu = _t_to_u(A, _profiles_to_field(visc_t, kmt)[:, 1:km + 1])
+    worst_u = float(np.abs(A.get("VVC") - expu)[selu].max() / cfg.kpp_rich_mix)
+    print("KPP interior (smoothing passes %d): VDC %.3e, VVC %.3e of kpp_rich_mix; %r" % (cfg.num_v_smooth_Ri, worst, worst_u, counts))
+    fig = max(worst, worst_u)
+    assert fig <= _dyn_tol(A, RICHARDSON_FIGURE[km] if figure is None else figure), "interior KPP coefficients differ from the closed forms by %.3e of kpp_rich_mix (VDC %.3e, VVC %.3e)" % (fig, worst, worst_u)
+    return fig
+
+
+# double diffusion: one interface after the other below the cap, cyclically.  ("finger" | "dc", R_rho), the two quadrants without a term, and a step
+# of temperature alone; the two last-but-one entries also bring salinity and temperature back to where the cycle began
+DD_CYCLE = (("finger", 1.16), ("finger", 1.5), ("finger", 1.95), ("finger", 3.0), ("finger", 4.0), ("dc", 0.03), ("dc", 0.2), ("dc", 0.3),
+            ("dc", 0.55), ("dc", 0.6), ("ds0", None), ("stable", None), ("unstable", None))
+DD_DENSITY_STEP = 1.2e-4                          # |alpha dT - beta dS| of every constructed step: |db| stays above 1e-4 g
+
+
+def _dd_terms(T, S, pz, km):
+    """alpha dT and beta dS of every interface (ddmix, vmix_kpp.F90:3404-3445): the expansion coefficients are the means of the two
+    levels', each at its OWN pressure, from tests/eos_ref.py"""
+    import eos_ref
+    _, rt, rs = eos_ref.rho_derivs(T[1:km + 1], S[1:km + 1], pz[1:km + 1])
+    adt, bds = np.zeros(km + 1), np.zeros(km + 1)
+    adt[1:km] = -0.5 * (rt[:-1] + rt[1:]) * (T[1:km] - T[2:km + 1])
+    bds[1:km] = 0.5 * (rs[:-1] + rs[1:]) * (S[1:km] - S[2:km + 1])
+    return adt, bds
+
+
+def _double_diffusion_column(km, pz):
+    """T, S (1-based) of the column of check_kpp_double_diffusion: the steps are sized with eos_ref's coefficients (the expected values
+    are formed from the column as it stands, whatever the steps turn out to be) and rounded to 2^-20 deg C and 2^-30 g/g"""
+    import eos_ref
+    T0, S0 = 20.0, 0.035
+    T, S = np.zeros(km + 1), np.zeros(km + 1)
+    T[3], S[3] = T0, S0
+    T[1] = T[2] = T0 + CAP_JUMP
+    S[1] = S[2] = S0
+    d = DD_DENSITY_STEP
+    for k in range(3, km):
+        kind, R = DD_CYCLE[(k - 3) % len(DD_CYCLE)]
+        _, rtk, rsk = (float(x) for x in eos_ref.rho_derivs(T[k], S[k], pz[k]))
+        rt, rs = rtk, rsk
+        for _ in range(4):                         # the coefficients are the means of the two levels': settle the lower level's
+            if kind == "finger":                   # alpha dT > beta dS > 0
+                b = d / (R - 1.0); a = R * b
+            elif kind == "dc":                     # beta dS < alpha dT < 0
+                b = -d / (1.0 - R); a = R * b
+            elif kind == "ds0":
+                a, b = 2.0e-4, 0.0
+            elif kind == "stable":                 # warm and fresh over cold and salty: salinity back to S0 + 2e-4
+                a, b = 2.0e-4, rs * (S[k] - (S0 + 2.0e-4))
+            else:                                  # cold and salty over warm and fresh: temperature back to T0; statically unstable
+                a, b = -rt * (T[k] - T0), rs * 2.0e-4
+            T[k + 1] = np.round((T[k] + a / rt) * 2.0 ** 20) / 2.0 ** 20      # alpha dT = -rho_T (T_k - T_{k+1})
+            S[k + 1] = np.round((S[k] - b / rs) * 2.0 ** 30) / 2.0 ** 30      # beta dS = rho_S (S_k - S_{k+1})
+            _, rtn, rsn = (float(x) for x in eos_ref.rho_derivs(T[k + 1], S[k + 1], pz[k + 1]))
+            rt, rs = 0.5 * (rtk + rtn), 0.5 * (rsk + rsn)
+    return T, S
+
+
+def check_kpp_double_diffusion(A, figure=DOUBLE_DIFFUSION_FIGURE):
+    """ddmix (vmix_kpp.F90:3404-3497) with lrich = 0 and no velocity: below the boundary layer (the cap of check_kpp_interior_richardson)
+    VDC of the temperature class (n = 0) and of the salinity class (n = 1) hold the background, the double-diffusive term and the
+    convective term.  With alpha dT = -1/2 (rho_T(k at p_k) + rho_T(k+1 at p_{k+1})) (T_k - T_{k+1}), beta dS = 1/2 (rho_S ...) (S_k - S_{k+1})
+    (derivatives of tests/eos_ref.py) and R = alpha dT / beta dS:
+      salt fingering, alpha dT > beta dS > 0:    nu_S = 1.0 (1 - (min(R, 2.55) - 1) / 1.55)^3,  nu_T = 0.7 nu_S
+      diffusive convection, beta dS < alpha dT < 0:  nu_T = 1.5e-2 * 0.909 exp(4.6 exp(-0.54 (1 / R - 1))),
+                                                 nu_S = nu_T (1.85 - 0.85 / R) R for R > 0.5, else 0.15 R nu_T          LMD94 (32)-(34)
+    LMD94 (31) has the bracket of the fingering form SQUARED before the cube, (1 - ((R - 1) / (R0 - 1))^2)^3; the reference has no square
+    (vmix_kpp.F90:3468-3469) and this check follows the reference.  The column (DD_CYCLE) holds fingering at R = 1.16, 1.5, 1.95 and at
+    3 and 4 (beyond Rrho0 = 2.55: no mixing), diffusive convection at 0.03, 0.2, 0.3, 0.55 and 0.6 (both sides of the 0.5 switch), one interface in
+    each of the two quadrants without a term (one of them statically unstable) and one with dS = 0; every |db| is above 1e-4 g and every R
+    at least 0.02 from 1, 0.5 and 2.55.  The count of interfaces per branch is asserted, and VDC n = 0 differs from n = 1 wherever a term acts.
+    Returns the worst difference in cm^2/s (dsfmax = 1); the oracle's figures are 3.0e-15 (km = 20) and 1.15e-14 (km = 60), flat and stepped."""
+    import eos_ref
+    km, cfg = A.km, A.cfg
+    assert cfg.ldbl_diff == 1 and cfg.lrich == 0 and cfg.bckgrnd_vdc2 == 0.0
+    kmt = _kpp_setup(A, 3, 30.0, 20.0, CAP_USTAR, CAP_STF, salt=0.035)
+    pz = eos_ref.pressz(km)
+    T, S = _double_diffusion_column(km, pz)
+    _set_column(A, T, S, np.zeros(km + 1))
+    _kpp_run(A)
+    ok = _deep_neighbourhood(kmt)
+    kbl = A.geti("KBL")
+    assert (kbl[ok] == 3).all(), "the boundary layer does not end below the cap: KBL %d .. %d" % (kbl[ok].min(), kbl[ok].max())
+    KB = 3
+    db = _column_db(T, S, pz, km)
+    adt, bds = _dd_terms(T, S, pz, km)
+    assert all(abs(db[k]) >= 1.0e-4 * GRAV for k in range(KB, km))
+    nu = np.zeros((2, km + 2))                       # [class, interface]
+    branch = {}
+    for k in range(KB, km):
+        a, b = adt[k], bds[k]
+        R = a / b if b != 0.0 else np.inf
+        if a > b > 0.0:
+            assert min(abs(R - 1.0), abs(R - RRHO0)) >= 0.02
+            nus = DSFMAX * (1.0 - (min(R, RRHO0) - 1.0) / (RRHO0 - 1.0)) ** 3
+            nu[0, k], nu[1, k] = 0.7 * nus, nus
+            branch[k] = "fingering" if R < RRHO0 else "fingering-beyond-Rrho0"
+        elif b < a < 0.0:
+            assert min(abs(R - 1.0), abs(R - 0.5), R) >= 0.02
+            nut = 1.5e-2 * 0.909 * math.exp(4.6 * math.exp(-0.54 * (1.0 / R - 1.0)))
+            nu[0, k], nu[1, k] = nut, nut * ((1.85 - 0.85 / R) * R if R > 0.5 else 0.15 * R)
+            branch[k] = "diffusive-R>0.5" if R > 0.5 else "diffusive-R<=0.5"
+        else:
+            branch[k] = "dS=0" if b == 0.0 else "warm-fresh-over-cold-salty" if (a > 0.0 and b < 0.0) else \
+                "cold-salty-over-warm-fresh" if (a < 0.0 and b > 0.0) else "unstable-same-sign"
+        conv = cfg.convect_diff if db[k] <= 0.0 else 0.0
+        nu[:, k] += cfg.bckgrnd_vdc1 + conv
+    assert "unstable-same-sign" not in branch.values()
+    lev = np.arange(km + 2)[None, :, None, None]
+    sel = ok[:, None] & (lev >= KB) & (lev < kmt[:, None])
+    names = np.array([branch.get(k, "") for k in range(km + 2)])
+    counts = {b: int((sel & (names == b)[None, :, None, None]).sum()) for b in
+              ("fingering", "fingering-beyond-Rrho0", "diffusive-R>0.5", "diffusive-R<=0.5", "dS=0", "warm-fresh-over-cold-salty", "cold-salty-over-warm-fresh")}
+    counts["convective"] = int((sel & (np.concatenate([db, [1.0]]) <= 0.0)[None, :, None, None]).sum())
+    counts["columns"] = int(ok.sum())
+    if cfg.stepped_bathymetry:
+        counts["shallower-than-km"] = int((sel & (kmt[:, None] < km)).sum())
+    assert all(v > 0 for v in counts.values()), "a branch was not met: %r" % counts
+    got = [A.get("VDC", 1, n) for n in range(2)]
+    worst = 0.0
+    for n in range(2):
+        worst = max(worst, float(np.abs(got[n] - nu[n][None, :, None, None])[sel].max() / DSFMAX))
+    acts = sel & (nu[0] != nu[1])[None, :, None, None]
+    assert acts.sum() > 0 and (got[0][acts] != got[1][acts]).all() and np.array_equal(got[0][sel & ~acts], got[1][sel & ~acts])
+    print("KPP double diffusion: %.3e cm^2/s; %r" % (worst, counts))
+    assert worst <= _dyn_tol(A, figure), "double-diffusive coefficients differ from the closed forms by %.3e cm^2/s" % worst
+    return worst
+
+
+# name -> (configuration, k*, asserted columns with a land neighbour required, whether the bottom clamp acts on an asserted column)
+HBLT_LAYOUTS = {
+    "one-block": (dict(block_size_x=48, block_size_y=40), 8, 10, False),
+    "blocks-12x10": (dict(), 8, 10, False),                                                     # the neighbours come through the halo
+    "closed-stepped-24x20": (dict(block_size_x=24, block_size_y=20, ew_boundary=0, stepped_bathymetry=1), 8, 10, False),
+    "closed-stepped-24x20-jump-below-shallow-columns": (dict(block_size_x=24, block_size_y=20, ew_boundary=0, stepped_bathymetry=1), 14, 10, True),
+}
+
+
+def check_kpp_hblt_smoothing(A, kstar,figure=HBLT_SMOOTHING_FIGURE, min_land=10):
+    """smooth_hblt (vmix_kpp.F90:3797-3870) on the two-layer column of check_kpp_hblt_two_layer with a lower-layer temperature that varies
+    with the global (i, j): the unsmoothed depth of a column with KMT >= k* is its own closed form,
+        h(i, j) = zt(k*-1) + (zt(k*) - zt(k*-1)) sqrt(Ri_c / Ri*(i, j)),   Ri* = (d - eps d / 2) db(i, j) / |dV|^2,  d = zt(k*),
+    with db from tests/eos_ref.py, and zt(KMT) for a column that ends above the jump (no level exceeds Ri_c).  Expected HBLT: the 5-point
+    mean with weights 1/2 and 1/8, a land neighbour's weight moved to the centre, clamped at zt(KMT) and floored at zt(1); expected KBL:
+    the level with zt(k-1) < HBLT <= zt(k), at least 2.  Asserted on the ocean columns whose ocean neighbours are all deeper than k*;
+    at least min_land of them have a land neighbour, and some have none.  Returns the worst relative difference and the counts.  The
+    oracle's figure is 7.9e-12 on every layout of HBLT_LAYOUTS (what the closed form leaves out of the bulk Richardson number's denominator: the unresolved shear of the
+    neutral lower layer and eps."""
+    import eos_ref
+    km = A.km
+    t1, salt, du = 16.0, 0.035, 14.0
+    kmt = _kpp_setup(A, kstar, t1, 15.0, 1.0, -1.0e-4, u1=du, u2=0.0, salt=salt)
+    ig, jg = _global_index(A)
+    t2 = 15.0 - 0.4 * (1.0 + np.sin(2.0 * np.pi * ig / A.cfg.nx_global + 0.3) * np.cos(3.0 * np.pi * jg / A.cfg.ny_global))     # 14.2 .. 15
+    t2 = np.round(t2 * 64.0) / 64.0                                                                                              # few distinct values
+    shp = A.get("TRACER", 1, 0).shape
+    lev = np.arange(1, km + 1)[None, :, None, None]
+    Tf = np.where(lev < kstar, t1, t2[:, None]) + np.zeros(shp)
+    Uf = np.where((lev < kstar) & (lev <= A.geti("KMU")[:, None]), du, 0.0) + np.zeros(shp)
+    for tl in range(3):
+        A.set("TRACER", Tf, tl, 0)
+        A.set("UVEL", Uf, tl)
+    _kpp_run(A)
+    zt = A.vert("zt")
+    pz = eos_ref.pressz(km)
+    db = GRAV * eos_ref.one_minus_ratio(t1, salt, t2, salt, pz[kstar])
+    d = zt[kstar]
+    ri = (d - 0.5 * EPSSFC * d) * db / (du * du)
+    assert ri.min() > RICR
+    ocean = kmt > 0
+    h0 = np.where(kmt >= kstar, zt[kstar - 1] + (zt[kstar] - zt[kstar - 1]) * np.sqrt(RICR / ri), zt[np.maximum(kmt, 0)])
+    cc = np.full(kmt.shape, 0.5)
+    hs = np.zeros(kmt.shape)
+    nland = np.zeros(kmt.shape, dtype=int)
+    deep = np.ones(kmt.shape, dtype=bool)
+    for di, dj in ((-1, 0), (1, 0), (0, -1), (0, 1)):
+        on, hn = _sh(ocean, di, dj), _sh(h0, di, dj)
+        cc = cc + np.where(on, 0.0, 0.125)
+        hs = hs + np.where(on, 0.125 * hn, 0.0)
+        nland += ~on
+        deep &= ~on | (_sh(kmt, di, dj) > kstar)
+    hs = hs + cc * h0
+    expect = np.maximum(np.minimum(hs, zt[np.maximum(kmt, 0)]), zt[1])
+    ok = ocean & deep
+    ok[:, :2, :] = False; ok[:, -2:, :] = False; ok[:, :, :2] = False; ok[:, :, -2:] = False
+    ok = ok & _owned_mask(A)
+    counts = {"columns": int(ok.sum()), "land-neighbour": int((ok & (nland > 0)).sum()), "no-land-neighbour": int((ok & (nland == 0)).sum()),
+              "clamped-at-the-bottom": int((ok & (hs > zt[np.maximum(kmt, 0)])).sum())}
+    hblt, kbl = A.get("HBLT"), A.geti("KBL")
+    err = float((np.abs(hblt - expect) / expect)[ok].max())
+    kexp = np.maximum(np.searchsorted(zt[1:km + 1], expect, side="left") + 1, 2)
+    edge = np.abs(expect[..., None] - zt[1:km + 1]).min(axis=-1) <= 1.0e-5 * expect          # a depth this close to a level's is not asked for its level
+    print("smooth_hblt: %.3e; %r" % (err, counts))
+    assert counts["land-neighbour"] >= min_land and counts["no-land-neighbour"] > 0, counts
+    assert err <= _dyn_tol(A, figure), "smoothed HBLT differs from the closed form by %.3e" % err
+    assert (kbl == kexp)[ok & ~edge].all()
+    return err, counts
+
+
+def _owned_mask(A):
+    own = np.zeros(A.geti("KMT").shape, dtype=bool)
+    for n, b in enumerate(A.blocks()):
+        own[n, b["jb"] - 1:b["je"], b["ib"] - 1:b["ie"]] = True
+    return own
