@@ -26,7 +26,7 @@ case = sys.argv[2]
 cfg = named_config("gx1v7", bckgrnd_vdc1=0.16)
 m = pkg.PopModel(cfg)
 if case in ("tidal", "tidal+bck"):
-    from test_tidal_host import smooth_flux
+    from tidal_common import smooth_flux     # here, not at the top: --parent may name a checkout from before tests/tidal_common.py
     m.init_tidal_mixing(smooth_flux(m, 0.02))
 if case in ("bck", "tidal+bck"):
     m.init_kpp_bckgrnd(bckgrnd_vdc_eq=0.01, bckgrnd_vdc_psim=0.13, bckgrnd_vdc_ban=1.0)

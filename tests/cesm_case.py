@@ -1,10 +1,14 @@
 """The configurations with CESM's gx-grid schemes switched on -- anisotropic viscosity, the submesoscale scheme, Jayne tidal mixing
 and the latitude-varying KPP background -- shared by tests/test_gpu_schemes_oracle.py, tests/golden/make_golden.py (cesm_all) and,
-restated in C, oracle/check_main.c.  Everything here is built on the CPU oracle's state, so a case can be prepared with no GPU."""
+restated in C, oracle/check_main.c.  Everything here is built on the CPU oracle's state, so a case can be prepared with no GPU; pair()
+alone also builds the device model.  The top of the helper stack: it starts every scheme's init call, so it imports the scheme modules."""
 import numpy as np
 
 import orclib
-from bckgrnd_ref import CESM  # noqa: F401  (the background values the cases pass to the init call)
+import tidal_common
+from bckgrnd_ref import CESM
+from common import block_masks, physical
+from parity import force_kpp_case
 
 # CESM_TINY of tests/test_gpu_submeso.py plus the rest of the CESM set-up: transition layer, once-a-day 'bfre' kappa with a day of
 # four steps (with the Robert filter every fourth step ends a day, the fifth recomputes kappa), upwind3, Robert filter, P-CSI + EVP
@@ -31,44 +35,12 @@ def all_on_config(c5):
     return pkg.submeso_config(pkg.anisotropic_config(c5, **ANISO_EAST_VARIABLE), **SUBMESO_CESM)
 
 
-def physical(orc):
-    ph = np.zeros((orc.nblocks, orc.nyb, orc.nxb), dtype=bool)
-    ib, ie, jb, je = (orc.ivec(n, orc.nblocks) for n in ("blk_ib", "blk_ie", "blk_jb", "blk_je"))
-    for b in range(orc.nblocks):
-        ph[b, jb[b] - 1:je[b], ib[b] - 1:ie[b]] = True
-    return ph
-
-
-def smooth_flux(orc, seed=5):
-    """test_tidal_host.smooth_flux with amplitude 1 on the oracle's blocks, its ghost cells filled as the init call fills them"""
-    nx, ny = orc.cfg.nx_global, orc.cfg.ny_global
-    fac = 0.5 + np.random.default_rng(seed).random((ny + 1, nx + 1))
-    ig = orc.ivec("i_glob", orc.nxb * orc.nblocks).reshape(orc.nblocks, orc.nxb)
-    jg = orc.ivec("j_glob", orc.nyb * orc.nblocks).reshape(orc.nblocks, orc.nyb)
-    F = np.zeros((orc.nblocks, orc.nyb, orc.nxb))
-    for b in range(orc.nblocks):
-        i = np.clip(ig[b], 0, nx)[None, :]
-        j = np.clip(jg[b], 0, ny)[:, None]
-        F[b] = (1.0 + 0.5 * np.cos(2.0 * np.pi * i / nx) * np.sin(np.pi * j / ny)) * fac[j, i]
-    import ctypes as C
-    orc.L.orc_halo(orc.h, F.ctypes.data_as(C.POINTER(C.c_double)), 1, 0, 0)
-    return F
-
-
-def flux_amplitude(orc, F1):
-    """test_gpu_tidal.amplitude on the oracle's current tracers: tidal_mix_max / (median of the unit-flux TIDAL_DIFF over the stably
-    stratified cells of the four levels above the bottom), from the NumPy restatement alone"""
-    import test_gpu_tidal
-    m = orclib.AsModel(orc)
-    return test_gpu_tidal.amplitude(orclib, m, orc.cfg, F1, m.get("TRACER", 1, 0), m.get("TRACER", 1, 1))
-
-
 def tidal_branches(orc, nml):
     """cells of the oracle's last evaluation in each branch of tidal_compute_diff, counted on its own fields: N^2 <= 0 ('neg'),
     limited by tidal_mix_max ('cap'), raised by the stability control ('stab')"""
     N2, COEF, TD, KMT = orc.f3("TIDAL_N2"), orc.f3("TIDAL_COEF_3D"), orc.f3("TIDAL_DIFF"), orc.i2("KMT")[:, None]
     lev = np.arange(1, orc.km + 1)[None, :, None, None]
-    wet = (lev < KMT) & physical(orc)[:, None]
+    wet = (lev < KMT) & physical(orclib.AsModel(orc))[:, None]
     with np.errstate(divide="ignore", invalid="ignore"):
         raw = np.where(N2 > 0.0, COEF / np.where(N2 > 0.0, N2, 1.0), 0.0)
     mx = nml.tidal_mix_max or 100.0
@@ -97,7 +69,6 @@ def force_kpp_case_above_deep_water(gpu, orc, min_kmt=8):
     levels) off by more than 1e-12, and HBLT 1.2e-14, VDC 2.4e-14, VVC 1.7e-14, TRACER 1.4e-14 with min_kmt = 12 (115 distinct depths, 1250 .. 212344 cm):
     tests/test_gpu_land_schemes.py."""
     keep = {(f, tl, n): orc.f3(f, tl, n).copy() for f, tls, ns in (("TRACER", (0, 1, 2), (0, 1)), ("RHO", (0, 1), (0,))) for tl in tls for n in ns}
-    from test_gpu_parity import force_kpp_case
     force_kpp_case(gpu, orc)
     shallow = (orc.i2("KMT") < min_kmt)[:, None]
     assert shallow.any() and not shallow.all()
@@ -105,3 +76,32 @@ def force_kpp_case_above_deep_water(gpu, orc, min_kmt=8):
         x = orc.f3(f, tl, n)
         x[...] = np.where(shallow, a, x)
         gpu.set(f, x, tl=tl, n=n)
+
+
+def pair(pkg, cfg, grid=None, tuning=None, kpp=True, state=force_kpp_case, tidal=False, bck=False, tidal_first=True, tidal_diag=1, masks=False):
+    """the device model and the oracle with the same state (state(gpu, orc) with KPP), the same energy flux and the same init calls.
+    The flux is tidal_common.unit_flux times tidal_common.amplitude, both formed on the oracle from the NumPy restatement alone."""
+    gpu, orc = pkg.PopModel(cfg, grid=grid, tuning=tuning), orclib.Oracle(cfg, grid=grid)
+    if masks:
+        gpu.masks = block_masks(gpu)
+        assert gpu.masks["short"] > 0, "no block is short: %d" % gpu.masks["short"]
+    for n in (0, 1):
+        a, b = gpu.get("TRACER", 1, n), orc.f3("TRACER", 1, n)
+        assert np.array_equal(a, b), "initial TRACER %d: %d cells differ, max %.3e" % (n, int((a != b).sum()), np.abs(a - b).max())
+    if kpp:
+        state(gpu, orc)
+    nml = None
+
+    def init_tidal():
+        m = orclib.AsModel(orc)
+        F1 = tidal_common.unit_flux(m)
+        F = tidal_common.amplitude(orclib, m, orc.cfg, F1, m.get("TRACER", 1, 0), m.get("TRACER", 1, 1)) * F1
+        gpu.init_tidal_mixing(F, tidal_diag=tidal_diag)
+        return orc.init_tidal_mixing(F, tidal_diag=tidal_diag)
+    if tidal and tidal_first:
+        nml = init_tidal()
+    if bck:
+        gpu.init_kpp_bckgrnd(**CESM); orc.init_kpp_bckgrnd(**CESM)
+    if tidal and not tidal_first:
+        nml = init_tidal()
+    return gpu, orc, nml

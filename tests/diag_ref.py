@@ -12,6 +12,7 @@ import math
 import numpy as np
 
 import aniso_ref
+from common import physical
 
 GRAV = 980.6                                     # pop_constants.F90:235
 SALT_TO_PPT = 1000.0
@@ -26,14 +27,6 @@ U53 = 2.0 ** -53
 def blocks(m):
     """get_block of every local block, in local (= block-id) order"""
     return [m.get_block(b) for b in m.local_block_ids()]
-
-
-def physical(m):
-    """(nblocks, ny_block, nx_block) mask of the physical cells ib:ie, jb:je"""
-    P = np.zeros((m.nblocks, m.nyb, m.nxb), dtype=bool)
-    for lb, B in enumerate(blocks(m)):
-        P[lb, B["jb"] - 1:B["je"], B["ib"] - 1:B["ie"]] = True
-    return P
 
 
 def grid(m, pbc=False):

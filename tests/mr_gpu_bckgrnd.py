@@ -12,6 +12,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+from tidal_common import smooth_flux  # noqa: E402
 
 
 def main():
@@ -22,7 +23,6 @@ def main():
     sys.argv = [sys.argv[0]] + argv[:at] + argv[at + 2:]
     import __graft_entry__ as ge
     from bckgrnd_ref import CESM
-    from test_tidal_host import smooth_flux
     pkg = ge.load_package()
     init, selftest = pkg.PopModel.__init__, pkg.PopModel.comm_selftest
 

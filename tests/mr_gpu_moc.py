@@ -15,6 +15,8 @@ import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import moc_ref  # noqa: E402
+from moc_ref import CASES, REG2  # noqa: E402
 
 
 def main():
@@ -28,8 +30,6 @@ def main():
     import __graft_entry__ as ge
     from popcfg import named_config
     import bench
-    import moc_ref
-    from test_gpu_moc import CASES, REG2
     pkg = ge.load_package()
     kw, sub, gkw, nml, two = CASES[args.case]
     cfg = named_config("tiny", **kw)

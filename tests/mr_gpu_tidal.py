@@ -1,5 +1,5 @@
 """Multi-rank check of Jayne tidal mixing (pop_init_tidal_mixing): tests/mr_gpu_check.py with tidal mixing initialised on every model it
-builds, from an energy flux that is a function of the global indices (tests/test_tidal_host.py smooth_flux) of amplitude --tidal amp.
+builds, from an energy flux that is a function of the global indices (tests/tidal_common.py smooth_flux) of amplitude --tidal amp.
 
     python -m torch.distributed.run --nproc-per-node 2 tests/mr_gpu_tidal.py --tidal "amp=1.0e3" --config tiny --steps 2 --no-restart \
         --kw vmix_choice=3,bckgrnd_vdc1=0.16
@@ -12,6 +12,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+from tidal_common import smooth_flux  # noqa: E402
 
 
 def main():
@@ -21,7 +22,6 @@ def main():
     amp = opt.pop("amp", 1.0e3)
     sys.argv = [sys.argv[0]] + argv[:at] + argv[at + 2:]
     import __graft_entry__ as ge
-    from test_tidal_host import smooth_flux
     pkg = ge.load_package()
     init, selftest = pkg.PopModel.__init__, pkg.PopModel.comm_selftest
 

@@ -4,6 +4,13 @@ oracle-side emulation of the ideal-age module (iage_mod.F90) through the oracle'
 (topology x scheme) it is run on."""
 import numpy as np
 
+from bckgrnd_ref import CESM
+from common import TOL_SOLVE
+from orclib import AsModel
+from parity import check, force_kpp_case
+from popcfg import named_config, synthetic_dzbc, synthetic_grid
+from tidal_common import unit_flux
+
 SECONDS_IN_YEAR = 365.0 * 86400.0
 GRAV = 980.6
 
@@ -134,10 +141,9 @@ class IageEmulation:
 
 
 def run_phases_nt(gpu, orc, step, tol_state, nt, emul=(), tol_passive=None, skip=()):
-    """test_gpu_parity.run_phases for the prognostic fields of every tracer: one step, phase by phase, the tracers n < nt compared after
+    """parity.run_phases for the prognostic fields of every tracer: one step, phase by phase, the tracers n < nt compared after
     the baroclinic driver (the stored right-hand side for n >= 2), after correct_adjust and after the tail.  emul: IageEmulation objects;
     tol_passive: tolerance of the tracers n >= 2 before the first solve (default tol_state); skip: tracers not compared here."""
-    from test_gpu_parity import TOL_LOCAL, TOL_SOLVE, check
     L = orc.L
     tp = tol_state if tol_passive is None else tol_passive
     tol = lambda n: tol_state if n < 2 else tp
@@ -199,6 +205,22 @@ def age_closed_form(kmt, dz, dzw, vdc, psurf, dt):
     return np.linalg.solve(M, rhs)
 
 
+def closed_form_worst(age, kmt, dz, dzw, vdc, psurf, dt):
+    """worst |age - closed form| / max(column) over the levels 2 .. KMT of every interior ocean column with KMT >= 2"""
+    worst, ncol = 0.0, 0
+    nb, km, ny, nx = age.shape
+    for b in range(nb):
+        for j in range(2, ny - 2):
+            for i in range(2, nx - 2):
+                K = int(kmt[b, j, i])
+                if K < 2:
+                    continue
+                x = age_closed_form(K, dz, dzw, vdc[b, :, j, i], psurf[b, j, i], dt)
+                worst = max(worst, np.abs(age[b, 1:K, j, i] - x[1:]).max() / np.abs(x).max())
+                ncol += 1
+    return worst, ncol
+
+
 # ---- the salinity-twin matrix: tests/test_passive_host.py pins the property on the oracle, tests/test_gpu_passive_matrix.py runs it on the device
 KPP = dict(vmix_choice=3, km=24)
 DEL4 = dict(hmix_tracer=4, ah=-1.0e21)
@@ -254,7 +276,6 @@ TWIN_IDS = ["%s-%s" % r for r in TWIN_ROWS]
 def twin_row(pkg, topology, scheme, nt=5, lpressure_avg=0, without_scheme=False):
     """(config, grid, tidal?) of a row of the matrix.  without_scheme: the same row with the scheme's switches left at their defaults
     (km stays: the state and the vertical grid are the row's)."""
-    from popcfg import named_config, synthetic_grid, synthetic_dzbc
     tkw, own_grid = TOPOLOGIES[topology]
     skw = dict({**PART_SCHEMES, **SCHEMES}[scheme])
     submeso, tidal = skw.pop("submeso", False), skw.pop("tidal", False)
@@ -273,13 +294,9 @@ def twin_start(orc, models, scheme, tidal):
     """The state of a row on the oracle and on the device models `models`: force_kpp_case where the row's scheme has KPP (also in its run
     without the scheme: the same state), tidal mixing and the varying background where it asks for them, then -- with nt = 5 -- the twin
     layout.  Returns the field of tracer 4."""
-    from orclib import AsModel
     if {**PART_SCHEMES, **SCHEMES}[scheme].get("vmix_choice") == 3:
-        from test_gpu_parity import force_kpp_case
         force_kpp_case(NoDevice(), orc)
     if tidal:
-        from bckgrnd_ref import CESM
-        from test_gpu_tidal import unit_flux
         orc.init_tidal_mixing(1.0e3 * unit_flux(AsModel(orc)))
         orc.init_kpp_bckgrnd(**CESM)
         for m in models:

@@ -51,6 +51,8 @@ import math
 import numpy as np
 from scipy.linalg import solve_banded
 
+from common import interior
+
 GRAV = 980.6           # pop_constants.F90:235 (non-CCSMCOUPLED)
 THREE_D = ("TRACER", "UVEL", "VVEL", "RHO", "VVC", "KPP_SRC", "UISOP", "VISOP", "WISOP", "GM_SF_SLX", "GM_SF_SLY")
 
@@ -240,10 +242,6 @@ class GpuAdapter:
 
     def close(self):
         self.m.close()
-
-
-def interior(a):
-    return a[..., 2:-2, 2:-2]
 
 
 def _prepare(A, nsteps=2):

@@ -291,3 +291,18 @@ def read_header(path, fields=()):
         except HeaderError as e:
             hd.problems.append(str(e))
     return hd
+
+
+def parse_hdr(path):
+    """<path>.hdr read plainly, without the reference's rules: section -> {name: (type text, value text)}"""
+    sec, cur = {}, None
+    for line in open(path + ".hdr"):
+        line = line.strip()
+        if line.startswith("&"):
+            cur = line[1:].strip(); sec[cur] = {}
+        elif line.startswith("/"):
+            cur = None
+        elif cur is not None and line.count(":") >= 2:
+            name, typ, val = line.split(":", 2)
+            sec[cur][name.strip()] = (typ.strip(), val.strip())
+    return sec

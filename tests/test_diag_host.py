@@ -7,6 +7,7 @@ import pytest
 
 import aniso_ref
 import diag_ref
+from common import physical
 from ice_common import ice_grid
 from popcfg import named_config
 
@@ -43,7 +44,7 @@ def test_arming_and_refusals_without_a_device(pkg):
 def test_grid_volumes(pkg, pbc, kw):
     """every sum within N 2^-53 sum|term| of the exact sum of the same terms (the first-order bound of any order of summation)"""
     m = host(pkg, pbc=pbc, **kw)
-    km, P = m.km, diag_ref.physical(m)
+    km, P = m.km, physical(m)
     TAREA, UAREA, HT, HU, KMT, KMU = m.get("TAREA"), m.get("UAREA"), m.get("HT"), m.get("HU"), m.geti("KMT"), m.geti("KMU")
     dz = aniso_ref.vertical_dz(km)
     if pbc:                                                   # grid.F90:1001-1020: HT, HU end with the partial bottom cell

@@ -4,91 +4,32 @@ del2 with am = 0, and whole steps."""
 import numpy as np
 import pytest
 
-import aniso_ref
-from popcfg import named_config, synthetic_grid, synthetic_dzbc
-from test_gpu_parity import TOL_LOCAL
+from aniso_common import CASES, angle_grid, reference, state
+from common import TOL_LOCAL, physical
+from mr_launch import ROOT, run_check
+from popcfg import named_config, synthetic_dzbc
 
 pytestmark = pytest.mark.gpu
-
-GX3V7 = dict(aniso_alignment="east", lvariable_hmix_aniso=1, vconst_4=2.0e-8)
-
-
-def _state(m, seed):
-    """random U, V (0 below KMU) at time levels old and current, ghost cells from the halo update"""
-    rng = np.random.default_rng(seed)
-    kmu = m.geti("KMU")
-    wet = kmu[:, None] >= np.arange(1, m.km + 1)[None, :, None, None]
-    U = np.where(wet, rng.standard_normal((m.nblocks, m.km, m.nyb, m.nxb)), 0.0)
-    V = np.where(wet, rng.standard_normal(U.shape), 0.0)
-    for tl in (0, 1):
-        m.set("UVEL", U, tl); m.set("VVEL", V, tl)
-        m.halo_update_loc("UVEL", tl, 0, "NEcorner", "vector"); m.halo_update_loc("VVEL", tl, 0, "NEcorner", "vector")
-    return m.get("UVEL", 1), m.get("VVEL", 1)
-
-
-def _physical(m):
-    mask = np.zeros((m.nblocks, m.nyb, m.nxb), dtype=bool)
-    for lb, bid in enumerate(m.local_block_ids()):
-        b = m.get_block(bid)
-        mask[lb, b["jb"] - 1:b["je"], b["ib"] - 1:b["ie"]] = True
-    return mask
 
 
 def _friction(pkg, cfg, grid=None, seed=5, tuning=None):
     m = pkg.PopModel(cfg, grid=grid, tuning=tuning)
-    U, V = _state(m, seed)
+    U, V = state(m, seed)
     m.time_manager()
     m.run_phase("hmix_momentum")
     return m, U, V, m.get("HDU"), m.get("HDV")
 
 
-def _reference(m, cfg, U, V):
-    f = aniso_ref.geometry(m.get("HTN"), m.get("HTE"), m.get("DXUR"), m.get("DYUR"), m.scalar("dtu"))
-    for n in ("UAREA", "ANGLE", "ULAT", "DXU", "DYU"):
-        f[n] = m.get(n)
-    f["KMU"] = m.geti("KMU")
-    if cfg.lsmag_aniso:
-        f["DSMIN"], f["F_PERP_SMAG"] = m.get("DSMIN"), m.get("F_PERP_SMAG")
-    fpa = fpe = dzu = None
-    if cfg.lvariable_hmix_aniso:
-        fpa, fpe = m.get("F_PARA"), m.get("F_PERP")
-    if cfg.partial_bottom_cells:
-        dz = aniso_ref.vertical_dz(m.km)
-        kmu, dzub = f["KMU"], m.get("DZUB")
-        ks = np.arange(1, m.km + 1)[None, :, None, None]
-        dzu = np.where(kmu[:, None] == ks, dzub[:, None], dz[1:][None, :, None, None] + 0.0 * U)
-    return aniso_ref.hdiffu(U, V, f, cfg, fpa, fpe, dzu)
-
-
-def _angle_grid(c5):
-    g = synthetic_grid(c5)
-    nx, ny = c5.nx_global, c5.ny_global
-    g["ANGLE"] = 0.4 * np.sin(2.0 * np.pi * np.arange(nx) / nx)[None, :] * np.cos(np.pi * np.arange(ny) / ny)[:, None]
-    return g
-
-
-CASES = [
-    ("grid-constant", "tiny", {}, dict(visc_para=2.0e9, visc_perp=0.5e9), False),
-    ("east-variable-angle", "tiny", {}, dict(aniso_alignment="east", lvariable_hmix_aniso=1), True),
-    ("smag", "tiny", {}, dict(lsmag_aniso=1, c_para=8.0, c_perp=4.0, smag_lat_fact=0.98), False),
-    ("smag-variable-east", "tiny", {}, dict(aniso_alignment="east", lsmag_aniso=1, lvariable_hmix_aniso=1, c_para=8.0, c_perp=4.0,
-                                            smag_lat_fact=0.98), True),
-    ("partial-bottom-cells", "tiny", {"partial_bottom_cells": 1, "stepped_bathymetry": 1}, dict(visc_para=2.0e9, visc_perp=0.5e9), False),
-    ("padded-blocks", "tiny", {"block_size_x": 20, "block_size_y": 16}, dict(lvariable_hmix_aniso=1), False),
-    ("tripole-east-variable", "tiny", {"ns_boundary": 2, "block_size_x": 48, "block_size_y": 10}, dict(GX3V7), True),
-]
-
-
 @pytest.mark.parametrize("name,cname,kw5,kw6,angle", CASES, ids=[c[0] for c in CASES])
 def test_friction_phase_matches_restatement(pkg, name, cname, kw5, kw6, angle):
     c5 = named_config(cname, **kw5)
-    grid = _angle_grid(c5) if angle else None
+    grid = angle_grid(c5) if angle else None
     if grid is not None and c5.partial_bottom_cells:
         grid["DZBC"] = synthetic_dzbc(c5, grid["KMT"])
     cfg = pkg.anisotropic_config(c5, **kw6)
     m, U, V, hdu, hdv = _friction(pkg, cfg, grid)
-    ru, rv = _reference(m, cfg, U, V)
-    phys = _physical(m)[:, None] & np.ones((1, m.km, 1, 1), dtype=bool)
+    ru, rv = reference(m, cfg, U, V)
+    phys = physical(m)[:, None] & np.ones((1, m.km, 1, 1), dtype=bool)
     for a, b in ((hdu, ru), (hdv, rv)):
         assert np.isfinite(a).all()
         s = np.abs(b[phys]).max()
@@ -104,7 +45,7 @@ def test_east_equals_grid_bitwise(pkg):
     _, _, _, gu, gv = _friction(pkg, pkg.anisotropic_config(c5, **kw))
     _, _, _, eu, ev = _friction(pkg, pkg.anisotropic_config(c5, aniso_alignment="east", **kw))
     assert np.array_equal(gu, eu) and np.array_equal(gv, ev)
-    g = _angle_grid(c5)
+    g = angle_grid(c5)
     iso = dict(visc_para=1.0e9, visc_perp=1.0e9)
     _, _, _, gu, gv = _friction(pkg, pkg.anisotropic_config(c5, **iso), g)
     _, _, _, eu, ev = _friction(pkg, pkg.anisotropic_config(c5, aniso_alignment="east", **iso), g)
@@ -122,7 +63,7 @@ def test_zero_friction_momentum_equals_del2_with_am_zero(pkg, rows):
     a.set("HDU", z); a.set("HDV", z)
     a.run_phase("momentum_rhs")
     d = pkg.PopModel(c5, tuning=tun)
-    _state(d, 5)
+    state(d, 5)
     d.time_manager()
     d.run_phase("momentum_rhs")
     for n, tl in (("UVEL", 2), ("VVEL", 2), ("ZX", 1), ("ZY", 1)):
@@ -240,10 +181,10 @@ def test_friction_dissipates_energy(pkg, align):
     sum UAREA dz (U HDU + V HDV) is <= 0 on every level (hmix_aniso.F90:565-569: positive-definite dissipation)"""
     rng = np.random.default_rng(11)
     m, d = _cartesian(pkg, ring=2, aniso_alignment=align, visc_para=4.0e9, visc_perp=1.0e9, ANGLE=rng.uniform(-np.pi, np.pi, (40, 48)))
-    U, V = _state(m, 17)
+    U, V = state(m, 17)
     m.time_manager(); m.run_phase("hmix_momentum")
     hdu, hdv, area = m.get("HDU"), m.get("HDV"), m.get("UAREA")
-    phys = _physical(m)
+    phys = physical(m)
     for k in range(m.km):
         w = (area * (U[:, k] * hdu[:, k] + V[:, k] * hdv[:, k]))[phys].sum()
         e = (area * (U[:, k] ** 2 + V[:, k] ** 2))[phys].sum()
@@ -301,7 +242,5 @@ def test_gx1v7_cesm_setup_steps(pkg):
 ])
 def test_multirank_equals_single_rank(nranks, aniso, kw, grid):
     import os
-    from test_gpu_multirank import _run_check
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    _run_check(["--nproc-per-node", str(nranks), os.path.join(root, "tests", "mr_gpu_aniso.py"), "--aniso", aniso, "--config", "tiny",
+    run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_aniso.py"), "--aniso", aniso, "--config", "tiny",
                 "--steps", "3", "--grid", str(grid), "--kw", kw], 300)

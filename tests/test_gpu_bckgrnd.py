@@ -1,40 +1,21 @@
 """The latitude-varying KPP background diffusivity on the GPU (pop_init_kpp_bckgrnd; k_kpp_bckgrnd, k_kpp_tidal<., true>): row by row
 against the unchanged CPU oracle, the coefficients below the boundary layer against a run with a uniform background, a uniform field
 bit for bit against the per-level background, the tidal diagnostics, every KPP kernel form, the look-ahead, and two ranks."""
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
-import bckgrnd_ref
 import tidal_ref
+from bckgrnd_common import FIELDS, ORACLE_CASES, STEPPED, banda_arctic_grid, feed_oracle, restated, set_flux
 from bckgrnd_ref import CESM
+from common import TOL_LOCAL, physical
+from mr_launch import ROOT, run_check
 from orclib import Oracle
 from popcfg import named_config
-from test_bckgrnd_host import banda_arctic_grid
-from test_gpu_parity import TOL_LOCAL
-from test_gpu_submeso import physical
-from test_gpu_tidal import amplitude, noisy_state, set_state, unit_flux
+from tidal_common import KPP, amplitude, noisy_state, set_state, unit_flux
 
 pytestmark = pytest.mark.gpu
-
-KPP = dict(vmix_choice=3, bckgrnd_vdc1=0.16)
-STEPPED = dict(KPP, stepped_bathymetry=1)
-FIELDS = (("VDC0", ("VDC", 1, 0)), ("VDC1", ("VDC", 1, 1)), ("VVC", ("VVC",)), ("HBLT", ("HBLT",)), ("SRC0", ("KPP_SRC", 1, 0)),
-          ("SRC1", ("KPP_SRC", 1, 1)))
-
-
-def surface_flux(TLAT):
-    """surface tracer fluxes (test_gpu_parity.force_kpp_case): cooling, hence an unstable boundary layer and a non-zero non-local source
-    KPP_SRC, in the north; heating in the south"""
-    return -3.0e-2 * np.sin(TLAT) - 1.0e-2, 2.0e-6 * np.cos(2.0 * TLAT)
-
-
-def set_flux(m):
-    stf_t, stf_s = surface_flux(m.get("TLAT"))
-    m.set("STF", stf_t, n=0); m.set("STF", stf_s, n=1)
-    return stf_t, stf_s
 
 
 def outputs(m, diag=False):
@@ -63,30 +44,6 @@ def run(pkg, cfg, grid=None, tuning=None, bck=CESM, tidal=None, tidal_first=Fals
     return m, T, S, F, nml
 
 
-def restated(m, cfg, bck=CESM):
-    return bckgrnd_ref.field(m.get("TLAT"), m.get("TLON"), cfg.bckgrnd_vdc1, **bck)
-
-
-def _feed_oracle(orc, T, S):
-    """the tracers at every time level and the densities that belong to them (the oracle's half of test_gpu_tidal._feed)"""
-    P = C.POINTER(C.c_double)
-    orc.L.orc_state.argtypes = [C.c_void_p, C.c_int, C.c_int, P, P, P, P, P, C.c_int]
-    for tl in (0, 1, 2):
-        for n, X in ((0, T), (1, S)):
-            orc.f3("TRACER", tl, n)[...] = X
-    R = np.empty_like(T)
-    for k in range(orc.km):
-        t = np.ascontiguousarray(T[:, k]); s_ = np.ascontiguousarray(S[:, k]); r = np.empty_like(t)
-        orc.L.orc_state(orc.h, k + 1, k + 1, t.ctypes.data_as(P), s_.ctypes.data_as(P), r.ctypes.data_as(P), None, None, t.size)
-        R[:, k] = r
-    for tl in (0, 1):
-        orc.f3("RHO", tl)[...] = R
-    return R
-
-
-ORACLE_CASES = [("tiny", {}, False), ("banda-grid", {}, True), ("dbl-diff", dict(ldbl_diff=1), False), ("no-rich", dict(lrich=0), False)]
-
-
 @pytest.mark.parametrize("name,kw5,own_grid", ORACLE_CASES, ids=[c[0] for c in ORACLE_CASES])
 def test_rows_match_oracle(pkg, orclib_built, name, kw5, own_grid):
     """KPP depends on the background column by column (only the average to VVC mixes rows), and on a lat-lon grid the field takes few
@@ -100,7 +57,7 @@ def test_rows_match_oracle(pkg, orclib_built, name, kw5, own_grid):
         for X in (T, S):
             x = np.ascontiguousarray(X[:, k]); gpu.halo_update_host_loc(x); X[:, k] = x
     o0 = Oracle(cfg, grid=grid)
-    R = _feed_oracle(o0, T, S)
+    R = feed_oracle(o0, T, S)
     o0.close()
     for tl in (0, 1, 2):
         gpu.set("TRACER", T, tl=tl, n=0); gpu.set("TRACER", S, tl=tl, n=1)
@@ -126,7 +83,7 @@ def test_rows_match_oracle(pkg, orclib_built, name, kw5, own_grid):
     diff, scale, seen = {n: 0.0 for n in got}, {n: 0.0 for n in got}, np.zeros(ocean.shape, dtype=bool)
     for v in values:
         orc = Oracle(named_config("tiny", **dict(KPP, **dict(kw5, bckgrnd_vdc1=float(v)))), grid=grid)
-        _feed_oracle(orc, T, S)
+        feed_oracle(orc, T, S)
         orc.L.orc_time_manager(orc.h); orc.run_phase("tracer_rhs")
         want = {"VDC0": orc.vdc(0), "VDC1": orc.vdc(1), "SRC0": orc.f3("KPP_SRC", 1, 0), "SRC1": orc.f3("KPP_SRC", 1, 1), "HBLT": orc.f2("HBLT")}
         sel = ocean & (ref == v)
@@ -138,7 +95,7 @@ def test_rows_match_oracle(pkg, orclib_built, name, kw5, own_grid):
             scale[n] = max(scale[n], np.abs(want[n][s]).max())
         orc.close()
     assert np.array_equal(seen, ocean)
-    # test_gpu_parity.relerr's rule.  The state is fed as the issue says, without a surface flux, so KPP_SRC is 0 on both sides here;
+    # common.relerr's rule.  The state is fed as the issue says, without a surface flux, so KPP_SRC is 0 on both sides here;
     # the tests below set a flux (set_flux) and compare a non-zero KPP_SRC bit for bit.  With this noisy state AND a flux the device's
     # HBLT differs from the oracle's by 5e-13 whatever the background is (measured: the same figure with lrich = 0 and with ldbl_diff),
     # which is the boundary-layer-depth interpolation on an unsmooth profile and nothing this comparison is about.
@@ -350,7 +307,5 @@ def test_look_ahead_on_and_off(pkg):
 
 @pytest.mark.parametrize("opt", ["", "tidal=1.0e3"], ids=["no-tidal", "tidal"])
 def test_two_ranks_equal_single_rank(opt):
-    from test_gpu_multirank import _run_check
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    _run_check(["--nproc-per-node", "2", os.path.join(root, "tests", "mr_gpu_bckgrnd.py"), "--bckgrnd", opt,
+    run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_bckgrnd.py"), "--bckgrnd", opt,
                 "--config", "tiny", "--steps", "2", "--no-restart", "--kw", "vmix_choice=3,bckgrnd_vdc1=0.16,stepped_bathymetry=1"], 300)

@@ -1,5 +1,5 @@
 """Global and CFL diagnostics on the device (pop_diag_*) against the NumPy restatement tests/diag_ref.py.  Base config 'tiny'
-(48 x 40 x 16, 16 blocks of 12 x 10, land, an averaging step at step 2), perturbed as tests/test_gpu_tavg.py::make perturbs it.
+(48 x 40 x 16, 16 blocks of 12 x 10, land, an averaging step at step 2), perturbed as tavg_common.make perturbs it.
 
 Global sums: every term of the restatement is formed in the reference's order and the terms are summed exactly (math.fsum); the
 device value must lie within N 2^-53 sum|term| of that sum -- the first-order bound of ANY order of summation of N terms, so it is
@@ -8,14 +8,14 @@ import numpy as np
 import pytest
 
 import diag_ref
+from common import STATE
 from popcfg import named_config
-from test_gpu_land import FIELDS
-from test_gpu_tavg import make
+from tavg_common import make
 
 pytestmark = pytest.mark.gpu
 
 ONE_BLOCK = dict(block_size_x=48, block_size_y=40)
-SUM_CASES = {                                    # name -> (case of test_gpu_tavg.make, more config keywords, steps armed)
+SUM_CASES = {                                    # name -> (case of tavg_common.make, more config keywords, steps armed)
     "avgfit": ("avgfit", {}, (1, 2, 3)),         # the Euler, the averaging and a leapfrog step
     "robert": ("robert", {}, (1, 2)),
     "pbc": ("pbc", {}, (2, 3)),
@@ -121,7 +121,7 @@ def test_arming_leaves_the_model_alone(pkg):
         a.step(); b.step()
         assert a.solver_diagnostics()[0] == b.solver_diagnostics()[0], step
     assert a.dim("land_skip_active") == 1                            # the sites ran beside kernels that skip land tiles
-    for name, n in FIELDS:
+    for name, n in STATE:
         for tl in (0, 1, 2):
             assert np.array_equal(a.get(name, tl, n), b.get(name, tl, n)), (name, tl)
     assert a.diag_global()["nsteps_total_after"] == 10 and a.diag_cfl("advt")["nsteps_total"] == 10

@@ -4,9 +4,10 @@ involve the oracle."""
 import numpy as np
 import pytest
 
+from common import TOL_LOCAL, TOL_SOLVE, pick, relerr
 from popcfg import named_config, synthetic_grid
 from orclib import Oracle
-from test_gpu_parity import run_phases, force_kpp_case, relerr, pick, TOL_LOCAL, TOL_SOLVE
+from parity import run_phases, force_kpp_case
 
 pytestmark = pytest.mark.gpu
 

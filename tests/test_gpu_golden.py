@@ -6,7 +6,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-TOL = 1e-8     # fp64, downstream of the solver's fixed-tree dot products (see test_gpu_parity.py)
+TOL = 1e-8     # fp64, downstream of the solver's fixed-tree dot products (see tests/common.py)
 
 
 @pytest.mark.parametrize("case", ["const", "kpp_del4", "upwind3", "robert", "pcsi_evp", "lw_lim", "pbc_kpp_del4", "padded", "gm", "gm_tlt", "cesm_all"])

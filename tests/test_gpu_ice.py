@@ -6,9 +6,9 @@ import numpy as np
 import pytest
 
 import ice_ref
+from common import STATE, TOL_LOCAL
 from ice_common import cold_start, ice_grid, wet_mask
 from popcfg import named_config
-from test_gpu_parity import TOL_LOCAL
 
 pytestmark = pytest.mark.gpu
 
@@ -94,8 +94,6 @@ STEP_CASES = {
     "del4": (dict(hmix_momentum=4, hmix_tracer=4, am=-1.0e22, ah=-1.0e21, tmix_opt=0), NML, dict(d2t_fuse=1, d2u_fuse=1)),
     "nt4-iage": (dict(nt=4), NML, None),
 }
-STATE = [("TRACER", 0), ("TRACER", 1), ("UVEL", 0), ("VVEL", 0), ("RHO", 0), ("PSURF", 0), ("UBTROP", 0), ("VBTROP", 0),
-         ("GRADPX", 0), ("GRADPY", 0), ("PGUESS", 0)]
 
 
 def start(pkg, cfg, nml, tuning=None, ice=True):

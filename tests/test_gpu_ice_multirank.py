@@ -6,8 +6,9 @@ import os
 
 import pytest
 
+from mr_launch import ROOT, run_check
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("nranks,kw,grid", [
@@ -19,7 +20,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     (4, "ns_boundary=2", 1),                        # 4 x 4 blocks, a row of blocks per rank: the fold has one owner
 ], ids=["2-default", "4-default", "2-robert", "4-robert", "2-tripole", "4-tripole"])
 def test_ranks_equal_single_rank(nranks, kw, grid):
-    from test_gpu_multirank import _run_check
-    out = _run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_ice.py"),
-                      "--config", "tiny", "--steps", "3", "--no-restart", "--grid", str(grid), "--kw", kw], 300)
+    out = run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_ice.py"),
+                     "--config", "tiny", "--steps", "3", "--no-restart", "--grid", str(grid), "--kw", kw], 300)
     assert "no ice field was compared" not in out, out[-2000:]

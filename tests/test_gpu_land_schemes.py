@@ -30,13 +30,13 @@ import pytest
 
 import cesm_case as cc
 from bckgrnd_ref import CESM
+from cesm_case import pair
+from common import STATE, TOL_LOCAL, TOL_SOLVE, WORK
 from ice_common import cold_start
+from parity import run_phases
 from popcfg import named_config
-from test_gpu_land import FIELDS, WORK
-from test_gpu_parity import TOL_LOCAL, TOL_SOLVE, run_phases
-from test_gpu_schemes_oracle import pair
-from test_gpu_tavg import ICE_NML, buffers, request
-from test_tidal_host import smooth_flux
+from tavg_common import ICE_NML, buffers, request
+from tidal_common import smooth_flux
 import tavg_ref
 
 pytestmark = pytest.mark.gpu
@@ -56,7 +56,7 @@ MUST = {"gm": ["GM_GTK"], "bolus": ["UISOP", "VISOP", "WISOP"], "tlt": ["TLT_DIA
 
 
 def kpp_state(m):
-    """what test_gpu_parity.force_kpp_case does to an oracle, from the model's own fields: surface fluxes and a nearly homogeneous upper
+    """what parity.force_kpp_case does to an oracle, from the model's own fields: surface fluxes and a nearly homogeneous upper
     ocean (eight levels, where sin(3 TLAT) > 0), so that the boundary layer spans several levels, the non-local source is at work and
     the mixed layer the submesoscale scheme reads is deep; the densities of the new state through pop_state_host"""
     tlat, kmt = m.get("TLAT"), m.geti("KMT")
@@ -124,7 +124,7 @@ def same_everywhere(a, b, scheme, what):
             d = x != y
             col = d if d.ndim == 3 else d.any(axis=1)
             bad.append("%s: %d cells, %d columns of them %d ocean" % (label, d.sum(), col.sum(), (col & ocean).sum()))
-    for f, n in FIELDS:
+    for f, n in STATE:
         for tl in (0, 1, 2):
             cmp("%s(%d) tl %d" % (f, n, tl), a.get(f, tl, n), b.get(f, tl, n))
     for f in WORK:
@@ -332,7 +332,7 @@ def test_exact_restart_across_the_switch(pkg, tmp_path, fresh):
         a.step(); b.step()
         assert a.dim("land_skip_active") == 1 and b.dim("land_skip_active") == (1 if s > 4 else 0), s
         assert a.solver_diagnostics() == b.solver_diagnostics(), "step %d after the restart" % s
-    for f, n in FIELDS:
+    for f, n in STATE:
         for tl in (0, 1):
             assert np.array_equal(a.get(f, tl, n), b.get(f, tl, n)), (f, n, tl)
     a.close(); b.close()
@@ -376,7 +376,7 @@ def test_tuning_field_is_bitwise_neutral(pkg, row):
         for _ in range(nsteps):
             m.step()
             iters.append(m.solver_diagnostics())
-        out = {(f, n, tl): m.get(f, tl, n) for f, n in FIELDS for tl in (0, 1)}
+        out = {(f, n, tl): m.get(f, tl, n) for f, n in STATE for tl in (0, 1)}
         return m, iters, out
     defaults = {}
     for ix, xt in enumerate(xs):

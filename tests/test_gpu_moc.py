@@ -12,25 +12,11 @@ import numpy as np
 import pytest
 
 import moc_ref
+from common import STATE
+from moc_ref import CASES, REG2
 from popcfg import named_config
-from test_gpu_land import FIELDS
 
 pytestmark = pytest.mark.gpu
-
-REG2 = (6,)
-GM = dict(hmix_tracer=3, ah=0.8e7, gm_diag_bolus=1)
-SOUTHERN = dict(lat_aux_grid_type="southern")
-USER = dict(lat_aux_grid_type="user-specified", lat_aux_begin=-60.0, lat_aux_end=60.0, n_lat_aux_grid=24)
-# name -> (config keywords, submeso_config keywords or None, grid keywords, transports_nml keywords, two regions)
-CASES = {
-    "avgfit": (dict(), None, dict(), SOUTHERN, True),                                   # centred advection, const vmix, an averaging step
-    "kpp_robert": (dict(vmix_choice=3, km=24, tmix_opt=3), None, dict(), SOUTHERN, False),
-    "gm_bolus": (dict(GM), None, dict(), USER, True),                                   # some ocean cells lie in no bin
-    # KPP: the mixed layer of submeso_sf is HMXL, deeper than the first level, so WSUBM moves (it is 0 where the layer ends at zw(1))
-    "gm_submeso": (dict(GM, vmix_choice=3, km=24), dict(submeso_diag=1), dict(), SOUTHERN, True),
-    "submeso_no_bolus": (dict(hmix_tracer=3, ah=0.8e7, vmix_choice=3, km=24), dict(submeso_diag=1), dict(), SOUTHERN, False),   # component 2 stays 0
-    "full": (dict(), None, dict(bend=False, one_longitude=True), dict(lat_aux_grid_type="full"), True),
-}
 
 
 def make(pkg, case, request=1, tuning=None):
@@ -168,7 +154,7 @@ def test_request_leaves_the_model_alone(pkg):
     for s in range(10):
         a.step(); b.step()
         assert a.solver_diagnostics() == b.solver_diagnostics(), s
-    for name, n in FIELDS:
+    for name, n in STATE:
         for tl in (0, 1, 2):
             assert np.array_equal(a.get(name, tl, n), b.get(name, tl, n)), (name, tl)
     assert np.abs(a.moc_get()).max() > 0.0

@@ -4,10 +4,10 @@ import os
 
 import pytest
 
+from mr_launch import ROOT, run_check
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_two_ranks_equal_single_rank():
-    from test_gpu_multirank import _run_check
-    _run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_moc.py"), "--case", "gm_submeso", "--steps", "3"], 300)
+    run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_moc.py"), "--case", "gm_submeso", "--steps", "3"], 300)

@@ -7,40 +7,15 @@ import sys
 
 import pytest
 
+from mr_launch import ROOT, STUB, run_check
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-STUB = os.path.join(ROOT, "tests", "rccl_stub", "librccl_stub.so")
-_RDZV_ERRORS = ("address already in use", "EADDRINUSE", "RendezvousConnectionError", "RendezvousTimeoutError", "DistNetworkError",
-                "failed to bind", "The server socket has failed")
-
-
-def _run_check(args, timeout, env=None, transport="staged"):
-    """Launch tests/mr_gpu_check.py under torch.distributed.run.  torchrun itself binds a free rendezvous port
-    (--standalone), so there is no window between choosing and binding it.  The launch is repeated ONCE, and only
-    when there is no verdict AND stderr names a rendezvous / bind error; a run that ends without a verdict for any
-    other reason (a rank that aborted or faulted) fails with its output, and a FAILED verdict is never retried."""
-    env = dict(os.environ, **(env or {}))
-    if transport == "native":
-        if not os.path.exists(STUB):
-            subprocess.check_call(["make", "-s", "-C", os.path.dirname(STUB)])
-        env["POP_RCCL_LIB"] = STUB
-        args = args + ["--transport", "native"]
-    out = None
-    for attempt in range(2):
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--standalone", "--local-addr", "127.0.0.1", "--nnodes=1"] + args
-        out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
-        if "MR_GPU_CHECK" in out.stdout or not any(e in out.stderr for e in _RDZV_ERRORS):
-            break
-    assert "MR_GPU_CHECK OK" in out.stdout, out.stdout[-6000:] + out.stderr[-3000:]
-    return out.stdout
 
 
 def test_gx1v7_two_ranks_equal_single_rank():
     """BASELINE configs[3] rehearsed on one GPU: gx1v7 (KPP, pcg) in two j-bands -- the replicated barotropic solve
     and the 3-D halo exchanges at production size -- is bit for bit the single-rank run."""
-    _run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "gx1v7", "--steps", "2",
+    run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "gx1v7", "--steps", "2",
                 "--kw", "block_size_y=192"], 600)
 
 
@@ -48,14 +23,14 @@ def test_large_grid_two_ranks_equal_single_rank():
     """The large-grid kernel selection of tx0.1v3 (del4 + KPP, 62 levels; presummed block sums, two-cell solver
     kernels, column KPP, 64x4 tracer tiles, fused distributed pcg) on a quarter-size domain in two j-bands: bit for
     bit the single-rank run."""
-    _run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tx0.1v3", "--steps", "2",
+    run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tx0.1v3", "--steps", "2",
                 "--kw", "nx_global=1800,ny_global=1200,block_size_x=1800,block_size_y=600"], 900)
 
 
 def test_large_grid_pcsi_two_ranks_equal_single_rank():
     """... and with P-CSI, where the large-grid selection is two iterations per launch and per halo exchange on both sides of the
     comparison (k_pcsi_step_x2: single rank with the rings read at their source cells, two ranks with x, dx, r' exchanged two rings wide)."""
-    _run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tx0.1v3", "--steps", "2",
+    run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tx0.1v3", "--steps", "2",
                 "--kw", "nx_global=1800,ny_global=1200,block_size_x=1800,block_size_y=600,solver_choice=3"], 900)
 
 
@@ -84,7 +59,7 @@ def test_large_grid_pcsi_two_ranks_equal_single_rank():
     (2, "hmix_momentum=4,hmix_tracer=4,am=-1.0e22,ah=-1.0e21,lvariable_hmix=1", {"POP_D2T_FUSE": "1"}),   # del4 first Laplacians formed by the previous step's kernels: their ghost ring crosses ranks
 ])
 def test_multirank_equals_single_rank(nranks, kw, env):
-    _run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tiny", "--steps", "3",
+    run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tiny", "--steps", "3",
                 "--kw", kw], 300, env)
 
 
@@ -113,14 +88,14 @@ def test_multirank_equals_single_rank(nranks, kw, env):
     (3, "hmix_momentum=4,hmix_tracer=4,am=-1.0e22,ah=-1.0e21,block_size_x=24,block_size_y=20,vmix_choice=3,km=24", {"POP_D2T_FUSE": "1"}),   # the same with uneven ownership and KPP
 ])
 def test_native_transport_equals_single_rank(nranks, kw, env):
-    _run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tiny", "--steps", "3",
+    run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tiny", "--steps", "3",
                 "--kw", kw], 300, env, transport="native")
 
 
 def test_native_transport_large_grid_two_ranks():
     """quarter-size tx0.1v3 in two j-bands over the native transport: the large-grid kernel selection with the
     distributed solver (3-D halo messages of 62 levels through ncclSend/ncclRecv groups)"""
-    _run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tx0.1v3", "--steps", "2",
+    run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tx0.1v3", "--steps", "2",
                 "--kw", "nx_global=1800,ny_global=1200,block_size_x=1800,block_size_y=600"], 900,
                {"POP_RCCL_STUB_BOX_MB": "16", "POP_SOLVER_DISTRIBUTED": "1"}, transport="native")
 
@@ -136,8 +111,8 @@ def test_stream_operations_per_distributed_iteration():
     stream, k_fpcg_b(reads the receive buffer) | block sums | all-reduce = 7 enqueued, 6 on the critical path (round 1:
     9, all serial).  ChronGear: exchange | k_fcg_a | block sums | ONE all-reduce | k_fcg_b(+pack) = 5."""
     args = ["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tiny", "--steps", "2", "--kw"]
-    assert _ops(_run_check(args + [""], 300, transport="native")) <= 7.0 + 0.5
-    assert _ops(_run_check(args + ["solver_choice=2"], 300, transport="native")) <= 5.0 + 0.5
+    assert _ops(run_check(args + [""], 300, transport="native")) <= 7.0 + 0.5
+    assert _ops(run_check(args + ["solver_choice=2"], 300, transport="native")) <= 5.0 + 0.5
 
 
 # ---- land elimination across ranks (POP_LAND_FULL_STEPS=0: tiles without ocean are skipped from the first step, in the
@@ -158,7 +133,7 @@ _SKIP = {"POP_LAND_FULL_STEPS": "0"}
 ])
 def test_land_elimination_across_ranks(nranks, kw, env, transport):
     """(see the comment above the parameter list)"""
-    _run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "wide", "--steps", "4",
+    run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "wide", "--steps", "4",
                 "--kw", kw], 300, env, transport=transport)
 
 
@@ -171,7 +146,7 @@ def test_land_elimination_across_ranks(nranks, kw, env, transport):
     (4, "distribution=1,block_size_x=48,block_size_y=4", dict(_SKIP, POP_SOLVER_DISTRIBUTED="1"), "native"),
 ])
 def test_balanced_distribution_equals_single_rank(nranks, kw, env, transport):
-    _run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tiny", "--steps", "3",
+    run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tiny", "--steps", "3",
                 "--kw", kw], 300, env, transport=transport)
 
 
@@ -188,7 +163,7 @@ def test_balanced_distribution_equals_single_rank(nranks, kw, env, transport):
     (2, "ns_boundary=2,tadvect=3,block_size_x=48,block_size_y=10", {"POP_SOLVER_DISTRIBUTED": "1"}, "native"),   # lw_lim: flux-velocity fields across the fold and the ranks
 ])
 def test_tripole_across_ranks_equals_single_rank(nranks, kw, env, transport):
-    _run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tiny", "--steps", "3",
+    run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tiny", "--steps", "3",
                 "--grid", "1", "--kw", kw], 300, env, transport=transport)
 
 
@@ -199,7 +174,7 @@ def test_tripole_across_ranks_equals_single_rank(nranks, kw, env, transport):
 def test_land_elimination_with_overlapped_halo(nranks, kw, env):
     """tall j-band blocks: the mid-step exchange of the new tracers runs beside the momentum kernel on a window of tile rows
     (windows classify their tiles one by one, the whole launch uses the compacted list)"""
-    _run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tiny", "--steps", "3",
+    run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tiny", "--steps", "3",
                 "--kw", kw], 300, env, transport="native")
 
 
@@ -330,6 +305,6 @@ def test_75_row_bands_on_four_ranks_equal_single_rank():
     """the same band height over the native transport on four ranks (balanced by ocean columns: uneven block counts per rank), a
     narrower domain so that four ranks and their single-rank twins fit the one GPU of the test box: 900 x 1200 x 62 is still above
     the 2^19-column threshold of the large-grid kernel selection"""
-    _run_check(["--nproc-per-node", "4", os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tx0.1v3", "--steps", "3", "--no-restart",
+    run_check(["--nproc-per-node", "4", os.path.join(ROOT, "tests", "mr_gpu_check.py"), "--config", "tx0.1v3", "--steps", "3", "--no-restart",
                 "--kw", "nx_global=900,ny_global=1200,block_size_x=900,block_size_y=75,distribution=1"], 900,
                {"POP_RCCL_STUB_BOX_MB": "16", "POP_SOLVER_DISTRIBUTED": "1", "POP_LAND_FULL_STEPS": "0"}, transport="native")

@@ -5,35 +5,14 @@ into blocks that divide it."""
 import numpy as np
 import pytest
 
+from common import TOL_LOCAL, TOL_SOLVE, block_masks, relerr
 from popcfg import named_config
 from orclib import Oracle
-from test_gpu_parity import run_phases, force_kpp_case, relerr, TOL_LOCAL, TOL_SOLVE
+from parity import run_phases, force_kpp_case
 
 pytestmark = pytest.mark.gpu
 
 DEL4 = {"hmix_momentum": 4, "hmix_tracer": 4, "lvariable_hmix": 1, "am": -1.0e22, "ah": -1.0e21}
-
-
-def block_masks(m):
-    """phys: the physical cells of every local block; near: cells with non-zero global indices whose eight neighbours have them too"""
-    nb, ny, nx = m.nblocks, m.nyb, m.nxb
-    phys = np.zeros((nb, ny, nx), dtype=bool)
-    cell = np.zeros((nb, ny, nx), dtype=bool)
-    short = 0
-    for lb, bid in enumerate(m.local_block_ids()):
-        blk = m.get_block(bid)
-        phys[lb, blk["jb"] - 1:blk["je"], blk["ib"] - 1:blk["ie"]] = True
-        cell[lb] = (blk["j_glob"] != 0)[:, None] & (blk["i_glob"] != 0)[None, :]
-        short += (blk["ie"] < nx - 2) or (blk["je"] < ny - 2)
-    near = cell.copy()
-    for dj in (-1, 0, 1):
-        for di in (-1, 0, 1):
-            sh = np.ones_like(cell)
-            js = slice(max(dj, 0), ny + min(dj, 0)); jd = slice(max(-dj, 0), ny + min(-dj, 0))
-            is_ = slice(max(di, 0), nx + min(di, 0)); id_ = slice(max(-di, 0), nx + min(-di, 0))
-            sh[:, jd, id_] = cell[:, js, is_]
-            near &= sh
-    return {"phys": phys, "near": near, "short": short}
 
 
 @pytest.mark.parametrize("name,kw,nsteps", [

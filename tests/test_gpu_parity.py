@@ -1,156 +1,14 @@
 """GPU parity (run on the MI355X box): every phase of the step_mod.F90 sequence through the C ABI
-against the CPU oracle on the same inputs.
-
-Tolerances (fp64):
-  * phases without a global reduction (tracer/momentum tendencies, Thomas solves, state, halos):
-    TOL_LOCAL = 1e-13 relative to the field's max -- both sides are compiled with
-    -ffp-contract=off in the reference's evaluation order, so only library-function rounding
-    (sqrt, division are correctly rounded; exp/atan differ by ulps) separates them;
-  * anything downstream of the barotropic solver: TOL_SOLVE = 1e-8, because the GPU sums dot
-    products in a fixed tree instead of the serial (j,i) order; the PCG iteration count must be
-    IDENTICAL (north_star: "PCG iteration count unchanged").
-"""
+against the CPU oracle on the same inputs (tests/parity.py; the two tolerances are explained in tests/common.py)."""
 import numpy as np
 import pytest
 
+from common import TOL_LOCAL, TOL_SOLVE, interior, relerr, tripole_expected
+from parity import force_kpp_case, run_phases
 from popcfg import named_config, synthetic_grid, synthetic_dzbc
 from orclib import Oracle
 
 pytestmark = pytest.mark.gpu
-TOL_LOCAL = 1e-13
-TOL_SOLVE = 1e-8
-
-
-def interior(a):
-    return a[..., 2:-2, 2:-2]
-
-
-def relerr(a, b):
-    d = np.abs(a - b).max()
-    s = np.abs(b).max()
-    return d / s if s > 0 else d
-
-
-def pick(gpu, a, inner):
-    """the cells a comparison looks at: the physical cells (inner) or every cell of the block arrays; with padded blocks (block
-    size not dividing the domain, tests/test_gpu_padded.py sets gpu.masks) the physical cells of each block, resp. the cells that
-    exist and whose neighbours exist (the padding holds nothing, and a ghost cell next to it is formed from it)"""
-    m = getattr(gpu, "masks", None)
-    if m is None:
-        return interior(a) if inner else a
-    sel = m["phys"] if inner else m["near"]
-    if a.ndim == 4:
-        sel = np.broadcast_to(sel[:, None], a.shape)
-    return a[sel]
-
-
-def check(gpu, orc, name, tol, tl=1, n=0, three_d=True, inner=True, what=""):
-    a = gpu.get(name, tl, n)
-    b = (orc.f3 if three_d else orc.f2)(name, tl, n)
-    a, b = pick(gpu, a, inner), pick(gpu, b, inner)
-    e = relerr(a, b)
-    assert e <= tol, "%s %s(tl=%d,n=%d): rel err %.3e > %.1e" % (what, name, tl, n, e, tol)
-    return e
-
-
-def run_phases(gpu, orc, step, tol_state, tidal_diag=False, levels_must_differ=False):
-    """one step, phase by phase.  tidal_diag: both models keep the tidal diagnostics (pop_tidal_nml.tidal_diag), compared after the
-    baroclinic driver; levels_must_differ: on a leapfrog step the old and current U and T must differ, so that the comparison tells a
-    kernel that reads curtime from one that reads mixtime (tests/test_gpu_schemes_oracle.py)"""
-    L = orc.L
-    gpu.time_manager(); L.orc_time_manager(orc.h)
-    assert gpu.dim("leapfrogts") == orc.dim("leapfrogts") and gpu.dim("avg_ts") == orc.dim("avg_ts")
-    if levels_must_differ and gpu.dim("leapfrogts"):
-        for name in ("UVEL", "TRACER"):
-            assert not np.array_equal(pick(gpu, gpu.get(name, 0), True), pick(gpu, gpu.get(name, 1), True)), "step %d: %s old = cur" % (step, name)
-            assert not np.array_equal(pick(gpu, orc.f3(name, 0), True), pick(gpu, orc.f3(name, 1), True)), "step %d: oracle %s old = cur" % (step, name)
-    gpu.dhdt(); L.orc_dhdt(orc.h)
-    w = "step %d dhdt" % step
-    check(gpu, orc, "DH", tol_state, three_d=False, inner=False, what=w)
-    check(gpu, orc, "DHU", tol_state, three_d=False, inner=False, what=w)
-    gpu.baroclinic_driver(); L.orc_baroclinic_driver(orc.h)
-    w = "step %d baroclinic_driver" % step
-    for n in (0, 1):
-        check(gpu, orc, "TRACER", tol_state, tl=2, n=n, what=w)
-    check(gpu, orc, "UVEL", tol_state, tl=2, what=w)
-    check(gpu, orc, "VVEL", tol_state, tl=2, what=w)
-    check(gpu, orc, "ZX", tol_state, three_d=False, what=w)
-    check(gpu, orc, "ZY", tol_state, three_d=False, what=w)
-    check(gpu, orc, "VVC", tol_state, what=w)
-    if gpu.cfg.vmix_choice == 3:
-        a, b = gpu.get("VDC", n=0), orc.vdc(0)
-        assert relerr(pick(gpu, a, True), pick(gpu, b, True)) <= tol_state * 10, "%s VDC(T): %g" % (w, relerr(pick(gpu, a, True), pick(gpu, b, True)))
-        a, b = gpu.get("VDC", n=1), orc.vdc(1)
-        assert relerr(pick(gpu, a, True), pick(gpu, b, True)) <= tol_state * 10, "%s VDC(S)" % w
-        check(gpu, orc, "HBLT", tol_state * 10, three_d=False, what=w)
-        for n in (0, 1):
-            check(gpu, orc, "KPP_SRC", tol_state * 100, n=n, what=w)
-    if gpu.cfg.hmix_momentum == 3:                           # anis: the friction clinic has just formed from the mixtime velocities
-        check(gpu, orc, "HDU", tol_state, what=w)
-        check(gpu, orc, "HDV", tol_state, what=w)
-    # the submesoscale and tidal fields are functions of KPP's output (HMXL; N^2 of the mixtime tracers next to VDC): VDC / HBLT's factor
-    if getattr(gpu.cfg, "lsubmesoscale_mixing", 0):          # needs submeso_diag = 1
-        check(gpu, orc, "SUBM_ML_DEPTH", tol_state * 10, three_d=False, what=w)
-        check(gpu, orc, "HLS_SUBM", tol_state * 10, three_d=False, what=w)
-        for n in (0, 1):
-            check(gpu, orc, "SUBM_ADV_TEND", tol_state * 10, n=n, what=w)
-    if tidal_diag:
-        for f in ("TIDAL_DIFF", "KVMIX", "KVMIX_M"):
-            check(gpu, orc, f, tol_state * 10, what=w)
-    gpu.barotropic_driver(); assert L.orc_barotropic_driver(orc.h) == 0
-    w = "step %d barotropic_driver" % step
-    it_g, rms_g = gpu.solver_diagnostics()
-    assert it_g == L.orc_solver_iterations(orc.h), "%s: PCG iterations %d vs oracle %d" % (w, it_g, L.orc_solver_iterations(orc.h))
-    check(gpu, orc, "RHS", max(tol_state, TOL_LOCAL * 10), three_d=False, inner=False, what=w)
-    for f in ("PSURF", "GRADPX", "GRADPY", "UBTROP", "VBTROP"):
-        check(gpu, orc, f, TOL_SOLVE, tl=2, three_d=False, inner=(f in ("UBTROP", "VBTROP")), what=w)
-    gpu.baroclinic_correct_adjust(); L.orc_baroclinic_correct_adjust(orc.h)
-    w = "step %d correct_adjust" % step
-    for n in (0, 1):
-        check(gpu, orc, "TRACER", TOL_SOLVE, tl=2, n=n, what=w)
-    check(gpu, orc, "RHO", TOL_SOLVE, tl=2, what=w)
-    gpu.step_tail(); L.orc_step_tail(orc.h)
-    w = "step %d tail" % step
-    for tl in (0, 1):
-        for n in (0, 1):
-            check(gpu, orc, "TRACER", TOL_SOLVE, tl=tl, n=n, inner=False, what=w)
-        for f in ("UVEL", "VVEL", "RHO"):
-            check(gpu, orc, f, TOL_SOLVE, tl=tl, inner=False, what=w)
-        for f in ("PSURF", "GRADPX", "GRADPY", "UBTROP", "VBTROP"):
-            check(gpu, orc, f, TOL_SOLVE, tl=tl, three_d=False, inner=False, what=w)
-    check(gpu, orc, "PGUESS", TOL_SOLVE, three_d=False, inner=False, what=w)
-    return it_g
-
-
-def force_kpp_case(gpu, orc):
-    """Surface buoyancy forcing + a weakly stratified upper ocean so the KPP boundary layer spans
-    several levels (bulk-Richardson interpolation, shape functions, non-local source all active)."""
-    tlat = orc.f2("TLAT")
-    stf_t = -3.0e-2 * np.sin(tlat) - 1.0e-2          # degC cm/s: cooling (unstable) in the north
-    stf_s = 2.0e-6 * np.cos(2.0 * tlat)
-    kmt = orc.i2("KMT")
-    for tl in (0, 1, 2):
-        for n, slope in ((0, 2.0e-4), (1, -2.0e-9)):
-            T = orc.f3("TRACER", tl, n)
-            z = np.arange(T.shape[1])[None, :, None, None]
-            mix = T[:, 0:1] - slope * z                   # nearly homogeneous upper ocean
-            shallow = (z < 8) & (z < kmt[:, None]) & (np.sin(3 * tlat)[:, None] > 0)
-            T[...] = np.where(shallow, mix, T)
-            gpu.set("TRACER", T, tl=tl, n=n)
-    orc.f2("STF", 1, 0)[...] = stf_t
-    orc.f2("STF", 1, 1)[...] = stf_s
-    gpu.set("STF", stf_t, n=0); gpu.set("STF", stf_s, n=1)
-    # densities of the modified state (init_ts computes RHO for cur and old)
-    import ctypes as C
-    for tl in (0, 1):
-        T, S, R = orc.f3("TRACER", tl, 0), orc.f3("TRACER", tl, 1), orc.f3("RHO", tl)
-        P = C.POINTER(C.c_double)
-        orc.L.orc_state.argtypes = [C.c_void_p, C.c_int, C.c_int, P, P, P, P, P, C.c_int]
-        for k in range(orc.km):
-            t = np.ascontiguousarray(T[:, k]); s_ = np.ascontiguousarray(S[:, k]); r = np.empty_like(t)
-            orc.L.orc_state(orc.h, k + 1, k + 1, t.ctypes.data_as(P), s_.ctypes.data_as(P), r.ctypes.data_as(P), None, None, t.size)
-            R[:, k] = r
-        gpu.set("RHO", R, tl=tl)
 
 
 @pytest.mark.parametrize("name,kw,nsteps", [
@@ -439,7 +297,6 @@ def test_halo_update_rule_on_device(pkg):
 def test_tripole_halo_on_device(pkg, loc, kind):
     """Device halo update on a tripole decomposition against the rule of test/unit/halo/POP.F90Tripole
     (2-D and 3-D fields); time stepping on such a decomposition is refused (no tripole grid)."""
-    from test_oracle_fixtures import _tripole_expected
     cfg = named_config("tiny", ns_boundary=2)
     m = pkg.PopModel(cfg)
     nx, ny, nb = cfg.nx_global, cfg.ny_global, m.nblocks
@@ -452,10 +309,10 @@ def test_tripole_halo_on_device(pkg, loc, kind):
         ig, jg = blk["i_glob"], blk["j_glob"]
         for j in range(2, m.nyb - 2):
             a2[b, j, 2:-2] = G[jg[j] - 1, ig[2:-2] - 1]
-        e2[b] = _tripole_expected(G, ig, jg, nx, ny, loc, kind)
+        e2[b] = tripole_expected(G, ig, jg, nx, ny, loc, kind)
         for k in range(m.km):
             a3[b, k, 2:-2, 2:-2] = a2[b, 2:-2, 2:-2] * (k + 1)
-            e3[b, k] = _tripole_expected(G * (k + 1), ig, jg, nx, ny, loc, kind)
+            e3[b, k] = tripole_expected(G * (k + 1), ig, jg, nx, ny, loc, kind)
     m.set("PSURF", a2, tl=2); m.halo_update_loc("PSURF", tl=2, loc=loc, kind=kind)
     assert np.array_equal(m.get("PSURF", tl=2), e2)
     m.set("UVEL", a3, tl=2); m.halo_update_loc("UVEL", tl=2, loc=loc, kind=kind)

@@ -14,16 +14,14 @@ Every case is the `tiny` configuration (48 x 40 in 16 blocks of 12 x 10), km = 1
 import numpy as np
 import pytest
 
+from common import TOL_LOCAL, TOL_SOLVE, interior
 from orclib import Oracle
+from parity import force_kpp_case
 from popcfg import named_config
-from passive_common import (IageEmulation, NoDevice, SECONDS_IN_YEAR, copy_state, passive_field, passive_fields, run_phases_nt, set_passive)
-from test_gpu_parity import TOL_LOCAL, TOL_SOLVE, force_kpp_case, interior
-from test_passive_host import closed_form_worst
+from passive_common import (DEL4, KPP, IageEmulation, NoDevice, SECONDS_IN_YEAR, closed_form_worst, copy_state, passive_field, passive_fields,
+                            run_phases_nt, set_passive)
 
 pytestmark = pytest.mark.gpu
-
-KPP = dict(vmix_choice=3, km=24)
-DEL4 = dict(hmix_tracer=4, ah=-1.0e21)
 
 
 def cfg_of(pkg, kw, **more):

@@ -21,11 +21,12 @@ Every comparison is np.array_equal over all cells, except the halo rule on padde
 import numpy as np
 import pytest
 
+import land_common
+from common import block_masks
 from orclib import AsModel, Oracle
 from popcfg import named_config, synthetic_grid
 from passive_common import (DEL4, KPP, TWINS, TWIN_IDS, TWIN_ROWS, assert_neighbour, assert_twin, make_salinity_twin,
                             passive_field, set_passive, twin_layout, twin_row, twin_start)
-from test_gpu_padded import block_masks
 
 pytestmark = pytest.mark.gpu
 NSTEPS = 5
@@ -128,7 +129,7 @@ def _b2_id(row):
 
 
 def _own_twins(m):
-    """The twin layout from the device model's own state, where no oracle is at hand.  With KPP first what test_gpu_parity.force_kpp_case
+    """The twin layout from the device model's own state, where no oracle is at hand.  With KPP first what parity.force_kpp_case
     does to an oracle: surface fluxes and a nearly homogeneous upper ocean (eight levels, where sin(3 TLAT) > 0), so that the boundary layer
     spans several levels and the non-local source is at work; the densities of the new state through pop_state_host."""
     if m.cfg.vmix_choice == 3:
@@ -205,17 +206,15 @@ def test_b2_kernel_forms_are_neutral_with_passive_tracers(pkg, orclib_built, row
 
 # ------------------------------------------------------------------ B3
 def _land_cases():
-    from test_gpu_land import CASES
-    return [CASES[0], CASES[2], CASES[-2]]
+    return [land_common.CASES[0], land_common.CASES[2], land_common.CASES[-2]]
 
 
 @pytest.mark.parametrize("pavg", [0, 1], ids=["all-tracer", "pavg"])
 @pytest.mark.parametrize("case", [0, 1, 2], ids=["kpp-del4-big", "two-blocks-upwind3-avg", "d2t-fuse-tracer-fwd"])
 def test_b3_land_elimination_is_invisible_with_passive_tracers(pkg, monkeypatch, case, pavg):
-    from test_gpu_land import _model
     name, kw, env, nsteps = _land_cases()[case]
     cfg = named_config(name, nt=5, lpressure_avg=pavg, **kw)
-    a, b = _model(pkg, monkeypatch, cfg, env, False), _model(pkg, monkeypatch, cfg, env, True)
+    a, b = land_common.model(pkg, monkeypatch, cfg, env, False), land_common.model(pkg, monkeypatch, cfg, env, True)
     assert b.scalar("land_tile_fraction") > 0.05, "the case has no land tiles"
     for m in (a, b):
         _own_twins(m)

@@ -6,8 +6,9 @@ import os
 
 import pytest
 
+from mr_launch import ROOT, run_check
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("nranks,kw,grid", [
@@ -21,7 +22,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     (2, "nt=4,ns_boundary=2", 1),                   # as the tripole row of tests/test_gpu_aniso.py: the caller-supplied grid, no wind
 ], ids=["2-default", "4-default", "2-kpp", "4-kpp", "2-nt5-del4", "2-nt5-gm-kpp", "2-nt5-lw_lim-robert", "2-nt4-tripole"])
 def test_ranks_equal_single_rank(nranks, kw, grid):
-    from test_gpu_multirank import _run_check
-    out = _run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_passive.py"),
+    out = run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_passive.py"),
                 "--config", "tiny", "--steps", "3", "--no-restart", "--grid", str(grid), "--kw", kw], 300)
     assert "no passive tracer was compared" not in out, out[-2000:]

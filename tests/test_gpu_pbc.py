@@ -5,9 +5,10 @@ column to column."""
 import numpy as np
 import pytest
 
+from common import TOL_LOCAL, TOL_SOLVE, relerr
 from popcfg import named_config, synthetic_grid, synthetic_dzbc
 from orclib import Oracle
-from test_gpu_parity import run_phases, force_kpp_case, relerr, TOL_LOCAL, TOL_SOLVE
+from parity import run_phases, force_kpp_case
 
 pytestmark = pytest.mark.gpu
 

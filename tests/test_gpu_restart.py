@@ -6,29 +6,15 @@ import numpy as np
 import pytest
 
 import restart_ref
+from common import STATE
 from popcfg import named_config, synthetic_grid
+from restart_ref import parse_hdr
 
 pytestmark = pytest.mark.gpu
 
 FIELDS_2D = ["UBTROP_CUR", "UBTROP_OLD", "VBTROP_CUR", "VBTROP_OLD", "PSURF_CUR", "PSURF_OLD", "GRADPX_CUR", "GRADPX_OLD",
              "GRADPY_CUR", "GRADPY_OLD", "PGUESS", "FW_OLD", "FW_FREEZE"]
 FIELDS_3D = ["UVEL_CUR", "UVEL_OLD", "VVEL_CUR", "VVEL_OLD", "TEMP_CUR", "SALT_CUR", "TEMP_OLD", "SALT_OLD"]
-STATE = [("TRACER", 0), ("TRACER", 1), ("UVEL", 0), ("VVEL", 0), ("RHO", 0), ("PSURF", 0), ("UBTROP", 0), ("VBTROP", 0),
-         ("GRADPX", 0), ("GRADPY", 0), ("PGUESS", 0)]
-
-
-def parse_hdr(path):
-    sec, cur = {}, None
-    for line in open(path + ".hdr"):
-        line = line.strip()
-        if line.startswith("&"):
-            cur = line[1:].strip(); sec[cur] = {}
-        elif line.startswith("/"):
-            cur = None
-        elif cur is not None and line.count(":") >= 2:
-            name, typ, val = line.split(":", 2)
-            sec[cur][name.strip()] = (typ.strip(), val.strip())
-    return sec
 
 
 @pytest.mark.parametrize("kw,n1,n2", [

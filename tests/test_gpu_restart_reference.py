@@ -9,9 +9,10 @@ import numpy as np
 import pytest
 
 import restart_ref as rr
+from common import STATE
 from ice_common import cold_start, ice_grid
 from popcfg import named_config
-from test_gpu_restart import STATE, parse_hdr
+from restart_ref import parse_hdr
 
 pytestmark = pytest.mark.gpu
 

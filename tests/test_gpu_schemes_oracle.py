@@ -1,5 +1,5 @@
 """Whole steps with the four newest schemes -- anisotropic viscosity, the submesoscale scheme, Jayne tidal mixing, the latitude-varying
-KPP background -- phase by phase against the CPU oracle (test_gpu_parity.run_phases), which restates them from the reference on its
+KPP background -- phase by phase against the CPU oracle (parity.run_phases), which restates them from the reference on its
 own (oracle/orc_aniso.inc, orc_submeso.inc, orc_tidal.inc).  From step 2 on the old and current time levels differ (asserted), so a
 kernel that reads curtime where the reference reads mixtime, a friction term added at the wrong step type, a background the look-ahead
 picks up a step late or a tendency that drifts once a day has ended shows here.  Solver iteration counts are identical to the
@@ -13,44 +13,18 @@ import numpy as np
 import pytest
 
 import cesm_case as cc
+from aniso_common import angle_grid
+from bckgrnd_common import banda_arctic_grid
 from bckgrnd_ref import CESM
-from orclib import Oracle
+from cesm_case import pair
+from common import TOL_LOCAL, TOL_SOLVE, physical, pick, relerr
+from orclib import AsModel
+from parity import check, run_phases
 from popcfg import named_config
-from test_bckgrnd_host import banda_arctic_grid
-from test_gpu_aniso import _angle_grid
-from test_gpu_padded import block_masks
-from test_gpu_parity import TOL_LOCAL, TOL_SOLVE, check, force_kpp_case, pick, relerr, run_phases
 
 pytestmark = pytest.mark.gpu
 
 KPP = dict(vmix_choice=3, bckgrnd_vdc1=0.16, km=24)
-
-
-def pair(pkg, cfg, grid=None, tuning=None, kpp=True, state=force_kpp_case, tidal=False, bck=False, tidal_first=True, tidal_diag=1, masks=False):
-    """the device model and the oracle with the same state (state(gpu, orc) with KPP), the same energy flux and the same init calls.
-    The flux amplitude is test_gpu_tidal.amplitude's, formed on the oracle's tracers from the NumPy restatement alone."""
-    gpu, orc = pkg.PopModel(cfg, grid=grid, tuning=tuning), Oracle(cfg, grid=grid)
-    if masks:
-        gpu.masks = block_masks(gpu)
-        assert gpu.masks["short"] > 0
-    for n in (0, 1):
-        assert np.array_equal(gpu.get("TRACER", 1, n), orc.f3("TRACER", 1, n))
-    if kpp:
-        state(gpu, orc)
-    nml = None
-
-    def init_tidal():
-        F1 = cc.smooth_flux(orc)
-        F = cc.flux_amplitude(orc, F1) * F1
-        gpu.init_tidal_mixing(F, tidal_diag=tidal_diag)
-        return orc.init_tidal_mixing(F, tidal_diag=tidal_diag)
-    if tidal and tidal_first:
-        nml = init_tidal()
-    if bck:
-        gpu.init_kpp_bckgrnd(**CESM); orc.init_kpp_bckgrnd(**CESM)
-    if tidal and not tidal_first:
-        nml = init_tidal()
-    return gpu, orc, nml
 
 
 def steps(gpu, orc, nsteps, nml=None, need=("neg", "cap", "stab")):
@@ -71,7 +45,7 @@ def test_aniso_east_variable_on_the_angle_grid(pkg, orclib_built):
     """case 1: avgfit, so step 2 averages"""
     c5 = named_config("tiny")
     cfg = pkg.anisotropic_config(c5, **cc.ANISO_EAST_VARIABLE)
-    gpu, orc, _ = pair(pkg, cfg, grid=_angle_grid(c5), kpp=False)
+    gpu, orc, _ = pair(pkg, cfg, grid=angle_grid(c5), kpp=False)
     assert np.abs(orc.f2("ANGLE")).max() > 0.1
     steps(gpu, orc, 5)
 
@@ -104,7 +78,7 @@ def test_kpp_varying_background_on_the_banda_arctic_grid(pkg, orclib_built):
     test_oracle_schemes.test_case4_state_is_stable_to_an_ulp_of_pow)"""
     cfg = named_config("tiny", **dict(KPP, ldbl_diff=1))
     gpu, orc, _ = pair(pkg, cfg, grid=banda_arctic_grid(cfg), state=cc.force_kpp_case_above_deep_water, bck=True)
-    b = orc.f2("BCKGRND_VDC")[cc.physical(orc) & (orc.i2("KMT") > 0)]
+    b = orc.f2("BCKGRND_VDC")[physical(AsModel(orc)) & (orc.i2("KMT") > 0)]
     assert (b == CESM["bckgrnd_vdc_ban"]).sum() >= 12 and len(np.unique(b)) > 10
     steps(gpu, orc, 5)
 
@@ -145,7 +119,7 @@ def test_all_on_padded_blocks(pkg, orclib_built):
 def test_all_on_tripole(pkg, orclib_built):
     """case 8b: the synthetic grid with a fold (and a non-zero ANGLE, which 'east' reads)"""
     cfg = all_on(ns_boundary=2)
-    gpu, orc, nml = pair(pkg, cfg, grid=_angle_grid(cfg), tuning={"kpp_ahead": 0}, tidal=True, bck=True)
+    gpu, orc, nml = pair(pkg, cfg, grid=angle_grid(cfg), tuning={"kpp_ahead": 0}, tidal=True, bck=True)
     steps(gpu, orc, 4, nml)
 
 

@@ -7,31 +7,12 @@ import numpy as np
 import pytest
 
 import submeso_ref
+from common import TOL_LOCAL, physical
+from mr_launch import ROOT, run_check
 from popcfg import named_config, synthetic_grid
-from test_gpu_parity import TOL_LOCAL
-from test_submeso_host import CLOSED_FORM_ULPS, closed_form, linear_state, open_ocean
+from submeso_common import CASES, CLOSED_FORM_ULPS, GM, KPP, branches, closed_form, field, linear_state, open_ocean
 
 pytestmark = pytest.mark.gpu
-
-GM = dict(hmix_tracer=3)
-KPP = dict(hmix_tracer=3, vmix_choice=3)
-
-
-def field(m, hx, dtz, noise, front=0.0):
-    """T, S of the local blocks as functions of the global indices (so ghost cells agree with their source cells): a large-scale
-    pattern of amplitude hx [K], a decrease of dtz [K] per level, cell-to-cell variation of amplitude noise, and a step of `front` K
-    across the middle longitude"""
-    T = np.zeros((m.nblocks, m.km, m.nyb, m.nxb)); S = np.zeros_like(T)
-    nx, ny = m.cfg.nx_global, m.cfg.ny_global
-    k = np.arange(1, m.km + 1, dtype=np.float64)[:, None, None]
-    for lb, bid in enumerate(m.local_block_ids()):
-        b = m.get_block(bid)
-        i = np.asarray(b["i_glob"], dtype=np.float64)[None, None, :]
-        j = np.asarray(b["j_glob"], dtype=np.float64)[None, :, None]
-        wig = np.sin(12.9898 * i + 78.233 * j + 37.719 * k) * np.cos(4.1 * i - 2.3 * j)
-        T[lb] = 18.0 - dtz * k + hx * np.cos(2.0 * np.pi * i / nx) * np.cos(np.pi * j / ny) + noise * wig + front * (i > nx / 2)
-        S[lb] = 0.035 + 1.0e-4 * hx * np.sin(2.0 * np.pi * i / nx + 0.3 * j) + 2.0e-5 * k * min(dtz, 1.0)
-    return T, S
 
 
 def run(pkg, cfg, state=(2.0, 0.3, 0.2), grid=None, tuning=None, TS=None):
@@ -48,14 +29,6 @@ def run(pkg, cfg, state=(2.0, 0.3, 0.2), grid=None, tuning=None, TS=None):
     return m, m.get("TRACER", 1, 0), m.get("TRACER", 1, 1)
 
 
-def physical(m):
-    mask = np.zeros((m.nblocks, m.nyb, m.nxb), dtype=bool)
-    for lb, bid in enumerate(m.local_block_ids()):
-        b = m.get_block(bid)
-        mask[lb, b["jb"] - 1:b["je"], b["ib"] - 1:b["ie"]] = True
-    return mask
-
-
 def compare(m, r, phys):
     """SUBM_ML_DEPTH, HLS_SUBM, SUBM_ADV_TEND n = 0, 1 on every physical cell, relative to the field's maximum"""
     p3 = np.broadcast_to(phys[:, None], (m.nblocks, m.km, m.nyb, m.nxb))
@@ -68,28 +41,6 @@ def compare(m, r, phys):
         err = np.abs(a - b).max() / s
         print("%s: max |device - restatement| / max |restatement| = %.3e" % (name, err))
         assert err <= TOL_LOCAL, name
-
-
-def branches(r, phys):
-    """how many physical ocean columns take each branch of HLS = max(WORK1, WORK2, hor_length_scale)"""
-    sel = phys & (r["KMT"] > 0)
-    w1, w2, h = r["WORK1"][sel], r["WORK2"][sel], r["HLS"][sel]
-    return {"work1": int(((w1 == h) & (w1 > w2)).sum()), "work2": int(((w2 == h) & (w2 >= w1)).sum()),
-            "floor": int(((h > w1) & (h > w2)).sum())}
-
-
-# (id, pop_config keywords, submeso keywords, state, grid from pop_create_with_grid, branch of the max that must be taken on > 20 columns)
-CASES = [
-    ("const-vmix", GM, {}, (2.0, 0.3, 0.2), False, None),
-    ("kpp", KPP, {}, (2.0, 0.3, 0.2), False, None),
-    ("kpp-stepped", dict(KPP, stepped_bathymetry=1), {}, (2.0, 0.3, 0.2), False, None),
-    ("const-length-scale", KPP, dict(luse_const_horiz_len_scale=1, hor_length_scale=2.0e5), (2.0, 0.3, 0.2), False, None),
-    ("padded-blocks", dict(KPP, block_size_x=20, block_size_y=16), {}, (2.0, 0.3, 0.2), False, None),
-    ("tripole", dict(KPP, ns_boundary=2, block_size_x=48, block_size_y=10), {}, (2.0, 0.3, 0.2), True, None),
-    ("front-work1", GM, dict(time_scale_constant=3.456e5), (8.0, 0.0, 3.0), False, "work1"),
-    ("stratified-work2", GM, {}, (0.1, 2.0, 0.0), False, "work2"),
-    ("weak-floor", GM, {}, (1.0e-3, 1.0e-4, 0.0), False, "floor"),
-]
 
 
 @pytest.mark.parametrize("name,kw5,kw7,state,with_grid,branch", CASES, ids=[c[0] for c in CASES])
@@ -283,10 +234,8 @@ def test_restart_is_exact(pkg, tmp_path):
 
 @pytest.mark.parametrize("nranks,kw,grid", [(2, "", 0), (3, "block_size_x=20,block_size_y=16", 0), (2, "ns_boundary=2", 1)])
 def test_multirank_equals_single_rank(nranks, kw, grid):
-    from test_gpu_multirank import _run_check
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     base = "hmix_tracer=3,vmix_choice=3"
-    _run_check(["--nproc-per-node", str(nranks), os.path.join(root, "tests", "mr_gpu_submeso.py"), "--submeso", "time_scale_constant=8.64e4",
+    run_check(["--nproc-per-node", str(nranks), os.path.join(ROOT, "tests", "mr_gpu_submeso.py"), "--submeso", "time_scale_constant=8.64e4",
                 "--config", "tiny", "--steps", "3", "--grid", str(grid), "--kw", base + ("," + kw if kw else "")], 300)
 
 

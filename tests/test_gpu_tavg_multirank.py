@@ -5,11 +5,11 @@ import os
 
 import pytest
 
+from mr_launch import ROOT, run_check
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_two_ranks_equal_single_rank():
-    from test_gpu_multirank import _run_check
-    _run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_tavg.py"), "--config", "tiny", "--steps", "3",
-                "--kw", "vmix_choice=3,km=24"], 300)
+    run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_tavg.py"), "--config", "tiny", "--steps", "3",
+               "--kw", "vmix_choice=3,km=24"], 300)

@@ -7,56 +7,15 @@ import numpy as np
 import pytest
 
 import tidal_ref
+from bckgrnd_common import feed_oracle
+from common import TOL_LOCAL, TOL_SOLVE, physical, relerr
+from mr_launch import ROOT, run_check
 from orclib import Oracle
 from popcfg import named_config, synthetic_grid
-from test_gpu_parity import TOL_LOCAL, TOL_SOLVE, relerr
-from test_gpu_submeso import field, physical
-from test_tidal_host import BOXES, smooth_flux, stepped_grid
+from submeso_common import field
+from tidal_common import CASES, KPP, NOISY, amplitude, branches, set_state, stepped_grid, unit_flux
 
 pytestmark = pytest.mark.gpu
-
-KPP = dict(vmix_choice=3, bckgrnd_vdc1=0.16)
-NOISY = (2.0, 0.3, 0.2)
-
-
-def noisy_state(m, state=NOISY, vert=0.25):
-    """field() of the submeso tests plus a temperature term that changes from level to level: the cell-to-cell variation of field()
-    advances by 37.719 = 6 * 2 pi + 0.02 radians per level, so on its own it leaves every interface stably stratified.  With 0.3 K per
-    level and +-0.25 K of this term about a fifth of the interfaces are unstable (the tests assert that both signs of N2 occur)."""
-    T, S = field(m, *state)
-    k = np.arange(1, m.km + 1, dtype=np.float64)[:, None, None]
-    for lb, bid in enumerate(m.local_block_ids()):
-        b = m.get_block(bid)
-        i = np.asarray(b["i_glob"], dtype=np.float64)[None, None, :]
-        j = np.asarray(b["j_glob"], dtype=np.float64)[None, :, None]
-        T[lb] += vert * np.sin(1.7 * k + 0.9 * i + 1.3 * j)
-    return T, S
-
-
-def set_state(m, state=NOISY):
-    """the tracers at both time levels, ghost cells from the halo update; returns what the model holds"""
-    T, S = noisy_state(m, state)
-    for tl in (0, 1):
-        m.set("TRACER", T, tl, 0); m.set("TRACER", S, tl, 1)
-        m.halo_update("TRACER", tl, 0); m.halo_update("TRACER", tl, 1)
-    return m.get("TRACER", 1, 0), m.get("TRACER", 1, 1)
-
-
-def unit_flux(m):
-    F = smooth_flux(m, 1.0)
-    m.halo_update_host_loc(F)          # what pop_init_tidal_mixing does to its copy of the record
-    return F
-
-
-def amplitude(pkg, m, cfg, F1, T, S):
-    """the flux amplitude [W/m^2] of a case, from the restatement alone: TIDAL_DIFF is linear in the flux until it is limited, so with
-    the amplitude tidal_mix_max / (median of the unit-flux TIDAL_DIFF over the stably stratified cells of the four levels above
-    the bottom) about half of those cells reach the cap and half stay below it"""
-    r = tidal_ref.from_model(m, cfg, pkg.tidal_nml(ltidal_max=0, ltidal_stabc=0), F1, T, S)
-    lev = np.arange(1, m.km + 1)[None, :, None, None]
-    kmt = r["KMT"][:, None]
-    sel = (lev < kmt) & (lev >= kmt - 4) & (r["N2"] > 0.0)
-    return 100.0 / np.median(r["DIFF"][sel])
 
 
 def run(pkg, cfg, grid=None, tuning=None, state=NOISY, amp=None, regions=None, **nml_kw):
@@ -84,26 +43,6 @@ def compare(m, r, phys):
         err = np.abs(a - b).max() / s
         print("%s: max |device - restatement| / max |restatement| = %.3e" % (name, err))
         assert err <= TOL_LOCAL, name
-
-
-def branches(r, phys):
-    p3 = np.broadcast_to(phys[:, None], r["N2"].shape)
-    return {n: int((b & p3).sum()) for n, b in r["branch"].items()}
-
-
-# (id, pop_config keywords, tidal_nml keywords, regions, grid: None | 'stepped' | 'synthetic', branches that must be taken on > 20 cells)
-CASES = [
-    ("default", {}, {}, None, None, ("neg", "cap", "stab")),
-    ("stepped-kmt", {}, {}, None, "stepped", ("neg", "cap", "stab")),
-    ("no-max", {}, dict(ltidal_max=0), None, None, ("neg", "cap")),
-    ("no-stabc", {}, dict(ltidal_stabc=0), None, None, ("neg", "cap", "stab-off")),
-    ("regions", dict(stepped_bathymetry=1), {}, BOXES, None, ("neg", "region")),
-    ("partial-bottom-cells", dict(partial_bottom_cells=1, stepped_bathymetry=1), {}, None, None, ("neg", "cap", "stab")),
-    ("padded-blocks", dict(block_size_x=20, block_size_y=16), {}, None, None, ("neg", "cap", "stab")),
-    ("tripole", dict(ns_boundary=2, block_size_x=48, block_size_y=10), {}, None, "synthetic", ("neg", "cap", "stab")),
-    ("no-rich", dict(lrich=0), {}, None, None, ("neg", "cap", "stab")),
-    ("dbl-diff", dict(ldbl_diff=1), {}, None, None, ("neg", "cap", "stab")),
-]
 
 
 @pytest.mark.parametrize("name,kw5,kwn,regions,gridkind,need", CASES, ids=[c[0] for c in CASES])
@@ -166,20 +105,11 @@ def test_below_the_boundary_layer(pkg):
 
 
 def _feed(gpu, orc, T, S):
-    """the same tracers at every time level of both models and the densities that belong to them (test_gpu_parity.force_kpp_case)"""
-    import ctypes as C
-    P = C.POINTER(C.c_double)
-    orc.L.orc_state.argtypes = [C.c_void_p, C.c_int, C.c_int, P, P, P, P, P, C.c_int]
+    """the same tracers at every time level of both models and the densities that belong to them (parity.force_kpp_case)"""
+    R = feed_oracle(orc, T, S)
     for tl in (0, 1, 2):
-        for n, X in ((0, T), (1, S)):
-            orc.f3("TRACER", tl, n)[...] = X
-            gpu.set("TRACER", X, tl=tl, n=n)
+        gpu.set("TRACER", T, tl=tl, n=0); gpu.set("TRACER", S, tl=tl, n=1)
     for tl in (0, 1):
-        R = orc.f3("RHO", tl)
-        for k in range(orc.km):
-            t = np.ascontiguousarray(T[:, k]); s_ = np.ascontiguousarray(S[:, k]); r = np.empty_like(t)
-            orc.L.orc_state(orc.h, k + 1, k + 1, t.ctypes.data_as(P), s_.ctypes.data_as(P), r.ctypes.data_as(P), None, None, t.size)
-            R[:, k] = r
         gpu.set("RHO", R, tl=tl)
 
 
@@ -313,7 +243,5 @@ def test_zero_flux_changes_nothing(pkg):
 
 
 def test_two_ranks_equal_single_rank():
-    from test_gpu_multirank import _run_check
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    _run_check(["--nproc-per-node", "2", os.path.join(root, "tests", "mr_gpu_tidal.py"), "--tidal", "amp=1.0e3",
+    run_check(["--nproc-per-node", "2", os.path.join(ROOT, "tests", "mr_gpu_tidal.py"), "--tidal", "amp=1.0e3",
                 "--config", "tiny", "--steps", "2", "--no-restart", "--kw", "vmix_choice=3,bckgrnd_vdc1=0.16,stepped_bathymetry=1"], 300)

@@ -1,29 +1,27 @@
 """The CPU oracle's restatements of the newest schemes (oracle/orc_tidal.inc, orc_aniso.inc, orc_submeso.inc) against the NumPy
 restatements the device's phase tests use (tests/tidal_ref.py, bckgrnd_ref.py, aniso_ref.py, submeso_ref.py): the same cases, the
-same states, every physical cell, relative to the field's maximum, at TOL_LOCAL.  No GPU: the helpers of the device tests are fed
-through orclib.AsModel, which serves them from an Oracle what they ask of a device model."""
+same states, every physical cell, relative to the field's maximum, at TOL_LOCAL.  No GPU: the helpers the device tests take from
+aniso_common, submeso_common, tidal_common and bckgrnd_common are fed through orclib.AsModel, which serves them from an Oracle what they
+ask of a device model."""
 import numpy as np
 import pytest
 
+import aniso_common
 import aniso_ref
+import bckgrnd_common
 import bckgrnd_ref
 import orclib
+import submeso_common
 import submeso_ref
+import tidal_common
 import tidal_ref
+from bckgrnd_common import banda_arctic_grid
 from bckgrnd_ref import CESM
+from common import TOL_LOCAL, physical
 from orclib import AsModel, Oracle
+from parity import force_kpp_case
 from popcfg import named_config, synthetic_dzbc, synthetic_grid
-from test_bckgrnd_host import banda_arctic_grid
-from test_gpu_parity import TOL_LOCAL
-from test_tidal_host import stepped_grid
-import test_gpu_aniso as dev_aniso
-import test_gpu_bckgrnd as dev_bck
-import test_gpu_submeso as dev_sub
-import test_gpu_tidal as dev_tidal
-
-
-def physical(m):
-    return dev_tidal.physical(m)
+from tidal_common import stepped_grid
 
 
 def relmax(a, b, sel):
@@ -98,9 +96,9 @@ def test_omitted_options_are_refused_with_a_message(pkg, orclib_built):
         o.close()
 
 
-# ------------------------------------------------------------------ anisotropic viscosity: CASES of tests/test_gpu_aniso.py
+# ------------------------------------------------------------------ anisotropic viscosity: CASES of tests/aniso_common.py
 
-ANISO_CASES = [c for c in dev_aniso.CASES if not c[3].get("lsmag_aniso")]      # the Smagorinsky viscosities are not restated in the oracle
+ANISO_CASES = [c for c in aniso_common.CASES if not c[3].get("lsmag_aniso")]      # the Smagorinsky viscosities are not restated in the oracle
 
 
 @pytest.mark.parametrize("name,cname,kw5,kw6,angle", ANISO_CASES, ids=[c[0] for c in ANISO_CASES])
@@ -108,19 +106,19 @@ def test_aniso_matches_restatement(pkg, orclib_built, name, cname, kw5, kw6, ang
     """the init-time fields (geometry, AMAX_CFL, F_PARA, F_PERP) and the friction HDU, HDV of one clinic on the random velocities of
     the device's phase test"""
     c5 = named_config(cname, **kw5)
-    grid = dev_aniso._angle_grid(c5) if angle else None
+    grid = aniso_common.angle_grid(c5) if angle else None
     if grid is not None and c5.partial_bottom_cells:
         grid["DZBC"] = synthetic_dzbc(c5, grid["KMT"])
     cfg = pkg.anisotropic_config(c5, **kw6)
     m = AsModel(Oracle(cfg, grid=grid))
-    U, V = dev_aniso._state(m, 5)
+    U, V = aniso_common.state(m, 5)
     m.time_manager()
     m.run_phase("hmix_momentum")
     phys = physical(m)
     p3 = np.broadcast_to(phys[:, None], U.shape)
     g = aniso_ref.geometry(m.get("HTN"), m.get("HTE"), m.get("DXUR"), m.get("DYUR"), m.scalar("dtu"))
     for n, want in g.items():
-        a = m.get(n)      # K1E, K1W vanish on a lat-lon grid: compared absolutely there, as test_gpu_parity.relerr does
+        a = m.get(n)      # K1E, K1W vanish on a lat-lon grid: compared absolutely there, as common.relerr does
         err = relmax(a, want, phys) if np.abs(want[phys]).max() > 0 else np.abs(a - want)[phys].max()
         assert err <= TOL_LOCAL, (n, err)
     if cfg.lvariable_hmix_aniso:
@@ -129,7 +127,7 @@ def test_aniso_matches_restatement(pkg, orclib_built, name, cname, kw5, kw6, ang
             err = relmax(m.get(n), want, p3)
             print("%s %s: max |oracle - restatement| / max |restatement| = %.3e" % (name, n, err))
             assert err <= TOL_LOCAL, n
-    ru, rv = dev_aniso._reference(m, cfg, U, V)
+    ru, rv = aniso_common.reference(m, cfg, U, V)
     for n, want in (("HDU", ru), ("HDV", rv)):
         a = m.get(n)
         assert np.isfinite(a).all(), n
@@ -139,15 +137,15 @@ def test_aniso_matches_restatement(pkg, orclib_built, name, cname, kw5, kw6, ang
     m.close()
 
 
-# ------------------------------------------------------------------ the submesoscale scheme: CASES of tests/test_gpu_submeso.py
+# ------------------------------------------------------------------ the submesoscale scheme: CASES of tests/submeso_common.py
 
-@pytest.mark.parametrize("name,kw5,kw7,state,with_grid,branch", dev_sub.CASES, ids=[c[0] for c in dev_sub.CASES])
+@pytest.mark.parametrize("name,kw5,kw7,state,with_grid,branch", submeso_common.CASES, ids=[c[0] for c in submeso_common.CASES])
 def test_submeso_matches_restatement(pkg, orclib_built, name, kw5, kw7, state, with_grid, branch):
     c5 = named_config("tiny", **kw5)
     grid = synthetic_grid(c5) if with_grid else None
     cfg = pkg.submeso_config(c5, submeso_diag=1, **kw7)
     m = AsModel(Oracle(cfg, grid=grid))
-    T, S = dev_sub.field(m, *state)
+    T, S = submeso_common.field(m, *state)
     for tl in (0, 1):
         m.set("TRACER", T, tl, 0); m.set("TRACER", S, tl, 1)
         m.halo_update("TRACER", tl, 0); m.halo_update("TRACER", tl, 1)
@@ -156,7 +154,7 @@ def test_submeso_matches_restatement(pkg, orclib_built, name, kw5, kw7, state, w
     T, S = m.get("TRACER", 1, 0), m.get("TRACER", 1, 1)
     r = submeso_ref.from_model(m, cfg, T, S)
     phys = physical(m)
-    nb = dev_sub.branches(r, phys)
+    nb = submeso_common.branches(r, phys)
     print(name, "branches of the max:", nb)
     if branch:
         assert nb[branch] > 20, nb
@@ -171,14 +169,14 @@ def test_submeso_matches_restatement(pkg, orclib_built, name, kw5, kw7, state, w
     m.close()
 
 
-# ------------------------------------------------------------------ tidal mixing: CASES of tests/test_gpu_tidal.py
+# ------------------------------------------------------------------ tidal mixing: CASES of tests/tidal_common.py
 
 def tidal_run(cfg, grid=None, **nml_kw):
     """test_gpu_tidal.run on the oracle: state, flux amplitude (from the restatement alone), init, one evaluation of the coefficients"""
     m = AsModel(Oracle(cfg, grid=grid))
-    T, S = dev_tidal.set_state(m)
-    F1 = dev_tidal.unit_flux(m)
-    amp = dev_tidal.amplitude(orclib, m, cfg, F1, T, S)      # orclib.tidal_nml stands in for the package's
+    T, S = tidal_common.set_state(m)
+    F1 = tidal_common.unit_flux(m)
+    amp = tidal_common.amplitude(orclib, m, cfg, F1, T, S)      # orclib.tidal_nml stands in for the package's
     F = amp * F1
     nml = m.orc.init_tidal_mixing(F, **dict(dict(tidal_diag=1), **nml_kw))
     m.time_manager()
@@ -186,20 +184,20 @@ def tidal_run(cfg, grid=None, **nml_kw):
     return m, nml, F, T, S, amp
 
 
-TIDAL_CASES = [c for c in dev_tidal.CASES if c[3] is None]      # ltidal_min_regions is not restated in the oracle: the 'regions' row stays NumPy-only
+TIDAL_CASES = [c for c in tidal_common.CASES if c[3] is None]      # ltidal_min_regions is not restated in the oracle: the 'regions' row stays NumPy-only
 
 
 @pytest.mark.parametrize("name,kw5,kwn,regions,gridkind,need", TIDAL_CASES, ids=[c[0] for c in TIDAL_CASES])
 def test_tidal_matches_restatement(orclib_built, name, kw5, kwn, regions, gridkind, need):
-    cfg = named_config("tiny", **dict(dev_tidal.KPP, **kw5))
+    cfg = named_config("tiny", **dict(tidal_common.KPP, **kw5))
     grid = stepped_grid(cfg) if gridkind == "stepped" else synthetic_grid(cfg) if gridkind == "synthetic" else None
     m, nml, F, T, S, amp = tidal_run(cfg, grid=grid, **kwn)
     r = tidal_ref.from_model(m, cfg, nml, F, T, S)
     phys = physical(m)
-    nb = dev_tidal.branches(r, phys)
+    nb = tidal_common.branches(r, phys)
     if "stab-off" in need:
         on = tidal_ref.from_model(m, cfg, orclib.tidal_nml(tidal_diag=1), F, T, S)
-        nb["stab-off"] = dev_tidal.branches(on, phys)["stab"]
+        nb["stab-off"] = tidal_common.branches(on, phys)["stab"]
         assert nb["stab"] == 0
     print(name, "flux amplitude %.3e W/m^2, branches:" % amp, nb)
     for b in need:
@@ -215,30 +213,30 @@ def test_tidal_matches_restatement(orclib_built, name, kw5, kwn, regions, gridki
     m.close()
 
 
-# ------------------------------------------------------------------ the varying background: ORACLE_CASES and test_with_tidal_mixing of tests/test_gpu_bckgrnd.py
+# ------------------------------------------------------------------ the varying background: ORACLE_CASES of tests/bckgrnd_common.py and test_with_tidal_mixing of tests/test_gpu_bckgrnd.py
 
 def _first_rows(m):
     return [(b["jb"] - 1 if b["j_glob"][b["jb"] - 1] == 1 else None) for b in (m.get_block(i) for i in m.local_block_ids())]
 
 
-@pytest.mark.parametrize("name,kw5,own_grid", dev_bck.ORACLE_CASES, ids=[c[0] for c in dev_bck.ORACLE_CASES])
+@pytest.mark.parametrize("name,kw5,own_grid", bckgrnd_common.ORACLE_CASES, ids=[c[0] for c in bckgrnd_common.ORACLE_CASES])
 def test_bckgrnd_matches_restatement(orclib_built, name, kw5, own_grid):
     """BCKGRND_VDC / BCKGRND_VVC and TLON against tests/bckgrnd_ref.py; then, as test_gpu_bckgrnd.test_rows_match_oracle does for the
     device, the coefficients of the varying run against runs with the uniform bckgrnd_vdc1 = v on the columns where the field is v
     (bit for bit here: both sides are this library, the varying field only changes which number is added)"""
-    cfg = named_config("tiny", **dict(dev_bck.KPP, **kw5))
+    cfg = named_config("tiny", **dict(tidal_common.KPP, **kw5))
     grid = banda_arctic_grid(cfg) if own_grid else None
     m = AsModel(Oracle(cfg, grid=grid))
-    T, S = dev_tidal.noisy_state(m)
+    T, S = tidal_common.noisy_state(m)
     for k in range(m.km):
         for X in (T, S):
             x = np.ascontiguousarray(X[:, k]); m.halo_update_host_loc(x); X[:, k] = x
-    dev_bck._feed_oracle(m.orc, T, S)
+    bckgrnd_common.feed_oracle(m.orc, T, S)
     m.orc.init_kpp_bckgrnd(**CESM)
     m.time_manager(); m.run_phase("vmix")
     phys = physical(m)
     ocean = phys & (m.geti("KMT") > 0)
-    ref, masks = dev_bck.restated(m, cfg)
+    ref, masks = bckgrnd_common.restated(m, cfg)
     tl = bckgrnd_ref.tlon(m.get("ULAT"), m.get("ULON"), _first_rows(m))
     for fname, a, b in (("TLON", m.get("TLON"), tl), ("BCKGRND_VDC", m.get("BCKGRND_VDC"), ref), ("BCKGRND_VVC", m.get("BCKGRND_VVC"), cfg.Prandtl * ref)):
         err = relmax(a, b, phys)
@@ -253,8 +251,8 @@ def test_bckgrnd_matches_restatement(orclib_built, name, kw5, own_grid):
     assert got["VDC0"].max() > 1.0 or kw5.get("lrich") == 0
     seen = np.zeros(ocean.shape, dtype=bool)
     for v in values[::max(1, len(values) // 6)]:      # a sixth of the rows: the identity is the same statement on each
-        orc = Oracle(named_config("tiny", **dict(dev_bck.KPP, **dict(kw5, bckgrnd_vdc1=float(v)))), grid=grid)
-        dev_bck._feed_oracle(orc, T, S)
+        orc = Oracle(named_config("tiny", **dict(tidal_common.KPP, **dict(kw5, bckgrnd_vdc1=float(v)))), grid=grid)
+        bckgrnd_common.feed_oracle(orc, T, S)
         orc.L.orc_time_manager(orc.h); orc.run_phase("tracer_rhs")
         want = {"VDC0": orc.vdc(0), "VDC1": orc.vdc(1), "SRC0": orc.f3("KPP_SRC", 1, 0), "HBLT": orc.f2("HBLT")}
         sel = ocean & (field == v)
@@ -270,26 +268,26 @@ def test_bckgrnd_matches_restatement(orclib_built, name, kw5, own_grid):
 def test_bckgrnd_with_tidal_mixing(orclib_built):
     """test_gpu_bckgrnd.test_with_tidal_mixing on the oracle: KVMIX = min(b + TIDAL_DIFF, tidal_mix_max), KVMIX_M = Prandtl
     min((Prandtl b) / Prandtl + TIDAL_DIFF, tidal_mix_max); both orders of the two init calls give the same bits"""
-    cfg = named_config("tiny", **dev_bck.STEPPED)
+    cfg = named_config("tiny", **bckgrnd_common.STEPPED)
     out = []
     for tidal_first in (False, True):
         m = AsModel(Oracle(cfg))
-        T, S = dev_tidal.set_state(m)
-        dev_bck.set_flux(m)
-        F1 = dev_tidal.unit_flux(m)
-        amp = dev_tidal.amplitude(orclib, m, cfg, F1, T, S)
+        T, S = tidal_common.set_state(m)
+        bckgrnd_common.set_flux(m)
+        F1 = tidal_common.unit_flux(m)
+        amp = tidal_common.amplitude(orclib, m, cfg, F1, T, S)
         if tidal_first:
             nml = m.orc.init_tidal_mixing(amp * F1, tidal_diag=1)
         m.orc.init_kpp_bckgrnd(**CESM)
         if not tidal_first:
             nml = m.orc.init_tidal_mixing(amp * F1, tidal_diag=1)
         m.time_manager(); m.run_phase("vmix")
-        out.append({n: m.get(*a) for n, a in dev_bck.FIELDS + tuple((n, (n,)) for n in ("TIDAL_DIFF", "KVMIX", "KVMIX_M"))})
+        out.append({n: m.get(*a) for n, a in bckgrnd_common.FIELDS + tuple((n, (n,)) for n in ("TIDAL_DIFF", "KVMIX", "KVMIX_M"))})
         if tidal_first:
             m.close()
             continue
         r = tidal_ref.from_model(m, cfg, nml, amp * F1, T, S)
-        b, _ = dev_bck.restated(m, cfg)
+        b, _ = bckgrnd_common.restated(m, cfg)
         b = b[:, None]
         Pr, mx = cfg.Prandtl, nml.tidal_mix_max
         wet = (np.arange(1, m.km + 1)[None, :, None, None] < r["KMT"][:, None]) & physical(m)[:, None]
@@ -316,7 +314,7 @@ class _NoDevice:
 
 def test_case4_state_is_stable_to_an_ulp_of_pow(orclib_built, tmp_path):
     """The device and the oracle evaluate the same expressions in the same order; what separates them before the first solve is the
-    rounding of the math library (TOL_LOCAL's premise, tests/test_gpu_parity.py).  A state can serve a comparison at TOL_LOCAL only if
+    rounding of the math library (TOL_LOCAL's premise, tests/common.py).  A state can serve a comparison at TOL_LOCAL only if
     the oracle itself moves by much less than that when a library function returns the neighbouring double.  Measured here without a
     device: the first baroclinic driver of case 4 by the oracle and by a second build of it whose pow is off by one ulp in half of its
     calls (tests/pow_ulp.h).  force_kpp_case on the Banda / Arctic grid: HBLT 5.8e-13, VDC 8.1e-13, VVC 4.0e-13, TRACER 2.0e-13, UVEL
@@ -326,7 +324,6 @@ def test_case4_state_is_stable_to_an_ulp_of_pow(orclib_built, tmp_path):
     import os
     import subprocess
     import cesm_case as cc
-    from test_gpu_parity import force_kpp_case
     src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "pop_oracle.c")
     lib = str(tmp_path / "libpop_oracle_pow_ulp.so")
     subprocess.check_call(["gcc", "-O2", "-fPIC", "-std=c11", "-ffp-contract=off", "-fno-fast-math", "-fno-builtin-sin", "-fno-builtin-cos", "-D_GNU_SOURCE",

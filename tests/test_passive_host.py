@@ -9,10 +9,12 @@ test the yardstick itself:
 import numpy as np
 import pytest
 
-from orclib import Oracle
+from common import physical
+from orclib import AsModel, Oracle
+from parity import force_kpp_case
 from popcfg import named_config
-from passive_common import (IageEmulation, NoDevice, SCHEMES, TWINS, WITHOUT_LAST_PART, TWIN_IDS, TWIN_ROWS, age_closed_form, assert_neighbour,
-                            assert_twin, passive_field, passive_fields, set_passive, twin_row, twin_start)
+from passive_common import (IageEmulation, NoDevice, SCHEMES, TWINS, WITHOUT_LAST_PART, TWIN_IDS, TWIN_ROWS, assert_neighbour, assert_twin,
+                            closed_form_worst, passive_field, passive_fields, set_passive, twin_row, twin_start)
 
 
 def test_init_iage_on_a_host_only_context(pkg):
@@ -60,7 +62,6 @@ EXP1 = [
 
 
 def _kpp_state(orc):
-    from test_gpu_parity import force_kpp_case
     force_kpp_case(NoDevice(), orc)
     stf = 1.0e-2 * np.cos(orc.f2("TLAT"))
     for n in range(2, orc.nt):
@@ -124,8 +125,6 @@ _S_WITHOUT = {}
 def _twin_oracle_run(pkg, topology, scheme, nt, without_scheme, tidal_off=False):
     """five steps of a row on the oracle; returns S(cur) at the start and after 4 steps and the mask of the physical ocean cells.
     tidal_off: the row's configuration without the two init calls"""
-    from orclib import AsModel
-    from test_tidal_host import physical
     cfg, grid, tidal = twin_row(pkg, topology, scheme, nt=nt, without_scheme=without_scheme)
     orc = Oracle(cfg, grid=grid)
     twin_start(orc, [], scheme, tidal and not tidal_off)
@@ -170,19 +169,3 @@ def test_oracle_salinity_twin_stays_salinity(pkg, orclib_built, topology, scheme
         assert not np.array_equal(S4, _S_WITHOUT[key]), "(b): S is what it is with %s alone" % WITHOUT_LAST_PART[scheme]
     if scheme == "tidal-bckgrnd":                    # (b) against KPP with the uniform background of the same bckgrnd_vdc1 as well
         assert not np.array_equal(S4, _twin_oracle_run(pkg, topology, scheme, 2, False, tidal_off=True)[1])
-
-
-def closed_form_worst(age, kmt, dz, dzw, vdc, psurf, dt):
-    """worst |age - closed form| / max(column) over the levels 2 .. KMT of every interior ocean column with KMT >= 2"""
-    worst, ncol = 0.0, 0
-    nb, km, ny, nx = age.shape
-    for b in range(nb):
-        for j in range(2, ny - 2):
-            for i in range(2, nx - 2):
-                K = int(kmt[b, j, i])
-                if K < 2:
-                    continue
-                x = age_closed_form(K, dz, dzw, vdc[b, :, j, i], psurf[b, j, i], dt)
-                worst = max(worst, np.abs(age[b, 1:K, j, i] - x[1:]).max() / np.abs(x).max())
-                ncol += 1
-    return worst, ncol

@@ -7,8 +7,7 @@ import pytest
 
 import submeso_ref
 from popcfg import named_config
-
-GM = dict(hmix_tracer=3)
+from submeso_common import CLOSED_FORM_ULPS, GM, closed_form, linear_state, open_ocean
 
 
 def test_layout7_round_trip(pkg):
@@ -81,67 +80,6 @@ def test_time_scale(pkg, tsc):
     assert ts.shape == f.shape and np.abs(ts / want - 1.0).max() <= 4 * np.finfo(float).eps
     assert ts.max() <= (tsc or 3.456e5) and ts.min() > 0.0
     m.close()
-
-
-def linear_state(m, T0=16.0, a=2.0 ** -6, c=-2.0 ** -5, b=-2.0 ** -3, S0=0.035):
-    """T = T0 + a i + c j + b k (global indices, 1-based level), uniform S, on the blocks of `m`; and the cells whose four neighbours
-    carry the next global index (not across the cyclic seam or a closed boundary, where the field is not linear)"""
-    T = np.zeros((m.nblocks, m.km, m.nyb, m.nxb))
-    lin = np.zeros((m.nblocks, m.nyb, m.nxb), dtype=bool)
-    for lb, bid in enumerate(m.local_block_ids()):
-        blk = m.get_block(bid)
-        ig = np.asarray(blk["i_glob"], dtype=np.float64)[None, None, :]
-        jg = np.asarray(blk["j_glob"], dtype=np.float64)[None, :, None]
-        T[lb] = T0 + a * ig + c * jg + b * np.arange(1, m.km + 1, dtype=np.float64)[:, None, None]
-        i1, j1 = np.asarray(blk["i_glob"]), np.asarray(blk["j_glob"])
-        oi = np.zeros(m.nxb, dtype=bool); oj = np.zeros(m.nyb, dtype=bool)
-        oi[1:-1] = (i1[2:] == i1[1:-1] + 1) & (i1[:-2] == i1[1:-1] - 1)
-        oj[1:-1] = (j1[2:] == j1[1:-1] + 1) & (j1[:-2] == j1[1:-1] - 1)
-        lin[lb] = oj[:, None] & oi[None, :]
-    return T, np.full_like(T, S0), lin
-
-
-def closed_form(r, a, c, b, eff, hls0):
-    """Level-1 and level-2 tendency of T for the linear state with ML_DEPTH = zw(1) and a constant length scale, written out by hand.
-    Only the two half cells of level 1 lie above ML_DEPTH (reference depths dz(1)/4 and 3 dz(1)/4, both with (1 - 2 r)^2 = 1/4), so
-    the shape value is (1 - 1/4)(1 + 5/84); BX = -grav DRDT a and BY = -grav DRDT c on all four faces; TZ(1) = 0 and TZ(2) = -b.
-    Returns (GTK1, GTK2, the largest single term of the flux sum) on the cells whose four neighbours lie inside the block."""
-    f, vg = r["f"], r["vg"]
-    dz1, dz2 = vg["dz"][1], vg["dz"][2]
-    shape = (1.0 - 0.25) * (1.0 + 5.0 / 84.0)
-    A = eff * dz1 ** 2 * shape * r["TS"] / hls0
-    drdt = r["DRDT"][:, 0]
-    sfx = A * (-submeso_ref.GRAV * drdt * a) * np.minimum(f["DXT"], 111.0e5)     # east = west face
-    sfy = A * (-submeso_ref.GRAV * drdt * c) * np.minimum(f["DYT"], 111.0e5)
-    hyx, hxy = f["HTE"] / f["HUS"], f["HTN"] / f["HUW"]
-    fx = np.zeros_like(sfx); fy = np.zeros_like(sfx)
-    fx[..., :-1] = 0.25 * hyx[..., :-1] * (-b) * (sfx[..., :-1] + sfx[..., 1:])
-    fy[..., :-1, :] = 0.25 * hxy[..., :-1, :] * (-b) * (sfy[..., :-1, :] + sfy[..., 1:, :])
-    g1, g2, big = (np.full_like(sfx, np.nan) for _ in range(3))
-    I = (Ellipsis, slice(1, -1), slice(1, -1))
-    W = (Ellipsis, slice(1, -1), slice(0, -2))
-    Sx = (Ellipsis, slice(0, -2), slice(1, -1))
-    fz = -0.25 * (sfx[I] * hyx[I] * a + sfy[I] * hxy[I] * c + sfx[I] * hyx[W] * a + sfy[I] * hxy[Sx] * c)
-    tar = f["TAREA_R"][I]
-    g1[I] = (fx[I] - fx[W] + fy[I] - fy[Sx] - fz) / dz1 * tar
-    g2[I] = fz / dz2 * tar
-    big[I] = np.maximum.reduce([np.abs(fx[I]), np.abs(fx[W]), np.abs(fy[I]), np.abs(fy[Sx]), np.abs(fz)]) / dz1 * tar
-    return g1, g2, big
-
-
-# every flux is a product of at most 12 factors (eff, ML^2, shape, TIME_SCALE, 1 / HLS, grav, DRDT, a, the grid scale, HYX, 1/4, b), the
-# tendency sums six of them and is scaled twice: fewer than 32 roundings of at most one ulp of the largest term each, in the restatement
-# and in the hand-written form alike
-CLOSED_FORM_ULPS = 64
-
-
-def open_ocean(r):
-    """cells whose own column and four neighbours reach the bottom level"""
-    K = r["KMT"]
-    km = r["DRDT"].shape[1]
-    ok = np.zeros(K.shape, dtype=bool)
-    ok[:, 1:-1, 1:-1] = (K[:, 1:-1, 1:-1] == km) & (K[:, 1:-1, 2:] == km) & (K[:, 1:-1, :-2] == km) & (K[:, 2:, 1:-1] == km) & (K[:, :-2, 1:-1] == km)
-    return ok
 
 
 def test_restatement_against_closed_form(pkg):

@@ -8,46 +8,11 @@ import numpy as np
 import pytest
 
 import tidal_ref
-from popcfg import named_config, synthetic_grid
+from common import physical
+from popcfg import named_config
+from tidal_common import BOXES, KPP, smooth_flux, stepped_grid
 
-KPP = dict(vmix_choice=3, bckgrnd_vdc1=0.16)
 EPS = np.finfo(float).eps
-# three boxes: plain, wrapping around 360 degrees (it overwrites part of the first), and one with klevels = 2
-BOXES = [dict(TLATmin=-30.0, TLATmax=30.0, TLONmin=20.0, TLONmax=100.0, min_value=20.0, klevels=6),
-         dict(TLATmin=-60.0, TLATmax=-20.0, TLONmin=300.0, TLONmax=40.0, min_value=35.0, klevels=6),
-         dict(TLATmin=30.0, TLATmax=70.0, TLONmin=150.0, TLONmax=205.0, min_value=50.0, klevels=2)]
-
-
-def stepped_grid(cfg):
-    """popcfg.synthetic_grid with the KMT record overwritten: land stays, the ocean takes 3, 4, 5 and km in turn"""
-    g = synthetic_grid(cfg)
-    ny, nx = g["KMT"].shape
-    ii, jj = np.arange(nx)[None, :], np.arange(ny)[:, None]
-    pick = np.array([3, 4, 5, cfg.km], dtype=np.int32)[(ii + 2 * jj) % 4]
-    g["KMT"] = np.ascontiguousarray(np.where(g["KMT"] > 0, pick, 0).astype(np.int32))
-    return g
-
-
-def smooth_flux(m, amp, seed=5):
-    """energy flux [W/m^2] of the local blocks: a smooth function of the global indices times a seeded factor in [0.5, 1.5]; the ghost
-    cells are left to the halo update"""
-    nx, ny = m.cfg.nx_global, m.cfg.ny_global
-    fac = 0.5 + np.random.default_rng(seed).random((ny + 1, nx + 1))
-    F = np.zeros((m.nblocks, m.nyb, m.nxb))
-    for lb, bid in enumerate(m.local_block_ids()):
-        b = m.get_block(bid)
-        i = np.clip(np.asarray(b["i_glob"]), 0, nx)[None, :]
-        j = np.clip(np.asarray(b["j_glob"]), 0, ny)[:, None]
-        F[lb] = amp * (1.0 + 0.5 * np.cos(2.0 * np.pi * i / nx) * np.sin(np.pi * j / ny)) * fac[j, i]
-    return F
-
-
-def physical(m):
-    mask = np.zeros((m.nblocks, m.nyb, m.nxb), dtype=bool)
-    for lb, bid in enumerate(m.local_block_ids()):
-        b = m.get_block(bid)
-        mask[lb, b["jb"] - 1:b["je"], b["ib"] - 1:b["ie"]] = True
-    return mask
 
 
 def test_host_fields_match_restatement(pkg):
