@@ -704,6 +704,46 @@ long long pop_moc_sums_count(pop_ctx *ctx);
 int pop_moc_sums_get(pop_ctx *ctx, double *sums, long long count);
 int pop_moc_sums_set(pop_ctx *ctx, const double *sums, long long count);
 
+/* ---- northward heat and salt transports N_HEAT, N_SALT (compute_tracer_transports, diags_on_lat_aux_grid.F90:1294-1594) ----------
+ * The reference forms them when it writes a tavg file, from the time means of ADVT/ADVS, HDIFT/HDIFS, VNT/VNS and their _ISOP and
+ * _SUBM companions (tavg.F90:7556-7614).  The routine is linear in them, so, as for the MOC, the library adds every step's binned
+ * sums on the device, weighted like a tavg entry, and holds no time-mean field.  The latitude grid, the regions and the masks are
+ * those of pop_init_transports.  DESIGN.md section 17 has the rules.
+ *
+ * undefined_nf, the netCDF default float fill value the reference masks with: entries without an ocean cell, and the total and
+ * diffusive components of region 2, whose southern-boundary diffusive transport is not available (:1563-1578). */
+#define POP_UNDEFINED_NF 9.9692099683868690e+36
+/* put the transports into one tavg stream, 1 .. POP_TAVG_MAX_STREAMS, for heat (tracer 1), salt (tracer 2) or both (non-zero
+ * flags; one at least): they follow that stream's ltavg_on, tavg_sum and the weight of the step, and pop_tavg_reset of the stream
+ * zeroes their sums.  A stream without an entry is switched on.  Refused between pop_time_manager and pop_step_tail, before
+ * pop_init_transports, a second time, and with tadvect = 3 (lw_lim) and two regions: the north-face value of lw_lim is not kept, so
+ * the southern-boundary transport of region 2 cannot be formed (with one region it is not needed).  The sums are taken right after
+ * the (T, S) right-hand side of a step (phase "tavg_transport" of pop_run_phase / pop_time_phase; pop_run_phase("tracer_rhs")
+ * includes the site, as a step does).  Every run of the site adds to the sums: pop_time_phase("tavg_transport", reps) adds the
+ * step's terms reps + 1 times, so reset the stream after timing it. */
+int pop_transport_request(pop_ctx *ctx, int stream, int heat, int salt);
+/* n_lat_aux_grid, n_transport_comp (3; 4 with hmix_tracer = 3 and gm_diag_bolus; 5 with lsubmesoscale_mixing, :886-889),
+ * n_transport_reg, and of the request the stream (0: none) and the two flags.  Any pointer may be NULL.  pop_get_dim
+ * "transport_stream", "n_transport_comp" give the same. */
+int pop_transport_info(pop_ctx *ctx, int *n_lat_aux_grid, int *n_transport_comp, int *n_transport_reg, int *stream, int *heat, int *salt);
+/* TAVG_N_HEAT_TRANS_G (tracer = 1, PW) or TAVG_N_SALT_TRANS_G (tracer = 2, unscaled as the reference leaves it) as
+ * out[n - 1][comp - 1][reg - 1] (reg fastest), count = (n_lat_aux_grid + 1) * n_transport_comp * n_transport_reg; in r8, where the
+ * reference stores r4.  Components: 1 total = 2 + 3, 2 Eulerian-mean advection, 3 horizontal mixing (with Gent-McWilliams: eddy-induced
+ * and submesoscale advection plus diffusion), 4 eddy-induced advection (0 without gm_diag_bolus), 5 submesoscale advection.
+ * normalize, which: as pop_moc_get.  Masked entries are POP_UNDEFINED_NF.  Synchronises; with several ranks collective, and the
+ * same on every rank. */
+int pop_transport_get(pop_ctx *ctx, int tracer, int normalize, int which, double *out, long long count);
+/* the reduced unnormalised sums of the running interval, carried across a restart as the MOC's: bins as
+ * [n_lat_aux_grid][2 tracers][4 terms: -ADV TAREA, -HDIF TAREA, -ADV_ISOP TAREA, -ADV_SUBM TAREA][n_transport_reg], then the
+ * southern-boundary row of region 2 as [2 tracers][3 terms: VNF, VNF_ISOP, VNF_SUBM] (only with two regions); a tracer that was
+ * not requested and a term the configuration does not form stay 0.  count = pop_transport_sums_count. */
+long long pop_transport_sums_count(pop_ctx *ctx);
+int pop_transport_sums_get(pop_ctx *ctx, double *sums, long long count);
+int pop_transport_sums_set(pop_ctx *ctx, const double *sums, long long count);
+/* pop_get_field of the per-column terms of the last accumulated step, n = tracer index 0 | 1, (nx_block, ny_block, nblocks):
+ * "TRN_ADV", "TRN_HDIF", "TRN_VNF" and, where the configuration forms them, "TRN_ADV_ISOP", "TRN_VNF_ISOP", "TRN_ADV_SUBM",
+ * "TRN_VNF_SUBM". */
+
 /* run all launches on the host framework's HIP stream (e.g. torch.cuda.current_stream().cuda_stream) */
 int pop_set_stream(pop_ctx *ctx, void *hip_stream);
 

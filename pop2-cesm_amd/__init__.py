@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("POP_AMD_LIB") or os.path.join(_HERE, "libpop_amd.so")   # POP_AMD_LIB: build-variant experiments
 POP_CREATE_HOST_ONLY = 1
 POP_CREATE_PLAN_ONLY = 2
+UNDEFINED_NF = 9.9692099683868690e+36   # POP_UNDEFINED_NF: the fill value of masked transport entries
 
 XCHG_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong),
                       C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong))
@@ -102,6 +103,9 @@ def lib():
         "pop_moc_mask": (ci, [vp, pi, ll]), "pop_moc_bin_map": (ci, [vp, pi, ll]), "pop_moc_request": (ci, [vp, ci]),
         "pop_moc_get": (ci, [vp, ci, ci, pd, ll]), "pop_moc_sums_count": (ll, [vp]),
         "pop_moc_sums_get": (ci, [vp, pd, ll]), "pop_moc_sums_set": (ci, [vp, pd, ll]),
+        "pop_transport_request": (ci, [vp, ci, ci, ci]), "pop_transport_info": (ci, [vp, pi, pi, pi, pi, pi, pi]),
+        "pop_transport_get": (ci, [vp, ci, ci, ci, pd, ll]), "pop_transport_sums_count": (ll, [vp]),
+        "pop_transport_sums_get": (ci, [vp, pd, ll]), "pop_transport_sums_set": (ci, [vp, pd, ll]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)       # AttributeError here = the library does not export the ABI
@@ -678,6 +682,39 @@ class PopModel:
             return v
         a = np.empty(max(self.L.pop_moc_sums_count(self.h), 0), dtype=np.float64)
         self._chk(self.L.pop_moc_sums_get(self.h, a.ctypes.data_as(C.POINTER(C.c_double)), a.size))
+        return a
+
+    # ---- northward heat and salt transports (compute_tracer_transports; include/pop_amd.h pop_transport_*)
+    def transport_request(self, stream, heat=True, salt=True):
+        """put N_HEAT and / or N_SALT into tavg stream 1 .. 9 (its ltavg_on, tavg_sum and reset); after init_transports"""
+        self._chk(self.L.pop_transport_request(self.h, stream, 1 if heat else 0, 1 if salt else 0))
+
+    def transport_info(self):
+        """dict(n_lat_aux_grid, n_transport_comp, n_transport_reg, stream (0: not requested), heat, salt)"""
+        v = [C.c_int() for _ in range(6)]
+        self._chk(self.L.pop_transport_info(self.h, *[C.byref(x) for x in v]))
+        out = dict(zip(("n_lat_aux_grid", "n_transport_comp", "n_transport_reg", "stream"), [x.value for x in v[:4]]))
+        out["heat"], out["salt"] = bool(v[4].value), bool(v[5].value)
+        return out
+
+    def transport_get(self, tracer, normalize=True, snapshot=False):
+        """TAVG_N_HEAT_TRANS_G (tracer "heat" or 1, PW) or TAVG_N_SALT_TRANS_G ("salt" or 2) as (n_lat_aux_grid + 1, n_transport_comp,
+        n_transport_reg); masked entries are UNDEFINED_NF; snapshot: the one tavg_write took before it reset the stream"""
+        t = {"heat": 1, "salt": 2}.get(tracer, tracer)
+        inf = self.transport_info()
+        a = np.empty((inf["n_lat_aux_grid"] + 1, inf["n_transport_comp"], inf["n_transport_reg"]), dtype=np.float64)
+        self._chk(self.L.pop_transport_get(self.h, t, 1 if normalize else 0, 1 if snapshot else 0, a.ctypes.data_as(C.POINTER(C.c_double)), a.size))
+        return a
+
+    def transport_sums(self, values=None):
+        """the reduced unnormalised sums of the running interval as one vector (bins (n, 2 tracers, 4 terms, reg), then the boundary
+        row of region 2 (2 tracers, 3 terms)); with `values` such a vector replaces the sums (it is added last when they are next read)"""
+        if values is not None:
+            v = np.ascontiguousarray(values, dtype=np.float64)
+            self._chk(self.L.pop_transport_sums_set(self.h, v.ctypes.data_as(C.POINTER(C.c_double)), v.size))
+            return v
+        a = np.empty(max(self.L.pop_transport_sums_count(self.h), 0), dtype=np.float64)
+        self._chk(self.L.pop_transport_sums_get(self.h, a.ctypes.data_as(C.POINTER(C.c_double)), a.size))
         return a
 
     # ---- step_mod.F90 sequence

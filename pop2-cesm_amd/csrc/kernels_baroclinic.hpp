@@ -177,6 +177,10 @@ struct TracerRhsArgs {
   // passive form (k_tracer_rhs<., ., ., NP, true>): the interior source of the tracer module (set_interior_passive_tracers,
   // baroclinic.F90:2151), one value per tracer, applied at 1 < k <= KMT (ideal age: iage_mod.F90:352-353)
   double isrc[2] = {0.0, 0.0};
+  // diagnostic form (k_tracer_rhs<., ., ., 2, false, true>, kernels_transport.hpp): nothing of the above is written; E[n], F[n] and
+  // D2N[n] receive the vertically integrated advective tendency, horizontal-mixing tendency and northward flux of tracer n per
+  // physical column, (nxb, nyb, nblocks).  The struct gains no member for them, so that the kernel arguments of every other
+  // instantiation -- and with them its code -- stay what they were.
 };
 __device__ __forceinline__ double sw_source(const TracerRhsArgs &a, double qsw, int k, int kmt, double dzrk, int chli, double &trans_km1, double dzt_pbc) {
   double top, bot;
@@ -202,8 +206,18 @@ __device__ __forceinline__ double sw_source(const TracerRhsArgs &a, double qsw, 
 // sets VDC[0] = VDC[1]); no short-wave source (add_sw_absorb is temperature's); the module's interior source isrc goes into the source sum
 // ahead of the KPP term (baroclinic.F90:2146-2181); the right-hand side is stored as c2dtt * FT at every level, without the
 // surface-pressure term of the predictor, which is for n = 1, 2 only (:2214-2237).  Every other operation is the (T, S) one, in its order.
-template <bool DEL4, bool UPW3, bool PBC = false, int NP = 2, bool PASSIVE = false>
-__global__ void __launch_bounds__(POP_COL_THREADS, POP_TRC_WAVES)
+// TRN: the diagnostic form of the northward tracer transports (diags_on_lat_aux_grid.F90:1294-1594).  Nothing of the step is stored;
+// the advective operator L, the horizontal-mixing term and the face flux velocity VTN of every level -- formed as above, so they are
+// the step's own -- are integrated over the column in k = 1 .. km order into
+//   ADV  = sum_k -dz(k) L(k), k <= KMT            (advection.F90:1803-1821)
+//   HDIF = sum_k dz(k) HDTK(k), k <= KMT          (horizontal_mix.F90:592-609)
+//   VNF  = sum_k FN(k) TAREA dz(k)                (diags_on_lat_aux_grid.F90:1484), FN = (p5 VTN TAREA_R)(T + T_north) centred,
+//          c2 (p5 VTN TAREA_R) TRACER_N upwind3 (advection.F90:1746, 1777, 1796); 0 with lw_lim, whose north-face value is not kept
+// The vertical diffusion, the sources and the short wave are not formed.  No partial bottom cells (init_lat_aux_grid refuses them).
+// The six column sums of TRN on top of the upwind3 weights do not fit the register budget of POP_TRC_WAVES waves per SIMD (del2 +
+// upwind3 spilled 28 bytes per lane), so the diagnostic form is compiled for one wave: it runs in accumulating steps only.
+template <bool DEL4, bool UPW3, bool PBC = false, int NP = 2, bool PASSIVE = false, bool TRN = false>
+__global__ void __launch_bounds__(POP_COL_THREADS, TRN ? 1 : POP_TRC_WAVES)
 k_tracer_rhs(DevGrid g, StepParams sp, TracerRhsArgs a) {
   Col c;
   if (!col_setup(g, c, true)) return;
@@ -248,6 +262,8 @@ k_tracer_rhs(DevGrid g, StepParams sp, TracerRhsArgs a) {
   }
   const long long vdcbase = ((long long)c.b * (km + 2)) * n2 + c.p2;
   double *__restrict__ const TNp[2] = {a.TNEW[0], a.TNEW[NP - 1]};   // outputs alias no input
+  double trn_adv[2] = {0.0, 0.0}, trn_hdif[2] = {0.0, 0.0}, trn_vnf[2] = {0.0, 0.0};
+  const double trn_tarea = TRN ? g.TAREA[c.q2] : 0.0;
   for (int k = 1; k <= km; ++k) {
     const long long o = c.base3 + (long long)(k - 1) * n2;
     const int kp1 = (k < km) ? k + 1 : km;
@@ -305,6 +321,7 @@ k_tracer_rhs(DevGrid g, StepParams sp, TracerRhsArgs a) {
         const double tn = upw3_face(k, FVN, kmtn, kmts, kmtnn, wy0, xs1, tc_k[n], xn1, xn2);
         const double tns = upw3_face(k, PBC ? VTS * (tarear_s / pbc_dz(g, k, kmts, dzbcs)) : VTS * tarear_s, kNs, kSs, kNNs, wys, xs2, xs1, tc_k[n], xn1);
         L = L + FVN * tn + FVS * tns;
+        if constexpr (TRN) trn_vnf[n] = trn_vnf[n] + 2.0 * (0.5 * VTN * tarear) * tn * trn_tarea * g.dz[k];
         // vertical: flux through the bottom face (:2397-2432)
         double azminus, dzminus;
         if (k < kmt - 1) { azminus = a.up.cz[3][k]; dzminus = a.up.cz[5][k]; } else { azminus = a.up.cz[3][k] + a.up.cz[5][k]; dzminus = 0.0; }
@@ -332,6 +349,12 @@ k_tracer_rhs(DevGrid g, StepParams sp, TracerRhsArgs a) {
         if (k != 1) L = L + dz2rk * wtk * (tc_km1[n] + tc_k[n]);
         if (k < km) L = L - dz2rk * wtkb * (tc_k[n] + tc_kp1[n]);
         }
+        if constexpr (TRN) trn_vnf[n] = trn_vnf[n] + (0.5 * VTN * tarear) * (tc_k[n] + TC[o + nxb]) * trn_tarea * g.dz[k];
+      }
+      if constexpr (TRN) {
+        if (k <= kmt) { trn_adv[n] = trn_adv[n] + -(g.dz[k] * L); trn_hdif[n] = trn_hdif[n] + g.dz[k] * FT; }
+        tc_km1[n] = tc_k[n]; tc_k[n] = tc_kp1[n]; to_k[n] = to_kp1[n];
+        continue;
       }
       FT = FT - L;
       if (k == 1) vtf[n] = (kmt >= 1) ? a.STF[n][c.q2] : 0.0;
@@ -359,6 +382,10 @@ k_tracer_rhs(DevGrid g, StepParams sp, TracerRhsArgs a) {
       tc_km1[n] = tc_k[n]; tc_k[n] = tc_kp1[n]; to_k[n] = to_kp1[n];
     }
     wtk = wtkb;
+  }
+  if constexpr (TRN) {
+#pragma unroll
+    for (int n = 0; n < NP; ++n) { a.E[n][c.q2] = trn_adv[n]; a.F[n][c.q2] = trn_hdif[n]; a.D2N[n][c.q2] = trn_vnf[n]; }
   }
 }
 

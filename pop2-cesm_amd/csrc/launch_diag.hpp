@@ -185,7 +185,7 @@ int diag_finish_global(pop_ctx *c, const char *who, DiagGlobalOut &o) {
   o.avg_tracer_k.assign((size_t)km * nt, nan);
   // pop_constants.F90:336, 364-365 with the code defaults unless pop_init_ice gave others (as launch_tavg.hpp)
   const pop_ctx::Ice &I = c->ice;
-  const double hflux_factor = I.inited ? I.k.hflux_factor : 1000.0 / ((4.1 / 3.996) * 3.996e7);
+  const double hflux_factor = hflux_factor_of(c);
   const double salinity_factor = -(I.inited ? I.nml.ocn_ref_salinity : 34.7) * 1.0e-4;
   const double salt_to_ppt = 1000.0;
   if (D.step_after >= 0) {

@@ -17,7 +17,6 @@ size_t moc_per_blist(const pop_ctx *c) { return (size_t)c->h.km * c->moc.aux.n_c
 size_t moc_n_bins(const pop_ctx *c) { return (size_t)c->moc.aux.n_lat * moc_per_list(c); }
 size_t moc_n_sums(const pop_ctx *c) { return moc_n_bins(c) + (c->moc.aux.n_reg > 1 ? moc_per_blist(c) : 0); }
 size_t moc_n_out(const pop_ctx *c) { const LatAux &A = c->moc.aux; return (size_t)(A.n_lat + 1) * (c->h.km + 1) * A.n_comp * A.n_reg; }
-size_t moc_n_gather(const pop_ctx *c) { return c->moc.aux.lists.size() * moc_per_list(c) + c->moc.aux.blists.size() * moc_per_blist(c); }
 
 int moc_inited(pop_ctx *c, const char *who) {
   if (c->moc.aux.inited) return 0;
@@ -25,10 +24,11 @@ int moc_inited(pop_ctx *c, const char *who) {
   return 1;
 }
 
-// the lists of this rank's blocks on the device, the accumulators and the scratch field
-int moc_alloc(pop_ctx *c) {
+// the lists of this rank's blocks on the device, once: the MOC and the tracer transports walk the same lists
+int moc_lists_upload(pop_ctx *c) {
   MocState &M = c->moc;
   const LatAux &A = M.aux;
+  if (M.lists_up) return 0;
   auto local = [&](const std::vector<MocList> &all, const std::vector<int> &cells, std::vector<int> &pick, MocList **d_lists, int **d_cells) {
     std::vector<MocList> loc;
     std::vector<int> lc;
@@ -43,6 +43,14 @@ int moc_alloc(pop_ctx *c) {
     return dev_upload(c, d_lists, loc.data(), loc.size()) || dev_upload(c, d_cells, lc.data(), lc.size());
   };
   if (local(A.lists, A.cells, M.loc_list, &M.d_lists, &M.d_cells) || local(A.blists, A.bcells, M.loc_blist, &M.d_blists, &M.d_bcells)) return 1;
+  M.lists_up = true;
+  return 0;
+}
+// the accumulators and the scratch field
+int moc_alloc(pop_ctx *c) {
+  MocState &M = c->moc;
+  const LatAux &A = M.aux;
+  if (moc_lists_upload(c)) return 1;
   if (dev_alloc(c, &M.ACC, M.loc_list.size() * moc_per_list(c)) || dev_alloc(c, &M.BACC, M.loc_blist.size() * moc_per_blist(c))) return 1;
   if (dev_alloc(c, &M.WE, (size_t)c->h.n3 * c->h.nblocks, false)) return 1;
   if (A.n_comp > 1 && !c->d2.count("HTN")) {
@@ -91,42 +99,50 @@ int moc_reset(pop_ctx *c) {
   return 0;
 }
 
-// the reduced unnormalised sums: bins [n][k][comp][reg], then the boundary row of region 2 [k][comp]
-int moc_reduce(pop_ctx *c, std::vector<double> &sums) {
-  MocState &M = c->moc;
+// per-(block, bin) accumulators on the lists of pop_init_transports (pl numbers per bin list in ACC, pb per boundary-row list in
+// BACC) -> the reduced unnormalised sums: the bins [n][pl], then the boundary row of region 2 [pb].  Shared by the MOC and the
+// tracer transports (launch_transport.hpp); gather: the caller's device buffer of a multi-rank reduce
+int lat_aux_reduce(pop_ctx *c, const char *who, const double *ACC, const double *BACC, size_t pl, size_t pb, double **gather,
+                   const std::vector<double> &set_sums, std::vector<double> &sums) {
+  const MocState &M = c->moc;
   const LatAux &A = M.aux;
-  const size_t pl = moc_per_list(c), pb = moc_per_blist(c), nL = A.lists.size(), boff = nL * pl;
-  std::vector<double> G(moc_n_gather(c), 0.0), loc(std::max(M.loc_list.size() * pl, M.loc_blist.size() * pb));
+  const size_t nL = A.lists.size(), boff = nL * pl, nbins = (size_t)A.n_lat * pl;
+  std::vector<double> G(nL * pl + A.blists.size() * pb, 0.0), loc(std::max(M.loc_list.size() * pl, M.loc_blist.size() * pb));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (!M.loc_list.empty()) HIPCHK(c, hipMemcpy(loc.data(), M.ACC, M.loc_list.size() * pl * sizeof(double), hipMemcpyDeviceToHost));
+  if (!M.loc_list.empty()) HIPCHK(c, hipMemcpy(loc.data(), ACC, M.loc_list.size() * pl * sizeof(double), hipMemcpyDeviceToHost));
   for (size_t i = 0; i < M.loc_list.size(); ++i) std::copy(loc.begin() + i * pl, loc.begin() + (i + 1) * pl, G.begin() + (size_t)M.loc_list[i] * pl);
-  if (!M.loc_blist.empty()) HIPCHK(c, hipMemcpy(loc.data(), M.BACC, M.loc_blist.size() * pb * sizeof(double), hipMemcpyDeviceToHost));
+  if (!M.loc_blist.empty()) HIPCHK(c, hipMemcpy(loc.data(), BACC, M.loc_blist.size() * pb * sizeof(double), hipMemcpyDeviceToHost));
   for (size_t i = 0; i < M.loc_blist.size(); ++i) std::copy(loc.begin() + i * pb, loc.begin() + (i + 1) * pb, G.begin() + boff + (size_t)M.loc_blist[i] * pb);
   if (c->h.nranks > 1 && !G.empty()) {   // as diag_publish: through the reduce buffer, in pieces of its size
-    if (!c->allred || !c->redbuf || c->red_doubles < 1) { c->err = "moc: multi-rank run without a transport"; return 1; }
-    if (!M.gather && dev_alloc(c, &M.gather, G.size(), false)) return 1;
-    HIPCHK(c, hipMemcpyAsync(M.gather, G.data(), G.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (!c->allred || !c->redbuf || c->red_doubles < 1) { c->err = std::string(who) + ": multi-rank run without a transport"; return 1; }
+    if (!*gather && dev_alloc(c, gather, G.size(), false)) return 1;
+    HIPCHK(c, hipMemcpyAsync(*gather, G.data(), G.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     for (size_t off = 0; off < G.size(); off += (size_t)c->red_doubles) {
       const size_t cnt = std::min(G.size() - off, (size_t)c->red_doubles);
-      HIPCHK(c, hipMemcpyAsync(c->redbuf, M.gather + off, cnt * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      if (c->allred(c->comm_user, 0, (long long)cnt)) { c->err = "moc: allreduce failed" + tr_err(c); return 1; }
-      HIPCHK(c, hipMemcpyAsync(M.gather + off, c->redbuf, cnt * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->redbuf, *gather + off, cnt * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      if (c->allred(c->comm_user, 0, (long long)cnt)) { c->err = std::string(who) + ": allreduce failed" + tr_err(c); return 1; }
+      HIPCHK(c, hipMemcpyAsync(*gather + off, c->redbuf, cnt * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(G.data(), M.gather, G.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(G.data(), *gather, G.size() * sizeof(double), hipMemcpyDeviceToHost));
   }
-  sums.assign(moc_n_sums(c), 0.0);
+  sums.assign(nbins + (A.n_reg > 1 ? pb : 0), 0.0);
   for (size_t l = 0; l < nL; ++l) {   // (block id, bin) order: within a bin the blocks in block-id order
     double *s = sums.data() + (size_t)A.lists[l].bin * pl;
     for (size_t e = 0; e < pl; ++e) s[e] = s[e] + G[l * pl + e];
   }
   if (A.n_reg > 1)
     for (size_t l = 0; l < A.blists.size(); ++l) {
-      double *s = sums.data() + moc_n_bins(c);
+      double *s = sums.data() + nbins;
       for (size_t e = 0; e < pb; ++e) s[e] = s[e] + G[boff + l * pb + e];
     }
-  if (!M.set_sums.empty()) for (size_t e = 0; e < sums.size(); ++e) sums[e] = sums[e] + M.set_sums[e];
+  if (!set_sums.empty()) for (size_t e = 0; e < sums.size(); ++e) sums[e] = sums[e] + set_sums[e];
   return 0;
+}
+// the MOC's: bins [n][k][comp][reg], then the boundary row of region 2 [k][comp]
+int moc_reduce(pop_ctx *c, std::vector<double> &sums) {
+  MocState &M = c->moc;
+  return lat_aux_reduce(c, "moc", M.ACC, M.BACC, moc_per_list(c), moc_per_blist(c), &M.gather, M.set_sums, sums);
 }
 
 // compute_moc from the sums on (:1054-1189): scale, prefix over the bins, southern boundary of region 2, Sverdrups

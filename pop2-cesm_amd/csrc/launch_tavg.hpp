@@ -60,7 +60,7 @@ std::vector<TavgAvail> tavg_avail(const pop_ctx *c) {
   auto vint = [&](const std::string &name, int site, int kmax, int expr, int a, int b = -1) { add(name, site, 2, TAVG_AVG, kmax, expr, a, b, false, true); };
   const pop_ctx::Ice &I = c->ice;
   // pop_constants.F90:336, 364-365 with the code defaults of rho_sw, cp_sw, ocn_ref_salinity unless pop_init_ice gave others
-  const double hflux_factor = I.inited ? I.k.hflux_factor : 1000.0 / ((4.1 / 3.996) * 3.996e7);
+  const double hflux_factor = hflux_factor_of(c);
   const double salinity_factor = -(I.inited ? I.nml.ocn_ref_salinity : 34.7) * 1.0e-4;
   const bool fw_as_salt = I.inited && I.nml.lfw_as_salt_flx;
   // FORCING
@@ -273,6 +273,7 @@ int tavg_reset_stream(pop_ctx *c, int ns) {
   T.sum[ns] = 0.0;
   if (T.has_qflux[ns]) T.sum_qflux[ns] = 0.0;
   if (c->moc.requested && c->moc.stream == ns && moc_reset(c)) return 1;
+  if (c->trn.requested && c->trn.stream == ns && trn_reset(c)) return 1;
   return 0;
 }
 void tavg_refresh_flags(pop_ctx *c) {
@@ -283,6 +284,8 @@ void tavg_refresh_flags(pop_ctx *c) {
   T.dirty = true;
   if (c->moc.requested) T.used[c->moc.stream] = true;   // the stream of pop_moc_request holds the MOC
   c->moc.active = c->moc.requested && T.on[c->moc.stream];
+  if (c->trn.requested) T.used[c->trn.stream] = true;   // ... and the stream of pop_transport_request the tracer transports
+  c->trn.active = c->trn.requested && T.on[c->trn.stream];
 }
 TavgEntry *tavg_find(pop_ctx *c, const char *name) {
   for (TavgEntry &e : c->tavg.req) if (e.name == name) return &e;

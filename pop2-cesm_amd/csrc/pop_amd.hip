@@ -25,6 +25,7 @@
 #include "kernels_tavg.hpp"
 #include "kernels_diag.hpp"
 #include "kernels_moc.hpp"
+#include "kernels_transport.hpp"
 #include "rccl_transport.hpp"
 
 using namespace pop;
@@ -33,6 +34,7 @@ using namespace pop;
 #include "launch_halo.hpp"
 #include "launch_solvers.hpp"
 #include "launch_moc.hpp"
+#include "launch_transport.hpp"
 #include "launch_tavg.hpp"
 #include "launch_diag.hpp"
 
@@ -101,6 +103,11 @@ int resolve(pop_ctx *c, const std::string &name, int tl, int n, double **ptr, lo
   if (name == "USUBM") return ok(c->subm.US, a3);
   if (name == "VSUBM") return ok(c->subm.VS, a3);
   if (name == "WSUBM") return ok(c->subm.WS, a3);
+  // pop_transport_request: the per-column terms of the last accumulated step, by tracer index (kernels_transport.hpp TrnCol)
+  if (name.compare(0, 4, "TRN_") == 0) {
+    const char *const col[TRN_NCOL] = {"TRN_ADV", "TRN_HDIF", "TRN_VNF", "TRN_ADV_ISOP", "TRN_VNF_ISOP", "TRN_ADV_SUBM", "TRN_VNF_SUBM"};
+    for (int f = 0; f < TRN_NCOL; ++f) if (name == col[f]) return (n == 0 || n == 1) ? ok(c->trn.COL[n][f], a2) : 1;
+  }
   if (c->tidal.on && c->mix.kpp) {   // tidal_diag: the last evaluation's TIDAL_DIFF, TIDAL_N2, KVMIX, KVMIX_M
     const TidalDev &td = ((const KppHost *)c->mix.kpp)->tidal;
     if (name == "TIDAL_DIFF") return ok(td.DIFF, a3);
@@ -955,6 +962,8 @@ int pop_get_dim(const pop_ctx *c, const char *name) {
   if (n == "ocean_columns_total") return (int)c->h.ocean_cols_total;
   if (n == "lat_aux_region_start") return (c->moc.aux.inited && c->moc.aux.n_reg > 1) ? c->moc.aux.region_start[1] : 0;   // pop_init_transports
   if (n == "moc_stream") return c->moc.requested ? c->moc.stream : 0;
+  if (n == "transport_stream") return c->trn.requested ? c->trn.stream : 0;
+  if (n == "n_transport_comp") return c->moc.aux.inited ? trn_n_comp(c->h.c) : 0;   // pop_init_transports
   if (n.compare(0, 5, "form_") == 0 && !c->h.plan_only) return forms_get(c->f, n.substr(5));   // any entry of the plan (forms.hpp)
   return -1;
 }
@@ -1472,13 +1481,10 @@ static int phase_advt_lw_lim(pop_ctx *c) {
   HIPCHK(c, hipGetLastError());
   return 0;
 }
-static int phase_tracer_rhs(pop_ctx *c, bool fwd = false) {
-  const StepParams sp = step_params(c);
+// the arguments of the (T, S) right-hand side that do not depend on the kernel form
+static TracerRhsArgs tracer_rhs_args(pop_ctx *c, const StepParams &sp) {
   TracerRhsArgs a{};
-  if (c->h.c.tadvect == 3) {
-    if (phase_advt_lw_lim(c)) return 1;
-    a.LTK[0] = c->lw.XOUT[0]; a.LTK[1] = c->lw.XOUT[1];
-  }
+  if (c->h.c.tadvect == 3) { a.LTK[0] = c->lw.XOUT[0]; a.LTK[1] = c->lw.XOUT[1]; }
   a.E[0] = c->E3; a.F[0] = c->F3; a.E[1] = c->S3c; a.F[1] = c->S3d;
   for (int n = 0; n < 2; ++n) {
     a.TCUR[n] = c->TR[n][c->curt]; a.TOLD[n] = c->TR[n][c->oldt]; a.TMIX[n] = c->TR[n][c->mixt]; a.TNEW[n] = c->TR[n][c->newt];
@@ -1492,6 +1498,14 @@ static int phase_tracer_rhs(pop_ctx *c, bool fwd = false) {
     a.sw_on = 1; a.sw_type = c->h.c.sw_absorption_type; a.sw_ksol = c->h.sw.ksol;
     a.QSW = c->SHF_QSW; a.swabs = c->h.sw.swabs; a.swTr = c->h.sw.Tr; a.swCHLI = c->h.sw.CHLI;
   }
+  return a;
+}
+// site "tavg_transport" (launch_transport.hpp): the step's launch has been made; not inside pop_time_phase, which times kernels only
+static int trn_after_rhs(pop_ctx *c, const TracerRhsArgs &a) { return (c->trn.active && !c->phase_timing) ? trn_site(c, a) : 0; }
+static int phase_tracer_rhs(pop_ctx *c, bool fwd = false) {
+  const StepParams sp = step_params(c);
+  if (c->h.c.tadvect == 3 && phase_advt_lw_lim(c)) return 1;
+  TracerRhsArgs a = tracer_rhs_args(c, sp);
   // the next step's first Laplacian: valid when that step is a leapfrog step whose mix time is this step's current time and nothing
   // rewrites the current tracers before then (no averaging step, no Robert filter) -- the rule of the KPP look-ahead
   // Gent-McWilliams (r4): the LDS kernel with the mixing tendency given (k_tracer_rhs_lds<., ., false, true>)
@@ -1507,7 +1521,7 @@ static int phase_tracer_rhs(pop_ctx *c, bool fwd = false) {
       if (halo_update_many(c, {{c->d2t_next[0], c->g.km}, {c->d2t_next[1], c->g.km}})) return 1;
       c->d2t_next_valid = true; c->d2t_next_slot = c->curt;
     }
-    return 0;
+    return trn_after_rhs(c, a);
   }
   if (fwd) { c->err = "fused forward elimination needs the LDS tracer kernel"; return 1; }
   const bool gm = c->h.c.hmix_tracer == 3, up3 = c->h.c.tadvect == 2;
@@ -1516,7 +1530,12 @@ static int phase_tracer_rhs(pop_ctx *c, bool fwd = false) {
   with_flags([&](auto GM, auto UP3, auto PBC) {
     hipLaunchKernelGGL((k_tracer_rhs<GM.value, UP3.value, PBC.value>), grid_stencil(c), block_stencil(), 0, c->stream, c->g, sp, a);
   }, gm, up3, c->g.pbc);
-  return 0;
+  return trn_after_rhs(c, a);
+}
+// pop_run_phase / pop_time_phase: the site on its own, from the fields the last right-hand side launch read
+static int trn_phase(pop_ctx *c) {
+  if (!c->trn.requested) { c->err = "tavg_transport: pop_transport_request has not been called"; return 1; }
+  return trn_site(c, tracer_rhs_args(c, step_params(c)));
 }
 // tracer_update (baroclinic.F90:1981-2300) for the passive tracers n = 3 .. nt, a pair per launch and one launch of one for an odd count,
 // on the launch stream after the (T, S) right-hand side: k_tracer_rhs<., ., ., NP, true>.  Every tracer uses cfg.tadvect and the (T, S)
@@ -2661,6 +2680,7 @@ static phase_fn_t phase_by_name(const std::string &p) {
   if (p == "diag_global_afterupdate") return diag_phase_after;
   if (p == "diag_cfl") return diag_phase_cfl;
   if (p == "tavg_moc") return moc_phase;   // the MOC site on its own, with the weight of the last pop_time_manager (launch_moc.hpp)
+  if (p == "tavg_transport") return trn_phase;   // the same for the tracer transports (launch_transport.hpp)
   if (p == "block_sums") return [](pop_ctx *x) { SolveView v = local_view(x); presum(x, v, v.partial, v.blocksum + 2 * v.nblocks_tot); return 0; };
   return nullptr;
 }
@@ -2705,6 +2725,9 @@ int pop_time_phase(pop_ctx *c, const char *phase, int reps, double *avg_ms) {
 }
 
 // ---- time-averaged output (tavg.F90; kernels_tavg.hpp, launch_tavg.hpp)
+static std::string tavg_left_out_hint(const std::string &nm) {   // the slab entries stay left out; the transports have their own request
+  return (nm == "N_HEAT" || nm == "N_SALT") ? ".  The northward transports are requested with pop_transport_request and read with pop_transport_get" : "";
+}
 int pop_tavg_request(pop_ctx *c, int ns, const char *name) {
   if (!c) return 1;
   if (!name) { c->err = "pop_tavg_request: no name"; return 1; }
@@ -2713,7 +2736,7 @@ int pop_tavg_request(pop_ctx *c, int ns, const char *name) {
   const std::string nm(name);
   if (nm == "MOC") { c->err = "pop_tavg_request: MOC is not a slab field: it is requested with pop_moc_request(stream) and read with pop_moc_get"; return 1; }
   if (const TavgEntry *e = tavg_find(c, name)) { c->err = "pop_tavg_request: " + nm + " is already requested, in stream " + std::to_string(e->stream) + " (a name belongs to one stream)"; return 1; }
-  for (const char *l : tavg_left_out) if (nm == l) { c->err = "pop_tavg_request: " + nm + " is known to the reference, not built (DESIGN.md section 14)"; return 1; }
+  for (const char *l : tavg_left_out) if (nm == l) { c->err = "pop_tavg_request: " + nm + " is known to the reference, not built (DESIGN.md section 14)" + tavg_left_out_hint(nm); return 1; }
   const std::vector<TavgAvail> avail = tavg_avail(c);
   const TavgAvail *a = nullptr;
   for (const TavgAvail &x : avail) if (x.name == nm) a = &x;
@@ -2746,7 +2769,7 @@ int pop_tavg_info(pop_ctx *c, const char *name, int *stream, int *ndims, int *nl
   if (!c) return 1;
   const std::string nm(name ? name : "");
   if (nm == "MOC") { c->err = "pop_tavg_info: MOC is not a slab field: it is requested with pop_moc_request(stream) and read with pop_moc_get"; return 1; }
-  for (const char *l : tavg_left_out) if (nm == l) { c->err = "pop_tavg_info: " + nm + " is known to the reference, not built (DESIGN.md section 14)"; return 1; }
+  for (const char *l : tavg_left_out) if (nm == l) { c->err = "pop_tavg_info: " + nm + " is known to the reference, not built (DESIGN.md section 14)" + tavg_left_out_hint(nm); return 1; }
   for (const TavgAvail &a : tavg_avail(c)) {
     if (a.name != nm) continue;
     const TavgEntry *e = tavg_find(c, name);
@@ -2805,6 +2828,7 @@ int pop_tavg_write(pop_ctx *c, int ns, const char *path, int restart_type) {
   auto fetch = [&](size_t i, double *buf) { return tavg_to_host(c, *ent[i], restart_type == 0, buf); };
   if (slab_file_write(c->h, path, at, fields, fetch, "tavg", c->err)) return 1;
   if (restart_type == 0 && c->moc.requested && c->moc.stream == ns && moc_snapshot(c)) return 1;   // write, then reset: the MOC of the interval stays readable
+  if (restart_type == 0 && c->trn.requested && c->trn.stream == ns && trn_snapshot(c)) return 1;   // ... and the tracer transports
   return restart_type == 0 ? tavg_reset_stream(c, ns) : 0;
 }
 int pop_tavg_read(pop_ctx *c, int ns, const char *path) {
@@ -2988,6 +3012,72 @@ int pop_moc_sums_set(pop_ctx *c, const double *sums, long long count) {
   if (tavg_between_steps(c, "pop_moc_sums_set") || count_is(c, (long long)moc_n_sums(c), count, "the MOC sums")) return 1;
   if (moc_reset(c)) return 1;   // the vector replaces the sums of the interval
   c->moc.set_sums.assign(sums, sums + count);
+  return 0;
+}
+
+// ---- northward heat and salt transports (compute_tracer_transports; kernels_transport.hpp, launch_transport.hpp)
+int pop_transport_request(pop_ctx *c, int ns, int heat, int salt) {
+  if (!c) return 1;
+  if (c->h.plan_only) { c->err = "pop_transport_request: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+  if (tavg_stream_ok(c, ns, "pop_transport_request") || tavg_between_steps(c, "pop_transport_request") || moc_inited(c, "pop_transport_request")) return 1;
+  if (c->trn.requested) { c->err = "pop_transport_request: the transports are already requested, in stream " + std::to_string(c->trn.stream); return 1; }
+  if (!heat && !salt) { c->err = "pop_transport_request: neither heat nor salt is asked for"; return 1; }
+  if (c->h.c.tadvect == 3 && c->moc.aux.n_reg > 1) {
+    c->err = "pop_transport_request: tadvect = 3 (lw_lim) with n_transport_reg = 2: the north-face value of lw_lim is not kept, so the southern-boundary transport of region 2 cannot be formed (one region is built)";
+    return 1;
+  }
+  c->trn.n_comp = trn_n_comp(c->h.c);
+  if (!c->host_only && (join_side(c, true) || trn_alloc(c))) return 1;
+  const bool first = !c->tavg.used[ns];
+  c->trn.requested = true; c->trn.stream = ns; c->trn.want[0] = heat != 0; c->trn.want[1] = salt != 0;
+  if (first) c->tavg.on[ns] = true;   // as the first pop_tavg_request of a stream
+  tavg_refresh_flags(c);
+  return 0;
+}
+int pop_transport_info(pop_ctx *c, int *n_lat, int *n_comp, int *n_reg, int *stream, int *heat, int *salt) {
+  if (!c || moc_inited(c, "pop_transport_info")) return 1;
+  if (n_lat) *n_lat = c->moc.aux.n_lat;
+  if (n_comp) *n_comp = trn_n_comp(c->h.c);
+  if (n_reg) *n_reg = c->moc.aux.n_reg;
+  if (stream) *stream = c->trn.requested ? c->trn.stream : 0;
+  if (heat) *heat = c->trn.want[0];
+  if (salt) *salt = c->trn.want[1];
+  return 0;
+}
+static int trn_requested(pop_ctx *c, const char *who) {
+  if (need_device(c) || moc_inited(c, who)) return 1;
+  if (!c->trn.requested) { c->err = std::string(who) + ": pop_transport_request has not been called"; return 1; }
+  return 0;
+}
+int pop_transport_get(pop_ctx *c, int tracer, int normalize, int which, double *out, long long count) {
+  if (trn_requested(c, "pop_transport_get")) return 1;
+  if ((tracer != 1 && tracer != 2) || !c->trn.want[tracer - 1]) { c->err = "pop_transport_get: tracer 1 (heat) or 2 (salt), as pop_transport_request asked for"; return 1; }
+  if (which != 0 && which != 1) { c->err = "pop_transport_get: which 0 (the running interval) or 1 (the snapshot of pop_tavg_write)"; return 1; }
+  if (count_is(c, (long long)trn_n_out(c), count, tracer == 1 ? "N_HEAT" : "N_SALT")) return 1;
+  if (which == 1) {
+    if (!c->trn.have_snap) { c->err = "pop_transport_get: no snapshot yet: pop_tavg_write(stream, path, 0) of the transports' stream takes it"; return 1; }
+    std::copy(c->trn.snap[tracer - 1].begin(), c->trn.snap[tracer - 1].end(), out);
+    return 0;
+  }
+  double factor;
+  std::vector<double> sums;
+  if (trn_factor(c, normalize, &factor) || join_side(c, true) || trn_reduce(c, sums)) return 1;
+  trn_finish(c, sums, factor, tracer - 1, out);
+  return 0;
+}
+long long pop_transport_sums_count(pop_ctx *c) { return (c && c->moc.aux.inited) ? (long long)trn_n_sums(c) : -1; }
+int pop_transport_sums_get(pop_ctx *c, double *sums, long long count) {
+  if (trn_requested(c, "pop_transport_sums_get")) return 1;
+  std::vector<double> s;
+  if (count_is(c, (long long)trn_n_sums(c), count, "the transport sums") || join_side(c, true) || trn_reduce(c, s)) return 1;
+  std::copy(s.begin(), s.end(), sums);
+  return 0;
+}
+int pop_transport_sums_set(pop_ctx *c, const double *sums, long long count) {
+  if (trn_requested(c, "pop_transport_sums_set")) return 1;
+  if (tavg_between_steps(c, "pop_transport_sums_set") || count_is(c, (long long)trn_n_sums(c), count, "the transport sums")) return 1;
+  if (trn_reset(c)) return 1;   // the vector replaces the sums of the interval
+  c->trn.set_sums.assign(sums, sums + count);
   return 0;
 }
 

@@ -63,11 +63,25 @@ struct MocState {
   bool requested = false; int stream = 0;           // pop_moc_request
   bool active = false;                              // requested and the stream is on: the one flag the site of a step tests
   std::vector<int> loc_list, loc_blist;             // the lists of aux.lists / aux.blists that belong to this rank's blocks
-  // device: the local lists (block = local index), their cells, the accumulators and the scratch field of k_moc_w
+  // device: the local lists (block = local index), their cells (moc_lists_upload: shared with the tracer transports), the
+  // accumulators and the scratch field of k_moc_w
+  bool lists_up = false;
   MocList *d_lists = nullptr, *d_blists = nullptr; int *d_cells = nullptr, *d_bcells = nullptr;
   double *ACC = nullptr, *BACC = nullptr, *WE = nullptr, *gather = nullptr;
   std::vector<double> set_sums;                     // pop_moc_sums_set: added last when the sums are read
   std::vector<double> snap; bool have_snap = false; // the normalised result pop_tavg_write took before it reset the stream
+};
+
+// ---- northward heat and salt transports (compute_tracer_transports; kernels_transport.hpp, launch_transport.hpp).  The latitude
+// grid, the regions and the uploaded cell lists are MocState's
+struct TrnState {
+  bool requested = false, want[2] = {false, false}; int stream = 0;   // pop_transport_request(stream, heat, salt)
+  bool active = false;                              // requested and the stream is on: the one flag the site of a step tests
+  int n_comp = 3;                                   // n_transport_comp (diags_on_lat_aux_grid.F90:886-889)
+  double *COL[2][TRN_NCOL] = {};                    // the per-column terms of the last accumulated step, (nxb, nyb, nblocks) per tracer
+  double *ACC = nullptr, *BACC = nullptr, *gather = nullptr;
+  std::vector<double> set_sums;                     // pop_transport_sums_set: added last when the sums are read
+  std::vector<double> snap[2]; bool have_snap = false;
 };
 
 struct pop_ctx {
@@ -219,6 +233,7 @@ struct pop_ctx {
   TavgState tavg;
   DiagState diag;
   MocState moc;
+  TrnState trn;
 };
 
 namespace {
@@ -280,6 +295,9 @@ StepParams step_params(const pop_ctx *c) {
 // time_weight of increment_tlast_ice (ice.F90:340-346) for the step pop_time_manager last set up: 0.5 on an averaging step (there are
 // no back_to_back steps here), otherwise 1
 double ice_time_weight(const pop_ctx *c) { return c->avg_ts ? 0.5 : 1.0; }
+// hflux_factor (pop_constants.F90:336) with the code defaults of rho_sw, cp_sw unless pop_init_ice gave others: the one factor of the
+// tavg entries, the global diagnostics and the heat transport
+double hflux_factor_of(const pop_ctx *c) { return c->ice.inited ? c->ice.k.hflux_factor : 1000.0 / ((4.1 / 3.996) * 3.996e7); }
 
 struct ScopedPhase {   // optional HIP-event timing of a phase on the launch stream
   pop_ctx *c; const char *name; hipEvent_t e0 = nullptr, e1 = nullptr;

@@ -570,6 +570,24 @@
          real (c_double), intent(out) :: moc(*)             ! [n][k][comp][reg], reg fastest
          integer (c_long_long), value :: count
       end function
+      ! ---- northward heat and salt transports (compute_tracer_transports)
+      integer (c_int) function pop_transport_request(ctx, stream, heat, salt) bind(C, name='pop_transport_request')
+         import :: c_int, c_ptr
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: stream, heat, salt
+      end function
+      integer (c_int) function pop_transport_info(ctx, n_lat, n_comp, n_reg, stream, heat, salt) bind(C, name='pop_transport_info')
+         import :: c_int, c_ptr
+         type (c_ptr), value :: ctx
+         integer (c_int), intent(out) :: n_lat, n_comp, n_reg, stream, heat, salt
+      end function
+      integer (c_int) function pop_transport_get(ctx, tracer, normalize, which, tr, count) bind(C, name='pop_transport_get')
+         import :: c_int, c_ptr, c_double, c_long_long
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: tracer, normalize, which
+         real (c_double), intent(out) :: tr(*)              ! [n][comp][reg], reg fastest
+         integer (c_long_long), value :: count
+      end function
    end interface
 
  contains

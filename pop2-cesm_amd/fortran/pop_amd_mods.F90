@@ -1069,12 +1069,15 @@
 ! there are two regions) before init_lat_aux_grid, which only checks them; init_moc_ts_transport_arrays builds the grid, the regions
 ! and the cell lists in the library and puts the MOC into tavg stream moc_stream.  The sums are taken inside the library's step, so
 ! compute_moc has no arguments: it fills TAVG_MOC_G from what the stream has accumulated (r4, as the reference stores it).
+! The same holds for the northward heat and salt transports: with n_heat_trans_requested / n_salt_trans_requested set before
+! init_moc_ts_transport_arrays they go into tavg stream transport_stream, and compute_tracer_transports(tracer_index) fills
+! TAVG_N_HEAT_TRANS_G / TAVG_N_SALT_TRANS_G; the reference's field arguments have no place, the library formed them step by step.
  module diags_on_lat_aux_grid
    use kinds_mod
    use pop_amd_c
    implicit none
    private
-   public :: init_lat_aux_grid, init_moc_ts_transport_arrays, compute_moc
+   public :: init_lat_aux_grid, init_moc_ts_transport_arrays, compute_moc, compute_tracer_transports
    real (r8), dimension(:), allocatable, public :: lat_aux_center, lat_aux_edge
    integer (int_kind), public :: n_lat_aux_grid = 0, n_transport_reg = 0, n_moc_comp = 0
    real (r4), dimension(:,:,:,:), allocatable, public :: TAVG_MOC_G          ! (n_lat_aux_grid+1, km+1, n_moc_comp, n_transport_reg)
@@ -1082,6 +1085,10 @@
    integer (int_kind), dimension(:,:), allocatable, target, public :: REGION_MASK_G   ! (nx_global, ny_global); unallocated: ocean cells
    integer (int_kind), public :: moc_stream = 1
    logical (log_kind), public :: moc_requested = .true.
+   integer (int_kind), public :: n_transport_comp = 0, transport_stream = 1
+   logical (log_kind), public :: n_heat_trans_requested = .false., n_salt_trans_requested = .false.
+   real (r4), dimension(:,:,:), allocatable, public :: TAVG_N_HEAT_TRANS_G, TAVG_N_SALT_TRANS_G   ! (n_lat_aux_grid+1, n_transport_comp, n_transport_reg)
+   real (r4), parameter, public :: undefined_nf = 9.9692099683868690e+36_r4
    public :: init_transports_nml
  contains
    subroutine init_transports_nml
@@ -1096,7 +1103,7 @@
    end subroutine
    subroutine init_moc_ts_transport_arrays(errorCode)
       integer (int_kind), intent(out) :: errorCode
-      integer (c_int) :: km1
+      integer (c_int) :: km1, n, nreg, ns, heat, salt
       if (transports%struct_bytes == 0) call pop_transports_nml_init(transports)
       if (allocated(REGION_MASK_G)) then
          errorCode = pop_init_transports(pop_ctx, transports, c_loc(REGION_MASK_G))
@@ -1110,6 +1117,13 @@
       call get_grid(lat_aux_edge, lat_aux_center, errorCode)
       if (errorCode /= 0) return
       if (moc_requested) errorCode = pop_moc_request(pop_ctx, moc_stream)
+      if (errorCode /= 0 .or. .not. (n_heat_trans_requested .or. n_salt_trans_requested)) return
+      errorCode = pop_transport_request(pop_ctx, transport_stream, merge(1, 0, n_heat_trans_requested), merge(1, 0, n_salt_trans_requested))
+      if (errorCode /= 0) return
+      errorCode = pop_transport_info(pop_ctx, n, n_transport_comp, nreg, ns, heat, salt)
+      if (errorCode /= 0) return
+      if (n_heat_trans_requested) allocate(TAVG_N_HEAT_TRANS_G(n_lat_aux_grid+1, n_transport_comp, n_transport_reg))   ! :899-911
+      if (n_salt_trans_requested) allocate(TAVG_N_SALT_TRANS_G(n_lat_aux_grid+1, n_transport_comp, n_transport_reg))
    end subroutine
    subroutine get_grid(edge, center, errorCode)
       real (r8), dimension(:), target, intent(out) :: edge, center
@@ -1131,6 +1145,30 @@
       do n = 1, n_lat_aux_grid+1
          TAVG_MOC_G(n,k,c,m) = real(W(m,c,k,n), r4)
       end do
+      end do
+      end do
+      end do
+   end subroutine
+   ! TAVG_N_HEAT_TRANS_G (tracer_index 1) or TAVG_N_SALT_TRANS_G (2) of the running interval of transport_stream, normalised by
+   ! its tavg_sum; a tracer that was not requested returns upon entry, as in the reference (:1367-1374)
+   subroutine compute_tracer_transports(tracer_index, errorCode)
+      integer (int_kind), intent(in) :: tracer_index
+      integer (int_kind), intent(out) :: errorCode
+      real (r8), allocatable :: W(:,:,:)
+      integer (int_kind) :: n, c, m
+      errorCode = 0
+      if (.not. ((tracer_index == 1 .and. n_heat_trans_requested) .or. (tracer_index == 2 .and. n_salt_trans_requested))) return
+      allocate(W(n_transport_reg, n_transport_comp, n_lat_aux_grid+1))     ! the library's order, region fastest
+      errorCode = pop_transport_get(pop_ctx, tracer_index, 1, 0, W, int(size(W), c_long_long))
+      if (errorCode /= 0) return
+      do m = 1, n_transport_reg
+      do c = 1, n_transport_comp
+      do n = 1, n_lat_aux_grid+1
+         if (tracer_index == 1) then
+            TAVG_N_HEAT_TRANS_G(n,c,m) = real(W(m,c,n), r4)
+         else
+            TAVG_N_SALT_TRANS_G(n,c,m) = real(W(m,c,n), r4)
+         endif
       end do
       end do
       end do
