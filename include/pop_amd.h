@@ -380,6 +380,105 @@ int pop_ice_export_reset(pop_ctx *ctx);
 /* tfreez (ice.F90:725-757) on count host values of salinity [g/g]: the host twin of the device function (one definition) */
 int pop_tfreez_host(pop_ctx *ctx, const double *S, double *TFRZ, long long count);
 
+/* ---- coupled surface forcing on the device (forcing_coupled.F90, drivers/mct/ocn_import_export.F90:171-239, the tail of
+ *      set_surface_forcing forcing.F90:379-437) through entry points of its own: a context that never makes the init call steps
+ *      exactly as before, and its caller keeps the surface forcing (pop_set_field of STF, SMF, SMFT, FW, TFW, SHF_QSW).  After the
+ *      call the library owns those six fields: pop_set_coupled_forcing forms them from the coupler's x2o fields once per coupling
+ *      interval, pop_set_surface_forcing -- the head of pop_step -- applies the per-step part.  The surface layer is the
+ *      variable-thickness one ('varthick'), as everywhere in this library.  DESIGN.md section 18 has the rules and what is not built. */
+/* ---- marginal-sea balance (ms_balance.F90): the excess or deficit of fresh water of every marginal sea (a region with a negative
+ *      number) is moved to or from a patch of the open ocean near it.  pop_init_ms_balance is init_ms_balance (:61-453); the balancing
+ *      itself (ms_balancing :461-646) runs inside pop_set_coupled_forcing when pop_coupled_nml.lms_balance = 1. */
+#define POP_MAX_MS 7              /* grid.F90:191 max_ms */
+#define POP_MS_WARN_TWO_REGIONS 1 /* the distribution points span two regions (ms_balance.F90:351-369) */
+#define POP_MS_WARN_MAX_POINTS 2  /* max_points reached: other points of the search area may have been left out (:340-345) */
+typedef struct pop_ms_region {    /* one record of the region_info_file (grid.F90:2709-2715) */
+  int number;                     /* REGION_MASK value; negative: a marginal sea */
+  char name[36];
+  double lat, lon, area;          /* marginal seas: centre of the search [degrees north / east, 0 .. 360] and the area asked for, in the units of DXT * DYT [cm^2] */
+} pop_ms_region;
+typedef struct pop_ms_balance_nml {
+  int struct_bytes;               /* sizeof(pop_ms_balance_nml) of the caller */
+  int num_regions;
+  int max_points;                 /* 0 = 5000 (ms_balance.F90:81) */
+  int reserved;                   /* 0 */
+  const pop_ms_region *regions;   /* num_regions records, read during the call only */
+} pop_ms_balance_nml;
+/* Once, after pop_create* (with several ranks on every rank, with the same arguments), before pop_init_coupled_forcing; a host-only
+ * context takes it too.  region_mask_global: REGION_MASK as (ny_global, nx_global), i fastest, as pop_init_transports takes it; when
+ * both calls are made the masks must be equal: the first call's array is the one copy kept, a second call with another mask is refused with the first differing cell.  For every marginal sea the expanding latitude / longitude box search
+ * over active-ocean points (duplicates, marginal-sea and land points rejected; it stops at max_points or when the accumulated area of
+ * the T cells reaches the area asked for), fracs = areas / area with the last fraction absorbing 1 - sum, MASK_FRAC scattered as a
+ * centre scalar.  Errors, not aborts: a marginal sea without a selected point; more than POP_MAX_MS seas; a second call; a call
+ * after pop_init_coupled_forcing or a step.  The monthly / annual depth bookkeeping and all printing are left out. */
+int pop_init_ms_balance(pop_ctx *ctx, const pop_ms_balance_nml *nml, const int *region_mask_global);
+/* marginal sea `sea` = 0 .. n_marginal_seas - 1 in region order (mask_index - 1): its REGION_MASK number, the number of distribution
+ * points, their area, POP_MS_WARN_* bits, and the transport [kg/s of fresh water] of the last pop_set_coupled_forcing (0 before one).
+ * Any pointer may be NULL.  Reading the transport waits for the device (the only call of the coupled forcing that does); with several
+ * ranks it is the same number on every rank. */
+int pop_ms_balance_info(pop_ctx *ctx, int sea, int *number, int *npts, double *area, int *warnings, double *transport);
+/* the distribution points of a sea, 1-based global (i, j) in selection order, and their fractions; count = npts */
+int pop_ms_balance_points(pop_ctx *ctx, int sea, int *ipts, int *jpts, double *fracs, long long count);
+
+typedef struct pop_coupled_nml {
+  int struct_bytes;             /* sizeof(pop_coupled_nml) of the caller */
+  int qsw_distrb_opt;           /* 0 'const', 1 '12hr' (any time stepping: the reference's restriction to avgfit / robert, forcing_coupled.F90:335-343, and its
+                                 * dttxcel / dtuxcel check :345-349 are not made -- the library has no accelerated time steps); 2 'cosz' is refused:
+                                 * compute_cosz needs shr_orb_mod of CIME, which is not part of POP */
+  int nsteps_per_interval;      /* steps per coupling interval, the length of qsw_12hr_factor; 0 = the time manager's own
+                                 * (steps_per_day, or full + half steps with avgfit) */
+  int lms_balance;              /* marginal-sea balancing (ms_balance.F90, forcing_coupled.F90:845-848): needs pop_init_ms_balance before this call and
+                                 * lfw_as_salt_flx (the reference balances in the virtual-salt-flux branch only) */
+  int shf_formulation;          /* 0 the coupled form; 1 'partially-coupled' is refused (set_combined_forcing is not built) */
+  int sfwf_formulation;         /* the same for the fresh-water flux */
+  int lestuary_on, lvsf_river, lebm_on;   /* 1 is refused each (MASK_ESTUARY is 0 in what is built) */
+  int luse_cpl_ifrac;           /* 1 is refused (OCN_WGT is not built) */
+  double latent_heat_vapor_mks; /* [J/kg]  0 = 2.501e6  (the coupled values of pop_constants.F90:283-290) */
+  double latent_heat_fusion_mks;/* [J/kg]  0 = 3.337e5 */
+  double sea_ice_salinity;      /* [psu]   0 = 4.0; read by the marginal-sea balance */
+  double rho_fw;                /* [g/cm^3] 0 = 1.0; likewise */
+} pop_coupled_nml;
+void pop_coupled_nml_init(pop_coupled_nml *nml);   /* struct_bytes = sizeof, everything else 0 ('const', the time manager's interval) */
+/* pop_init_coupled (forcing_coupled.F90:128-470) for what is built.  Once per context, after pop_create* and after pop_init_ice if
+ * that is used, before the first pop_time_manager / pop_step / pop_run_phase.  hflux_factor, salinity_factor = -ocn_ref_salinity *
+ * fwflux_factor, lfw_as_salt_flx, lactive_ice, tfreeze_option and the sea-ice salinity of the frazil-ice terms are the context's:
+ * pop_ice_nml's after pop_init_ice, its code defaults otherwise.  Forms ANGLET, COS_ANGLET = cos(ANGLET), SIN_ANGLET on the host
+ * (grid.F90:660-735; readable with pop_get_field on any context, before the call too) and qsw_12hr_factor from the context's
+ * time stepping (forcing_coupled.F90:358-408; pop_coupled_qsw_factor reads it back).  Works on a host-only context (no device
+ * fields).  Refused, each with its reason: a second call; a call after a step or a phase; a struct_bytes of another layout;
+ * everything the struct's comments call refused; nsteps_per_interval < 0; lms_balance without pop_init_ms_balance or without
+ * lfw_as_salt_flx.  pop_init_ice is refused after this call (the constants and branches above are taken from it here). */
+int pop_init_coupled_forcing(pop_ctx *ctx, const pop_coupled_nml *nml);
+/* qsw_12hr_factor(1 : nsteps_per_interval); count = nsteps_per_interval (pop_get_dim "cpl_nsteps_per_interval") */
+int pop_coupled_qsw_factor(pop_ctx *ctx, double *factor, long long count);
+/* the x2o fields of one coupling interval: host arrays in the local block layout of pop_set_field, (nx_block, ny_block, nblocks);
+ * only the physical cells are read for their values (ghost cells are filled by the halo update).  NULL = zeros.  MKS units, as the
+ * coupler sends them: taux, tauy [N/m^2] (true zonal / meridional); snow, rain, evap, meltw, rofl, rofi, salt [kg/m^2/s]; swnet,
+ * sen, lwup, lwdn, melth [W/m^2]; ifrac [fraction]; pslv [Pa]; duu10n [m^2/s^2]. */
+typedef struct pop_x2o {
+  int struct_bytes;             /* sizeof(pop_x2o) of the caller */
+  int reserved;                 /* 0 */
+  const double *taux, *tauy, *snow, *rain, *evap, *meltw, *rofl, *rofi, *salt, *swnet, *sen, *lwup, *lwdn, *melth, *ifrac, *pslv, *duu10n;
+} pop_x2o;
+/* ocn_import (the fields above), rotate_wind_stress, update_ghost_cells_coupler_fluxes and pop_set_coupled_forcing
+ * (forcing_coupled.F90:677-945): one staged upload of the given fields on the context's stream, then k_cpl_import, the halo updates
+ * of the imported fields (SMFT as centre-located vectors; three fused batches of at most eight fields, field by field on a tripole grid),
+ * k_cpl_combine, and with lms_balance the marginal-sea balance.  Leaves SMFT, SMF, STF(1), SHF_QSW and, with
+ * lfw_as_salt_flx = 0, FW and TFW, with lfw_as_salt_flx = 1 STF(2); the imported fields and SHF_QSW_RAW, SHF_COMP_QSW,
+ * SFWF_COMP_CPL, TFW_COMP_CPL for pop_get_field.  Resets the interval's step count to 0.  count = nx_block * ny_block * nblocks.
+ * The arrays are read during the call only.  Between steps only (refused between pop_time_manager and pop_step_tail).  On one
+ * rank nothing in the call waits for the device except the reuse of the staging buffer by a second call. */
+int pop_set_coupled_forcing(pop_ctx *ctx, const pop_x2o *x2o, long long count);
+/* the per-step tail of set_surface_forcing (forcing.F90:379-437): SHF_QSW = qsw_12hr_factor(index_qsw) * SHF_COMP_QSW with index_qsw =
+ * mod(steps of this interval, nsteps_per_interval) + 1; with lfw_as_salt_flx = 0 and ice formation on (pop_init_ice, ice_freq_opt
+ * 'coupled') FW = SFWF_COMP_CPL + FW_FREEZE, TFW(1) = TFW_COMP_CPL(1) + FW_FREEZE * tfreez(S(cur)), TFW(2) = TFW_COMP_CPL(2) +
+ * FW_FREEZE * salice.  pop_step calls it at its head, before pop_time_manager (step_mod.F90:231); a caller that owns the sequence
+ * calls it there.  pop_time_manager advances the interval's step count.  Returns 0 and does nothing while the coupled forcing is not
+ * initialised or no pop_set_coupled_forcing has been made. */
+int pop_set_surface_forcing(pop_ctx *ctx);
+/* out4 = {initialised, qsw_distrb_opt, nsteps_per_interval, steps of this interval so far}; n_marginal_seas: of pop_init_ms_balance */
+int pop_coupled_info(pop_ctx *ctx, int *out4, int *n_marginal_seas);
+
 /* ---- blocks.F90:43-63 / get_block (blocks.F90:282-320) ---------------------- */
 int pop_get_dim(const pop_ctx *ctx, const char *name);         /* nx_block, ny_block, km, nt,
                                                                   nblocks (local), nblocks_tot,

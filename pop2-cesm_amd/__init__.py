@@ -92,6 +92,10 @@ def lib():
         "pop_init_iage": (ci, [vp, ci]),
         "pop_ice_nml_init": (None, [vp]), "pop_init_ice": (ci, [vp, vp]), "pop_ice_formation": (ci, [vp, ci]),
         "pop_ice_flx_to_coupler": (ci, [vp]), "pop_ice_export_reset": (ci, [vp]), "pop_tfreez_host": (ci, [vp, pd, pd, ll]),
+        "pop_coupled_nml_init": (None, [vp]), "pop_init_coupled_forcing": (ci, [vp, vp]), "pop_coupled_qsw_factor": (ci, [vp, pd, ll]),
+        "pop_init_ms_balance": (ci, [vp, vp, pi]), "pop_ms_balance_info": (ci, [vp, ci, pi, pi, pd, pi, pd]),
+        "pop_ms_balance_points": (ci, [vp, ci, pi, pi, pd, ll]),
+        "pop_set_coupled_forcing": (ci, [vp, vp, ll]), "pop_set_surface_forcing": (ci, [vp]), "pop_coupled_info": (ci, [vp, pi, pi]),
         "pop_tavg_request": (ci, [vp, ci, cs]), "pop_tavg_set_on": (ci, [vp, ci, ci]), "pop_tavg_info": (ci, [vp, cs, pi, pi, pi, pi]),
         "pop_tavg_sums": (ci, [vp, ci, pd, pd]), "pop_tavg_get": (ci, [vp, cs, ci, pd, ll]), "pop_tavg_device_ptr": (vp, [vp, cs]),
         "pop_tavg_reset": (ci, [vp, ci]), "pop_tavg_write": (ci, [vp, ci, cs, ci]), "pop_tavg_read": (ci, [vp, ci, cs]),
@@ -298,6 +302,52 @@ def ice_nml(**kw):
             v = TFREEZE_OPTION[v]
         if not hasattr(n, k):
             raise AttributeError("pop_ice_nml has no field %r" % k)
+        setattr(n, k, v)
+    return n
+
+
+class PopCoupledNml(C.Structure):
+    """include/pop_amd.h pop_coupled_nml"""
+    _fields_ = [(n, C.c_int) for n in ("struct_bytes", "qsw_distrb_opt", "nsteps_per_interval", "lms_balance", "shf_formulation",
+                                       "sfwf_formulation", "lestuary_on", "lvsf_river", "lebm_on", "luse_cpl_ifrac")] + \
+        [(n, C.c_double) for n in ("latent_heat_vapor_mks", "latent_heat_fusion_mks", "sea_ice_salinity", "rho_fw")]
+
+
+class PopMsRegion(C.Structure):
+    """include/pop_amd.h pop_ms_region"""
+    _fields_ = [("number", C.c_int), ("name", C.c_char * 36), ("lat", C.c_double), ("lon", C.c_double), ("area", C.c_double)]
+
+
+class PopMsBalanceNml(C.Structure):
+    """include/pop_amd.h pop_ms_balance_nml"""
+    _fields_ = [(n, C.c_int) for n in ("struct_bytes", "num_regions", "max_points", "reserved")] + [("regions", C.POINTER(PopMsRegion))]
+
+
+MS_WARN_TWO_REGIONS, MS_WARN_MAX_POINTS = 1, 2
+QSW_DISTRB_OPT = {"const": 0, "12hr": 1, "cosz": 2}
+FORMULATION = {"coupled": 0, "partially-coupled": 1}
+X2O_FIELDS = ("taux", "tauy", "snow", "rain", "evap", "meltw", "rofl", "rofi", "salt", "swnet", "sen", "lwup", "lwdn", "melth", "ifrac",
+              "pslv", "duu10n")
+
+
+class PopX2o(C.Structure):
+    """include/pop_amd.h pop_x2o"""
+    _fields_ = [("struct_bytes", C.c_int), ("reserved", C.c_int)] + [(n, C.POINTER(C.c_double)) for n in X2O_FIELDS]
+
+
+def coupled_nml(**kw):
+    """pop_coupled_nml with pop_coupled_nml_init's values ('const', the time manager's interval, the coupled constants), then the
+    keywords: the members by name; qsw_distrb_opt may also be 'const' | '12hr' | 'cosz', shf_formulation / sfwf_formulation
+    'coupled' | 'partially-coupled'."""
+    n = PopCoupledNml()
+    lib().pop_coupled_nml_init(C.byref(n))
+    for k, v in kw.items():
+        if k == "qsw_distrb_opt" and isinstance(v, str):
+            v = QSW_DISTRB_OPT[v]
+        if k in ("shf_formulation", "sfwf_formulation") and isinstance(v, str):
+            v = FORMULATION[v]
+        if not hasattr(n, k):
+            raise AttributeError("pop_coupled_nml has no field %r" % k)
         setattr(n, k, v)
     return n
 
@@ -522,6 +572,82 @@ class PopModel:
         P = C.POINTER(C.c_double)
         self._chk(self.L.pop_tfreez_host(self.h, a.ctypes.data_as(P), out.ctypes.data_as(P), a.size))
         return out
+
+    # ---- coupled surface forcing (forcing_coupled.F90; include/pop_amd.h pop_init_coupled_forcing ...)
+    def init_coupled_forcing(self, **nml):
+        """pop_init_coupled (forcing_coupled.F90) for what is built: keywords as coupled_nml().  Once, after init_ice if that is used,
+        before the first step or phase.  Afterwards the library owns STF, SMF, SMFT, FW, TFW and SHF_QSW: set_coupled_forcing forms
+        them once per coupling interval, step() applies the per-step part.  Returns the pop_coupled_nml that was passed."""
+        n = coupled_nml(**nml)
+        self._chk(self.L.pop_init_coupled_forcing(self.h, C.byref(n)))
+        return n
+
+    def init_ms_balance(self, regions, region_mask, max_points=0, struct_bytes=None):
+        """init_ms_balance (ms_balance.F90:61-453): regions = the records of the region_info_file as (number, name, lat, lon, area)
+        tuples, a negative number marking a marginal sea; region_mask = REGION_MASK as a global (ny_global, nx_global) integer
+        array.  Once, before init_coupled_forcing(lms_balance=1); on every rank."""
+        recs = (PopMsRegion * max(len(regions), 1))()
+        for r, (number, name, lat, lon, area) in zip(recs, regions):
+            r.number, r.name, r.lat, r.lon, r.area = int(number), name.encode(), float(lat), float(lon), float(area)
+        n = PopMsBalanceNml()
+        n.struct_bytes = C.sizeof(PopMsBalanceNml) if struct_bytes is None else struct_bytes
+        n.num_regions, n.max_points, n.regions = len(regions), int(max_points), recs
+        rm = np.ascontiguousarray(region_mask, dtype=np.int32)
+        if rm.shape != (self.cfg.ny_global, self.cfg.nx_global):
+            raise ValueError("region_mask: shape %s, expected (ny_global, nx_global)" % (rm.shape,))
+        self._chk(self.L.pop_init_ms_balance(self.h, C.byref(n), rm.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def ms_balance_info(self, transports=True):
+        """one dict per marginal sea in region order: number, npts, area, warnings (MS_WARN_* bits), ipts, jpts (1-based global), fracs
+        and, with transports (the one call that waits for the device), the transport [kg/s] of the last set_coupled_forcing"""
+        out = []
+        for sea in range(self.coupled_info()["n_marginal_seas"]):
+            num, npts, warn, area, tr = C.c_int(), C.c_int(), C.c_int(), C.c_double(), C.c_double()
+            self._chk(self.L.pop_ms_balance_info(self.h, sea, C.byref(num), C.byref(npts), C.byref(area), C.byref(warn),
+                                                 C.byref(tr) if transports else None))
+            ip, jp, fr = np.empty(npts.value, dtype=np.int32), np.empty(npts.value, dtype=np.int32), np.empty(npts.value, dtype=np.float64)
+            self._chk(self.L.pop_ms_balance_points(self.h, sea, ip.ctypes.data_as(C.POINTER(C.c_int)), jp.ctypes.data_as(C.POINTER(C.c_int)),
+                                                   fr.ctypes.data_as(C.POINTER(C.c_double)), npts.value))
+            out.append({"number": num.value, "npts": npts.value, "area": area.value, "warnings": warn.value, "ipts": ip, "jpts": jp,
+                        "fracs": fr, "transport": tr.value if transports else None})
+        return out
+
+    def set_coupled_forcing(self, **fields):
+        """ocn_import + rotate_wind_stress + pop_set_coupled_forcing on the device: keywords are the x2o fields (X2O_FIELDS: taux, tauy,
+        snow, rain, evap, meltw, rofl, rofi, salt, swnet, sen, lwup, lwdn, melth, ifrac, pslv, duu10n) on the local blocks,
+        (nblocks, ny_block, nx_block), in the coupler's MKS units; a field left out is zero.  Resets the interval's step count."""
+        x, keep = PopX2o(), []
+        x.struct_bytes = C.sizeof(PopX2o)
+        shape = (self.nblocks, self.nyb, self.nxb)
+        for k, v in fields.items():
+            if k not in X2O_FIELDS:
+                raise AttributeError("pop_x2o has no field %r" % k)
+            if v is None:
+                continue
+            a = np.ascontiguousarray(v, dtype=np.float64)
+            if a.shape != shape:
+                raise ValueError("x2o field %s: shape %s, expected (nblocks, ny_block, nx_block) = %s" % (k, a.shape, shape))
+            keep.append(a)
+            setattr(x, k, a.ctypes.data_as(C.POINTER(C.c_double)))
+        self._chk(self.L.pop_set_coupled_forcing(self.h, C.byref(x), self.nblocks * self.nyb * self.nxb))
+        del keep
+
+    def set_surface_forcing(self):
+        """the per-step tail of set_surface_forcing (forcing.F90:379-437); step() calls it at its head, a caller that owns the
+        sequence calls it before time_manager()"""
+        self._chk(self.L.pop_set_surface_forcing(self.h))
+
+    def coupled_info(self):
+        """dict(initialised, qsw_distrb_opt, nsteps_per_interval, nsteps_this_interval, n_marginal_seas, qsw_12hr_factor)"""
+        out, nms = (C.c_int * 4)(), C.c_int()
+        self._chk(self.L.pop_coupled_info(self.h, out, C.byref(nms)))
+        inf = {"initialised": bool(out[0]), "qsw_distrb_opt": {v: k for k, v in QSW_DISTRB_OPT.items()}[out[1]],
+               "nsteps_per_interval": out[2], "nsteps_this_interval": out[3], "n_marginal_seas": nms.value, "qsw_12hr_factor": None}
+        if out[0]:
+            f = np.empty(out[2], dtype=np.float64)
+            self._chk(self.L.pop_coupled_qsw_factor(self.h, f.ctypes.data_as(C.POINTER(C.c_double)), f.size))
+            inf["qsw_12hr_factor"] = f
+        return inf
 
     # ---- time-averaged output (tavg.F90; include/pop_amd.h pop_tavg_*)
     TAVG_METHOD = {1: "avg", 2: "min", 3: "max", 4: "qflux", 5: "constant"}

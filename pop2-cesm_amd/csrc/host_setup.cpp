@@ -283,6 +283,22 @@ double host_global_sum_loc(const HostModel &h, const double *a, const double *ma
   return g;
 }
 
+// ANGLE of horiz_grid_file into an all-blocks array of zeros, scattered as an NE-corner field (grid.F90:1524-1525; scatter_global sets
+// no sign beyond a tripole fold).  Without the record (the internal lat-lon grid) the array stays 0
+static void scatter_angle(const HostModel &h, std::vector<double> &ANG) {
+  if (!(h.gin && h.gin->ANGLE)) return;
+  const int nxb = h.nxb, nyb = h.nyb, nxg = h.c.nx_global, nyg = h.c.ny_global;
+  for (int b = 0; b < h.nblocks_tot; ++b) {
+    const BlockInfo &B = h.all_blocks[b];
+    for (int j = 0; j < nyb; ++j) for (int i = 0; i < nxb; ++i) {
+      const int ig = B.i_glob[i], jg = B.j_glob[j];
+      if (ig == 0 || jg == 0) continue;
+      int is = ig, js = jg;
+      if (jg < 0) { js = nyg + (jg + nyg); is = nxg - ig; if (is < 1) is += nxg; if (is > nxg) is -= nxg; }
+      ANG[b * h.n2 + (size_t)j * nxb + i] = h.gin->ANGLE[(size_t)(js - 1) * nxg + (is - 1)];
+    }
+  }
+}
 // ---- anisotropic viscosity (hmix_momentum = 3): the time-independent part of init_aniso (hmix_aniso.F90:372-533) and
 // compute_ccsm_var_viscosity (:1069-1296) on every block, ghost cells included, after the grid and dtu are set
 static void aniso_setup(HostModel &h) {
@@ -322,18 +338,7 @@ static void aniso_setup(HostModel &h) {
   // ANGLE of horiz_grid_file, scattered as an NE-corner field (grid.F90:1524-1525; scatter_global sets no sign beyond a tripole fold);
   // 0 on the internal lat-lon grid
   auto &ANG = newf("ANGLE");
-  if (h.gin && h.gin->ANGLE) {
-    for (int b = 0; b < NB; ++b) {
-      const BlockInfo &B = h.all_blocks[b];
-      for (int j = 0; j < nyb; ++j) for (int i = 0; i < nxb; ++i) {
-        const int ig = B.i_glob[i], jg = B.j_glob[j];
-        if (ig == 0 || jg == 0) continue;
-        int is = ig, js = jg;
-        if (jg < 0) { js = nyg + (jg + nyg); is = nxg - ig; if (is < 1) is += nxg; if (is > nxg) is -= nxg; }
-        ANG[idx(b, i, j)] = h.gin->ANGLE[(size_t)(js - 1) * nxg + (is - 1)];
-      }
-    }
-  }
+  scatter_angle(h, ANG);
   if (!c.lvariable_hmix_aniso) return;
   // compute_ccsm_var_viscosity :1153-1291 ('ccsm-internal'); 0 = the code default (:211-217)
   const double v1 = c.vconst_1 != 0.0 ? c.vconst_1 : 1.e7, v2 = c.vconst_2 != 0.0 ? c.vconst_2 : 24.5, v3 = c.vconst_3 != 0.0 ? c.vconst_3 : 0.2;
@@ -980,6 +985,8 @@ int host_build(HostModel &h) {
     }
   }
   if (c.hmix_momentum == 3) aniso_setup(h);
+  // the caller's ANGLE outlives the call for ANGLET (host_forcing.cpp host_anglet_build); empty: zeros
+  if (h.gin && h.gin->ANGLE) { h.angle.assign(A2, 0.0); scatter_angle(h, h.angle); }
   // ---------------- P-CSI preprocessing (POP_SolversPrep) ----------------
   if (use_evp(c) || c.solver_choice == 3) {   // POP_SolversPrep (POP_SolversMod.F90:181-320): EVP first, then Lanczos
     const std::vector<double> C0 = host_center_init(h);

@@ -37,12 +37,23 @@ int tidal_nml_resolve(pop_tidal_nml &n, std::string &err) {
 // row copied from the row north of it, 0 <= TLON < 2 pi, then the halo update.  Shared by pop_init_tidal_mixing (region boxes) and
 // pop_init_kpp_bckgrnd (Banda Sea boxes); nothing else needs it.
 void host_tlon_build(const HostModel &h, std::vector<double> &tlon) {
+  const size_t n2 = h.n2;
+  std::vector<double> TLON;
+  host_tlon_all(h, TLON);
+  tlon.assign(n2 * h.nblocks, 0.0);
+  for (int lb = 0; lb < h.nblocks; ++lb) {
+    const size_t g0 = (size_t)(h.local_ids[lb] - 1) * n2;
+    std::copy(TLON.begin() + g0, TLON.begin() + g0 + n2, tlon.begin() + (size_t)lb * n2);
+  }
+}
+// the same on ALL blocks of the decomposition
+void host_tlon_all(const HostModel &h, std::vector<double> &TLON) {
   const int nxb = h.nxb, nyb = h.nyb, NB = h.nblocks_tot;
   const size_t n2 = h.n2;
   const double pi = 4.0 * std::atan(1.0), pi2 = 2.0 * pi;
   const std::vector<double> &ULAT = h.f2.at("ULAT"), &ULON = h.f2.at("ULON");
   auto idx = [&](int b, int i, int j) { return (size_t)b * n2 + (size_t)j * nxb + i; };
-  std::vector<double> TLON(n2 * NB, 0.0);
+  TLON.assign(n2 * NB, 0.0);
   for (int b = 0; b < NB; ++b) {
     const BlockInfo &B = h.all_blocks[b];
     for (int j = 1; j < nyb; ++j) for (int i = 1; i < nxb; ++i) {
@@ -64,11 +75,6 @@ void host_tlon_build(const HostModel &h, std::vector<double> &tlon) {
     }
   }
   host_halo_r8_loc(h, TLON.data(), 1, 0.0, 0, 0);
-  tlon.assign(n2 * h.nblocks, 0.0);
-  for (int lb = 0; lb < h.nblocks; ++lb) {
-    const size_t g0 = (size_t)(h.local_ids[lb] - 1) * n2;
-    std::copy(TLON.begin() + g0, TLON.begin() + g0 + n2, tlon.begin() + (size_t)lb * n2);
-  }
 }
 
 // flux: W/m^2 on the local blocks, ghost cells already updated; tlon: host_tlon_build

@@ -35,7 +35,8 @@ enum TavgExpr {
   TX_M_DIVC,       // where KMT > 0: x/c, else 0             (columns only)
   TX_M_SUMDIVC,    // where KMT > 0: (x + y)/c, else 0
   TX_M_MULCC,      // where KMT > 0: x*c*c2, else 0
-  TX_RHO_VINT      // x*thickness of the T cell where k <= KMT, else 0 (baroclinic.F90:2392-2414; columns only)
+  TX_RHO_VINT,     // x*thickness of the T cell where k <= KMT, else 0 (baroclinic.F90:2392-2414; columns only)
+  TX_MULCC         // x*c*c2 on every cell (TFW_S, forcing.F90:579)
 };
 
 // cell (q, k, b) of a source: p[((long long)b*nz + k + k0)*n2 + q]; nz = 1: a 2-D field
@@ -71,6 +72,7 @@ __device__ __forceinline__ double tavg_value(int expr, double x, double y, doubl
     case TX_M_DIVC: return ocean ? x / c : 0.0;
     case TX_M_SUMDIVC: return ocean ? (x + y) / c : 0.0;
     case TX_M_MULCC: return ocean ? x * c * c2 : 0.0;
+    case TX_MULCC: return x * c * c2;
     case TX_SQR: return x * x;
     case TX_XY: return x * y;
     case TX_KE: return 0.5 * (x * x + y * y);

@@ -23,9 +23,11 @@ enum TavgSid {
   SID_HU, SID_UB, SID_VB,
   SID_HBLT, SID_HMXL, SID_HMXL_DR, SID_VDC_T, SID_VDC_S, SID_VVC, SID_KPPS_T, SID_KPPS_S, SID_KVMIX, SID_KVMIX_M,
   SID_UISOP, SID_VISOP, SID_WISOP, SID_USUBM, SID_VSUBM, SID_WSUBM,
-  SID_QFLUX
+  SID_QFLUX,
+  SID_TFW1, SID_TFW2,
+  SID_CPL0                                  // + f: imported field f of the coupled forcing (kernels_forcing.hpp CplField)
 };
-enum TavgNeed { TN_NONE = 0, TN_KPP, TN_MLD, TN_TIDAL, TN_GM_BOLUS, TN_SUBM_DIAG, TN_ICE };
+enum TavgNeed { TN_NONE = 0, TN_KPP, TN_MLD, TN_TIDAL, TN_GM_BOLUS, TN_SUBM_DIAG, TN_ICE, TN_CPL };
 
 struct TavgAvail {
   std::string name;
@@ -42,7 +44,7 @@ const char *const tavg_left_out[] = {
   "UPV", "VPV", "UQ", "VQ", "UTE_POS", "UTE_NEG", "VTN_POS", "VTN_NEG", "WTK_POS", "WTK_NEG", "UEU", "VNU", "UEV", "VNV", "WTU", "WTV",
   "ADVU", "ADVV", "GRADX", "GRADY", "HDIFFU", "HDIFFV", "VDIFFU", "VDIFFV", "UDP",
   "HDIFT", "HDIFS", "DIA_IMPVF_TEMP", "DIA_IMPVF_SALT", "RF_TEND_TEMP", "RF_TEND_SALT", "RESID_T", "RESID_S",
-  "TEMP_27", "TEMP_43", "BSF", "N_HEAT", "N_SALT", "U2_2", "V2_2", "VDC_BCK", "VVC_BCK", "TFW_T", "TFW_S", "SFWF_WRST",
+  "TEMP_27", "TEMP_43", "BSF", "N_HEAT", "N_SALT", "U2_2", "V2_2", "VDC_BCK", "VVC_BCK", "SFWF_WRST",
   "TEMP_z_t_150m", "SALT_z_t_150m", "UVEL_z_t_150m", "VVEL_z_t_150m"};
 
 // every entry this configuration knows.  Host logic only: a host-only context answers pop_tavg_info from it too
@@ -76,6 +78,15 @@ std::vector<TavgAvail> tavg_avail(const pop_ctx *c) {
   f2("SSH", TS_FORCING, TX_DIVC, SID_PS, -1, TAVG_AVG, TN_NONE, GRAV); f2("SSH_2", TS_FORCING, TX_DIVC, SID_PS, -1, TAVG_AVG, TN_NONE, GRAV);
   f2("SSH2", TS_FORCING, TX_DIVC_SQR, SID_PS, -1, TAVG_AVG, TN_NONE, GRAV);
   f2("H3", TS_FORCING, TX_DIVC_SQSUM, SID_GX, SID_GY, TAVG_AVG, TN_NONE, GRAV);
+  // forcing.F90:578-580 and tavg_coupled_forcing (forcing_coupled.F90:1111-1122): after pop_init_coupled_forcing
+  f2("TFW_T", TS_FORCING, TX_DIVC, SID_TFW1, -1, TAVG_AVG, TN_CPL, hflux_factor);
+  f2("TFW_S", TS_FORCING, TX_MULCC, SID_TFW2, -1, TAVG_AVG, TN_CPL, I.inited ? I.nml.rho_sw : 4.1 / 3.996, 10.0);
+  f2("U10_SQR", TS_FORCING, TX_X, SID_CPL0 + CF_U10, -1, TAVG_AVG, TN_CPL);
+  {
+    const std::pair<const char *, int> cpl[] = {{"EVAP_F", CF_EVAP}, {"PREC_F", CF_PREC}, {"SNOW_F", CF_SNOW}, {"MELT_F", CF_MELT}, {"ROFF_F", CF_ROFF}, {"IOFF_F", CF_IOFF},
+                                                {"SALT_F", CF_SALT}, {"SENH_F", CF_SENH}, {"LWUP_F", CF_LWUP}, {"LWDN_F", CF_LWDN}, {"MELTH_F", CF_MELTH}, {"IFRAC", CF_IFRAC}};
+    for (const auto &e : cpl) f2(e.first, TS_FORCING, TX_X, SID_CPL0 + e.second, -1, TAVG_AVG, TN_CPL);
+  }
   // STATE
   f3("UVEL", TS_STATE, TX_X, SID_U); f3("UVEL_2", TS_STATE, TX_X, SID_U); f3("VVEL", TS_STATE, TX_X, SID_V); f3("VVEL_2", TS_STATE, TX_X, SID_V);
   f3("UVEL2", TS_STATE, TX_SQR, SID_U); f3("VVEL2", TS_STATE, TX_SQR, SID_V);
@@ -132,6 +143,7 @@ std::string tavg_missing(const pop_ctx *c, int need) {
     case TN_GM_BOLUS: return (cf.hmix_tracer == 3 && cf.gm_diag_bolus) ? "" : "hmix_tracer = 3 (gm) with gm_diag_bolus = 1";
     case TN_SUBM_DIAG: return (cf.struct_version >= 7 && cf.lsubmesoscale_mixing && cf.submeso_diag) ? "" : "lsubmesoscale_mixing with submeso_diag = 1";
     case TN_ICE: return c->ice.inited ? "" : "pop_init_ice";
+    case TN_CPL: return c->cpl.inited ? "" : "pop_init_coupled_forcing";
     default: return "";
   }
 }
@@ -142,6 +154,7 @@ TavgSrc tavg_src(pop_ctx *c, int sid) {
   auto s2 = [&](const double *p) { return TavgSrc{p, 1, 0}; };
   auto vd = [&](const double *p) { return TavgSrc{p, km + 2, 1}; };   // VDC is stored (0:km+1): reference level kk at slot kk
   if (sid >= SID_TR0 && sid < SID_TR0 + MAXNT) return s3(c->TR[sid - SID_TR0][cu]);
+  if (sid >= SID_CPL0 && sid < SID_CPL0 + CF_NF) return s2(c->cpl.F[sid - SID_CPL0]);
   switch (sid) {
     case SID_U: return s3(c->U[cu]);
     case SID_V: return s3(c->V[cu]);
@@ -178,6 +191,8 @@ TavgSrc tavg_src(pop_ctx *c, int sid) {
     case SID_VSUBM: return s3(c->subm.VS);
     case SID_WSUBM: return s3(c->subm.WS);
     case SID_QFLUX: return s2(c->ice.QFLUX);
+    case SID_TFW1: return s2(c->TFW[0]);
+    case SID_TFW2: return s2(c->TFW[1]);
   }
   return TavgSrc{nullptr, 1, 0};
 }
@@ -198,6 +213,15 @@ int tavg_build(pop_ctx *c) {
       sids[t.nsrc] = sid;
       return t.nsrc++;
     };
+    auto fits = [&](const TavgTable &t, const int *sids, const TavgEntry &e) {   // would the entry's sources find a slot?
+      int fresh = 0;
+      for (int sid : {e.a, e.b}) {
+        bool have = sid < 0;
+        for (int i = 0; i < t.nsrc && !have; ++i) have = sids[i] == sid;
+        fresh += have ? 0 : 1;
+      }
+      return t.nsrc + fresh <= TAVG_MAX_SRC && t.n < TAVG_MAX_FIELDS;
+    };
     auto put = [&](TavgTable &t, int *sids, const TavgEntry &e) -> int {
       const int a = slot(t, sids, e.a), b = slot(t, sids, e.b);
       if (a < 0 || b < 0 || t.n == TAVG_MAX_FIELDS) { c->err = "tavg: too many sources or entries at one site (" + e.name + ")"; return 1; }
@@ -212,6 +236,11 @@ int tavg_build(pop_ctx *c) {
         if (e.site != s || !T.on[e.stream]) continue;
         const int kind = e.cells ? 0 : (e.vint ? 2 : 1);
         if (kind != pass) continue;
+        if (pass == 1 && !fits(S.cols, S.sid_cols, e)) {   // the second launch of the site
+          if (put(S.cols_more, S.sid_cols_more, e)) return 1;
+          S.cols_more.n2d = S.cols_more.n; S.cols_more.kmax = 0;
+          continue;
+        }
         if (pass == 0 ? put(S.cells, S.sid_cells, e) : put(S.cols, S.sid_cols, e)) return 1;
         if (pass == 1) { S.cols.n2d = S.cols.n; S.cols.kmax = 0; }
         if (e.expr == TX_RHO_VINT) S.vint_psurf = true;
@@ -249,6 +278,15 @@ int tavg_site(pop_ctx *c, int site) {
     t.dtavg = T.dtavg;
     if (site == TS_QFLUX) for (int e = 0; e < t.n; ++e) t.d[e].cst = c->ice.tlast_ice;   // const = tlast_ice (step_mod.F90:848-849)
     const TavgVint w{S.vint_psurf ? c->PS[c->curt] : nullptr, GRAV};
+    with_flags([&](auto PBC) {
+      hipLaunchKernelGGL(k_tavg_columns<PBC.value>, dim3((c->g.n2 + 255) / 256, c->g.nblocks), dim3(256), 0, c->stream, c->g, t, w);
+    }, c->g.pbc != 0);
+  }
+  if (S.cols_more.n) {
+    TavgTable &t = S.cols_more;
+    for (int i = 0; i < t.nsrc; ++i) { t.src[i] = tavg_src(c, S.sid_cols_more[i]); if (!t.src[i].p) { c->err = "tavg: a source of the site does not exist"; return 1; } }
+    t.dtavg = T.dtavg;
+    const TavgVint w{nullptr, GRAV};
     with_flags([&](auto PBC) {
       hipLaunchKernelGGL(k_tavg_columns<PBC.value>, dim3((c->g.n2 + 255) / 256, c->g.nblocks), dim3(256), 0, c->stream, c->g, t, w);
     }, c->g.pbc != 0);

@@ -26,6 +26,7 @@
 #include "kernels_diag.hpp"
 #include "kernels_moc.hpp"
 #include "kernels_transport.hpp"
+#include "kernels_forcing.hpp"
 #include "rccl_transport.hpp"
 
 using namespace pop;
@@ -37,6 +38,7 @@ using namespace pop;
 #include "launch_transport.hpp"
 #include "launch_tavg.hpp"
 #include "launch_diag.hpp"
+#include "launch_forcing.hpp"
 
 namespace {
 
@@ -124,6 +126,7 @@ int resolve(pop_ctx *c, const std::string &name, int tl, int n, double **ptr, lo
   if (name == "AQICE") return ok(c->ice.AQICE, a2);
   if (name == "QFLUX") return ok(c->ice.QFLUX, a2);
   if (name == "FW_FREEZE") return ok(c->ice.FWF, a2);
+  if (double *p = cpl_field(c, name, n)) return ok(p, a2);   // pop_init_coupled_forcing: the imported fields and the interval's copies
   if (name == "SMF") return ok(c->d2[n == 0 ? "SMF1" : "SMF2"], a2);
   if (name == "SMFT") return ok(c->d2[n == 0 ? "SMFT1" : "SMFT2"], a2);
   auto it = c->d2.find(name);
@@ -889,6 +892,11 @@ int pop_destroy(pop_ctx *c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     for (double *p : {c->diag.h_pre, c->diag.h_after, c->diag.h_cfl}) if (p) hipHostFree(p);
   }
+  if (c->cpl.h_raw) {   // the upload of an import may still be in flight
+    if (c->stream) hipStreamSynchronize(c->stream);
+    hipHostFree(c->cpl.h_raw);
+  }
+  if (c->cpl.ev_up) hipEventDestroy(c->cpl.ev_up);
   if (c->ev_fork) hipEventDestroy(c->ev_fork);
   if (c->ev_d2t) hipEventDestroy(c->ev_d2t);
   if (c->ev_d2u) hipEventDestroy(c->ev_d2u);
@@ -924,6 +932,7 @@ int pop_get_dim(const pop_ctx *c, const char *name) {
   if (n == "nt") return c->h.nt;
   if (n == "nblocks") return c->h.nblocks;
   if (n == "nblocks_tot") return c->h.nblocks_tot;
+  if (n == "cpl_nsteps_per_interval") return c->cpl.inited ? c->cpl.nml.nsteps_per_interval : 0;   // pop_init_coupled_forcing: the length of qsw_12hr_factor
   if (n == "nblocks_x") return c->h.nbx;
   if (n == "nblocks_y") return c->h.nby;
   if (n == "nghost") return NGHOST;
@@ -1047,6 +1056,16 @@ int pop_get_field(pop_ctx *c, const char *name, int tl, int n, double *host, lon
   if (nm == "BCKGRND_VDC" || nm == "BCKGRND_VVC" || (nm == "TLON" && !c->tlon.empty())) {   // init-time fields of pop_init_kpp_bckgrnd (host copies); TLON of either init call
     if (nm != "TLON" && !c->bck.on) { c->err = nm + " exists after pop_init_kpp_bckgrnd with lhoriz_varying_bckgrnd only"; return 1; }
     return copy_out(c, nm == "TLON" ? c->tlon : nm == "BCKGRND_VDC" ? c->bck.f.vdc : c->bck.f.vvc, host, count, name);
+  }
+  if (nm == "ANGLET" || nm == "COS_ANGLET" || nm == "SIN_ANGLET") {   // grid.F90:660-735 and the rotation's cosine / sine (host copies)
+    if (c->h.plan_only) { c->err = nm + ": the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+    cpl_anglet(c);
+    return copy_out(c, nm == "ANGLET" ? c->anglet : nm == "COS_ANGLET" ? c->cos_anglet : c->sin_anglet, host, count, name);
+  }
+  if (nm == "MASK_FRAC" && c->msb.inited) {   // pop_init_ms_balance: by sea (host copy)
+    const size_t a2 = c->h.n2 * c->h.nblocks;
+    if (n < 0 || n >= (int)c->msb.seas.size()) { c->err = "MASK_FRAC: sea index " + std::to_string(n) + " is outside 0 .. n_marginal_seas - 1"; return 1; }
+    return copy_out(c, std::vector<double>(c->msb.mask_frac.begin() + n * a2, c->msb.mask_frac.begin() + (n + 1) * a2), host, count, name);
   }
   if (nm == "TIDAL_ENERGY_FLUX" || nm == "TIDAL_COEF_3D") {   // init-time fields of pop_init_tidal_mixing (host copies)
     if (!c->tidal.on) { c->err = nm + " exists after pop_init_tidal_mixing with ltidal_mixing only"; return 1; }
@@ -1271,6 +1290,7 @@ int pop_time_manager(pop_ctx *c) {
   if (!c->host_only) land_skip_for_step(c);
   c->leapfrogts = 1; c->f_euler_ts = 0; c->avg_ts = 0;
   c->nsteps_total += 1;
+  if (c->cpl.inited) c->cpl.nsteps += 1;   // the coupling interval's count: pop_set_coupled_forcing resets it
   if (cf.tmix_opt == 2) { c->nsteps_this_interval += 1; if (c->nsteps_this_interval > c->h.nsteps_per_interval) c->nsteps_this_interval = 1; }
   c->eod_last = c->eod;
   c->eod = (cf.tmix_opt == 2) ? (c->nsteps_this_interval == c->h.nsteps_per_interval) : (c->nsteps_total % cf.steps_per_day == 0);
@@ -2062,7 +2082,7 @@ int pop_step(pop_ctx *c) {
   if (c->h.c.ns_boundary == 2 && !c->grid_from_input) { c->err = "time stepping on a tripole decomposition needs the caller's grid (pop_create_with_grid): the internal lat-lon grid has no values beyond the fold"; return 1; }
   ScopedPhase ph(c, "STEP");
   int e;
-  if ((e = pop_time_manager(c)) || (e = pop_dhdt(c)) || (e = pop_baroclinic_driver(c)) || (e = kpp_look_ahead(c)) ||
+  if ((e = pop_set_surface_forcing(c)) || (e = pop_time_manager(c)) || (e = pop_dhdt(c)) || (e = pop_baroclinic_driver(c)) || (e = kpp_look_ahead(c)) ||
       (e = pop_barotropic_driver(c)) || (e = pop_baroclinic_correct_adjust(c)) || (e = pop_step_tail(c))) return e;
   return 0;
 }
@@ -2571,6 +2591,7 @@ int pop_init_ice(pop_ctx *c, const pop_ice_nml *nml) {
   if (!nml || nml->struct_bytes != (int)sizeof(pop_ice_nml)) { c->err = "pop_init_ice: pop_ice_nml.struct_bytes is not sizeof(pop_ice_nml) of this library (" + std::to_string(sizeof(pop_ice_nml)) + ")"; return 1; }
   if (c->h.plan_only) { c->err = "pop_init_ice: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
   if (c->ice.inited) { c->err = "pop_init_ice: called a second time (once per context)"; return 1; }
+  if (c->cpl.inited) { c->err = "pop_init_ice: after pop_init_coupled_forcing, which took its constants and branches from the ice set-up (call pop_init_ice first)"; return 1; }
   if (c->ran || c->nsteps_total > 0) { c->err = "pop_init_ice: a step or a phase has already run (call it right after pop_create)"; return 1; }
   if (ice_nml_check(c->h, *nml, c->err)) return 1;
   pop_ctx::Ice I;
@@ -2631,6 +2652,128 @@ int pop_tfreez_host(pop_ctx *c, const double *S, double *TFRZ, long long count) 
   if (!c->ice.inited) { c->err = "pop_tfreez_host needs pop_init_ice (tfreeze_option)"; return 1; }
   if (count < 0 || (count > 0 && (!S || !TFRZ))) { c->err = "pop_tfreez_host: bad arguments"; return 1; }
   for (long long q = 0; q < count; ++q) TFRZ[q] = ice_tfreez(c->ice.nml.tfreeze_option, S[q]);
+  return 0;
+}
+
+// ---- coupled surface forcing (forcing_coupled.F90; launch_forcing.hpp)
+void pop_coupled_nml_init(pop_coupled_nml *nml) { if (nml) coupled_nml_defaults(*nml); }
+int pop_init_coupled_forcing(pop_ctx *c, const pop_coupled_nml *nml) {
+  if (!c) return 1;
+  if (!nml || nml->struct_bytes != (int)sizeof(pop_coupled_nml)) { c->err = "pop_init_coupled_forcing: pop_coupled_nml.struct_bytes is not sizeof(pop_coupled_nml) of this library (" + std::to_string(sizeof(pop_coupled_nml)) + ")"; return 1; }
+  if (c->h.plan_only) { c->err = "pop_init_coupled_forcing: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+  if (c->cpl.inited) { c->err = "pop_init_coupled_forcing: called a second time (once per context)"; return 1; }
+  if (c->ran || c->nsteps_total > 0) { c->err = "pop_init_coupled_forcing: a step or a phase has already run (call it right after pop_create, after pop_init_ice)"; return 1; }
+  CplState s;
+  s.nml = *nml;
+  if (coupled_nml_resolve(c->h, s.nml, c->err)) return 1;
+  const double ocn_ref_salinity = c->ice.inited ? c->ice.nml.ocn_ref_salinity : 34.7;
+  s.k = coupled_consts(s.nml, hflux_factor_of(c), ocn_ref_salinity);
+  s.fwf = !(c->ice.inited && c->ice.nml.lfw_as_salt_flx);   // sfc_layer_type is 'varthick' throughout (forcing_coupled.F90:740-741)
+  s.icefw = s.fwf && c->ice.liceform;                        // :886-887, forcing.F90:417-426
+  if (host_qsw_12hr_factor(c->h, s.nml.qsw_distrb_opt, s.nml.nsteps_per_interval, s.qsw, c->err)) return 1;
+  if (s.nml.lms_balance) {   // forcing_coupled.F90:845-848: inside the virtual-salt-flux branch only
+    if (!c->msb.inited) { c->err = "pop_init_coupled_forcing: lms_balance needs pop_init_ms_balance first (the region table and REGION_MASK)"; return 1; }
+    if (s.fwf) { c->err = "pop_init_coupled_forcing: lms_balance needs lfw_as_salt_flx (pop_init_ice): the reference balances the marginal seas in the virtual-salt-flux branch only (forcing_coupled.F90:800-850)"; return 1; }
+    s.ms = !c->msb.seas.empty(); s.nseas = (int)c->msb.seas.size();
+    const pop_ice_nml &in = c->ice.nml;
+    const double sea_ice_salinity = s.nml.sea_ice_salinity != 0.0 ? s.nml.sea_ice_salinity : 4.0, rho_fw = s.nml.rho_fw != 0.0 ? s.nml.rho_fw : 1.0;
+    s.c_q = -(1.0e4 / in.latent_heat_fusion) * (ocn_ref_salinity - sea_ice_salinity) / ocn_ref_salinity;   // ms_balance.F90:558-566
+    s.c_s = -(1.0e3 / ocn_ref_salinity) * (rho_fw / in.rho_sw);
+    s.c_a = 1.0e-4; s.c_t = -ocn_ref_salinity;
+  }
+  cpl_anglet(c);
+  if (!c->host_only && cpl_init_device(c, s)) return 1;
+  s.inited = true;
+  c->cpl = s;
+  return 0;
+}
+static int region_mask_keep(pop_ctx *c, const int *region_mask_global, const char *who);
+int pop_init_ms_balance(pop_ctx *c, const pop_ms_balance_nml *nml, const int *region_mask_global) {
+  if (!c) return 1;
+  if (!nml || nml->struct_bytes != (int)sizeof(pop_ms_balance_nml)) { c->err = "pop_init_ms_balance: pop_ms_balance_nml.struct_bytes is not sizeof(pop_ms_balance_nml) of this library (" + std::to_string(sizeof(pop_ms_balance_nml)) + ")"; return 1; }
+  if (c->h.plan_only) { c->err = "pop_init_ms_balance: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+  if (c->msb.inited) { c->err = "pop_init_ms_balance: called a second time (once per context)"; return 1; }
+  if (c->cpl.inited) { c->err = "pop_init_ms_balance: after pop_init_coupled_forcing (call it before)"; return 1; }
+  if (c->ran || c->nsteps_total > 0) { c->err = "pop_init_ms_balance: a step or a phase has already run (call it right after pop_create)"; return 1; }
+  MsBalance M;
+  const bool had_mask = !c->region_mask.empty();
+  if (region_mask_keep(c, region_mask_global, "pop_init_ms_balance")) return 1;
+  if (host_ms_balance_build(c->h, *nml, region_mask_global, M, c->err)) { if (!had_mask) c->region_mask.clear(); return 1; }
+  M.region_mask.clear();   // one stored copy: pop_ctx::region_mask
+  c->msb = M;
+  if (c->tlon.empty()) host_tlon_build(c->h, c->tlon);   // pop_get_field("TLON"): the longitudes the search compared
+  return 0;
+}
+// REGION_MASK as pop_init_transports and pop_init_ms_balance take it: the first call's array is kept, the second call's must equal it
+static int region_mask_keep(pop_ctx *c, const int *region_mask_global, const char *who) {
+  if (!region_mask_global) return 0;
+  const size_t ng = (size_t)c->h.c.nx_global * c->h.c.ny_global;
+  if (c->region_mask.empty()) { c->region_mask.assign(region_mask_global, region_mask_global + ng); return 0; }
+  for (size_t g = 0; g < ng; ++g)
+    if (c->region_mask[g] != region_mask_global[g]) {
+      c->err = std::string(who) + ": REGION_MASK differs from the one the earlier init call was given, first at global (i, j) = (" + std::to_string(g % c->h.c.nx_global + 1) + ", " +
+               std::to_string(g / c->h.c.nx_global + 1) + "): " + std::to_string(region_mask_global[g]) + " against " + std::to_string(c->region_mask[g]);
+      return 1;
+    }
+  return 0;
+}
+static int ms_sea_arg(pop_ctx *c, int sea, const char *who) {
+  if (!c->msb.inited) { c->err = std::string(who) + " needs pop_init_ms_balance"; return 1; }
+  if (sea < 0 || sea >= (int)c->msb.seas.size()) { c->err = std::string(who) + ": sea is 0 .. n_marginal_seas - 1 = " + std::to_string((int)c->msb.seas.size() - 1); return 1; }
+  return 0;
+}
+int pop_ms_balance_info(pop_ctx *c, int sea, int *number, int *npts, double *area, int *warnings, double *transport) {
+  if (!c) return 1;
+  if (ms_sea_arg(c, sea, "pop_ms_balance_info")) return 1;
+  const MsSea &S = c->msb.seas[sea];
+  if (number) *number = S.number;
+  if (npts) *npts = (int)S.ipts.size();
+  if (area) *area = S.area;
+  if (warnings) *warnings = S.warn;
+  if (transport) {
+    *transport = 0.0;
+    if (c->cpl.ms && c->cpl.imported) {   // the only call of the coupled forcing that waits for the device
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      HIPCHK(c, hipMemcpy(transport, c->cpl.ms_sums + sea, sizeof(double), hipMemcpyDeviceToHost));
+    }
+  }
+  return 0;
+}
+int pop_ms_balance_points(pop_ctx *c, int sea, int *ipts, int *jpts, double *fracs, long long count) {
+  if (!c) return 1;
+  if (ms_sea_arg(c, sea, "pop_ms_balance_points")) return 1;
+  const MsSea &S = c->msb.seas[sea];
+  if (count_is(c, count, (long long)S.ipts.size(), "pop_ms_balance_points")) return 1;
+  if (ipts) std::copy(S.ipts.begin(), S.ipts.end(), ipts);
+  if (jpts) std::copy(S.jpts.begin(), S.jpts.end(), jpts);
+  if (fracs) std::copy(S.fracs.begin(), S.fracs.end(), fracs);
+  return 0;
+}
+int pop_coupled_qsw_factor(pop_ctx *c, double *factor, long long count) {
+  if (!c) return 1;
+  if (!c->cpl.inited) { c->err = "pop_coupled_qsw_factor needs pop_init_coupled_forcing"; return 1; }
+  return copy_out(c, c->cpl.qsw, factor, count, "qsw_12hr_factor");
+}
+int pop_set_coupled_forcing(pop_ctx *c, const pop_x2o *x2o, long long count) {
+  if (need_device(c)) return 1;
+  if (!c->cpl.inited) { c->err = "pop_set_coupled_forcing needs pop_init_coupled_forcing"; return 1; }
+  if (!x2o || x2o->struct_bytes != (int)sizeof(pop_x2o)) { c->err = "pop_set_coupled_forcing: pop_x2o.struct_bytes is not sizeof(pop_x2o) of this library (" + std::to_string(sizeof(pop_x2o)) + ")"; return 1; }
+  if (c->tavg.in_step) { c->err = "pop_set_coupled_forcing: between pop_time_manager and pop_step_tail of a step (the forcing of a step in hand does not change)"; return 1; }
+  if (count_is(c, count, (long long)c->g.n2 * c->g.nblocks, "pop_set_coupled_forcing")) return 1;
+  if (join_side(c)) return 1;   // work formed ahead (the KPP look-ahead) read the old STF and SHF_QSW
+  return cpl_import(c, x2o);
+}
+int pop_set_surface_forcing(pop_ctx *c) {
+  if (!c) return 1;
+  if (c->host_only || !cpl_step_active(c)) return 0;
+  if (c->tavg.in_step) { c->err = "pop_set_surface_forcing: between pop_time_manager and pop_step_tail of a step (it is the head of a step, step_mod.F90:231)"; return 1; }
+  if (join_side(c)) return 1;   // the KPP look-ahead read the SHF_QSW of the step before
+  return cpl_step(c);
+}
+int pop_coupled_info(pop_ctx *c, int *out4, int *n_marginal_seas) {
+  if (!c) return 1;
+  if (out4) { out4[0] = c->cpl.inited ? 1 : 0; out4[1] = c->cpl.nml.qsw_distrb_opt; out4[2] = c->cpl.nml.nsteps_per_interval; out4[3] = c->cpl.nsteps; }
+  if (n_marginal_seas) *n_marginal_seas = (int)c->msb.seas.size();
   return 0;
 }
 
@@ -2941,7 +3084,9 @@ int pop_init_transports(pop_ctx *c, const pop_transports_nml *nml, const int *re
   if (c->moc.aux.inited) { c->err = "pop_init_transports: called twice"; return 1; }
   if (c->ran) { c->err = "pop_init_transports: call it before the first step or phase"; return 1; }
   LatAux aux;
-  if (host_lat_aux_build(c->h, *nml, region_mask_global, aux, c->err)) return 1;
+  const bool had_mask = !c->region_mask.empty();
+  if (region_mask_keep(c, region_mask_global, "pop_init_transports")) return 1;
+  if (host_lat_aux_build(c->h, *nml, region_mask_global, aux, c->err)) { if (!had_mask) c->region_mask.clear(); return 1; }
   c->moc.aux = std::move(aux);
   return 0;
 }

@@ -28,7 +28,11 @@ struct TavgEntry {
   bool vint = false;         // columns: fed once per level
   double *buf = nullptr;     // device, (nxb, nyb, nlev, nblocks); null on a host-only context
 };
-struct TavgSiteTab { TavgTable cells{}, cols{}; int sid_cells[TAVG_MAX_SRC] = {}, sid_cols[TAVG_MAX_SRC] = {}; bool vint_psurf = false; };
+struct TavgSiteTab {
+  TavgTable cells{}, cols{}; int sid_cells[TAVG_MAX_SRC] = {}, sid_cols[TAVG_MAX_SRC] = {}; bool vint_psurf = false;
+  // a second launch of the 2-D column entries whose sources no longer fit the first (the forcing site with the coupled fields)
+  TavgTable cols_more{}; int sid_cols_more[TAVG_MAX_SRC] = {};
+};
 struct TavgState {
   std::vector<TavgEntry> req;
   bool on[TAVG_MAX_STREAMS + 1] = {};               // ltavg_on
@@ -82,6 +86,26 @@ struct TrnState {
   double *ACC = nullptr, *BACC = nullptr, *gather = nullptr;
   std::vector<double> set_sums;                     // pop_transport_sums_set: added last when the sums are read
   std::vector<double> snap[2]; bool have_snap = false;
+};
+
+// ---- coupled surface forcing (forcing_coupled.F90, the tail of set_surface_forcing; kernels_forcing.hpp, launch_forcing.hpp)
+struct CplState {
+  bool inited = false;                              // pop_init_coupled_forcing: the one flag the head of a step tests
+  bool imported = false;                            // a pop_set_coupled_forcing has been made: the interval's fields hold values
+  pop_coupled_nml nml{}; CplConsts k{};
+  int nsteps = 0;                                   // steps of this coupling interval (pop_time_manager advances, an import resets)
+  std::vector<double> qsw;                          // qsw_12hr_factor(1 : nml.nsteps_per_interval)
+  bool fwf = false, icefw = false;                  // the fresh-water form (not lfw_as_salt_flx); and ice formation on: FW_FREEZE joins FW / TFW every step
+  // device (null on a host-only context)
+  double *d_qsw = nullptr, *COSA = nullptr, *SINA = nullptr;
+  double *F[CF_NF] = {};                            // the imported fields
+  double *SHF_COMP_QSW = nullptr, *SFWF_COMP = nullptr, *TFW_COMP[2] = {nullptr, nullptr};
+  double *raw = nullptr, *h_raw = nullptr;          // staging of one import: X_NF planes on the device, the same pinned on the host
+  hipEvent_t ev_up = nullptr; bool up_pending = false;   // the upload of the last import (the next one reuses h_raw)
+  // marginal-sea balance (lms_balance): per sea the indicator and MASK_FRAC, (n2, nblocks, nseas); the per-cell TRANSPORT term; the reduced sums
+  bool ms = false; int nseas = 0;
+  double *MS_IND = nullptr, *MS_FRAC = nullptr, *MS_T = nullptr, *ms_sums = nullptr;
+  double c_q = 0, c_s = 0, c_a = 0, c_t = 0;
 };
 
 struct pop_ctx {
@@ -234,6 +258,10 @@ struct pop_ctx {
   DiagState diag;
   MocState moc;
   TrnState trn;
+  CplState cpl;
+  MsBalance msb;                                           // pop_init_ms_balance
+  std::vector<int> region_mask;                            // the caller's REGION_MASK (ny_global, nx_global): the one copy pop_init_transports and pop_init_ms_balance share
+  std::vector<double> anglet, cos_anglet, sin_anglet;      // ANGLET and its cosine / sine on the local blocks, formed on first use (host_anglet_build)
 };
 
 namespace {

@@ -104,6 +104,7 @@ struct HostModel {
   std::map<std::string, std::vector<int>> i2;
   std::map<std::string, std::vector<double>> f3;   // (nxb,nyb,km,nblocks), initial state only
   std::vector<double> aniso_f[2];                  // hmix_momentum = 3 with lvariable_hmix_aniso: F_PARA, F_PERP of ALL blocks (nxb,nyb,km,nblocks_tot)
+  std::vector<double> angle;                       // the caller's ANGLE on ALL blocks, kept for ANGLET (host_forcing.cpp); empty: zeros
   double uarea_equator = 0, residualNorm = 0, convergenceCriterion = 0, rcheck = 0, rconst = 0;
   double dtt = 0, dtu = 0, dtp = 0;
   int nsteps_per_interval = 0;
@@ -143,6 +144,26 @@ struct IceConsts { double cp_over_lhfusion, salice, salref, hflux_factor; };
 void ice_nml_defaults(pop_ice_nml &n);
 int ice_nml_check(const HostModel &h, const pop_ice_nml &n, std::string &err);
 IceConsts ice_consts(const pop_ice_nml &n);
+// ---- coupled surface forcing, host logic (host_forcing.cpp; grid.F90:660-735, forcing_coupled.F90:128-470)
+struct CplConsts { double lhv, lhf, hflux_factor, salinity_factor, sflux_factor, fwmass_to_fwflux, momentum_factor; };
+void coupled_nml_defaults(pop_coupled_nml &n);
+// what pop_init_coupled_forcing refuses from the namelist and the configuration; resolves nsteps_per_interval = 0
+int coupled_nml_resolve(const HostModel &h, pop_coupled_nml &n, std::string &err);
+CplConsts coupled_consts(const pop_coupled_nml &n, double hflux_factor, double ocn_ref_salinity);
+// ANGLET, cos(ANGLET), sin(ANGLET) on the local blocks
+void host_anglet_build(const HostModel &h, std::vector<double> &anglet, std::vector<double> &cosa, std::vector<double> &sina);
+// qsw_12hr_factor(1 : nspi) (forcing_coupled.F90:358-408); non-zero with the error set when the final integral is off
+int host_qsw_12hr_factor(const HostModel &h, int qsw_distrb_opt, int nspi, std::vector<double> &factor, std::string &err);
+// ---- marginal-sea balance, init_ms_balance (host_forcing.cpp; ms_balance.F90:61-453)
+struct MsSea { int number = 0, warn = 0; std::string name; double area = 0.0; std::vector<int> ipts, jpts; std::vector<double> fracs; };
+struct MsBalance {
+  bool inited = false;
+  std::vector<MsSea> seas;                          // in region order (mask_index - 1)
+  std::vector<int> region_mask;                     // (ny_global, nx_global)
+  std::vector<double> mask_frac, ind;               // per sea MASK_FRAC and the indicator REGION_MASK == number, local blocks: (n2, nblocks, nseas)
+};
+void host_tlon_all(const HostModel &h, std::vector<double> &TLON);   // TLON [radians] of ALL blocks (host_tidal.cpp)
+int host_ms_balance_build(const HostModel &h, const pop_ms_balance_nml &nml, const int *region_mask_global, MsBalance &out, std::string &err);
 // ---- auxiliary latitude grid and transport regions of the MOC (host_lat_aux.cpp; diags_on_lat_aux_grid.F90:121-936)
 // A cell list holds the physical ocean cells of one block that lie in one bin and in some region, in (j, i) order, as
 // p2 | flag << MOC_FLAG_SHIFT (p2 = j * nxb + i inside the block; flag bit 0: region 1, bit 1: region 2).  Lists are numbered over

@@ -112,6 +112,31 @@
       integer (c_int) :: struct_bytes, ice_freq_opt, licecesm2, kmxice, lactive_ice, lfw_as_salt_flx, tfreeze_option
       real (c_double) :: sea_ice_salinity, ocn_ref_salinity, latent_heat_fusion, cp_sw, rho_sw, rho_fw
    end type pop_ice_nml
+   ! mirrors `struct pop_coupled_nml` (the coupled surface forcing); fill with pop_coupled_nml_init, then set fields
+   type, bind(C) :: pop_coupled_nml
+      integer (c_int) :: struct_bytes, qsw_distrb_opt, nsteps_per_interval, lms_balance, shf_formulation, sfwf_formulation
+      integer (c_int) :: lestuary_on, lvsf_river, lebm_on, luse_cpl_ifrac
+      real (c_double) :: latent_heat_vapor_mks, latent_heat_fusion_mks, sea_ice_salinity, rho_fw
+   end type pop_coupled_nml
+   ! mirror `struct pop_ms_region` (a record of the region_info_file) and `struct pop_ms_balance_nml`
+   integer (c_int), parameter :: POP_MAX_MS = 7
+   type, bind(C) :: pop_ms_region
+      integer (c_int) :: number
+      character (kind=c_char) :: name(36)
+      real (c_double) :: lat, lon, area
+   end type pop_ms_region
+   type, bind(C) :: pop_ms_balance_nml
+      integer (c_int) :: struct_bytes, num_regions, max_points, reserved
+      type (c_ptr) :: regions
+   end type pop_ms_balance_nml
+   ! mirrors `struct pop_x2o`: c_loc of host arrays (nx_block, ny_block, nblocks_clinic), c_null_ptr = zeros
+   type, bind(C) :: pop_x2o
+      integer (c_int) :: struct_bytes = 0, reserved = 0
+      type (c_ptr) :: taux = c_null_ptr, tauy = c_null_ptr, snow = c_null_ptr, rain = c_null_ptr, evap = c_null_ptr
+      type (c_ptr) :: meltw = c_null_ptr, rofl = c_null_ptr, rofi = c_null_ptr, salt = c_null_ptr, swnet = c_null_ptr
+      type (c_ptr) :: sen = c_null_ptr, lwup = c_null_ptr, lwdn = c_null_ptr, melth = c_null_ptr, ifrac = c_null_ptr
+      type (c_ptr) :: pslv = c_null_ptr, duu10n = c_null_ptr
+   end type pop_x2o
    ! mirrors `struct pop_transports_nml` (transports_nml); fill with pop_transports_nml_init, then set fields
    integer (c_int), parameter :: POP_MAX_TRANSPORT_REG2 = 16
    type, bind(C) :: pop_transports_nml
@@ -452,6 +477,58 @@
          real (c_double), intent(in) :: S(*)                ! salinity, g/g
          real (c_double), intent(out) :: TFRZ(*)
          integer (c_long_long), value :: count
+      end function
+      ! ---- coupled surface forcing (forcing_coupled.F90, forcing.F90)
+      subroutine pop_coupled_nml_init(nml) bind(C, name='pop_coupled_nml_init')
+         import :: pop_coupled_nml
+         type (pop_coupled_nml), intent(out) :: nml
+      end subroutine
+      integer (c_int) function pop_init_coupled_forcing(ctx, nml) bind(C, name='pop_init_coupled_forcing')
+         import :: c_int, c_ptr, pop_coupled_nml
+         type (c_ptr), value :: ctx
+         type (pop_coupled_nml), intent(in) :: nml
+      end function
+      integer (c_int) function pop_coupled_qsw_factor(ctx, factor, count) bind(C, name='pop_coupled_qsw_factor')
+         import :: c_int, c_ptr, c_double, c_long_long
+         type (c_ptr), value :: ctx
+         real (c_double), intent(out) :: factor(*)
+         integer (c_long_long), value :: count
+      end function
+      integer (c_int) function pop_set_coupled_forcing_c(ctx, x2o, count) bind(C, name='pop_set_coupled_forcing')
+         import :: c_int, c_ptr, c_long_long, pop_x2o
+         type (c_ptr), value :: ctx
+         type (pop_x2o), intent(in) :: x2o
+         integer (c_long_long), value :: count                ! nx_block * ny_block * nblocks_clinic
+      end function
+      integer (c_int) function pop_init_ms_balance(ctx, nml, region_mask_global) bind(C, name='pop_init_ms_balance')
+         import :: c_int, c_ptr, pop_ms_balance_nml
+         type (c_ptr), value :: ctx
+         type (pop_ms_balance_nml), intent(in) :: nml
+         integer (c_int), intent(in) :: region_mask_global(*)   ! (nx_global, ny_global)
+      end function
+      integer (c_int) function pop_ms_balance_info(ctx, sea, number, npts, area, warnings, transport) bind(C, name='pop_ms_balance_info')
+         import :: c_int, c_ptr, c_double
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: sea                           ! 0-based, region order
+         integer (c_int), intent(out) :: number, npts, warnings
+         real (c_double), intent(out) :: area, transport
+      end function
+      integer (c_int) function pop_ms_balance_points(ctx, sea, ipts, jpts, fracs, count) bind(C, name='pop_ms_balance_points')
+         import :: c_int, c_ptr, c_double, c_long_long
+         type (c_ptr), value :: ctx
+         integer (c_int), value :: sea
+         integer (c_int), intent(out) :: ipts(*), jpts(*)        ! 1-based global, selection order
+         real (c_double), intent(out) :: fracs(*)
+         integer (c_long_long), value :: count                   ! npts of pop_ms_balance_info
+      end function
+      integer (c_int) function pop_set_surface_forcing(ctx) bind(C, name='pop_set_surface_forcing')
+         import :: c_int, c_ptr
+         type (c_ptr), value :: ctx
+      end function
+      integer (c_int) function pop_coupled_info(ctx, out4, n_marginal_seas) bind(C, name='pop_coupled_info')
+         import :: c_int, c_ptr
+         type (c_ptr), value :: ctx
+         integer (c_int), intent(out) :: out4(4), n_marginal_seas
       end function
       ! ---- time-averaged output (tavg.F90)
       integer (c_int) function pop_tavg_request(ctx, stream, name) bind(C, name='pop_tavg_request')

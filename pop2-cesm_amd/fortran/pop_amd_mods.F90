@@ -980,6 +980,172 @@
    end function
  end module ice
 
+! forcing_coupled.F90 and the coupler cap's import (drivers/mct/ocn_import_export.F90:171-239).  The cap hands over the x2o fields it
+! unpacked -- host arrays (nx_block, ny_block, nblocks_clinic) in the coupler's MKS units, which must live until
+! pop_set_coupled_forcing returns -- with rotate_wind_stress (taux, tauy) and coupler_field (the others, by the name pop_x2o gives
+! them); pop_set_coupled_forcing then runs the import, the rotation, the halo updates and the combinations on the device in one call.
+ module forcing_coupled
+   use kinds_mod
+   use pop_amd_c
+   use blocks
+   implicit none
+   private
+   character (char_len), public :: qsw_distrb_opt = 'const'
+   logical (log_kind), public :: lms_balance = .false.               ! needs init_ms_balance (module ms_balance) first and lfw_as_salt_flx
+   integer (int_kind), public :: nsteps_per_interval = 0             ! 0: the time manager's
+   real (r8), public :: latent_heat_vapor_mks = 0.0_r8, latent_heat_fusion_mks = 0.0_r8   ! 0: the coupled values of pop_constants.F90:283-290
+   real (r8), public :: sea_ice_salinity_cpl = 0.0_r8, rho_fw_cpl = 0.0_r8               ! what the marginal-sea balance reads; 0: 4.0 psu, 1.0 g/cm^3
+   real (r8), dimension(:), allocatable, public :: qsw_12hr_factor
+   type (pop_x2o), save :: x2o
+   public :: pop_init_coupled, pop_set_coupled_forcing, rotate_wind_stress, update_ghost_cells_coupler_fluxes, coupler_field
+ contains
+   subroutine pop_init_coupled(errorCode)
+      integer (int_kind), intent(out) :: errorCode
+      type (pop_coupled_nml) :: nml
+      integer (c_int) :: info(4), nseas
+      call pop_coupled_nml_init(nml)
+      select case (trim(qsw_distrb_opt))
+      case ('const'); nml%qsw_distrb_opt = 0
+      case ('12hr');  nml%qsw_distrb_opt = 1
+      case ('cosz');  nml%qsw_distrb_opt = 2
+      case default;   nml%qsw_distrb_opt = -1
+      end select
+      nml%nsteps_per_interval = nsteps_per_interval
+      nml%lms_balance = merge(1, 0, lms_balance)
+      nml%latent_heat_vapor_mks = latent_heat_vapor_mks; nml%latent_heat_fusion_mks = latent_heat_fusion_mks
+      nml%sea_ice_salinity = sea_ice_salinity_cpl; nml%rho_fw = rho_fw_cpl
+      errorCode = pop_init_coupled_forcing(pop_ctx, nml)
+      if (errorCode /= POP_Success) return
+      errorCode = pop_coupled_info(pop_ctx, info, nseas)
+      nsteps_per_interval = info(3)
+      if (allocated(qsw_12hr_factor)) deallocate(qsw_12hr_factor)
+      allocate(qsw_12hr_factor(nsteps_per_interval))
+      errorCode = pop_coupled_qsw_factor(pop_ctx, qsw_12hr_factor, int(nsteps_per_interval, c_long_long))
+   end subroutine
+   ! rotate_wind_stress(WORK1, WORK2) forcing_coupled.F90:1463: the true zonal / meridional stress the coupler sent [N/m^2]; the
+   ! rotation, the vector halo update and tgrid_to_ugrid run inside pop_set_coupled_forcing
+   subroutine rotate_wind_stress(WORK1, WORK2)
+      real (r8), dimension(:,:,:), intent(in), target, contiguous :: WORK1, WORK2
+      x2o%taux = c_loc(WORK1); x2o%tauy = c_loc(WORK2)
+   end subroutine
+   ! one of the other x2o fields: 'snow', 'rain', 'evap', 'meltw', 'rofl', 'rofi', 'salt', 'swnet', 'sen', 'lwup', 'lwdn', 'melth',
+   ! 'ifrac', 'pslv', 'duu10n'.  A field never given is zero
+   subroutine coupler_field(name, A, errorCode)
+      character (*), intent(in) :: name
+      real (r8), dimension(:,:,:), intent(in), target, contiguous :: A
+      integer (int_kind), intent(out) :: errorCode
+      errorCode = POP_Success
+      select case (trim(name))
+      case ('snow');   x2o%snow = c_loc(A)
+      case ('rain');   x2o%rain = c_loc(A)
+      case ('evap');   x2o%evap = c_loc(A)
+      case ('meltw');  x2o%meltw = c_loc(A)
+      case ('rofl');   x2o%rofl = c_loc(A)
+      case ('rofi');   x2o%rofi = c_loc(A)
+      case ('salt');   x2o%salt = c_loc(A)
+      case ('swnet');  x2o%swnet = c_loc(A)
+      case ('sen');    x2o%sen = c_loc(A)
+      case ('lwup');   x2o%lwup = c_loc(A)
+      case ('lwdn');   x2o%lwdn = c_loc(A)
+      case ('melth');  x2o%melth = c_loc(A)
+      case ('ifrac');  x2o%ifrac = c_loc(A)
+      case ('pslv');   x2o%pslv = c_loc(A)
+      case ('duu10n'); x2o%duu10n = c_loc(A)
+      case default;    errorCode = 1
+      end select
+   end subroutine
+   ! update_ghost_cells_coupler_fluxes(errorCode) forcing_coupled.F90:1141: the halo updates are one message inside
+   ! pop_set_coupled_forcing; kept so that a cap's call sequence compiles unchanged
+   subroutine update_ghost_cells_coupler_fluxes(errorCode)
+      integer (int_kind), intent(out) :: errorCode
+      errorCode = POP_Success
+   end subroutine
+   ! pop_set_coupled_forcing forcing_coupled.F90:677 on the fields handed over since the last call; forgets them afterwards
+   subroutine pop_set_coupled_forcing(errorCode)
+      integer (int_kind), intent(out) :: errorCode
+      type (pop_x2o) :: none
+      x2o%struct_bytes = int(c_sizeof(x2o), c_int)
+      errorCode = pop_set_coupled_forcing_c(pop_ctx, x2o, int(nx_block, c_long_long)*ny_block*nblocks_clinic)
+      x2o = none
+   end subroutine
+ end module forcing_coupled
+
+! ms_balance.F90: init_ms_balance on the region table and the global REGION_MASK (the reference reads both in grid.F90 area_masks);
+! ms_balancing itself runs on the device inside pop_set_coupled_forcing (module forcing_coupled, lms_balance = .true.), so the
+! subroutine of that name only reports the transports of the last balancing.
+ module ms_balance
+   use kinds_mod
+   use pop_amd_c
+   implicit none
+   private
+   public :: init_ms_balance, ms_balancing, ms_balance_sea
+ contains
+   subroutine init_ms_balance(numbers, names, lats, lons, areas, REGION_MASK_G, errorCode)
+      integer (int_kind), dimension(:), intent(in) :: numbers             ! negative: a marginal sea
+      character (*), dimension(:), intent(in) :: names
+      real (r8), dimension(:), intent(in) :: lats, lons, areas
+      integer (int_kind), dimension(:,:), intent(in), contiguous :: REGION_MASK_G   ! (nx_global, ny_global)
+      integer (int_kind), intent(out) :: errorCode
+      type (pop_ms_region), dimension(:), allocatable, target :: regions
+      type (pop_ms_balance_nml) :: nml
+      integer (int_kind) :: n, k
+      allocate(regions(size(numbers)))
+      do n = 1, size(numbers)
+         regions(n)%number = numbers(n); regions(n)%lat = lats(n); regions(n)%lon = lons(n); regions(n)%area = areas(n)
+         regions(n)%name = c_null_char
+         do k = 1, min(len_trim(names(n)), 35)
+            regions(n)%name(k) = names(n)(k:k)
+         end do
+      end do
+      nml%struct_bytes = int(c_sizeof(nml), c_int); nml%num_regions = size(numbers); nml%max_points = 0; nml%reserved = 0
+      nml%regions = c_loc(regions)
+      errorCode = pop_init_ms_balance(pop_ctx, nml, REGION_MASK_G)
+   end subroutine
+   ! the transport [kg/s of fresh water] of every marginal sea, region order, as the last pop_set_coupled_forcing left it (waits for the device)
+   subroutine ms_balancing(transport, errorCode)
+      real (r8), dimension(:), intent(out) :: transport
+      integer (int_kind), intent(out) :: errorCode
+      integer (c_int) :: number, npts, warnings
+      real (c_double) :: area
+      integer (int_kind) :: n
+      errorCode = POP_Success
+      do n = 1, size(transport)
+         errorCode = pop_ms_balance_info(pop_ctx, n - 1, number, npts, area, warnings, transport(n))
+         if (errorCode /= POP_Success) return
+      end do
+   end subroutine
+   ! marginal sea n (1-based, region order): its REGION_MASK number, area, warnings (bit 0: the points span two regions, bit 1:
+   ! max_points reached) and the selected points with their fractions (allocated here)
+   subroutine ms_balance_sea(n, number, area, warnings, ipts, jpts, fracs, errorCode)
+      integer (int_kind), intent(in) :: n
+      integer (int_kind), intent(out) :: number, warnings, errorCode
+      real (r8), intent(out) :: area
+      integer (int_kind), dimension(:), allocatable, intent(out) :: ipts, jpts
+      real (r8), dimension(:), allocatable, intent(out) :: fracs
+      integer (c_int) :: npts
+      real (c_double) :: transport
+      errorCode = pop_ms_balance_info(pop_ctx, n - 1, number, npts, area, warnings, transport)
+      if (errorCode /= POP_Success) return
+      allocate(ipts(npts), jpts(npts), fracs(npts))
+      errorCode = pop_ms_balance_points(pop_ctx, n - 1, ipts, jpts, fracs, int(npts, c_long_long))
+   end subroutine
+ end module ms_balance
+
+! forcing.F90: the per-step tail of set_surface_forcing (:379-437).  step calls it at its head; a caller that owns the sequence of
+! step_mod calls it before time_manager
+ module forcing
+   use kinds_mod
+   use pop_amd_c
+   implicit none
+   private
+   public :: set_surface_forcing
+ contains
+   subroutine set_surface_forcing(errorCode)
+      integer (int_kind), intent(out) :: errorCode
+      errorCode = pop_set_surface_forcing(pop_ctx)
+   end subroutine
+ end module forcing
+
 !-----------------------------------------------------------------------
  module tavg                 ! source/tavg.F90: requests, streams, sums and the 'bin' file; the accumulation runs inside the library's step
    use kinds_mod
