@@ -1,4 +1,5 @@
-// host_setup.cpp -- init-time host logic of libpop_amd: block decomposition, internal grid,
+// host_setup.cpp -- init-time host logic of libpop_amd: the reading of the caller's configuration
+// with every refusal rule of pop_create (config_read_check), block decomposition, internal grid,
 // masks, operator coefficients and the synthetic initial state.  Pure host code (no HIP), so
 // it is testable without a GPU.  Every rank builds the 2-D fields of ALL blocks of the
 // decomposition (they are functions of the global index only), which makes init-time halo
@@ -429,6 +430,90 @@ static void aniso_setup(HostModel &h) {
           const double amax = AMAX[b * n2 + p2];
           for (auto &F : h.aniso_f) if (F[o] > amax) F[o] = amax;
         }
+}
+
+// The caller's pop_config in the layout of its struct_version, the two settings derived from it, and every option this library
+// does not implement: refused here, before anything is built (the reference aborts in the init routine of the option's own
+// module, e.g. vertical_mix.F90:280-296, POP_SolversMod.F90:442-472).  The first rule that fires gives the message.
+int config_read_check(const pop_config *in, const pop_grid_input *grid, pop_config &out, std::string &err) {
+  // a version-5 caller's struct ends at kappa_depth_scale, a version-6 caller's at smag_lat_gauss: read that much only (the later members stay 0)
+  if (in->struct_version == POP_CONFIG_VERSION) out = *in;
+  else if (in->struct_version == 6) memcpy(&out, in, offsetof(pop_config, lsubmesoscale_mixing));
+  else memcpy(&out, in, offsetof(pop_config, aniso_alignment));
+  const pop_config *cfg = &out;
+  if (cfg->hmix_tracer == 3 && cfg->gm_transition_layer == 1 && cfg->vmix_choice == 3) out.kpp_ml_diagnostics = 1;   // the diabatic depth of the transition layer is the smoothed HMXL (hmix_gm.F90:1226-1228)
+  if (cfg->lsubmesoscale_mixing == 1 && cfg->vmix_choice == 3) out.kpp_ml_diagnostics = 1;   // ML_DEPTH of submeso_sf is HMXL (mix_submeso.F90:424-426)
+  auto bad = [&](const std::string &m) { err = "pop_create: " + m; return 1; };
+  if (cfg->struct_version != POP_CONFIG_VERSION && cfg->struct_version != 6 && cfg->struct_version != 5) return bad("pop_config.struct_version is " + std::to_string(cfg->struct_version) + ", this library reads 5, 6 and " + std::to_string(POP_CONFIG_VERSION) + " (include/pop_amd.h)");
+  if (cfg->reserved_i[0] != 0) return bad("pop_config.reserved_i must be 0");
+  if (cfg->gm_kappa_bkg_srfbl != 0 && cfg->gm_kappa_bkg_srfbl != 1) return bad("gm_kappa_bkg_srfbl: 0 or 1");
+  if (cfg->ah_bkg_bottom < 0.0) return bad("ah_bkg_bottom: >= 0");
+  if (cfg->gm_diag_bolus != 0 && cfg->gm_diag_bolus != 1) return bad("gm_diag_bolus: 0 or 1");
+  if (cfg->gm_diag_bolus && cfg->hmix_tracer != 3) return bad("gm_diag_bolus needs hmix_tracer = 3");
+  if (cfg->gm_transition_layer != 0 && cfg->gm_transition_layer != 1) return bad("gm_transition_layer: 0 or 1");
+  if (cfg->gm_transition_layer && cfg->hmix_tracer != 3) return bad("gm_transition_layer needs hmix_tracer = 3");
+  // the reference aborts in init_gm: 'hmix_gm currently incompatible with partial bottom cells' (hmix_gm.F90:782-785) -- its slopes, stream-function
+  // terms and flux divergence use dz(k), the tracer budget DZT (accepted until round 3 with dz(k) throughout, tracer content not conserved)
+  if (cfg->hmix_tracer == 3 && cfg->partial_bottom_cells) return bad("hmix_tracer = 3 (Gent-McWilliams) with partial_bottom_cells: the reference refuses the combination (hmix_gm.F90:782-785), so does this library");
+  // hmix_gm.F90:724-730: kappa_depth_2 = 0 with the 'depth' profile aborts in init_gm
+  if (cfg->hmix_tracer == 3 && cfg->gm_kappa_type == 2 && cfg->kappa_depth_2 == 0.0) return bad("gm_kappa_type = 2 ('depth') needs kappa_depth_2 /= 0 (hmix_gm.F90:724-730)");
+  if (cfg->hmix_tracer == 3 && cfg->gm_kappa_type == 1 && cfg->gm_kappa_freq == 0) return bad("gm_kappa_type = 1 ('bfre') needs gm_kappa_freq = 1 | 2: 'kappa_freq should not be set to never when model fields dependent kappa types are chosen' (hmix_gm.F90:756-780; no N^2 file here)");
+  if (cfg->gm_kappa_type < 0 || cfg->gm_kappa_type > 2) return bad("gm_kappa_type: 0 constant, 1 bfre, 2 depth (the other kappa choices of hmix_gm_nml are not built)");
+  if (cfg->gm_kappa_freq < 0 || cfg->gm_kappa_freq > 2) return bad("gm_kappa_freq: 0 never, 1 every_time_step, 2 once_a_day");
+  if (cfg->gm_kappa_freq == 2 && cfg->tmix_opt == 1) return bad("gm_kappa_freq = once_a_day with time_mix_opt 'avg' (half steps that do not fit the day: the end-of-day test of time_management.F90:3586-3592 on the calendar) is not built: avgfit, robert or none");
+  if (cfg->gm_slope_control < 0 || cfg->gm_slope_control > 3) return bad("gm_slope_control: 0 notanh, 1 tanh, 2 clip, 3 Gerd");
+  if (cfg->gm_slope_control == 2 && cfg->gm_transition_layer) return bad("gm_slope_control = clip with the transition layer (SLA_SAVE is formed before the slopes are clipped, hmix_gm.F90:1234-1245) is not built");
+  if (cfg->ah_bolus < 0.0 || cfg->ah_bkg_srfbl < 0.0 || cfg->slm_r < 0.0 || cfg->slm_b < 0.0) return bad("ah_bolus, ah_bkg_srfbl, slm_r, slm_b: >= 0 (0 = ah, ah, 0.3, 0.3)");
+  if (cfg->partial_bottom_cells != 0 && cfg->partial_bottom_cells != 1) return bad("partial_bottom_cells: 0 or 1");
+  if (cfg->partial_bottom_cells && grid && grid->DZBC == nullptr && grid->KMT != nullptr) return bad("partial_bottom_cells with a topography record needs pop_grid_input.DZBC (the record of bottom_cell_file)");
+  if (cfg->lsw_absorb != 0 && cfg->lsw_absorb != 1) return bad("lsw_absorb: 0 or 1");
+  if (cfg->nx_global < 1 || cfg->ny_global < 1 || cfg->km < 2 || cfg->block_size_x < 1 || cfg->block_size_y < 1) return bad("domain / block sizes must be positive (km >= 2)");
+  if (cfg->ew_boundary != 0 && cfg->ew_boundary != 1) return bad("ew_boundary: 0 closed, 1 cyclic");
+  if (cfg->ns_boundary < 0 || cfg->ns_boundary > 2) return bad("ns_boundary: 0 closed, 1 cyclic, 2 tripole");
+  if (cfg->hmix_momentum == 3 && cfg->struct_version < 6) return bad("hmix_momentum = 3 (anis) needs pop_config struct_version 6: the hmix_aniso_nml members (include/pop_amd.h)");
+  if (cfg->hmix_momentum != 2 && cfg->hmix_momentum != 4 && cfg->hmix_momentum != 3) return bad("hmix_momentum: 2 (del2), 4 (del4) or 3 (anis)");
+  if (cfg->hmix_momentum == 3) {   // hmix_aniso_nml (hmix_aniso.F90:167-347)
+    if (cfg->aniso_alignment == 2)
+      return bad("aniso_alignment = 2 ('flow') is not built: hmix_aniso.F90:787-794 resets the whole NORM1 / NORM2 block array whenever one point is "
+                 "slower than eps (land points have U = 0), so the reference's result depends on the block's loop order");
+    if (cfg->aniso_alignment != 0 && cfg->aniso_alignment != 1) return bad("aniso_alignment: 0 'grid', 1 'east' (2 'flow' is not built)");
+    if (cfg->lvariable_hmix_aniso != 0 && cfg->lvariable_hmix_aniso != 1) return bad("lvariable_hmix_aniso: 0 or 1");
+    if (cfg->lsmag_aniso != 0 && cfg->lsmag_aniso != 1) return bad("lsmag_aniso: 0 or 1");
+    if (cfg->lsmag_aniso && cfg->smag_lat_fact == 0.0) return bad("lsmag_aniso with smag_lat_fact = 0: the reference leaves F_PERP_SMAG unset then (hmix_aniso.F90:512-531)");
+    if (cfg->vconst_5 < 0) return bad("vconst_5: >= 0 (0 = 3)");
+    if (cfg->vconst_7 < 0.0 || cfg->smag_lat_gauss < 0.0) return bad("vconst_7, smag_lat_gauss: > 0 (0 = 45, 98)");
+  }
+  if (cfg->hmix_tracer != 2 && cfg->hmix_tracer != 4 && cfg->hmix_tracer != 3) return bad("hmix_tracer: 2 (del2), 4 (del4) or 3 (gm)");
+  if (cfg->lsubmesoscale_mixing != 0 && cfg->lsubmesoscale_mixing != 1) return bad("lsubmesoscale_mixing: 0 or 1");
+  if (cfg->lsubmesoscale_mixing) {   // mix_submeso_nml (mix_submeso.F90:164-232); a struct_version < 7 never gets here: its switch is not read
+    if (cfg->hmix_tracer != 3)
+      return bad("lsubmesoscale_mixing with hmix_tracer = 2 | 4 is not built: the reference allows it (horizontal_mix.F90:566-581), CESM never selects it, "
+                 "and the del2 / del4 tracer right-hand-side kernels have no additive tendency input; use hmix_tracer = 3 (gm)");
+    if (cfg->partial_bottom_cells) return bad("lsubmesoscale_mixing with partial_bottom_cells: its fluxes use dz(k), as Gent-McWilliams', which is refused with them");
+    if (cfg->luse_const_horiz_len_scale != 0 && cfg->luse_const_horiz_len_scale != 1) return bad("luse_const_horiz_len_scale: 0 or 1");
+    if (cfg->submeso_diag != 0 && cfg->submeso_diag != 1) return bad("submeso_diag: 0 or 1");
+    if (cfg->efficiency_factor < 0.0) return bad("efficiency_factor: >= 0 (0 = 0.07)");
+    if (cfg->time_scale_constant < 0.0) return bad("time_scale_constant: >= 0 (0 = 3.456e5 s)");
+    if (cfg->hor_length_scale < 0.0) return bad("hor_length_scale: >= 0 (0 = 5e5 cm)");
+  }
+  if (cfg->vmix_choice < 1 || cfg->vmix_choice > 3) return bad("vmix_choice: 1 const, 2 rich, 3 kpp");
+  if (cfg->tadvect < 1 || cfg->tadvect > 3) return bad("tadvect: 1 centered, 2 upwind3, 3 lw_lim");
+  if (cfg->solver_choice < 1 || cfg->solver_choice > 3) return bad("solver_choice: 1 pcg, 2 ChronGear, 3 PCSI");
+  if (cfg->preconditioner_choice != 0 && cfg->preconditioner_choice != 1) return bad("preconditioner_choice: 0 diagonal, 1 evp");
+  if (cfg->stepped_bathymetry != 0 && cfg->stepped_bathymetry != 1) return bad("stepped_bathymetry: 0 flat, 1 stepped");
+  if (cfg->distribution_type != 0 && cfg->distribution_type != 1) return bad("distribution_type: 0 equal block counts, 1 balanced by ocean columns");
+  if (cfg->kpp_ml_diagnostics != 0 && cfg->kpp_ml_diagnostics != 1) return bad("kpp_ml_diagnostics: 0 off, 1 HMXL and HMXL_DR every step");
+  if (cfg->max_iterations < 1 || cfg->convergence_check_freq < 1) return bad("max_iterations and convergence_check_freq must be >= 1");
+  if (cfg->tmix_opt < 0 || cfg->tmix_opt > 3) return bad("tmix_opt: 0 none, 1 avg, 2 avgfit, 3 robert");
+  if ((cfg->tmix_opt == 1 || cfg->tmix_opt == 2) && cfg->time_mix_freq < 1) return bad("time_mix_freq must be >= 1");
+  if (cfg->steps_per_day < 1) return bad("steps_per_day must be >= 1");
+  if (cfg->aidif != 1.0) return bad("aidif: only the fully implicit vertical mixing (aidif = 1) is built");
+  if (cfg->vmix_choice == 3 && cfg->lshort_wave && (cfg->sw_absorption_type < 0 || cfg->sw_absorption_type > 2)) return bad("KPP lshort_wave: sw_absorption_type 0 top-layer, 1 jerlov, 2 chlorophyll");
+  if (cfg->jerlov_water_type < 0 || cfg->jerlov_water_type > 5) return bad("jerlov_water_type: 1..5 (0 = 3)");
+  if (cfg->lsw_absorb != 0 && (cfg->sw_absorption_type < 0 || cfg->sw_absorption_type > 2)) return bad("lsw_absorb: sw_absorption_type 0 top-layer, 1 jerlov, 2 chlorophyll");
+  if (cfg->vmix_choice == 3 && cfg->num_v_smooth_Ri < 1) return bad("KPP: num_v_smooth_Ri must be >= 1 (the reference leaves FRI unset otherwise)");
+  if (!(cfg->convergence_criterion >= 0.0)) return bad("convergence_criterion must be >= 0");
+  return 0;
 }
 
 int host_build(HostModel &h) {

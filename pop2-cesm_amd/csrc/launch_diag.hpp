@@ -34,9 +34,7 @@ size_t diag_n_after(const pop_ctx *c) { return (size_t)c->h.nblocks_tot * diag_n
 size_t diag_n_cfl(const pop_ctx *c) { return (size_t)c->h.nblocks_tot * c->h.km * DIAG_NQ_CFL * 2; }
 
 int diag_pinned(pop_ctx *c, double **p, size_t n) {
-  if (*p) return 0;
-  HIPCHK(c, hipHostMalloc((void **)p, n * sizeof(double)));
-  return 0;
+  return *p ? 0 : pinned_alloc(c, p, n);
 }
 int diag_alloc_vec(pop_ctx *c) {
   DiagState &D = c->diag;

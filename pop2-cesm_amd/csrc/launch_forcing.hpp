@@ -37,9 +37,7 @@ int cpl_init_device(pop_ctx *c, CplState &s) {
     if (dev_upload(c, &s.MS_IND, c->msb.ind.data(), c->msb.ind.size()) || dev_upload(c, &s.MS_FRAC, c->msb.mask_frac.data(), c->msb.mask_frac.size())) return 1;
     if (dev_alloc(c, &s.MS_T, a2) || dev_alloc(c, &s.ms_sums, POP_MAX_MS)) return 1;
   }
-  HIPCHK(c, hipHostMalloc((void **)&s.h_raw, a2 * X_NF * sizeof(double)));
-  HIPCHK(c, hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming));
-  return 0;
+  return pinned_alloc(c, &s.h_raw, a2 * X_NF) || new_event(c, &s.ev_up);
 }
 
 template <class K, class A>

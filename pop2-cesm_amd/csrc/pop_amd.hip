@@ -1,7 +1,9 @@
-// pop_amd.hip -- context, launch orchestration (the step_mod.F90 call sequence) and the C ABI of
+// pop_amd.hip -- launch orchestration (the step_mod.F90 call sequence) and the C ABI of
 // libpop_amd.so.  gfx950 only.  See include/pop_amd.h for the boundary and DESIGN.md for the
 // kernel list.  The product path has no CPU fallback: every compute entry point fails loudly
-// when the context was created host-only or no HIP device is usable.
+// when the context was created host-only or no HIP device is usable.  The context is declared in
+// pop_ctx.hpp; pop_create_tuned fills it through the steps of create_device.hpp, and pop_destroy
+// releases what the context's ownership lists hold.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -39,6 +41,7 @@ using namespace pop;
 #include "launch_tavg.hpp"
 #include "launch_diag.hpp"
 #include "launch_forcing.hpp"
+#include "create_device.hpp"
 
 namespace {
 
@@ -152,6 +155,22 @@ int count_is(pop_ctx *c, long long have, long long want, const char *name) {
   c->err = name ? std::string("count mismatch for ") + name : std::string("count mismatch");
   return 1;
 }
+// ---- how every pop_init_* opens, stated once: a context, the namelist struct of this library's size (nml = null: the call takes
+// none), a context with fields, the first call.  `twice` is the entry point's own wording of the last
+int init_arg(pop_ctx *c, const char *fn, const char *nml, size_t want, const int *struct_bytes, bool inited, const char *twice = "called a second time (once per context)") {
+  if (!c) return 1;
+  const std::string who = std::string(fn) + ": ";
+  if (nml && (!struct_bytes || *struct_bytes != (int)want)) { c->err = who + nml + ".struct_bytes is not sizeof(" + nml + ") of this library (" + std::to_string(want) + ")"; return 1; }
+  if (c->h.plan_only) { c->err = who + "the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+  if (inited) { c->err = who + twice; return 1; }
+  return 0;
+}
+// ... and closes its checks: nothing has run yet (a restart file that was read counts as a run)
+int init_before_steps(pop_ctx *c, const char *fn, const char *hint = "call it right after pop_create") {
+  if (!c->ran && c->nsteps_total <= 0) return 0;
+  c->err = std::string(fn) + ": a step or a phase has already run (" + hint + ")";
+  return 1;
+}
 template <class V, class T>
 int copy_out(pop_ctx *c, const V &v, T *host, long long count, const char *name) {   // a host vector to the caller's array
   if (count_is(c, (long long)v.size(), count, name)) return 1;
@@ -251,96 +270,19 @@ int pop_read_grid_files(const char *horiz_grid_file, const char *topography_file
   return 0;
 }
 
+// The host model first (configuration, blocks, grid, halo plan: host_setup.cpp), then the plan (forms.hpp), then the device half as
+// the steps of create_device.hpp in their order
 int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const pop_tuning *tuning, int rank, int nranks, int flags, pop_ctx **out) {
   if (!cfg_in || !out || nranks < 1 || rank < 0 || rank >= nranks) return 1;
   pop_ctx *c = new pop_ctx();
   *out = c;
-  // a version-5 caller's struct ends at kappa_depth_scale, a version-6 caller's at smag_lat_gauss: read that much only (the later members stay 0)
-  if (cfg_in->struct_version == POP_CONFIG_VERSION) c->h.c = *cfg_in;
-  else if (cfg_in->struct_version == 6) memcpy(&c->h.c, cfg_in, offsetof(pop_config, lsubmesoscale_mixing));
-  else memcpy(&c->h.c, cfg_in, offsetof(pop_config, aniso_alignment));
-  const pop_config *cfg = &c->h.c;
   c->h.rank = rank; c->h.nranks = nranks;
-  if (cfg->hmix_tracer == 3 && cfg->gm_transition_layer == 1 && cfg->vmix_choice == 3) c->h.c.kpp_ml_diagnostics = 1;   // the diabatic depth of the transition layer is the smoothed HMXL (hmix_gm.F90:1226-1228)
-  if (cfg->lsubmesoscale_mixing == 1 && cfg->vmix_choice == 3) c->h.c.kpp_ml_diagnostics = 1;   // ML_DEPTH of submeso_sf is HMXL (mix_submeso.F90:424-426)
   if (tuning && tuning->struct_bytes != (int)sizeof(pop_tuning)) { c->err = "pop_create_tuned: pop_tuning.struct_bytes does not match this library (use pop_tuning_init)"; return 1; }
   tuning_resolve(c->h.tun, tuning);
   c->grid_from_input = grid != nullptr;
   if (grid && !(grid->ULAT && grid->ULON && grid->HTN && grid->HTE && grid->HUS && grid->HUW)) { c->err = "pop_create_with_grid: ULAT, ULON, HTN, HTE, HUS, HUW are required"; return 1; }
+  if (config_read_check(cfg_in, grid, c->h.c, c->err)) return 1;
   c->h.gin = grid;
-  {   // every option this library does not implement is refused here, before anything is built (the reference aborts
-      // in the init routine of the option's own module, e.g. vertical_mix.F90:280-296, POP_SolversMod.F90:442-472)
-    auto bad = [&](const std::string &m) { c->err = "pop_create: " + m; return 1; };
-    if (cfg->struct_version != POP_CONFIG_VERSION && cfg->struct_version != 6 && cfg->struct_version != 5) return bad("pop_config.struct_version is " + std::to_string(cfg->struct_version) + ", this library reads 5, 6 and " + std::to_string(POP_CONFIG_VERSION) + " (include/pop_amd.h)");
-    if (cfg->reserved_i[0] != 0) return bad("pop_config.reserved_i must be 0");
-    if (cfg->gm_kappa_bkg_srfbl != 0 && cfg->gm_kappa_bkg_srfbl != 1) return bad("gm_kappa_bkg_srfbl: 0 or 1");
-    if (cfg->ah_bkg_bottom < 0.0) return bad("ah_bkg_bottom: >= 0");
-    if (cfg->gm_diag_bolus != 0 && cfg->gm_diag_bolus != 1) return bad("gm_diag_bolus: 0 or 1");
-    if (cfg->gm_diag_bolus && cfg->hmix_tracer != 3) return bad("gm_diag_bolus needs hmix_tracer = 3");
-    if (cfg->gm_transition_layer != 0 && cfg->gm_transition_layer != 1) return bad("gm_transition_layer: 0 or 1");
-    if (cfg->gm_transition_layer && cfg->hmix_tracer != 3) return bad("gm_transition_layer needs hmix_tracer = 3");
-    // the reference aborts in init_gm: 'hmix_gm currently incompatible with partial bottom cells' (hmix_gm.F90:782-785) -- its slopes, stream-function
-    // terms and flux divergence use dz(k), the tracer budget DZT (accepted until round 3 with dz(k) throughout, tracer content not conserved)
-    if (cfg->hmix_tracer == 3 && cfg->partial_bottom_cells) return bad("hmix_tracer = 3 (Gent-McWilliams) with partial_bottom_cells: the reference refuses the combination (hmix_gm.F90:782-785), so does this library");
-    // hmix_gm.F90:724-730: kappa_depth_2 = 0 with the 'depth' profile aborts in init_gm
-    if (cfg->hmix_tracer == 3 && cfg->gm_kappa_type == 2 && cfg->kappa_depth_2 == 0.0) return bad("gm_kappa_type = 2 ('depth') needs kappa_depth_2 /= 0 (hmix_gm.F90:724-730)");
-    if (cfg->hmix_tracer == 3 && cfg->gm_kappa_type == 1 && cfg->gm_kappa_freq == 0) return bad("gm_kappa_type = 1 ('bfre') needs gm_kappa_freq = 1 | 2: 'kappa_freq should not be set to never when model fields dependent kappa types are chosen' (hmix_gm.F90:756-780; no N^2 file here)");
-    if (cfg->gm_kappa_type < 0 || cfg->gm_kappa_type > 2) return bad("gm_kappa_type: 0 constant, 1 bfre, 2 depth (the other kappa choices of hmix_gm_nml are not built)");
-    if (cfg->gm_kappa_freq < 0 || cfg->gm_kappa_freq > 2) return bad("gm_kappa_freq: 0 never, 1 every_time_step, 2 once_a_day");
-    if (cfg->gm_kappa_freq == 2 && cfg->tmix_opt == 1) return bad("gm_kappa_freq = once_a_day with time_mix_opt 'avg' (half steps that do not fit the day: the end-of-day test of time_management.F90:3586-3592 on the calendar) is not built: avgfit, robert or none");
-    if (cfg->gm_slope_control < 0 || cfg->gm_slope_control > 3) return bad("gm_slope_control: 0 notanh, 1 tanh, 2 clip, 3 Gerd");
-    if (cfg->gm_slope_control == 2 && cfg->gm_transition_layer) return bad("gm_slope_control = clip with the transition layer (SLA_SAVE is formed before the slopes are clipped, hmix_gm.F90:1234-1245) is not built");
-    if (cfg->ah_bolus < 0.0 || cfg->ah_bkg_srfbl < 0.0 || cfg->slm_r < 0.0 || cfg->slm_b < 0.0) return bad("ah_bolus, ah_bkg_srfbl, slm_r, slm_b: >= 0 (0 = ah, ah, 0.3, 0.3)");
-    if (cfg->partial_bottom_cells != 0 && cfg->partial_bottom_cells != 1) return bad("partial_bottom_cells: 0 or 1");
-    if (cfg->partial_bottom_cells && grid && grid->DZBC == nullptr && grid->KMT != nullptr) return bad("partial_bottom_cells with a topography record needs pop_grid_input.DZBC (the record of bottom_cell_file)");
-    if (cfg->lsw_absorb != 0 && cfg->lsw_absorb != 1) return bad("lsw_absorb: 0 or 1");
-    if (cfg->nx_global < 1 || cfg->ny_global < 1 || cfg->km < 2 || cfg->block_size_x < 1 || cfg->block_size_y < 1) return bad("domain / block sizes must be positive (km >= 2)");
-    if (cfg->ew_boundary != 0 && cfg->ew_boundary != 1) return bad("ew_boundary: 0 closed, 1 cyclic");
-    if (cfg->ns_boundary < 0 || cfg->ns_boundary > 2) return bad("ns_boundary: 0 closed, 1 cyclic, 2 tripole");
-    if (cfg->hmix_momentum == 3 && cfg->struct_version < 6) return bad("hmix_momentum = 3 (anis) needs pop_config struct_version 6: the hmix_aniso_nml members (include/pop_amd.h)");
-    if (cfg->hmix_momentum != 2 && cfg->hmix_momentum != 4 && cfg->hmix_momentum != 3) return bad("hmix_momentum: 2 (del2), 4 (del4) or 3 (anis)");
-    if (cfg->hmix_momentum == 3) {   // hmix_aniso_nml (hmix_aniso.F90:167-347)
-      if (cfg->aniso_alignment == 2)
-        return bad("aniso_alignment = 2 ('flow') is not built: hmix_aniso.F90:787-794 resets the whole NORM1 / NORM2 block array whenever one point is "
-                   "slower than eps (land points have U = 0), so the reference's result depends on the block's loop order");
-      if (cfg->aniso_alignment != 0 && cfg->aniso_alignment != 1) return bad("aniso_alignment: 0 'grid', 1 'east' (2 'flow' is not built)");
-      if (cfg->lvariable_hmix_aniso != 0 && cfg->lvariable_hmix_aniso != 1) return bad("lvariable_hmix_aniso: 0 or 1");
-      if (cfg->lsmag_aniso != 0 && cfg->lsmag_aniso != 1) return bad("lsmag_aniso: 0 or 1");
-      if (cfg->lsmag_aniso && cfg->smag_lat_fact == 0.0) return bad("lsmag_aniso with smag_lat_fact = 0: the reference leaves F_PERP_SMAG unset then (hmix_aniso.F90:512-531)");
-      if (cfg->vconst_5 < 0) return bad("vconst_5: >= 0 (0 = 3)");
-      if (cfg->vconst_7 < 0.0 || cfg->smag_lat_gauss < 0.0) return bad("vconst_7, smag_lat_gauss: > 0 (0 = 45, 98)");
-    }
-    if (cfg->hmix_tracer != 2 && cfg->hmix_tracer != 4 && cfg->hmix_tracer != 3) return bad("hmix_tracer: 2 (del2), 4 (del4) or 3 (gm)");
-    if (cfg->lsubmesoscale_mixing != 0 && cfg->lsubmesoscale_mixing != 1) return bad("lsubmesoscale_mixing: 0 or 1");
-    if (cfg->lsubmesoscale_mixing) {   // mix_submeso_nml (mix_submeso.F90:164-232); a struct_version < 7 never gets here: its switch is not read
-      if (cfg->hmix_tracer != 3)
-        return bad("lsubmesoscale_mixing with hmix_tracer = 2 | 4 is not built: the reference allows it (horizontal_mix.F90:566-581), CESM never selects it, "
-                   "and the del2 / del4 tracer right-hand-side kernels have no additive tendency input; use hmix_tracer = 3 (gm)");
-      if (cfg->partial_bottom_cells) return bad("lsubmesoscale_mixing with partial_bottom_cells: its fluxes use dz(k), as Gent-McWilliams', which is refused with them");
-      if (cfg->luse_const_horiz_len_scale != 0 && cfg->luse_const_horiz_len_scale != 1) return bad("luse_const_horiz_len_scale: 0 or 1");
-      if (cfg->submeso_diag != 0 && cfg->submeso_diag != 1) return bad("submeso_diag: 0 or 1");
-      if (cfg->efficiency_factor < 0.0) return bad("efficiency_factor: >= 0 (0 = 0.07)");
-      if (cfg->time_scale_constant < 0.0) return bad("time_scale_constant: >= 0 (0 = 3.456e5 s)");
-      if (cfg->hor_length_scale < 0.0) return bad("hor_length_scale: >= 0 (0 = 5e5 cm)");
-    }
-    if (cfg->vmix_choice < 1 || cfg->vmix_choice > 3) return bad("vmix_choice: 1 const, 2 rich, 3 kpp");
-    if (cfg->tadvect < 1 || cfg->tadvect > 3) return bad("tadvect: 1 centered, 2 upwind3, 3 lw_lim");
-    if (cfg->solver_choice < 1 || cfg->solver_choice > 3) return bad("solver_choice: 1 pcg, 2 ChronGear, 3 PCSI");
-    if (cfg->preconditioner_choice != 0 && cfg->preconditioner_choice != 1) return bad("preconditioner_choice: 0 diagonal, 1 evp");
-    if (cfg->stepped_bathymetry != 0 && cfg->stepped_bathymetry != 1) return bad("stepped_bathymetry: 0 flat, 1 stepped");
-    if (cfg->distribution_type != 0 && cfg->distribution_type != 1) return bad("distribution_type: 0 equal block counts, 1 balanced by ocean columns");
-    if (cfg->kpp_ml_diagnostics != 0 && cfg->kpp_ml_diagnostics != 1) return bad("kpp_ml_diagnostics: 0 off, 1 HMXL and HMXL_DR every step");
-    if (cfg->max_iterations < 1 || cfg->convergence_check_freq < 1) return bad("max_iterations and convergence_check_freq must be >= 1");
-    if (cfg->tmix_opt < 0 || cfg->tmix_opt > 3) return bad("tmix_opt: 0 none, 1 avg, 2 avgfit, 3 robert");
-    if ((cfg->tmix_opt == 1 || cfg->tmix_opt == 2) && cfg->time_mix_freq < 1) return bad("time_mix_freq must be >= 1");
-    if (cfg->steps_per_day < 1) return bad("steps_per_day must be >= 1");
-    if (cfg->aidif != 1.0) return bad("aidif: only the fully implicit vertical mixing (aidif = 1) is built");
-    if (cfg->vmix_choice == 3 && cfg->lshort_wave && (cfg->sw_absorption_type < 0 || cfg->sw_absorption_type > 2)) return bad("KPP lshort_wave: sw_absorption_type 0 top-layer, 1 jerlov, 2 chlorophyll");
-    if (cfg->jerlov_water_type < 0 || cfg->jerlov_water_type > 5) return bad("jerlov_water_type: 1..5 (0 = 3)");
-    if (cfg->lsw_absorb != 0 && (cfg->sw_absorption_type < 0 || cfg->sw_absorption_type > 2)) return bad("lsw_absorb: sw_absorption_type 0 top-layer, 1 jerlov, 2 chlorophyll");
-    if (cfg->vmix_choice == 3 && cfg->num_v_smooth_Ri < 1) return bad("KPP: num_v_smooth_Ri must be >= 1 (the reference leaves FRI unset otherwise)");
-    if (!(cfg->convergence_criterion >= 0.0)) return bad("convergence_criterion must be >= 0");
-  }
   c->h.plan_only = (flags & POP_CREATE_PLAN_ONLY) != 0;
   const int hb = host_build(c->h);
   c->h.gin = nullptr;
@@ -353,569 +295,25 @@ int pop_create_tuned(const pop_config *cfg_in, const pop_grid_input *grid, const
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { c->err = "no HIP device available; libpop_amd has no CPU fallback"; return 1; }
   HIPCHK(c, hipStreamCreate(&c->stream));
   c->own_stream = true;
-  const Forms &f = c->f;
-  HostModel &h = c->h;
-  DevGrid &g = c->g;
-  g.nxb = h.nxb; g.nyb = h.nyb; g.km = h.km; g.nt = h.nt; g.nblocks = h.nblocks;
-  g.n2 = (int)h.n2; g.n3 = (long long)h.n3;
-  g.xcd_remap = f.xcd_remap; g.lds_order = f.lds_order; g.red_band = f.red_band;   // workgroup orders (kernels_common.hpp)
-  g.ib = NGHOST + 1; g.ie = h.nxb - NGHOST; g.jb = NGHOST + 1; g.je = h.nyb - NGHOST;
-  {   // padded blocks (blocks.F90:174-265): per-block last physical column / row, only when some local block ends early
-    std::vector<int> ieb(h.nblocks), jeb(h.nblocks);
-    bool short_block = false;
-    for (int lb = 0; lb < h.nblocks; ++lb) {
-      const BlockInfo &B = h.all_blocks[h.local_ids[lb] - 1];
-      ieb[lb] = B.ie; jeb[lb] = B.je;
-      if (B.ie != g.ie || B.je != g.je) short_block = true;
-    }
-    g.ieb = nullptr; g.jeb = nullptr;
-    if (short_block) {
-      int *d0, *d1;
-      if (dev_upload(c, &d0, ieb.data(), ieb.size()) || dev_upload(c, &d1, jeb.data(), jeb.size())) return 1;
-      g.ieb = d0; g.jeb = d1;
-    }
-  }
-  // vertical arrays
-  {
-    struct { CArr *dst; std::vector<double> *src; } V[] = {
-      {&g.dz, &h.dz}, {&g.dzw, &h.dzw}, {&g.zt, &h.zt}, {&g.zw, &h.zw}, {&g.c2dz, &h.c2dz}, {&g.dzr, &h.dzr}, {&g.dz2r, &h.dz2r},
-      {&g.dzwr, &h.dzwr}, {&g.pressz, &h.pressz}, {&g.bouss, &h.bouss}, {&g.afac_t, &h.afac_t}, {&g.afac_u, &h.afac_u}};
-    for (auto &v : V) { double *p; if (dev_upload(c, &p, v.src->data(), v.src->size())) return 1; *v.dst = p; }
-    // per-level MWJF coefficients (k_state3d_lv): formed on the device
-    if (g.km + 1 <= 1024) {
-      double *p = nullptr;
-      std::vector<double> z((size_t)6 * (g.km + 2), 0.0);
-      if (dev_upload(c, &p, z.data(), z.size())) return 1;
-      hipLaunchKernelGGL(k_eos_level_table, dim3(1), dim3(g.km + 1), 0, 0, g, p);
-      HIPCHK(c, hipDeviceSynchronize());
-      g.eosP = p;
-    }
-    g.state_lv = f.state3d_levels;
-  }
-  // 2-D fields: upload the local blocks of every host field
-  for (auto &kv : h.f2) {
-    std::vector<double> all;
-    const std::vector<double> *src = &kv.second;
-    if (cfg->ns_boundary == 2 && kv.first == "centerWgtIndep") {
-      // Beyond a tripole fold the reference forms z = r / centerWgt in the ghost rows with the ghost cells' OWN centerWgt, whose four
-      // terms were added in the mirrored order: equal to the owner's value up to rounding only.  The fused solver kernels (and
-      // the exchange of z between ranks) give a ghost cell its owner's z instead; so that every solver path of this library
-      // agrees bit for bit, the device copy of the state-independent part of centerWgt takes the owners' values in those rows
-      // (the area and the mask in the other part are mirrored copies already).  The host copy keeps the reference's values.
-      all = kv.second;
-      host_halo_r8_loc(h, all.data(), 1, 0.0, 0, 0);
-      src = &all;
-    }
-    const int wgt = kv.first == "btropWgtNE" ? 1 : kv.first == "btropWgtEast" ? 2 : kv.first == "btropWgtNorth" ? 3 : 0;
-    if (wgt) {
-      // The reference forms the off-centre weights from i = 2, j = 2 of the block array on (POP_SolversMod.F90:795-815); the
-      // first row and column stay 0 and nothing reads them.  The two-iterations-per-launch P-CSI across ranks forms the operator at the
-      // first ring of ghost cells, whose west / south weights live in that row and column: the device copy holds them, made of the
-      // same two U-point terms in the same order.  The host copy keeps the reference's values.
-      all = kv.second;
-      const std::vector<double> &XW = h.f2.at("btropXW"), &YW = h.f2.at("btropYW");
-      const int nxb = h.nxb, nyb = h.nyb;
-      const size_t n2 = (size_t)nxb * nyb;
-      for (size_t b = 0; b < all.size() / n2; ++b)
-        for (int j = 0; j < nyb; ++j) for (int i = 0; i < nxb; ++i) {
-          if (i > 0 && j > 0) continue;
-          const size_t q = b * n2 + (size_t)j * nxb + i;
-          if (wgt == 1) all[q] = XW[q] + YW[q];
-          else if (wgt == 2 && j > 0) all[q] = XW[q] + XW[q - nxb] - YW[q] - YW[q - nxb];
-          else if (wgt == 3 && i > 0) all[q] = YW[q] + YW[q - 1] - XW[q] - XW[q - 1];
-        }
-      src = &all;
-    }
-    auto loc = local_part(h, *src); double *p; if (dev_upload(c, &p, loc.data(), loc.size())) return 1; c->d2[kv.first] = p;
-  }
-  for (auto &kv : h.i2) { auto loc = local_part(h, kv.second); int *p; if (dev_upload(c, &p, loc.data(), loc.size())) return 1; c->di2[kv.first] = p; }
-#define G2(f) g.f = c->d2[#f]
-  G2(DXU); G2(DYU); G2(DXUR); G2(DYUR); G2(UAREA_R); G2(TAREA_R); G2(TAREA); G2(FCOR); G2(FCORT); G2(HU); G2(HUR);
-  G2(AU0); G2(AUN); G2(AUE); G2(AUNE); G2(RCALCT); G2(DTN); G2(DTS); G2(DTE); G2(DTW);
-  G2(DUC); G2(DUN); G2(DUS); G2(DUE); G2(DUW); G2(DMC); G2(DMN); G2(DMS); G2(DME); G2(DMW); G2(DUM); G2(KXU); G2(KYU);
-  {   // byte copy of the solver mask (RCALCT: exactly 0 or 1, POP_SolversMod.F90:886)
-    const std::vector<double> mm = local_part(h, h.f2["mMask"]);
-    std::vector<unsigned char> m8(mm.size());
-    for (size_t p = 0; p < mm.size(); ++p) {
-      if (mm[p] != 0.0 && mm[p] != 1.0) { c->err = "solver mask is not 0/1"; return 1; }
-      m8[p] = mm[p] != 0.0;
-    }
-    unsigned char *d8;
-    if (dev_upload(c, &d8, m8.data(), m8.size())) return 1;
-    g.mMask8 = d8;
-  }
-  G2(mMask); G2(CHECKER); G2(CONSTNT); G2(SMF1); G2(SMF2); G2(SMFT1); G2(SMFT2);
-  g.pbc = cfg->partial_bottom_cells ? 1 : 0;
-  if (g.pbc) { G2(DZBC); G2(DZUB); }
-#undef G2
-  if (dev_alloc(c, &g.dump, 8192)) return 1;
-  { double *z; if (dev_alloc(c, &z, 64)) return 1; g.zero = z; }
-  {   // land elimination (DevGrid::opre): prefix count of the cells that have an ocean T cell within two cells in either
-      // direction.  The margin is what makes the skipped values independent of the state: every field the full kernels write
-      // on a cell further than one stencil from any ocean cell (tgrid_to_ugrid averages, gradients at land U points, ...) is a
-      // constant.  Ghost cells count with the KMT their halo update gave them.
-    const std::vector<int> kmt = local_part(h, h.i2["KMT"]);
-    std::vector<int> pre((size_t)(h.n2 + 1) * h.nblocks);
-    long long tiles = 0, land = 0;
-    for (int b = 0; b < h.nblocks; ++b) {
-      const int *K = kmt.data() + (size_t)b * h.n2;
-      int *P = pre.data() + (size_t)b * (h.n2 + 1);
-      const BlockInfo &B = h.all_blocks[h.local_ids[b] - 1];
-      P[0] = 0;
-      for (int j = 0; j < h.nyb; ++j)
-        for (int i = 0; i < h.nxb; ++i) {
-          // ghost cells beyond a closed boundary are rewritten with the fill value by every halo update and recomputed by the
-          // whole-block kernels of averaging steps: their values do depend on the step, so they count as cells to compute
-          int near = (B.i_glob[i] == 0 || B.j_glob[j] == 0) ? 1 : 0;
-          for (int dj = -2; dj <= 2 && !near; ++dj)
-            for (int di = -2; di <= 2; ++di) {
-              const int ii = i + di, jj = j + dj;
-              if (ii >= 0 && ii < h.nxb && jj >= 0 && jj < h.nyb && K[(size_t)jj * h.nxb + ii] > 0) { near = 1; break; }
-            }
-          P[(size_t)j * h.nxb + i + 1] = P[(size_t)j * h.nxb + i] + near;
-        }
-      for (int j = 0; j < h.nyb; ++j)
-        for (int i0 = 0; i0 < h.nxb; i0 += 64) {
-          const int i1 = std::min(i0 + 64, h.nxb);
-          ++tiles;
-          if (P[(size_t)j * h.nxb + i1] == P[(size_t)j * h.nxb + i0]) ++land;
-        }
-    }
-    int *d;
-    if (dev_upload(c, &d, pre.data(), pre.size())) return 1;
-    g.opre = d;
-    g.skip = 0;
-    c->opre_host = pre;
-    for (int R : {4, 8}) {   // DevGrid::lds_act4 / lds_act8
-      const int ntx = (h.nxb - 2 * NGHOST + POP_COL_THREADS - 1) / POP_COL_THREADS, nty = (h.nyb - 2 * NGHOST + R - 1) / R;
-      if (ntx > 0xffff || nty > 0x7fff) continue;
-      // tiles in the numbering the launch order is built on (patch by patch for lds_order 1, row-major otherwise)
-      std::vector<std::vector<int>> act(h.nblocks);
-      size_t longest = 0;
-      for (int b = 0; b < h.nblocks; ++b) {
-        const int *P = pre.data() + (size_t)b * (h.n2 + 1);
-        for (int gi = 0; gi < ntx * nty; ++gi) {
-          int ti, tj;
-          if (g.lds_order) { if (!lds_tile_from_gi(gi, ntx, nty, ti, tj)) continue; }
-          else { ti = gi % ntx; tj = gi / ntx; }
-          const int i0 = NGHOST + ti * POP_COL_THREADS, i1 = std::min(i0 + POP_COL_THREADS, h.nxb);
-          int n = 0;
-          for (int j = NGHOST + tj * R; j < std::min(NGHOST + tj * R + R, h.nyb); ++j) n += P[(size_t)j * h.nxb + i1] - P[(size_t)j * h.nxb + i0];
-          if (n) act[b].push_back(tj << 16 | ti);
-        }
-        longest = std::max(longest, act[b].size());
-      }
-      if (longest == 0 || longest == (size_t)ntx * nty) continue;
-      // lds_order 1: the a-th tile WITH OCEAN goes where the a-th tile of the full numbering would: runs of 32 such tiles -- a
-      // compact patch -- to one XCD, so the halo rows neighbouring tiles share are still fetched into one L2 (a plain packed list
-      // would deal consecutive tiles to eight different XCDs: measured 1.34 x the algorithmic traffic for the momentum kernel
-      // against 1.15 x)
-      if (g.lds_order) longest = 256 * ((longest + 255) / 256);
-      std::vector<int> list((size_t)longest * h.nblocks, -1);
-      for (int b = 0; b < h.nblocks; ++b)
-        for (size_t a = 0; a < act[b].size(); ++a) list[(size_t)b * longest + (g.lds_order ? (size_t)lds_slot_of((int)a) : a)] = act[b][a];
-      int *dl;
-      if (dev_upload(c, &dl, list.data(), list.size())) return 1;
-      if (R == 4) { g.lds_act4 = dl; g.lds_n4 = (int)longest; } else { g.lds_act8 = dl; g.lds_n8 = (int)longest; }
-    }
-    c->land_fraction = tiles ? (double)land / (double)tiles : 0.0;
-    c->full_left = f.land_full_steps;
-  }
-  g.WNE = c->d2["btropWgtNE"]; g.WEa = c->d2["btropWgtEast"]; g.WNo = c->d2["btropWgtNorth"]; g.WC0 = c->d2["centerWgtIndep"];
-  g.XW = c->d2["btropXW"]; g.YW = c->d2["btropYW"];
-  if (cfg->hmix_tracer == 4) { g.DTN = c->d2["d4DTN"]; g.DTS = c->d2["d4DTS"]; g.DTE = c->d2["d4DTE"]; g.DTW = c->d2["d4DTW"]; }
-  if (cfg->hmix_momentum == 4) {
-    g.DUC = c->d2["d4DUC"]; g.DUN = c->d2["d4DUN"]; g.DUS = c->d2["d4DUS"]; g.DUE = c->d2["d4DUE"]; g.DUW = c->d2["d4DUW"];
-    g.DMC = c->d2["d4DMC"]; g.DMN = c->d2["d4DMN"]; g.DMS = c->d2["d4DMS"]; g.DME = c->d2["d4DME"]; g.DMW = c->d2["d4DMW"]; g.DUM = c->d2["d4DUM"];
-  }
-  if (cfg->hmix_tracer == 4 || cfg->hmix_momentum == 4) { c->mix.D4AMF = c->d2["D4AMF"]; c->mix.D4AHF = c->d2["D4AHF"]; }
-  if (cfg->hmix_momentum == 3) {   // anisotropic viscosity: the friction fields and the variable viscosities (local blocks)
-    const size_t a3h = h.n3 * h.nblocks;
-    if (dev_alloc(c, &c->HDU, a3h) || dev_alloc(c, &c->HDV, a3h)) return 1;
-    if (cfg->lvariable_hmix_aniso) {
-      const std::vector<double> fpa = local_part3(h, h.aniso_f[0]), fpe = local_part3(h, h.aniso_f[1]);
-      if (dev_upload(c, &c->FPARA, fpa.data(), fpa.size()) || dev_upload(c, &c->FPERP, fpe.data(), fpe.size())) return 1;
-    }
-  }
-  if (cfg->tadvect == 2) {
-    const char *nx[6] = {"TALFXP", "TBETXP", "TGAMXP", "TALFXM", "TBETXM", "TDELXM"};
-    const char *ny[6] = {"TALFYP", "TBETYP", "TGAMYP", "TALFYM", "TBETYM", "TDELYM"};
-    for (int t = 0; t < 6; ++t) {
-      c->upw3.cx[t] = c->d2[nx[t]]; c->upw3.cy[t] = c->d2[ny[t]];
-      double *p; if (dev_upload(c, &p, h.upw_z[t].data(), h.upw_z[t].size())) return 1;
-      c->upw3.cz[t] = p;
-    }
-  }
-  if (cfg->tadvect == 3) {   // lw_lim: three flux-velocity fields, three work fields per tracer
-    const size_t a3l = h.n3 * h.nblocks;
-    if (dev_alloc(c, &c->lw.UTE, a3l) || dev_alloc(c, &c->lw.VTN, a3l) || dev_alloc(c, &c->lw.WTKB, a3l)) return 1;
-    for (int n = 0; n < 2; ++n) if (dev_alloc(c, &c->lw.XOUT[n], a3l) || dev_alloc(c, &c->lw.XSTAR[n], a3l) || dev_alloc(c, &c->lw.XSTAR2[n], a3l)) return 1;
-    c->lw.HTE = c->d2["HTE"]; c->lw.HTN = c->d2["HTN"]; c->lw.DXT = c->d2["DXT"]; c->lw.DYT = c->d2["DYT"];
-    if (!c->lw.HTE || !c->lw.HTN || !c->lw.DXT || !c->lw.DYT) { c->err = "lw_lim: grid fields HTE / HTN / DXT / DYT missing"; return 1; }
-  }
-  if (cfg->hmix_tracer == 3) {   // Gent-McWilliams: 14 coefficient fields + the tendency of each tracer
-    const size_t a3g = h.n3 * h.nblocks;
-    GmDev &G = c->gm;
-    for (int t = 0; t < 4; ++t) if (dev_alloc(c, &G.SLX[t], a3g) || dev_alloc(c, &G.SLY[t], a3g)) return 1;
-    for (int t = 0; t < 2; ++t) if (dev_alloc(c, &G.KI[t], a3g) || dev_alloc(c, &G.KT[t], a3g) || dev_alloc(c, &G.HD[t], a3g) || dev_alloc(c, &G.GTK[t], a3g)) return 1;
-    if (cfg->gm_kappa_type == 1) {   // KAPPA_VERTICAL: module state, 1 until the profile is computed (hmix_gm.F90:860)
-      if (dev_alloc(c, &G.KV, a3g, false)) return 1;
-      std::vector<double> ones(a3g, 1.0);
-      HIPCHK(c, hipMemcpy(G.KV, ones.data(), a3g * sizeof(double), hipMemcpyHostToDevice));
-    }
-    G.tlt = cfg->gm_transition_layer == 1;
-    if (G.tlt) {   // transition layer: SLA_SAVE of both halves, the layer's 2-D fields, the column terms of the merged stream function
-      const size_t a2g = h.n2 * h.nblocks;
-      for (int t = 0; t < 2; ++t) if (dev_alloc(c, &G.SLA[t], a3g)) return 1;
-      if (dev_alloc(c, &G.DD, a2g) || dev_alloc(c, &G.TH, a2g) || dev_alloc(c, &G.ID, a2g) || dev_alloc(c, &G.KL, a2g) || dev_alloc(c, &G.ZTW, a2g)) return 1;
-      for (int t = 0; t < 8; ++t) if (dev_alloc(c, &G.MW[t], a2g)) return 1;
-    }
-    if (cfg->gm_diag_bolus) {
-      if (dev_alloc(c, &G.UISOP, a3g) || dev_alloc(c, &G.VISOP, a3g) || dev_alloc(c, &G.WISOP, a3g)) return 1;
-      G.HTE = c->d2["HTE"]; G.HTN = c->d2["HTN"];
-      if (!G.HTE || !G.HTN) { c->err = "gm: HTE / HTN missing"; return 1; }
-    }
-    G.HYX = c->d2["gmHYX"]; G.HXY = c->d2["gmHXY"]; G.RBR = c->d2["gmRBR"]; G.DXT = c->d2["DXT"]; G.DYT = c->d2["DYT"];
-    if (!G.HYX || !G.HXY || !G.RBR || !G.DXT || !G.DYT) { c->err = "gm: grid fields missing"; return 1; }
-    // hmix_gm_nml (hmix_gm.F90:364-428); 0 = the value of the default set-up
-    G.ah = cfg->ah;
-    G.ah_bolus = (cfg->ah_bolus != 0.0) ? cfg->ah_bolus : cfg->ah;
-    G.ah_bkg_srfbl = (cfg->ah_bkg_srfbl != 0.0) ? cfg->ah_bkg_srfbl : cfg->ah;
-    G.slm_r = (cfg->slm_r != 0.0) ? cfg->slm_r : 0.3;
-    G.slm_b = (cfg->slm_b != 0.0) ? cfg->slm_b : 0.3;
-    G.slope_tanh = cfg->gm_slope_control == 1; G.slope_ctl = cfg->gm_slope_control;
-    G.HUS = c->d2["HUS"]; G.HUW = c->d2["HUW"];
-    if (cfg->gm_kappa_type == 2) {   // KAPPA_VERTICAL(k) = kappa_depth(k) (:850-874): a 1-D profile, uploaded as the level table the coefficient kernel reads
-      std::vector<double> kd(h.km + 2, 1.0);
-      const double sc = (cfg->kappa_depth_scale != 0.0) ? cfg->kappa_depth_scale : 150000.0;
-      for (int k = 1; k <= h.km; ++k) kd[k] = cfg->kappa_depth_1 + cfg->kappa_depth_2 * std::exp(-h.zt[k] / sc);
-      double *p = nullptr;
-      if (dev_upload(c, &p, kd.data(), kd.size())) return 1;
-      G.kdepth = p;
-    }
-    G.kappa_bkg = cfg->gm_kappa_bkg_srfbl == 1; G.ah_bkg_bottom = cfg->ah_bkg_bottom;
-    G.diff_tapering = G.slm_r != G.slm_b;                              // :964-968
-    G.cancellation = !(G.diff_tapering || G.ah != G.ah_bolus) && !G.tlt;   // :970-987 (both kappa types equal)
-    if (!G.cancellation && f.gm_sf_stored) for (int t = 0; t < 8; ++t) if (dev_alloc(c, &G.SF[t], a3g)) return 1;
-  }
-  if (cfg->lsubmesoscale_mixing) {   // submesoscale scheme: six 2-D fields; with submeso_diag the tendency alone and the velocities
-    const size_t a2s = h.n2 * h.nblocks, a3s = h.n3 * h.nblocks;
-    SubmDev &W = c->subm;
-    if (dev_alloc(c, &W.ML, a2s) || dev_alloc(c, &W.HLS, a2s)) return 1;
-    for (int t = 0; t < 4; ++t) if (dev_alloc(c, &W.B[t], a2s)) return 1;
-    if (cfg->submeso_diag) {
-      if (dev_alloc(c, &W.TD[0], a3s) || dev_alloc(c, &W.TD[1], a3s) || dev_alloc(c, &W.US, a3s) || dev_alloc(c, &W.VS, a3s) || dev_alloc(c, &W.WS, a3s)) return 1;
-    }
-    W.GTK[0] = c->gm.GTK[0]; W.GTK[1] = c->gm.GTK[1];
-    W.TS = c->d2["SUBM_TIME_SCALE"]; W.HYX = c->gm.HYX; W.HXY = c->gm.HXY; W.DXT = c->gm.DXT; W.DYT = c->gm.DYT; W.HTE = c->d2["HTE"]; W.HTN = c->d2["HTN"];
-    if (!W.TS || !W.HTE || !W.HTN) { c->err = "submeso: TIME_SCALE / HTE / HTN missing"; return 1; }
-    // mix_submeso_nml (mix_submeso.F90:183-188); 0 = the code default
-    W.eff = (cfg->efficiency_factor != 0.0) ? cfg->efficiency_factor : 0.07;
-    W.hls0 = (cfg->hor_length_scale != 0.0) ? cfg->hor_length_scale : 5.0e5;
-    W.max_hgs = 111.0e5;
-    W.const_hls = cfg->luse_const_horiz_len_scale;
-    W.all_levels = f.submeso_all_levels ? 1 : 0;
-  }
-#define GI(f) g.f = c->di2[#f]
-  GI(KMT); GI(KMU); GI(KMTN); GI(KMTS); GI(KMTE); GI(KMTW); GI(KMTEE); GI(KMTNN);
-#undef GI
-  const size_t a2 = h.n2 * h.nblocks, a3 = h.n3 * h.nblocks;
-  for (int t = 0; t < 3; ++t) {
-    for (int n = 0; n < h.nt; ++n) if (dev_alloc(c, &c->TR[n][t], a3)) return 1;
-    if (dev_alloc(c, &c->U[t], a3) || dev_alloc(c, &c->V[t], a3) || dev_alloc(c, &c->RHO[t], a3)) return 1;
-    if (dev_alloc(c, &c->PS[t], a2) || dev_alloc(c, &c->GX[t], a2) || dev_alloc(c, &c->GY[t], a2) || dev_alloc(c, &c->UB[t], a2) || dev_alloc(c, &c->VB[t], a2)) return 1;
-  }
-  for (int n = 0; n < h.nt; ++n)
-    if (dev_alloc(c, &c->STF[n], a2) || dev_alloc(c, &c->TFW[n], a2) || dev_alloc(c, &c->KPP_SRC[n], a3)) return 1;
-  if (h.nt > 2) {   // work fields of the passive tracers (pop_ctx.hpp)
-    if (cfg->hmix_tracer == 3 || cfg->hmix_tracer == 4) {
-      for (int n = 2; n < h.nt; ++n) if (dev_alloc(c, &c->PW[n], a3)) return 1;
-      if ((h.nt & 1) && dev_alloc(c, &c->PWX, a3)) return 1;
-    }
-    if (cfg->tadvect == 3 && (dev_alloc(c, &c->PL[0], a3) || dev_alloc(c, &c->PL[1], a3))) return 1;
-    if (cfg->lsubmesoscale_mixing && cfg->submeso_diag) {
-      for (int n = 2; n < h.nt; ++n) if (dev_alloc(c, &c->PTD[n], a3)) return 1;
-      if ((h.nt & 1) && dev_alloc(c, &c->PTDX, a3)) return 1;
-    }
-    if (cfg->vmix_choice == 3 && dev_alloc(c, &c->KPPX, a3)) return 1;
-  }
-  // Forms::vdc_shared: one array serves both tracer classes; pop_get_field("VDC", n) returns it for n = 0 and 1
-  if (dev_alloc(c, &c->VDC[0], (size_t)(h.km + 2) * a2)) return 1;
-  if (f.vdc_shared) c->VDC[1] = c->VDC[0];
-  else if (dev_alloc(c, &c->VDC[1], (size_t)(h.km + 2) * a2)) return 1;
-  double **two[] = {&c->PGUESS, &c->FW, &c->FW_OLD, &c->SHF_QSW, &c->CHL, &c->DH, &c->DHU, &c->ZX, &c->ZY, &c->UH, &c->VH, &c->W3, &c->W4, &c->RHS,
-                    &c->R, &c->S0, &c->S1, &c->Q, &c->Z, &c->AZ, &c->HBLT, &c->HMXL, &c->HMXL_DR};
-  for (auto p : two) if (dev_alloc(c, p, a2)) return 1;
-  c->centerWgt = c->d2["centerWgt"];
-  double **three[] = {&c->VVC, &c->E3, &c->F3, &c->S3a, &c->S3b, &c->S3c, &c->S3d};
-  for (auto p : three) if (dev_alloc(c, p, a3)) return 1;
-  c->d2t[0] = c->S3a; c->d2t[1] = c->S3b; c->d2u[0] = c->S3a; c->d2u[1] = c->S3b;
-  if (f.side_stream) {
-    HIPCHK(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_d2t, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_d2u, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_vmixu, hipEventDisableTiming));
-  }
-  if (f.del4_side && (dev_alloc(c, &c->d2t[0], a3) || dev_alloc(c, &c->d2t[1], a3) || dev_alloc(c, &c->d2u[0], a3) || dev_alloc(c, &c->d2u[1], a3))) return 1;
-  if (f.d2t_fuse && (dev_alloc(c, &c->d2t_next[0], a3) || dev_alloc(c, &c->d2t_next[1], a3))) return 1;
-  if (f.d2u_fuse && (dev_alloc(c, &c->d2u_next[0], a3) || dev_alloc(c, &c->d2u_next[1], a3))) return 1;
-  c->nchunk = red_grid_x(g);
-  {   // DevGrid::red_act: the chunks (256 consecutive cells) the fused solver kernels have to visit
-    const int nc = (int)((h.n2 + 255) / 256);
-    const bool multi = h.nranks > 1;
-    std::vector<std::vector<int>> act(h.nblocks), land(h.nblocks);
-    size_t longest = 0;
-    for (int b = 0; b < h.nblocks; ++b) {
-      const int *P = c->opre_host.data() + (size_t)b * (h.n2 + 1);
-      for (int k = 0; k < nc; ++k) {
-        const long long p0 = 256LL * k, p1 = std::min<long long>(p0 + 256, (long long)h.n2);
-        bool is_land = P[p1] == P[p0];
-        if (is_land && multi) {   // as red_land(g, deep): chunks within NGHOST of the edge of the physical domain work for other ranks
-          const int j0 = (int)(p0 / h.nxb), j1 = (int)((p1 - 1) / h.nxb);
-          const int i0 = (j0 == j1) ? (int)(p0 % h.nxb) : 0, i1 = (j0 == j1) ? (int)((p1 - 1) % h.nxb) : h.nxb - 1;
-          const BlockInfo &Bk = h.all_blocks[h.local_ids[b] - 1];
-          is_land = i0 >= g.ib - 1 + NGHOST && i1 <= Bk.ie - 1 - NGHOST && j0 >= g.jb - 1 + NGHOST && j1 <= Bk.je - 1 - NGHOST;
-        }
-        (is_land && !(b == 0 && k == 0) ? land[b] : act[b]).push_back(k);
-      }
-      longest = std::max(longest, act[b].size());
-      c->red_active_total += (int)act[b].size();
-    }
-    // launch order: workgroup w runs on XCD w % 8; XCD x takes one contiguous band of the chunks with ocean (as red_band does
-    // for the full launch), so the rows j +- 1 of the 9-point matvec are in the L2 that fetched row j.  The publishing workgroup
-    // (0,0) stays chunk 0.  Padding (land chunks) fills each band up to the common length.
-    longest = 16 * ((longest + 15) / 16);   // multiple of 16: k_fpcg_a_pair takes entries e and e + 8
-    std::vector<int> list((size_t)longest * h.nblocks), cnt_pad(h.nblocks);
-    bool can_pad = true;
-    for (int b = 0; b < h.nblocks; ++b) if (act[b].size() + land[b].size() < longest) can_pad = false;
-    for (int b = 0; b < h.nblocks && can_pad; ++b) {
-      std::vector<int> seq = act[b];
-      for (size_t w = act[b].size(); w < longest; ++w) seq.push_back(land[b][w - act[b].size()]);   // shorter list => it has land chunks to pad with
-      const size_t per = longest / 8;
-      for (size_t w = 0; w < longest; ++w) list[(size_t)b * longest + (w % per) * 8 + w / per] = seq[w];
-    }
-    if (!can_pad) longest = (size_t)nc;   // no list
-    if (longest < (size_t)nc) {
-      std::vector<int> cnt(h.nblocks);
-      for (int b = 0; b < h.nblocks; ++b) cnt[b] = (int)act[b].size();
-      if (dev_upload(c, &c->red_act, list.data(), list.size()) || dev_upload(c, &c->red_cnt, cnt.data(), cnt.size())) return 1;
-      c->red_nact = (int)longest;
-    }
-  }
-  if (dev_alloc(c, &c->partial, (size_t)c->nchunk * h.nblocks * 2 + POP_RELAY_SLACK) || dev_alloc(c, &c->blocksum, (size_t)h.nblocks_tot * 4)) return 1;
-  { std::vector<int> io(h.nblocks_tot); for (int b = 0; b < h.nblocks_tot; ++b) io[b] = b; if (dev_upload(c, &c->iota, io.data(), io.size())) return 1; }
-  if (dev_alloc(c, &c->sc, 1)) return 1;
-  { std::vector<int> gid(h.nblocks); for (int lb = 0; lb < h.nblocks; ++lb) gid[lb] = h.local_ids[lb] - 1; if (dev_upload(c, &c->gid, gid.data(), gid.size())) return 1; }
-  { std::vector<int> log(h.nblocks_tot, -1); for (int lb = 0; lb < h.nblocks; ++lb) log[h.local_ids[lb] - 1] = lb; if (dev_upload(c, &c->loc_of_gid, log.data(), log.size())) return 1; }
-  // halo plan lists
-  c->ncopy = (int)h.halo.copy_dst.size(); c->nfill = (int)h.halo.fill_dst.size();
-  if (c->ncopy && (dev_upload(c, &c->copy_dst, h.halo.copy_dst.data(), c->ncopy) || dev_upload(c, &c->copy_src, h.halo.copy_src.data(), c->ncopy))) return 1;
-  if (c->nfill && dev_upload(c, &c->fill_dst, h.halo.fill_dst.data(), c->nfill)) return 1;
-  for (auto &pp : h.halo.peers) {
-    DevPeer d; d.rank = pp.rank; d.nsend = (int)pp.send_src.size(); d.nrecv = (int)pp.recv_dst.size();
-    if (d.nsend && dev_upload(c, &d.send_src, pp.send_src.data(), d.nsend)) return 1;
-    if (d.nrecv && dev_upload(c, &d.recv_dst, pp.recv_dst.data(), d.nrecv)) return 1;
-    c->peers.push_back(d);
-  }
-  if (cfg->ns_boundary == 2) {   // tripole plan (non-empty on the rank that owns the top row of blocks) + evaluation buffer
-    size_t nmax = 1;
-    for (int loc = 0; loc < 5; ++loc) {
-      const TripolePlan &T = h.halo.tripole[loc];
-      c->tp_n[loc] = (int)T.dst.size();
-      nmax = std::max(nmax, T.dst.size());
-      if (c->tp_n[loc] && (dev_upload(c, &c->tp_dst[loc], T.dst.data(), T.dst.size()) || dev_upload(c, &c->tp_a[loc], T.a.data(), T.a.size()) ||
-                           dev_upload(c, &c->tp_b[loc], T.b.data(), T.b.size()))) return 1;
-    }
-    if (dev_alloc(c, &c->tp_buf, nmax * (size_t)(h.km + 2))) return 1;
-  }
-  {   // concatenated peer lists
-    std::vector<int> ss, st, sc, rd, rt, rc;
-    for (auto &pp : h.halo.peers) {
-      const int s0 = (int)ss.size(), r0 = (int)rd.size();
-      for (int v : pp.send_src) { ss.push_back(v); st.push_back(s0); sc.push_back((int)pp.send_src.size()); }
-      for (int v : pp.recv_dst) { rd.push_back(v); rt.push_back(r0); rc.push_back((int)pp.recv_dst.size()); }
-    }
-    c->nsend_all = (int)ss.size(); c->nrecv_all = (int)rd.size();
-    if (!h.halo.peers.empty()) {   // per-cell maps of the same lists for the kernels that pack / read a one-level message themselves
-      std::vector<int> smap(a2, -1), rmp(a2, -1), off(1, 0), slot;
-      std::map<int, std::vector<int>> by_cell;
-      for (size_t t = 0; t < ss.size(); ++t) by_cell[ss[t]].push_back((int)t);
-      for (auto &kv : by_cell) { smap[kv.first] = (int)off.size() - 1; for (int t : kv.second) slot.push_back(t); off.push_back((int)slot.size()); }
-      for (size_t t = 0; t < rd.size(); ++t) rmp[rd[t]] = (int)t;
-      // the same answer on every rank (the overlapped update uses the second communicator: all ranks or none): every
-      // block's east neighbour -- the cyclic one included -- is owned by the block's own rank, i.e. the shards are j-bands
-      c->halo_ns_only = true;
-      for (const BlockInfo &B : h.all_blocks) {
-        int ie = B.iblock + 1;
-        if (ie > h.nbx) { if (h.c.ew_boundary != 1) continue; ie = 1; }
-        for (const BlockInfo &E : h.all_blocks)
-          if (E.jblock == B.jblock && E.iblock == ie && h.block_owner[E.block_id - 1] != h.block_owner[B.block_id - 1]) c->halo_ns_only = false;
-      }
-      if (dev_upload(c, &c->sendmap, smap.data(), smap.size()) || dev_upload(c, &c->send_off, off.data(), off.size()) ||
-          dev_upload(c, &c->send_slot, slot.data(), std::max<size_t>(slot.size(), 1)) || dev_upload(c, &c->rmap, rmp.data(), rmp.size())) return 1;
-      HIPCHK(c, hipEventCreateWithFlags(&c->ev_sa, hipEventDisableTiming));
-      HIPCHK(c, hipEventCreateWithFlags(&c->ev_sx, hipEventDisableTiming));
-    }
-    if (c->nsend_all && (dev_upload(c, &c->sa_src, ss.data(), ss.size()) || dev_upload(c, &c->sa_start, st.data(), st.size()) || dev_upload(c, &c->sa_cnt, sc.data(), sc.size()))) return 1;
-    if (c->nrecv_all && (dev_upload(c, &c->ra_dst, rd.data(), rd.size()) || dev_upload(c, &c->ra_start, rt.data(), rt.size()) || dev_upload(c, &c->ra_cnt, rc.data(), rc.size()))) return 1;
-  }
-  {   // source map for the fused solver path: ghost cell -> local source cell, -1 = fill value
-    c->h_srcmap = local_srcmap(h);
-    if (dev_upload(c, &c->srcmap, c->h_srcmap.data(), c->h_srcmap.size())) return 1;
-    HIPCHK(c, hipHostMalloc((void **)&c->persist_out, 4 * sizeof(double)));
-    HIPCHK(c, hipHostMalloc((void **)&c->host_sc, sizeof(SolverScalars)));
-    HIPCHK(c, hipHostMalloc((void **)&c->host_rr, 8 * sizeof(double)));
-    for (auto &e : c->chk_ev) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (cfg->solver_choice == 3) {   // omega_k of P-CSI (POP_SolversMod.F90:1617-1620, 1695): a function of the eigenvalue bounds only
-      const double csalpha = 2.0 / (h.pcsi_max_eig - h.pcsi_min_eig);
-      const double csbeta = (h.pcsi_max_eig + h.pcsi_min_eig) / (h.pcsi_max_eig - h.pcsi_min_eig);
-      const double csy = csbeta / csalpha;
-      std::vector<double> om(cfg->max_iterations + 2);
-      om[0] = 1.0 / csy;
-      double csomga = 2.0 / csy;
-      for (int m = 1; m <= cfg->max_iterations; ++m) { csomga = 1.0 / (csy - csomga / (4.0 * csalpha * csalpha)); om[m] = csomga; }
-      c->pcsi_csy = csy;
-      if (dev_upload(c, &c->pcsi_omega, om.data(), om.size()) || dev_alloc(c, &c->pcsi_base, 1)) return 1;
-    }
-    if (use_evp(*cfg)) {   // EVP sub-blocks of the local blocks, coefficient arrays transposed to [cell][sub-block]
-      const EvpHost &E = h.evp;
-      const size_t nsb = (size_t)E.xnb * E.ynb, S = nsb * h.nblocks;
-      constexpr int NC = EVP_LD * EVP_LD, NR = EVP_LE * EVP_LE;
-      std::vector<int4> meta(S);
-      std::vector<double> cc(S * NC), ne(S * NC), icc(S * NC), ine(S * NC), rinv(S * NR);
-      for (int lb = 0; lb < h.nblocks; ++lb) {
-        const size_t gb = (size_t)h.local_ids[lb] - 1;
-        for (int j = 1; j <= E.ynb; ++j) for (int i = 1; i <= E.xnb; ++i) {
-          const size_t sl = lb * nsb + (size_t)(j - 1) * E.xnb + (i - 1), sg = gb * nsb + (size_t)(j - 1) * E.xnb + (i - 1);
-          const int is = E.xidx[i], ie = E.xidx[i + 1] + 1, js = E.yidx[j], je = E.yidx[j + 1] + 1;
-          int ocean = 0;   // w: no ocean cell in the interior of the sub-block (cells of no block at all count as land)
-          {
-            const std::vector<int> &KMT = h.i2.at("KMT");
-            for (int cj = js + 1; cj <= je - 1; ++cj) for (int ci = is + 1; ci <= ie - 1; ++ci)
-              if (KMT[gb * h.n2 + (size_t)(cj - 1) * h.nxb + (ci - 1)] > 0) ocean = 1;
-          }
-          meta[sl] = make_int4((int)(lb * h.n2 + (size_t)(js - 1) * h.nxb + (is - 1)), (ie - is + 1) | ((je - js + 1) << 8), E.land[sg], (E.land[sg] && !ocean) ? 1 : 0);
-          for (int q = 0; q < NC; ++q) {
-            cc[q * S + sl] = E.cc[sg * NC + q]; ne[q * S + sl] = E.ne[sg * NC + q];
-            icc[q * S + sl] = E.icc[sg * NC + q]; ine[q * S + sl] = E.ine[sg * NC + q];
-          }
-          for (int q = 0; q < NR; ++q) rinv[q * S + sl] = E.rinv[sg * NR + q];
-        }
-      }
-      int4 *dm; double *d0, *d1, *d2, *d3, *d4;
-      if (dev_upload(c, &dm, meta.data(), S) || dev_upload(c, &d0, cc.data(), cc.size()) || dev_upload(c, &d1, ne.data(), ne.size()) ||
-          dev_upload(c, &d2, icc.data(), icc.size()) || dev_upload(c, &d3, ine.data(), ine.size()) || dev_upload(c, &d4, rinv.data(), rinv.size())) return 1;
-      c->evp = EvpDev{(long long)S, dm, d0, d1, d2, d3, d4, c->d2["evpC0"], c->d2["btropWgtNE"]};
-      c->use_evp = true;
-    }
-    if (f.pcsi_two_step || f.pcsi_two_step_dist) {   // two P-CSI iterations per launch: the raw residual of a pair, the fold rows of a tripole
-      if (dev_alloc(c, &c->pcsi_raw, a2)) return 1;
-      std::vector<int> jfold;
-      pcsi_fold_local(h, c->h_srcmap, jfold);
-      if (cfg->ns_boundary == 2 && dev_upload(c, &c->pcsi_jfold, jfold.data(), jfold.size())) return 1;
-    }
-    if (f.replicated) {
-      const size_t NG = h.n2 * h.nblocks_tot;
-      SolveView &v = c->gv;
-      v.g = c->g; v.g.nblocks = h.nblocks_tot;
-      double *p;
-      if (dev_upload(c, &p, h.f2["btropWgtNE"].data(), NG)) return 1; v.g.WNE = p;
-      if (dev_upload(c, &p, h.f2["btropWgtEast"].data(), NG)) return 1; v.g.WEa = p;
-      if (dev_upload(c, &p, h.f2["btropWgtNorth"].data(), NG)) return 1; v.g.WNo = p;
-      if (dev_upload(c, &p, h.f2["btropXW"].data(), NG)) return 1; v.g.XW = p;
-      if (dev_upload(c, &p, h.f2["btropYW"].data(), NG)) return 1; v.g.YW = p;
-      if (dev_upload(c, &p, h.f2["centerWgtIndep"].data(), NG)) return 1; v.g.WC0 = p;
-      if (dev_upload(c, &p, h.f2["mMask"].data(), NG)) return 1; v.g.mMask = p;
-      { std::vector<unsigned char> m8(NG); for (size_t q = 0; q < NG; ++q) m8[q] = h.f2["mMask"][q] != 0.0;
-        unsigned char *d8; if (dev_upload(c, &d8, m8.data(), NG)) return 1; v.g.mMask8 = d8; }
-      if (dev_upload(c, &c->gTAREA, h.f2["TAREA"].data(), NG)) return 1;
-      if (dev_upload(c, &c->gKMT, h.i2["KMT"].data(), NG)) return 1;
-      double **vecs[] = {&v.X, &v.R, &v.Z, &v.S0, &v.S1, &v.Q, &v.RHS, &v.C};
-      for (auto q : vecs) if (dev_alloc(c, q, NG)) return 1;
-      if (dev_alloc(c, &v.partial, (size_t)c->nchunk * h.nblocks_tot * 2 + POP_RELAY_SLACK) || dev_alloc(c, &v.blocksum, (size_t)h.nblocks_tot * 4)) return 1;
-      std::vector<int> gsm = global_srcmap(h), gid(h.nblocks_tot);
-      for (int b = 0; b < h.nblocks_tot; ++b) gid[b] = b;
-      if (dev_upload(c, &v.srcmap, gsm.data(), gsm.size()) || dev_upload(c, &v.gid, gid.data(), gid.size())) return 1;
-      v.nchunk = c->nchunk; v.nblocks_tot = h.nblocks_tot;
-    }
-  }
-  // vmix_const: constant coefficients for all time (vmix_const.F90:121-122)
-  if (cfg->vmix_choice == 1) {
-    std::vector<double> v((size_t)(h.km + 2) * a2, cfg->const_vdc), w(a3, cfg->const_vvc);
-    HIPCHK(c, hipMemcpy(c->VDC[0], v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->VVC, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
-  if (mix_create(c->h, f, c->g, c->mix, c->allocs, c->err)) return 1;
-  c->KBL = const_cast<int *>(mix_kpp_kbl(c->mix));
-  if (cfg->lsw_absorb != 0 && sw_tables_create(c->h, c->allocs, c->err)) return 1;   // lsw_absorb without KPP's lshort_wave
-  if (c->h.sw.CHLI) {   // the default chlorophyll amount the table index was built for
-    std::vector<double> chl((size_t)c->g.n2 * c->g.nblocks, 0.25);
-    HIPCHK(c, hipMemcpy(c->CHL, chl.data(), chl.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
-  // KPP look-ahead (Forms::kpp_ahead): second set of KPP outputs, own stream
-  // (Gent-McWilliams adds its isopycnal part to VDC after vmix_coeffs -- to the arrays swapped in, at the step they belong to; with the
-  // mixed-layer-depth diagnostics the look-ahead writes a second pair HMXL / HMXL_DR that is swapped in with the rest)
-  if (f.kpp_ahead) {
-    for (int n = 0; n < 2; ++n) if (dev_alloc(c, &c->KPPa[n], a3)) return 1;
-    if (h.nt > 2 && dev_alloc(c, &c->KPPXa, a3)) return 1;
-    if (dev_alloc(c, &c->VDCa[0], (size_t)(h.km + 2) * a2)) return 1;
-    if (f.vdc_shared) c->VDCa[1] = c->VDCa[0];
-    else if (dev_alloc(c, &c->VDCa[1], (size_t)(h.km + 2) * a2)) return 1;
-    if (dev_alloc(c, &c->VVCa, a3) || dev_alloc(c, &c->HBLTa, a2) || dev_alloc(c, &c->KBLa, a2)) return 1;
-    if (c->h.c.kpp_ml_diagnostics == 1 && (dev_alloc(c, &c->HMXLa, a2) || dev_alloc(c, &c->HMXL_DRa, a2))) return 1;
-    HIPCHK(c, hipStreamCreateWithFlags(&c->ahead, hipStreamNonBlocking));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_ahead_fork, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_ahead, hipEventDisableTiming));
-  }
-  // initial state (initial.F90:1389-1427, 1660-1676): T,S on all three levels, RHO(cur), RHO(old)
-  c->oldt = 0; c->curt = 1; c->newt = 2; c->mixt = 1;
-  for (int t = 0; t < 3; ++t) {
-    HIPCHK(c, hipMemcpy(c->TR[0][t], h.f3["TEMP0"].data(), a3 * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->TR[1][t], h.f3["SALT0"].data(), a3 * sizeof(double), hipMemcpyHostToDevice));
-  }
-  launch_state3d(c->g, c->TR[0][c->curt], c->TR[1][c->curt], c->RHO[c->curt], c->stream);
-  launch_state3d(c->g, c->TR[0][c->oldt], c->TR[1][c->oldt], c->RHO[c->oldt], c->stream);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  h.f3.clear();
-  return 0;
+  return create_grid_device(c) || create_land_lists(c) || create_hmix_advect(c) || create_gm(c) || create_submeso(c) || create_state_fields(c) ||
+         create_solver_lists(c) || create_halo_device(c) || create_solver_device(c) || create_mix_and_ahead(c) || create_initial_state(c);
 }
 
+// Everything the context owns is in its four lists (pop_ctx.hpp); KPP keeps its own stream and events (kpp_destroy)
 int pop_destroy(pop_ctx *c) {
-  if (c) for (hipEvent_t &e : c->ev_solve) if (e) { hipEventDestroy(e); e = nullptr; }
   if (!c) return 0;
+  // copies into pinned buffers (an armed step's diagnostics, an import's upload) and exchanges may still be in flight
+  if (c->stream) hipStreamSynchronize(c->stream);
+  for (hipStream_t s : c->streams) hipStreamSynchronize(s);
   for (auto &g : c->graphs) hipGraphExecDestroy(g.exec);
-  if (c->host_sc) hipHostFree(c->host_sc);
-  if (c->host_rr) hipHostFree(c->host_rr);
-  if (c->persist_out) hipHostFree(c->persist_out);
-  if (c->diag.h_pre || c->diag.h_after || c->diag.h_cfl) {   // copies of an armed step may still be in flight
-    if (c->stream) hipStreamSynchronize(c->stream);
-    for (double *p : {c->diag.h_pre, c->diag.h_after, c->diag.h_cfl}) if (p) hipHostFree(p);
-  }
-  if (c->cpl.h_raw) {   // the upload of an import may still be in flight
-    if (c->stream) hipStreamSynchronize(c->stream);
-    hipHostFree(c->cpl.h_raw);
-  }
-  if (c->cpl.ev_up) hipEventDestroy(c->cpl.ev_up);
-  if (c->ev_fork) hipEventDestroy(c->ev_fork);
-  if (c->ev_d2t) hipEventDestroy(c->ev_d2t);
-  if (c->ev_d2u) hipEventDestroy(c->ev_d2u);
-  if (c->ev_vmixu) hipEventDestroy(c->ev_vmixu);
-  if (c->ahead) { hipStreamSynchronize(c->ahead); hipStreamDestroy(c->ahead); }
-  if (c->ev_ahead_fork) hipEventDestroy(c->ev_ahead_fork);
-  if (c->ev_ahead) hipEventDestroy(c->ev_ahead);
-  if (c->ev_sa) hipEventDestroy(c->ev_sa);
-  if (c->ev_sx) hipEventDestroy(c->ev_sx);
-  for (auto &e : c->chk_ev) if (e) hipEventDestroy(e);
+  for (void *p : c->pinned) hipHostFree(p);
+  for (hipEvent_t e : c->events) hipEventDestroy(e);
   if (c->rccl_tr) {
-    if (c->stream) hipStreamSynchronize(c->stream);
-    if (c->comm_side) hipStreamSynchronize(c->comm_side);
     if (c->rccl_tr->comm2) rccl().CommDestroy(c->rccl_tr->comm2);
     if (c->rccl_tr->comm) rccl().CommDestroy(c->rccl_tr->comm);
     delete c->rccl_tr;
   }
-  if (c->comm_side) hipStreamDestroy(c->comm_side);
-  if (c->side) { hipStreamSynchronize(c->side); hipStreamDestroy(c->side); }
+  for (hipStream_t s : c->streams) hipStreamDestroy(s);
   kpp_destroy(c->mix);
   for (void *p : c->allocs) hipFree(p);
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -1913,7 +1311,7 @@ static int barotropic_driver(pop_ctx *c, bool update_zx_zy) {
   hipLaunchKernelGGL(k_btrop_rhs2, G, B, 0, c->stream, c->g, sp, a);
   if (halo_update(c, c->RHS, 1)) return 1;
   solve_collect(c);
-  if (!c->ev_solve[0]) { HIPCHK(c, hipEventCreate(&c->ev_solve[0])); HIPCHK(c, hipEventCreate(&c->ev_solve[1])); }
+  if (!c->ev_solve[0] && (new_event(c, &c->ev_solve[0], hipEventDefault) || new_event(c, &c->ev_solve[1], hipEventDefault))) return 1;
   HIPCHK(c, hipEventRecord(c->ev_solve[0], c->stream));
   const int e = pop_solver_run(c);
   if (e) return e;
@@ -2350,7 +1748,7 @@ int pop_comm_init_rccl(pop_ctx *c, const unsigned char *id128) {
     for (int b = 0; b < 128; ++b) id2.internal[b] = (char)(unsigned char)enc[b];
     const int rc2 = rccl().CommInitRank(&t->comm2, c->h.nranks, id2, c->h.rank);
     if (rc2) { c->err = "pop_comm_init_rccl: second communicator: " + rccl().what(rc2); return 1; }
-    HIPCHK(c, hipStreamCreateWithFlags(&c->comm_side, hipStreamNonBlocking));
+    if (new_stream(c, &c->comm_side)) return 1;
     t->side = &c->comm_side;
     c->xchg_side = rccl_exchange_side;
   }
@@ -2468,11 +1866,7 @@ int pop_halo_plan_local(const pop_ctx *c, int *dst, int *src, int *fill_dst) {
 // ---- tidal mixing: tidal_nml and the energy-flux record through an entry point of their own (tidal_mixing.F90 init_tidal_mixing1 / 2)
 void pop_tidal_nml_init(pop_tidal_nml *nml) { if (nml) tidal_nml_defaults(*nml); }
 int pop_init_tidal_mixing(pop_ctx *c, const pop_tidal_nml *nml, const double *energy_flux, long long count) {
-  if (!c) return 1;
-  if (!nml || nml->struct_bytes != (int)sizeof(pop_tidal_nml)) { c->err = "pop_init_tidal_mixing: pop_tidal_nml.struct_bytes is not sizeof(pop_tidal_nml) of this library (" + std::to_string(sizeof(pop_tidal_nml)) + ")"; return 1; }
-  if (c->h.plan_only) { c->err = "pop_init_tidal_mixing: the context has no grid fields (POP_CREATE_PLAN_ONLY)"; return 1; }
-  if (c->tidal.inited) { c->err = "pop_init_tidal_mixing: called a second time (once per context)"; return 1; }
-  if (c->ran || c->nsteps_total > 0) { c->err = "pop_init_tidal_mixing: a step or a phase has already run (call it right after pop_create)"; return 1; }
+  if (init_arg(c, "pop_init_tidal_mixing", "pop_tidal_nml", sizeof(pop_tidal_nml), nml ? &nml->struct_bytes : nullptr, c && c->tidal.inited) || init_before_steps(c, "pop_init_tidal_mixing")) return 1;
   if (!nml->ltidal_mixing) { c->tidal.inited = true; c->tidal.nml = *nml; return 0; }   // builds nothing
   const pop_config &cf = c->h.c;
   if (cf.vmix_choice != 3) { c->err = "tidal mixing needs vmix_choice = 3 (kpp) (initial.F90:1962)"; return 1; }
@@ -2524,11 +1918,7 @@ int pop_init_tidal_mixing(pop_ctx *c, const pop_tidal_nml *nml, const double *en
 // ---- latitude-varying KPP background diffusivity (the lhoriz_varying_bckgrnd branch of init_vmix_kpp, vmix_kpp.F90:544-611)
 void pop_kpp_bckgrnd_nml_init(pop_kpp_bckgrnd_nml *nml) { if (nml) kpp_bckgrnd_nml_defaults(*nml); }
 int pop_init_kpp_bckgrnd(pop_ctx *c, const pop_kpp_bckgrnd_nml *nml) {
-  if (!c) return 1;
-  if (!nml || nml->struct_bytes != (int)sizeof(pop_kpp_bckgrnd_nml)) { c->err = "pop_init_kpp_bckgrnd: pop_kpp_bckgrnd_nml.struct_bytes is not sizeof(pop_kpp_bckgrnd_nml) of this library (" + std::to_string(sizeof(pop_kpp_bckgrnd_nml)) + ")"; return 1; }
-  if (c->h.plan_only) { c->err = "pop_init_kpp_bckgrnd: the context has no grid fields (POP_CREATE_PLAN_ONLY)"; return 1; }
-  if (c->bck.inited) { c->err = "pop_init_kpp_bckgrnd: called a second time (once per context)"; return 1; }
-  if (c->ran || c->nsteps_total > 0) { c->err = "pop_init_kpp_bckgrnd: a step or a phase has already run (call it right after pop_create)"; return 1; }
+  if (init_arg(c, "pop_init_kpp_bckgrnd", "pop_kpp_bckgrnd_nml", sizeof(pop_kpp_bckgrnd_nml), nml ? &nml->struct_bytes : nullptr, c && c->bck.inited) || init_before_steps(c, "pop_init_kpp_bckgrnd")) return 1;
   if (!nml->lhoriz_varying_bckgrnd) { c->bck.inited = true; c->bck.nml = *nml; return 0; }   // builds nothing
   const pop_config &cf = c->h.c;
   if (cf.vmix_choice != 3) { c->err = "lhoriz_varying_bckgrnd needs vmix_choice = 3 (kpp): it is a switch of vmix_kpp_nml"; return 1; }
@@ -2570,11 +1960,10 @@ int pop_init_kpp_bckgrnd(pop_ctx *c, const pop_kpp_bckgrnd_nml *nml) {
 
 // ---- ideal age (iage_mod.F90): tracer n (1-based, 3 .. nt) gets the module's interior source and surface reset, and starts from 0
 int pop_init_iage(pop_ctx *c, int n) {
-  if (!c) return 1;
-  if (c->h.plan_only) { c->err = "pop_init_iage: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
+  if (init_arg(c, "pop_init_iage", nullptr, 0, nullptr, false)) return 1;
   if (n < 3 || n > c->h.nt) { c->err = "pop_init_iage: n is the 1-based number of a passive tracer, 3 .. nt = " + std::to_string(c->h.nt) + " (got " + std::to_string(n) + ")"; return 1; }
   if (c->h.iage[n - 1]) { c->err = "pop_init_iage: tracer " + std::to_string(n) + " is ideal age already (once per tracer)"; return 1; }
-  if (c->ran || c->nsteps_total > 0) { c->err = "pop_init_iage: a step or a phase has already run (call it right after pop_create)"; return 1; }
+  if (init_before_steps(c, "pop_init_iage")) return 1;
   if (!c->host_only) {   // init_iage with init_iage_option 'startup' (iage_mod.F90:176-180): 0 at every time level
     const size_t bytes = (size_t)c->g.n3 * c->g.nblocks * sizeof(double);
     for (int t = 0; t < 3; ++t) HIPCHK(c, hipMemsetAsync(c->TR[n - 1][t], 0, bytes, c->stream));
@@ -2587,12 +1976,9 @@ int pop_init_iage(pop_ctx *c, int n) {
 // ---- frazil ice formation (ice.F90)
 void pop_ice_nml_init(pop_ice_nml *nml) { if (nml) ice_nml_defaults(*nml); }
 int pop_init_ice(pop_ctx *c, const pop_ice_nml *nml) {
-  if (!c) return 1;
-  if (!nml || nml->struct_bytes != (int)sizeof(pop_ice_nml)) { c->err = "pop_init_ice: pop_ice_nml.struct_bytes is not sizeof(pop_ice_nml) of this library (" + std::to_string(sizeof(pop_ice_nml)) + ")"; return 1; }
-  if (c->h.plan_only) { c->err = "pop_init_ice: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
-  if (c->ice.inited) { c->err = "pop_init_ice: called a second time (once per context)"; return 1; }
+  if (init_arg(c, "pop_init_ice", "pop_ice_nml", sizeof(pop_ice_nml), nml ? &nml->struct_bytes : nullptr, c && c->ice.inited)) return 1;
   if (c->cpl.inited) { c->err = "pop_init_ice: after pop_init_coupled_forcing, which took its constants and branches from the ice set-up (call pop_init_ice first)"; return 1; }
-  if (c->ran || c->nsteps_total > 0) { c->err = "pop_init_ice: a step or a phase has already run (call it right after pop_create)"; return 1; }
+  if (init_before_steps(c, "pop_init_ice")) return 1;
   if (ice_nml_check(c->h, *nml, c->err)) return 1;
   pop_ctx::Ice I;
   if (!c->host_only) {
@@ -2658,11 +2044,8 @@ int pop_tfreez_host(pop_ctx *c, const double *S, double *TFRZ, long long count) 
 // ---- coupled surface forcing (forcing_coupled.F90; launch_forcing.hpp)
 void pop_coupled_nml_init(pop_coupled_nml *nml) { if (nml) coupled_nml_defaults(*nml); }
 int pop_init_coupled_forcing(pop_ctx *c, const pop_coupled_nml *nml) {
-  if (!c) return 1;
-  if (!nml || nml->struct_bytes != (int)sizeof(pop_coupled_nml)) { c->err = "pop_init_coupled_forcing: pop_coupled_nml.struct_bytes is not sizeof(pop_coupled_nml) of this library (" + std::to_string(sizeof(pop_coupled_nml)) + ")"; return 1; }
-  if (c->h.plan_only) { c->err = "pop_init_coupled_forcing: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
-  if (c->cpl.inited) { c->err = "pop_init_coupled_forcing: called a second time (once per context)"; return 1; }
-  if (c->ran || c->nsteps_total > 0) { c->err = "pop_init_coupled_forcing: a step or a phase has already run (call it right after pop_create, after pop_init_ice)"; return 1; }
+  if (init_arg(c, "pop_init_coupled_forcing", "pop_coupled_nml", sizeof(pop_coupled_nml), nml ? &nml->struct_bytes : nullptr, c && c->cpl.inited) ||
+      init_before_steps(c, "pop_init_coupled_forcing", "call it right after pop_create, after pop_init_ice")) return 1;
   CplState s;
   s.nml = *nml;
   if (coupled_nml_resolve(c->h, s.nml, c->err)) return 1;
@@ -2689,12 +2072,9 @@ int pop_init_coupled_forcing(pop_ctx *c, const pop_coupled_nml *nml) {
 }
 static int region_mask_keep(pop_ctx *c, const int *region_mask_global, const char *who);
 int pop_init_ms_balance(pop_ctx *c, const pop_ms_balance_nml *nml, const int *region_mask_global) {
-  if (!c) return 1;
-  if (!nml || nml->struct_bytes != (int)sizeof(pop_ms_balance_nml)) { c->err = "pop_init_ms_balance: pop_ms_balance_nml.struct_bytes is not sizeof(pop_ms_balance_nml) of this library (" + std::to_string(sizeof(pop_ms_balance_nml)) + ")"; return 1; }
-  if (c->h.plan_only) { c->err = "pop_init_ms_balance: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
-  if (c->msb.inited) { c->err = "pop_init_ms_balance: called a second time (once per context)"; return 1; }
+  if (init_arg(c, "pop_init_ms_balance", "pop_ms_balance_nml", sizeof(pop_ms_balance_nml), nml ? &nml->struct_bytes : nullptr, c && c->msb.inited)) return 1;
   if (c->cpl.inited) { c->err = "pop_init_ms_balance: after pop_init_coupled_forcing (call it before)"; return 1; }
-  if (c->ran || c->nsteps_total > 0) { c->err = "pop_init_ms_balance: a step or a phase has already run (call it right after pop_create)"; return 1; }
+  if (init_before_steps(c, "pop_init_ms_balance")) return 1;
   MsBalance M;
   const bool had_mask = !c->region_mask.empty();
   if (region_mask_keep(c, region_mask_global, "pop_init_ms_balance")) return 1;
@@ -3078,10 +2458,7 @@ int pop_grid_volumes(pop_ctx *c, double *area_t, double *volume_t, double *volum
 // ---- meridional overturning circulation (diags_on_lat_aux_grid.F90; host_lat_aux.cpp, kernels_moc.hpp, launch_moc.hpp)
 void pop_transports_nml_init(pop_transports_nml *nml) { if (nml) transports_nml_defaults(*nml); }
 int pop_init_transports(pop_ctx *c, const pop_transports_nml *nml, const int *region_mask_global) {
-  if (!c) return 1;
-  if (!nml || nml->struct_bytes != (int)sizeof(pop_transports_nml)) { c->err = "pop_init_transports: struct_bytes is not sizeof(pop_transports_nml)"; return 1; }
-  if (c->h.plan_only) { c->err = "pop_init_transports: the context has no fields (POP_CREATE_PLAN_ONLY)"; return 1; }
-  if (c->moc.aux.inited) { c->err = "pop_init_transports: called twice"; return 1; }
+  if (init_arg(c, "pop_init_transports", "pop_transports_nml", sizeof(pop_transports_nml), nml ? &nml->struct_bytes : nullptr, c && c->moc.aux.inited, "called twice")) return 1;
   if (c->ran) { c->err = "pop_init_transports: call it before the first step or phase"; return 1; }
   LatAux aux;
   const bool had_mask = !c->region_mask.empty();

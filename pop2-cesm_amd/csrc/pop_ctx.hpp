@@ -1,5 +1,6 @@
-// pop_ctx.hpp -- the context of one model instance and the small helpers every launch file uses.
-// Part of the single translation unit pop_amd.hip (included after the kernel headers).
+// pop_ctx.hpp -- the context of one model instance and the small helpers every launch file uses: the ownership helpers
+// (device memory, events, streams, pinned host memory: each recorded in the context where it is made), launch shapes and
+// step parameters.  Part of the single translation unit pop_amd.hip (included after the kernel headers).
 #pragma once
 
 #define HIPCHK(ctx, call)                                                                       \
@@ -118,7 +119,12 @@ struct pop_ctx {
   DevGrid g{};
   std::map<std::string, double *> d2;     // device 2-D fields (local blocks)
   std::map<std::string, int *> di2;
+  // what the context owns, recorded where it is made (dev_alloc, new_event, new_stream, pinned_alloc) and released by pop_destroy:
+  // device memory, events, streams other than the launch stream, pinned host memory
   std::vector<void *> allocs;
+  std::vector<hipEvent_t> events;
+  std::vector<hipStream_t> streams;
+  std::vector<void *> pinned;
   // prognostic state, physical slots; logical levels via oldt/curt/newt
   double *TR[MAXNT][3] = {}, *U[3] = {}, *V[3] = {}, *RHO[3] = {};
   double *PS[3] = {}, *GX[3] = {}, *GY[3] = {}, *UB[3] = {}, *VB[3] = {};
@@ -281,23 +287,23 @@ int dev_upload(pop_ctx *c, T **p, const T *src, size_t n) {
   HIPCHK(c, hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
   return 0;
 }
-// extract the local blocks of an all-blocks host field
+// an event, a non-blocking stream, pinned host memory: made here, released by pop_destroy (lazily made ones included)
+int new_event(pop_ctx *c, hipEvent_t *e, unsigned flags = hipEventDisableTiming) {
+  HIPCHK(c, hipEventCreateWithFlags(e, flags));
+  c->events.push_back(*e);
+  return 0;
+}
+int new_stream(pop_ctx *c, hipStream_t *s) {
+  HIPCHK(c, hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+  c->streams.push_back(*s);
+  return 0;
+}
 template <class T>
-std::vector<T> local_part(const HostModel &h, const std::vector<T> &all) {
-  std::vector<T> out(h.n2 * h.nblocks);
-  for (int lb = 0; lb < h.nblocks; ++lb)
-    std::copy(all.begin() + (size_t)(h.local_ids[lb] - 1) * h.n2, all.begin() + (size_t)h.local_ids[lb] * h.n2, out.begin() + (size_t)lb * h.n2);
-  return out;
+int pinned_alloc(pop_ctx *c, T **p, size_t n) {
+  HIPCHK(c, hipHostMalloc((void **)p, n * sizeof(T)));
+  c->pinned.push_back(*p);
+  return 0;
 }
-
-// the same for an all-blocks 3-D host field (nxb, nyb, km, nblocks_tot)
-std::vector<double> local_part3(const HostModel &h, const std::vector<double> &all) {
-  std::vector<double> out(h.n3 * h.nblocks);
-  for (int lb = 0; lb < h.nblocks; ++lb)
-    std::copy(all.begin() + (size_t)(h.local_ids[lb] - 1) * h.n3, all.begin() + (size_t)h.local_ids[lb] * h.n3, out.begin() + (size_t)lb * h.n3);
-  return out;
-}
-
 // column kernels: one wave per workgroup; tile order per kernels_common.hpp col_setup
 dim3 grid_cols(const pop_ctx *c) { return dim3(col_grid(c->g, POP_COL_THREADS), c->g.nblocks); }
 dim3 block_stencil() { return dim3(POP_COL_THREADS, 1); }

@@ -5,7 +5,9 @@
 // (source/prognostic.F90:47-66) -- so one wavefront reads 64 consecutive i of one level
 // (512 B, fully coalesced) and a thread owns a water column and marches k in registers.
 #pragma once
+#include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -126,6 +128,41 @@ struct HostModel {
 };
 
 int host_build(HostModel &h);            // host_setup.cpp
+// the caller's pop_config read in the layout of its struct_version into `out`, and every refusal rule of pop_create (host_setup.cpp)
+int config_read_check(const pop_config *in, const pop_grid_input *grid, pop_config &out, std::string &err);
+// the local blocks of an all-blocks host field: 2-D, and 3-D (nxb, nyb, km, nblocks_tot)
+template <class T>
+std::vector<T> local_part(const HostModel &h, const std::vector<T> &all) {
+  std::vector<T> out(h.n2 * h.nblocks);
+  for (int lb = 0; lb < h.nblocks; ++lb)
+    std::copy(all.begin() + (size_t)(h.local_ids[lb] - 1) * h.n2, all.begin() + (size_t)h.local_ids[lb] * h.n2, out.begin() + (size_t)lb * h.n2);
+  return out;
+}
+inline std::vector<double> local_part3(const HostModel &h, const std::vector<double> &all) {
+  std::vector<double> out(h.n3 * h.nblocks);
+  for (int lb = 0; lb < h.nblocks; ++lb)
+    std::copy(all.begin() + (size_t)(h.local_ids[lb] - 1) * h.n3, all.begin() + (size_t)h.local_ids[lb] * h.n3, out.begin() + (size_t)lb * h.n3);
+  return out;
+}
+// ---- the lists and rewritten tables context creation uploads, as pure functions of the host model (host_tables.cpp).  The
+// solver's summation order and the XCD placement follow the order of these lists
+std::vector<int> land_prefix(const HostModel &h, double &land_fraction);   // DevGrid::opre, (n2 + 1) per local block; the share of 64-cell row tiles without work
+struct ChunkLists { std::vector<int> list, cnt; int nact = 0, active_total = 0; };   // nact = 0: no list, every chunk is visited
+ChunkLists solver_chunk_lists(const HostModel &h, const std::vector<int> &pre);      // red_act / red_cnt of the fused solver kernels
+struct PeerLists { std::vector<int> ss, st, sc, rd, rt, rc; };     // all peers concatenated: cell, start and length of its message (send, receive)
+PeerLists peer_lists(const HaloPlan &p);
+struct PeerCellMaps { std::vector<int> smap, off, slot, rmap; };   // per cell: its send entries (smap -> off -> slot) and its receive slot
+PeerCellMaps peer_cell_maps(const PeerLists &L, size_t ncells);
+bool halo_ns_only(const HostModel &h);                             // every block's east neighbour is on the block's own rank (j-band shards)
+struct EvpTables {                                                 // local sub-blocks, coefficient arrays transposed to [cell][sub-block]
+  size_t S = 0;
+  std::vector<int> meta;                                           // four words per sub-block: first cell, nx | ny << 8, land, land without interior ocean
+  std::vector<double> cc, ne, icc, ine, rinv;
+};
+EvpTables evp_tables(const HostModel &h);
+std::vector<double> btrop_wgt_ring(const HostModel &h, int wgt);   // btropWgtNE (1) / East (2) / North (3) of all blocks with the first row and column filled
+int mask_bytes(const std::vector<double> &m, std::vector<unsigned char> &m8);   // a 0/1 field as bytes; 1 when a value is neither
+std::vector<double> pcsi_omega(const HostModel &h, double &csy);   // omega_k of P-CSI, k = 0 .. max_iterations
 // ---- Jayne tidal mixing, init-time fields on the local blocks (host_tidal.cpp; tidal_mixing.F90)
 struct TidalFields {
   std::vector<double> flux, coef;          // TIDAL_ENERGY_FLUX_2D [g/s^3], TIDAL_COEF_3D (nxb,nyb,km,nblocks)
